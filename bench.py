@@ -10,7 +10,10 @@ covariance / eigen / loss -> backward -> Adam step on the whole global cloud; th
 sequence (configs[3] shape: weak scaling, sequences are independent) and the ranks exchange
 one RCCL all-reduce of [sum loss, dL/dw] per step.
 
-Prints ONE JSON line (contract in the task statement).  `roofline` describes the dominant kernel with
+Prints ONE JSON line (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+warm-up, the K timed steps (`value`, `ms_per_step`), the outputs of the last step if --dump-outputs DIR is given, the line.
+Everything else below -- the set-up breakdown, the k-NN build, `roofline`, the side measurements under `config` and
+`cpu_baseline` -- runs only with --full (otherwise those fields are absent or null).  `roofline` describes the dominant kernel with
 MEASURED quantities: its duration (HIP events stamped with the dispatch's own start / end inside the timed
 region), its HBM traffic and VALU instruction count from the rocprofv3 PMC passes committed under profiles/
 (looked up by the exact kernel instantiation this run launched; null when no profile of that kernel exists)
@@ -21,6 +24,7 @@ gather as an HBM access although Morton order + LDS staging serve them on chip -
 reference algorithm) timed on this host's cores on the same C2 workload.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -48,11 +52,17 @@ def parse():
     ap.add_argument('--c4-sequences', type=int, default=0, help='--workload c4: sequences (default: one per rank)')
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: set-up breakdown, k-NN build, per-kernel stamps and roofline, side '
+                         'measurements (sustained / cold / fp64 / multi-sequence / other forms / pose mode / train() / C1 / online), '
+                         'the all-reduce alone and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64)')
     ap.add_argument('--scans', type=int, default=10)
     ap.add_argument('--points', type=int, default=200_000, help='points per scan')
     ap.add_argument('--k', type=int, default=10)
     ap.add_argument('--dtype', default='float32', choices=['float32', 'float64'])
-    ap.add_argument('--cpu-scans', type=int, default=10, help='scans in the CPU baseline (10 = the full C2 workload; 0 = skip)')
+    ap.add_argument('--cpu-scans', type=int, default=10, help='with --full: scans in the CPU baseline (10 = the full C2 workload; 0 = skip)')
     ap.add_argument('--cpu-iters', type=int, default=5, help='timed iterations of the fp64 all-cores CPU baseline (BASELINE.md 3: >= 5 after one warm-up)')
     ap.add_argument('--cpu-variants', type=int, default=1, help='also time the fp32 and the 8-thread variants (BASELINE.md 3)')
     ap.add_argument('--no-sort', action='store_true', help='keep the scan-major point order (ablation)')
@@ -64,7 +74,7 @@ def parse():
     ap.add_argument('--graph', action='store_true',
                     help='with --autograd: capture the whole iteration (loss, backward, Adam) into one hipGraph and replay it')
     ap.add_argument('--timer-every', type=int, default=8,
-                    help='HIP-event timing of every N-th launch of the hot kernels inside the timed region (0 = off)')
+                    help='with --full: HIP-event timing of every N-th launch of the hot kernels inside the timed region (0 = off)')
     ap.add_argument('--bwd-layout', default='runs', choices=['runs', 'slots'], help='backward block-table layout (ablation)')
     ap.add_argument('--fwd-generic', action='store_true', help='run-time slot loop in the forward kernel (ablation)')
     ap.add_argument('--no-block-tables', action='store_true', help='gather from global memory instead of LDS (ablation)')
@@ -78,7 +88,7 @@ def parse():
                     help='native loop: the ordinary two launches per step (evaluation, reduction + Adam) instead of chained steps '
                          '(one launch per step: each launch also finishes the previous step; dc_sequence_step_chained)')
     ap.add_argument('--two-pass', action='store_true', help='basis form with separate forward and backward kernels (ablation)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the C1 / online-correction side measurements')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the side measurements under config')
     ap.add_argument('--multi-sequences', type=int, default=4, help='extras: sequences of the same shape stepped together on one GPU (0 / 1: skip)')
     ap.add_argument('--step-var', type=int, default=None, help='dc_set_option(6, v): form of the one-pass step kernel (A-B measurements)')
     return ap.parse_args()
@@ -230,6 +240,15 @@ def profile_key(kernel, n):
     return '%s/N%d' % (kernel.replace('kStepVar', '7'), n)
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, one float64 DIR/<name>.npy per array (a few
+    dozen bytes in all: the inputs are seeded, so two builds run with the same arguments can be compared file by file)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().to('cpu', torch.float64).numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -306,11 +325,12 @@ def main():
     plan, info = build()
     torch.cuda.synchronize()
     setup_first_s = time.perf_counter() - t0
-    del plan, info
-    t0 = time.perf_counter()
-    plan, info = build(stage_times=True)
-    torch.cuda.synchronize()
-    setup_ms = (time.perf_counter() - t0) * 1e3
+    if args.full:
+        del plan, info
+        t0 = time.perf_counter()
+        plan, info = build(stage_times=True)
+        torch.cuda.synchronize()
+        setup_ms = (time.perf_counter() - t0) * 1e3
     from depth_correction_amd import _native as nv
     if args.fwd_generic:
         nv.check(nv.lib().dc_set_option(1, 1), 'dc_set_option')
@@ -321,17 +341,18 @@ def main():
     # the k-NN build alone, on the global cloud (reported separately)
     # (one untimed call first: the variant without distances is not the one the set-up ran, and a code object's first launch pages
     # it in -- 11 ms in the round-4 driver line against 1.7 ms for the kernels; then the median of five)
-    ops.knn(info['points0'], args.k, want_dist=False)
-    torch.cuda.synchronize()
-    knn_all = []
-    for _ in range(5):
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    if args.full:
         ops.knn(info['points0'], args.k, want_dist=False)
-        ev1.record()
         torch.cuda.synchronize()
-        knn_all.append(ev0.elapsed_time(ev1))
-    knn_ms = float(np.median(knn_all))
+        knn_all = []
+        for _ in range(5):
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            ops.knn(info['points0'], args.k, want_dist=False)
+            ev1.record()
+            torch.cuda.synchronize()
+            knn_all.append(ev0.elapsed_time(ev1))
+        knn_ms = float(np.median(knn_all))
 
     n_local = plan.n
     from depth_correction_amd.plan import SequenceTrainer, KernelTimer
@@ -421,7 +442,9 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    with KernelTimer(every=args.timer_every) as timer:
+    # (--full: the library stamps every N-th hot-kernel launch of the timed region for the roofline block; a plain run times
+    # the steps alone)
+    with (KernelTimer(every=args.timer_every) if args.full else contextlib.nullcontext()) as timer:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             loss = step()
@@ -431,16 +454,23 @@ def main():
         if dist is not None:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        kernel_ms = timer.read()
-        kernel_names = timer.kernels()
+        kernel_ms = timer.read() if args.full else {}
+        kernel_names = timer.kernels() if args.full else {}
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     loss = loss.detach().cpu()
     final_loss = float(loss) if loss.numel() == 1 else float(loss[0] / loss[1])
+    if args.dump_outputs and rank == 0:
+        # the last timed step as its caller sees it: the mean loss and dL/dw of its evaluation, the weights after its Adam
+        # update (native loop: the step returns the sums [sum loss, count, dL/dw]; drop-in loop: the loss, w.grad, w)
+        if loss.numel() == 1:
+            dump_outputs(args.dump_outputs, {'loss': loss.reshape(1), 'grad_w': w.grad.reshape(-1), 'w': w.reshape(-1)})
+        else:
+            dump_outputs(args.dump_outputs, {'loss': loss[:1] / loss[1], 'grad_w': loss[2:] / loss[1], 'w': trainer.w})
     rccl = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the path's only exchange, measured by itself right after the timed region (all ranks take part): the packed fp64
         # vector [sum loss, count, dL/dw] every step all-reduces, 100 back-to-back calls between two events
         buf = torch.zeros((2 + len(w0),), dtype=torch.float64, device=dev)
@@ -459,8 +489,9 @@ def main():
     # ---- side measurements, after the timed region (the GPU goes idle between their host-synchronised calls; run before
     # the loop they left it at idle clocks for the first timed steps)
     extras = {}
+    extras_on = args.full and not args.no_extras
     sustained_kernel_ms = sustained_kernel_names = None
-    if world == 1 and not args.autograd and not args.no_extras:
+    if world == 1 and not args.autograd and extras_on:
         # the same chained step (a) sustained -- 2 000 steps back to back, what a training run of the reference's default length
         # and longer sees -- and (b) cold -- the first `steps` steps after the device has sat idle for a second (clocks down, no
         # device warm-up: what `--device-warmup-ms 0` times).  Their own trainer: the timed run's state is left alone.
@@ -494,7 +525,7 @@ def main():
         extras['cold_ms_per_step'] = (time.perf_counter() - t0) / args.steps * 1e3
         extras['cold_note'] = '%d chained steps + flush started after one second of an idle device, no device warm-up' % args.steps
         del tr2
-    if world == 1 and not args.autograd and not args.no_extras and args.dtype == 'float32' and args.scans * args.points <= 4_000_000:
+    if world == 1 and not args.autograd and extras_on and args.dtype == 'float32' and args.scans * args.points <= 4_000_000:
         # the reference's DEFAULT float_type is float64 (config.py:179): the same sequence with float64 clouds (fp64 points and
         # basis rows, consistency_step_basis_kernel<double, ...>), 200 chained steps
         scans64 = [s_.astype(np.float64) for s_ in scans_xyz]
@@ -521,7 +552,7 @@ def main():
                                      'what': 'float64 clouds (the reference default float_type): fp64 points and first sweep, 48-byte staged rows {x fp64 | u, c float32} for the second'}
         del tr64, plan64, info64, scans64
         torch.cuda.empty_cache()
-    if world == 1 and not args.autograd and not args.no_extras and args.multi_sequences > 1 and args.scans * args.points <= 4_000_000:
+    if world == 1 and not args.autograd and extras_on and args.multi_sequences > 1 and args.scans * args.points <= 4_000_000:
         # (d) S sequences of the same shape on ONE GPU, stepped together as train() does for several train_names (train.py:172-175;
         # eval.py:85-112 pools their sums): S x 118 MB of rows and tables no longer fit the 256 MiB Infinity Cache, so every launch
         # fetches its working set from HBM -- the number the single-sequence line cannot give
@@ -568,7 +599,7 @@ def main():
                     'set exceeds the 256 MiB Infinity Cache, unlike the single-sequence step' % (S, args.scans, args.points // 1000)}
         del trm, mplans, mposes
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_extras:        # single-process runs only: the other ranks must not wait for rank 0
+    if world == 1 and extras_on:        # single-process runs only: the other ranks must not wait for rank 0
         # the same step without the loop-invariant hoisting (general path: dc_points_fwd + forward + backward every iteration,
         # what the reference's own loop recomputes) and with separate forward / backward kernels, for comparison
         if not args.autograd and not args.no_basis and not args.two_pass:
@@ -616,7 +647,6 @@ def main():
         # the reference-API loop itself: train() (train.py:220-322) with its default callbacks on this very workload, wall clock
         # per iteration from two runs of different length (set-up cancels); see tools/train_bench.py for the C4 shape
         if args.scans * args.points <= 4_000_000:
-            import contextlib
             import io
             import tempfile
             from depth_correction_amd.config import Config as _Cfg
@@ -823,13 +853,16 @@ def main():
                        'skipped_note': 'share of the 64-centre wavefronts whose centres are ALL outside the loss mask: they stage their rows '
                                        'and skip the moments, the eigen-solve and the second sweep (every term they would add carries the mask); '
                                        'the plan forms wavefronts of one kind (64 Morton-consecutive points inside, or outside, the mask)', 'spatial_sort': not args.no_sort, 'final_loss': final_loss,
-                       'knn_build_ms': knn_ms, 'knn_points_per_s': n_local / (knn_ms * 1e-3),
-                       'setup_ms': setup_ms, 'setup_stages_ms': info['setup_ms'], 'setup_first_call_s': setup_first_s, 'device_init_s': device_init_s, 'library_load_s': library_load_s,
-                       'setup_note': 'setup_ms: the whole set-up phase (upload, 10 local feature clouds, global k-NN, masks, Morton '
-                                     'order, transpose, block tables) rebuilt in a warm process; setup_first_call_s additionally '
-                                     'holds the one-time code-object load and allocator warm-up'},
+                       'setup_first_call_s': setup_first_s, 'device_init_s': device_init_s, 'library_load_s': library_load_s},
             'roofline': roofline,
         }
+        if args.full:
+            out['config'].update({
+                'knn_build_ms': knn_ms, 'knn_points_per_s': n_local / (knn_ms * 1e-3),
+                'setup_ms': setup_ms, 'setup_stages_ms': info['setup_ms'],
+                'setup_note': 'setup_ms: the whole set-up phase (upload, 10 local feature clouds, global k-NN, masks, Morton '
+                              'order, transpose, block tables) rebuilt in a warm process; setup_first_call_s additionally '
+                              'holds the one-time code-object load and allocator warm-up'})
         if ramp:
             out['config']['device_warmup'] = {
                 'evaluations': 25 * len(ramp), 'ms': sum(ramp) * 25 / 1e3,
@@ -841,7 +874,7 @@ def main():
             out['config'].update(rccl)
             out['rccl_ranks'] = rccl['rccl_ranks']
             out['allreduce_us_per_step'] = rccl['allreduce_us_per_step']
-        if world == 1 and args.cpu_scans > 0:
+        if world == 1 and args.full and args.cpu_scans > 0:
             torch.cuda.empty_cache()
             out['cpu_baseline'] = cpu_baseline(scans_xyz[:args.cpu_scans], poses[:args.cpu_scans], args.k,
                                                args.cpu_iters, 1e-3, args.cpu_variants)
@@ -892,11 +925,17 @@ def main_c4(args, world, rank, local_rank, dev, dist):
                 clock['t0'] = time.perf_counter()
 
     with contextlib.redirect_stdout(io.StringIO()):
-        train(cfg, callbacks=Clock(cfg), train_datasets=seqs, val_datasets=[])
+        best = train(cfg, callbacks=Clock(cfg), train_datasets=seqs, val_datasets=[])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - clock['t0']
+    if args.dump_outputs and rank == 0:
+        # what train() hands its caller: the config of the best iteration, whose model state and pose corrections it saved
+        state = torch.load(best.model_state_dict, map_location='cpu')
+        arrays = {'model_' + key: v.reshape(-1) for key, v in state.items() if torch.is_tensor(v) and v.is_floating_point()}
+        arrays['pose_deltas'] = torch.stack(torch.load(best.train_pose_deltas, map_location='cpu'))
+        dump_outputs(args.dump_outputs, arrays)
     stats = torch.tensor([elapsed, float(n_points)], dtype=torch.float64, device=dev)
     if dist is not None:
         el = stats[:1].clone()
@@ -905,7 +944,7 @@ def main_c4(args, world, rank, local_rank, dev, dist):
         dist.all_reduce(pts)
         elapsed, n_points = float(el.item()), float(pts.item())
     rccl = None
-    if dist is not None:
+    if dist is not None and args.full:
         buf = torch.zeros((2 + 2,), dtype=torch.float64, device=dev)
         for _ in range(10):
             dist.all_reduce(buf)

@@ -85,9 +85,13 @@ def _worker(rank, world, port, result):
 
 
 def test_two_ranks_equal_single_process():
+    threads = torch.get_num_threads()
     torch.set_num_threads(2)
-    single = _make_trainer([_Seq(q) for q in range(N_SEQ)], distributed=False)
-    ref = torch.stack([single.step().clone() for _ in range(N_STEPS)])
+    try:
+        single = _make_trainer([_Seq(q) for q in range(N_SEQ)], distributed=False)
+        ref = torch.stack([single.step().clone() for _ in range(N_STEPS)])
+    finally:
+        torch.set_num_threads(threads)          # (later tests in this process keep their threads)
     ctx = mp.get_context('spawn')
     result = ctx.Manager().dict()
     port = 29500 + os.getpid() % 2000

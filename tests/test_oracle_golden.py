@@ -168,6 +168,16 @@ def test_point_to_point(golden):
     np.testing.assert_allclose(npy(O.point_to_point(posed, found)), g['p2p_metric_nn'], rtol=1e-6)
 
 
+def _mkl_avx512_path():
+    """True on the CPUs whose MKL vector-math code path made the fixtures: Intel with AVX-512."""
+    try:
+        with open('/proc/cpuinfo') as f:
+            intel = 'GenuineIntel' in f.read()
+    except OSError:
+        return False
+    return intel and torch.backends.cpu.get_cpu_capability() == 'AVX512'
+
+
 @pytest.mark.parametrize('tag', ['f64', 'f32'])
 def test_shadow_filter(golden, tag):
     """filters.filter_shadow_points (filters.py:257-309) on the fixture's direction neighbourhoods."""
@@ -178,8 +188,15 @@ def test_shadow_filter(golden, tag):
                               [float(np.radians(float(g['bounds_deg']))), float('inf')])
     assert np.array_equal(npy(mask), g[tag + '_mask'])
     valid = g[tag + '_dir_neighbors'] >= 0
-    a = np.where(valid, npy(ang), 10.0)
-    np.testing.assert_allclose(a.min(-1), g[tag + '_angle_min'], rtol=0, atol=0)
+    a = np.where(valid, npy(ang), 10.0).min(-1)
+    # the angles come out of torch.acos, whose CPU kernel is MKL's vector math library: the fixture holds the bits of MKL's
+    # AVX-512 code path, which MKL takes on Intel CPUs only (elsewhere its AVX2 path rounds a few inputs the other way).  Same
+    # bits on such a CPU; on any other, one unit in the last place at most and for fewer than 1 % of the points
+    want = g[tag + '_angle_min']
+    np.testing.assert_array_max_ulp(a, want, maxulp=1)
+    assert np.count_nonzero(a != want) < 0.01 * a.size
+    if _mkl_avx512_path():
+        np.testing.assert_array_equal(a, want)
     # the direction neighbourhoods themselves: radius search on the unit directions (depth_cloud.py:217-224)
     r = float(torch.sqrt(2. * (1. - torch.cos(torch.as_tensor(float(g['angle']))))))
     ind = O.radius_ckdtree(g[tag + '_dirs'][:4000].astype(np.float64), r)

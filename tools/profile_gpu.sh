@@ -15,13 +15,13 @@ cd "$ROOT"
 # has a time limit, and seven runs of bench.py with its side measurements do not fit one
 PASSES=${PASSES:-kt 1 2 3 4 5}
 if [[ " $PASSES " == *" kt "* ]]; then
-python3 bench.py $BENCH_ARGS > "$OUT/bench_line.json" 2> "$OUT/raw/bench.err" || exit 1
+python3 bench.py --full $BENCH_ARGS > "$OUT/bench_line.json" 2> "$OUT/raw/bench.err" || exit 1
 echo "bench line done"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw/kt" -o p -- python3 bench.py $BENCH_ARGS > "$OUT/raw/kt.log" 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw/kt" -o p -- python3 bench.py --full $BENCH_ARGS > "$OUT/raw/kt.log" 2>&1 || exit 1
 cp "$(find "$OUT/raw/kt" -name 'p_kernel_stats.csv' | head -1)" "$OUT/kernel_stats.csv"
 echo "kernel trace done"
 fi
-PMC_ARGS="--steps 6 --warmup 2 --cpu-scans 0 ${PMC_EXTRA:-}"
+PMC_ARGS="--full --steps 6 --warmup 2 --cpu-scans 0 ${PMC_EXTRA:-}"
 i=0
 for counters in \
     "FETCH_SIZE" \
