@@ -129,6 +129,14 @@ _SIGNATURES = {
     'dc_shadow_mask': (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _f64, _f64, _f64, _vp, _vp]),
     'dc_correct_depth': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),
     'dc_shadow_filter': (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _f64, _f64, _f64, _vp, _vp, _sz, _vp]),
+    'dc_ransac_score': (_i32, [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dc_ransac_refit_partial_count': (_i32, [_i64]),
+    'dc_ransac_refit': (_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _i32, _vp, _vp, _vp]),
+    'dc_dbscan': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dc_plane_moments_fwd': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
+    'dc_plane_moments_bwd': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

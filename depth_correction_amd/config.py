@@ -74,6 +74,10 @@ class Config(object):
         self.nn_grid_res = 0.5
         self.min_valid_neighbors = 5
         self.max_neighborhoods = None
+        # plane neighbourhoods (NeighborhoodType.plane): RANSAC inlier distance, hypotheses per round, sample size
+        self.ransac_dist_thresh = 0.03
+        self.num_ransac_iters = 500
+        self.ransac_model_size = 3
         self.nn_scale = None
         # filters (:204-218)
         self.shadow_neighborhood_angle = 0.017453

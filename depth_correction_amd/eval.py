@@ -181,8 +181,10 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         return loss, views, poses_upd, views
 
     offsets = [offset_cloud(c, model) for c in clouds] if cfg.loss_offset else None
-    global_clouds = [global_cloud(clouds=c, model=model, poses=p) for c, p in zip(clouds, poses_upd)]
-    feat_clouds = [compute_neighborhood_features(cloud=cloud, neighborhoods=nn, cfg=cfg)
+    # plane neighbourhoods: the model is applied per plane with the plane normals (eval.py:90-96)
+    plane = cfg.nn_type == NeighborhoodType.plane
+    global_clouds = [global_cloud(clouds=c, model=None if plane else model, poses=p) for c, p in zip(clouds, poses_upd)]
+    feat_clouds = [compute_neighborhood_features(cloud=cloud, model=model if plane else None, neighborhoods=nn, cfg=cfg)
                    for cloud, nn in zip(global_clouds, ns)]
     if (not masks or masks[0] is None) and isinstance(feat_clouds[0], DepthCloud):
         masks = [global_cloud_mask(cloud, cloud.mask if hasattr(cloud, 'mask') else None, cfg) for cloud in feat_clouds]

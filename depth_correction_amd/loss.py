@@ -21,6 +21,7 @@ import torch
 from . import ops
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry
+from .segmentation import Planes
 from .utils import trace
 
 __all__ = ['batch_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'min_eigval_loss', 'point_to_plane_dist',
@@ -65,6 +66,7 @@ def _pointwise(raw_fun, cloud, mask, offset, sqrt, reduction, inlier_max_loss, i
                only_finite, skip_nans):
     """Shared tail of min_eigval_loss / trace_loss (loss.py:244-294, 324-370)."""
     assert offset is None or isinstance(offset, (DepthCloud, torch.Tensor))
+    # (plane neighbourhoods: every plane is one entry, loss.py:216-294 on Planes.eigvals / Planes.cov)
     if mask is not None:
         print('Using %.3f valid entries from input cloud.' % mask.float().mean())
         cloud, mask = cloud[mask], None
@@ -100,7 +102,7 @@ def min_eigval_loss(cloud, mask=None, offset=None, sqrt=False, normalization=Fal
         return batch_loss(min_eigval_loss, cloud, masks=mask, offsets=offset, sqrt=sqrt, normalization=normalization,
                           reduction=reduction, inlier_max_loss=inlier_max_loss, inlier_ratio=inlier_ratio,
                           inlier_loss_mult=inlier_loss_mult, only_finite=only_finite, skip_nans=skip_nans)
-    assert isinstance(cloud, DepthCloud) and cloud.eigvals is not None
+    assert isinstance(cloud, (DepthCloud, Planes)) and cloud.eigvals is not None
 
     def raw(c):
         lam = c.eigvals
@@ -116,7 +118,7 @@ def trace_loss(cloud, mask=None, offset=None, sqrt=None, reduction=Reduction.MEA
         return batch_loss(trace_loss, cloud, masks=mask, offsets=offset, sqrt=sqrt, reduction=reduction,
                           inlier_max_loss=inlier_max_loss, inlier_ratio=inlier_ratio, inlier_loss_mult=inlier_loss_mult,
                           only_finite=only_finite, skip_nans=skip_nans)
-    assert isinstance(cloud, DepthCloud) and cloud.cov is not None
+    assert isinstance(cloud, (DepthCloud, Planes)) and cloud.cov is not None
     return _pointwise(lambda c: trace(c.cov), cloud, mask, offset, sqrt, reduction, inlier_max_loss, inlier_ratio,
                       inlier_loss_mult, only_finite, skip_nans)
 

@@ -1,6 +1,6 @@
 """Per-iteration glue with the reference's signatures (preproc.py:25-243): filtered / local feature clouds, the
-global cloud, neighbourhood establishment, per-iteration features and the global mask -- for ball neighbourhoods
-(NeighborhoodType.plane needs RANSAC plane segmentation from PCL / open3d and is out of scope).
+global cloud, neighbourhood establishment, per-iteration features and the global mask -- for ball neighbourhoods and for
+plane neighbourhoods (NeighborhoodType.plane: GPU RANSAC + DBSCAN segmentation and per-plane moments, segmentation.py).
 """
 from __future__ import annotations
 
@@ -18,8 +18,8 @@ __all__ = ['compute_neighborhood_features', 'establish_neighborhoods', 'filtered
 
 
 def _ball_only(cfg):
-    if cfg.nn_type != NeighborhoodType.ball:
-        raise NotImplementedError('only ball neighbourhoods are implemented (plane neighbourhoods need PCL / open3d)')
+    if cfg.nn_type not in (NeighborhoodType.ball, NeighborhoodType.plane):
+        raise NotImplementedError('only ball and plane neighbourhoods are implemented, got %s' % (cfg.nn_type,))
 
 
 def filtered_cloud(cloud, cfg: Config):
@@ -172,6 +172,14 @@ def establish_neighborhoods(dataset=None, clouds=None, poses=None, cloud=None, c
     _ball_only(cfg)
     if cloud is None:
         cloud = global_cloud(clouds=clouds, poses=poses, dataset=dataset)
+    if cfg.nn_type == NeighborhoodType.plane:        # preproc.py:186-191
+        from .segmentation import Planes
+        if not cloud.dirs.is_cuda:
+            raise RuntimeError('plane neighbourhoods need a GPU: the cloud is on %s (depth_correction_amd has no CPU path)'
+                               % cloud.dirs.device)
+        return Planes.fit(cloud.to_points().detach(), cfg.ransac_dist_thresh, min_support=cfg.min_valid_neighbors,
+                          max_iterations=cfg.num_ransac_iters, max_models=cfg.max_neighborhoods,
+                          eps=2.0 * np.sqrt(3) * cfg.grid_res, seed=cfg.random_seed)
     cloud.update_all(k=cfg.nn_k, r=cfg.nn_r, scale=cfg.nn_scale, keep_neighbors=False)
     return cloud.neighbors, cloud.weights
 
@@ -182,8 +190,36 @@ def compute_neighborhood_features(dataset=None, clouds=None, poses=None, model=N
     _ball_only(cfg)
     if neighborhoods is None:
         neighborhoods = establish_neighborhoods(dataset=dataset, cloud=cloud, cfg=cfg)
+    plane = cfg.nn_type == NeighborhoodType.plane
     if cloud is None:
-        cloud = global_cloud(clouds=clouds, model=model, poses=poses, pose_corrections=pose_corrections, dataset=dataset)
+        # plane neighbourhoods: the model is applied with the plane normals below (preproc.py:205-210)
+        cloud = global_cloud(clouds=clouds, model=None if plane else model, poses=poses, pose_corrections=pose_corrections,
+                             dataset=dataset)
+    if plane:
+        return _plane_features(cloud, neighborhoods, model)
     cloud.neighbors, cloud.weights = neighborhoods
     cloud.update_all(scale=cfg.nn_scale, keep_neighbors=True)
     return cloud
+
+
+def _plane_features(cloud, planes, model):
+    """Per-plane covariances and eigenvalues of the global cloud (preproc.py:218-243): the incidence angles against the plane
+    normal, the model and the moments in one kernel (dc_plane_moments_fwd), eigh on the [P,3,3] result."""
+    from .segmentation import plane_moments
+    out = planes.copy()
+    cov = plane_moments(cloud, planes, model)
+    out.cov = cov
+    out.eigvals = torch.linalg.eigh(cov)[0]
+
+    def plane_clouds():
+        clouds = []
+        with torch.no_grad():
+            for i in range(len(planes)):
+                c = cloud[planes.indices[i].to(cloud.dirs.device)]
+                c.mask = None
+                c.normals = planes.params[i:i + 1, :-1].to(device=c.dirs.device, dtype=c.dirs.dtype).expand((len(c), -1))
+                c.update_incidence_angles()
+                clouds.append(model(c) if model is not None else c)
+        return clouds
+    out._plane_cloud_fn = plane_clouds
+    return out

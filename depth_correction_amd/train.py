@@ -22,6 +22,7 @@ import torch
 
 from .config import Config, NeighborhoodType, PoseCorrection
 from .dataset import create_dataset
+from .depth_cloud import DepthCloud
 from .distributed import GradReducer, gather_objects, shard_sequences, world_info
 from .eval import eval_loss_clouds, initialize_pose_corrections
 from .loss import create_loss, icp_correspondences
@@ -90,8 +91,11 @@ def _load_sequences(datasets, cfg):
         for cloud, pose in ds:
             raw.append(cloud)
             poses.append(pose)
+        if cfg.nn_type == NeighborhoodType.plane:
+            # plane neighbourhoods: the clouds as they are, no local features (train.py:98-101)
+            clouds = [DepthCloud.from_structured_array(c, dtype=cfg.numpy_float_type(), device=cfg.device) for c in raw]
         # independent scans that do not fill the chip one at a time: a few streams side by side (pipeline.on_streams)
-        if torch.device(cfg.device).type == 'cuda':
+        elif torch.device(cfg.device).type == 'cuda':
             from .pipeline import on_streams
             clouds = on_streams([lambda c=c: local_feature_cloud(c, cfg) for c in raw], cfg.device)
         else:
@@ -170,9 +174,12 @@ def train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
 
 
 def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
-    assert cfg.nn_type == NeighborhoodType.ball
+    assert cfg.nn_type in (NeighborhoodType.ball, NeighborhoodType.plane)
     callbacks = callbacks or TrainCallbacks(cfg)
     rank, world, sharded = _sharding(cfg)
+    plane = cfg.nn_type == NeighborhoodType.plane
+    if plane and sharded:
+        raise NotImplementedError('plane neighbourhoods are not supported by the sharded (multi-rank) training loops')
     if sharded and torch.device(cfg.device).type == 'cuda' and torch.device(cfg.device).index is not None:
         # object collectives (the checkpoint gather) and RCCL's own staging use torch's current device: it must be this
         # rank's GPU, whatever the launcher did.  An index-less 'cuda' means "the current device" (the launcher has already
@@ -238,6 +245,8 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
     if cfg.loss == 'icp_loss':
         ratio = cfg.loss_kwargs['icp_inlier_ratio']
         train_masks, val_masks = _icp_masks(train_clouds, train_poses, ratio), _icp_masks(val_clouds, val_poses, ratio)
+    elif plane:                                       # no global mask with plane neighbourhoods (eval.py:104-106)
+        train_masks, val_masks = len(train_global) * [None], len(val_global) * [None]
     else:
         train_masks = [global_cloud_mask(c, c.mask, cfg) for c in train_global]
         val_masks = [global_cloud_mask(c, c.mask, cfg) for c in val_global]
@@ -254,7 +263,7 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
         return loss * weight if loss is not None else torch.zeros((), dtype=torch.float64, device=cfg.device)
 
     batch = int(getattr(cfg, 'loop_batch', 64) or 1)
-    if (batch > 1 and _only_watches_the_clock(callbacks) and torch.device(cfg.device).type == 'cuda' and cfg.n_opt_iters > 0):
+    if (batch > 1 and not plane and _only_watches_the_clock(callbacks) and torch.device(cfg.device).type == 'cuda' and cfg.n_opt_iters > 0):
         # nobody looks at an iteration while it runs: the loop runs without a host synchronisation per iteration -- see _batched_loop.
         # Sharded sequences (one process per GPU): the same loops with the iteration's ONE all-reduce enqueued on the stream between
         # the evaluations and the finishing launches; every rank must take the same loop, so they agree on it first

@@ -721,6 +721,43 @@ int dc_profiler_read(int kind, double* total_ms, int64_t* launches);
 /* Source-level name of the kernel instantiation the last launch of `kind` used (which variant the dispatch chose). */
 int dc_profiler_kernel(int kind, char* buf, int len);
 
+/* ---- plane neighbourhoods (depth_correction_amd/csrc/dc_planes.hip; the determinism spec is its header comment) ----
+ * One RANSAC round of fit_plane (PCL SACSegmentation, segmentation.py:127-140, called by the loop of segmentation.py:194-276):
+ * n_hyp (<= 1024) deterministic hypotheses from the int32 list `remaining` of row numbers of points [*,3] (dtype), each scored
+ * against every remaining point.  hyp double [n_hyp,4] (n, d), anchor double [n_hyp,3] (first sample), valid int32 [n_hyp],
+ * counts int32 [n_hyp] (-1: degenerate), best int32 [2] = (h, count) of the winner (largest count, lowest h). */
+int dc_ransac_score(const void* points, int dtype, const int32_t* remaining, int64_t n_rem, int64_t seed, int64_t round, int n_hyp,
+                    double thresh, double* hyp, double* anchor, int32_t* valid, int32_t* counts, int32_t* best, dcStream_t stream);
+/* Number of double[10] partial rows dc_ransac_refit needs for n_rem remaining points. */
+int dc_ransac_refit_partial_count(int64_t n_rem);
+/* set_optimize_coefficients(True) of the winner of dc_ransac_score (segmentation.py:132): least-squares plane of its inliers
+ * -> params double [4] (largest-magnitude normal component positive), then mask uint8 [n_rem] = the inliers of the refined plane. */
+int dc_ransac_refit(const void* points, int dtype, const int32_t* remaining, int64_t n_rem, const double* hyp, const double* anchor,
+                    const int32_t* best, double thresh, double* partials, int n_partials, double* params, uint8_t* mask,
+                    dcStream_t stream);
+/* cluster_dbscan of open3d with min_points = 10 (segmentation.py:166-177) on the radius table nbr int32 [m,k] (ascending, -1
+ * padded, the point itself included) of the support: core uint8 [m], lab int32 [m] (scratch), label_out int32 [m] (smallest
+ * member index of the cluster, -1 = noise), sizes int32 [m] (points per label), flag int32 [1] (scratch), best int32 [2] =
+ * (label, size) of the largest cluster (ties: smaller label; (-1, 0) without a cluster).  Synchronises `stream` once per
+ * union-find pass. */
+int dc_dbscan(const int32_t* nbr, int64_t m, int k, int min_pts, uint8_t* core, int32_t* lab, int32_t* label_out, int32_t* sizes,
+              int32_t* flag, int32_t* best, dcStream_t stream);
+/* Plane features of compute_neighborhood_features (preproc.py:218-243): for the points idx[plane_ptr[p] .. plane_ptr[p+1]) of
+ * vps / dirs [N,3], depth [N] (dtype), inc = arccos|dir . normals[p]|, d' = model(d, inc) (model_kind, w / e double [n_terms]),
+ * x = vp + d' dir -> cov double [P,3,3] (covs: Bessel, utils.py:109) and mean double [P,3].  Work split: block b covers
+ * plane blk_plane[b] from entry blk_begin[b] for up to `chunk` entries; the blocks of plane p are plane_blk[p] .. plane_blk[p+1].
+ * partials: double [n_blocks,9]. */
+int dc_plane_moments_fwd(const void* vps, const void* dirs, const void* depth, int dtype, const int32_t* idx, const int32_t* plane_ptr,
+                         const double* normals, int n_planes, const int32_t* blk_plane, const int32_t* blk_begin, const int32_t* plane_blk,
+                         int n_blocks, int chunk, int model_kind, int n_terms, const double* w, const double* e, double* partials,
+                         double* cov, double* mean, dcStream_t stream);
+/* Backward of dc_plane_moments_fwd for dL/dcov gcov double [P,3,3]: g_vps / g_dirs [N,3], g_depth [N] (dtype; rows outside every
+ * plane are left as they are, planes must not share points), g_w double [n_terms] (through wpartials double [n_blocks,n_terms]). */
+int dc_plane_moments_bwd(const void* vps, const void* dirs, const void* depth, int dtype, const int32_t* idx, const int32_t* plane_ptr,
+                         const double* normals, int n_planes, const int32_t* blk_plane, const int32_t* blk_begin, int n_blocks, int chunk,
+                         int model_kind, int n_terms, const double* w, const double* e, const double* mean, const double* gcov,
+                         void* g_vps, void* g_dirs, void* g_depth, double* wpartials, double* g_w, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
