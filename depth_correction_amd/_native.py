@@ -137,6 +137,12 @@ _SIGNATURES = {
                                     _vp, _vp, _vp]),
     'dc_plane_moments_bwd': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dc_sequence_landscape_workspace_count': (_i64, [_i64]),
+    'dc_sequence_landscape': (_i32, [_vp, _i32, _f64, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
+                                     _vp, _vp]),
+    'dc_plane_landscape_partials_count': (_i32, [_i32, _i32]),
+    'dc_plane_landscape': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                  _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
 }
 
 

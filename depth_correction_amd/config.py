@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['Config', 'Loss', 'Model', 'NeighborhoodType', 'PoseCorrection', 'nonempty']
+__all__ = ['Config', 'Loss', 'loss_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'nonempty']
 
 
 class _Names(type):
@@ -48,6 +48,17 @@ class PoseCorrection(metaclass=_Names):
 
 def nonempty(iterable):
     return [x for x in iterable if x]
+
+
+def loss_eval_csv(log_dir: str, loss: str, subset: str = None):
+    """CSV file eval_loss_all appends to for one loss and subset (config.py:96-103)."""
+    if subset:
+        path = 'loss_eval_{loss}_{subset}.csv'.format(loss=loss, subset=subset)
+    else:
+        path = 'loss_eval_{loss}.csv'.format(loss=loss)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
 
 
 class Config(object):
@@ -98,6 +109,9 @@ class Config(object):
         self.data_start = None
         self.data_stop = None
         self.data_step = 1
+        self.train_poses_path = []
+        self.val_poses_path = []
+        self.test_poses_path = []
         # training (:246-266)
         self.loss = Loss.min_eigval_loss
         self.loss_offset = False
@@ -115,6 +129,9 @@ class Config(object):
         self.train_pose_deltas = None
         self.test_pose_deltas = None
         self.log_filters = False
+        # evaluation (:275, :282): eval_loss appends its result to loss_eval_csv when set; eval_loss_all evaluates these losses
+        self.loss_eval_csv = None
+        self.eval_losses = list(Loss)
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_noise = 0.0           # dataset.noisy_dataset (config.py:242-244)

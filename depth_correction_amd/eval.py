@@ -5,20 +5,29 @@ cover (ball neighbourhoods on the GPU, min-eigenvalue or trace loss -- with or w
 offsets / distance weights, any of the reference's models or none) every sequence is evaluated by its cached
 ``SequencePlan`` -- one to three kernel launches -- and the returned loss carries the hand-derived backward to
 ``model.w`` / ``model.exponent`` / the pose corrections.  Any other configuration goes through the un-fused DepthCloud operators with identical results.
+
+``eval_loss`` / ``eval_loss_all`` are the reference's test-set evaluation (eval.py:115-211).  ``landscape_clouds`` evaluates
+the loss for many candidate weights of the model at once: every model with a basis form is affine in its weights, so a
+neighbourhood's covariance is a quadratic form in w and one pass over the neighbours (dc_sequence_landscape) serves every
+row; configurations outside that path loop over ``eval_loss_clouds`` ("Loss landscape").
 """
 from __future__ import annotations
 
+import copy
+from collections import Counter
+
+import numpy as np
 import torch
 
-from .config import Config, NeighborhoodType, PoseCorrection
+from .config import Config, NeighborhoodType, PoseCorrection, loss_eval_csv, nonempty
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry, SequencePlan, consistency_loss
 from .preproc import (compute_neighborhood_features, global_cloud, global_cloud_mask, local_feature_cloud,
                       offset_cloud)
 from .transform import corrected_poses, xyz_axis_angle_to_matrix
 
-__all__ = ['create_corrected_poses', 'eval_loss_clouds', 'initialize_pose_corrections', 'fused_supported',
-           'PlanCloud', 'LazyFeatureCloud']
+__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape',
+           'initialize_pose_corrections', 'fused_supported', 'landscape_clouds', 'landscape_paths', 'PlanCloud', 'LazyFeatureCloud']
 
 
 def initialize_pose_corrections(datasets, cfg: Config):
@@ -190,3 +199,275 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         masks = [global_cloud_mask(cloud, cloud.mask if hasattr(cloud, 'mask') else None, cfg) for cloud in feat_clouds]
     loss, loss_cloud = loss_fun(feat_clouds, mask=masks, offset=offsets)
     return loss, loss_cloud, poses_upd, feat_clouds
+
+
+def _load_test_sequences(cfg: Config, test_datasets):
+    """Local clouds and poses of every test sequence (eval.py:147-164): ball neighbourhoods get local feature clouds, plane
+    neighbourhoods plain DepthClouds (as train._load_sequences)."""
+    all_clouds, all_poses = [], []
+    for ds in test_datasets:
+        clouds, poses = [], []
+        for cloud, pose in ds:
+            if cfg.nn_type == NeighborhoodType.ball:
+                cloud = local_feature_cloud(cloud, cfg)
+            else:
+                cloud = DepthCloud.from_structured_array(cloud, dtype=cfg.numpy_float_type(), device=cfg.device)
+            clouds.append(cloud)
+            poses.append(pose)
+        all_clouds.append(clouds)
+        all_poses.append(torch.as_tensor(np.stack(poses).astype(dtype=cfg.numpy_float_type()), device=cfg.device))
+    return all_clouds, all_poses
+
+
+def _test_setup(cfg: Config, test_datasets, model):
+    from .dataset import create_dataset
+    from .model import load_model
+    if test_datasets:
+        test_names = [str(ds) for ds in test_datasets]
+        print('Using provided test datasets: %s.' % ', '.join(test_names))
+    else:
+        print('Creating test datasets from config: %s.' % ', '.join(cfg.test_names))
+        test_names = cfg.test_names
+        test_datasets = []
+        for i, name in enumerate(cfg.test_names):
+            # the synthetic datasets take no poses_path: passed only when the configuration names one
+            kwargs = {'poses_path': cfg.test_poses_path[i]} if cfg.test_poses_path and cfg.test_poses_path[i] else {}
+            test_datasets.append(create_dataset(name, cfg, **kwargs))
+    if model is None:
+        model = load_model(cfg=cfg, eval_mode=True)
+    return test_names, test_datasets, model
+
+
+def _test_pose_deltas(cfg: Config, test_datasets):
+    if cfg.test_poses_path and nonempty(cfg.test_poses_path):          # eval.py:166-170
+        assert cfg.pose_correction != PoseCorrection.none
+        return torch.load(cfg.test_pose_deltas, map_location=cfg.device)
+    return initialize_pose_corrections(test_datasets, cfg)
+
+
+def eval_loss(cfg: Config, test_datasets=None, test_ns=None, model=None, loss_fun=None, return_neighborhood=False):
+    """Loss on the test sequences (eval.py:115-191): datasets from ``cfg.test_names`` unless given, model from the
+    configuration unless given, neighbourhoods established unless ``test_ns`` is given; the global masks are recomputed for
+    the evaluated model.  Prints the loss, appends it to ``cfg.loss_eval_csv`` when set and returns it (with the
+    neighbourhoods when ``return_neighborhood``)."""
+    from .io import append
+    from .loss import create_loss
+    from .preproc import establish_neighborhoods
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    if loss_fun is None:
+        loss_fun = create_loss(cfg)
+    assert callable(loss_fun)
+    test_clouds, test_poses = _load_test_sequences(cfg, test_datasets)
+    test_masks = [None] * len(test_datasets)
+    test_pose_deltas = _test_pose_deltas(cfg, test_datasets)
+    if test_ns is None:
+        test_ns = [establish_neighborhoods(clouds=clouds, poses=poses, cfg=cfg) for clouds, poses in zip(test_clouds, test_poses)]
+    test_loss, _, _, _ = eval_loss_clouds(test_clouds, test_poses, test_pose_deltas, test_masks, test_ns, model, loss_fun, cfg)
+    print('Test loss on %s: %.9f' % (', '.join(test_names), test_loss.item()))
+    if cfg.loss_eval_csv:
+        append(cfg.loss_eval_csv, '%s %.9f\n' % (','.join(test_names), test_loss))
+        if len(test_names) > 1:
+            print('Test loss on %s written to %s.' % (', '.join(test_names), cfg.loss_eval_csv))
+    if return_neighborhood:
+        return test_loss, test_ns
+    return test_loss
+
+
+def eval_loss_all(cfg: Config):
+    """Every loss of ``cfg.eval_losses`` on the train, val and test subsets with ground-truth poses, one CSV file per loss and
+    subset (eval.py:194-211)."""
+    for names, suffix in zip([cfg.train_names, cfg.val_names, cfg.test_names], ['train', 'val', 'test']):
+        if not names:
+            continue
+        for loss in cfg.eval_losses:
+            eval_cfg = cfg.copy()
+            eval_cfg.test_names = names
+            eval_cfg.train_poses_path = []
+            eval_cfg.val_poses_path = []
+            eval_cfg.test_poses_path = []
+            eval_cfg.loss = loss
+            eval_cfg.loss_eval_csv = loss_eval_csv(cfg.log_dir, loss, suffix)
+            eval_loss(cfg=eval_cfg)
+
+
+# ---- loss landscape over the model weights --------------------------------------------------------------------------------
+landscape_paths = Counter()     # 'kernel' / 'loop': how many landscape_clouds calls took each path
+_MAX_EIG_BOUNDS = 8
+
+
+def _n_weights(model):
+    if model is None:
+        return 0
+    if getattr(model, 'kernel_kind', None) is not None:
+        return model.kernel_params()[0].numel()
+    return sum(p.numel() for p in model.parameters())
+
+
+def _weight_rows(weights, n_params, device):
+    """[W, P] fp64 device rows; a [W] vector is accepted when P == 1."""
+    w = torch.as_tensor(weights).detach().to(device=device, dtype=torch.float64)
+    if w.dim() == 1:
+        if n_params != 1:
+            raise ValueError('weights of shape %s for a model with %d weights: expected [W, %d]' % (tuple(w.shape), n_params, n_params))
+        w = w.reshape(-1, 1)
+    if w.dim() != 2 or w.shape[1] != n_params or n_params == 0:
+        raise ValueError('weights of shape %s for a model with %d weights: expected [W, %d]' % (tuple(w.shape), n_params, n_params))
+    return w.contiguous()
+
+
+def _model_with_weights(model, row):
+    """A copy of ``model`` whose kernel weights (or, for models without a kernel form, its parameters in order) are ``row``."""
+    m = copy.deepcopy(model)
+    with torch.no_grad():
+        if getattr(m, 'kernel_kind', None) == 'Linear':
+            params = [m.w0, m.w1, m.b]
+        elif getattr(m, 'kernel_kind', None) is not None:
+            params = [m.w]
+        else:
+            params = list(m.parameters())
+        off = 0
+        for p in params:
+            p.copy_(row[off:off + p.numel()].reshape(p.shape).to(device=p.device, dtype=p.dtype))
+            off += p.numel()
+    return m
+
+
+def _eig_bounds(cfg: Config):
+    """(eigenvalue, denominator or -1, lo, hi) of the eigenvalue and eigenvalue-ratio bounds of global_cloud_mask."""
+    lo_hi = lambda lo, hi: (float('-inf') if lo is None else float(lo), float('inf') if hi is None else float(hi))
+    out = [(int(b[0]), -1) + lo_hi(b[1], b[2]) for b in (cfg.eigenvalue_bounds or [])]
+    out += [(int(b[0]), int(b[1])) + lo_hi(b[2], b[3]) for b in (cfg.eigenvalue_ratio_bounds or [])]
+    return out
+
+
+def _landscape_supported(clouds, model, n_params, cfg: Config):
+    kw = cfg.loss_kwargs
+    return (fused_supported(clouds, model, cfg) and model is not None and getattr(model, 'kernel_kind', None) is not None
+            and n_params in (1, 2) and kw.get('inlier_ratio', 1.0) == 1.0 and kw.get('inlier_max_loss') is None
+            and not kw.get('only_finite') and not kw.get('skip_nans') and not cfg.vp_dispersion_to_depth2_bounds
+            and len(_eig_bounds(cfg)) <= _MAX_EIG_BOUNDS)
+
+
+def _static_mask(seq_clouds, poses, nn, cfg: Config):
+    """The part of global_cloud_mask that does not depend on the model: local masks, valid neighbours, direction and
+    viewpoint dispersion (eval.py:105-107 without the eigenvalue bounds, which the kernel applies per weight row)."""
+    cfg0 = cfg.copy()
+    cfg0.eigenvalue_bounds, cfg0.eigenvalue_ratio_bounds = [], []
+    g = compute_neighborhood_features(cloud=global_cloud(clouds=seq_clouds, model=None, poses=poses.detach()), neighborhoods=nn,
+                                      cfg=cfg0)
+    return global_cloud_mask(g, g.mask, cfg0)
+
+
+def _landscape_kernel(clouds, poses_upd, masks, ns, model, w, cfg: Config):
+    """(sums [W], counts [W]) of every sequence through SequencePlan.eval_landscape, or None when a plan has no basis form."""
+    _, e = model.kernel_params()
+    e = e.detach().reshape(-1).to(device=w.device, dtype=torch.float64).contiguous()
+    total = torch.zeros((w.shape[0],), dtype=torch.float64, device=w.device)
+    count = torch.zeros_like(total)
+    recompute = not masks or masks[0] is None
+    for i, (c, p, nn) in enumerate(zip(clouds, poses_upd, ns)):
+        m = _static_mask(c, p, nn, cfg) if recompute else masks[i]
+        plan = _plan_for(c, p, nn, m, model, cfg)
+        if not plan.supports_landscape(w.shape[1]):
+            return None
+        out = torch.empty((w.shape[0], 2), dtype=torch.float64, device=w.device)
+        plan.eval_landscape(w, e, plan.poses12(p), out, bounds=_eig_bounds(cfg) if recompute else ())
+        total += out[:, 0]
+        count += out[:, 1]
+    return total, count
+
+
+def _loop_count(views, cfg: Config):
+    """Entries behind the loop's mean: the fused views' counts, else the loss clouds' entries (loss.reduce keeps the finite /
+    non-NaN ones under only_finite / skip_nans); nan for the ICP loss, which is no mean over points."""
+    if cfg.loss == 'icp_loss':
+        return float('nan')
+    kw = cfg.loss_kwargs
+    total = 0.0
+    for v in views:
+        if isinstance(v, PlanCloud):
+            total += float(v.count)
+            continue
+        loss = getattr(v, 'loss', None)
+        if not isinstance(loss, torch.Tensor):
+            return float('nan')
+        loss = loss.reshape(-1)
+        total += float(torch.isfinite(loss).sum() if kw.get('only_finite') else
+                       (~torch.isnan(loss)).sum() if kw.get('skip_nans') else loss.numel())
+    return total
+
+
+def _plane_landscape_supported(clouds, model, n_params, cfg: Config):
+    from .segmentation import PLANE_LANDSCAPE_KINDS
+    kw = cfg.loss_kwargs
+    return (getattr(cfg, 'fused', True) and cfg.nn_type == NeighborhoodType.plane and cfg.loss in ('min_eigval_loss', 'trace_loss')
+            and not cfg.loss_offset and model is not None and getattr(model, 'kernel_kind', None) in PLANE_LANDSCAPE_KINDS
+            and n_params in (1, 2) and kw.get('inlier_ratio', 1.0) == 1.0 and kw.get('inlier_max_loss') is None
+            and not kw.get('only_finite') and not kw.get('skip_nans') and clouds[0][0].dirs.is_cuda)
+
+
+def _plane_landscape_kernel(clouds, poses_upd, masks, ns, model, w, cfg: Config):
+    """(sums [W], counts [W]) of every sequence through Planes.eval_landscape (the global cloud before the model, as
+    eval_loss_clouds builds it for plane neighbourhoods)."""
+    _, e = model.kernel_params()
+    kw = cfg.loss_kwargs
+    normalization = bool(kw.get('normalization', False)) and cfg.loss == 'min_eigval_loss'
+    total = torch.zeros((w.shape[0],), dtype=torch.float64, device=w.device)
+    count = torch.zeros_like(total)
+    for i, (c, p, planes) in enumerate(zip(clouds, poses_upd, ns)):
+        g = global_cloud(clouds=c, model=None, poses=p)
+        out = torch.empty((w.shape[0], 2), dtype=torch.float64, device=w.device)
+        planes.eval_landscape(g, model.kernel_kind, w, e, out, loss=cfg.loss, normalization=normalization, sqrt=bool(kw.get('sqrt')),
+                              mask=masks[i] if masks else None)
+        total += out[:, 0]
+        count += out[:, 1]
+    return total, count
+
+
+def landscape_clouds(clouds, poses, pose_deltas, masks, ns, model, weights, cfg: Config):
+    """Loss for every row of ``weights`` ([W, P], or [W] when P == 1; P = the model's kernel weights, exponents from the model)
+    -> (loss [W] fp64, count [W] fp64 of the points or planes behind each mean).  Entry j equals ``eval_loss_clouds`` under
+    no_grad for a copy of the model with weights[j], for given masks and for masks of None (the global mask recomputed per
+    row).  Ball neighbourhoods in a configuration of the fused path (min-eigenvalue or trace loss, no quantile gating, no
+    NaN policy, no vp_dispersion_to_depth2 bounds) and P in {1, 2} take one pass over the neighbourhoods
+    (dc_sequence_landscape); plane neighbourhoods with a Polynomial / ScaledPolynomial model of 1 or 2 weights and the same
+    losses one pass over the plane points (dc_plane_landscape); everything else loops over eval_loss_clouds.
+    ``landscape_paths`` counts the path taken."""
+    from .loss import create_loss
+    device = clouds[0][0].dirs.device
+    n_params = _n_weights(model)
+    w = _weight_rows(weights, n_params, device)
+    with torch.no_grad():
+        ball = _landscape_supported(clouds, model, n_params, cfg)
+        if ball or _plane_landscape_supported(clouds, model, n_params, cfg):
+            poses_upd = [p.detach() for p in create_corrected_poses(poses, pose_deltas, cfg)]
+            res = (_landscape_kernel if ball else _plane_landscape_kernel)(clouds, poses_upd, masks, ns, model, w, cfg)
+            if res is not None:
+                landscape_paths['kernel'] += 1
+                total, count = res
+                return total / count, count          # 0 / 0 = nan, like the mean over an empty mask
+        landscape_paths['loop'] += 1
+        loss_fun = create_loss(cfg)
+        losses, counts = [], []
+        for row in w:
+            m = _model_with_weights(model, row)
+            loss, views, _, _ = eval_loss_clouds(clouds, poses, pose_deltas, list(masks) if masks else masks, ns, m, loss_fun, cfg)
+            losses.append(torch.as_tensor(loss, dtype=torch.float64, device=device).reshape(()))
+            counts.append(_loop_count(views, cfg))
+        return torch.stack(losses), torch.tensor(counts, dtype=torch.float64, device=device)
+
+
+def eval_loss_landscape(cfg: Config, weights, test_datasets=None, test_ns=None, model=None, return_neighborhood=False):
+    """``eval_loss`` for every row of ``weights`` (see landscape_clouds): datasets, model and neighbourhoods as eval_loss, the
+    global masks recomputed per row.  Returns (loss [W], count [W]) (and the neighbourhoods when ``return_neighborhood``)."""
+    from .preproc import establish_neighborhoods
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    test_clouds, test_poses = _load_test_sequences(cfg, test_datasets)
+    test_pose_deltas = _test_pose_deltas(cfg, test_datasets)
+    if test_ns is None:
+        test_ns = [establish_neighborhoods(clouds=clouds, poses=poses, cfg=cfg) for clouds, poses in zip(test_clouds, test_poses)]
+    loss, count = landscape_clouds(test_clouds, test_poses, test_pose_deltas, [None] * len(test_datasets), test_ns, model, weights,
+                                   cfg)
+    if return_neighborhood:
+        return loss, count, test_ns
+    return loss, count

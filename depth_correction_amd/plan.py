@@ -648,6 +648,41 @@ class SequencePlan:
         self.version += 1
         return out
 
+    def supports_landscape(self, n_terms):
+        """Whether eval_landscape can run on this plan: basis rows for n_terms in {1, 2}, every row a centre.  The landscape kernel
+        reads only the basis rows and ``nbr``; the block-table and backward-layout conditions are those under which _set_basis builds
+        the rows (the fused kernels' basis form), so a plan built without block tables evaluates its landscape by the loop."""
+        return (n_terms in (1, 2) and self.point_format in ('q32', 'f64') and self.use_basis and self.fwd_table is not None
+                and self._block_tables and self._bwd_layout == 'runs' and self.centre_idx is None
+                and nv.MODEL_KINDS.get(self.model_kind, 0) != 0)
+
+    @on_device
+    def eval_landscape(self, weights, exponent, poses12, out, bounds=()):
+        """The loss for every weight row in one pass over the neighbourhoods (dc_sequence_landscape).  weights: fp64 device
+        [W, P] (P in {1, 2}); exponent: fp64 device [P]; poses12: fp64 device [S,12]; out: fp64 device [W, 2] <- {sum of the
+        pointwise loss over the centres that count, their number}.  bounds: (eigenvalue index, denominator index or -1, lo, hi)
+        tuples checked on the eigenvalues of every C(w) on top of the plan's mask (the w-dependent part of global_cloud_mask)."""
+        nw, nt = weights.shape
+        if not self.supports_landscape(nt):
+            raise RuntimeError('this plan has no basis form for a landscape of %d weights' % nt)
+        d = self.desc(nt)
+        need(weights, (nw, nt), dtype=torch.float64, name='weights', device=self.device)
+        need(exponent, (nt,), dtype=torch.float64, name='exponent', device=self.device)
+        need(poses12, (self.n_scans, 12), dtype=torch.float64, name='poses12', device=self.device)
+        need(out, (nw, 2), dtype=torch.float64, name='out', device=self.device)
+        self._set_basis(d, weights[0], exponent, poses12, False, False)
+        rows = self._basis[1]
+        ws = torch.empty((lib().dc_sequence_landscape_workspace_count(self.n),), dtype=torch.float64, device=self.device)
+        flat = [float(v) for b in bounds for v in b]
+        barr = (ctypes.c_double * max(len(flat), 1))(*flat)
+        mask = None if self.mask is None else self.mask.view(torch.uint8)
+        fmt = nv.DC_Q32 if self.qfmt is not None else nv.DC_F64
+        check(lib().dc_sequence_landscape(ptr(rows), fmt, self.qfmt.scale if self.qfmt is not None else 0.0, nt, ptr(self.nbr), self.n,
+                                          self.nbr.shape[1], ptr(mask), ptr(weights), nw, nv.LOSS_KINDS[self.loss],
+                                          int(self.normalization), int(self.sqrt), len(bounds), ctypes.cast(barr, ctypes.c_void_p),
+                                          ptr(ws), ws.numel(), ptr(out), stream_ptr()), 'dc_sequence_landscape')
+        return out
+
     # ------------------------------------------------------------------------------------------------
     def poses12(self, poses):
         """[S,4,4] poses -> contiguous fp64 [S,12] on the plan's device.  The last conversion is kept: an optimisation

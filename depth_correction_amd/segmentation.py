@@ -14,7 +14,7 @@ import torch
 from . import ops
 from ._native import MODEL_KINDS, check, dtype_code, lib, need, on_device, ptr, stream_ptr
 
-__all__ = ['Planes', 'fit_planes', 'plane_moments', 'ransac_sample', 'splitmix64', 'DBSCAN_MIN_POINTS']
+__all__ = ['Planes', 'fit_planes', 'plane_landscape', 'plane_moments', 'ransac_sample', 'splitmix64', 'DBSCAN_MIN_POINTS']
 
 DBSCAN_MIN_POINTS = 10          # cluster_open3d ignores its min_points argument (segmentation.py:166-177)
 _M64 = (1 << 64) - 1
@@ -100,6 +100,12 @@ class Planes(object):
         if self._csr is None or self._csr.ptr.device != torch.device(device):
             self._csr = _PlaneCSR(self.indices, device)
         return self._csr
+
+    def eval_landscape(self, cloud, model_kind, weights, exponent, out, loss='min_eigval_loss', normalization=False, sqrt=False,
+                       mask=None):
+        """The plane loss for every weight row in one pass over the plane points (plane_landscape)."""
+        return plane_landscape(cloud, self, model_kind, weights, exponent, out, loss=loss, normalization=normalization, sqrt=sqrt,
+                               mask=mask)
 
     @staticmethod
     def fit(x, distance_threshold, min_support=3, max_iterations=1000, max_models=10, eps=None, seed=0, **kwargs):
@@ -334,3 +340,48 @@ def plane_moments(cloud, planes, model=None):
     cov = _PlaneMoments.apply(sub.vps.to(dt).contiguous(), sub.dirs.to(dt).contiguous(), sub.depth.reshape(-1, 1).to(dt).contiguous(),
                               None, None, normals, local.csr(dirs.device), None)
     return cov.to(dt)
+
+
+PLANE_LANDSCAPE_KINDS = ('Polynomial', 'ScaledPolynomial')
+
+
+@on_device
+def plane_landscape(cloud, planes, model_kind, weights, exponent, out, loss='min_eigval_loss', normalization=False, sqrt=False,
+                    mask=None):
+    """Plane loss of the global ``cloud`` (not corrected yet) for every row of ``weights`` fp64 device [W, P] (P in {1, 2}) of a
+    Polynomial / ScaledPolynomial model with ``exponent`` fp64 [P] (dc_plane_landscape): the plane features of
+    compute_neighborhood_features and min_eigval_loss / trace_loss over the planes (every plane one entry; ``mask`` bool [planes]:
+    the planes that count).  out fp64 device [W, 2] <- (sum of the loss over the planes, their number)."""
+    n = len(cloud)
+    dirs = cloud.dirs
+    if not dirs.is_cuda:
+        raise RuntimeError('plane features need a GPU: the cloud is on %s (depth_correction_amd has no CPU path)' % dirs.device)
+    if model_kind not in PLANE_LANDSCAPE_KINDS:
+        raise ValueError('the plane landscape takes %s models, not %s' % (' / '.join(PLANE_LANDSCAPE_KINDS), model_kind))
+    dev = dirs.device
+    nw, nt = weights.shape
+    need(weights, (nw, nt), dtype=torch.float64, name='weights', device=dev)
+    need(out, (nw, 2), dtype=torch.float64, name='out', device=dev)
+    ev = exponent.detach().reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+    need(ev, (nt,), dtype=torch.float64, name='exponent', device=dev)
+    vps = (cloud.vps.expand(n, 3) if cloud.vps.dim() == 2 else cloud.vps).detach().contiguous()
+    dirs = dirs.detach().contiguous()
+    depth = cloud.depth.reshape(n).detach().contiguous()
+    csr = planes.csr(dev)
+    nrm = planes.params[:, :3].detach().to(device=dev, dtype=torch.float64).contiguous()
+    m8 = None
+    if mask is not None:
+        m8 = torch.as_tensor(mask, device=dev).to(torch.bool).contiguous()
+        need(m8, (csr.n_planes,), dtype=torch.bool, name='mask', device=dev)
+        m8 = m8.view(torch.uint8)
+    count = lib().dc_plane_landscape_partials_count(csr.n_blocks, nt)
+    if count < 0:
+        raise ValueError('the plane landscape takes 1 or 2 weights, not %d' % nt)
+    partials = torch.empty((count,), dtype=torch.float64, device=dev)
+    pm = torch.empty((max(csr.n_planes, 1) * (count // max(csr.n_blocks, 1)),), dtype=torch.float64, device=dev)
+    check(lib().dc_plane_landscape(ptr(vps), ptr(dirs), ptr(depth), dtype_code(dirs), ptr(csr.idx), ptr(csr.ptr), ptr(nrm), csr.n_planes,
+                                   ptr(csr.blk_plane), ptr(csr.blk_begin), ptr(csr.plane_blk), csr.n_blocks, csr.CHUNK,
+                                   MODEL_KINDS[model_kind], nt, ptr(ev), ptr(m8), ptr(weights), nw,
+                                   {'min_eigval_loss': 0, 'trace_loss': 1}[loss], int(normalization), int(sqrt), ptr(partials),
+                                   partials.numel(), ptr(pm), ptr(out), stream_ptr()), 'dc_plane_landscape')
+    return out

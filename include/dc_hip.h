@@ -758,6 +758,37 @@ int dc_plane_moments_bwd(const void* vps, const void* dirs, const void* depth, i
                          int model_kind, int n_terms, const double* w, const double* e, const double* mean, const double* gcov,
                          void* g_vps, void* g_dirs, void* g_depth, double* wpartials, double* g_w, dcStream_t stream);
 
+/* ---- loss landscape over the model weights (depth_correction_amd/csrc/dc_landscape.hip) ----
+ * The test-set evaluation of eval.py:115-191, repeated for every candidate weight by the reference's sweeps (loss_landscape.py:166,
+ * scripts/weights_search), in one pass over the neighbourhoods.  rows: basis rows of dc_points_basis [n, 6 + n_terms] (point_fmt
+ * DC_Q32: int32 / float32 words on the grid of step `step` (QFormat.scale); DC_F64: fp64), nbr int32 [n,k] (-1 = missing; fixed
+ * k-NN or radius rows padded with -1), mask uint8 [n] (NULL = all), weights double [n_w, n_terms] (device), n_terms 1 or 2.
+ * loss_kind DC_LOSS_MIN_EIGVAL / DC_LOSS_TRACE with normalization / sqrt_ as dc_consistency_fwd (loss.py:237-287, no offset, no
+ * NaN policy).  bounds: HOST double [n_bounds, 4] = (eigenvalue index, denominator index or -1, lo, hi) -- the eigenvalue and
+ * eigenvalue-ratio bounds of global_cloud_mask (preproc.py:122-164), evaluated on the eigenvalues of every C(w); n_bounds <= 8.
+ * out double [n_w, 2] = (sum of the pointwise loss over the centres that count, their number).  workspace double
+ * [dc_sequence_landscape_workspace_count(n)]; any n_w (chunks of 128 weight rows).  Bitwise reproducible. */
+int64_t dc_sequence_landscape_workspace_count(int64_t n);
+int dc_sequence_landscape(const void* rows, int point_fmt, double step, int n_terms, const int32_t* nbr, int64_t n, int k,
+                          const uint8_t* mask, const double* weights, int64_t n_w, int loss_kind, int normalization, int sqrt_,
+                          int n_bounds, const double* bounds, double* workspace, int64_t workspace_count, double* out,
+                          dcStream_t stream);
+
+/* The same for plane neighbourhoods (the plane features of preproc.py:218-243 and the per-plane loss of loss.py:216-294, swept over
+ * the weights as loss_landscape.py:166 does): the planes' points idx[plane_ptr[p] .. plane_ptr[p+1]) of vps / dirs [N,3], depth [N]
+ * (dtype), gamma = arccos |dir . normals[p]| fixed per plane, model_kind DC_MODEL_POLYNOMIAL / DC_MODEL_SCALED_POLYNOMIAL with
+ * exponents e double [n_terms] (1 or 2; device).  Work split of dc_plane_moments_fwd (blk_plane, blk_begin, plane_blk, chunk).
+ * One launch sums the quadratic-form moments of every block (partials double [dc_plane_landscape_partials_count(n_blocks,
+ * n_terms)]), one sums them per plane in block order (plane_moments double [n_planes, partials_count / n_blocks]), one thread per
+ * weight row then forms cov(w) (Bessel), its eigenvalues and the loss of every plane in plane order: out double [n_w, 2] = (sum
+ * of the loss over the planes with mask[p] != 0 (mask uint8 [n_planes], NULL = all), their number).  Bitwise reproducible. */
+int dc_plane_landscape_partials_count(int n_blocks, int n_terms);
+int dc_plane_landscape(const void* vps, const void* dirs, const void* depth, int dtype, const int32_t* idx, const int32_t* plane_ptr,
+                       const double* normals, int n_planes, const int32_t* blk_plane, const int32_t* blk_begin, const int32_t* plane_blk,
+                       int n_blocks, int chunk, int model_kind, int n_terms, const double* e, const uint8_t* mask, const double* weights,
+                       int64_t n_w, int loss_kind, int normalization, int sqrt_, double* partials, int64_t partials_count,
+                       double* plane_moments, double* out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
