@@ -27,6 +27,7 @@ from .distributed import GradReducer, gather_objects, shard_sequences, world_inf
 from .eval import eval_loss_clouds, initialize_pose_corrections
 from .loss import create_loss, icp_correspondences
 from .model import load_model
+from .plan import SequencePlan
 from .preproc import establish_neighborhoods, global_cloud, global_cloud_mask, local_feature_cloud
 
 __all__ = ['TrainCallbacks', 'train', 'release_plans']
@@ -75,7 +76,6 @@ def _only_watches_the_clock(callbacks):
 
 def _agree(code, device):
     """The same value on every rank: ``code`` when all ranks hold it, else 0 (one small all-reduce at set-up)."""
-    from .distributed import all_reduce_sum
     import torch.distributed as dist
     v = torch.tensor([float(code), -float(code)], dtype=torch.float64, device=device)
     if dist.is_available() and dist.is_initialized():
@@ -270,7 +270,7 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
         use_native = getattr(cfg, 'loop_native', True)
         shard = dict(rank=rank, world=world, n_train=n_train, n_val=n_val) if sharded else None
         native = _native_loop_plan(cfg, model, optimizer, train_clouds, train_poses, train_masks, train_ns, val_clouds, val_poses,
-                                   val_masks, val_ns, sharded) if use_native else None
+                                   val_masks, val_ns) if use_native else None
         pose_native = None
         if native is None and use_native:
             pose_native = _native_pose_loop_plan(cfg, model, optimizer, val_optimizer, train_clouds, train_poses, train_masks, train_ns,
@@ -329,14 +329,7 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
             deltas = [p.detach().cpu().clone() for p in train_pose_deltas if p is not None]
             poses_out = [p.detach().cpu().clone() for p in train_poses_upd if p is not None]
             if sharded:
-                # sequence order: rank r owns sequences r, r + world, ...; every rank takes part in the gather
-                by_rank = gather_objects((shard_sequences(n_train, rank, world), deltas, poses_out), device=cfg.device)
-                deltas, poses_out = n_train * [None], n_train * [None]
-                for idx, ds_, ps_ in by_rank:
-                    for k, i in enumerate(idx):
-                        deltas[i] = ds_[k] if k < len(ds_) else None
-                        poses_out[i] = ps_[k] if k < len(ps_) else None
-                deltas, poses_out = [d for d in deltas if d is not None], [p for p in poses_out if p is not None]
+                deltas, poses_out = _gather_in_sequence_order(deltas, poses_out, n_train, rank, world, cfg.device)
             if rank == 0:
                 torch.save(model.state_dict(), stem + '_state_dict.pth')
                 torch.save(deltas, stem + '_pose_deltas.pth')
@@ -368,15 +361,28 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
     return best_cfg
 
 
+def _gather_in_sequence_order(deltas, poses, n_train, rank, world, device):
+    """Every rank's pose corrections and corrected poses (lists of CPU tensors, one per local training sequence) in sequence order:
+    rank r owns sequences r, r + world, ...; every rank takes part in the gather."""
+    by_rank = gather_objects((shard_sequences(n_train, rank, world), deltas, poses), device=device)
+    deltas, poses = n_train * [None], n_train * [None]
+    for idx, ds_, ps_ in by_rank:
+        for k, i in enumerate(idx):
+            deltas[i] = ds_[k] if k < len(ds_) else None
+            poses[i] = ps_[k] if k < len(ps_) else None
+    return [d for d in deltas if d is not None], [p for p in poses if p is not None]
+
+
 class _Bookkeeper(object):
     """The reference's per-iteration bookkeeping (train.py:219-244: improvement rule, progress line, checkpoint files, best
     config), fed with RECORDED iterations in order.  A batch of records ends with ``end_batch``, which writes the files of the
     batch's last improvement."""
 
-    def __init__(self, cfg, model, shard=None):
+    def __init__(self, cfg, model, shard=None, weights=None, poses=None):
         """shard: None, or dict(rank, world, n_train, n_val) when the sequences are dealt over ranks -- every rank replays the same
         records (the losses are all-reduced: identical everywhere), rank 0 prints and writes, and a checkpoint gathers the pose
-        corrections / corrected poses of the sequences the other ranks own (one object gather per batch, at its last improvement)."""
+        corrections / corrected poses of the sequences the other ranks own (one object gather per batch, at its last improvement).
+        weights: the model's parameter that record_fast's rows hold; poses: the fixed poses of its checkpoints without rest()."""
         import copy
         self.cfg, self.min_val, self.best, self._last = cfg, np.inf, None, None
         self.shard = shard
@@ -385,6 +391,10 @@ class _Bookkeeper(object):
         # attributes (fixed exponents) in to() only, and a progress line that reads a device tensor waits for every queued iteration
         self.shadow = copy.deepcopy(model).to('cpu')
         self.shadow_sd = self.shadow.state_dict()
+        if weights is not None:                                   # the rest of the model's state is that of the set-up
+            self.sd_const = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+            self.w_key = [k for k, v in model.state_dict().items() if v.data_ptr() == weights.data_ptr()][0]
+            self.poses = [T.detach().cpu().clone() for T in poses] if poses is not None else None
 
     def record(self, it, tl, vl, sd, deltas, poses):
         """sd: {name: CPU tensor} of the model at iteration ``it``; deltas / poses: lists of CPU tensors."""
@@ -398,43 +408,38 @@ class _Bookkeeper(object):
             self.shadow_sd[k].copy_(v)
         print('It. %03i: train loss: %.9f, val.: %.9f. Model %s %s.' % (it, tl, vl, self.shadow, 'saved' if saved else 'not saved'))
 
-    def record_fast(self, it, tl, vl, key, value, payload):
-        """record() for the loops that log into a device ring: only the tensor ``key`` of the model's state changes from
-        iteration to iteration (``value``: a NumPy row), and what a checkpoint needs -- (state dict, corrections, poses) -- is built
-        by ``payload()`` only for the iteration whose files are written at the end of the batch."""
+    def record_fast(self, it, tl, vl, w_row, rest=None):
+        """record() for the loops that log into a device ring: only the weights change in the model's state from iteration to
+        iteration (``w_row``: a NumPy row, left alone until the batch ends), and the (corrections, poses) of a checkpoint are built
+        by ``rest()`` only for the iteration whose files are written at the end of the batch."""
         saved = tl < np.inf and vl < self.min_val
         if saved:
             self.min_val = vl
-            self._last = (it, vl, payload)
+            self._last = (it, vl, w_row, rest)
         if not self.lead:
             return
-        t = self.shadow_sd[key]
-        t.copy_(torch.from_numpy(np.ascontiguousarray(value)).reshape(t.shape))
+        t = self.shadow_sd[self.w_key]
+        t.copy_(torch.from_numpy(np.ascontiguousarray(w_row)).reshape(t.shape))
         print('It. %03i: train loss: %.9f, val.: %.9f. Model %s %s.' % (it, tl, vl, self.shadow, 'saved' if saved else 'not saved'))
 
     def end_batch(self):
         if self._last is None:
             return
-        if len(self._last) == 3:
-            it, vl, payload = self._last
-            sd, deltas, poses = payload()
+        if len(self._last) == 4:                                  # record_fast's
+            it, vl, w_row, rest = self._last
+            sd, t = dict(self.sd_const), self.sd_const[self.w_key]
+            sd[self.w_key] = torch.from_numpy(w_row).reshape(t.shape).to(t.dtype)
+            deltas, poses = rest() if rest is not None else ([], self.poses)
         else:
             it, vl, sd, deltas, poses = self._last
         self._last = None
         cfg = self.cfg
         stem = '%s/%03i_%.6g' % (cfg.log_dir, it, vl)
         if self.shard is not None:
-            # sequence order: rank r owns sequences r, r + world, ...; every rank takes part in the gather (train.py:232-240 saves
-            # the corrections and corrected poses of ALL training sequences)
+            # (train.py:232-240 saves the corrections and corrected poses of ALL training sequences)
             sh = self.shard
-            by_rank = gather_objects((shard_sequences(sh['n_train'], sh['rank'], sh['world']), [d.clone() for d in deltas],
-                                      [p.clone() for p in poses]), device=cfg.device)
-            deltas, poses = sh['n_train'] * [None], sh['n_train'] * [None]
-            for idx, ds_, ps_ in by_rank:
-                for k, i in enumerate(idx):
-                    deltas[i] = ds_[k] if k < len(ds_) else None
-                    poses[i] = ps_[k] if k < len(ps_) else None
-            deltas, poses = [d for d in deltas if d is not None], [p for p in poses if p is not None]
+            deltas, poses = _gather_in_sequence_order([d.clone() for d in deltas], [p.clone() for p in poses], sh['n_train'],
+                                                      sh['rank'], sh['world'], cfg.device)
         best = cfg.copy()
         best.model_state_dict = stem + '_state_dict.pth'
         best.train_pose_deltas = stem + '_pose_deltas.pth'
@@ -593,6 +598,67 @@ def _batched_loop(cfg, model, optimizer, val_optimizer, train_pose_deltas, val_p
     return book.best
 
 
+def _status_bits(plans, first, upto):
+    """The OR of the plans' status words (read after a ring copy: no further wait; a plan without one adds nothing), with a warning
+    when iterations first .. upto - 1 left the extent of the 32-bit fixed-point format."""
+    bits = 0
+    for p_ in plans:
+        bits |= p_.status_bits() if hasattr(p_, 'status_bits') else 0
+    if bits & SequencePlan.STATUS_OVERFLOW:
+        warnings.warn('train(): points left the extent of the 32-bit fixed-point format (or are NaN) in iterations %d..%d: '
+                      'their losses are NaN; build the plan with point_format="f64" for maps that grow this much' % (first, upto - 1))
+    return bits
+
+
+def _losses(train, val):
+    """(training loss, validation loss) from the joint [sum, count] of each loss (eval.py:85-112): sum / count, NaN for a zero
+    count.  ``val`` None (no validation sequences): the validation loss is the training loss."""
+    tl = float(train[0] / train[1]) if train[1] > 0 else float('nan')
+    if val is None:
+        return tl, tl
+    return tl, (float(val[0] / val[1]) if val[1] > 0 else float('nan'))
+
+
+def _run_batches(n_it, R, launch, fetch, bookkeep, sharded=False):
+    """The batches of the ring-logged loops and what an interrupted run keeps.  launch(it, left) starts at most
+    ``left`` iterations from ``it`` and returns how many, 0 when the plan refuses the step; fetch(first, upto) returns the batch's
+    records on the host, None when the loop has abandoned its chain and finished the run itself; bookkeep(fetched, first, upto).
+    Returns False when the first launch is refused (nothing was launched); a later refusal, or any of a sharded run, raises."""
+    prev = None                            # (first, upto) of the last batch launched and not bookkept yet
+    fetched = None                         # its records on the host, once fetched
+    launched = 0
+    try:
+        while True:
+            if prev is not None:
+                fetched = fetch(*prev)
+                if fetched is None:
+                    return True
+            start = launched
+            end = min(start + R, n_it)
+            while launched < end:
+                n = launch(launched, end - launched)
+                if not n:
+                    if launched or sharded:
+                        raise RuntimeError('train(): a sequence plan refused the native step after the loop had been chosen')
+                    return False
+                launched += n
+            if prev is not None:
+                bookkeep(fetched, *prev)
+            if start == end:
+                return True
+            prev, fetched = (start, end), None
+    except BaseException:
+        try:
+            if prev is not None and not sharded:
+                if fetched is None and launched == prev[1]:
+                    fetched = fetch(*prev)
+                if fetched is not None:
+                    bookkeep(fetched, *prev)
+        except Exception:
+            pass
+        raise
+
+
 def _native_pose_loop_plan(cfg, model, optimizer, val_optimizer, train_clouds, train_poses, train_masks, train_ns, train_pose_deltas,
                            val_clouds, val_poses, val_masks, val_ns, val_pose_deltas):
     """([train plans], [validation plans]) when the loop WITH per-pose / per-sequence corrections can run on plan.PoseSequenceTrainer
@@ -688,53 +754,35 @@ def _native_pose_loop(cfg, model, optimizer, val_optimizer, plans, vplans, train
     n_extra = 0 if extra is None else extra.numel()
     rings = [torch.zeros((R, t_.record_len + n_extra), dtype=torch.float64, device=dev) for t_ in trs]
     vrings = [torch.zeros((R, v.record_len + n_extra), dtype=torch.float64, device=dev) for v in vtr]
-    sd_const = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    w_key = [k for k, v in model.state_dict().items() if v.data_ptr() == w_param.data_ptr()][0]
+    a0 = tr.head + 2 * nt + 12 * plan.n_scans                      # where a record's weights start
     d_dtype, T_dtype = train_pose_deltas[0].dtype, train_poses[0].dtype
-    all_plans = list(plans) + list(vplans)
-    book = _Bookkeeper(cfg, model, shard)
+    book = _Bookkeeper(cfg, model, shard, w_param)
 
-    def fetch():
-        """The ring on the host (synchronises: every launched iteration has finished)."""
-        bits = 0
-        hs, hv = [r_.cpu() for r_ in rings], [v.cpu() for v in vrings]          # synchronises
-        for p_ in all_plans:
-            bits |= p_.status_bits() if hasattr(p_, 'status_bits') else 0
-        return hs, hv, bits
+    def fetch(first, upto):
+        """The rings on the host (synchronises: every launched iteration has finished)."""
+        hs, hv = [r_.cpu().numpy() for r_ in rings], [v.cpu().numpy() for v in vrings]     # synchronises
+        _status_bits(list(plans) + list(vplans), first, upto)
+        return hs, hv
+
+    def corrections_of(rows):
+        def rest():
+            parts = [t_.split_record(torch.from_numpy(r_[:t_.record_len])) for t_, r_ in zip(trs, rows)]
+            return [p_[2].to(d_dtype).clone() for p_ in parts], [p_[3].to(T_dtype).clone() for p_ in parts]
+        return rest
 
     def bookkeep(fetched, first, upto):
-        hs, hv, bits = fetched
-        if bits and bits & plan.STATUS_OVERFLOW:
-            warnings.warn('train(): points left the extent of the 32-bit fixed-point format (or are NaN) in iterations %d..%d: '
-                          'their losses are NaN; build the plan with point_format="f64" for maps that grow this much'
-                          % (first, upto - 1))
-        HS, HV = [h.numpy() for h in hs], [v.numpy() for v in hv]
-        a0 = tr.head + 2 * nt + 12 * plan.n_scans
-
-        def joint_loss(group, rows):
-            if tr.icp:                                                # icp_loss: the mean of the sequences' losses (loss.py:403)
-                return float(sum(r_[0] for r_ in rows) / len(rows))
-            cnt = float(sum(r_[1] for r_ in rows))                    # eval.py:85-112: sum of the sums / sum of the counts
-            return float(sum(r_[0] for r_ in rows)) / cnt if cnt > 0 else float('nan')
-
-        def payload_of(rows):
-            def build():
-                parts = [t_.split_record(torch.from_numpy(r_[:t_.record_len])) for t_, r_ in zip(trs, rows)]
-                sd = dict(sd_const)
-                sd[w_key] = parts[0][1].reshape(w_param.shape).to(w_param.dtype).clone()
-                return sd, [p_[2].to(d_dtype).clone() for p_ in parts], [p_[3].to(T_dtype).clone() for p_ in parts]
-            return build
-
+        HS, HV = fetched
         for it in range(first, upto):
-            rows = [H[it % R] for H in HS]
+            rows = [H[it % R].copy() for H in HS]
             if n_extra:                                               # the joint sums over all sequences (and ranks) ride in every record
                 t2 = rows[0][-n_extra:].reshape(2, 2 + nt)
-                tl = float(t2[0, 0] / t2[0, 1]) if t2[0, 1] > 0 else float('nan')
-                vl = (float(t2[1, 0] / t2[1, 1]) if t2[1, 1] > 0 else float('nan')) if has_val else tl
+                tl, vl = _losses(t2[0], t2[1] if has_val else None)
+            elif tr.icp:                                              # one sequence per loss: icp_loss is its loss (loss.py:403)
+                tl = float(rows[0][0])
+                vl = float(HV[0][it % R][0]) if vtr else tl
             else:
-                tl = joint_loss(trs, rows)
-                vl = joint_loss(vtr, [V[it % R] for V in HV]) if vtr else tl
-            book.record_fast(it, tl, vl, w_key, rows[0][a0:a0 + nt], payload_of([r_.copy() for r_ in rows]))
+                tl, vl = _losses(rows[0], HV[0][it % R] if vtr else None)
+            book.record_fast(it, tl, vl, rows[0][a0:a0 + nt], corrections_of(rows))
         book.end_batch()
 
     def body():
@@ -764,19 +812,19 @@ def _native_pose_loop(cfg, model, optimizer, val_optimizer, plans, vplans, train
         for v, vr in zip(vtr, vrings):
             v.finish(None, None, None, 0.0, vr, vtotals, extra)
 
-    state = dict(launched=0, graph=None, tried=False)
+    graph, tried = None, False
     G = max(1, min(int(getattr(cfg, 'loop_graph_iters', 8) or 1), R))     # iterations per captured graph
 
-    def run_some(left):
-        """Launch the next iteration(s), at most ``left``; returns how many."""
+    def launch(it, left):
+        """Launch iteration ``it`` (and the ones after it, at most ``left``); returns how many."""
+        nonlocal graph, tried
         # (sharded: launched eagerly -- a collective inside a captured graph is not something this path relies on)
-        if (state['launched'] >= 3 and not state['tried'] and n_it - state['launched'] >= G + 3 and getattr(cfg, 'loop_graph', True)
-                and not sharded):
+        if it >= 3 and not tried and n_it - it >= G + 3 and getattr(cfg, 'loop_graph', True) and not sharded:
             # every launch of an iteration takes the same pointers (the record's ring slot follows the device step counter): G
             # iterations are captured once, after three eager ones (pose tables built, allocator warm), and replayed -- one graph
             # launch per G iterations.  (An iteration is one to three short launches: replayed one by one the HOST's ~45 us per
             # graph launch would set the pace of an ICP iteration whose single launch takes half of that.)
-            state['tried'] = True
+            tried = True
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             try:
@@ -784,45 +832,23 @@ def _native_pose_loop(cfg, model, optimizer, val_optimizer, plans, vplans, train
                 with torch.cuda.graph(g_, stream=side):
                     for _ in range(G):
                         body()
-                state['graph'] = g_
+                graph = g_
                 # (a capture launches nothing: the G iterations it recorded have not run)
             except Exception as ex:                                   # not capturable here: keep launching eagerly
                 print('train(): the iteration could not be captured as a graph (%s); running eagerly' % (ex,))
             torch.cuda.current_stream(dev).wait_stream(side)
-        n = G if (state['graph'] is not None and left >= G) else 1
+        n = G if (graph is not None and left >= G) else 1
         if callbacks is not None:
             for q in range(n):
-                callbacks.iteration_started(state['launched'] + q)
-        if n == G and state['graph'] is not None:
-            state['graph'].replay()
+                callbacks.iteration_started(it + q)
+        if n == G and graph is not None:
+            graph.replay()
         else:
             body()
-        state['launched'] += n
         return n
 
-    # batches of R iterations: the records of a batch are fetched (one synchronisation) BEFORE the next batch is launched into the
-    # same ring, and replayed through the reference's bookkeeping WHILE the device runs that next batch
-    prev, start = None, 0
     try:
-        while start < n_it:
-            end = min(start + R, n_it)
-            fetched = fetch() if prev is not None else None
-            it_ = start
-            while it_ < end:
-                it_ += run_some(end - it_)
-            if prev is not None:
-                bookkeep(fetched, *prev)
-            prev, start = (start, end), end
-        if prev is not None:
-            bookkeep(fetch(), *prev)
-            prev = None
-    except BaseException:
-        try:                                                          # an interrupted run keeps the batch it had finished
-            if prev is not None and state['launched'] == prev[1] and not sharded:
-                bookkeep(fetch(), *prev)
-        except Exception:
-            pass
-        raise
+        _run_batches(n_it, R, launch, fetch, bookkeep, sharded)
     finally:
         with torch.no_grad():                                         # the caller's tensors follow the optimisation
             for d, t_ in zip(list(train_pose_deltas) + list(val_pose_deltas), trs + vtr):
@@ -831,8 +857,7 @@ def _native_pose_loop(cfg, model, optimizer, val_optimizer, plans, vplans, train
     return book.best
 
 
-def _native_loop_plan(cfg, model, optimizer, train_clouds, train_poses, train_masks, train_ns, val_clouds, val_poses, val_masks, val_ns,
-                      sharded=False):
+def _native_loop_plan(cfg, model, optimizer, train_clouds, train_poses, train_masks, train_ns, val_clouds, val_poses, val_masks, val_ns):
     """([train plans], [validation plans]) when the whole loop can run on plan.SequenceTrainer's native steps -- only the weights
     of a polynomial model are optimised, with Adam as train() builds it, over up to sixteen (local) training sequences through the
     fused min-eigenvalue / trace loss without inlier gating -- else None."""
@@ -890,77 +915,39 @@ def _native_shared_loop(cfg, model, optimizer, plans, vplans, train_poses, val_p
     ring_w = torch.zeros((R, nt), dtype=torch.float64, device=dev)          # and the weights it used
     vouts = [torch.zeros((2 + 2 * nt + 12 * vp.n_scans,), dtype=torch.float64, device=dev) for vp in vplans]
     vP = [vp.poses12(T) for vp, T in zip(vplans, val_poses)]
-    sd_const = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    w_key = [k for k, v in model.state_dict().items() if v.data_ptr() == w_param.data_ptr()][0]
-    poses_cpu = [T.detach().cpu().clone() for T in train_poses]
-    book = _Bookkeeper(cfg, model, shard)
-    all_plans = list(plans) + list(vplans)
+    book = _Bookkeeper(cfg, model, shard, w_param, train_poses)
 
-    def launch(it):
+    def launch(it, left):
         slot = it % R
         if callbacks is not None:
             callbacks.iteration_started(it)
         if tr.step(w_used_prev=ring_w[slot], require_chain=True, defer_reduce=True) is None:
-            return False
+            return 0
         for vp, P, vo in zip(vplans, vP, vouts):                     # validation with the weights of THIS iteration
             vp.eval_native(tr.w, tr.exponent, P, vo, want_grad=False)
         combine_sums(tr.outs, vouts, ring[slot])
         if sharded:
             all_reduce_sum(ring[slot])                                # the iteration's ONE collective
         tr.use_sums(ring[slot, 0])
-        return True
+        return 1
 
-    def fetch():
-        h, hw = ring.cpu(), ring_w.cpu()                              # synchronises
-        bits = 0
-        for p_ in all_plans:
-            bits |= p_.status_bits()
-        return h.numpy(), hw.numpy(), bits
+    def fetch(first, upto):
+        h, hw = ring.cpu().numpy(), ring_w.cpu().numpy()              # synchronises
+        _status_bits(list(plans) + list(vplans), first, upto)
+        return h, hw
 
     def bookkeep(fetched, first, upto):
-        H, HW, bits = fetched
-        if bits & all_plans[0].STATUS_OVERFLOW:
-            warnings.warn('train(): points left the extent of the 32-bit fixed-point format (or are NaN) in iterations %d..%d: '
-                          'their losses are NaN; build the plan with point_format="f64" for maps that grow this much'
-                          % (first, upto - 1))
+        H, HW = fetched
         for it in range(first, upto):
             sums = H[it % R]
-            tl = float(sums[0, 0] / sums[0, 1]) if sums[0, 1] > 0 else float('nan')
-            vl = (float(sums[1, 0] / sums[1, 1]) if sums[1, 1] > 0 else float('nan')) if has_val else tl
-            w_row = np.array(HW[it % R], dtype=np.float64, copy=True)
-
-            def payload(w_row=w_row):
-                sd = dict(sd_const)
-                sd[w_key] = torch.from_numpy(w_row).reshape(w_param.shape).to(w_param.dtype).clone()
-                return sd, [], poses_cpu
-            book.record_fast(it, tl, vl, w_key, w_row, payload)
+            tl, vl = _losses(sums[0], sums[1] if has_val else None)
+            book.record_fast(it, tl, vl, np.array(HW[it % R], dtype=np.float64, copy=True))
         book.end_batch()
 
-    prev, start, launched = None, 0, 0
     try:
-        while start < n_it:
-            end = min(start + R, n_it)
-            fetched = fetch() if prev is not None else None
-            for it in range(start, end):
-                if not launch(it):
-                    if it or sharded:
-                        raise RuntimeError('train(): a sequence plan refused the native step after the loop had been chosen')
-                    return False, None                             # nothing was launched
-                launched = it + 1
-            if prev is not None:
-                bookkeep(fetched, *prev)
-            prev, start = (start, end), end
-        if prev is not None:
-            bookkeep(fetch(), *prev)
-            prev = None
+        if not _run_batches(n_it, R, launch, fetch, bookkeep, sharded):
+            return False, None
         tr.flush()                                                  # the last iteration's Adam update (train.py:312)
-    except BaseException:
-        try:                                                        # an interrupted run keeps the batch it had finished
-            if prev is not None and launched == prev[1] and not sharded:
-                bookkeep(fetch(), *prev)
-        except Exception:
-            pass
-        raise
     finally:
         torch.autograd.graph.increment_version(w_param)            # written through its pointer
     return True, book.best
@@ -989,29 +976,17 @@ def _native_loop(cfg, model, optimizer, plans, vplans, train_poses, val_poses, b
     ring_w = torch.zeros((R, nt), dtype=torch.float64, device=dev)
     vrings = [torch.zeros((R, 2 + 2 * nt + 12 * vp.n_scans), dtype=torch.float64, device=dev) for vp in vplans]
     vP = [vp.poses12(T) for vp, T in zip(vplans, val_poses)]
-    sd_const = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    w_key = [k for k, v in model.state_dict().items() if v.data_ptr() == w_param.data_ptr()][0]
-    poses_cpu = [T.detach().cpu().clone() for T in train_poses]
-    book = _Bookkeeper(cfg, model)
-    snap = None                      # optimiser state after the last fetched iteration: where a batch can be started again
+    book = _Bookkeeper(cfg, model, weights=w_param, poses=train_poses)
 
     def snapshot():
         return tr.w.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone(), tr.t
 
-    def record(it, sums, w_used, vsums):
-        tl = float(sums[0] / sums[1]) if sums[1] > 0 else float('nan')
-        if vsums:
-            vs, vc = sum(float(v[0]) for v in vsums), sum(float(v[1]) for v in vsums)
-            vl = vs / vc if vc > 0 else float('nan')
-        else:
-            vl = tl
-        w_row = np.array(w_used, dtype=np.float64, copy=True)
+    snap = snapshot()                # optimiser state after the last fetched iteration: where a batch can be started again
 
-        def payload():
-            sd = dict(sd_const)
-            sd[w_key] = torch.from_numpy(w_row).reshape(w_param.shape).to(w_param.dtype).clone()
-            return sd, [], poses_cpu
-        book.record_fast(it, tl, vl, w_key, w_row, payload)
+    def record(it, sums, w_used, vsums):
+        vjoint = (sum(float(v[0]) for v in vsums), sum(float(v[1]) for v in vsums)) if vsums else None
+        tl, vl = _losses(sums, vjoint)
+        book.record_fast(it, tl, vl, np.array(w_used, dtype=np.float64, copy=True))
 
     def plain_iterations(first):
         """Iterations first .. n_it - 1 with ordinary (two-launch) steps and one synchronisation each: where the loop goes on
@@ -1034,10 +1009,7 @@ def _native_loop(cfg, model, optimizer, plans, vplans, train_poses, val_poses, b
         tr.flush(out=ring[(upto - 1) % R])
         h, hw = ring.cpu(), ring_w.cpu()                            # synchronises
         hv = [v.cpu() for v in vrings]
-        bits = 0
-        for p_ in plans:
-            bits |= p_.status_bits()                                # (free: the copies above have synchronised)
-        if bits & plan.STATUS_CHAIN_TIMEOUT:
+        if _status_bits(plans, first, upto) & plan.STATUS_CHAIN_TIMEOUT:
             warnings.warn('train(): a chained step gave up waiting for its weights (iterations %d..%d); repeating them and '
                           'finishing the run with ordinary steps' % (first, upto - 1))
             for p_ in plans:
@@ -1046,10 +1018,6 @@ def _native_loop(cfg, model, optimizer, plans, vplans, train_poses, val_poses, b
             tr.w.copy_(w0_); tr.exp_avg.copy_(m0_); tr.exp_avg_sq.copy_(v0_); tr.t = t0_
             plain_iterations(first)
             return None
-        if bits & plan.STATUS_OVERFLOW:
-            warnings.warn('train(): points left the extent of the 32-bit fixed-point format (or are NaN) in iterations %d..%d: '
-                          'their losses are NaN; build the plan with point_format="f64" for maps that grow this much'
-                          % (first, upto - 1))
         snap = snapshot()                                           # the optimiser after iteration upto - 1: where a batch can restart
         return h.numpy(), hw.numpy(), [v.numpy() for v in hv]
 
@@ -1060,48 +1028,19 @@ def _native_loop(cfg, model, optimizer, plans, vplans, train_poses, val_poses, b
             record(it, H[sl], HW[sl], [v[sl] for v in HV])
         book.end_batch()
 
-    # batches of R iterations: the records of a batch are fetched (one synchronisation) BEFORE the next batch is launched into the
-    # same ring, and replayed through the reference's bookkeeping WHILE the device runs that next batch
-    snap = snapshot()
-    prev, fetched, start, launched = None, None, 0, 0
+    def launch(it, left):
+        slot = (it - 1) % R
+        if callbacks is not None:
+            callbacks.iteration_started(it)
+        if tr.step(out_prev=ring[slot], w_used_prev=ring_w[slot], require_chain=True) is None:
+            return 0                                                # this plan does not chain
+        for vp, P, vr in zip(vplans, vP, vrings):                    # validation with the weights of THIS iteration
+            vp.eval_native(tr.w, tr.exponent, P, vr[it % R], want_grad=False)
+        return 1
+
     try:
-        while start < n_it:
-            end = min(start + R, n_it)
-            if prev is not None:
-                fetched = fetch(*prev)
-                if fetched is None:
-                    prev = None
-                    break
-            for it in range(start, end):
-                slot = (it - 1) % R
-                if callbacks is not None:
-                    callbacks.iteration_started(it)
-                if tr.step(out_prev=ring[slot], w_used_prev=ring_w[slot], require_chain=True) is None:
-                    assert it == 0
-                    return False, None                             # this plan does not chain; nothing was launched
-                for vp, P, vr in zip(vplans, vP, vrings):            # validation with the weights of THIS iteration
-                    vp.eval_native(tr.w, tr.exponent, P, vr[it % R], want_grad=False)
-                launched = it + 1
-            if prev is not None:
-                bookkeep(fetched, *prev)
-                fetched = None
-            prev, start = (start, end), end
-        if prev is not None:
-            fetched = fetch(*prev)
-            if fetched is not None:
-                bookkeep(fetched, *prev)
-            prev = fetched = None
-    except BaseException:
-        # an interrupted run keeps the batch it had finished: its records are on the host already, or still whole in the ring
-        try:
-            if prev is not None:
-                if fetched is None and launched == prev[1]:
-                    fetched = fetch(*prev)
-                if fetched is not None:
-                    bookkeep(fetched, *prev)
-        except Exception:
-            pass
-        raise
+        if not _run_batches(n_it, R, launch, fetch, bookkeep):
+            return False, None
     finally:
         torch.autograd.graph.increment_version(w_param)            # written through its pointer
     return True, book.best
