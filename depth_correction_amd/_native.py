@@ -143,6 +143,9 @@ _SIGNATURES = {
     'dc_plane_landscape_partials_count': (_i32, [_i32, _i32]),
     'dc_plane_landscape': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                   _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    'dc_bvh_workspace_bytes': (_sz, [_i64]),
+    'dc_bvh_build': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_raycast': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 

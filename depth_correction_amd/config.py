@@ -134,6 +134,9 @@ class Config(object):
         self.eval_losses = list(Loss)
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
+        self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse
+        self.depth_bias_model_args = []                         # (config.py:237-240); all-zero weights add nothing
+        self.depth_bias_model_kwargs = {}
         self.depth_noise = 0.0           # dataset.noisy_dataset (config.py:242-244)
         self.pose_noise = 0.0
         self.pose_noise_mode = None

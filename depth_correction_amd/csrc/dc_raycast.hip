@@ -1,0 +1,359 @@
+// Triangle-mesh ray casting for the rendered-mesh datasets (render.py; the reference rasterises with pytorch3d, dataset.py:1073-1130).
+//
+// LBVH build (dc_bvh_build), Karras 2012 "Maximizing parallelism in the construction of BVHs, octrees and k-d trees":
+//   1. key[f] = (morton30(centroid_f in the scene box) << 32) | f -- unique keys, so the tree does not depend on scheduling;
+//   2. dc::sort_pairs_u64 (dc_sort.h) orders the faces by key -> leaf_face;
+//   3. internal node i of the n - 1 covers the leaf range found from the common-prefix lengths of its neighbours' keys;
+//   4. bottom-up fitting: every leaf writes its box and climbs; one atomic counter per internal node lets the second child that
+//      arrives form the parent's box.  Boxes are float32, rounded outward from the fp64 vertex bounds (round-down for the
+//      minimum, round-up for the maximum), and an internal box is the exact min / max of its children's: bit-identical for any
+//      arrival order, and every face lies inside each box on its path to the root.
+// Node numbering: internal nodes 0 .. n-2 (root 0), leaf i is node n-1+i; with one face the root is leaf 0.  The tree's depth is
+// at most 63: a child's keys share a strictly longer prefix than its parent's, and the 64-bit keys start with two zero bits.
+//
+// Closest-hit cast (dc_raycast): one lane per ray, every (pose, ray) pair in one launch.  The boxes are tested in fp32 (slab test;
+// the exit distance is scaled by 1 + 2^-20, Ize 2013's 1 + 2 gamma_3 with headroom for the fp32 rounding of the direction, and
+// the boxes grow by 2^-22 |origin| for the rounding of the origin), so no box a ray touches in exact arithmetic is rejected.  The
+// nearer child is visited first; the other goes on a per-lane stack in LDS (depth 64, lane-minor so that a wavefront's pushes hit
+// 64 distinct banks).  Triangles are tested in fp64 with the watertight test of Woop, Benthin and Wald (JCGT 2013): a ray through
+// a shared edge or vertex hits at least one of the faces around it (no FMA contraction there, see test_triangle).  A hit counts
+// when t > t_min (and dot(n, d) < 0 with culling); the smallest t wins, equal t the lower face index -- independent of the
+// traversal order, so results are bitwise reproducible.
+#include "dc_common.h"
+#include "dc_hostutil.h"
+#include "dc_sort.h"
+#include "../../include/dc_hip.h"
+
+namespace {
+
+constexpr int kBuildBlock = 256;
+constexpr int kCastBlock = 128;
+constexpr int kStackDepth = 64;
+
+__device__ __forceinline__ uint32_t expand_bits10(uint32_t v) {
+  v &= 0x3ffu;
+  v = (v | (v << 16)) & 0x030000ffu;
+  v = (v | (v << 8)) & 0x0300f00fu;
+  v = (v | (v << 4)) & 0x030c30c3u;
+  v = (v | (v << 2)) & 0x09249249u;
+  return v;
+}
+
+__device__ __forceinline__ uint32_t quantise10(double c, double lo, double scale) {
+  double q = (c - lo) * scale;
+  q = q < 0.0 ? 0.0 : (q > 1023.0 ? 1023.0 : q);
+  return (uint32_t)q;
+}
+
+struct SceneBox {
+  double lo[3];
+  double scale[3];        // 1024 / extent (0 for a flat axis)
+};
+
+__global__ void __launch_bounds__(kBuildBlock) morton_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                             int64_t n, SceneBox box, uint64_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ vals) {
+  const int64_t f = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (f >= n) return;
+  uint32_t code = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double c = (verts[3 * (int64_t)faces[3 * f] + a] + verts[3 * (int64_t)faces[3 * f + 1] + a] +
+                      verts[3 * (int64_t)faces[3 * f + 2] + a]) * (1.0 / 3.0);
+    code |= expand_bits10(quantise10(c, box.lo[a], box.scale[a])) << (2 - a);
+  }
+  keys[f] = ((uint64_t)code << 32) | (uint64_t)(uint32_t)f;
+  vals[f] = (uint32_t)f;
+}
+
+// length of the common prefix of keys i and j, -1 outside [0, n)
+__device__ __forceinline__ int delta(const uint64_t* __restrict__ keys, int64_t n, int64_t i, int64_t j) {
+  if (j < 0 || j >= n) return -1;
+  return __clzll((long long)(keys[i] ^ keys[j]));
+}
+
+__global__ void __launch_bounds__(kBuildBlock) karras_kernel(const uint64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ child,
+                                                             int32_t* __restrict__ parent) {
+  const int64_t i = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (i >= n - 1) return;
+  const int d = delta(keys, n, i, i + 1) > delta(keys, n, i, i - 1) ? 1 : -1;
+  const int dmin = delta(keys, n, i, i - d);
+  int64_t lmax = 2;
+  while (delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
+  int64_t l = 0;
+  for (int64_t t = lmax / 2; t >= 1; t /= 2)
+    if (delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+  const int64_t j = i + l * d;
+  const int dnode = delta(keys, n, i, j);
+  int64_t s = 0;
+  for (int64_t t = (l + 1) / 2;; t = (t + 1) / 2) {       // ceil(l / 2), ceil(l / 4), ... down to 1
+    if (delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+    if (t == 1) break;
+  }
+  const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
+  const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
+  const int32_t left = (int32_t)(lo == gamma ? (n - 1) + gamma : gamma);
+  const int32_t right = (int32_t)(hi == gamma + 1 ? (n - 1) + gamma + 1 : gamma + 1);
+  child[2 * i] = left;
+  child[2 * i + 1] = right;
+  parent[left] = (int32_t)i;
+  parent[right] = (int32_t)i;
+}
+
+__device__ __forceinline__ float load_box(const float* p) {
+  return __uint_as_float(__hip_atomic_load((const uint32_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+__global__ void __launch_bounds__(kBuildBlock) fit_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces, int64_t n,
+                                                          const int32_t* __restrict__ leaf_face, const int32_t* __restrict__ child,
+                                                          const int32_t* __restrict__ parent, int32_t* __restrict__ counter,
+                                                          float* node_box, double* __restrict__ leaf_tri) {
+  const int64_t i = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t f = leaf_face[i];
+  double v[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) v[3 * c + a] = verts[3 * (int64_t)faces[3 * f + c] + a];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) leaf_tri[9 * i + k] = v[k];
+  int64_t node = (n - 1) + i;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    node_box[6 * node + a] = __double2float_rd(fmin(fmin(v[a], v[3 + a]), v[6 + a]));
+    node_box[6 * node + 3 + a] = __double2float_ru(fmax(fmax(v[a], v[3 + a]), v[6 + a]));
+  }
+  node = parent[node];
+  while (node >= 0) {
+    __threadfence();                                        // this child's box is visible before the counter says so
+    if (atomicAdd(&counter[node], 1) == 0) return;          // the sibling is still on its way: it fits the parent
+    __threadfence();
+    const int64_t a0 = child[2 * node], b0 = child[2 * node + 1];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      node_box[6 * node + a] = fminf(load_box(node_box + 6 * a0 + a), load_box(node_box + 6 * b0 + a));
+      node_box[6 * node + 3 + a] = fmaxf(load_box(node_box + 6 * a0 + 3 + a), load_box(node_box + 6 * b0 + 3 + a));
+    }
+    node = parent[node];
+  }
+}
+
+struct Ray32 {
+  float o[3], inv[3], margin;
+};
+
+// entry distance of the box of `node` (>= 0), or +inf when the ray misses it before t_far
+__device__ __forceinline__ float box_entry(const float* __restrict__ node_box, int64_t node, const Ray32& r, float t_far) {
+  const float* b = node_box + 6 * node;
+  float tn = 0.0f, tf = t_far;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float t0 = (b[a] - r.margin - r.o[a]) * r.inv[a];
+    const float t1 = (b[3 + a] + r.margin - r.o[a]) * r.inv[a];
+    tn = fmaxf(tn, fminf(t0, t1));
+    tf = fminf(tf, fmaxf(t0, t1) * (1.0f + 0x1p-20f));
+  }
+  return tn <= tf ? tn : INFINITY;
+}
+
+struct Hit {
+  double t, u, v;
+  int32_t face;
+};
+
+// A ray in the frame of the watertight test: axes permuted to (kx, ky, kz), kz the dominant one.  Scalars only: the compiler turns
+// a select between elements of a private array into a runtime index, and a runtime-indexed private array lives in scratch memory.
+struct Ray64 {
+  double d0, d1, d2;            // direction (world frame), for the culling test
+  double ox, oy, oz;            // origin, permuted
+  double sx, sy, sz;            // shear constants
+  int kx, ky, kz;
+};
+
+__device__ __forceinline__ double pick(int k, double a, double b, double c) { return k == 0 ? a : (k == 1 ? b : c); }
+
+// Woop, Benthin, Wald 2013 in fp64; t, u (weight of v1), v (weight of v2) of a hit with t > t_min that beats `best`
+__device__ __forceinline__ void test_triangle(const double* __restrict__ tri, int32_t face, const Ray64& r, double t_min, bool cull,
+                                              Hit& best) {
+  // no fused multiply-adds here: watertightness needs the edge function of a shared edge to be computed as the exact negation
+  // of the neighbour's (fl(a b) - fl(c d) = -(fl(c d) - fl(a b)); fma(a, b, -fl(c d)) is not -fma(c, d, -fl(a b)))
+#pragma clang fp contract(off)
+  const double t0 = tri[0], t1 = tri[1], t2 = tri[2], t3 = tri[3], t4 = tri[4], t5 = tri[5], t6 = tri[6], t7 = tri[7], t8 = tri[8];
+  const double Az = pick(r.kz, t0, t1, t2) - r.oz, Bz = pick(r.kz, t3, t4, t5) - r.oz, Cz = pick(r.kz, t6, t7, t8) - r.oz;
+  const double Ax = (pick(r.kx, t0, t1, t2) - r.ox) - r.sx * Az, Ay = (pick(r.ky, t0, t1, t2) - r.oy) - r.sy * Az;
+  const double Bx = (pick(r.kx, t3, t4, t5) - r.ox) - r.sx * Bz, By = (pick(r.ky, t3, t4, t5) - r.oy) - r.sy * Bz;
+  const double Cx = (pick(r.kx, t6, t7, t8) - r.ox) - r.sx * Cz, Cy = (pick(r.ky, t6, t7, t8) - r.oy) - r.sy * Cz;
+  const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+  if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return;
+  const double det = U + V + W;
+  if (det == 0.0) return;
+  const double T = U * (r.sz * Az) + V * (r.sz * Bz) + W * (r.sz * Cz);
+  const double t = T / det;
+  if (!(t > t_min) || t > best.t || (t == best.t && face >= best.face)) return;
+  if (cull) {
+    const double e10 = t3 - t0, e11 = t4 - t1, e12 = t5 - t2, e20 = t6 - t0, e21 = t7 - t1, e22 = t8 - t2;
+    const double nd = (e11 * e22 - e12 * e21) * r.d0 + (e12 * e20 - e10 * e22) * r.d1 + (e10 * e21 - e11 * e20) * r.d2;
+    if (!(nd < 0.0)) return;
+  }
+  best.t = t;
+  best.u = V / det;
+  best.v = W / det;
+  best.face = face;
+}
+
+__global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                                             const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
+                                                             int64_t n, const double* __restrict__ dirs, const double* __restrict__ t_min,
+                                                             int64_t n_rays, const double* __restrict__ poses, int64_t total, int cull,
+                                                             int32_t* __restrict__ face_out, double* __restrict__ t_out,
+                                                             double* __restrict__ bary_out) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  if (g >= total) return;
+  const int64_t p = g / n_rays, r = g - p * n_rays;
+  const double* M = poses + 16 * p;
+  const double s0 = dirs[3 * r], s1 = dirs[3 * r + 1], s2 = dirs[3 * r + 2];
+  Ray64 ray64;
+  ray64.d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
+  ray64.d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
+  ray64.d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
+  const double o0 = M[3], o1 = M[7], o2 = M[11];
+  const double tmin = t_min[r];
+  // watertight test set-up: kz = dominant axis, (kx, ky) keep the winding
+  const double ad0 = fabs(ray64.d0), ad1 = fabs(ray64.d1), ad2 = fabs(ray64.d2);
+  const int kz = ad0 >= ad1 ? (ad0 >= ad2 ? 0 : 2) : (ad1 >= ad2 ? 1 : 2);
+  int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+  const double dz = pick(kz, ray64.d0, ray64.d1, ray64.d2);
+  if (dz < 0.0) { const int s = kx; kx = ky; ky = s; }
+  ray64.kx = kx;
+  ray64.ky = ky;
+  ray64.kz = kz;
+  ray64.sz = 1.0 / dz;
+  ray64.sx = pick(kx, ray64.d0, ray64.d1, ray64.d2) * ray64.sz;
+  ray64.sy = pick(ky, ray64.d0, ray64.d1, ray64.d2) * ray64.sz;
+  ray64.ox = pick(kx, o0, o1, o2);
+  ray64.oy = pick(ky, o0, o1, o2);
+  ray64.oz = pick(kz, o0, o1, o2);
+  Ray32 ray;
+  const double oo[3] = {o0, o1, o2}, dd[3] = {ray64.d0, ray64.d1, ray64.d2};
+  float omax = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ray.o[a] = (float)oo[a];
+    omax = fmaxf(omax, fabsf(ray.o[a]));
+    float da = (float)dd[a];
+    if (fabsf(da) < 1e-20f) da = copysignf(1e-20f, da);
+    ray.inv[a] = 1.0f / da;
+  }
+  ray.margin = fmaxf(omax * 0x1p-22f, 1e-30f);
+
+  Hit best;
+  best.t = INFINITY;
+  best.u = best.v = 0.0;
+  best.face = -1;
+  int sp = 0;
+  int64_t node = 0;
+  bool live = box_entry(node_box, 0, ray, INFINITY) < INFINITY;
+  while (live) {
+    if (node >= n - 1) {
+      const int64_t leaf = node - (n - 1);
+      test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], ray64, tmin, cull != 0, best);
+    } else {
+      const float t_far = __double2float_ru(best.t);
+      const int64_t ca = child[2 * node], cb = child[2 * node + 1];
+      const float ta = box_entry(node_box, ca, ray, t_far), tb = box_entry(node_box, cb, ray, t_far);
+      if (ta < INFINITY || tb < INFINITY) {
+        if (ta < INFINITY && tb < INFINITY) {
+          const bool a_first = ta <= tb;
+          if (sp < kStackDepth) stack[sp * kCastBlock + lane] = (int32_t)(a_first ? cb : ca);    // sp < 64 always (depth <= 63)
+          ++sp;
+          node = a_first ? ca : cb;
+        } else {
+          node = ta < INFINITY ? ca : cb;
+        }
+        continue;
+      }
+    }
+    // next postponed node whose box the ray still reaches before the best hit
+    live = false;
+    while (sp > 0) {
+      --sp;
+      node = sp < kStackDepth ? stack[sp * kCastBlock + lane] : 0;
+      if (box_entry(node_box, node, ray, __double2float_ru(best.t)) < INFINITY) { live = true; break; }
+    }
+  }
+  face_out[g] = best.face;
+  t_out[g] = best.t;
+  bary_out[2 * g] = best.u;
+  bary_out[2 * g + 1] = best.v;
+}
+
+inline unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+}  // namespace
+
+extern "C" {
+
+size_t dc_bvh_workspace_bytes(int64_t n_faces) {
+  if (n_faces < 1) return 0;
+  dc::Carver c(nullptr);
+  c.take<uint64_t>(n_faces);
+  c.take<uint64_t>(n_faces);
+  c.take<uint32_t>(n_faces);
+  c.take<int32_t>(n_faces);
+  c.take<char>(dc::sort_pairs_bytes((size_t)n_faces, 64));
+  return c.off + 256;
+}
+
+int dc_bvh_build(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* scene_box, int32_t* leaf_face,
+                 int32_t* child, int32_t* parent, float* node_box, double* leaf_tri, void* ws, size_t ws_bytes, dcStream_t stream_) {
+  if (n_faces < 1 || n_faces > (int64_t)INT32_MAX / 2 || n_verts < 1 || !verts || !faces || !scene_box || !leaf_face || !child || !parent ||
+      !node_box || !leaf_tri)
+    return DC_ERR_ARG;
+  if (!ws || ws_bytes < dc_bvh_workspace_bytes(n_faces)) return DC_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  SceneBox box;
+  for (int a = 0; a < 3; ++a) {
+    const double ext = scene_box[3 + a] - scene_box[a];
+    if (!(ext >= 0.0)) return DC_ERR_ARG;
+    box.lo[a] = scene_box[a];
+    box.scale[a] = ext > 0.0 ? 1024.0 / ext : 0.0;
+  }
+  dc::Carver c(ws);
+  uint64_t* keys_in = c.take<uint64_t>(n_faces);
+  uint64_t* keys_out = c.take<uint64_t>(n_faces);
+  uint32_t* vals_in = c.take<uint32_t>(n_faces);
+  int32_t* counter = c.take<int32_t>(n_faces);
+  const size_t sort_bytes = dc::sort_pairs_bytes((size_t)n_faces, 64);
+  void* sort_tmp = c.take<char>(sort_bytes);
+  DC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t), stream));                    // the root has no parent
+  DC_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t) * n_faces, stream));
+  morton_kernel<<<grid_of(n_faces, kBuildBlock), kBuildBlock, 0, stream>>>(verts, faces, n_faces, box, keys_in, vals_in);
+  DC_HIP(hipGetLastError());
+  DC_HIP(dc::sort_pairs_u64(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, leaf_face, (size_t)n_faces, 0, 62, stream));
+  if (n_faces > 1) {
+    karras_kernel<<<grid_of(n_faces - 1, kBuildBlock), kBuildBlock, 0, stream>>>(keys_out, n_faces, child, parent);
+    DC_HIP(hipGetLastError());
+  }
+  fit_kernel<<<grid_of(n_faces, kBuildBlock), kBuildBlock, 0, stream>>>(verts, faces, n_faces, leaf_face, child, parent, counter, node_box,
+                                                                       leaf_tri);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+               const double* dirs, const double* t_min, int64_t n_rays, const double* poses, int n_poses, int cull, int32_t* face_out,
+               double* t_out, double* bary_out, dcStream_t stream) {
+  if (n_faces < 1 || n_rays < 0 || n_poses < 0 || !node_box || !leaf_tri || !leaf_face || (n_faces > 1 && !child)) return DC_ERR_ARG;
+  const int64_t total = n_rays * (int64_t)n_poses;
+  if (total == 0) return DC_OK;
+  if (!dirs || !t_min || !poses || !face_out || !t_out || !bary_out) return DC_ERR_ARG;
+  raycast_kernel<<<grid_of(total, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(child, node_box, leaf_tri, leaf_face, n_faces, dirs, t_min,
+                                                                                    n_rays, poses, total, cull, face_out, t_out, bary_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+}  // extern "C"

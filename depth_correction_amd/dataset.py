@@ -1,7 +1,9 @@
-"""Synthetic scan generators (host side, numpy only).
+"""Synthetic scan generators (host side, numpy only) and the rendered-mesh datasets.
 
-Only the generators the hot path's tests and ``bench.py`` need are provided; the reference's
-real-data readers and mesh renderers (dataset.py:361-1331, datasets/*) are out of scope.
+The analytic generators the hot path's tests and ``bench.py`` need are here; lidar scans rendered from triangle meshes
+(``RenderedMeshDataset``, ``DepthBiasDataset``, ``render_lidar_cloud``; reference dataset.py:490-716, 850-873, 1073-1130) live in
+``render.py`` and are re-exported here.  The reference's real-data readers (dataset.py:361-489, datasets/*) are out of scope
+(SURVEY 2, #13).
 
 * ``PlaneDataset``   -- restatement of the reference generator of BASELINE config 0
                         (dataset.py:240-358): two 10x10 m half planes, per-scan random subsample.
@@ -17,7 +19,8 @@ import numpy as np
 from numpy.lib.recfunctions import unstructured_to_structured, merge_arrays
 
 __all__ = ['PlaneDataset', 'RoomBoxDataset', 'KittiLikeDataset', 'create_dataset', 'add_depth_noise', 'Forwarding',
-           'TransformingDataset', 'FilteredDataset', 'NoisyPoseDataset', 'NoisyDepthDataset', 'noisy_dataset', 'euler_matrix']
+           'TransformingDataset', 'FilteredDataset', 'NoisyPoseDataset', 'NoisyDepthDataset', 'noisy_dataset', 'euler_matrix',
+           'RenderedMeshDataset', 'DepthBiasDataset', 'render_lidar_cloud', 'render_lidar_clouds', 'lidar_directions']
 
 
 def _structured(xyz, normals=None):
@@ -169,7 +172,13 @@ def add_depth_noise(cloud, sigma, rng):
 
 
 def create_dataset(name, cfg=None, **kwargs):
-    """Subset of the reference's ``create_dataset`` (dataset.py:953-962): synthetic names only."""
+    """Subset of the reference's ``create_dataset`` (dataset.py:953-962): the synthetic names and ``rendered_mesh/...`` (keyword
+    arguments such as ``poses_path`` go to RenderedMeshDataset; its device defaults to ``cfg.device``)."""
+    from .render import RenderedMeshDataset
+    if name.startswith(RenderedMeshDataset.dataset_name + '/'):
+        if cfg is not None and 'device' not in kwargs:
+            kwargs['device'] = cfg.device
+        return RenderedMeshDataset(name, **kwargs)
     if name.startswith('plane'):
         return PlaneDataset(**kwargs)
     if name.startswith('room'):
@@ -313,8 +322,18 @@ class NoisyDepthDataset(TransformingDataset):
 
 
 def noisy_dataset(ds, cfg):
-    """Depth noise and pose noise of the configuration on top of ``ds`` (dataset.py:933-950; the depth-bias wrapper needs a
-    mesh-free inverse model and is applied by the caller where wanted)."""
+    """Depth bias, depth noise and pose noise of the configuration on top of ``ds`` (dataset.py:933-950): the bias of
+    ``cfg.depth_bias_model_class`` (with its args / kwargs) through DepthBiasDataset when that model's weights are not all
+    zero -- with the defaults they are, and ``ds`` is left unwrapped."""
+    if getattr(cfg, 'depth_bias_model_class', None):
+        from .model import model_by_name
+        gt_model = model_by_name(cfg.depth_bias_model_class)(*(getattr(cfg, 'depth_bias_model_args', None) or []),
+                                                              **(getattr(cfg, 'depth_bias_model_kwargs', None) or {}))
+        w = gt_model.kernel_params()[0] if gt_model.kernel_kind is not None else None
+        if w is not None and (w != 0.0).any():
+            print('Adding bias from %s.' % gt_model)
+            from .render import DepthBiasDataset
+            ds = DepthBiasDataset(ds, gt_model, cfg=cfg)
     if getattr(cfg, 'depth_noise', 0.0):
         print('Adding depth noise %.3g.' % cfg.depth_noise)
         ds = NoisyDepthDataset(ds, noise=cfg.depth_noise)
@@ -322,3 +341,14 @@ def noisy_dataset(ds, cfg):
         print('Adding pose noise %s, %s.' % (cfg.pose_noise, cfg.pose_noise_mode))
         ds = NoisyPoseDataset(ds, noise=cfg.pose_noise, mode=cfg.pose_noise_mode)
     return ds
+
+
+_RENDER_NAMES = ('RenderedMeshDataset', 'DepthBiasDataset', 'render_lidar_cloud', 'render_lidar_clouds', 'lidar_directions')
+
+
+def __getattr__(name):
+    """The rendered-mesh names live in render.py (which builds on the wrappers above) and are re-exported here on first use."""
+    if name in _RENDER_NAMES:
+        from . import render
+        return getattr(render, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

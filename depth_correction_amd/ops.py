@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast',
 ]
 
 
@@ -1031,3 +1031,60 @@ class IcpSequence:
             return False
         check(rc, 'dc_icp_sequence_step')
         return True
+
+
+# ------------------------------------------------------------------------------------------------
+# triangle-mesh ray casting (dc_raycast.hip)
+# ------------------------------------------------------------------------------------------------
+@on_device
+def bvh_build(verts, faces, scene_box):
+    """LBVH of verts f64 [V,3] / faces i32 [F,3] (indices checked here) in the box ``scene_box`` (6 floats: lo xyz, hi xyz) ->
+    mesh.MeshBVH (leaf_face i32 [F], child i32 [F-1,2], parent i32 [2F-1], node_box f32 [2F-1,6], leaf_tri f64 [F,9])."""
+    import numpy as np
+    from .mesh import MeshBVH
+    need(verts, (None, 3), dtype=torch.float64, name='verts')
+    need(faces, (None, 3), dtype=torch.int32, name='faces', device=verts.device)
+    nv_, nf = verts.shape[0], faces.shape[0]
+    if nv_ == 0 or nf == 0:
+        raise ValueError('bvh_build needs at least one vertex and one face')
+    lo, hi = int(faces.min()), int(faces.max())
+    if lo < 0 or hi >= nv_:
+        raise ValueError('face indices must lie in [0, %d), got [%d, %d]' % (nv_, lo, hi))
+    box = np.ascontiguousarray(np.asarray(scene_box, dtype=np.float64).reshape(6))
+    if not (np.isfinite(box).all() and (box[3:] >= box[:3]).all()):
+        raise ValueError('scene_box must be finite with hi >= lo, got %s' % box)
+    dev = verts.device
+    leaf_face = torch.empty((nf,), dtype=torch.int32, device=dev)
+    child = torch.empty((max(nf - 1, 0), 2), dtype=torch.int32, device=dev)
+    parent = torch.empty((2 * nf - 1,), dtype=torch.int32, device=dev)
+    node_box = torch.empty((2 * nf - 1, 6), dtype=torch.float32, device=dev)
+    leaf_tri = torch.empty((nf, 9), dtype=torch.float64, device=dev)
+    nbytes = lib().dc_bvh_workspace_bytes(nf)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_bvh_build(ptr(verts), nv_, ptr(faces), nf, box.ctypes.data_as(ctypes.c_void_p), ptr(leaf_face),
+                             ptr(child) if nf > 1 else None, ptr(parent), ptr(node_box), ptr(leaf_tri), ptr(ws), nbytes, stream_ptr()),
+          'dc_bvh_build')
+    return MeshBVH(leaf_face, child, parent, node_box, leaf_tri)
+
+
+@on_device
+def raycast(bvh, dirs, poses, t_min, cull=True):
+    """Closest hits of the rays dirs f64 [R,3] (sensor frame) of every pose of poses f64 [P,4,4] (world from sensor), hits
+    beyond t_min f64 [R] (and facing the ray with ``cull``) -> (face i32 [P,R] (-1 = miss), t f64 [P,R] (inf on a miss),
+    bary f64 [P,R,2]): the hit is v0 + u (v1 - v0) + v (v2 - v0).  One launch (dc_raycast)."""
+    dev = bvh.leaf_face.device
+    need(dirs, (None, 3), dtype=torch.float64, name='dirs', device=dev)
+    r = dirs.shape[0]
+    need(t_min, (r,), dtype=torch.float64, name='t_min', device=dev)
+    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
+    p = poses.shape[0]
+    if p * r >= 2 ** 62:
+        raise ValueError('too many rays')
+    face = torch.empty((p, r), dtype=torch.int32, device=dev)
+    t = torch.empty((p, r), dtype=torch.float64, device=dev)
+    bary = torch.empty((p, r, 2), dtype=torch.float64, device=dev)
+    nf = bvh.n_faces
+    check(lib().dc_raycast(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                           ptr(dirs), ptr(t_min), r, ptr(poses), p, 1 if cull else 0, ptr(face), ptr(t), ptr(bary), stream_ptr()),
+          'dc_raycast')
+    return face, t, bary

@@ -1,0 +1,297 @@
+"""Lidar scans rendered from triangle meshes, and the datasets built on them (reference dataset.py:490-716, 850-873, 1073-1130).
+
+The reference composes a scan of ``num_segments`` perspective renders of pytorch3d's rasteriser, one segment at a time on the
+host.  Here every ray of every pose is cast in one launch against an LBVH of the mesh (``dc_raycast``); the rays restate the
+reference's cameras (``lidar_directions``).  Compaction, the sensor-frame transform and the field assembly use torch.
+"""
+from __future__ import annotations
+
+import functools
+import math
+import os
+import tempfile
+from copy import copy
+
+import numpy as np
+import torch
+from numpy.lib.recfunctions import unstructured_to_structured
+
+from .dataset import TransformingDataset
+
+__all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'DepthBiasDataset', 'mesh_dir']
+
+Z_CLIP = 1e-3          # pytorch3d RasterizationSettings(z_clip_value=1e-3) of the reference
+
+
+def mesh_dir():
+    """Meshes named by a relative path are looked up here (the reference's <pkg>/data/meshes); none are shipped."""
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'data', 'meshes')
+
+
+def _check_pattern(fov, size, num_segments):
+    if len(fov) != 2 or not (0.0 < fov[0] < 180.0) or not (0.0 < fov[1] <= 360.0):
+        raise ValueError('fov must be (vertical in (0, 180), horizontal in (0, 360]) degrees, got %s' % (fov,))
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError('size must be (rows, columns) >= 1, got %s' % (size,))
+    if int(num_segments) < 1 or int(size[1]) // int(num_segments) < 1:
+        raise ValueError('num_segments must be in 1 .. columns, got %s for size %s' % (num_segments, size))
+
+
+@functools.lru_cache(maxsize=16)
+def _directions(fov, size, num_segments):
+    fv, fh = math.radians(fov[0]), math.radians(fov[1])
+    h, s = int(size[0]), int(num_segments)
+    ws = int(size[1] / s)
+    fx = (ws / 2.0) / math.tan(fh / (2.0 * s))
+    fy = (h / 2.0) / math.tan(fv / 2.0)
+    rows = (h / 2.0 - (np.arange(h) + 0.5)) / fy          # up
+    cols = (ws / 2.0 - (np.arange(ws) + 0.5)) / fx        # left
+    out = np.empty((s, h, ws, 3))
+    fwd = np.empty((s, 3))
+    for i in range(s):
+        a = -fh / 2.0 + i * fh / s + 1e-3
+        ef = np.array([math.cos(a), math.sin(a), 0.0])
+        eu = np.array([0.0, 0.0, 1.0])
+        el = np.cross(eu, ef)
+        out[i] = ef + cols[None, :, None] * el + rows[:, None, None] * eu
+        fwd[i] = ef
+    norm = np.linalg.norm(out, axis=-1, keepdims=True)
+    d = out / norm
+    t_min = Z_CLIP / np.einsum('shwc,sc->shw', d, fwd)
+    d, t_min = d.reshape(-1, 3), t_min.reshape(-1)
+    d.flags.writeable = False
+    t_min.flags.writeable = False
+    return d, t_min
+
+
+def lidar_directions(size=(64, 512), fov=(90., 360.), num_segments=32):
+    """Unit sensor-frame ray directions float64 [S*H*W_s, 3] and their near clips t_min [S*H*W_s] of the reference's lidar
+    (render_lidar_cloud, dataset.py:1073-1130): segment i looks along yaw a_i = -F_h/2 + i F_h/S + 1e-3 with H rows and
+    W_s = int(W / S) columns; pixel (r, c) casts along e_f + ((W_s/2 - (c+.5)) / f_x) e_l + ((H/2 - (r+.5)) / f_y) e_u, with
+    f_x = (W_s/2) / tan(F_h / 2S), f_y = (H/2) / tan(F_v/2), e_f = (cos a_i, sin a_i, 0), e_u = z, e_l = e_u x e_f (pytorch3d's
+    screen convention); t_min = 1e-3 / (d . e_f) keeps depth along e_f above z_clip_value.  Segment-major, then row, column."""
+    fov, size = tuple(float(x) for x in fov), tuple(int(x) for x in size)
+    _check_pattern(fov, size, num_segments)
+    return _directions(fov, size, int(num_segments))
+
+
+def _device(mesh_device):
+    dev = torch.device(mesh_device) if mesh_device is not None else torch.device('cuda')
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise RuntimeError('rendering a mesh needs a GPU (device %s%s): depth_correction_amd has no CPU path'
+                           % (dev, '' if torch.cuda.is_available() else ', and torch sees none'))
+    return dev
+
+
+_DT = np.dtype([(f, np.float64) for f in ('x', 'y', 'z', 'vp_x', 'vp_y', 'vp_z', 'normal_x', 'normal_y', 'normal_z')])
+
+
+def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True):
+    """Scans of ``mesh`` (mesh.TriangleMesh) from every pose of ``poses`` [P,4,4] (world from sensor) in one cast: a list of P
+    structured arrays of RenderedMeshDataset.cloud_dtype in the sensor frame (vp = 0, normals rotated into it), misses dropped,
+    points in lidar_directions' order.  The hit point is v0 + u (v1 - v0) + v (v2 - v0) in fp64 from the face's vertices."""
+    from .ops import raycast
+    dev = _device(device)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    dirs_h, tmin_h = lidar_directions(size=size, fov=fov, num_segments=num_segments)
+    verts, faces, normals, bvh = mesh.on_device(dev)
+    dev = verts.device
+    dirs = torch.as_tensor(np.array(dirs_h), device=dev)
+    t_min = torch.as_tensor(np.array(tmin_h), device=dev)
+    P = torch.as_tensor(poses, device=dev)
+    face, _, bary = raycast(bvh, dirs, P, t_min, cull=cull)
+    out = []
+    for p in range(poses.shape[0]):
+        keep = face[p] >= 0
+        f = face[p][keep].long()
+        uv = bary[p][keep]
+        tri = verts[faces[f].long()]                                        # [M,3,3]
+        x = tri[:, 0] + uv[:, :1] * (tri[:, 1] - tri[:, 0]) + uv[:, 1:] * (tri[:, 2] - tri[:, 0])
+        R, t = P[p, :3, :3], P[p, :3, 3]
+        # utils.transform with the pose inverse: x' = R^T x - R^T t, normals rotated only, the view point becomes 0
+        xs = x @ R - (R.t() @ t)
+        ns = normals[f] @ R
+        arr = torch.cat([xs, torch.zeros_like(xs), ns], dim=1).cpu().numpy()
+        out.append(unstructured_to_structured(np.ascontiguousarray(arr), dtype=_DT))
+    return out
+
+
+def render_lidar_cloud(mesh, pose, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True):
+    """One scan (render_lidar_clouds of one pose)."""
+    return render_lidar_clouds(mesh, np.asarray(pose, dtype=np.float64)[None], fov=fov, size=size, num_segments=num_segments,
+                               device=device, cull=cull)[0]
+
+
+class RenderedMeshDataset(object):
+    """Lidar scans rendered from a mesh at given poses (dataset.py:490-716).  ``name``: an absolute mesh path, a path relative to
+    mesh_dir(), or ``rendered_mesh/<mesh>[/<params>]`` with params such as ``n_10_size_64_512_fov_45_360``.  Poses from
+    ``poses`` [N,4,4] or ``poses_path`` (a poses CSV, scan_io.read_poses_csv).  All poses are rendered in one cast at the first
+    cloud asked for; ``cache`` reads and writes ``cloud_%05i.bin`` files (np.tofile of cloud_dtype) under ``cache_dir``."""
+
+    dataset_name = 'rendered_mesh'
+    cloud_dtype = _DT
+
+    def __init__(self, name, n=None, size=(64, 512), fov=(45., 360.), num_segments=16, poses_path=None, poses=None, cache=False,
+                 device='cuda', cache_dir=None):
+        from .mesh import load_mesh
+        from .scan_io import read_poses_csv
+        from .utils import hashable
+        if os.path.isabs(name):
+            path = name
+        else:
+            parts = name.split('/')
+            if not 1 <= len(parts) <= 3:
+                raise ValueError('Invalid rendered mesh name: %s' % name)
+            if len(parts) >= 2:
+                if parts[0] != RenderedMeshDataset.dataset_name:
+                    raise ValueError('Invalid rendered mesh name: %s (expected %s/<mesh>[/<params>])'
+                                     % (name, RenderedMeshDataset.dataset_name))
+                name = parts[1]
+                if len(parts) == 3:
+                    n, size, fov = self.parse_params(parts[2].split('_'), n, size, fov)
+            path = os.path.join(mesh_dir(), name)
+        if not os.path.exists(path):
+            raise FileNotFoundError('Mesh %s does not exist.' % path)
+        if n is not None and not (isinstance(n, int) and n > 0):
+            raise ValueError('n must be a positive int, got %r' % (n,))
+        _check_pattern(tuple(fov), tuple(size), num_segments)
+        self.hash_name = ''
+        if poses is None:
+            if not poses_path:
+                raise ValueError('RenderedMeshDataset needs poses or poses_path (viewpoint generation is not provided)')
+            if not os.path.isabs(poses_path):
+                self.hash_name = poses_path.replace(os.path.basename(poses_path), '').replace('/', '_')
+                poses_path = os.path.join(mesh_dir(), poses_path)
+            if not os.path.exists(poses_path):
+                raise FileNotFoundError('Poses path %s does not exist.' % poses_path)
+            ids, poses = read_poses_csv(poses_path)
+            self.poses = np.stack(poses).astype(np.float64)
+        else:
+            if poses_path:
+                raise ValueError('give poses or poses_path, not both')
+            self.poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+            self.hash_name = str(abs(hash(hashable(self.poses))))
+        if n is not None:
+            self.poses = self.poses[:n]
+        self.ids = list(range(len(self.poses)))
+        self.path, self.size, self.fov, self.num_segments = path, tuple(size), tuple(fov), num_segments
+        self.poses_path, self.cache, self.device = poses_path, cache, device
+        self.cache_dir = cache_dir or os.path.join(tempfile.gettempdir(), 'depth_correction_amd', 'gen')
+        self.n = len(self)
+        self._load_mesh = load_mesh
+        self._state = {'mesh': None, 'clouds': None}            # shared by the copies that slicing makes
+
+    def get_mesh(self):
+        if self._state['mesh'] is None:
+            self._state['mesh'] = self._load_mesh(self.path)
+        return self._state['mesh']
+
+    def __getitem__(self, i):
+        if isinstance(i, (int, np.integer)):
+            id = self.ids[i]
+            return self.local_cloud(id), self.cloud_pose(id)
+        ds = copy(self)
+        if isinstance(i, (list, tuple)):
+            ds.ids = [self.ids[j] for j in i]
+        elif isinstance(i, slice):
+            ds.ids = self.ids[i]
+        else:
+            raise ValueError('Invalid index: %s.' % i)
+        return ds
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self[i]
+
+    def __str__(self):
+        return '%s/%s' % (RenderedMeshDataset.dataset_name, os.path.basename(self.path))
+
+    @staticmethod
+    def parse_params(params, n, size, fov):
+        """n, size, fov from the tokens of ``n_10_size_64_512_fov_45_360`` (the reference's parse_params)."""
+        if 'n' in params:
+            i = params.index('n')
+            n = int(params[i + 1])
+        if 'size' in params:
+            i = params.index('size')
+            size = [int(x) for x in params[i + 1:i + 3]]
+        if 'fov' in params:
+            i = params.index('fov')
+            fov = [float(x) for x in params[i + 1:i + 3]]
+        return n, size, fov
+
+    def dataset_dir(self):
+        path = os.path.join(self.cache_dir, RenderedMeshDataset.dataset_name, os.path.basename(self.path))
+        if self.poses_path:
+            path = os.path.join(path, os.path.basename(self.poses_path))
+        return path
+
+    def cloud_path(self, id):
+        return os.path.join(self.dataset_dir(), 'hash_%s_size_%i_%i_fov_%.0f_%.0f' % (self.hash_name, *self.size, *self.fov),
+                            'cloud_%05i.bin' % id)
+
+    def _render_all(self):
+        """Every pose's scan, in one cast (the files of the cache are read instead where present)."""
+        clouds = self._state['clouds']
+        if clouds is None:
+            clouds = [None] * len(self.poses)
+            if self.cache:
+                for id in range(len(self.poses)):
+                    if os.path.exists(self.cloud_path(id)):
+                        clouds[id] = np.fromfile(self.cloud_path(id), dtype=RenderedMeshDataset.cloud_dtype)
+            todo = [id for id, c in enumerate(clouds) if c is None]
+            if todo:
+                rendered = render_lidar_clouds(self.get_mesh(), self.poses[todo], fov=self.fov, size=self.size,
+                                               num_segments=self.num_segments, device=self.device)
+                for id, c in zip(todo, rendered):
+                    clouds[id] = c
+                    if self.cache:
+                        os.makedirs(os.path.dirname(self.cloud_path(id)), exist_ok=True)
+                        c.tofile(self.cloud_path(id))
+            self._state['clouds'] = clouds
+        return clouds
+
+    def local_cloud(self, id):
+        return self._render_all()[id].copy()
+
+    def cloud_pose(self, id):
+        return self.poses[id]
+
+
+class DepthBiasDataset(TransformingDataset):
+    """Clouds with the depth bias of ``model`` added through model.inverse (dataset.py:850-873): incidence angles from the
+    cloud's normals when it has them (update_incidence_angles), else from estimated normals (update_all(k=cfg.nn_k,
+    r=cfg.nn_r)); x, y, z are written back."""
+
+    def __init__(self, dataset, model=None, cfg=None):
+        super().__init__(dataset)
+        self.model = model
+        self.cfg = cfg
+
+    def transform_cloud(self, cloud, **kwargs):
+        from .depth_cloud import DepthCloud
+        from .model import BaseModel
+        if self.model is None:
+            return cloud
+        assert isinstance(self.model, BaseModel)
+        w = self.model.kernel_params()[0] if self.model.kernel_kind is not None else None
+        device = w.device if w is not None else None
+        dc = DepthCloud.from_structured_array(cloud, device=device)
+        log = getattr(self.cfg, 'log_filters', False)
+        if dc.normals is None:
+            if log:
+                print('Estimating normals from data for introducing depth bias.')
+            dc.update_all(k=self.cfg.nn_k, r=self.cfg.nn_r)
+        else:
+            if log:
+                print('Using provided normals for introducing depth bias.')
+            dc.update_incidence_angles()
+        with torch.no_grad():
+            dc = self.model.inverse(dc)
+        pts = dc.to_points().detach().cpu().numpy()
+        cloud = cloud.copy()
+        cloud[['x', 'y', 'z']] = unstructured_to_structured(pts.astype(np.float64), names=['x', 'y', 'z'])
+        return cloud

@@ -789,6 +789,26 @@ int dc_plane_landscape(const void* vps, const void* dirs, const void* depth, int
                        int64_t n_w, int loss_kind, int normalization, int sqrt_, double* partials, int64_t partials_count,
                        double* plane_moments, double* out, dcStream_t stream);
 
+/* ---- triangle-mesh ray casting (depth_correction_amd/csrc/dc_raycast.hip; build, traversal and precision rules in its header
+ * comment), the renderer of the reference's rendered-mesh datasets (dataset.py:490-716, render_lidar_cloud :1073-1130) ----
+ * LBVH of the mesh verts double [n_verts,3], faces int32 [n_faces,3] (indices < n_verts: checked by the caller) in the scene
+ * box scene_box (HOST double [6] = lo xyz, hi xyz, containing every vertex): leaf_face int32 [n_faces] (face of leaf i, in
+ * Morton order), child int32 [n_faces-1, 2] (node numbers: internal 0 .. n_faces-2, root 0; leaf i = n_faces-1+i), parent
+ * int32 [2 n_faces-1] (-1 at the root), node_box float [2 n_faces-1, 6] (lo xyz, hi xyz; rounded outward), leaf_tri double
+ * [n_faces, 9] (the vertices of leaf i's face).  Deterministic: the same inputs give bit-identical outputs.
+ * ws: dc_bvh_workspace_bytes(n_faces). */
+size_t dc_bvh_workspace_bytes(int64_t n_faces);
+int dc_bvh_build(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* scene_box, int32_t* leaf_face,
+                 int32_t* child, int32_t* parent, float* node_box, double* leaf_tri, void* ws, size_t ws_bytes, dcStream_t stream);
+/* Closest hit of every ray r (sensor-frame direction dirs double [n_rays,3]) of every pose p (poses double [n_poses,4,4], world
+ * from sensor): origin = the pose's translation, direction = its rotation times dirs[r].  A hit counts when t > t_min[r] (double
+ * [n_rays]) and, with cull != 0, dot(face normal, direction) < 0; the smallest t wins, equal t the lower face index.  Row
+ * p * n_rays + r of face_out int32 (-1 = miss), t_out double (+inf on a miss) and bary_out double [., 2] = (u, v): the hit is
+ * v0 + u (v1 - v0) + v (v2 - v0).  Arrays of dc_bvh_build; one launch. */
+int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+               const double* dirs, const double* t_min, int64_t n_rays, const double* poses, int n_poses, int cull, int32_t* face_out,
+               double* t_out, double* bary_out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
