@@ -24,6 +24,10 @@ DC_ERR_ARG, DC_ERR_DTYPE, DC_ERR_WORKSPACE, DC_ERR_UNSUPPORTED = -1, -2, -3, -4 
 DC_ERR_BACKWARD_TABLES = -5
 MODEL_KINDS = {None: 0, 'BaseModel': 0, 'Polynomial': 1, 'ScaledPolynomial': 2, 'Linear': 3, 'InvCos': 4, 'ScaledInvCos': 5}
 MAX_MODEL_TERMS = 8
+# include/dc_hip.h: the ICP registration state (DC_ICP_STATE_*), its block partials and status codes (DC_ICP_*)
+DC_ICP_STATE_COUNT, DC_ICP_STATE_POSE, DC_ICP_STATE_PRIOR, DC_ICP_STATE_PAIRS, DC_ICP_STATE_SSE, DC_ICP_STATE_OVERLAP = 64, 0, 16, 48, 49, 50
+DC_ICP_MAX_SMOOTH, DC_ICP_PARTIALS = 8, 30
+ICP_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'singular', -3: 'not_finite', -4: 'bound'}
 
 _LIB = None
 _vp, _i32, _i64, _f64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
@@ -146,6 +150,15 @@ _SIGNATURES = {
     'dc_bvh_workspace_bytes': (_sz, [_i64]),
     'dc_bvh_build': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dc_raycast': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'dc_knn_grid_build': (_i32, [_vp, _i32, _i32, _i64, _i64, _i32, _f64, _vp, _sz, _vp]),
+    'dc_knn_grid_query': (_i32, [_i64, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),
+    'dc_quantile_workspace_bytes': (_sz, []),
+    'dc_quantile': (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _sz, _vp]),
+    'dc_icp_blocks': (_i32, [_i64]),
+    'dc_icp_init': (_i32, [_vp, _vp, _vp, _vp]),
+    'dc_icp_accumulate': (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'dc_icp_finish': (_i32, [_vp, _i32, _i64, _f64, _f64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp]),
+    'dc_map_select': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
 }
 
 

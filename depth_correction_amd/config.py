@@ -12,7 +12,8 @@ import tempfile
 
 import yaml
 
-__all__ = ['Config', 'Loss', 'loss_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'nonempty']
+__all__ = ['Config', 'Loss', 'loss_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
+           'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
 class _Names(type):
@@ -46,6 +47,20 @@ class PoseCorrection(metaclass=_Names):
     pose = 'pose'
 
 
+class SLAM(metaclass=_Names):
+    """SLAM pipelines eval_slam can run (config.py:82-84).  The reference's one is norlab_icp_mapper through ROS; this package has
+    its own scan-to-map point-to-plane ICP configured like it (slam.py, DESIGN "SLAM evaluation")."""
+    icp_mapper = 'icp_mapper'
+
+
+class PoseProvider(metaclass=_Names):
+    ground_truth = 'ground_truth'
+
+
+for _slam in SLAM:                # SLAM pipelines are pose providers too (config.py:91-93)
+    setattr(PoseProvider, _slam, _slam)
+
+
 def nonempty(iterable):
     return [x for x in iterable if x]
 
@@ -56,6 +71,36 @@ def loss_eval_csv(log_dir: str, loss: str, subset: str = None):
         path = 'loss_eval_{loss}_{subset}.csv'.format(loss=loss, subset=subset)
     else:
         path = 'loss_eval_{loss}.csv'.format(loss=loss)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def slam_eval_csv(log_dir: str, slam: str, subset: str = None):
+    """CSV file eval_slam_all appends to for one SLAM pipeline and subset (config.py:106-113)."""
+    if subset:
+        path = 'slam_eval_{slam}_{subset}.csv'.format(slam=slam, subset=subset)
+    else:
+        path = 'slam_eval_{slam}.csv'.format(slam=slam)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def slam_eval_bag(log_dir: str, slam: str):
+    """(config.py:126-130; no bag is recorded here)"""
+    path = 'slam_eval_{slam}.bag'.format(slam=slam)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def slam_poses_csv(log_dir: str, name: str, slam: str):
+    """Poses CSV of one sequence's SLAM run (config.py:133-140)."""
+    if name:
+        path = os.path.join(name, 'slam_poses_{slam}.csv'.format(slam=slam))
+    else:
+        path = os.path.join('slam_poses_{slam}.csv'.format(slam=slam))
     if log_dir:
         path = os.path.join(log_dir, path)
     return path
@@ -126,12 +171,35 @@ class Config(object):
         # more than one (train.py of this package), False = every process trains on all sequences
         self.distributed = None
         self.pose_correction = PoseCorrection.none
+        self.pose_provider = PoseProvider.ground_truth      # (config.py:169-170)
+        self.slam = SLAM.icp_mapper
         self.train_pose_deltas = None
         self.test_pose_deltas = None
         self.log_filters = False
         # evaluation (:275, :282): eval_loss appends its result to loss_eval_csv when set; eval_loss_all evaluates these losses
         self.loss_eval_csv = None
         self.eval_losses = list(Loss)
+        # SLAM evaluation (config.py:276-283; slam.py): eval_slam appends to slam_eval_csv, writes slam_poses_csv when set
+        self.slam_eval_csv = None
+        self.slam_eval_bag = None
+        self.slam_poses_csv = None
+        self.odom_cov = [0.0, 0.0, 0.0, 0.0, 0.0, 0.0]     # odometry noise: a scalar, [rot, trans], 6 variances or a 6 x 6 matrix
+        self.eval_slams = list(SLAM)
+        # the mapper (config/slam/input_filters.yaml, icp.yaml, launch/slam.launch)
+        self.slam_normals_k = 9                 # SurfaceNormalDataPointsFilter knn, normals oriented toward the sensor
+        self.icp_knn = 3                        # KDTreeMatcher knn
+        self.icp_max_dist = 10.0                # KDTreeMatcher maxDist
+        self.icp_trim_ratio = 0.8               # TrimmedDistOutlierFilter ratio
+        self.icp_max_normal_angle = 1.57        # SurfaceNormalOutlierFilter maxAngle
+        self.icp_min_diff_rot = 0.001           # DifferentialTransformationChecker minDiffRotErr
+        self.icp_min_diff_trans = 0.01          # minDiffTransErr
+        self.icp_smooth_length = 2              # smoothLength
+        self.icp_max_iters = 100                # CounterTransformationChecker maxIterationCount
+        self.icp_max_rotation = 0.8             # BoundTransformationChecker maxRotationNorm
+        self.icp_max_translation = 30.0         # maxTranslationNorm
+        self.slam_min_overlap = 0.9             # map_update_overlap
+        self.slam_min_dist_new_point = 0.1      # min_dist_new_point
+        self.slam_sensor_max_range = 25.0       # sensor_max_range
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse

@@ -228,8 +228,12 @@ struct Nn1State {
   unsigned int hist[256];
 };
 
-__global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st, int shift, int first) {
+// (stop: optional device word; once it is non-zero the select's launches return at once and the threshold keeps its value --
+//  dc_quantile inside a registration that has ended)
+__global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st, int shift, int first,
+                                                          const int32_t* __restrict__ stop) {
   __shared__ unsigned int s_hist[256];
+  if (stop && *stop != 0) return;
   s_hist[threadIdx.x] = 0;
   __syncthreads();
   const unsigned long long prefix = first ? 0ull : st->prefix;
@@ -245,8 +249,8 @@ __global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restri
   if (s_hist[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], s_hist[threadIdx.x]);
 }
 
-__global__ void nn1_pick_kernel(Nn1State* st, int shift, int first, double ratio) {
-  if (threadIdx.x != 0) return;
+__global__ void nn1_pick_kernel(Nn1State* st, int shift, int first, double ratio, const int32_t* __restrict__ stop) {
+  if (threadIdx.x != 0 || (stop && *stop != 0)) return;
   if (first) {
     long long total = 0;
     for (int q = 0; q < 256; ++q) total += st->hist[q];
@@ -272,9 +276,11 @@ __global__ void nn1_pick_kernel(Nn1State* st, int shift, int first, double ratio
   for (int q = 0; q < 256; ++q) st->hist[q] = 0;
 }
 
-__global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st) {
+__global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st,
+                                                          const int32_t* __restrict__ stop) {
   __shared__ long long s_cnt[kBlock / kWave];
   __shared__ unsigned long long s_min[kBlock / kWave];
+  if (stop && *stop != 0) return;
   const unsigned long long v = st->prefix;
   long long cnt = 0;
   unsigned long long mn = ~0ull;
@@ -301,8 +307,8 @@ __global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restri
   }
 }
 
-__global__ void nn1_threshold_kernel(Nn1State* st, double* __restrict__ threshold) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__global__ void nn1_threshold_kernel(Nn1State* st, double* __restrict__ threshold, const int32_t* __restrict__ stop) {
+  if (threadIdx.x != 0 || blockIdx.x != 0 || (stop && *stop != 0)) return;
   if (st->n_valid <= 0) { *threshold = __longlong_as_double(0x7ff8000000000000ll); return; }      // np.quantile of nothing: NaN
   const double a = __longlong_as_double((long long)st->prefix);
   // a[lo + 1]: another copy of a[lo] when more than lo + 1 elements are <= it, else the next distinct value (a[lo] itself at the end)
@@ -310,6 +316,23 @@ __global__ void nn1_threshold_kernel(Nn1State* st, double* __restrict__ threshol
   if (st->lo + 1 < st->n_valid) b = (st->n_le >= st->lo + 2) ? a : __longlong_as_double((long long)st->next_bits);
   const double t = st->gamma, diff = b - a;
   *threshold = t >= 0.5 ? b - diff * (1.0 - t) : a + diff * t;       // numpy's _lerp
+}
+
+// The select itself: state cleared, eight byte passes (histogram + pick), the next value, numpy's interpolation -> *threshold.
+static hipError_t launch_quantile(const double* dist, int64_t n, double ratio, const int32_t* stop, Nn1State* st, double* threshold,
+                                  hipStream_t stream) {
+  hipError_t err = hipMemsetAsync(st, 0, sizeof(Nn1State), stream);
+  if (err != hipSuccess) return err;
+  const unsigned blocks_all = (unsigned)((n + kBlock - 1) / kBlock);
+  const unsigned blocks = blocks_all < 512u ? blocks_all : 512u;
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = 56 - 8 * pass;
+    hipLaunchKernelGGL(nn1_hist_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, shift, pass == 0 ? 1 : 0, stop);
+    hipLaunchKernelGGL(nn1_pick_kernel, dim3(1), dim3(64), 0, stream, st, shift, pass == 0 ? 1 : 0, ratio, stop);
+  }
+  hipLaunchKernelGGL(nn1_next_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, stop);
+  hipLaunchKernelGGL(nn1_threshold_kernel, dim3(1), dim3(64), 0, stream, st, threshold, stop);
+  return hipGetLastError();
 }
 
 __global__ __launch_bounds__(kBlock) void nn1_flag_kernel(const double* __restrict__ dist, int64_t n, const double* __restrict__ threshold,
@@ -637,23 +660,25 @@ int dc_nn1_corr(const double* dist, const int32_t* idx, int64_t n, double ratio,
   int32_t* flags = reinterpret_cast<int32_t*>(base + st_bytes);
   int32_t* pos = reinterpret_cast<int32_t*>(base + st_bytes + arr);
   void* scan_ws = base + st_bytes + 2 * arr;
-  hipError_t err = hipMemsetAsync(st, 0, sizeof(dc::Nn1State), stream);
+  hipError_t err = dc::launch_quantile(dist, n, ratio, nullptr, st, threshold_out, stream);
   if (err != hipSuccess) return (int)err;
   const unsigned blocks_all = (unsigned)((n + dc::kBlock - 1) / dc::kBlock);
-  const unsigned blocks = blocks_all < 512u ? blocks_all : 512u;
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    hipLaunchKernelGGL(dc::nn1_hist_kernel, dim3(blocks), dim3(dc::kBlock), 0, stream, dist, n, st, shift, pass == 0 ? 1 : 0);
-    hipLaunchKernelGGL(dc::nn1_pick_kernel, dim3(1), dim3(64), 0, stream, st, shift, pass == 0 ? 1 : 0, ratio);
-  }
-  hipLaunchKernelGGL(dc::nn1_next_kernel, dim3(blocks), dim3(dc::kBlock), 0, stream, dist, n, st);
-  hipLaunchKernelGGL(dc::nn1_threshold_kernel, dim3(1), dim3(64), 0, stream, st, threshold_out);
   hipLaunchKernelGGL(dc::nn1_flag_kernel, dim3(blocks_all), dim3(dc::kBlock), 0, stream, dist, n, (const double*)threshold_out, mask_out, flags);
   err = dc::exclusive_scan_32(scan_ws, dc::scan_bytes((size_t)n), flags, pos, (size_t)n, stream);
   if (err != hipSuccess) return (int)err;
   hipLaunchKernelGGL(dc::nn1_scatter_kernel, dim3(blocks_all), dim3(dc::kBlock), 0, stream, idx, (const uint8_t*)mask_out, (const int32_t*)pos, n,
                      idx_out, count_out);
   err = hipGetLastError();
+  return err == hipSuccess ? DC_OK : (int)err;
+}
+
+size_t dc_quantile_workspace_bytes(void) { return ((sizeof(dc::Nn1State) + 255) / 256) * 256; }
+
+int dc_quantile(const double* v, int64_t n, double ratio, const int32_t* stop, double* threshold_out, void* ws, size_t ws_bytes,
+                hipStream_t stream) {
+  if (n < 1 || n > 0x7fffffff || !v || !(ratio >= 0.0 && ratio <= 1.0) || !threshold_out || !ws) return DC_ERR_ARG;
+  if (ws_bytes < dc_quantile_workspace_bytes()) return DC_ERR_WORKSPACE;
+  const hipError_t err = dc::launch_quantile(v, n, ratio, stop, reinterpret_cast<dc::Nn1State*>(ws), threshold_out, stream);
   return err == hipSuccess ? DC_OK : (int)err;
 }
 

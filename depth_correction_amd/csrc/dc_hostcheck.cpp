@@ -4,6 +4,7 @@
 #include "dc_common.h"
 #include "dc_eig3.h"
 #include "dc_pointmath.h"
+#include "dc_slam_math.h"
 
 extern "C" {
 
@@ -88,5 +89,11 @@ double dc_host_model_depth(int kind, int n_terms, const double* w, const double*
 void dc_host_normal_inc(const double* dir, const double* v0, double* normal, double* inc) {
   dc::normal_and_incidence(dir, v0, normal, inc);
 }
+
+// ICP normal equations (dc_slam.hip's finish kernel): a21 = JtJ upper triangle row by row, b6 = Jtr -> x = -(JtJ)^-1 Jtr; 1 = singular
+int dc_host_icp_solve(const double* a21, const double* b6, double* x6) { return dc::icp_solve6(a21, b6, x6); }
+
+// out = [R(x[0:3]) x[3:6]; 0 1] T (row-major 4 x 4): the finish kernel's pose update
+void dc_host_icp_step(const double* x6, const double* T, double* out) { dc::icp_apply_step(x6, T, out); }
 
 }  // extern "C"

@@ -1391,6 +1391,25 @@ __global__ __launch_bounds__(kBlock) void to_f64_kernel(const T* __restrict__ xy
   out[i * 3] = p[0]; out[i * 3 + 1] = p[1]; out[i * 3 + 2] = p[2];
 }
 
+// Queries of dc_knn_grid_query: fp64 [n,3] points moved by the row-major 4 x 4 `pose` (device), x = ((T00 p0 + T01 p1) + T02 p2) + T03
+// rounded in that order (contraction is off in this unit); every query becomes NaN -- a row the search kernels fill with -1 / inf
+// without walking the grid -- once *stop != 0.  Thread 0 also clears the pending-query counter of the search that follows.
+__global__ __launch_bounds__(kBlock) void moved_queries_kernel(const double* __restrict__ q, int64_t n, const double* __restrict__ pose,
+                                                               const int32_t* __restrict__ stop, double* __restrict__ out,
+                                                               int32_t* __restrict__ n_pending) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *n_pending = 0;
+  if (i >= n) return;
+  const bool halt = stop && *stop != 0;
+  const double p[3] = {q[i * 3], q[i * 3 + 1], q[i * 3 + 2]};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double* T = pose + r * 4;
+    const double x = (T[0] * p[0] + T[1] * p[1]) + T[2] * p[2] + T[3];
+    out[i * 3 + r] = halt ? __longlong_as_double(0x7ff8000000000000ll) : x;
+  }
+}
+
 // ---- transposed neighbour list ------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void edge_keys_kernel(const int32_t* __restrict__ nbr, int64_t n_edges, int k,
                                                            int32_t n, uint32_t* __restrict__ keys,
@@ -1792,6 +1811,34 @@ int dc_radius_fill(int64_t n, double r, int kmax, int32_t* idx_out, void* ws, si
   DC_HIP(hipGetLastError());
   if (kmax <= kRadiusSortMax && kmax > 1) { const int rc = launch_radius_sort(idx_out, n, kmax, stream); if (rc) return rc; }
   return DC_OK;
+}
+
+// k-NN against a grid that outlives the call (the SLAM map's, rebuilt only when the map changes): dc_knn_grid_build leaves the grid
+// of `points` in `ws` (dc_knn_workspace_bytes(n, n_query_max)); every dc_knn_grid_query then moves its queries by a device-side pose
+// and searches that grid with the kernels of dc_knn_build -- the same tables as dc_knn_build on the moved points.
+int dc_knn_grid_build(const void* points, int stride, int dtype, int64_t n, int64_t n_query_max, int k, double cell_hint, void* ws,
+                      size_t ws_bytes, hipStream_t stream) {
+  if (!points || n < 1 || n_query_max < 0 || k < 1 || k > 64 || !ws || stride < 3) return DC_ERR_ARG;
+  if (n >= (int64_t)0x7fffffff || n_query_max >= (int64_t)0x7fffffff) return DC_ERR_UNSUPPORTED;
+  GridWs w = carve_grid(ws, n, n_query_max);
+  if (ws_bytes < w.total) return DC_ERR_WORKSPACE;
+  if (dtype == DC_F32) return build_grid((const float*)points, stride, n, k, cell_hint, w, stream);
+  if (dtype == DC_F64) return build_grid((const double*)points, stride, n, k, cell_hint, w, stream);
+  return DC_ERR_DTYPE;
+}
+
+int dc_knn_grid_query(int64_t n, int64_t n_query_max, const double* query, int64_t n_query, const double* pose, const int32_t* stop, int k,
+                      double r, int32_t* idx_out, double* dist_out, void* ws, size_t ws_bytes, hipStream_t stream) {
+  if (n < 1 || n_query < 0 || n_query > n_query_max || k < 1 || k > 64 || !pose || !ws) return DC_ERR_ARG;
+  if (n_query > 0 && (!query || !idx_out)) return DC_ERR_ARG;
+  GridWs w = carve_grid(ws, n, n_query_max);
+  if (ws_bytes < w.total) return DC_ERR_WORKSPACE;
+  if (n_query == 0) return DC_OK;
+  CellTable tab{w.tab_key, w.tab_s, w.tab_n - 1};
+  hipLaunchKernelGGL(moved_queries_kernel, dim3((unsigned)((n_query + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, query, n_query, pose,
+                     stop, w.qf64, w.n_pending);
+  return launch_knn(k, w.sp, w.sids, n, w.qf64, nullptr, n_query, w.grid, tab, r, idx_out, dist_out, w.pending, w.n_pending, nullptr, nullptr,
+                    stream);
 }
 
 size_t dc_knn_transpose_workspace_bytes(int64_t n, int k) {

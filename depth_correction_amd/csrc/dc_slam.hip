@@ -1,0 +1,245 @@
+// Scan-to-map point-to-plane ICP of the SLAM evaluation (gfx950): a restatement of the reference's mapper configuration
+// (config/slam/icp.yaml, input_filters.yaml, launch/slam.launch; eval.py:214-290 runs it through ROS), not of libpointmatcher.
+// C ABI at the bottom; see include/dc_hip.h.  The algorithm, its deviations and its measured cost are in DESIGN "SLAM evaluation".
+//
+// One ICP iteration on the device, with nothing returned to the host in between:
+//   dc_knn_grid_query  (dc_knn.hip)    reading points moved by the device-side estimate, k-NN in the map's grid built earlier;
+//   dc_quantile        (dc_filters.hip) the trimmed threshold: dc_nn1_corr's radix select over the M x knn distance table;
+//   dc_icp_accumulate                   both pair filters, residuals, fp64 block partials of JtJ (21), Jtr (6), pairs, sum r^2,
+//                                       points with a kept pair;
+//   dc_icp_finish                       one block: the partials in block order, the 6 x 6 Cholesky solve, the pose update, the
+//                                       checks and the status word.
+// A registration whose status word is set turns every later launch of these four into an early exit, so the host can queue
+// several iterations and read the status once.  Reductions run in a fixed order and use no atomics: bit-reproducible.
+#include "dc_common.h"
+#include "../../include/dc_hip.h"
+#include "dc_device.h"
+#include "dc_hostutil.h"
+#include "dc_slam_math.h"
+
+namespace dc {
+
+constexpr int kIcpBlocksMax = 512;
+
+static int icp_blocks(int64_t m) {
+  const int64_t b = (m + kBlock - 1) / kBlock;
+  return (int)(b < 1 ? 1 : (b > kIcpBlocksMax ? kIcpBlocksMax : b));
+}
+
+// x = R p + t with the products and sums rounded in this order (dc_knn_grid_query moves the queries with the same arithmetic,
+// so the point a pair is formed with is the point that was matched)
+__device__ __forceinline__ void move_point(const double* T, const double* p, double* x) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    x[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T[r * 4], p[0]), __dmul_rn(T[r * 4 + 1], p[1])), __dmul_rn(T[r * 4 + 2], p[2])),
+                     T[r * 4 + 3]);
+}
+
+__global__ void icp_init_kernel(const double* __restrict__ prior, double* __restrict__ state, int32_t* __restrict__ status) {
+  const int t = threadIdx.x;
+  if (t < 16) { state[DC_ICP_STATE_POSE + t] = prior[t]; state[DC_ICP_STATE_PRIOR + t] = prior[t]; }
+  else if (t < 16 + (DC_ICP_STATE_COUNT - 32)) state[32 + (t - 16)] = 0.0;
+  if (t < 4) status[t] = 0;
+}
+
+__global__ __launch_bounds__(kBlock) void icp_accumulate_kernel(const double* __restrict__ reading, const double* __restrict__ rnormals,
+                                                                int64_t m, const double* __restrict__ map_points,
+                                                                const double* __restrict__ map_normals, const int32_t* __restrict__ idx,
+                                                                const double* __restrict__ dist, int knn, const double* __restrict__ threshold,
+                                                                double cos_min, const double* __restrict__ state,
+                                                                const int32_t* __restrict__ status, double* __restrict__ partials,
+                                                                uint8_t* __restrict__ kept_out) {
+  __shared__ double lds[kWavesPerBlock * DC_ICP_PARTIALS];
+  if (status[0] != 0) return;                       // the registration has ended: nothing to do (block-uniform)
+  double T[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) T[q] = state[DC_ICP_STATE_POSE + q];
+  const double thr = *threshold;
+  double v[DC_ICP_PARTIALS];
+#pragma unroll
+  for (int q = 0; q < DC_ICP_PARTIALS; ++q) v[q] = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) {
+    const double p[3] = {reading[i * 3], reading[i * 3 + 1], reading[i * 3 + 2]};
+    const double pn[3] = {rnormals[i * 3], rnormals[i * 3 + 1], rnormals[i * 3 + 2]};
+    double x[3];
+    move_point(T, p, x);
+    double nr[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) nr[r] = T[r * 4] * pn[0] + T[r * 4 + 1] * pn[1] + T[r * 4 + 2] * pn[2];
+    bool any = false;
+    for (int j = 0; j < knn; ++j) {
+      const int64_t e = i * knn + j;
+      const int32_t id = idx[e];
+      bool keep = id >= 0 && dist[e] <= thr;        // TrimmedDistOutlierFilter (NaN threshold keeps nothing)
+      double n[3] = {0.0, 0.0, 0.0}, y[3] = {0.0, 0.0, 0.0};
+      if (keep) {
+        n[0] = map_normals[(int64_t)id * 3]; n[1] = map_normals[(int64_t)id * 3 + 1]; n[2] = map_normals[(int64_t)id * 3 + 2];
+        y[0] = map_points[(int64_t)id * 3]; y[1] = map_points[(int64_t)id * 3 + 1]; y[2] = map_points[(int64_t)id * 3 + 2];
+        keep = fabs(nr[0] * n[0] + nr[1] * n[1] + nr[2] * n[2]) >= cos_min;     // SurfaceNormalOutlierFilter
+      }
+      if (kept_out) kept_out[e] = keep ? 1 : 0;
+      if (!keep) continue;
+      any = true;
+      const double r = n[0] * (x[0] - y[0]) + n[1] * (x[1] - y[1]) + n[2] * (x[2] - y[2]);
+      const double J[6] = {x[1] * n[2] - x[2] * n[1], x[2] * n[0] - x[0] * n[2], x[0] * n[1] - x[1] * n[0], n[0], n[1], n[2]};
+      int q = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) v[q++] += J[a] * J[b];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) v[21 + a] += J[a] * r;
+      v[27] += 1.0;
+      v[28] += r * r;
+    }
+    if (any) v[29] += 1.0;
+  }
+  block_sum<DC_ICP_PARTIALS>(v, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < DC_ICP_PARTIALS; ++q) partials[(int64_t)blockIdx.x * DC_ICP_PARTIALS + q] = v[q];
+  }
+}
+
+struct IcpParams {
+  double min_rot, min_trans, max_rot, max_trans;
+  int smooth, max_iters, min_pairs;
+};
+
+// One block: lanes 8 q .. 8 q + 7 sum value q over the blocks b = lane, lane + 8, ... in order, lane 8 q adds the eight sums in
+// order; thread 0 then solves and updates.
+__global__ __launch_bounds__(kBlock) void icp_finish_kernel(const double* __restrict__ partials, int n_blocks, int64_t m, IcpParams prm,
+                                                            double* __restrict__ state, int32_t* __restrict__ status) {
+  __shared__ double s_part[DC_ICP_PARTIALS * 8];
+  __shared__ double s_tot[DC_ICP_PARTIALS];
+  if (status[0] != 0) return;
+  const int t = threadIdx.x;
+  if (t < DC_ICP_PARTIALS * 8) {
+    const int q = t >> 3, l = t & 7;
+    double s = 0.0;
+    for (int b = l; b < n_blocks; b += 8) s += partials[(int64_t)b * DC_ICP_PARTIALS + q];
+    s_part[t] = s;
+  }
+  __syncthreads();
+  if (t < DC_ICP_PARTIALS) {
+    double s = 0.0;
+    for (int l = 0; l < 8; ++l) s += s_part[t * 8 + l];
+    s_tot[t] = s;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  const double* tot = s_tot;
+  double* st = state;
+  const int iter = status[1] + 1;
+  status[1] = iter;
+  st[DC_ICP_STATE_PAIRS] = tot[27];
+  st[DC_ICP_STATE_SSE] = tot[28];
+  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[29] / (double)m : 0.0;
+  if (tot[27] < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
+  double x[6];
+  if (icp_solve6(tot, tot + 21, x)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
+  double Tn[16];
+  icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
+  bool finite = true;
+  for (int q = 0; q < 6; ++q) finite = finite && isfinite(x[q]);
+  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
+  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  double C[16];
+  rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);            // the total correction relative to the prior (BoundTransformationChecker)
+  const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
+  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
+  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
+  // DifferentialTransformationChecker: the mean rotation / translation of the last `smooth` increments
+  const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
+  st[DC_ICP_STATE_HIST_ROT + slot] = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  st[DC_ICP_STATE_HIST_TRANS + slot] = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
+  if (iter >= prm.smooth) {
+    double mr = 0.0, mt = 0.0;
+    for (int h = 0; h < prm.smooth; ++h) {
+      const int s = (iter - 1 - h) % DC_ICP_MAX_SMOOTH;
+      mr += st[DC_ICP_STATE_HIST_ROT + s];
+      mt += st[DC_ICP_STATE_HIST_TRANS + s];
+    }
+    mr /= (double)prm.smooth;
+    mt /= (double)prm.smooth;
+    if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
+  }
+  if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;      // CounterTransformationChecker: stop, keep the estimate
+}
+
+// Reading points the map takes: world coordinates and normals of every point, mask = nearest map point farther than min_dist
+// (dist1 NULL: an empty map) and depth <= max_range.
+__global__ __launch_bounds__(kBlock) void map_select_kernel(const double* __restrict__ reading, const double* __restrict__ rnormals,
+                                                            const double* __restrict__ depth, int64_t m, const double* __restrict__ pose,
+                                                            const double* __restrict__ dist1, double min_dist, double max_range,
+                                                            uint8_t* __restrict__ mask, double* __restrict__ pts_out,
+                                                            double* __restrict__ nrm_out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m) return;
+  double T[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) T[q] = pose[q];
+  const double p[3] = {reading[i * 3], reading[i * 3 + 1], reading[i * 3 + 2]};
+  const double pn[3] = {rnormals[i * 3], rnormals[i * 3 + 1], rnormals[i * 3 + 2]};
+  double x[3];
+  move_point(T, p, x);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    pts_out[i * 3 + r] = x[r];
+    nrm_out[i * 3 + r] = T[r * 4] * pn[0] + T[r * 4 + 1] * pn[1] + T[r * 4 + 2] * pn[2];
+  }
+  const double d = dist1 ? dist1[i] : INFINITY;
+  mask[i] = (d > min_dist && depth[i] <= max_range) ? 1 : 0;
+}
+
+}  // namespace dc
+
+using namespace dc;
+
+extern "C" {
+
+int dc_icp_blocks(int64_t m) { return m < 0 ? 0 : icp_blocks(m); }
+
+int dc_icp_init(const double* prior, double* state, int32_t* status, hipStream_t stream) {
+  if (!prior || !state || !status) return DC_ERR_ARG;
+  hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, stream, prior, state, status);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_icp_accumulate(const double* reading, const double* normals, int64_t m, const double* map_points, const double* map_normals,
+                      const int32_t* idx, const double* dist, int knn, const double* threshold, double cos_min, const double* state,
+                      const int32_t* status, double* partials, int n_blocks, uint8_t* kept_out, hipStream_t stream) {
+  if (m < 1 || knn < 1 || knn > 64 || !reading || !normals || !map_points || !map_normals || !idx || !dist || !threshold || !state ||
+      !status || !partials)
+    return DC_ERR_ARG;
+  if (m >= (int64_t)0x7fffffff / knn) return DC_ERR_UNSUPPORTED;
+  if (n_blocks != icp_blocks(m)) return DC_ERR_WORKSPACE;
+  hipLaunchKernelGGL(icp_accumulate_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, reading, normals, m, map_points, map_normals,
+                     idx, dist, knn, threshold, cos_min, state, status, partials, kept_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_icp_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
+                  double max_rot, double max_trans, int min_pairs, double* state, int32_t* status, hipStream_t stream) {
+  if (!partials || !state || !status || n_blocks < 1 || n_blocks > kIcpBlocksMax || m < 0) return DC_ERR_ARG;
+  if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1) return DC_ERR_ARG;
+  IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
+  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(kBlock), 0, stream, partials, n_blocks, m, prm, state, status);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_map_select(const double* reading, const double* normals, const double* depth, int64_t m, const double* pose, const double* dist1,
+                  double min_dist, double max_range, uint8_t* mask_out, double* points_out, double* normals_out, hipStream_t stream) {
+  if (m == 0) return DC_OK;
+  if (m < 0 || !reading || !normals || !depth || !pose || !mask_out || !points_out || !normals_out) return DC_ERR_ARG;
+  hipLaunchKernelGGL(map_select_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, reading, normals, depth, m,
+                     pose, dist1, min_dist, max_range, mask_out, points_out, normals_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+}  // extern "C"

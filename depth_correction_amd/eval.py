@@ -6,7 +6,8 @@ offsets / distance weights, any of the reference's models or none) every sequenc
 ``SequencePlan`` -- one to three kernel launches -- and the returned loss carries the hand-derived backward to
 ``model.w`` / ``model.exponent`` / the pose corrections.  Any other configuration goes through the un-fused DepthCloud operators with identical results.
 
-``eval_loss`` / ``eval_loss_all`` are the reference's test-set evaluation (eval.py:115-211).  ``landscape_clouds`` evaluates
+``eval_loss`` / ``eval_loss_all`` are the reference's test-set evaluation (eval.py:115-211); ``eval_slam`` / ``eval_slam_all`` its
+localization-accuracy evaluation (eval.py:214-290) with this package's ICP mapper instead of ROS (slam.py).  ``landscape_clouds`` evaluates
 the loss for many candidate weights of the model at once: every model with a basis form is affine in its weights, so a
 neighbourhood's covariance is a quadratic form in w and one pass over the neighbours (dc_sequence_landscape) serves every
 row; configurations outside that path loop over ``eval_loss_clouds`` ("Loss landscape").
@@ -19,14 +20,14 @@ from collections import Counter
 import numpy as np
 import torch
 
-from .config import Config, NeighborhoodType, PoseCorrection, loss_eval_csv, nonempty
+from .config import SLAM, Config, NeighborhoodType, PoseCorrection, loss_eval_csv, nonempty, slam_eval_csv
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry, SequencePlan, consistency_loss
 from .preproc import (compute_neighborhood_features, global_cloud, global_cloud_mask, local_feature_cloud,
                       offset_cloud)
 from .transform import corrected_poses, xyz_axis_angle_to_matrix
 
-__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape',
+__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape', 'eval_slam', 'eval_slam_all',
            'initialize_pose_corrections', 'fused_supported', 'landscape_clouds', 'landscape_paths', 'PlanCloud', 'LazyFeatureCloud']
 
 
@@ -288,6 +289,62 @@ def eval_loss_all(cfg: Config):
             eval_cfg.loss = loss
             eval_cfg.loss_eval_csv = loss_eval_csv(cfg.log_dir, loss, suffix)
             eval_loss(cfg=eval_cfg)
+
+
+def eval_slam(cfg: Config, test_datasets=None, model=None):
+    """SLAM accuracy on the test sequences (eval.py:214-260 with scripts/robot_data:176-204): each sequence's scans go through the
+    depth and grid filters, the correction by ``model`` (from the configuration unless given, as slam_eval.launch runs the
+    correction node) and the mapper of ``cfg.slam``, fed with the odometry of ``cfg.odom_cov``.  Appends
+    ``name r_angle t_norm rel_angle rel_offset`` to ``cfg.slam_eval_csv``; writes the SLAM poses to ``cfg.slam_poses_csv`` when
+    set (one sequence only).  Returns the per-sequence results of slam.run_slam with their ``errors``."""
+    import os
+    from .io import append
+    from .scan_io import write_poses_csv
+    from .slam import run_slam, slam_errors
+    if cfg.slam not in SLAM:
+        raise ValueError('SLAM pipeline %r is not available here; available: %s' % (cfg.slam, ', '.join(SLAM)))
+    assert cfg.slam_eval_csv
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    assert not cfg.slam_poses_csv or len(test_names) == 1
+    if cfg.slam_eval_bag:
+        print('slam_eval_bag %s ignored: no bag is recorded.' % cfg.slam_eval_bag)
+    results = []
+    for name, ds in zip(test_names, test_datasets):
+        print('SLAM evaluation on %s started.' % name)
+        res = run_slam(ds, model, cfg)
+        r_angle, t_norm, rel_angle, rel_offset = res['errors'] = slam_errors(res['slam'], res['gt'], res['path_lengths'])
+        print('Average error: rot. %.6f deg. (%.3f deg/m), transl. %.6f m (%.3f %%).'
+              % (np.degrees(r_angle), np.degrees(rel_angle), t_norm, 100. * rel_offset))
+        append(cfg.slam_eval_csv, '%s %.9f %.9f %.9f %.9f\n' % (name, r_angle, t_norm, rel_angle, rel_offset))
+        if cfg.slam_poses_csv:
+            if os.path.exists(cfg.slam_poses_csv):
+                print('File with SLAM poses already exists: %s. It will be overwritten.' % cfg.slam_poses_csv)
+            os.makedirs(os.path.dirname(os.path.abspath(cfg.slam_poses_csv)), exist_ok=True)
+            write_poses_csv(res['ids'], res['slam'], cfg.slam_poses_csv)
+        print('SLAM evaluation on %s finished.' % name)
+        results.append(res)
+    return results
+
+
+def eval_slam_all(cfg: Config):
+    """Every SLAM pipeline of ``cfg.eval_slams`` on the train, val and test subsets with ground-truth poses, one CSV file per pipeline
+    and subset, no bag and no poses file (eval.py:263-290)."""
+    out = {}
+    for names, suffix in zip([cfg.train_names, cfg.val_names, cfg.test_names], ['train', 'val', 'test']):
+        if not names:
+            continue
+        for slam in cfg.eval_slams:
+            eval_cfg = cfg.copy()
+            eval_cfg.test_names = names
+            eval_cfg.train_poses_path = []
+            eval_cfg.val_poses_path = []
+            eval_cfg.test_poses_path = []
+            eval_cfg.slam = slam
+            eval_cfg.slam_eval_bag = ''
+            eval_cfg.slam_eval_csv = slam_eval_csv(cfg.log_dir, slam, suffix)
+            eval_cfg.slam_poses_csv = ''
+            out[(slam, suffix)] = eval_slam(cfg=eval_cfg)
+    return out
 
 
 # ---- loss landscape over the model weights --------------------------------------------------------------------------------

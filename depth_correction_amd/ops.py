@@ -17,6 +17,7 @@ __all__ = [
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast',
+    'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
 ]
 
 
@@ -1088,3 +1089,131 @@ def raycast(bvh, dirs, poses, t_min, cull=True):
                            ptr(dirs), ptr(t_min), r, ptr(poses), p, 1 if cull else 0, ptr(face), ptr(t), ptr(bary), stream_ptr()),
           'dc_raycast')
     return face, t, bary
+
+
+# ------------------------------------------------------------------------------------------------
+# SLAM evaluation: scan-to-map point-to-plane ICP (csrc/dc_slam.hip, slam.py).  The per-iteration wrappers take every output and
+# workspace from the caller, so a queue of iterations allocates nothing and copies nothing.
+# ------------------------------------------------------------------------------------------------
+class KnnGrid(object):
+    """A k-NN grid of ``n`` points kept in ``ws`` for later queries of at most ``n_query_max`` points (dc_knn_grid_build)."""
+
+    def __init__(self, ws, n, n_query_max, device):
+        self.ws, self.n, self.n_query_max, self.device = ws, n, n_query_max, device
+
+
+@on_device
+def knn_grid_build(points, n_query_max, k, cell_hint=0.0, ws=None):
+    """Grid of points [N,3] (N >= 1) for k-NN queries of up to ``n_query_max`` points; ``ws`` (uint8, optional) is reused when large
+    enough (dc_knn_grid_build)."""
+    need(points, (None, 3), name='points')
+    n = points.shape[0]
+    if n < 1:
+        raise ValueError('knn_grid_build needs at least one point')
+    nbytes = lib().dc_knn_workspace_bytes(n, n_query_max)
+    if ws is None or ws.numel() < nbytes or ws.device != points.device:
+        ws = _ws(nbytes, points.device)
+    check(lib().dc_knn_grid_build(ptr(points), 3, dtype_code(points), n, int(n_query_max), int(k), float(cell_hint), ptr(ws), ws.numel(),
+                                  stream_ptr()), 'dc_knn_grid_build')
+    return KnnGrid(ws, n, int(n_query_max), points.device)
+
+
+@on_device
+def knn_grid_query(grid, query, pose, k, r=None, stop=None, idx=None, dist=None):
+    """k-NN of ``pose @ query`` (query f64 [M,3], pose f64 device [4,4]) in ``grid`` -> (dist f64 [M,k], idx i32 [M,k]), written into
+    ``idx`` / ``dist`` when given; ``stop`` (int32 device word): rows -1 / inf once it is non-zero (dc_knn_grid_query)."""
+    need(query, (None, 3), dtype=torch.float64, name='query', device=grid.device)
+    need(pose, (4, 4), dtype=torch.float64, name='pose', device=grid.device)
+    m = query.shape[0]
+    if m > grid.n_query_max:
+        raise ValueError('%d queries, the grid was built for %d' % (m, grid.n_query_max))
+    idx = torch.empty((m, k), dtype=torch.int32, device=grid.device) if idx is None else need(idx, (m, k), torch.int32, 'idx', grid.device)
+    dist = torch.empty((m, k), dtype=torch.float64, device=grid.device) if dist is None else need(dist, (m, k), torch.float64, 'dist',
+                                                                                                  grid.device)
+    if stop is not None:
+        need(stop, None, dtype=torch.int32, name='stop', device=grid.device)
+    check(lib().dc_knn_grid_query(grid.n, grid.n_query_max, ptr(query), m, ptr(pose), ptr(stop), int(k), float(r) if r else 0.0,
+                                  ptr(idx), ptr(dist), ptr(grid.ws), grid.ws.numel(), stream_ptr()), 'dc_knn_grid_query')
+    return dist, idx
+
+
+@on_device
+def quantile(v, ratio, stop=None, out=None, ws=None):
+    """np.quantile(v[~isnan(v)], ratio) of non-negative v (f64, any shape) as a device f64 [1] (``out`` when given), by dc_nn1_corr's
+    radix select; ``stop`` as in knn_grid_query (dc_quantile)."""
+    need(v, None, dtype=torch.float64, name='v')
+    n = v.numel()
+    nbytes = lib().dc_quantile_workspace_bytes()
+    ws = _ws(nbytes, v.device) if ws is None else ws
+    out = torch.empty((1,), dtype=torch.float64, device=v.device) if out is None else need(out, (1,), torch.float64, 'out', v.device)
+    check(lib().dc_quantile(ptr(v), n, float(ratio), ptr(stop), ptr(out), ptr(ws), ws.numel(), stream_ptr()), 'dc_quantile')
+    return out
+
+
+def icp_blocks(m):
+    """Blocks (rows of partials) of icp_accumulate for m reading points (dc_icp_blocks)."""
+    return int(lib().dc_icp_blocks(int(m)))
+
+
+@on_device
+def icp_init(prior, state, status):
+    """state f64 [DC_ICP_STATE_COUNT] / status i32 [4] of a registration that starts from prior f64 device [4,4] (dc_icp_init)."""
+    need(prior, (4, 4), dtype=torch.float64, name='prior')
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=prior.device)
+    need(status, (4,), dtype=torch.int32, name='status', device=prior.device)
+    check(lib().dc_icp_init(ptr(prior), ptr(state), ptr(status), stream_ptr()), 'dc_icp_init')
+
+
+@on_device
+def icp_accumulate(reading, normals, map_points, map_normals, idx, dist, threshold, cos_min, state, status, partials, kept=None):
+    """Filtered point-to-plane pairs of one ICP iteration -> block partials f64 [icp_blocks(M), DC_ICP_PARTIALS] (dc_icp_accumulate);
+    ``kept`` (uint8 [M,k], optional) receives the kept flags."""
+    dev = reading.device
+    need(reading, (None, 3), dtype=torch.float64, name='reading')
+    m = reading.shape[0]
+    need(normals, (m, 3), dtype=torch.float64, name='normals', device=dev)
+    need(map_points, (None, 3), dtype=torch.float64, name='map_points', device=dev)
+    need(map_normals, tuple(map_points.shape), dtype=torch.float64, name='map_normals', device=dev)
+    need(idx, (m, None), dtype=torch.int32, name='idx', device=dev)
+    k = idx.shape[1]
+    need(dist, (m, k), dtype=torch.float64, name='dist', device=dev)
+    need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    nb = icp_blocks(m)
+    need(partials, (nb, nv.DC_ICP_PARTIALS), dtype=torch.float64, name='partials', device=dev)
+    if kept is not None:
+        need(kept, (m, k), dtype=torch.uint8, name='kept', device=dev)
+    check(lib().dc_icp_accumulate(ptr(reading), ptr(normals), m, ptr(map_points), ptr(map_normals), ptr(idx), ptr(dist), k, ptr(threshold),
+                                  float(cos_min), ptr(state), ptr(status), ptr(partials), nb, ptr(kept), stream_ptr()), 'dc_icp_accumulate')
+
+
+@on_device
+def icp_finish(partials, m, state, status, min_rot, min_trans, smooth, max_iters, max_rot, max_trans, min_pairs=6):
+    """Solve, update and check one ICP iteration in one block (dc_icp_finish)."""
+    dev = partials.device
+    need(partials, (None, nv.DC_ICP_PARTIALS), dtype=torch.float64, name='partials')
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    check(lib().dc_icp_finish(ptr(partials), partials.shape[0], int(m), float(min_rot), float(min_trans), int(smooth), int(max_iters),
+                              float(max_rot), float(max_trans), int(min_pairs), ptr(state), ptr(status), stream_ptr()), 'dc_icp_finish')
+
+
+@on_device
+def map_select(reading, normals, depth, pose, dist1, min_dist, max_range):
+    """(mask bool [M], points f64 [M,3], normals f64 [M,3]): reading points and normals moved by pose f64 device [4,4] and the mask of
+    those the map takes -- nearest map point (dist1 [M]; None = empty map) beyond min_dist, depth <= max_range (dc_map_select)."""
+    dev = reading.device
+    need(reading, (None, 3), dtype=torch.float64, name='reading')
+    m = reading.shape[0]
+    need(normals, (m, 3), dtype=torch.float64, name='normals', device=dev)
+    need(depth, (m,), dtype=torch.float64, name='depth', device=dev)
+    need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    if dist1 is not None:
+        need(dist1, (m,), dtype=torch.float64, name='dist1', device=dev)
+    mask = torch.empty((m,), dtype=torch.uint8, device=dev)
+    pts = torch.empty((m, 3), dtype=torch.float64, device=dev)
+    nrm = torch.empty((m, 3), dtype=torch.float64, device=dev)
+    check(lib().dc_map_select(ptr(reading), ptr(normals), ptr(depth), m, ptr(pose), ptr(dist1), float(min_dist), float(max_range),
+                              ptr(mask), ptr(pts), ptr(nrm), stream_ptr()), 'dc_map_select')
+    return mask.view(torch.bool), pts, nrm

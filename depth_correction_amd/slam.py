@@ -1,0 +1,302 @@
+"""SLAM evaluation without ROS: the perturbed odometry and the metric of scripts/robot_data:123-204 and a scan-to-map point-to-plane
+ICP mapper configured like the reference's norlab_icp_mapper (config/slam/icp.yaml, input_filters.yaml, launch/slam.launch).
+
+The mapper is a restatement of that configuration, not libpointmatcher; DESIGN "SLAM evaluation" states the algorithm and its
+deviations.  Its device state is the map (points and the normals of the scans they came from), the map's k-NN grid and one
+registration's state; an ICP iteration runs on the device without the host (csrc/dc_slam.hip), which reads one status word every
+``status_every`` iterations.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _native as nv
+from . import ops
+from .config import Config, SLAM
+from .utils import delta_transform, rotation_angle, translation_norm
+
+__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'mapper_input', 'odometry_cov', 'odometry_poses', 'path_lengths',
+           'run_slam', 'slam_errors']
+
+# launches of one ICP iteration: dc_knn_grid_query 3 (moved queries, the 16-lanes-per-query search, the tail search), dc_quantile 18
+# (a state memset, 8 x histogram + pick, next value, threshold), dc_icp_accumulate 1, dc_icp_finish 1
+LAUNCHES_PER_ITERATION = 23
+FAILED = ('empty', 'too_few_pairs', 'singular', 'not_finite', 'bound')
+
+
+def odometry_cov(odom_cov):
+    """The 6 x 6 covariance of the odometry noise from the forms robot_data:56-68 accepts: a scalar (every variance), [rot, trans],
+    six variances (the diagonal) or a 6 x 6 matrix; None = no noise."""
+    if odom_cov is None:
+        return None
+    if isinstance(odom_cov, str):
+        import yaml
+        odom_cov = yaml.safe_load(odom_cov)
+    if isinstance(odom_cov, (int, float)):
+        odom_cov = 6 * [float(odom_cov)]
+    cov = np.asarray(odom_cov, dtype=np.float64)
+    if cov.shape == (2,):
+        cov = np.array(3 * [cov[0]] + 3 * [cov[1]])
+    if cov.shape == (6,):
+        cov = np.diag(cov)
+    if cov.shape != (6, 6):
+        raise ValueError('odom_cov must be a scalar, 2 or 6 variances or a 6 x 6 matrix, got shape %s' % (cov.shape,))
+    return cov
+
+
+def odometry_poses(gt_poses, odom_cov, seed=135):
+    """Odometry of robot_data.precompute_poses / random_transform: odom[0] = gt[0], odom[i] = odom[i-1] delta(gt[i-1], gt[i]) T(noise_i)
+    with noise_i ~ N(0, odom_cov) drawn from default_rng(seed) and T = euler_matrix(*noise[:3]) with noise[3:] as translation."""
+    from .dataset import euler_matrix
+    gt = np.asarray(gt_poses, dtype=np.float64)
+    cov = odometry_cov(odom_cov)
+    rng = np.random.default_rng(seed)
+    odom = gt.copy()
+    for i in range(1, len(gt)):
+        delta = delta_transform(gt[i - 1], gt[i])
+        if cov is not None:
+            noise = rng.multivariate_normal(np.zeros((6,)), cov)
+            T = euler_matrix(*noise[:3])
+            T[:3, 3] = noise[3:]
+            delta = np.matmul(delta, T)
+        odom[i] = np.matmul(odom[i - 1], delta)
+    return odom
+
+
+def path_lengths(gt_poses):
+    """Travelled distance at every pose (robot_data:127-141): 0, then the sum of the ground-truth steps' translation norms."""
+    gt = np.asarray(gt_poses, dtype=np.float64)
+    out = [0.0]
+    for i in range(1, len(gt)):
+        out.append(out[i - 1] + translation_norm(delta_transform(gt[i - 1], gt[i])))
+    return np.asarray(out)
+
+
+def slam_errors(slam_poses, gt_poses, lengths):
+    """(r_angle, t_norm, rel_angle, rel_offset): the means over every pose, index 0 included, of robot_data.evaluate_pose's errors of
+    delta(slam, gt); the relative ones divide by the path length and are 0 where it is 0 (robot_data:153-187)."""
+    r, t, ra, ro = [], [], [], []
+    for slam, gt, length in zip(slam_poses, gt_poses, lengths):
+        delta = delta_transform(slam, gt)
+        r_angle, t_norm = rotation_angle(delta), translation_norm(delta)
+        r.append(r_angle)
+        t.append(t_norm)
+        ra.append(r_angle / length if length > 0. else 0.)
+        ro.append(t_norm / length if length > 0. else 0.)
+    return tuple(float(np.mean(v)) for v in (r, t, ra, ro))
+
+
+def mapper_input(cloud, model, cfg: Config):
+    """One scan as the mapper receives it (launch/slam_eval.launch): the depth and grid filters of cfg, then, with a model, the
+    correction node (online.correct_cloud).  A DepthCloud in the sensor frame."""
+    from .depth_cloud import DepthCloud
+    from .online import correct_cloud
+    from .preproc import filtered_cloud
+    cloud = filtered_cloud(cloud, cfg)
+    if model is not None:
+        return correct_cloud(cloud, model, cfg)
+    if isinstance(cloud, DepthCloud):
+        return cloud
+    return DepthCloud.from_structured_array(cloud, dtype=np.float64, device=cfg.device)
+
+
+class MapperScan(object):
+    """A reading as the ICP uses it: points fp64 [M,3] in the sensor frame, their normals [M,3] (k nearest neighbours inside the scan,
+    oriented toward the sensor: input_filters.yaml) and depths [M]."""
+
+    def __init__(self, points, normals, depth):
+        self.points, self.normals, self.depth = points, normals, depth
+
+    def __len__(self):
+        return self.points.shape[0]
+
+
+class IcpMapper(object):
+    """Scan-to-map point-to-plane ICP and map of the reference's mapper configuration (see DESIGN "SLAM evaluation").
+
+    ``register(scan, prior)`` -> (pose, info): the registered pose (the prior when the registration fails: info['ok'] is False) and
+    info (status, iterations, overlap, pairs, sse); ``update(scan, pose, overlap=None)`` adds the reading points that are new to the
+    map; ``map_points()`` -> (points, normals) of the map."""
+
+    def __init__(self, cfg: Config, device=None, status_every=4):
+        if not (1 <= int(cfg.icp_smooth_length) <= nv.DC_ICP_MAX_SMOOTH):
+            raise ValueError('icp_smooth_length must be in 1..%d' % nv.DC_ICP_MAX_SMOOTH)
+        self.cfg = cfg
+        self.device = torch.device(device or cfg.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('IcpMapper runs on the GPU (depth_correction_amd has no CPU path)')
+        self.status_every = max(1, int(status_every))
+        self.knn = int(cfg.icp_knn)
+        self.n_map = 0
+        self._pts = torch.empty((0, 3), dtype=torch.float64, device=self.device)
+        self._nrm = torch.empty((0, 3), dtype=torch.float64, device=self.device)
+        self.grid = None
+        self.grid_builds = 0
+        self.state = torch.zeros((nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, device=self.device)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=self.device)
+        self.host_reads = 0            # status reads of the last registration
+        self.quantile_ws = torch.empty((max(int(nv.lib().dc_quantile_workspace_bytes()), 1),), dtype=torch.uint8, device=self.device)
+
+    # ---- input --------------------------------------------------------------------------------------------------------------
+    def prepare(self, cloud):
+        """MapperScan of a DepthCloud / points (sensor frame): fp64 points, k = cfg.slam_normals_k normals oriented toward the sensor
+        (computed here even when a correction computed normals of its own), depths."""
+        from .depth_cloud import DepthCloud
+        if isinstance(cloud, MapperScan):
+            return cloud
+        if isinstance(cloud, DepthCloud):
+            pts = cloud.get_points().detach().to(device=self.device, dtype=torch.float64).contiguous()
+            vps = cloud.vps.detach().to(device=self.device, dtype=torch.float64).expand_as(pts).contiguous()
+        else:
+            if getattr(getattr(cloud, 'dtype', None), 'names', None):
+                cloud = DepthCloud.from_structured_array(cloud, dtype=np.float64, device=self.device)
+                return self.prepare(cloud)
+            pts = torch.as_tensor(cloud, dtype=torch.float64, device=self.device).reshape(-1, 3).contiguous()
+            vps = torch.zeros_like(pts)
+        m = pts.shape[0]
+        if m == 0:
+            z = torch.empty((0, 3), dtype=torch.float64, device=self.device)
+            return MapperScan(z, z.clone(), torch.empty((0,), dtype=torch.float64, device=self.device))
+        dc = DepthCloud.from_points(pts, vps=vps, dtype=torch.float64, device=self.device)
+        dc.update_all(k=min(int(self.cfg.slam_normals_k), m))
+        normals = torch.nan_to_num(dc.normals.detach(), nan=0.0).to(torch.float64).contiguous()
+        depth = dc.depth.detach().reshape(-1).to(torch.float64).contiguous()
+        return MapperScan(pts, normals, depth)
+
+    # ---- registration ---------------------------------------------------------------------------------------------------------
+    def _info(self, status, iterations=0, overlap=0.0, pairs=0, sse=0.0):
+        return dict(status=status, ok=status not in FAILED, iterations=iterations, overlap=overlap, pairs=pairs, sse=sse,
+                    host_reads=self.host_reads, launches_per_iteration=LAUNCHES_PER_ITERATION)
+
+    def register(self, scan, prior):
+        """Pose of ``scan`` in the map from ``prior`` (4 x 4): ICP iterations queued ``status_every`` at a time, one status read
+        after each group.  An empty scan or failed registration returns the prior; an empty map returns the prior with status
+        'init' (the first scan initialises the map)."""
+        cfg = self.cfg
+        scan = self.prepare(scan)
+        prior = np.asarray(prior, dtype=np.float64).reshape(4, 4)
+        self.host_reads = 0
+        m = len(scan)
+        if m == 0:
+            return prior.copy(), self._info('empty')
+        if self.n_map == 0:
+            return prior.copy(), self._info('init')
+        self._ensure_grid(m)
+        dev, k = self.device, self.knn
+        prior_d = torch.as_tensor(prior, device=dev)
+        idx = torch.empty((m, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((m, k), dtype=torch.float64, device=dev)
+        thr = torch.empty((1,), dtype=torch.float64, device=dev)
+        partials = torch.empty((ops.icp_blocks(m), nv.DC_ICP_PARTIALS), dtype=torch.float64, device=dev)
+        pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
+        map_pts, map_nrm = self._pts[:self.n_map], self._nrm[:self.n_map]
+        cos_min = float(np.cos(cfg.icp_max_normal_angle))
+        ops.icp_init(prior_d, self.state, self.status)
+        done = 0
+        code = 0
+        while done < cfg.icp_max_iters:
+            for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
+                self.iteration(scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min)
+                done += 1
+            st = self.status.cpu()
+            self.host_reads += 1
+            code = int(st[0])
+            if code != 0:
+                break
+        st = self.state.cpu().numpy()
+        iters = int(self.status[1].item())
+        info = self._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
+                          float(st[nv.DC_ICP_STATE_SSE]))
+        if not info['ok']:
+            return prior.copy(), info
+        return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+
+    def iteration(self, scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, kept=None):
+        """One ICP iteration, queued on the stream: match, trimmed threshold, pairs and partials, solve and update."""
+        cfg = self.cfg
+        ops.knn_grid_query(self.grid, scan.points, pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx, dist=dist)
+        ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
+        ops.icp_accumulate(scan.points, scan.normals, map_pts, map_nrm, idx, dist, thr, cos_min, self.state, self.status, partials,
+                           kept=kept)
+        ops.icp_finish(partials, len(scan), self.state, self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans, cfg.icp_smooth_length,
+                       cfg.icp_max_iters, cfg.icp_max_rotation, cfg.icp_max_translation)
+
+    # ---- map ------------------------------------------------------------------------------------------------------------------
+    def _ensure_grid(self, m):
+        if self.grid is not None and self.grid.n == self.n_map and self.grid.n_query_max >= m:
+            return
+        n_query_max = max(m, self.grid.n_query_max if self.grid is not None else 0)
+        self.grid = ops.knn_grid_build(self._pts[:self.n_map], n_query_max, self.knn,
+                                       ws=self.grid.ws if self.grid is not None else None)
+        self.grid_builds += 1
+
+    def update(self, scan, pose, overlap=None):
+        """Add the reading points of ``scan`` at ``pose`` whose nearest map point is farther than cfg.slam_min_dist_new_point and whose
+        depth is <= cfg.slam_sensor_max_range -- unless ``overlap`` (of its registration) is >= cfg.slam_min_overlap.  The first scan
+        initialises the map.  Returns the number of points added; the map's grid is rebuilt when it changes."""
+        cfg = self.cfg
+        scan = self.prepare(scan)
+        m = len(scan)
+        if m == 0 or (self.n_map > 0 and overlap is not None and overlap >= cfg.slam_min_overlap):
+            return 0
+        pose_d = torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(4, 4), device=self.device)
+        dist1 = None
+        if self.n_map > 0:
+            self._ensure_grid(m)
+            dist1, _ = ops.knn_grid_query(self.grid, scan.points, pose_d, 1)
+            dist1 = dist1.reshape(-1)
+        mask, pts, nrm = ops.map_select(scan.points, scan.normals, scan.depth, pose_d, dist1, cfg.slam_min_dist_new_point,
+                                        cfg.slam_sensor_max_range)
+        new_pts, new_nrm = ops.compact_rows(mask, [pts, nrm])
+        added = new_pts.shape[0]
+        if added == 0:
+            return 0
+        need = self.n_map + added
+        if need > self._pts.shape[0]:
+            cap = max(need, 2 * self._pts.shape[0])
+            for name in ('_pts', '_nrm'):
+                old = getattr(self, name)
+                grown = torch.empty((cap, 3), dtype=torch.float64, device=self.device)
+                grown[:self.n_map] = old[:self.n_map]
+                setattr(self, name, grown)
+        self._pts[self.n_map:need] = new_pts
+        self._nrm[self.n_map:need] = new_nrm
+        self.n_map = need
+        self._ensure_grid(m)
+        return added
+
+    def map_points(self):
+        """(points, normals) fp64 [N,3] of the map (world frame)."""
+        return self._pts[:self.n_map], self._nrm[:self.n_map]
+
+
+def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
+    """The mapper over one sequence with the perturbed odometry of cfg.odom_cov (robot_data): prior[i] = slam[i-1] odom[i-1]^-1 odom[i],
+    slam[0] = odom[0] = gt[0]; a failed registration keeps its prior and leaves the map as it is.  Returns dict(slam, odom, gt
+    [N,4,4], path_lengths [N], info [N dicts], ids)."""
+    if cfg.slam not in SLAM:
+        raise ValueError('unknown SLAM pipeline %r; available: %s' % (cfg.slam, ', '.join(SLAM)))
+    items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in dataset]
+    gt = np.stack([pose for _, pose in items]) if items else np.zeros((0, 4, 4))
+    odom = odometry_poses(gt, cfg.odom_cov)
+    lengths = path_lengths(gt)
+    mapper = mapper or IcpMapper(cfg)
+    slam = odom.copy()
+    infos = []
+    for i, (cloud, _) in enumerate(items):
+        prior = odom[0] if i == 0 else np.matmul(slam[i - 1], delta_transform(odom[i - 1], odom[i]))
+        scan = mapper.prepare(mapper_input(cloud, model, cfg))
+        pose, info = mapper.register(scan, prior)
+        if info['ok']:
+            info['added'] = mapper.update(scan, pose, overlap=info['overlap'] if info['status'] != 'init' else None)
+        else:
+            print('SLAM: registration of scan %d failed (%s); keeping the odometry prior.' % (i, info['status']))
+            info['added'] = 0
+        info['map_size'] = mapper.n_map
+        slam[i] = pose
+        infos.append(info)
+        if verbose:
+            print('scan %d: %s' % (i, info))
+    ids = list(getattr(dataset, 'ids', range(len(items))))
+    return dict(slam=slam, odom=odom, gt=gt, path_lengths=lengths, info=infos, ids=ids)

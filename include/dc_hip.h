@@ -809,6 +809,68 @@ int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_t
                const double* dirs, const double* t_min, int64_t n_rays, const double* poses, int n_poses, int cull, int32_t* face_out,
                double* t_out, double* bary_out, dcStream_t stream);
 
+/* ---- SLAM evaluation: scan-to-map point-to-plane ICP (depth_correction_amd/csrc/dc_slam.hip; algorithm and deviations in DESIGN
+ * "SLAM evaluation"), what eval.py:214-290 eval_slam runs through ROS and norlab_icp_mapper with config/slam/icp.yaml,
+ * input_filters.yaml and launch/slam.launch.  One iteration = dc_knn_grid_query + dc_quantile + dc_icp_accumulate + dc_icp_finish,
+ * nothing returned to the host in between; once the status word is set every later launch of the four returns at once. ---- */
+#ifndef DC_ICP_STATE_COUNT
+#define DC_ICP_STATE_COUNT 64       /* doubles of a registration's device state: */
+#define DC_ICP_STATE_POSE 0         /*   [16] the estimate, row-major 4 x 4 (world from sensor) */
+#define DC_ICP_STATE_PRIOR 16       /*   [16] the prior the bound check measures the correction from */
+#define DC_ICP_STATE_HIST_ROT 32    /*   [8] rotation angles of the last increments (a ring) */
+#define DC_ICP_STATE_HIST_TRANS 40  /*   [8] their translation norms */
+#define DC_ICP_STATE_PAIRS 48       /*   pairs kept by the last iteration */
+#define DC_ICP_STATE_SSE 49         /*   their sum of squared residuals */
+#define DC_ICP_STATE_OVERLAP 50     /*   fraction of reading points with a kept pair in the last iteration */
+#define DC_ICP_MAX_SMOOTH 8         /* largest smoothLength of the differential check */
+#define DC_ICP_PARTIALS 30          /* doubles per block partial: JtJ upper triangle (21), Jtr (6), pairs, sum r^2, points used */
+/* status word (int32 [4]: code, iterations done, 2 spare): */
+#define DC_ICP_RUNNING 0
+#define DC_ICP_CONVERGED 1          /* DifferentialTransformationChecker */
+#define DC_ICP_MAX_ITERS 2          /* CounterTransformationChecker: the estimate is kept */
+#define DC_ICP_FAIL_PAIRS (-1)      /* fewer kept pairs than min_pairs */
+#define DC_ICP_FAIL_SINGULAR (-2)   /* a Cholesky pivot <= 1e-12 x the largest diagonal entry */
+#define DC_ICP_FAIL_NONFINITE (-3)
+#define DC_ICP_FAIL_BOUND (-4)      /* BoundTransformationChecker: correction from the prior above max_rot / max_trans */
+#endif
+/* Grid of `points` [n, stride] (k-NN cell size for k unless cell_hint > 0) kept in ws (dc_knn_workspace_bytes(n, n_query_max)) for
+ * later queries: the map of the mapper, searched every iteration and rebuilt only when the map changes (KDTreeMatcher). */
+int dc_knn_grid_build(const void* points, int stride, int dtype, int64_t n, int64_t n_query_max, int k, double cell_hint, void* ws,
+                      size_t ws_bytes, dcStream_t stream);
+/* k-NN (dc_knn_build's contract and kernels, k <= 64, r > 0: matches farther than r are missing) of T query[i] in that grid, query
+ * fp64 [n_query <= n_query_max, 3], T = pose (DEVICE double [16], row-major; x = ((T00 p0 + T01 p1) + T02 p2) + T03 unfused).  stop
+ * (DEVICE int32, optional): when *stop != 0 every row gets -1 / inf without a search.  idx_out int32 / dist_out fp64 [n_query, k]. */
+int dc_knn_grid_query(int64_t n, int64_t n_query_max, const double* query, int64_t n_query, const double* pose, const int32_t* stop, int k,
+                      double r, int32_t* idx_out, double* dist_out, void* ws, size_t ws_bytes, dcStream_t stream);
+/* *threshold_out <- np.quantile(v[~isnan(v)], ratio) for non-negative v fp64 [n]: dc_nn1_corr's radix select (TrimmedDistOutlierFilter
+ * ratio over the M x knn distance table).  stop as in dc_knn_grid_query (then the threshold keeps its value). */
+size_t dc_quantile_workspace_bytes(void);
+int dc_quantile(const double* v, int64_t n, double ratio, const int32_t* stop, double* threshold_out, void* ws, size_t ws_bytes,
+                dcStream_t stream);
+/* Blocks of dc_icp_accumulate for m reading points (partials double [blocks * DC_ICP_PARTIALS]). */
+int dc_icp_blocks(int64_t m);
+/* state double [DC_ICP_STATE_COUNT] <- the prior (DEVICE double [16]) as estimate and bound origin, history cleared; status int32 [4]
+ * <- 0. */
+int dc_icp_init(const double* prior, double* state, int32_t* status, dcStream_t stream);
+/* Pairs of reading point i (sensor frame, fp64 [m,3], its normals [m,3]) moved by the estimate with its knn map neighbours idx / dist
+ * [m, knn] (dc_knn_grid_query): kept when idx >= 0, dist <= *threshold (TrimmedDistOutlierFilter) and |R n_read . n_map| >= cos_min
+ * (SurfaceNormalOutlierFilter maxAngle); r = n_map . (x - y), J = [x x n_map, n_map] (PointToPlaneErrorMinimizer).  partials
+ * double [n_blocks = dc_icp_blocks(m), DC_ICP_PARTIALS]; kept_out uint8 [m, knn] (optional) the kept flags. */
+int dc_icp_accumulate(const double* reading, const double* normals, int64_t m, const double* map_points, const double* map_normals,
+                      const int32_t* idx, const double* dist, int knn, const double* threshold, double cos_min, const double* state,
+                      const int32_t* status, double* partials, int n_blocks, uint8_t* kept_out, dcStream_t stream);
+/* One block: the partials summed in block order, x = -(JtJ)^-1 Jtr (fp64 Cholesky), estimate <- [R(x[0:3]) x[3:6]] estimate (axis
+ * angle as transform.axis_angle_to_matrix), then the checks of icp.yaml transformationCheckers: DC_ICP_FAIL_* (estimate left as
+ * it was), DC_ICP_CONVERGED when the mean rotation / translation of the last `smooth` increments is below min_rot / min_trans,
+ * DC_ICP_MAX_ITERS at max_iters iterations. */
+int dc_icp_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
+                  double max_rot, double max_trans, int min_pairs, double* state, int32_t* status, dcStream_t stream);
+/* Map update of norlab_icp_mapper (slam.launch: minDistNewPoint, sensorMaxRange): reading points and normals moved by pose (DEVICE
+ * double [16]) into points_out / normals_out fp64 [m,3]; mask_out uint8 [m] = nearest map point (dist1 fp64 [m], 1-NN of the moved
+ * points; NULL = empty map) farther than min_dist and depth [m] <= max_range.  dc_compact_rows then appends the kept rows. */
+int dc_map_select(const double* reading, const double* normals, const double* depth, int64_t m, const double* pose, const double* dist1,
+                  double min_dist, double max_range, uint8_t* mask_out, double* points_out, double* normals_out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
