@@ -230,8 +230,12 @@ struct Nn1State {
 
 // (stop: optional device word; once it is non-zero the select's launches return at once and the threshold keeps its value --
 //  dc_quantile inside a registration that has ended)
+//  finite_only: infinite elements are skipped like NaN ones -- dc_quantile's rule, where +inf marks a neighbour that is missing;
+//  dc_nn1_corr keeps numpy's rule, which counts them)
+__device__ __forceinline__ bool nn1_skipped(double d, int finite_only) { return d != d || (finite_only && isinf(d)); }
+
 __global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st, int shift, int first,
-                                                          const int32_t* __restrict__ stop) {
+                                                          const int32_t* __restrict__ stop, int finite_only) {
   __shared__ unsigned int s_hist[256];
   if (stop && *stop != 0) return;
   s_hist[threadIdx.x] = 0;
@@ -240,7 +244,7 @@ __global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restri
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const double d = dist[i];
-    if (d != d) continue;
+    if (nn1_skipped(d, finite_only)) continue;
     const unsigned long long b = (unsigned long long)__double_as_longlong(d);
     if (!first && (b >> (shift + 8)) != (prefix >> (shift + 8))) continue;
     atomicAdd(&s_hist[(b >> shift) & 255u], 1u);
@@ -250,6 +254,9 @@ __global__ __launch_bounds__(kBlock) void nn1_hist_kernel(const double* __restri
 }
 
 __global__ void nn1_pick_kernel(Nn1State* st, int shift, int first, double ratio, const int32_t* __restrict__ stop) {
+  // numpy rounds the position before it takes the fractional part: fused, gamma would come from the exact product and (n - 1) * ratio
+  // = 204.0 would leave 1.1e-14, or a negative gamma where the product rounds up to an integer -- a threshold below a[lo]
+#pragma clang fp contract(off)
   if (threadIdx.x != 0 || (stop && *stop != 0)) return;
   if (first) {
     long long total = 0;
@@ -277,7 +284,7 @@ __global__ void nn1_pick_kernel(Nn1State* st, int shift, int first, double ratio
 }
 
 __global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restrict__ dist, int64_t n, Nn1State* st,
-                                                          const int32_t* __restrict__ stop) {
+                                                          const int32_t* __restrict__ stop, int finite_only) {
   __shared__ long long s_cnt[kBlock / kWave];
   __shared__ unsigned long long s_min[kBlock / kWave];
   if (stop && *stop != 0) return;
@@ -287,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restri
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const double d = dist[i];
-    if (d != d) continue;
+    if (nn1_skipped(d, finite_only)) continue;
     const unsigned long long b = (unsigned long long)__double_as_longlong(d);
     if (b <= v) ++cnt;
     else mn = b < mn ? b : mn;
@@ -308,6 +315,7 @@ __global__ __launch_bounds__(kBlock) void nn1_next_kernel(const double* __restri
 }
 
 __global__ void nn1_threshold_kernel(Nn1State* st, double* __restrict__ threshold, const int32_t* __restrict__ stop) {
+#pragma clang fp contract(off)                       // numpy's _lerp rounds the product and the sum one after the other
   if (threadIdx.x != 0 || blockIdx.x != 0 || (stop && *stop != 0)) return;
   if (st->n_valid <= 0) { *threshold = __longlong_as_double(0x7ff8000000000000ll); return; }      // np.quantile of nothing: NaN
   const double a = __longlong_as_double((long long)st->prefix);
@@ -319,18 +327,18 @@ __global__ void nn1_threshold_kernel(Nn1State* st, double* __restrict__ threshol
 }
 
 // The select itself: state cleared, eight byte passes (histogram + pick), the next value, numpy's interpolation -> *threshold.
-static hipError_t launch_quantile(const double* dist, int64_t n, double ratio, const int32_t* stop, Nn1State* st, double* threshold,
-                                  hipStream_t stream) {
+static hipError_t launch_quantile(const double* dist, int64_t n, double ratio, const int32_t* stop, int finite_only, Nn1State* st,
+                                  double* threshold, hipStream_t stream) {
   hipError_t err = hipMemsetAsync(st, 0, sizeof(Nn1State), stream);
   if (err != hipSuccess) return err;
   const unsigned blocks_all = (unsigned)((n + kBlock - 1) / kBlock);
   const unsigned blocks = blocks_all < 512u ? blocks_all : 512u;
   for (int pass = 0; pass < 8; ++pass) {
     const int shift = 56 - 8 * pass;
-    hipLaunchKernelGGL(nn1_hist_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, shift, pass == 0 ? 1 : 0, stop);
+    hipLaunchKernelGGL(nn1_hist_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, shift, pass == 0 ? 1 : 0, stop, finite_only);
     hipLaunchKernelGGL(nn1_pick_kernel, dim3(1), dim3(64), 0, stream, st, shift, pass == 0 ? 1 : 0, ratio, stop);
   }
-  hipLaunchKernelGGL(nn1_next_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, stop);
+  hipLaunchKernelGGL(nn1_next_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, n, st, stop, finite_only);
   hipLaunchKernelGGL(nn1_threshold_kernel, dim3(1), dim3(64), 0, stream, st, threshold, stop);
   return hipGetLastError();
 }
@@ -660,7 +668,7 @@ int dc_nn1_corr(const double* dist, const int32_t* idx, int64_t n, double ratio,
   int32_t* flags = reinterpret_cast<int32_t*>(base + st_bytes);
   int32_t* pos = reinterpret_cast<int32_t*>(base + st_bytes + arr);
   void* scan_ws = base + st_bytes + 2 * arr;
-  hipError_t err = dc::launch_quantile(dist, n, ratio, nullptr, st, threshold_out, stream);
+  hipError_t err = dc::launch_quantile(dist, n, ratio, nullptr, 0, st, threshold_out, stream);
   if (err != hipSuccess) return (int)err;
   const unsigned blocks_all = (unsigned)((n + dc::kBlock - 1) / dc::kBlock);
   hipLaunchKernelGGL(dc::nn1_flag_kernel, dim3(blocks_all), dim3(dc::kBlock), 0, stream, dist, n, (const double*)threshold_out, mask_out, flags);
@@ -678,7 +686,7 @@ int dc_quantile(const double* v, int64_t n, double ratio, const int32_t* stop, d
                 hipStream_t stream) {
   if (n < 1 || n > 0x7fffffff || !v || !(ratio >= 0.0 && ratio <= 1.0) || !threshold_out || !ws) return DC_ERR_ARG;
   if (ws_bytes < dc_quantile_workspace_bytes()) return DC_ERR_WORKSPACE;
-  const hipError_t err = dc::launch_quantile(v, n, ratio, stop, reinterpret_cast<dc::Nn1State*>(ws), threshold_out, stream);
+  const hipError_t err = dc::launch_quantile(v, n, ratio, stop, 1, reinterpret_cast<dc::Nn1State*>(ws), threshold_out, stream);
   return err == hipSuccess ? DC_OK : (int)err;
 }
 

@@ -96,4 +96,18 @@ int dc_host_icp_solve(const double* a21, const double* b6, double* x6) { return 
 // out = [R(x[0:3]) x[3:6]; 0 1] T (row-major 4 x 4): the finish kernel's pose update
 void dc_host_icp_step(const double* x6, const double* T, double* out) { dc::icp_apply_step(x6, T, out); }
 
+// dc_icp_finish on the host: the same argument checks, the partials summed in the kernel's order, the same tail; state [DC_ICP_STATE_COUNT]
+// and status [4] are host arrays.  0, or 1 for arguments dc_icp_finish refuses.
+int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
+                       double max_rot, double max_trans, int min_pairs, double* state, int32_t* status) {
+  if (!partials || !state || !status || n_blocks < 1 || n_blocks > dc::kIcpBlocksMax || m < 0) return 1;
+  if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1) return 1;
+  if (status[0] != 0) return 0;
+  double tot[DC_ICP_PARTIALS];
+  for (int q = 0; q < DC_ICP_PARTIALS; ++q) tot[q] = dc::icp_block_sum(partials, n_blocks, q);
+  const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
+  dc::icp_finish_tail(tot, m, prm, state, status);
+  return 0;
+}
+
 }  // extern "C"

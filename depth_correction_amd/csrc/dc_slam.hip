@@ -4,7 +4,8 @@
 //
 // One ICP iteration on the device, with nothing returned to the host in between:
 //   dc_knn_grid_query  (dc_knn.hip)    reading points moved by the device-side estimate, k-NN in the map's grid built earlier;
-//   dc_quantile        (dc_filters.hip) the trimmed threshold: dc_nn1_corr's radix select over the M x knn distance table;
+//   dc_quantile        (dc_filters.hip) the trimmed threshold: dc_nn1_corr's radix select over the matched (finite) distances of the
+//                                       M x knn table;
 //   dc_icp_accumulate                   both pair filters, residuals, fp64 block partials of JtJ (21), Jtr (6), pairs, sum r^2,
 //                                       points with a kept pair;
 //   dc_icp_finish                       one block: the partials in block order, the 6 x 6 Cholesky solve, the pose update, the
@@ -19,20 +20,18 @@
 
 namespace dc {
 
-constexpr int kIcpBlocksMax = 512;
-
 static int icp_blocks(int64_t m) {
   const int64_t b = (m + kBlock - 1) / kBlock;
   return (int)(b < 1 ? 1 : (b > kIcpBlocksMax ? kIcpBlocksMax : b));
 }
 
 // x = R p + t with the products and sums rounded in this order (dc_knn_grid_query moves the queries with the same arithmetic,
-// so the point a pair is formed with is the point that was matched)
+// so the point a pair is formed with is the point that was matched).  Plain operators with contraction switched off for this
+// function: __dmul_rn / __dadd_rn are inline functions of plain operators, which the compiler fuses into fma where it inlines them.
 __device__ __forceinline__ void move_point(const double* T, const double* p, double* x) {
+#pragma clang fp contract(off)
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
-    x[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T[r * 4], p[0]), __dmul_rn(T[r * 4 + 1], p[1])), __dmul_rn(T[r * 4 + 2], p[2])),
-                     T[r * 4 + 3]);
+  for (int r = 0; r < 3; ++r) x[r] = ((T[r * 4] * p[0] + T[r * 4 + 1] * p[1]) + T[r * 4 + 2] * p[2]) + T[r * 4 + 3];
 }
 
 __global__ void icp_init_kernel(const double* __restrict__ prior, double* __restrict__ state, int32_t* __restrict__ status) {
@@ -102,70 +101,24 @@ __global__ __launch_bounds__(kBlock) void icp_accumulate_kernel(const double* __
   }
 }
 
-struct IcpParams {
-  double min_rot, min_trans, max_rot, max_trans;
-  int smooth, max_iters, min_pairs;
-};
-
-// One block: lanes 8 q .. 8 q + 7 sum value q over the blocks b = lane, lane + 8, ... in order, lane 8 q adds the eight sums in
-// order; thread 0 then solves and updates.
+// One block: threads 8 q .. 8 q + 7 sum value q over the blocks b = l, l + 8, ... in order (icp_lane_sum), thread q adds the eight
+// sums of value q in order; thread 0 then solves and updates (icp_finish_tail).
 __global__ __launch_bounds__(kBlock) void icp_finish_kernel(const double* __restrict__ partials, int n_blocks, int64_t m, IcpParams prm,
                                                             double* __restrict__ state, int32_t* __restrict__ status) {
-  __shared__ double s_part[DC_ICP_PARTIALS * 8];
+  __shared__ double s_part[DC_ICP_PARTIALS * kIcpSumLanes];
   __shared__ double s_tot[DC_ICP_PARTIALS];
   if (status[0] != 0) return;
   const int t = threadIdx.x;
-  if (t < DC_ICP_PARTIALS * 8) {
-    const int q = t >> 3, l = t & 7;
-    double s = 0.0;
-    for (int b = l; b < n_blocks; b += 8) s += partials[(int64_t)b * DC_ICP_PARTIALS + q];
-    s_part[t] = s;
-  }
+  if (t < DC_ICP_PARTIALS * kIcpSumLanes) s_part[t] = icp_lane_sum(partials, n_blocks, t / kIcpSumLanes, t % kIcpSumLanes);
   __syncthreads();
   if (t < DC_ICP_PARTIALS) {
     double s = 0.0;
-    for (int l = 0; l < 8; ++l) s += s_part[t * 8 + l];
+    for (int l = 0; l < kIcpSumLanes; ++l) s += s_part[t * kIcpSumLanes + l];
     s_tot[t] = s;
   }
   __syncthreads();
   if (t != 0) return;
-  const double* tot = s_tot;
-  double* st = state;
-  const int iter = status[1] + 1;
-  status[1] = iter;
-  st[DC_ICP_STATE_PAIRS] = tot[27];
-  st[DC_ICP_STATE_SSE] = tot[28];
-  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[29] / (double)m : 0.0;
-  if (tot[27] < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
-  double x[6];
-  if (icp_solve6(tot, tot + 21, x)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
-  double Tn[16];
-  icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
-  bool finite = true;
-  for (int q = 0; q < 6; ++q) finite = finite && isfinite(x[q]);
-  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
-  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
-  double C[16];
-  rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);            // the total correction relative to the prior (BoundTransformationChecker)
-  const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
-  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
-  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
-  // DifferentialTransformationChecker: the mean rotation / translation of the last `smooth` increments
-  const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
-  st[DC_ICP_STATE_HIST_ROT + slot] = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  st[DC_ICP_STATE_HIST_TRANS + slot] = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-  if (iter >= prm.smooth) {
-    double mr = 0.0, mt = 0.0;
-    for (int h = 0; h < prm.smooth; ++h) {
-      const int s = (iter - 1 - h) % DC_ICP_MAX_SMOOTH;
-      mr += st[DC_ICP_STATE_HIST_ROT + s];
-      mt += st[DC_ICP_STATE_HIST_TRANS + s];
-    }
-    mr /= (double)prm.smooth;
-    mt /= (double)prm.smooth;
-    if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
-  }
-  if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;      // CounterTransformationChecker: stop, keep the estimate
+  icp_finish_tail(s_tot, m, prm, state, status);
 }
 
 // Reading points the map takes: world coordinates and normals of every point, mask = nearest map point farther than min_dist

@@ -1,9 +1,11 @@
 // The per-iteration algebra of the scan-to-map point-to-plane ICP (dc_slam.hip), shared by the finish kernel and the
-// test-only host build (dc_hostcheck.cpp): the 6 x 6 fp64 normal equations and the pose update.  Reference configuration:
-// config/slam/icp.yaml (PointToPlaneErrorMinimizer); DESIGN "SLAM evaluation" states the algorithm.
+// test-only host build (dc_hostcheck.cpp): the 6 x 6 fp64 normal equations, the pose update and the checks that end a
+// registration.  Reference configuration: config/slam/icp.yaml (PointToPlaneErrorMinimizer, transformationCheckers); DESIGN
+// "SLAM evaluation" states the algorithm.
 #pragma once
 #include <math.h>
 #include "dc_common.h"
+#include "../../include/dc_hip.h"
 
 namespace dc {
 
@@ -90,6 +92,71 @@ DC_HD void rigid_div(const double* A, const double* B, double* C) {
       for (int k = 0; k < 4; ++k) s += A[r * 4 + k] * Bi[k * 4 + c];
       C[r * 4 + c] = s;
     }
+}
+
+struct IcpParams {
+  double min_rot, min_trans, max_rot, max_trans;
+  int smooth, max_iters, min_pairs;
+};
+
+constexpr int kIcpBlocksMax = 512;      // most blocks (rows of partials) of dc_icp_accumulate
+constexpr int kIcpSumLanes = 8;         // lanes that share the sum of one value over the blocks
+
+// The order dc_icp_finish adds the block partials [n_blocks, DC_ICP_PARTIALS] of value q in: lane l of eight takes the blocks l,
+// l + 8, ... in order (icp_lane_sum: one thread of the finish kernel each), then the eight sums are added in order (the kernel's
+// second stage; icp_block_sum is the same additions run one after the other, for the host build).
+DC_HD double icp_lane_sum(const double* partials, int n_blocks, int q, int l) {
+  double s = 0.0;
+  for (int b = l; b < n_blocks; b += kIcpSumLanes) s += partials[(int64_t)b * DC_ICP_PARTIALS + q];
+  return s;
+}
+
+DC_HD double icp_block_sum(const double* partials, int n_blocks, int q) {
+  double tot = 0.0;
+  for (int l = 0; l < kIcpSumLanes; ++l) tot += icp_lane_sum(partials, n_blocks, q, l);
+  return tot;
+}
+
+// The single-thread tail of dc_icp_finish once the DC_ICP_PARTIALS totals of an iteration are complete: counts the iteration,
+// records pairs / SSE / overlap, solves, and then in this order: DC_ICP_FAIL_PAIRS, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE,
+// DC_ICP_FAIL_BOUND (each leaves the estimate as it was), the estimate and the increment history updated, DC_ICP_CONVERGED,
+// DC_ICP_MAX_ITERS.  A status word that is already set is the caller's to test: this function is not called then.
+DC_HD void icp_finish_tail(const double* tot, int64_t m, const IcpParams& prm, double* st, int32_t* status) {
+  const int iter = status[1] + 1;
+  status[1] = iter;
+  st[DC_ICP_STATE_PAIRS] = tot[27];
+  st[DC_ICP_STATE_SSE] = tot[28];
+  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[29] / (double)m : 0.0;
+  if (tot[27] < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
+  double x[6];
+  if (icp_solve6(tot, tot + 21, x)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
+  double Tn[16];
+  icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
+  bool finite = true;
+  for (int q = 0; q < 6; ++q) finite = finite && isfinite(x[q]);
+  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
+  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  double C[16];
+  rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);            // the total correction relative to the prior (BoundTransformationChecker)
+  const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
+  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
+  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
+  // DifferentialTransformationChecker: the mean rotation / translation of the last `smooth` increments
+  const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
+  st[DC_ICP_STATE_HIST_ROT + slot] = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  st[DC_ICP_STATE_HIST_TRANS + slot] = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
+  if (iter >= prm.smooth) {
+    double mr = 0.0, mt = 0.0;
+    for (int h = 0; h < prm.smooth; ++h) {
+      const int s = (iter - 1 - h) % DC_ICP_MAX_SMOOTH;
+      mr += st[DC_ICP_STATE_HIST_ROT + s];
+      mt += st[DC_ICP_STATE_HIST_TRANS + s];
+    }
+    mr /= (double)prm.smooth;
+    mt /= (double)prm.smooth;
+    if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
+  }
+  if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;      // CounterTransformationChecker: stop, keep the estimate
 }
 
 }  // namespace dc

@@ -1139,8 +1139,9 @@ def knn_grid_query(grid, query, pose, k, r=None, stop=None, idx=None, dist=None)
 
 @on_device
 def quantile(v, ratio, stop=None, out=None, ws=None):
-    """np.quantile(v[~isnan(v)], ratio) of non-negative v (f64, any shape) as a device f64 [1] (``out`` when given), by dc_nn1_corr's
-    radix select; ``stop`` as in knn_grid_query (dc_quantile)."""
+    """np.quantile(v[isfinite(v)], ratio) of non-negative v (f64, any shape) as a device f64 [1] (``out`` when given), by dc_nn1_corr's
+    radix select; NaN and +inf entries (missing neighbours) are not counted, NaN when nothing is left; ``stop`` as in knn_grid_query
+    (dc_quantile)."""
     need(v, None, dtype=torch.float64, name='v')
     n = v.numel()
     nbytes = lib().dc_quantile_workspace_bytes()

@@ -842,8 +842,9 @@ int dc_knn_grid_build(const void* points, int stride, int dtype, int64_t n, int6
  * (DEVICE int32, optional): when *stop != 0 every row gets -1 / inf without a search.  idx_out int32 / dist_out fp64 [n_query, k]. */
 int dc_knn_grid_query(int64_t n, int64_t n_query_max, const double* query, int64_t n_query, const double* pose, const int32_t* stop, int k,
                       double r, int32_t* idx_out, double* dist_out, void* ws, size_t ws_bytes, dcStream_t stream);
-/* *threshold_out <- np.quantile(v[~isnan(v)], ratio) for non-negative v fp64 [n]: dc_nn1_corr's radix select (TrimmedDistOutlierFilter
- * ratio over the M x knn distance table).  stop as in dc_knn_grid_query (then the threshold keeps its value). */
+/* *threshold_out <- np.quantile(v[isfinite(v)], ratio) for non-negative v fp64 [n]: dc_nn1_corr's radix select (TrimmedDistOutlierFilter
+ * ratio over the M x knn distance table, whose +inf entries are the neighbours dc_knn_grid_query did not find: the quantile is of
+ * the matched distances).  NaN when no element is finite.  stop as in dc_knn_grid_query (then the threshold keeps its value). */
 size_t dc_quantile_workspace_bytes(void);
 int dc_quantile(const double* v, int64_t n, double ratio, const int32_t* stop, double* threshold_out, void* ws, size_t ws_bytes,
                 dcStream_t stream);
@@ -859,7 +860,8 @@ int dc_icp_init(const double* prior, double* state, int32_t* status, dcStream_t 
 int dc_icp_accumulate(const double* reading, const double* normals, int64_t m, const double* map_points, const double* map_normals,
                       const int32_t* idx, const double* dist, int knn, const double* threshold, double cos_min, const double* state,
                       const int32_t* status, double* partials, int n_blocks, uint8_t* kept_out, dcStream_t stream);
-/* One block: the partials summed in block order, x = -(JtJ)^-1 Jtr (fp64 Cholesky), estimate <- [R(x[0:3]) x[3:6]] estimate (axis
+/* One block: the partials summed in a fixed order (lane l of eight takes the blocks l, l + 8, ... in order, then the eight sums in
+ * order), x = -(JtJ)^-1 Jtr (fp64 Cholesky), estimate <- [R(x[0:3]) x[3:6]] estimate (axis
  * angle as transform.axis_angle_to_matrix), then the checks of icp.yaml transformationCheckers: DC_ICP_FAIL_* (estimate left as
  * it was), DC_ICP_CONVERGED when the mean rotation / translation of the last `smooth` increments is below min_rot / min_trans,
  * DC_ICP_MAX_ITERS at max_iters iterations. */

@@ -47,3 +47,37 @@ def assert_eigvals_close(lam, ref, rtol, what=''):
     tol = rtol * np.abs(ref) + 1e-12 * np.abs(ref).max(axis=-1, keepdims=True)
     bad = np.abs(lam - ref) > tol
     assert not bad.any(), '%s: %d eigenvalues off, worst rel %.3g' % (what, bad.sum(), (np.abs(lam - ref) / np.abs(ref))[bad].max())
+
+
+# ---- SLAM tests (test_slam_host.py, test_slam_reference_host.py, test_gpu_slam_parity.py) -------------------------------------------
+def slam_pose(yaw, t, roll=0.0, pitch=0.0):
+    """4 x 4 pose from euler angles and a translation."""
+    from depth_correction_amd.dataset import euler_matrix
+    T = euler_matrix(roll, pitch, yaw)
+    T[:3, 3] = t
+    return T
+
+
+def hostcheck_lib():
+    """libdc_hostcheck.so (the test-only host build of the per-point math), built when it is missing."""
+    import ctypes
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.path.join(root, 'depth_correction_amd', 'lib', 'libdc_hostcheck.so')
+    if not os.path.exists(path):
+        import __graft_entry__ as ge
+        ge.build()
+    lib = ctypes.CDLL(path)
+    lib.dc_host_icp_finish.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64] + 2 * [ctypes.c_double] + 2 * [ctypes.c_int] + \
+        2 * [ctypes.c_double] + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return lib
+
+
+def host_icp_finish(lib, partials, m, prm, state, status):
+    """dc_host_icp_finish on partials [n_blocks, 30] with the parameters of slam_reference.params; state f64 [64] and status i32 [4]
+    are numpy arrays changed in place."""
+    partials = np.ascontiguousarray(partials, dtype=np.float64).reshape(-1, 30)
+    rc = lib.dc_host_icp_finish(partials.ctypes.data, partials.shape[0], m, prm.icp_min_diff_rot, prm.icp_min_diff_trans,
+                                int(prm.icp_smooth_length), int(prm.icp_max_iters), prm.icp_max_rotation, prm.icp_max_translation,
+                                int(prm.min_pairs), state.ctypes.data, status.ctypes.data)
+    assert rc == 0

@@ -240,3 +240,44 @@ def test_failure_paths_keep_prior_and_map(room):
     assert info['status'] == 'bound' and not info['ok'], info
     assert np.array_equal(pose, ds[1][1] @ _pose(0.0, (0.3, 0.0, 0.0)))
     assert mapper.n_map == n0 and torch.equal(mapper.map_points()[0], before)
+
+
+def test_mapper_bookkeeping(room):
+    """grid_builds rises exactly when the map changed or a larger reading arrives; update() with enough overlap, or of a scan that
+    is already in the map, adds and builds nothing; a failed registration leaves the map, its rows and the grid as they were."""
+    from depth_correction_amd.slam import IcpMapper, MapperScan, mapper_input
+    cfg = _cfg()
+    ds = _dataset(room, n=3)
+    mapper = IcpMapper(cfg)
+    s0 = mapper.prepare(mapper_input(ds[0][0], None, cfg))
+    s1 = mapper.prepare(mapper_input(ds[1][0], None, cfg))
+    pose, info = mapper.register(s1, ds[1][1])
+    assert info['status'] == 'init' and info['ok'] and info['iterations'] == 0 and np.array_equal(pose, ds[1][1])
+    assert mapper.grid_builds == 0 and mapper.n_map == 0
+    assert mapper.update(s0, ds[0][1]) == len(s0) and mapper.grid_builds == 1
+    small = MapperScan(s1.points[:1000].contiguous(), s1.normals[:1000].contiguous(), s1.depth[:1000].contiguous())
+    prior = ds[1][1] @ _pose(0.01, (0.05, 0.0, 0.0))
+    for _ in range(2):                                     # a repeated register() of a reading the grid already holds room for
+        pose, info = mapper.register(small, prior)
+        assert info['ok'] and mapper.grid_builds == 1
+    n_query_max = mapper.grid.n_query_max
+    larger = len(s1) > n_query_max
+    pose, info = mapper.register(s1, prior)
+    assert info['ok'] and mapper.grid_builds == (2 if larger else 1)
+    pose2, info2 = mapper.register(s1, prior)
+    assert mapper.grid_builds == (2 if larger else 1) and np.array_equal(pose, pose2) and info2['iterations'] == info['iterations']
+    builds, n0 = mapper.grid_builds, mapper.n_map
+    rows = mapper.map_points()[0].clone()
+    assert mapper.update(s1, pose, overlap=cfg.slam_min_overlap) == 0          # overlap >= slam_min_overlap: nothing added, nothing built
+    assert mapper.update(s1, pose, overlap=1.0) == 0
+    assert mapper.update(s0, ds[0][1], overlap=0.0) == 0                       # every point is within min_dist of itself in the map
+    assert mapper.grid_builds == builds and mapper.n_map == n0
+    tight = _cfg(icp_max_translation=0.01)
+    mapper.cfg = tight
+    pose, info = mapper.register(s1, ds[1][1] @ _pose(0.0, (0.3, 0.0, 0.0)))
+    assert info['status'] == 'bound' and mapper.grid_builds == builds and mapper.n_map == n0
+    assert torch.equal(mapper.map_points()[0], rows)
+    mapper.cfg = cfg
+    added = mapper.update(s1, ds[1][1], overlap=0.0)
+    assert added > 0 and mapper.grid_builds == builds + 1 and mapper.n_map == n0 + added
+    assert torch.equal(mapper.map_points()[0][:n0], rows)

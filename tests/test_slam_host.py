@@ -1,5 +1,7 @@
 """SLAM evaluation on the host (no GPU): the perturbed odometry of scripts/robot_data, the metric, the CSV line and file names of
-eval_slam, the ICP's 6 x 6 solve and pose update (libdc_hostcheck.so, the header the finish kernel uses) and the new Config fields."""
+eval_slam, the ICP's 6 x 6 solve and pose update (libdc_hostcheck.so, the header the finish kernel uses), the finish kernel's state
+machine through its host export against scripted registrations (tests/slam_reference.py; tests/test_gpu_slam_parity.py runs the
+same table on the device) and the new Config fields."""
 import ctypes
 import os
 
@@ -188,3 +190,84 @@ def test_icp_step_matches_numpy_rodrigues(host):
         np.testing.assert_allclose(out.reshape(4, 4), D @ T, rtol=0, atol=1e-12)
         D2 = xyz_axis_angle_to_matrix(torch.as_tensor(np.concatenate([x[3:], x[:3]]))).numpy()
         np.testing.assert_allclose(out.reshape(4, 4), D2 @ T, rtol=0, atol=1e-12)
+
+
+# ---- dc_icp_finish as a state machine (dc_host_icp_finish: the kernel's block sum and its single-thread tail, compiled for the host)
+def _host_finish(host, partials, m, prm, state, status):
+    from helpers import host_icp_finish, hostcheck_lib
+    host_icp_finish(hostcheck_lib(), partials, m, prm, state, status)
+
+
+def _finish_cases():
+    import slam_reference as R
+    return R.finish_cases()
+
+
+@pytest.mark.parametrize('case', _finish_cases(), ids=lambda c: c[0])
+def test_icp_finish_scripted_registrations(host, case):
+    """Every step of a scripted registration: status, iteration count, pairs / SSE / overlap and the history bit-equal to the Python
+    restatement (slam_reference.finish), the pose within 1e-14 (numpy's Rodrigues formula against the header's quaternion form, at
+    most eleven steps); a failure leaves the 16 pose words bit-identical; after the end one more call changes no byte."""
+    import slam_reference as R
+    name, over, steps, expect = case
+    prm = R.script_params(over)
+    ref = R.new_state(R.SCRIPT_PRIOR)
+    state, status = R.state_vector(ref), np.zeros(4, dtype=np.int32)
+    codes = []
+    for step in steps:
+        if status[0] != 0:
+            break
+        tot, m = R.script_totals(step)
+        before = state.copy()
+        _host_finish(host, tot, m, prm, state, status)
+        R.finish(tot, m, prm, ref)
+        codes.append(int(status[0]))
+        want = R.state_vector(ref)
+        assert status[0] == ref.code and status[1] == ref.iters == len(codes), (name, codes)
+        assert state[16:].tobytes() == want[16:].tobytes(), (name, len(codes), state[32:51], want[32:51])
+        assert np.abs(state[:16] - want[:16]).max() <= 1e-14, (name, len(codes))
+        if status[0] < 0:
+            assert state[:16].tobytes() == before[:16].tobytes(), name
+        elif len(codes) > 0:
+            assert state[:16].tobytes() != before[:16].tobytes(), name          # the estimate moved (max_iters keeps the update)
+    assert codes == expect, (name, codes)
+    frozen = (state.tobytes(), status.tobytes())
+    _host_finish(host, R.script_totals(steps[0])[0], 50, prm, state, status)
+    assert (state.tobytes(), status.tobytes()) == frozen, name
+
+
+def test_icp_finish_bound_is_measured_from_the_prior(host):
+    """Ten steps of 0.1 rad with max_rot 0.85: every single step is inside the bound, the ninth total (0.9) is not, and the estimate
+    left in the state is the eighth's."""
+    import slam_reference as R
+    prm = R.script_params(dict(icp_max_rotation=0.85, icp_min_diff_rot=2.0 ** -30, icp_min_diff_trans=2.0 ** -30))
+    state, status = R.state_vector(R.new_state(R.SCRIPT_PRIOR)), np.zeros(4, dtype=np.int32)
+    x = np.zeros(6)
+    x[2] = 0.1
+    for _ in range(10):
+        _host_finish(host, R.script_totals(x)[0], 50, prm, state, status)
+    assert status[0] == R.FAIL_BOUND and status[1] == 9
+    C = state[:16].reshape(4, 4) @ R.rigid_inv(R.SCRIPT_PRIOR)
+    assert abs(R.rotation_angle(C) - 0.8) <= 1e-14
+
+
+@pytest.mark.parametrize('n_blocks', [1, 7, 8, 9, 64, 511, 512])
+def test_icp_finish_block_sum_order_is_bit_exact(host, n_blocks):
+    """The documented order of the block sum (lane l of eight: blocks l, l + 8, ...; then the eight sums in order) emulated in numpy
+    fp64: pairs / SSE / overlap and the pose after a step with JtJ = 2^4 I are bit-equal.  An IEEE statement, not a tolerance: the
+    step rotates about z by an angle below 1e-9 from the identity, where every product of the update is exact.  The host build
+    shares the per-lane loop (icp_lane_sum) with the finish kernel but adds the eight lane sums in a loop of its own: the kernel's
+    second stage is pinned by the same case on the device (tests/test_gpu_slam_parity.py)."""
+    import slam_reference as R
+    partials, want_state = _block_sum_case(n_blocks)
+    prm = R.script_params(dict(min_pairs=-2 ** 31 + 1, icp_max_rotation=3.0, icp_max_translation=1e30))
+    state, status = R.state_vector(R.new_state(np.eye(4))), np.zeros(4, dtype=np.int32)
+    _host_finish(host, partials, 64, prm, state, status)
+    assert status[1] == 1 and status[0] in (0, 1)
+    assert state[:16].tobytes() == want_state[:16].tobytes(), (state[:16], want_state[:16])
+    assert state[48:51].tobytes() == want_state[48:51].tobytes()
+
+
+def _block_sum_case(n_blocks, seed=21):
+    import slam_reference as R
+    return R.block_sum_case(n_blocks, seed)
