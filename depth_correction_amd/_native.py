@@ -150,6 +150,8 @@ _SIGNATURES = {
     'dc_bvh_workspace_bytes': (_sz, [_i64]),
     'dc_bvh_build': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dc_raycast': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'dc_mesh_closest': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp]),
+    'dc_mesh_sample': (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'dc_knn_grid_build': (_i32, [_vp, _i32, _i32, _i64, _i64, _i32, _f64, _vp, _sz, _vp]),
     'dc_knn_grid_query': (_i32, [_i64, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),
     'dc_quantile_workspace_bytes': (_sz, []),

@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['Config', 'Loss', 'loss_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
+__all__ = ['Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
            'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
@@ -82,6 +82,14 @@ def slam_eval_csv(log_dir: str, slam: str, subset: str = None):
         path = 'slam_eval_{slam}_{subset}.csv'.format(slam=slam, subset=subset)
     else:
         path = 'slam_eval_{slam}.csv'.format(slam=slam)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def map_eval_csv(log_dir: str, subset: str = None):
+    """CSV file eval_map_all appends to for one subset (named as slam_eval_csv names its files; not in the reference)."""
+    path = 'map_eval_{subset}.csv'.format(subset=subset) if subset else 'map_eval.csv'
     if log_dir:
         path = os.path.join(log_dir, path)
     return path
@@ -200,6 +208,13 @@ class Config(object):
         self.slam_min_overlap = 0.9             # map_update_overlap
         self.slam_min_dist_new_point = 0.1      # min_dist_new_point
         self.slam_sensor_max_range = 25.0       # sensor_max_range
+        # map accuracy against the ground-truth mesh (eval.eval_map, DESIGN "Map accuracy"; not in the reference's Config):
+        # eval_map appends to map_eval_csv; map_eval_poses 'dataset' (the poses the dataset yields) or 'slam' (the poses run_slam
+        # estimates); the quantile of trimmed_mean; samples of the mesh for completeness_mean (0 = not computed)
+        self.map_eval_csv = None
+        self.map_eval_poses = 'dataset'
+        self.map_eval_inlier_ratio = 0.8
+        self.map_eval_samples = 0
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse

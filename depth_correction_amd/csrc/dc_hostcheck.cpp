@@ -5,6 +5,7 @@
 #include "dc_eig3.h"
 #include "dc_pointmath.h"
 #include "dc_slam_math.h"
+#include "dc_trimath.h"
 
 extern "C" {
 
@@ -109,5 +110,20 @@ int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double m
   dc::icp_finish_tail(tot, m, prm, state, status);
   return 0;
 }
+
+// dc_mesh_closest's per-triangle step: closest point of tri (a, b, c) [9] to p [3] -> closest [3], *region (optional) the branch
+// taken (dc::kTri*); returns the squared distance the kernel compares
+double dc_host_closest_on_triangle(const double* tri, const double* p, double* closest, int* region) {
+  return dc::closest_on_triangle(tri, p, closest, region);
+}
+
+// dc_mesh_sample's sample i of `seed` on the triangle tri [9]: u [3] <- the three uniforms, p [3] <- the point
+void dc_host_mesh_sample_point(const double* tri, int64_t seed, int64_t i, double* u, double* p) {
+  dc::mesh_sample_uniforms(seed, i, u);
+  dc::mesh_sample_point(tri, u[1], u[2], p);
+}
+
+// dc_mesh_sample's face for the uniform u0 and the inclusive area prefix sum area_cdf [n]
+int64_t dc_host_mesh_sample_face(const double* area_cdf, int64_t n, double u0) { return dc::mesh_sample_face(area_cdf, n, u0); }
 
 }  // extern "C"

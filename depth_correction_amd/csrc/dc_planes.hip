@@ -24,6 +24,7 @@
 #include "dc_common.h"
 #include "../../include/dc_hip.h"
 #include "dc_pointmath.h"
+#include "dc_rng.h"
 
 namespace dc {
 
@@ -32,13 +33,6 @@ constexpr int kPBlock = 256;                 // threads of every kernel here (4 
 constexpr int kPWaves = kPBlock / 64;
 constexpr int kScorePts = 4;                 // points per thread of the scoring kernel
 constexpr int kMaxHyp = 1024;                // LDS: 32 B of plane + 16 B of per-wave counts per hypothesis
-
-DC_HD uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 template <typename T>
 __device__ __forceinline__ void load3(const T* p, int64_t i, double* x) {

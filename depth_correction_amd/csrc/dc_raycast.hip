@@ -309,8 +309,8 @@ size_t dc_bvh_workspace_bytes(int64_t n_faces) {
 
 int dc_bvh_build(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* scene_box, int32_t* leaf_face,
                  int32_t* child, int32_t* parent, float* node_box, double* leaf_tri, void* ws, size_t ws_bytes, dcStream_t stream_) {
-  if (n_faces < 1 || n_faces > (int64_t)INT32_MAX / 2 || n_verts < 1 || !verts || !faces || !scene_box || !leaf_face || !child || !parent ||
-      !node_box || !leaf_tri)
+  if (n_faces < 1 || n_faces > (int64_t)INT32_MAX / 2 || n_verts < 1 || !verts || !faces || !scene_box || !leaf_face ||
+      (n_faces > 1 && !child) || !parent || !node_box || !leaf_tri)       // one face: the root is a leaf and child has no rows
     return DC_ERR_ARG;
   if (!ws || ws_bytes < dc_bvh_workspace_bytes(n_faces)) return DC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;

@@ -2,11 +2,12 @@
 
 The analytic generators the hot path's tests and ``bench.py`` need are here; lidar scans rendered from triangle meshes
 (``RenderedMeshDataset``, ``DepthBiasDataset``, ``render_lidar_cloud``; reference dataset.py:490-716, 850-873, 1073-1130) live in
-``render.py`` and are re-exported here.  The reference's real-data readers (dataset.py:361-489, datasets/*) are out of scope
+``render.py`` and are re-exported here.  The reference's real-data readers (dataset.py:361-416, datasets/*) are out of scope
 (SURVEY 2, #13).
 
 * ``PlaneDataset``   -- restatement of the reference generator of BASELINE config 0
                         (dataset.py:240-358): two 10x10 m half planes, per-scan random subsample.
+* ``MeshDataset``    -- the same measurements of a cloud sampled from a mesh (dataset.py:417-488; sampling on the GPU).
 * ``RoomBoxDataset`` -- "ASL-laser-shaped" scans of BASELINE configs 1-3.
 * ``KittiLikeDataset`` -- "KITTI-360-shaped" ring scans of BASELINE config 4.
 
@@ -18,7 +19,7 @@ from __future__ import annotations
 import numpy as np
 from numpy.lib.recfunctions import unstructured_to_structured, merge_arrays
 
-__all__ = ['PlaneDataset', 'RoomBoxDataset', 'KittiLikeDataset', 'create_dataset', 'add_depth_noise', 'Forwarding',
+__all__ = ['PlaneDataset', 'MeshDataset', 'RoomBoxDataset', 'KittiLikeDataset', 'create_dataset', 'add_depth_noise', 'Forwarding',
            'TransformingDataset', 'FilteredDataset', 'NoisyPoseDataset', 'NoisyDepthDataset', 'noisy_dataset', 'euler_matrix',
            'RenderedMeshDataset', 'DepthBiasDataset', 'render_lidar_cloud', 'render_lidar_clouds', 'lidar_directions']
 
@@ -81,6 +82,65 @@ class PlaneDataset(_Seq):
     def __getitem__(self, i):
         i = self.ids[i]
         return self.local_cloud(i), self.cloud_pose(i)
+
+
+class MeshDataset(PlaneDataset):
+    """Measurements of a ground-truth environment given as a mesh (reference dataset.py:417-488 on BaseDataset :240-317): the
+    global cloud is ``n_pts_to_sample`` area-weighted samples of the mesh (mesh.TriangleMesh.sample with ``seed``: this package's
+    deterministic sampler, not pytorch3d's generator) cropped to ``size``; its normals are the face normals (the reference
+    estimates normals only for meshes that gave none).  Local clouds and poses as PlaneDataset; indexing by int, list or slice.
+    ``mesh_name``: an absolute path, a path relative to render.mesh_dir(), or ``mesh/<file>``."""
+
+    dataset_name = 'mesh'
+
+    def __init__(self, mesh_name, n_poses=5, size=([-10.0, 10.0], [-10.0, 10.0], [-10.0, 10.0]), n_pts_to_sample=10_000_000,
+                 height=2.0, seed=135, device='cuda'):
+        import os
+        from .mesh import load_mesh
+        from .render import mesh_dir
+        name = str(mesh_name)
+        if name.startswith(MeshDataset.dataset_name + '/'):
+            name = name[len(MeshDataset.dataset_name) + 1:]
+        path = name if os.path.isabs(name) else os.path.join(mesh_dir(), name)
+        if not os.path.exists(path):
+            raise FileNotFoundError('Mesh file %s does not exist.' % path)
+        mesh = load_mesh(path)
+        if int(n_poses) < 1 or int(n_pts_to_sample) < 1:
+            raise ValueError('n_poses and n_pts_to_sample must be positive')
+        self.name, self.n_poses, self.height, self.size = name, int(n_poses), height, size
+        self.n_pts_to_sample, self.seed, self.mesh = int(n_pts_to_sample), int(seed), mesh
+        self.ids = range(self.n_poses)
+        pts, normals, _ = mesh.sample(self.n_pts_to_sample, seed=self.seed, device=device)
+        pts, normals = pts.cpu().numpy(), normals.cpu().numpy()
+        keep = np.ones(len(pts), dtype=bool)
+        for a in range(3):                                   # dataset.py:454-459: crop to the volume ``size``
+            keep &= (pts[:, a] >= size[a][0]) & (pts[:, a] <= size[a][1])
+        self.pts, self.normals = pts[keep], normals[keep]
+        self.n_pts = len(self.pts)
+
+    def get_mesh(self):
+        return self.mesh
+
+    def local_cloud(self, i):
+        rng = np.random.default_rng(i)                       # dataset.py:269-286 (choice over the index range)
+        sel = rng.choice(self.n_pts, size=self.n_pts // self.n_poses, replace=False)
+        pose = self.cloud_pose(i)
+        R, t = pose[:3, :3], pose[:3, 3]
+        return _structured((self.pts[sel] - t) @ R, self.normals[sel] @ R)
+
+    def __getitem__(self, i):
+        if isinstance(i, (int, np.integer)):
+            id = self.ids[i]
+            return self.local_cloud(id), self.cloud_pose(id)
+        from copy import copy
+        ds = copy(self)
+        if isinstance(i, (list, tuple)):
+            ds.ids = [self.ids[j] for j in i]
+        elif isinstance(i, slice):
+            ds.ids = self.ids[i]
+        else:
+            raise ValueError('Invalid index: %s.' % (i,))
+        return ds
 
 
 class RoomBoxDataset(_Seq):
@@ -172,13 +232,18 @@ def add_depth_noise(cloud, sigma, rng):
 
 
 def create_dataset(name, cfg=None, **kwargs):
-    """Subset of the reference's ``create_dataset`` (dataset.py:953-962): the synthetic names and ``rendered_mesh/...`` (keyword
-    arguments such as ``poses_path`` go to RenderedMeshDataset; its device defaults to ``cfg.device``)."""
+    """Subset of the reference's ``create_dataset`` (dataset.py:953-962): the synthetic names, ``rendered_mesh/...`` (keyword
+    arguments such as ``poses_path`` go to RenderedMeshDataset) and ``mesh/<file>`` (MeshDataset); their device defaults to
+    ``cfg.device``."""
     from .render import RenderedMeshDataset
     if name.startswith(RenderedMeshDataset.dataset_name + '/'):
         if cfg is not None and 'device' not in kwargs:
             kwargs['device'] = cfg.device
         return RenderedMeshDataset(name, **kwargs)
+    if name.startswith(MeshDataset.dataset_name + '/'):
+        if cfg is not None and 'device' not in kwargs:
+            kwargs['device'] = cfg.device
+        return MeshDataset(name, **kwargs)
     if name.startswith('plane'):
         return PlaneDataset(**kwargs)
     if name.startswith('room'):

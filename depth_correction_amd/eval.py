@@ -7,7 +7,8 @@ offsets / distance weights, any of the reference's models or none) every sequenc
 ``model.w`` / ``model.exponent`` / the pose corrections.  Any other configuration goes through the un-fused DepthCloud operators with identical results.
 
 ``eval_loss`` / ``eval_loss_all`` are the reference's test-set evaluation (eval.py:115-211); ``eval_slam`` / ``eval_slam_all`` its
-localization-accuracy evaluation (eval.py:214-290) with this package's ICP mapper instead of ROS (slam.py).  ``landscape_clouds`` evaluates
+localization-accuracy evaluation (eval.py:214-290) with this package's ICP mapper instead of ROS (slam.py); ``eval_map`` /
+``eval_map_all`` the accuracy of the map against the ground-truth mesh (scripts/mapping_accuracy:82-118).  ``landscape_clouds`` evaluates
 the loss for many candidate weights of the model at once: every model with a basis form is affine in its weights, so a
 neighbourhood's covariance is a quadratic form in w and one pass over the neighbours (dc_sequence_landscape) serves every
 row; configurations outside that path loop over ``eval_loss_clouds`` ("Loss landscape").
@@ -20,14 +21,14 @@ from collections import Counter
 import numpy as np
 import torch
 
-from .config import SLAM, Config, NeighborhoodType, PoseCorrection, loss_eval_csv, nonempty, slam_eval_csv
+from .config import SLAM, Config, NeighborhoodType, PoseCorrection, loss_eval_csv, map_eval_csv, nonempty, slam_eval_csv
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry, SequencePlan, consistency_loss
 from .preproc import (compute_neighborhood_features, global_cloud, global_cloud_mask, local_feature_cloud,
                       offset_cloud)
 from .transform import corrected_poses, xyz_axis_angle_to_matrix
 
-__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape', 'eval_slam', 'eval_slam_all',
+__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape', 'eval_map', 'eval_map_all', 'eval_slam', 'eval_slam_all',
            'initialize_pose_corrections', 'fused_supported', 'landscape_clouds', 'landscape_paths', 'PlanCloud', 'LazyFeatureCloud']
 
 
@@ -344,6 +345,74 @@ def eval_slam_all(cfg: Config):
             eval_cfg.slam_eval_csv = slam_eval_csv(cfg.log_dir, slam, suffix)
             eval_cfg.slam_poses_csv = ''
             out[(slam, suffix)] = eval_slam(cfg=eval_cfg)
+    return out
+
+
+# ---- map accuracy against the ground-truth mesh ----------------------------------------------------------------------------------
+MAP_EVAL_FIELDS = ('n', 'mean', 'rms', 'median', 'trimmed_mean', 'signed_mean')
+
+
+def _dataset_mesh(ds, name):
+    get = getattr(ds, 'get_mesh', None)          # reached through the Forwarding wrappers
+    if not callable(get):
+        raise ValueError('dataset %s gives no ground-truth mesh (no get_mesh()): eval_map needs one' % name)
+    return get()
+
+
+def eval_map(cfg: Config, test_datasets=None, model=None):
+    """Accuracy of the map of every test sequence against its dataset's mesh (scripts/mapping_accuracy:82-118 against the mesh
+    instead of a surveyed cloud): each scan goes through slam.mapper_input (depth and grid filters, the correction by ``model``,
+    from the configuration unless given), is moved by its pose -- ``cfg.map_eval_poses`` 'dataset': the poses the dataset yields,
+    'slam': the poses slam.run_slam estimates -- the clouds are concatenated and voxel-filtered with filter_grid(keep='first') at
+    cfg.grid_res (mapping_accuracy:106; skipped when 0), and metrics.map_accuracy is taken.  Appends ``name n mean rms median
+    trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and returns the per-sequence dicts."""
+    from .filters import filter_grid
+    from .io import append
+    from .metrics import map_accuracy
+    from .slam import mapper_input, run_slam
+    if cfg.map_eval_poses not in ('dataset', 'slam'):
+        raise ValueError("map_eval_poses must be 'dataset' or 'slam', got %r" % (cfg.map_eval_poses,))
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    results = []
+    for name, ds in zip(test_names, test_datasets):
+        mesh = _dataset_mesh(ds, name)
+        items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in ds]
+        poses = run_slam(ds, model, cfg)['slam'] if cfg.map_eval_poses == 'slam' else [pose for _, pose in items]
+        moved = []
+        for (cloud, _), pose in zip(items, poses):
+            scan = mapper_input(cloud, model, cfg)
+            with torch.no_grad():
+                pts = scan.get_points().detach().to(device=cfg.device, dtype=torch.float64)
+                T = torch.as_tensor(np.asarray(pose, dtype=np.float64), device=pts.device)
+                moved.append(pts @ T[:3, :3].t() + T[:3, 3])
+        points = torch.cat(moved).contiguous() if moved else torch.empty((0, 3), dtype=torch.float64, device=cfg.device)
+        if cfg.grid_res and cfg.grid_res > 0.0 and points.shape[0]:
+            points = filter_grid(points, float(cfg.grid_res), keep='first').contiguous()
+        res = map_accuracy(points, mesh, inlier_ratio=cfg.map_eval_inlier_ratio, n_samples=cfg.map_eval_samples or None,
+                           seed=cfg.random_seed)
+        res['name'] = name
+        print('Map accuracy on %s: %d points, mean %.6f m, rms %.6f m, median %.6f m, trimmed mean %.6f m, signed mean %.6f m.'
+              % ((name, int(res['n'])) + tuple(res[f] for f in MAP_EVAL_FIELDS[1:])))
+        if cfg.map_eval_csv:
+            append(cfg.map_eval_csv, '%s %d %s\n' % (name, int(res['n']), ' '.join('%.9f' % res[f] for f in MAP_EVAL_FIELDS[1:])))
+        results.append(res)
+    return results
+
+
+def eval_map_all(cfg: Config):
+    """eval_map on the train, val and test subsets with the poses the datasets yield, one CSV file per subset (the shape of
+    eval_slam_all)."""
+    out = {}
+    for names, suffix in zip([cfg.train_names, cfg.val_names, cfg.test_names], ['train', 'val', 'test']):
+        if not names:
+            continue
+        eval_cfg = cfg.copy()
+        eval_cfg.test_names = names
+        eval_cfg.train_poses_path = []
+        eval_cfg.val_poses_path = []
+        eval_cfg.test_poses_path = []
+        eval_cfg.map_eval_csv = map_eval_csv(cfg.log_dir, suffix)
+        out[suffix] = eval_map(cfg=eval_cfg)
     return out
 
 

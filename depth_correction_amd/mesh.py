@@ -47,6 +47,7 @@ class TriangleMesh(object):
         self.vertices = v
         self.faces = np.ascontiguousarray(f.astype(np.int32))
         self._device = {}
+        self._area_cdf = {}
 
     def __len__(self):
         return self.faces.shape[0]
@@ -65,6 +66,31 @@ class TriangleMesh(object):
         n = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
         norm = np.linalg.norm(n, axis=1, keepdims=True)
         return np.divide(n, norm, out=np.zeros_like(n), where=norm > 0)
+
+    def face_areas(self):
+        """|(v1 - v0) x (v2 - v0)| / 2 per face, float64 [F]."""
+        v = self.vertices[self.faces]
+        return 0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1)
+
+    def area_cdf(self):
+        """Inclusive prefix sum of face_areas() (numpy cumsum: one fixed order), what sample() searches."""
+        return np.cumsum(self.face_areas())
+
+    def sample(self, n, seed=135, device='cuda'):
+        """``n`` points drawn from the surface with probability proportional to area (the reference's sample_points_from_meshes,
+        dataset.py:450) -> (points f64 [n,3], normals f64 [n,3] = the face normals, face i32 [n]) on ``device``.  A pure function
+        of (mesh, n, seed): dc_mesh_sample's formula, not pytorch3d's generator.  ``seed`` defaults to Config.random_seed's 135."""
+        import torch
+        from .ops import mesh_sample
+        verts, faces, normals, _ = self.on_device(device)
+        cdf = self._area_cdf.get(verts.device)
+        if cdf is None:
+            host = self.area_cdf()
+            if not (np.isfinite(host[-1]) and host[-1] > 0.0):
+                raise ValueError('a mesh of total area %r cannot be sampled' % float(host[-1]))
+            cdf = self._area_cdf[verts.device] = torch.as_tensor(host, device=verts.device)
+        face, pts = mesh_sample(verts, faces, cdf, n, seed)
+        return pts, normals[face.long()], face
 
     def save_ply(self, path, binary=True):
         """Write the mesh as PLY (binary_little_endian or ascii): double x y z, a uchar / int list per face."""

@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'mesh_closest', 'mesh_sample',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
 ]
 
@@ -1089,6 +1089,52 @@ def raycast(bvh, dirs, poses, t_min, cull=True):
                            ptr(dirs), ptr(t_min), r, ptr(poses), p, 1 if cull else 0, ptr(face), ptr(t), ptr(bary), stream_ptr()),
           'dc_raycast')
     return face, t, bary
+
+
+# ------------------------------------------------------------------------------------------------
+# map accuracy against a mesh (dc_meshdist.hip)
+# ------------------------------------------------------------------------------------------------
+@on_device
+def mesh_closest(bvh, points, max_dist=None, want_closest=True):
+    """Nearest triangle of the mesh behind ``bvh`` (mesh.MeshBVH) for every row of points f32 | f64 [N,3] (world frame) -> (face i32
+    [N], dist f64 [N], closest f64 [N,3] or None without ``want_closest``): the smallest distance wins, equal distance the lower
+    face index.  With ``max_dist`` a point whose nearest triangle is farther gets -1 / inf / NaN, as does a row holding a NaN or an
+    infinity.  One launch (dc_mesh_closest)."""
+    dev = bvh.leaf_face.device
+    need(points, (None, 3), name='points', device=dev)
+    code = dtype_code(points)
+    n = points.shape[0]
+    md = 0.0 if max_dist is None else float(max_dist)
+    if md != md:
+        raise ValueError('max_dist must not be NaN')
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    dist = torch.empty((n,), dtype=torch.float64, device=dev)
+    closest = torch.empty((n, 3), dtype=torch.float64, device=dev) if want_closest else None
+    nf = bvh.n_faces
+    check(lib().dc_mesh_closest(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                                ptr(points), code, n, md, ptr(face), ptr(dist), ptr(closest), stream_ptr()), 'dc_mesh_closest')
+    return face, dist, closest
+
+
+@on_device
+def mesh_sample(verts, faces, area_cdf, n_samples, seed):
+    """``n_samples`` area-weighted samples of the mesh verts f64 [V,3] / faces i32 [F,3] (indices checked by the caller, as for
+    bvh_build) with area_cdf f64 [F] the inclusive prefix sum of the face areas -> (face i32 [n], points f64 [n,3]); a pure function
+    of (mesh, n_samples, seed) (dc_mesh_sample)."""
+    need(verts, (None, 3), dtype=torch.float64, name='verts')
+    dev = verts.device
+    need(faces, (None, 3), dtype=torch.int32, name='faces', device=dev)
+    nf = faces.shape[0]
+    need(area_cdf, (nf,), dtype=torch.float64, name='area_cdf', device=dev)
+    n, seed = int(n_samples), int(seed)
+    if nf < 1 or n < 0:
+        raise ValueError('mesh_sample needs at least one face and n_samples >= 0')
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError('seed must fit a signed 64-bit integer, got %d' % seed)
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    pts = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    check(lib().dc_mesh_sample(ptr(verts), ptr(faces), nf, ptr(area_cdf), n, seed, ptr(face), ptr(pts), stream_ptr()), 'dc_mesh_sample')
+    return face, pts
 
 
 # ------------------------------------------------------------------------------------------------

@@ -809,6 +809,23 @@ int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_t
                const double* dirs, const double* t_min, int64_t n_rays, const double* poses, int n_poses, int cull, int32_t* face_out,
                double* t_out, double* bary_out, dcStream_t stream);
 
+/* ---- map accuracy against a mesh (depth_correction_amd/csrc/dc_meshdist.hip; the box-bound margin rule is derived in its header
+ * comment, the algorithm in DESIGN "Map accuracy") ----
+ * For every point (DC_F32 | DC_F64 [n_points,3], world frame) the nearest triangle of the mesh behind the arrays of dc_bvh_build:
+ * face_out int32 [n_points] (mesh numbering), dist_out double [n_points] = sqrt(d^2) correctly rounded, closest_out double
+ * [n_points,3] (optional) the nearest point of that face.  The smallest d^2 wins, equal d^2 the lower face index.  max_dist > 0 and
+ * finite: a point whose nearest triangle is farther gets -1 / +inf / NaN (dist == max_dist is found); max_dist <= 0 or +inf: no
+ * bound.  A row holding a NaN or an infinity gets -1 / +inf / NaN.  One launch, no workspace; n_points == 0 launches nothing. */
+int dc_mesh_closest(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                    const void* points, int dtype, int64_t n_points, double max_dist, int32_t* face_out, double* dist_out,
+                    double* closest_out, dcStream_t stream);
+/* n_samples area-weighted samples of the mesh verts double [.,3], faces int32 [n_faces,3] with area_cdf double [n_faces] the
+ * inclusive prefix sum of the face areas (last entry > 0).  Sample i: u_t = (splitmix64(splitmix64(seed) + 4 i + t) >> 11) 2^-53 for
+ * t = 0, 1, 2 (uint64, wrapping); face = the first f with u_0 area_cdf[n_faces-1] < area_cdf[f]; s = sqrt(u_1), point =
+ * ((1 - s) v0 + s (1 - u_2) v1) + s u_2 v2, unfused.  face_out int32 [n_samples], points_out double [n_samples,3]. */
+int dc_mesh_sample(const double* verts, const int32_t* faces, int64_t n_faces, const double* area_cdf, int64_t n_samples, int64_t seed,
+                   int32_t* face_out, double* points_out, dcStream_t stream);
+
 /* ---- SLAM evaluation: scan-to-map point-to-plane ICP (depth_correction_amd/csrc/dc_slam.hip; algorithm and deviations in DESIGN
  * "SLAM evaluation"), what eval.py:214-290 eval_slam runs through ROS and norlab_icp_mapper with config/slam/icp.yaml,
  * input_filters.yaml and launch/slam.launch.  One iteration = dc_knn_grid_query + dc_quantile + dc_icp_accumulate + dc_icp_finish,
