@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
+__all__ = ['bias_eval_csv', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
            'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
@@ -82,6 +82,14 @@ def slam_eval_csv(log_dir: str, slam: str, subset: str = None):
         path = 'slam_eval_{slam}_{subset}.csv'.format(slam=slam, subset=subset)
     else:
         path = 'slam_eval_{slam}.csv'.format(slam=slam)
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def bias_eval_csv(log_dir: str, subset: str = None):
+    """CSV file eval_bias_all appends to for one subset (named as map_eval_csv names its files; not in the reference)."""
+    path = 'bias_eval_{subset}.csv'.format(subset=subset) if subset else 'bias_eval.csv'
     if log_dir:
         path = os.path.join(log_dir, path)
     return path
@@ -215,6 +223,15 @@ class Config(object):
         self.map_eval_poses = 'dataset'
         self.map_eval_inlier_ratio = 0.8
         self.map_eval_samples = 0
+        # depth bias against the ground-truth mesh (eval.eval_bias, DESIGN "Depth bias against the mesh"; not in the reference's
+        # Config): eval_bias appends a line per sequence to bias_eval_csv and writes the per-bin table to bias_eval_curve_csv; bins of
+        # the true incidence angle over [0, pi/2]; rays with |d - t| above bias_eval_max_residual (metres) are left out; back-face
+        # culling of the cast
+        self.bias_eval_csv = None
+        self.bias_eval_curve_csv = None
+        self.bias_eval_bins = 18
+        self.bias_eval_max_residual = None
+        self.bias_eval_cull = True
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse

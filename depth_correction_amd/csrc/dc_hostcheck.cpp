@@ -6,6 +6,7 @@
 #include "dc_pointmath.h"
 #include "dc_slam_math.h"
 #include "dc_trimath.h"
+#include "dc_biasmath.h"
 
 extern "C" {
 
@@ -125,5 +126,48 @@ void dc_host_mesh_sample_point(const double* tri, int64_t seed, int64_t i, doubl
 
 // dc_mesh_sample's face for the uniform u0 and the inclusive area prefix sum area_cdf [n]
 int64_t dc_host_mesh_sample_face(const double* area_cdf, int64_t n, double u0) { return dc::mesh_sample_face(area_cdf, n, u0); }
+
+// dc_bias_accumulate on host arrays: the same argument checks, per-ray terms (dc_biasmath.h) and `out` layout; the sums run over the
+// rays in index order (the kernel's order is per block, then over the blocks: equal counts, sums equal up to rounding).  0, or 1
+// for arguments dc_bias_accumulate refuses.
+int dc_host_bias_accumulate(const void* depth, const void* inc_est, int dtype, const uint8_t* mask, const int32_t* face,
+                            const double* t_true, const double* inc_true, int64_t n, int model_kind, const double* exponent, int n_terms,
+                            int n_bins, double max_residual, double* out) {
+  if (n < 0 || n_bins < 1 || n_bins > DC_BIAS_MAX_BINS || n_terms < 1 || n_terms > DC_BIAS_MAX_TERMS || !exponent || !out ||
+      (model_kind != DC_MODEL_POLYNOMIAL && model_kind != DC_MODEL_SCALED_POLYNOMIAL) || max_residual != max_residual)
+    return 1;
+  if (n > 0 && (!depth || !face || !t_true || !inc_true)) return 1;
+  if (dtype != DC_F32 && dtype != DC_F64) return 1;
+  dc::BiasParams prm;
+  prm.kind = model_kind; prm.n_terms = n_terms; prm.n_bins = n_bins; prm.max_residual = max_residual;
+  for (int k = 0; k < DC_BIAS_MAX_TERMS; ++k) {
+    prm.e[k] = k < n_terms ? exponent[k] : 0.0;
+    if (!(prm.e[k] - prm.e[k] == 0.0)) return 1;
+  }
+  const int total = DC_BIAS_OUT_COUNT(n_bins, n_terms);
+  for (int q = 0; q < total; ++q) out[q] = 0.0;
+  double flat[dc::kBiasFlat];
+  for (int q = 0; q < dc::kBiasFlat; ++q) flat[q] = 0.0;
+  for (int64_t i = 0; i < n; ++i) {
+    const double d = dtype == DC_F32 ? (double)((const float*)depth)[i] : ((const double*)depth)[i];
+    const double ge = !inc_est ? NAN : (dtype == DC_F32 ? (double)((const float*)inc_est)[i] : ((const double*)inc_est)[i]);
+    const dc::BiasRay o = dc::bias_ray(prm, d, ge, mask ? mask[i] != 0 : true, face[i], t_true[i], inc_true[i]);
+    dc::bias_flat_add(prm, o, inc_true[i], ge, flat);
+    if (o.bin < 0) continue;
+    double v[dc::kBiasBinVals];
+    dc::bias_bin_terms(o, v);
+    double* row = out + DC_BIAS_TOTALS + DC_BIAS_BIN_COLS * o.bin;
+    row[0] += 1.0;
+    for (int q = 0; q < dc::kBiasBinVals; ++q) row[1 + q] += v[q];
+  }
+  for (int j = 0; j < dc::kBiasFlat; ++j) {
+    const int dst = dc::bias_flat_to_out(j, n_bins, n_terms);
+    if (dst >= 0) out[dst] = flat[j];
+  }
+  return 0;
+}
+
+// bin of the true incidence angle g (dc_biasmath.h)
+int dc_host_bias_bin(double g, int n_bins) { return dc::bias_bin(g, n_bins); }
 
 }  // extern "C"

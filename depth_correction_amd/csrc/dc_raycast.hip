@@ -19,6 +19,9 @@
 // a shared edge or vertex hits at least one of the faces around it (no FMA contraction there, see test_triangle).  A hit counts
 // when t > t_min (and dot(n, d) < 0 with culling); the smallest t wins, equal t the lower face index -- independent of the
 // traversal order, so results are bitwise reproducible.
+//
+// dc_raycast_rays casts the rays of measured clouds (per-ray view point and direction, per-scan pose) through the same device
+// function (cast_ray) and adds the true incidence angle on the winning triangle: the ground truth of eval_bias.
 #include "dc_common.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
@@ -160,6 +163,7 @@ __device__ __forceinline__ float box_entry(const float* __restrict__ node_box, i
 struct Hit {
   double t, u, v;
   int32_t face;
+  int32_t leaf;                 // the winning leaf (row of leaf_tri), -1 without a hit
 };
 
 // A ray in the frame of the watertight test: axes permuted to (kx, ky, kz), kz the dominant one.  Scalars only: the compiler turns
@@ -174,8 +178,8 @@ struct Ray64 {
 __device__ __forceinline__ double pick(int k, double a, double b, double c) { return k == 0 ? a : (k == 1 ? b : c); }
 
 // Woop, Benthin, Wald 2013 in fp64; t, u (weight of v1), v (weight of v2) of a hit with t > t_min that beats `best`
-__device__ __forceinline__ void test_triangle(const double* __restrict__ tri, int32_t face, const Ray64& r, double t_min, bool cull,
-                                              Hit& best) {
+__device__ __forceinline__ void test_triangle(const double* __restrict__ tri, int32_t face, int32_t leaf, const Ray64& r, double t_min,
+                                              bool cull, Hit& best) {
   // no fused multiply-adds here: watertightness needs the edge function of a shared edge to be computed as the exact negation
   // of the neighbour's (fl(a b) - fl(c d) = -(fl(c d) - fl(a b)); fma(a, b, -fl(c d)) is not -fma(c, d, -fl(a b)))
 #pragma clang fp contract(off)
@@ -200,27 +204,19 @@ __device__ __forceinline__ void test_triangle(const double* __restrict__ tri, in
   best.u = V / det;
   best.v = W / det;
   best.face = face;
+  best.leaf = leaf;
 }
 
-__global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
-                                                             const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
-                                                             int64_t n, const double* __restrict__ dirs, const double* __restrict__ t_min,
-                                                             int64_t n_rays, const double* __restrict__ poses, int64_t total, int cull,
-                                                             int32_t* __restrict__ face_out, double* __restrict__ t_out,
-                                                             double* __restrict__ bary_out) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
-  const int lane = threadIdx.x;
-  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
-  if (g >= total) return;
-  const int64_t p = g / n_rays, r = g - p * n_rays;
-  const double* M = poses + 16 * p;
-  const double s0 = dirs[3 * r], s1 = dirs[3 * r + 1], s2 = dirs[3 * r + 2];
+// Closest hit of one ray (origin o, direction d, both fp64 world frame) over the tree: the traversal both cast kernels share.
+// `stack` is the block's LDS stack (kStackDepth x kCastBlock, lane-minor); best.leaf is the winning leaf's row of leaf_tri.
+__device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                        const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face, int64_t n, double d0,
+                                        double d1, double d2, double o0, double o1, double o2, double tmin, int cull, int32_t* stack,
+                                        int lane) {
   Ray64 ray64;
-  ray64.d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
-  ray64.d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
-  ray64.d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
-  const double o0 = M[3], o1 = M[7], o2 = M[11];
-  const double tmin = t_min[r];
+  ray64.d0 = d0;
+  ray64.d1 = d1;
+  ray64.d2 = d2;
   // watertight test set-up: kz = dominant axis, (kx, ky) keep the winding
   const double ad0 = fabs(ray64.d0), ad1 = fabs(ray64.d1), ad2 = fabs(ray64.d2);
   const int kz = ad0 >= ad1 ? (ad0 >= ad2 ? 0 : 2) : (ad1 >= ad2 ? 1 : 2);
@@ -253,13 +249,14 @@ __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __re
   best.t = INFINITY;
   best.u = best.v = 0.0;
   best.face = -1;
+  best.leaf = -1;
   int sp = 0;
   int64_t node = 0;
   bool live = box_entry(node_box, 0, ray, INFINITY) < INFINITY;
   while (live) {
     if (node >= n - 1) {
       const int64_t leaf = node - (n - 1);
-      test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], ray64, tmin, cull != 0, best);
+      test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], (int32_t)leaf, ray64, tmin, cull != 0, best);
     } else {
       const float t_far = __double2float_ru(best.t);
       const int64_t ca = child[2 * node], cb = child[2 * node + 1];
@@ -284,10 +281,74 @@ __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __re
       if (box_entry(node_box, node, ray, __double2float_ru(best.t)) < INFINITY) { live = true; break; }
     }
   }
+  return best;
+}
+
+__global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                                             const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
+                                                             int64_t n, const double* __restrict__ dirs, const double* __restrict__ t_min,
+                                                             int64_t n_rays, const double* __restrict__ poses, int64_t total, int cull,
+                                                             int32_t* __restrict__ face_out, double* __restrict__ t_out,
+                                                             double* __restrict__ bary_out) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  if (g >= total) return;
+  const int64_t p = g / n_rays, r = g - p * n_rays;
+  const double* M = poses + 16 * p;
+  const double s0 = dirs[3 * r], s1 = dirs[3 * r + 1], s2 = dirs[3 * r + 2];
+  const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
+  const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
+  const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
+  const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, M[3], M[7], M[11], t_min[r], cull, stack, lane);
   face_out[g] = best.face;
   t_out[g] = best.t;
   bary_out[2 * g] = best.u;
   bary_out[2 * g + 1] = best.v;
+}
+
+// The rays of measured clouds (dc_raycast_rays): per-ray view point and direction in the sensor frame of the ray's scan.  The scan is
+// found by bisection of scan_offset (a few loads of one small cached array per lane, against a traversal of hundreds); the index is
+// clamped to [0, n_scans), so offsets that do not span [0, n] cannot move a read outside poses.
+template <typename T>
+__global__ void __launch_bounds__(kCastBlock) raycast_rays_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                                                  const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
+                                                                  int64_t n, const T* __restrict__ vps, const T* __restrict__ dirs,
+                                                                  int64_t total, const int64_t* __restrict__ scan_offset,
+                                                                  const double* __restrict__ poses, int n_scans, double t_min, int cull,
+                                                                  int32_t* __restrict__ face_out, double* __restrict__ t_out,
+                                                                  double* __restrict__ inc_out) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  if (g >= total) return;
+  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
+  }
+  const double* M = poses + 16 * (int64_t)lo;
+  const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
+  const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
+  const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
+  const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
+  const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
+  const double o0 = (M[0] * v0 + M[1] * v1 + M[2] * v2) + M[3];
+  const double o1 = (M[4] * v0 + M[5] * v1 + M[6] * v2) + M[7];
+  const double o2 = (M[8] * v0 + M[9] * v1 + M[10] * v2) + M[11];
+  const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min, cull, stack, lane);
+  face_out[g] = best.face;
+  t_out[g] = best.t;
+  double inc = NAN;
+  if (best.leaf >= 0) {
+    const double* tri = leaf_tri + 9 * (int64_t)best.leaf;
+    const double e10 = tri[3] - tri[0], e11 = tri[4] - tri[1], e12 = tri[5] - tri[2];
+    const double e20 = tri[6] - tri[0], e21 = tri[7] - tri[1], e22 = tri[8] - tri[2];
+    const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
+    const double c = fabs(n0 * d0 + n1 * d1 + n2 * d2) / (sqrt(n0 * n0 + n1 * n1 + n2 * n2) * sqrt(d0 * d0 + d1 * d1 + d2 * d2));
+    inc = acos(fmin(1.0, c));                       // 0 / 0 on a face of zero area: NaN
+  }
+  inc_out[g] = inc;
 }
 
 inline unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
@@ -352,6 +413,26 @@ int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_t
   if (!dirs || !t_min || !poses || !face_out || !t_out || !bary_out) return DC_ERR_ARG;
   raycast_kernel<<<grid_of(total, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(child, node_box, leaf_tri, leaf_face, n_faces, dirs, t_min,
                                                                                     n_rays, poses, total, cull, face_out, t_out, bary_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_raycast_rays(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                    const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                    double t_min, int cull, int32_t* face_out, double* t_out, double* inc_out, dcStream_t stream) {
+  if (n_faces < 1 || n < 0 || n_scans < 0 || !node_box || !leaf_tri || !leaf_face || (n_faces > 1 && !child) || !(t_min == t_min))
+    return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (n_scans < 1 || !vps || !dirs || !scan_offset || !poses || !face_out || !t_out || !inc_out) return DC_ERR_ARG;
+  if (dtype == DC_F32)
+    raycast_rays_kernel<float><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const float*)vps, (const float*)dirs, n, scan_offset, poses, n_scans, t_min, cull,
+        face_out, t_out, inc_out);
+  else
+    raycast_rays_kernel<double><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, n, scan_offset, poses, n_scans, t_min, cull,
+        face_out, t_out, inc_out);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

@@ -8,7 +8,9 @@ offsets / distance weights, any of the reference's models or none) every sequenc
 
 ``eval_loss`` / ``eval_loss_all`` are the reference's test-set evaluation (eval.py:115-211); ``eval_slam`` / ``eval_slam_all`` its
 localization-accuracy evaluation (eval.py:214-290) with this package's ICP mapper instead of ROS (slam.py); ``eval_map`` /
-``eval_map_all`` the accuracy of the map against the ground-truth mesh (scripts/mapping_accuracy:82-118).  ``landscape_clouds`` evaluates
+``eval_map_all`` the accuracy of the map against the ground-truth mesh (scripts/mapping_accuracy:82-118); ``eval_bias`` /
+``eval_bias_all`` the depth error of every ray against the mesh over the true incidence angle and the supervised fit
+(scripts/bias_estimation, depth_bias.py).  ``landscape_clouds`` evaluates
 the loss for many candidate weights of the model at once: every model with a basis form is affine in its weights, so a
 neighbourhood's covariance is a quadratic form in w and one pass over the neighbours (dc_sequence_landscape) serves every
 row; configurations outside that path loop over ``eval_loss_clouds`` ("Loss landscape").
@@ -21,14 +23,14 @@ from collections import Counter
 import numpy as np
 import torch
 
-from .config import SLAM, Config, NeighborhoodType, PoseCorrection, loss_eval_csv, map_eval_csv, nonempty, slam_eval_csv
+from .config import SLAM, Config, NeighborhoodType, PoseCorrection, bias_eval_csv, loss_eval_csv, map_eval_csv, nonempty, slam_eval_csv
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry, SequencePlan, consistency_loss
 from .preproc import (compute_neighborhood_features, global_cloud, global_cloud_mask, local_feature_cloud,
                       offset_cloud)
 from .transform import corrected_poses, xyz_axis_angle_to_matrix
 
-__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_loss_landscape', 'eval_map', 'eval_map_all', 'eval_slam', 'eval_slam_all',
+__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_bias', 'eval_bias_all', 'eval_loss_landscape', 'eval_map', 'eval_map_all', 'eval_slam', 'eval_slam_all',
            'initialize_pose_corrections', 'fused_supported', 'landscape_clouds', 'landscape_paths', 'PlanCloud', 'LazyFeatureCloud']
 
 
@@ -352,10 +354,10 @@ def eval_slam_all(cfg: Config):
 MAP_EVAL_FIELDS = ('n', 'mean', 'rms', 'median', 'trimmed_mean', 'signed_mean')
 
 
-def _dataset_mesh(ds, name):
+def _dataset_mesh(ds, name, who='eval_map'):
     get = getattr(ds, 'get_mesh', None)          # reached through the Forwarding wrappers
     if not callable(get):
-        raise ValueError('dataset %s gives no ground-truth mesh (no get_mesh()): eval_map needs one' % name)
+        raise ValueError('dataset %s gives no ground-truth mesh (no get_mesh()): %s needs one' % (name, who))
     return get()
 
 
@@ -413,6 +415,99 @@ def eval_map_all(cfg: Config):
         eval_cfg.test_poses_path = []
         eval_cfg.map_eval_csv = map_eval_csv(cfg.log_dir, suffix)
         out[suffix] = eval_map(cfg=eval_cfg)
+    return out
+
+
+# ---- depth bias against the ground-truth mesh -------------------------------------------------------------------------------------
+def _fmt_weights(w):
+    return ','.join('%.9g' % x for x in np.asarray(w, dtype=np.float64).reshape(-1))
+
+
+def bias_eval_line(name, res, fit):
+    """One line of cfg.bias_eval_csv: ``name used mean_abs rms rel_rms (before) mean_abs rms rel_rms (after, nan without a model)
+    angle_err_rms w_true_angles w_est_angles`` (the weight vectors comma-separated)."""
+    b = res['before']['overall']
+    a = res['after']['overall'] if res.get('after') else {k: float('nan') for k in b}
+    vals = [b['mean_abs'], b['rms'], b['rel_rms'], a['mean_abs'], a['rms'], a['rel_rms'], b['angle_err_rms']]
+    return '%s %d %s %s %s\n' % (name, int(res['before']['totals']['used']), ' '.join('%.9f' % v for v in vals),
+                                 _fmt_weights(fit['w_true_angles']), _fmt_weights(fit['w_est_angles']))
+
+
+def write_bias_curve_csv(path, name, res):
+    """Append the per-bin table of a depth_bias result to ``path``: a header line, then per bin ``name bin angle_lo angle_hi`` and
+    count, mean, rms, mean_abs, rel_mean, rel_rms, angle_err_mean, angle_err_rms before and after (nan without a model)."""
+    from .io import append
+    from .metrics import BIAS_BIN_FIELDS
+    edges = res['bin_edges'].cpu().numpy()
+    cols = {}
+    for part in ('before', 'after'):
+        for f in BIAS_BIN_FIELDS:
+            cols[part, f] = res[part][f].detach().cpu().numpy() if res.get(part) else np.full(len(edges) - 1, np.nan)
+    lines = ['# name bin angle_lo angle_hi ' + ' '.join('%s_%s' % (f, part) for part in ('before', 'after') for f in BIAS_BIN_FIELDS) + '\n']
+    for b in range(len(edges) - 1):
+        lines.append('%s %d %.9f %.9f %s\n' % (name, b, edges[b], edges[b + 1], ' '.join(
+            '%.9g' % cols[part, f][b] for part in ('before', 'after') for f in BIAS_BIN_FIELDS)))
+    append(path, ''.join(lines))
+
+
+def eval_bias(cfg: Config, test_datasets=None, model=None):
+    """Depth bias of every test sequence against its dataset's mesh (what scripts/bias_estimation and depth_bias.py measure with a
+    board; DESIGN "Depth bias against the mesh"): each scan goes through preproc.filtered_cloud and local_feature_cloud -- the
+    estimated incidence angles and the planarity mask train() sees -- and its rays are cast in the mesh frame with the poses the
+    dataset yields.  Only ground-truth poses are meaningful here: with any other pose the difference to the mesh measures the pose
+    error, not the sensor's bias, so there is no 'slam' option.  metrics.depth_bias gives the error over the true incidence angle
+    before and after ``model`` (from the configuration unless given); metrics.fit_bias the weights a supervised fit of the model's
+    class (ScaledPolynomial [2, 4] for a model that is no polynomial) finds at true and at estimated angles.  Prints one line per
+    sequence, appends bias_eval_line to ``cfg.bias_eval_csv`` and the per-bin table to ``cfg.bias_eval_curve_csv`` when set, and
+    returns the per-sequence dicts of depth_bias with ``name`` and ``fit``."""
+    from .io import append
+    from .metrics import depth_bias, fit_bias
+    from .preproc import filtered_cloud
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    meshes = [_dataset_mesh(ds, name, 'eval_bias') for name, ds in zip(test_names, test_datasets)]
+    if torch.device(cfg.device).type != 'cuda':
+        raise RuntimeError('eval_bias needs a GPU (cfg.device %s): depth_correction_amd has no CPU path' % (cfg.device,))
+    results = []
+    for name, ds, mesh in zip(test_names, test_datasets, meshes):
+        clouds, poses = [], []
+        for cloud, pose in ds:
+            clouds.append(local_feature_cloud(filtered_cloud(cloud, cfg), cfg))
+            poses.append(np.asarray(pose, dtype=np.float64))
+        res = depth_bias(clouds, np.stack(poses), mesh, model=model, bins=cfg.bias_eval_bins, max_residual=cfg.bias_eval_max_residual,
+                         cull=cfg.bias_eval_cull)
+        fit = res['fit'] = fit_bias(res, res['fit_class'], res['fit_exponent'])
+        res['name'] = name
+        b, a = res['before']['overall'], (res['after'] or {}).get('overall')
+        print('Depth bias on %s: %d of %d rays used, mean |r| %.6f m, rms %.6f m, rel. rms %.6f%s, angle error rms %.6f rad; '
+              'supervised %s fit: w [%s] at true angles, [%s] at estimated angles.'
+              % (name, int(res['before']['totals']['used']), int(res['before']['totals']['rays']), b['mean_abs'], b['rms'], b['rel_rms'],
+                 ' (after correction: %.6f m, %.6f m, %.6f)' % (a['mean_abs'], a['rms'], a['rel_rms']) if a else '',
+                 b['angle_err_rms'], fit['model_class'], _fmt_weights(fit['w_true_angles']), _fmt_weights(fit['w_est_angles'])))
+        if fit['message']:
+            print('Supervised fit on %s: %s.' % (name, fit['message']))
+        if cfg.bias_eval_csv:
+            append(cfg.bias_eval_csv, bias_eval_line(name, res, fit))
+        if cfg.bias_eval_curve_csv:
+            write_bias_curve_csv(cfg.bias_eval_curve_csv, name, res)
+        results.append(res)
+    return results
+
+
+def eval_bias_all(cfg: Config):
+    """eval_bias on the train, val and test subsets with the poses the datasets yield, one CSV file per subset (the shape of
+    eval_map_all)."""
+    out = {}
+    for names, suffix in zip([cfg.train_names, cfg.val_names, cfg.test_names], ['train', 'val', 'test']):
+        if not names:
+            continue
+        eval_cfg = cfg.copy()
+        eval_cfg.test_names = names
+        eval_cfg.train_poses_path = []
+        eval_cfg.val_poses_path = []
+        eval_cfg.test_poses_path = []
+        eval_cfg.bias_eval_csv = bias_eval_csv(cfg.log_dir, suffix)
+        eval_cfg.bias_eval_curve_csv = ''
+        out[suffix] = eval_bias(cfg=eval_cfg)
     return out
 
 

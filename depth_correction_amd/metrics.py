@@ -7,14 +7,28 @@ instead of pytorch3d's ``knn_points``; batches are lists / a leading dimension o
 
 ``point_to_mesh_distance`` / ``map_accuracy``: a map against the ground-truth MESH (what scripts/mapping_accuracy:82-118 does
 against a surveyed cloud): the exact distance from every map point to the nearest triangle (dc_mesh_closest) and its
-statistics; DESIGN "Map accuracy"."""
+statistics; DESIGN "Map accuracy".
+
+``depth_bias`` / ``fit_bias``: the direct measurement behind the reference's scripts/bias_estimation and depth_bias.py: the rays of
+measured clouds are cast against the ground-truth mesh (dc_raycast_rays), the depth error is binned over the TRUE incidence angle,
+the estimated angles are compared with the true ones, and the weights a supervised fit to ground truth would have found come from
+the normal equations dc_bias_accumulate sums; DESIGN "Depth bias against the mesh"."""
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 from . import ops
 
-__all__ = ['chamfer_distance', 'map_accuracy', 'map_statistics', 'point_to_mesh_distance']
+__all__ = ['bias_statistics', 'chamfer_distance', 'depth_bias', 'fit_bias', 'fitted_model', 'map_accuracy', 'map_statistics',
+           'point_to_mesh_distance']
+
+BIAS_TOTALS, BIAS_BIN_COLS = 5, 9                    # include/dc_hip.h: DC_BIAS_TOTALS, DC_BIAS_BIN_COLS
+BIAS_TOTAL_NAMES = ('rays', 'masked', 'hits', 'used', 'beyond_gate')
+BIAS_BIN_FIELDS = ('count', 'mean', 'rms', 'mean_abs', 'rel_mean', 'rel_rms', 'angle_err_mean', 'angle_err_rms')
+BIAS_OVERALL_FIELDS = ('mean_abs', 'rms', 'rel_rms', 'angle_err_rms')
 
 
 def _as_batch(x):
@@ -109,3 +123,185 @@ def map_accuracy(points, mesh, inlier_ratio=0.8, n_samples=None, seed=135):
         finite = pts[torch.isfinite(dist)].to(torch.float64).contiguous()
         out['completeness_mean'] = float(chamfer_distance(surface, finite)) if finite.shape[0] else float('nan')
     return out
+
+
+# ---- depth bias against the mesh -------------------------------------------------------------------------------------------------
+def _bias_system_len(p):
+    return 2 + p + p * (p + 1) // 2
+
+
+def _bias_shape(count, n_terms=None):
+    """(n_bins, n_terms) of an ``out`` of dc_bias_accumulate with ``count`` entries."""
+    for p in ([int(n_terms)] if n_terms else range(1, 5)):
+        rest = count - BIAS_TOTALS - 2 * _bias_system_len(p)
+        if rest > 0 and rest % BIAS_BIN_COLS == 0:
+            return rest // BIAS_BIN_COLS, p
+    raise ValueError('%d values are not an out of dc_bias_accumulate%s' % (count, ' with %d terms' % n_terms if n_terms else ''))
+
+
+def bias_statistics(out, n_bins):
+    """The finishing arithmetic of depth_bias on the sums of dc_bias_accumulate (``out`` f64 tensor, any device; layout in
+    include/dc_hip.h): dict of ``totals`` (rays, masked, hits, used, beyond_gate: floats), the per-bin f64 tensors count, mean, rms,
+    mean_abs (of r = d - t, metres), rel_mean, rel_rms (of r / d), angle_err_mean, angle_err_rms (of the estimated minus the true
+    incidence angle, over the rays that have an estimate) -- NaN in an empty bin -- and the same over all used rays as floats
+    (mean, rms, mean_abs, rel_mean, rel_rms, angle_err_mean, angle_err_rms).  rms is sqrt(sum x^2 / count): about zero, not about
+    the mean."""
+    out = out.detach().reshape(-1).to(torch.float64)
+    b = int(n_bins)
+    if out.numel() < BIAS_TOTALS + BIAS_BIN_COLS * b:
+        raise ValueError('out holds %d values, %d bins need at least %d' % (out.numel(), b, BIAS_TOTALS + BIAS_BIN_COLS * b))
+    rows = out[BIAS_TOTALS:BIAS_TOTALS + BIAS_BIN_COLS * b].reshape(b, BIAS_BIN_COLS)
+
+    def finish(r):
+        nan = torch.full_like(r[..., 0], float('nan'))
+        n, na = r[..., 0], r[..., 8]
+        div = lambda num, den: torch.where(den > 0, num / den.clamp(min=1.0), nan)
+        return dict(count=n, mean=div(r[..., 1], n), rms=div(r[..., 2], n).sqrt(), mean_abs=div(r[..., 3], n), rel_mean=div(r[..., 4], n),
+                    rel_rms=div(r[..., 5], n).sqrt(), angle_err_mean=div(r[..., 6], na), angle_err_rms=div(r[..., 7], na).sqrt())
+
+    res = finish(rows)
+    res['totals'] = {k: float(v) for k, v in zip(BIAS_TOTAL_NAMES, out[:BIAS_TOTALS].tolist())}
+    # the overall figures: the bins added in bin order (one fixed order)
+    res['overall'] = {k: float(v) for k, v in finish(rows.sum(dim=0)).items()}
+    return res
+
+
+def _cat_field(clouds, name, n_cols):
+    parts = [getattr(c, name) for c in clouds]
+    if any(p is None for p in parts):
+        return None
+    parts = [p.detach().reshape(-1, n_cols) if n_cols else p.detach().reshape(-1) for p in parts]
+    return torch.cat(parts).contiguous()
+
+
+def _fit_basis(model, fit_class, fit_exponent):
+    kind = getattr(model, 'kernel_kind', None)
+    if fit_class is None:
+        fit_class = kind if kind in ('Polynomial', 'ScaledPolynomial') else 'ScaledPolynomial'
+    fit_class = fit_class if isinstance(fit_class, str) else fit_class.__name__
+    if fit_exponent is None:
+        fit_exponent = model.exponent.detach().reshape(-1).tolist() if kind in ('Polynomial', 'ScaledPolynomial') else [2.0, 4.0]
+    return fit_class, [float(e) for e in fit_exponent]
+
+
+def depth_bias(clouds, poses, mesh, model=None, bins=18, max_residual=None, cull=True, fit_class=None, fit_exponent=None):
+    """Depth error of every ray of the DepthClouds ``clouds`` (one sequence, on a GPU, sensor frame) against ``mesh``
+    (mesh.TriangleMesh, the frame of ``poses`` [S,4,4]: world from sensor; only ground-truth poses give a meaningful answer), as a
+    function of the TRUE incidence angle.  The rays (vps, dirs) are cast once (ops.raycast_rays: true depth t and true angle per
+    ray); the clouds' ``mask`` and ``inc_angles`` are used when present.  Statistics (bias_statistics) are taken of the depths as
+    given -> ``before`` and, with a ``model``, of the depths of ``model(cloud)`` -> ``after`` (else None), in ``bins`` equal bins of
+    [0, pi/2] (``bin_edges`` f64 [bins+1]); rays with |d - t| > ``max_residual`` (the ray hit something the mesh does not hold, or
+    missed what it holds) are counted and left out.  ``before['out']`` / ``after['out']`` keep the raw sums with the normal equations
+    of fit_bias for ``fit_class`` / ``fit_exponent`` (default: the model's class and exponents when it is a polynomial, else
+    ScaledPolynomial with [2, 4]).  ``face`` / ``t`` / ``inc`` are the cast's per-ray outputs, ``inc_est`` / ``mask`` and
+    ``before['depth']`` / ``after['depth']`` the per-ray inputs of the sums, all scan-major in the order of ``clouds``."""
+    clouds = list(clouds)
+    if not clouds:
+        raise ValueError('depth_bias needs at least one cloud')
+    dev = clouds[0].depth.device
+    if dev.type != 'cuda':
+        raise RuntimeError('depth_bias needs clouds on a GPU (depth_correction_amd has no CPU path)')
+    fit_class, fit_exponent = _fit_basis(model, fit_class, fit_exponent)
+    dirs = _cat_field(clouds, 'dirs', 3)
+    vps = torch.cat([c.vps.detach().reshape(-1, 3).expand(len(c), 3) for c in clouds]).to(dirs.dtype).contiguous()
+    offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+    T = torch.as_tensor(np.asarray(poses.detach().cpu() if isinstance(poses, torch.Tensor) else poses, dtype=np.float64).reshape(-1, 4, 4),
+                        device=dev).contiguous()
+    if T.shape[0] != len(clouds):
+        raise ValueError('%d clouds but %d poses' % (len(clouds), T.shape[0]))
+    bvh = mesh.on_device(dev)[3]
+    face, t, inc = ops.raycast_rays(bvh, vps, dirs, offsets, T, t_min=0.0, cull=cull)
+    inc_est = _cat_field(clouds, 'inc_angles', 0)
+    mask = None
+    if any(c.mask is not None for c in clouds):
+        mask = torch.cat([c.mask.detach().reshape(-1).bool() if c.mask is not None else torch.ones((len(c),), dtype=torch.bool, device=dev)
+                          for c in clouds]).contiguous()
+    n_terms = len(fit_exponent)
+    ws = ops.bias_workspace(bins, n_terms, dev)
+
+    def stats(cs):
+        depth = _cat_field(cs, 'depth', 0)
+        est = None if inc_est is None else inc_est.to(depth.dtype)
+        out = ops.bias_accumulate(depth, est, mask, face, t, inc, fit_class, fit_exponent, n_bins=bins, max_residual=max_residual, ws=ws)
+        res = bias_statistics(out, bins)
+        res['out'], res['depth'] = out, depth
+        return res
+
+    res = dict(bins=int(bins), bin_edges=torch.linspace(0.0, math.pi / 2, int(bins) + 1, dtype=torch.float64), fit_class=fit_class,
+               fit_exponent=fit_exponent, face=face, t=t, inc=inc, inc_est=inc_est, mask=mask, before=stats(clouds), after=None)
+    if model is not None:
+        with torch.no_grad():
+            res['after'] = stats([model(c) for c in clouds])
+    return res
+
+
+def _solve_normal(sys_, p):
+    """(w [p], residual rms, cond(A), n, message or None) of one system of dc_bias_accumulate: count, upper triangle, b, sum y^2."""
+    n = float(sys_[0])
+    A = np.zeros((p, p))
+    iu = np.triu_indices(p)
+    A[iu] = sys_[1:1 + len(iu[0])]
+    A = A + np.triu(A, 1).T
+    b = sys_[1 + len(iu[0]):1 + len(iu[0]) + p]
+    yy = float(sys_[1 + len(iu[0]) + p])
+    nan_w = np.full(p, np.nan)
+    if n < p:
+        return nan_w, float('nan'), float('nan'), n, '%d rays for %d weights' % (n, p)
+    if not (np.isfinite(A).all() and np.isfinite(b).all()):
+        return nan_w, float('nan'), float('nan'), n, 'the sums are not finite'
+    # scale to a unit diagonal before judging the rank: the columns gamma^e differ by orders of magnitude by construction
+    dg = np.sqrt(np.diag(A))
+    if not (dg > 0).all():
+        return nan_w, float('nan'), float('inf'), n, 'a basis column is zero on every ray'
+    As = A / np.outer(dg, dg)
+    cond = float(np.linalg.cond(As))
+    if not np.isfinite(cond) or cond > 1e13:
+        return nan_w, float('nan'), cond, n, 'the system is singular (condition number %.3g after diagonal scaling)' % cond
+    w = np.linalg.solve(As, b / dg) / dg
+    sse = yy - 2.0 * float(w @ b) + float(w @ A @ w)
+    return w, math.sqrt(max(sse, 0.0) / n), cond, n, None
+
+
+def fit_bias(stats_or_out, model_class, exponent):
+    """The supervised fit to ground truth: the weights of ``model_class`` ('Polynomial': d - t = sum_k w_k gamma^e_k, or
+    'ScaledPolynomial': (d - t) / d = sum_k w_k gamma^e_k; a name or a class of model.py) with the exponents ``exponent`` that
+    minimise the squared residual over the used rays, once with the basis at the TRUE incidence angles (``w_true_angles``: the
+    upper bound self-supervised training is compared with) and once at the ESTIMATED ones (``w_est_angles``).  ``stats_or_out``: a
+    result of depth_bias (its ``before`` sums), one of its ``before`` / ``after`` dicts, or the raw ``out`` of ops.bias_accumulate
+    taken for this class and these exponents.  Both models are linear in w: the P x P normal equations are solved in fp64 on the
+    host.  Returns numpy weights, ``rms_true_angles`` / ``rms_est_angles`` (the residual rms, from the sums sum y^2 - 2 w.b + w.A w: an exact
+    fit leaves the rounding of those sums, up to sqrt(3 n 2^-53) of the target's rms), ``cond_true_angles`` / ``cond_est_angles`` (condition number of A scaled to a unit diagonal),
+    ``n_true_angles`` / ``n_est_angles`` and ``message``: a singular system (too few rays, every angle zero, ...) gives NaN weights
+    and says why; it does not raise."""
+    name = model_class if isinstance(model_class, str) else model_class.__name__
+    if name not in ('Polynomial', 'ScaledPolynomial'):
+        raise ValueError("fit_bias fits 'Polynomial' or 'ScaledPolynomial', got %r" % (name,))
+    e = [float(x) for x in (exponent.detach().reshape(-1).tolist() if isinstance(exponent, torch.Tensor) else np.asarray(exponent).reshape(-1))]
+    p = len(e)
+    src = stats_or_out
+    if isinstance(src, dict):
+        if 'fit_class' in src and (src['fit_class'] != name or list(src['fit_exponent']) != e):
+            raise ValueError('these statistics hold the systems of %s %s, not of %s %s'
+                             % (src['fit_class'], src['fit_exponent'], name, e))
+        src = src['before'] if 'before' in src else src
+        src = src['out']
+    out = (src.detach().cpu().numpy() if isinstance(src, torch.Tensor) else np.asarray(src)).astype(np.float64).reshape(-1)
+    n_bins, _ = _bias_shape(out.size, p)
+    base, ln = BIAS_TOTALS + BIAS_BIN_COLS * n_bins, _bias_system_len(p)
+    res, messages = dict(model_class=name, exponent=e), []
+    for s, key in enumerate(('true_angles', 'est_angles')):
+        w, rms, cond, n, msg = _solve_normal(out[base + s * ln:base + (s + 1) * ln], p)
+        res['w_' + key], res['rms_' + key], res['cond_' + key], res['n_' + key] = w, rms, cond, n
+        if msg:
+            messages.append('%s: %s' % (key, msg))
+    res['message'] = '; '.join(messages) if messages else None
+    return res
+
+
+def fitted_model(fit, which='true_angles', device=None):
+    """A model of the fitted class carrying the weights of a fit_bias result (``which``: 'true_angles' or 'est_angles')."""
+    from .model import model_by_name
+    if which not in ('true_angles', 'est_angles'):
+        raise ValueError("which must be 'true_angles' or 'est_angles', got %r" % (which,))
+    kw = {} if device is None else {'device': torch.device(device)}
+    return model_by_name(fit['model_class'])(w=[float(x) for x in fit['w_' + which]], exponent=list(fit['exponent']), **kw)

@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'mesh_closest', 'mesh_sample',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
 ]
 
@@ -1089,6 +1089,105 @@ def raycast(bvh, dirs, poses, t_min, cull=True):
                            ptr(dirs), ptr(t_min), r, ptr(poses), p, 1 if cull else 0, ptr(face), ptr(t), ptr(bary), stream_ptr()),
           'dc_raycast')
     return face, t, bary
+
+
+@on_device
+def raycast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, cull=True):
+    """Closest hits of the rays of measured clouds: ray i (view point vps[i], direction dirs[i], f32 | f64 [N,3], sensor frame,
+    scan-major) of the scan s with scan_offset[s] <= i < scan_offset[s+1] (S+1 integers from 0 to N: a sequence, checked here, or an int64
+    device tensor, taken as it is) is cast
+    from R_s vps[i] + t_s along R_s dirs[i] (poses f64 [S,4,4], world from sensor) -> (face i32 [N] (-1 = miss), t f64 [N] in units
+    of |dirs[i]| (inf on a miss), inc f64 [N] the incidence angle on the face that was hit (NaN on a miss)).  Hits count beyond
+    ``t_min`` (and facing the ray with ``cull``); traversal and tie rule are raycast's.  One launch (dc_raycast_rays)."""
+    dev = bvh.leaf_face.device
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n = dirs.shape[0]
+    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
+    code = dtype_code(dirs)
+    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
+    s = poses.shape[0]
+    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
+        # offsets already on the device are not read back (no synchronisation): the kernel clamps the scan index, so wrong offsets
+        # give wrong poses, never a read outside ``poses``
+        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)
+    else:
+        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
+        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    if n and s < 1:
+        raise ValueError('rays need at least one pose')
+    tm = float(t_min)
+    if tm != tm:
+        raise ValueError('t_min must not be NaN')
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    t = torch.empty((n,), dtype=torch.float64, device=dev)
+    inc = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n == 0:
+        return face, t, inc
+    off = off.to(dev)
+    nf = bvh.n_faces
+    check(lib().dc_raycast_rays(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                                ptr(vps), ptr(dirs), code, n, ptr(off), ptr(poses), s, tm, 1 if cull else 0, ptr(face), ptr(t),
+                                ptr(inc), stream_ptr()), 'dc_raycast_rays')
+    return face, t, inc
+
+
+# ------------------------------------------------------------------------------------------------
+# depth bias against the mesh (dc_bias.hip)
+# ------------------------------------------------------------------------------------------------
+def bias_out_count(n_bins, n_terms):
+    """Length of bias_accumulate's ``out`` (DC_BIAS_OUT_COUNT of include/dc_hip.h)."""
+    return nv.DC_BIAS_TOTALS + nv.DC_BIAS_BIN_COLS * n_bins + 2 * (2 + n_terms + n_terms * (n_terms + 1) // 2)
+
+
+@on_device
+def bias_accumulate(depth, inc_est, mask, face, t_true, inc_true, model_kind, exponent, n_bins=18, max_residual=None, out=None, ws=None):
+    """Binned statistics of r = depth - t_true over the true incidence angle and the normal equations of the supervised fit
+    (dc_bias_accumulate; definitions and the layout of the returned f64 [bias_out_count(n_bins, P)] in include/dc_hip.h).  depth /
+    inc_est f32 | f64 [N] or [N,1] (inc_est optional), mask bool | uint8 [N] (optional), face i32 / t_true f64 / inc_true f64 [N] of
+    raycast_rays, model_kind 'Polynomial' | 'ScaledPolynomial', exponent the P <= 4 exponents (host floats), n_bins <= 256.  ``out`` /
+    ``ws`` (bias_workspace) from the caller make the call allocation-free."""
+    need(face, (None,), dtype=torch.int32, name='face')
+    dev, n = face.device, face.shape[0]
+    depth = depth.reshape(-1) if isinstance(depth, torch.Tensor) else depth
+    need(depth, (n,), name='depth', device=dev)
+    code = dtype_code(depth)
+    if inc_est is not None:
+        inc_est = inc_est.reshape(-1) if isinstance(inc_est, torch.Tensor) else inc_est
+        need(inc_est, (n,), dtype=depth.dtype, name='inc_est', device=dev)
+    if mask is not None:
+        need(mask, (n,), name='mask', device=dev)
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        elif mask.dtype != torch.uint8:
+            raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
+    need(t_true, (n,), dtype=torch.float64, name='t_true', device=dev)
+    need(inc_true, (n,), dtype=torch.float64, name='inc_true', device=dev)
+    if model_kind not in ('Polynomial', 'ScaledPolynomial'):
+        raise ValueError("model_kind must be 'Polynomial' or 'ScaledPolynomial', got %r" % (model_kind,))
+    e = [float(x) for x in (exponent.detach().reshape(-1).tolist() if isinstance(exponent, torch.Tensor) else exponent)]
+    p, b = len(e), int(n_bins)
+    if not 1 <= p <= nv.DC_BIAS_MAX_TERMS or not 1 <= b <= nv.DC_BIAS_MAX_BINS:
+        raise ValueError('bias_accumulate takes 1..%d terms and 1..%d bins, got %d and %d' % (nv.DC_BIAS_MAX_TERMS, nv.DC_BIAS_MAX_BINS, p, b))
+    count = bias_out_count(b, p)
+    if out is None:
+        out = torch.empty((count,), dtype=torch.float64, device=dev)
+    need(out, (count,), dtype=torch.float64, name='out', device=dev)
+    nbytes = lib().dc_bias_workspace_bytes(b, p)
+    if ws is None:
+        ws = _ws(nbytes, dev)
+    need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
+    e_host = (ctypes.c_double * p)(*e)
+    check(lib().dc_bias_accumulate(ptr(depth), ptr(inc_est), code, ptr(mask), ptr(face), ptr(t_true), ptr(inc_true), n,
+                                   nv.MODEL_KINDS[model_kind], ctypes.cast(e_host, ctypes.c_void_p), p, b,
+                                   0.0 if max_residual is None else float(max_residual), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+          'dc_bias_accumulate')
+    return out
+
+
+def bias_workspace(n_bins, n_terms, device):
+    """Workspace of bias_accumulate for the given sizes (uint8 tensor)."""
+    return _ws(lib().dc_bias_workspace_bytes(int(n_bins), int(n_terms)), device)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -808,6 +808,51 @@ int dc_bvh_build(const double* verts, int64_t n_verts, const int32_t* faces, int
 int dc_raycast(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
                const double* dirs, const double* t_min, int64_t n_rays, const double* poses, int n_poses, int cull, int32_t* face_out,
                double* t_out, double* bary_out, dcStream_t stream);
+/* Closest hit of the rays of MEASURED clouds: ray i (view point vps[i], direction dirs[i]: DC_F32 | DC_F64 [n,3], sensor frame,
+ * scan-major; fp32 is converted exactly) belongs to the scan s with scan_offset[s] <= i < scan_offset[s+1] (DEVICE int64
+ * [n_scans+1], non-decreasing from 0 to n; empty scans allowed) and is cast from R_s vps[i] + t_s along R_s dirs[i] (poses DEVICE
+ * double [n_scans,4,4], world from sensor), both formed in fp64 with dc_raycast's expressions; traversal, box test, watertight
+ * triangle test, t > t_min / culling and the tie rule are dc_raycast's (one device function), so with vps = 0, the tiled pattern
+ * and the same poses face_out / t_out are bit-equal to dc_raycast's.  face_out int32 [n] (-1 = miss), t_out double [n] in units of
+ * |dirs[i]| (+inf on a miss), inc_out double [n] the incidence angle on the winning triangle, arccos(min(1, |n . d| / (|n| |d|)))
+ * with n = (v1 - v0) x (v2 - v0) in fp64 from that triangle's leaf_tri row (NaN on a miss, and on a face of zero area).  Every
+ * scan in one launch; n == 0 launches nothing. */
+int dc_raycast_rays(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                    const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                    double t_min, int cull, int32_t* face_out, double* t_out, double* inc_out, dcStream_t stream);
+
+/* ---- depth bias against the mesh (depth_correction_amd/csrc/dc_bias.hip, per-ray terms in dc_biasmath.h; DESIGN "Depth bias against
+ * the mesh") ----
+ * Per ray i of n: d = depth[i], g_est = inc_est[i] (DC_F32 | DC_F64 [n]; inc_est optional), the cast's face[i], t = t_true[i],
+ * g = inc_true[i] (dc_raycast_rays); r = d - t, rho = r / d, delta = g_est - g.  A ray is USED when mask[i] != 0 (uint8 [n]; NULL:
+ * every ray), face[i] >= 0 with t and g finite, d > 0 and finite, and |r| <= max_residual (max_residual <= 0: no gate).  Its bin is
+ * b = min(n_bins - 1, floor(g n_bins / (pi / 2))).  With y = rho for DC_MODEL_SCALED_POLYNOMIAL, y = r for DC_MODEL_POLYNOMIAL and
+ * phi_k(x) = x^exponent[k] (HOST double [n_terms]) the used rays also feed two least-squares systems for the model's weights, one
+ * with phi at g and one with phi at g_est (the latter, and the delta sums, take the used rays with a finite g_est only).
+ * out double [DC_BIAS_OUT_COUNT(n_bins, n_terms)]:
+ *   [0 .. 4]                                totals: rays, masked-in rays, masked-in rays that hit, used rays, rays that passed every
+ *                                           test but the gate
+ *   [DC_BIAS_TOTALS + DC_BIAS_BIN_COLS b + c]  bin b, column c: 0 count, 1 sum r, 2 sum r^2, 3 sum |r|, 4 sum rho, 5 sum rho^2,
+ *                                           6 sum delta, 7 sum delta^2, 8 count of the delta terms
+ *   [DC_BIAS_TOTALS + DC_BIAS_BIN_COLS n_bins + DC_BIAS_SYSTEM(n_terms) s + ..]  system s (0: true angles, 1: estimated angles):
+ *                                           count, the upper triangle of A = sum phi phi^T row by row (P (P + 1) / 2), sum phi y (P),
+ *                                           sum y^2
+ * 1 <= n_bins <= DC_BIAS_MAX_BINS, 1 <= n_terms <= DC_BIAS_MAX_TERMS, exponents finite (DC_ERR_ARG otherwise).  Reduction: every
+ * block of a bounded grid walks its rays with a grid stride; per trip thread b adds the block's terms of bin b in lane order,
+ * the totals and systems are block sums in a fixed order; a one-block finish adds the block partials in block order.  No atomics:
+ * the same inputs give bit-identical out.  ws: dc_bias_workspace_bytes(n_bins, n_terms); no allocation, copy or synchronisation. */
+#ifndef DC_BIAS_MAX_BINS
+#define DC_BIAS_MAX_BINS 256
+#define DC_BIAS_MAX_TERMS 4
+#define DC_BIAS_TOTALS 5
+#define DC_BIAS_BIN_COLS 9
+#define DC_BIAS_SYSTEM(p) (2 + (p) + (p) * ((p) + 1) / 2)
+#define DC_BIAS_OUT_COUNT(b, p) (DC_BIAS_TOTALS + DC_BIAS_BIN_COLS * (b) + 2 * DC_BIAS_SYSTEM(p))
+#endif
+size_t dc_bias_workspace_bytes(int n_bins, int n_terms);
+int dc_bias_accumulate(const void* depth, const void* inc_est, int dtype, const uint8_t* mask, const int32_t* face, const double* t_true,
+                       const double* inc_true, int64_t n, int model_kind, const double* exponent, int n_terms, int n_bins,
+                       double max_residual, double* out, void* ws, size_t ws_bytes, dcStream_t stream);
 
 /* ---- map accuracy against a mesh (depth_correction_amd/csrc/dc_meshdist.hip; the box-bound margin rule is derived in its header
  * comment, the algorithm in DESIGN "Map accuracy") ----
