@@ -75,8 +75,10 @@ __global__ __launch_bounds__(kBlock) void dispersion_kernel(const T* __restrict_
 // [lo, hi].  One lane per point walks its neighbour row; nothing of the reference's [N, K, 3] tensors is materialised.
 // Arithmetic in the cloud's dtype and in torch's operation order (cosine_similarity normalises each vector by
 // max(|v|, 1e-8) first, then sums the three products; acos of a value an ulp outside [-1, 1] is NaN and, like the
-// reference's amin / amax over a row holding a NaN, removes the point).  Missing neighbours (-1) count as `fill`
-// (the reference overwrites them with the mean of the bounds).
+// reference's amin / amax over a row holding a NaN, removes the point).  The squared norm is torch's too: its CPU
+// reduction accumulates acc = fma(v, v, acc) element by element (linalg_vector_norm's `acc + v * v`, contracted in its
+// AVX2 / AVX-512 builds), which decides whether the cosine of a collinear triple lands on 1 or an ulp beyond.
+// Missing neighbours (-1) count as `fill` (the reference overwrites them with the mean of the bounds).
 template <typename T>
 __global__ __launch_bounds__(kBlock) void shadow_mask_kernel(const T* __restrict__ x, const T* __restrict__ vps, int vps_rows,
                                                              const int32_t* __restrict__ dnbr, int64_t n, int k, T lo, T hi,
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void shadow_mask_kernel(const T* __restrict
   const T xi0 = x[i * 3], xi1 = x[i * 3 + 1], xi2 = x[i * 3 + 2];
   const T* o = vps + (vps_rows == 1 ? 0 : i * 3);
   T a0 = o[0] - xi0, a1 = o[1] - xi1, a2 = o[2] - xi2;
-  const T na = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+  const T na = sqrt(fma(a2, a2, fma(a1, a1, a0 * a0)));
   const T da = na > eps ? na : eps;
   a0 /= da; a1 /= da; a2 /= da;
   T amin = (T)INFINITY, amax = -(T)INFINITY;
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void shadow_mask_kernel(const T* __restrict
     T ang = fill;
     if (j >= 0) {
       T b0 = x[(int64_t)j * 3] - xi0, b1 = x[(int64_t)j * 3 + 1] - xi1, b2 = x[(int64_t)j * 3 + 2] - xi2;
-      const T nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+      const T nb = sqrt(fma(b2, b2, fma(b1, b1, b0 * b0)));
       const T db = nb > eps ? nb : eps;
       b0 /= db; b1 /= db; b2 /= db;
       const T c = a0 * b0 + a1 * b1 + a2 * b2;

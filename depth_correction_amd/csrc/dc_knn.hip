@@ -1202,7 +1202,7 @@ __global__ __launch_bounds__(kBlock) void shadow_group_kernel(const double* __re
   const T xi0 = x[i * 3], xi1 = x[i * 3 + 1], xi2 = x[i * 3 + 2];
   const T* o = vps + (vps_rows == 1 ? 0 : i * 3);
   T a0 = o[0] - xi0, a1 = o[1] - xi1, a2 = o[2] - xi2;
-  const T na = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+  const T na = sqrt(fma(a2, a2, fma(a1, a1, a0 * a0)));       // torch's norm: an fma chain (see shadow_mask_kernel)
   const T da = na > eps ? na : eps;
   a0 /= da; a1 /= da; a2 /= da;
   // The extreme ANGLES are the arc cosines of the extreme COSINES (acos does not increase anywhere): the walk keeps the largest and the
@@ -1252,7 +1252,7 @@ __global__ __launch_bounds__(kBlock) void shadow_group_kernel(const double* __re
         const int64_t jn = sids[p];
         if (has && sqdist(pp, q) <= r2) {
           T b0 = x[jn * 3] - xi0, b1 = x[jn * 3 + 1] - xi1, b2 = x[jn * 3 + 2] - xi2;
-          const T nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+          const T nb = sqrt(fma(b2, b2, fma(b1, b1, b0 * b0)));
           const T db = nb > eps ? nb : eps;
           b0 /= db; b1 /= db; b2 /= db;
           const T cs = a0 * b0 + a1 * b1 + a2 * b2;

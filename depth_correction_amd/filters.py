@@ -29,6 +29,10 @@ def _report(keep, lo, name, hi):
              hi if hi is not None else float('nan')))
 
 
+def _f32(bound):
+    return float(np.float32(bound)) if isinstance(bound, float) else bound
+
+
 def within_bounds(x, min=None, max=None, bounds=None, log_variable=None):
     """Mask of min <= x <= max (inclusive); None / infinite bounds are inactive; NaN fails active bounds."""
     x = x if isinstance(x, torch.Tensor) else torch.tensor(x)
@@ -36,10 +40,12 @@ def within_bounds(x, min=None, max=None, bounds=None, log_variable=None):
         assert min is None and max is None
         min, max = bounds
     keep = torch.ones((x.numel(),), dtype=torch.bool, device=x.device)
+    # the reference wraps a bound in torch.tensor(bound): a float32 scalar whatever x's dtype, compared by its widened
+    # value -- a Python float against an fp64 tensor would compare unrounded
     if min is not None and min > -float('inf'):
-        keep = keep & (x.flatten() >= min)
+        keep = keep & (x.flatten() >= _f32(min))
     if max is not None and max < float('inf'):
-        keep = keep & (x.flatten() <= max)
+        keep = keep & (x.flatten() <= _f32(max))
     if log_variable is not None:
         _report(keep, min, log_variable, max)
     return keep

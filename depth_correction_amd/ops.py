@@ -642,7 +642,11 @@ def _bound(v, default):
     if v is None:
         return default
     v = float(v)
-    return default if v != v else v        # config files encode "unbounded" as nan (config.py:41-43)
+    if v != v:                             # config files encode "unbounded" as nan (config.py:41-43)
+        return default
+    # the reference compares with torch.tensor(bound), a float32 scalar whatever the values' dtype (filters.py:97-104):
+    # the kernels get its widened value (infinities stay what they are)
+    return v if v in (float('-inf'), float('inf')) else torch.tensor(v, dtype=torch.float32).item()
 
 
 @on_device
@@ -813,8 +817,9 @@ def cloud_from_points(points, vps=None, dtype=None, ego_box=None, min_depth=None
     nbytes = lib().dc_cloud_from_points_workspace_bytes(n)
     ws = _ws(nbytes, dev)
     nan = float('nan')
+    # (the depth bounds go through the reference's within_bounds too, filters.py:137: float32-rounded on fp64 rows as well)
     check(lib().dc_cloud_from_points(ptr(points), stride, dtype_code(points), ptr(vps), n, float(ego_box or 0.0),
-                                     nan if min_depth is None else float(min_depth), nan if max_depth is None else float(max_depth),
+                                     _bound(min_depth, nan), _bound(max_depth, nan),
                                      nv.DC_F32 if dtype == torch.float32 else nv.DC_F64, ptr(dirs), ptr(depth), ptr(vps_out),
                                      ptr(index), ptr(count), ptr(ws), nbytes, stream_ptr()), 'dc_cloud_from_points')
     m = int(count.item()) if filtered else n

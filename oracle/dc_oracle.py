@@ -31,7 +31,7 @@ __all__ = [
     'shadow_mask',
     'global_mask', 'knn_bruteforce', 'knn_ckdtree', 'local_mask', 'model_bias', 'model_apply', 'pointwise_loss',
     'point_to_plane', 'points_from', 'radius_bruteforce', 'radius_ckdtree', 'reduce_loss', 'trace',
-    'transform_cloud', 'within_bounds', 'xyz_axis_angle_to_matrix', 'nn1_correspondences',
+    'transform_cloud', 'within_bounds', 'filter_grid', 'voxel_face_cloud', 'xyz_axis_angle_to_matrix', 'nn1_correspondences',
 ]
 
 
@@ -261,13 +261,47 @@ def features(points, neighbors, dirs, weights=None, scale=None):
 # K13: filters / masks.  filters.py:85-113,184-254 ; preproc.py:53-62,122-164 ; depth_cloud.py:314-326
 # ----------------------------------------------------------------------------------------------
 def within_bounds(x, lo=None, hi=None):
-    """filters.py:85-113: inclusive bounds; None / +-inf = unbounded; NaN compares False."""
+    """filters.py:85-113: inclusive bounds; None / +-inf = unbounded (a NaN bound too: it fails ``> -inf``); NaN values
+    compare False.  A bound is wrapped in ``torch.tensor(bound)`` (:98-103): a float32 scalar whatever x's dtype, so an
+    fp64 x is compared with the WIDENED float32 value of the bound, not with the Python float."""
     keep = torch.ones((x.numel(),), dtype=torch.bool)
     if lo is not None and lo > -float('inf'):
-        keep = keep & (x.flatten() >= lo)
+        keep = keep & (x.flatten() >= (lo if isinstance(lo, torch.Tensor) else torch.tensor(lo)))
     if hi is not None and hi < float('inf'):
-        keep = keep & (x.flatten() <= hi)
+        keep = keep & (x.flatten() <= (hi if isinstance(hi, torch.Tensor) else torch.tensor(hi)))
     return keep
+
+
+def filter_grid(points, grid_res, keep='random', preserve_order=False, rng=None):
+    """filters.py:24-82 with only_mask=True: the indices of one survivor per voxel of edge ``grid_res``.  The voxel of a
+    point is ``np.floor(x / grid_res).astype(int)`` on the array AS GIVEN (:42: a float32 array divides in float32).
+    Points are fed to a dict {voxel: index} in the processing sequence -- identity ('last'), reversed ('first') or the
+    index list shuffled by ``rng`` ('random') -- so the LAST point of the sequence in a voxel survives and the voxels are
+    listed in order of first appearance (:64-68), or the survivors by index with ``preserve_order``."""
+    assert keep in ('first', 'random', 'last')
+    keys = np.floor(np.asarray(points) / grid_res).astype(int).tolist()          # :42
+    ind = list(range(len(keys)))
+    if keep == 'first':                                                          # :47-50
+        keys, ind = keys[::-1], ind[::-1]
+    elif keep == 'random':                                                       # :51-55
+        rng.shuffle(ind)
+        keys = [keys[i] for i in ind]
+    key_to_ind = dict(zip([tuple(k) for k in keys], ind))                        # :61-64
+    return sorted(key_to_ind.values()) if preserve_order else list(key_to_ind.values())
+
+
+def voxel_face_cloud(grid_res, dtype, kmax, seed=0):
+    """Test cloud [3 (2 kmax + 1), 3] of ``dtype`` with y = z = 0 and x ON and NEXT TO the voxel faces of ``grid_res``:
+    x = fl(k * fl(res)) for k in -kmax .. kmax and the neighbouring floats on both sides, in a seeded random order.
+    Voxel k holds the float above face k and the float below face k + 1 whatever the arithmetic; where the two face
+    points land depends on how ``x / res`` rounds, and that changes which point of the voxel survives."""
+    dtype = np.dtype(dtype).type
+    k = np.arange(-kmax, kmax + 1).astype(dtype)
+    face = k * dtype(grid_res)
+    x = np.concatenate([face, np.nextafter(face, dtype(-np.inf)), np.nextafter(face, dtype(np.inf))])
+    pts = np.zeros((len(x), 3), dtype=dtype)
+    pts[:, 0] = x[np.random.default_rng(seed).permutation(len(x))]
+    return pts
 
 
 def _eig_masks(eigvals, eigenvalue_bounds, eigenvalue_ratio_bounds):

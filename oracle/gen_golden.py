@@ -9,7 +9,7 @@ oracle's restatement of the published algorithm (recorded in each fixture's ``me
 Before a fixture is written, the oracle restatement (oracle/dc_oracle.py) is run on the same inputs
 and asserted equal to the reference's outputs, so a committed fixture certifies both.
 
-Usage:  python oracle/gen_golden.py [names]    (writes tests/golden/{c0_plane,room_k10,icp_pairs,knn,grid,shadow,models,inliers,io,online}.npz, about 12 MB)
+Usage:  python oracle/gen_golden.py [names]    (writes tests/golden/{c0_plane,room_k10,icp_pairs,knn,grid,filters_edge,shadow,models,inliers,io,online}.npz, about 12 MB)
 """
 import os
 import sys
@@ -444,6 +444,107 @@ def gen_grid():
     np.savez_compressed(os.path.join(GOLD, 'grid.npz'), **out)
 
 
+def _bounds_table(dtype, rng, n_rows=1500):
+    """Eigenvalue table [n_rows, 3] whose values (columns 0, 1) and ratios (0 / 1, 1 / 2) sit ON the bounds as the reference
+    holds them: float32(bound), both its neighbouring floats and (fp64 only) the unrounded bound and the doubles next to
+    float32(bound), for 0.0004 (rounds down) and 0.1 (rounds up); ratios with exact (power of two) and inexact denominators
+    (the division rounds in storage precision); zero denominators, NaN and inf entries; ordinary rows in between."""
+    f = np.dtype(dtype).type
+    rows = []
+    for b in (0.0004, 0.1):
+        b32 = np.float32(b)
+        targets = [f(b32), f(np.nextafter(b32, np.float32(-np.inf))), f(np.nextafter(b32, np.float32(np.inf)))]
+        if f is np.float64:
+            targets += [f(b), np.nextafter(f(b32), -np.inf), np.nextafter(f(b32), np.inf), np.nextafter(f(b), f(b32))]
+        for v in targets:
+            rows += [[v, 1, 1], [1, v, 1], [v, v, v], [v, 0, v], [0, v, 0], [v, v, np.nan]]
+            for d in [f(2.0) ** m for m in range(-3, 4)] + list(rng.uniform(0.5, 2.0, size=24).astype(f)):
+                rows += [[v * d, d, 1], [1, v * d, d]]
+    rows += [[0, 0, 0], [1, 0, 0], [-1, 0, 1], [1, -0.0, 1], [np.nan, 1, 1], [1, np.nan, 1], [np.inf, 1, 1], [1, np.inf, 1],
+             [np.inf, np.inf, 1], [-np.inf, 1, 0]]
+    assert len(rows) < n_rows - 200, len(rows)
+    fill = np.sort(np.exp(rng.normal(np.log(0.01), 2.5, size=(n_rows - len(rows), 3))), axis=1)
+    with np.errstate(all='ignore'):
+        table = np.concatenate([np.array(rows, dtype=np.float64).astype(f), fill.astype(f)])
+    return np.ascontiguousarray(table[rng.permutation(len(table))])
+
+
+def gen_filters_edge():
+    """The pre-processing filters where their kernels can go wrong: filter_grid (filters.py:24-82) on clouds ON the voxel
+    faces, at resolutions whose division rounds (0.1, 0.2, 0.3) and one where it does not (0.25), in fp32 and fp64, and on
+    a clustered cloud with negative coordinates; filter_eigenvalue / filter_eigenvalue_ratio (:196-254) on tables whose
+    values and ratios sit on the float32-rounded bounds within_bounds compares with (:97-104)."""
+    from depth_correction.filters import (filter_eigenvalue, filter_eigenvalue_ratio, filter_eigenvalue_ratios,
+                                          filter_eigenvalues, filter_grid)
+    out = dict(meta=np.array(META))
+    nan, inf = float('nan'), float('inf')
+
+    # ---- voxel filter
+    clouds = {}
+    for res in (0.1, 0.2, 0.3, 0.25):
+        for tag, dtype in (('f32', np.float32), ('f64', np.float64)):
+            clouds['face_%s_r%03d' % (tag, round(res * 100))] = (O.voxel_face_cloud(res, dtype, 300, seed=9), res)
+    rng = np.random.default_rng(33)
+    centres = rng.integers(-6, 6, size=(500, 3)) * 0.2                      # about 500 voxels around the origin, both signs
+    pts = centres[rng.integers(0, 500, size=2000)] + rng.uniform(0.0, 0.2, size=(2000, 3))
+    clouds['cluster_f32'] = (pts.astype(np.float32), 0.2)
+    clouds['cluster_f64'] = (pts, 0.2)
+    out['grid_names'] = np.array(sorted(clouds))
+    for name, (pts, res) in clouds.items():
+        out[name + '_points'], out[name + '_res'] = pts, res
+        for keep in ('first', 'last', 'random'):
+            for po in (False, True):
+                ind = filter_grid(pts, res, only_mask=True, keep=keep, preserve_order=po, rng=np.random.default_rng(135))
+                mine = O.filter_grid(pts, res, keep=keep, preserve_order=po, rng=np.random.default_rng(135))
+                assert mine == ind, 'filter_grid restatement differs: %s %s %d' % (name, keep, po)
+                out['%s_%s_%d' % (name, keep, po)] = np.asarray(ind, dtype=np.int32)
+        print('filters_edge: %-16s %5d points -> %5d voxels (res %.2f)' % (name, len(pts), len(out[name + '_last_0']), res))
+    # the face clouds are not harmless: the precision of the division and a reciprocal multiply change the voxels
+    x = clouds['face_f32_r020'][0][:, 0]
+    n_prec = int((np.floor(x / np.float32(0.2)) != np.floor(x.astype(np.float64) / 0.2)).sum())
+    x = clouds['face_f32_r030'][0][:, 0]
+    n_rcp = int((np.floor(x / np.float32(0.3)) != np.floor(x * (np.float32(1.0) / np.float32(0.3)))).sum())
+    x = clouds['face_f32_r025'][0][:, 0]
+    n_exact = int((np.floor(x / np.float32(0.25)) != np.floor(x.astype(np.float64) / 0.25)).sum())
+    assert n_prec > 100 and n_rcp > 30 and n_exact == 0, (n_prec, n_rcp, n_exact)
+
+    # ---- eigenvalue / ratio bounds
+    value_cases = [(0, 0.0004, 0.1), (1, 0.0004, nan), (0, nan, 0.1), (1, 0.1, inf), (0, -inf, 0.0004), (2, nan, nan),
+                   (0, 0.1, 0.0004)]
+    ratio_cases = [(0, 1, 0.0004, 0.1), (1, 2, 0.1, nan), (0, 1, nan, 0.0004), (1, 2, 0.0004, inf), (0, 1, -inf, inf),
+                   (1, 0, 0.1, nan), (2, 1, 0.0, 10.0)]
+    out['value_cases'], out['ratio_cases'] = np.array(value_cases), np.array(ratio_cases)
+    rng = np.random.default_rng(34)
+    for tag, dtype in (('f32', np.float32), ('f64', np.float64)):
+        table = _bounds_table(dtype, rng)
+        ev = torch.as_tensor(table)
+        cloud = DepthCloud(torch.zeros_like(ev), torch.zeros_like(ev), torch.zeros_like(ev[:, :1]), eigvals=ev)
+        vm, rm = [], []
+        with np.errstate(all='ignore'):
+            for e, lo, hi in value_cases:
+                m = filter_eigenvalue(cloud, e, min=lo, max=hi, only_mask=True)
+                assert torch.equal(m, O.within_bounds(ev[:, e], lo, hi)), ('value bounds restatement', tag, e, lo, hi)
+                assert torch.equal(m, filter_eigenvalue(cloud, e, min=None if lo != lo else lo, max=None if hi != hi else hi,
+                                                        only_mask=True))           # a NaN bound is no bound, like None
+                vm.append(npy(m))
+            for i, j, lo, hi in ratio_cases:
+                m = filter_eigenvalue_ratio(cloud, (i, j), min=lo, max=hi, only_mask=True)
+                assert torch.equal(m, O.within_bounds(ev[:, i] / ev[:, j], lo, hi)), ('ratio bounds restatement', tag, i, j)
+                rm.append(npy(m))
+            va = filter_eigenvalues(cloud, [list(c) for c in value_cases[:3]], only_mask=True)
+            ra = filter_eigenvalue_ratios(cloud, [list(c) for c in ratio_cases[:3]], only_mask=True)
+        assert torch.equal(va, O.local_mask(ev, value_cases[:3], None)) and torch.equal(ra, O.local_mask(ev, None, ratio_cases[:3]))
+        assert np.array_equal(npy(va), np.logical_and.reduce(vm[:3])) and np.array_equal(npy(ra), np.logical_and.reduce(rm[:3]))
+        out[tag + '_eigvals'], out[tag + '_value_masks'], out[tag + '_ratio_masks'] = table, np.stack(vm), np.stack(rm)
+        out[tag + '_values_all'], out[tag + '_ratios_all'] = npy(va), npy(ra)
+        # the rounded bound matters: an unrounded comparison would change the masks
+        plain = npy((ev[:, 0].double() >= 0.0004) & (ev[:, 0].double() <= 0.1))
+        assert (plain != vm[0]).sum() >= 10, 'no row tells the float32 bound from the unrounded one'
+        print('filters_edge: bounds %s: %d rows, kept per case %s / %s, %d rows tell the float32 bound from the Python float'
+              % (tag, len(table), [int(m.sum()) for m in vm], [int(m.sum()) for m in rm], int((plain != vm[0]).sum())))
+    np.savez_compressed(os.path.join(GOLD, 'filters_edge.npz'), **out)
+
+
 def gen_knn():
     """nearest_neighbors() itself: k, k within r, r only (nearest_neighbors.py:22-80)."""
     rng = np.random.default_rng(3)
@@ -656,7 +757,7 @@ def gen_online():
 if __name__ == '__main__':
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ['knn', 'grid', 'c0', 'room', 'icp', 'shadow', 'models', 'inliers', 'io', 'online', 'helpers']
+    which = sys.argv[1:] or ['knn', 'grid', 'c0', 'room', 'icp', 'shadow', 'models', 'inliers', 'io', 'online', 'helpers', 'filters_edge']
     if 'io' in which:
         gen_io()
     if 'online' in which:
@@ -665,6 +766,8 @@ if __name__ == '__main__':
         gen_helpers()
     if 'grid' in which:
         gen_grid()
+    if 'filters_edge' in which:
+        gen_filters_edge()
     if 'knn' in which:
         gen_knn()
     if 'c0' in which:

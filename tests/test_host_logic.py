@@ -408,3 +408,51 @@ def test_cat_rows_views_consecutive_slices_and_copies_the_rest():
     for bad in ([base[7:12], base[0:7]], [base[0:7], base.clone()[7:12]], [base[0:7], base[8:12]], [base[3:9]], [base[:, :2][0:4], base[:, :2][4:8]]):
         got = ops.cat_rows(bad)
         assert torch.equal(got, torch.cat(bad)) and (len(bad) == 1 or got.data_ptr() not in [b.data_ptr() for b in bad])
+
+
+def test_filter_grid_host_at_voxel_faces(golden):
+    """filter_grid on host arrays that sit on the voxel faces (fp32 and fp64, resolutions whose division rounds) and on a
+    clustered cloud with negative coordinates, against the live reference's survivors."""
+    g = golden('filters_edge')
+    for name in g['grid_names'].tolist():
+        pts, res = g[name + '_points'], float(g[name + '_res'])
+        for keep in ('first', 'last', 'random'):
+            for po in (False, True):
+                ind = filter_grid(pts, res, only_mask=True, keep=keep, preserve_order=po, rng=np.random.default_rng(135))
+                assert np.array_equal(np.asarray(ind), g['%s_%s_%d' % (name, keep, po)]), (name, keep, po)
+
+
+@pytest.mark.parametrize('tag', ['f32', 'f64'])
+def test_within_bounds_uses_the_float32_bound(golden, tag):
+    """within_bounds on CPU tensors against the reference's masks on values and ratios that equal float32(bound), its
+    neighbouring floats and the unrounded bound: the reference compares with torch.tensor(bound), a float32 scalar."""
+    g = golden('filters_edge')
+    ev = torch.as_tensor(g[tag + '_eigvals'])
+    cloud = DepthCloud(torch.zeros_like(ev), torch.zeros_like(ev), torch.zeros_like(ev[:, :1]))
+    cloud.eigvals = ev
+    from depth_correction_amd.filters import (filter_eigenvalue, filter_eigenvalue_ratio, filter_eigenvalue_ratios,
+                                              filter_eigenvalues)
+    nn = lambda b: None if b != b else b
+    for (e, lo, hi), want in zip(g['value_cases'].tolist(), g[tag + '_value_masks']):
+        assert np.array_equal(within_bounds(ev[:, int(e)], min=nn(lo), max=nn(hi)).numpy(), want), (e, lo, hi)
+        assert np.array_equal(within_bounds(ev[:, int(e)], bounds=[lo, hi]).numpy(), want), (e, lo, hi)
+        assert np.array_equal(filter_eigenvalue(cloud, int(e), min=nn(lo), max=nn(hi), only_mask=True).numpy(), want)
+    for (i, j, lo, hi), want in zip(g['ratio_cases'].tolist(), g[tag + '_ratio_masks']):
+        got = filter_eigenvalue_ratio(cloud, (int(i), int(j)), min=nn(lo), max=nn(hi), only_mask=True)
+        assert np.array_equal(got.numpy(), want), (i, j, lo, hi)
+    vb = [[int(e), lo, hi] for e, lo, hi in g['value_cases'][:3].tolist()]
+    rb = [[int(i), int(j), lo, hi] for i, j, lo, hi in g['ratio_cases'][:3].tolist()]
+    assert np.array_equal(filter_eigenvalues(cloud, vb, only_mask=True).numpy(), g[tag + '_values_all'])
+    assert np.array_equal(filter_eigenvalue_ratios(cloud, rb, only_mask=True).numpy(), g[tag + '_ratios_all'])
+    x = torch.tensor([float(np.float32(0.0004)), float(np.float32(0.1))], dtype=ev.dtype)
+    assert within_bounds(x, min=0.0004, max=0.1).tolist() == [True, True]
+
+
+def test_device_bounds_are_rounded_like_the_reference():
+    """What the mask kernels and the depth bounds of cloud_from_points receive: the widened float32 value of the bound
+    (torch.tensor(bound)); None and NaN mean unbounded, infinities stay."""
+    from depth_correction_amd.ops import _bound
+    inf = float('inf')
+    assert _bound(0.0004, -inf) == float(np.float32(0.0004)) < 0.0004 and _bound(0.1, inf) == float(np.float32(0.1)) > 0.1
+    assert _bound(0.25, inf) == 0.25 and _bound(5, -inf) == 5.0
+    assert _bound(None, -inf) == -inf and _bound(float('nan'), inf) == inf and _bound(inf, inf) == inf and _bound(-inf, 0.0) == -inf

@@ -219,3 +219,54 @@ def test_other_models(golden, name):
     np.testing.assert_allclose(npy(w.grad), m[name + '_grad_w'], rtol=1e-6, atol=1e-12)
     d0 = O.model_apply(scans[0]['depth'], scans[0]['inc'], scans[0]['mask'], w.detach(), None, name)
     np.testing.assert_allclose(npy(d0), m[name + '_depth0'], rtol=1e-12)
+
+
+KEEP_MODES = [(keep, po) for keep in ('first', 'last', 'random') for po in (False, True)]
+
+
+def test_filter_grid_at_voxel_faces(golden):
+    """filters.filter_grid (filters.py:24-82) restated (O.filter_grid) on clouds ON the voxel faces, where the precision of
+    ``x / grid_res`` decides the voxel, and on a clustered cloud with negative coordinates: fp32 and fp64 arrays, every
+    keep mode.  The face clouds are what O.voxel_face_cloud builds, so the GPU tests can build larger ones."""
+    g = golden('filters_edge')
+    for name in g['grid_names'].tolist():
+        pts, res = g[name + '_points'], float(g[name + '_res'])
+        assert pts.dtype == (np.float32 if '_f32' in name else np.float64)
+        for keep, po in KEEP_MODES:
+            ind = O.filter_grid(pts, res, keep=keep, preserve_order=po, rng=np.random.default_rng(135))
+            assert np.array_equal(np.asarray(ind), g['%s_%s_%d' % (name, keep, po)]), (name, keep, po)
+        if name.startswith('face_'):
+            assert np.array_equal(pts, O.voxel_face_cloud(res, pts.dtype, 300, seed=9))
+    # what makes the fixture worth having: at 0.2 the fp32 division and an fp64 division of the same points disagree, at
+    # 0.3 a reciprocal multiply disagrees with the division, at 0.25 (a power of two) nothing can
+    x = g['face_f32_r020_points'][:, 0]
+    assert (np.floor(x / np.float32(0.2)) != np.floor(x.astype(np.float64) / 0.2)).sum() > 100
+    x = g['face_f32_r030_points'][:, 0]
+    assert (np.floor(x / np.float32(0.3)) != np.floor(x * (np.float32(1.0) / np.float32(0.3)))).sum() > 30
+    x = g['face_f32_r025_points'][:, 0]
+    assert np.array_equal(np.floor(x / np.float32(0.25)), np.floor(x.astype(np.float64) / 0.25))
+
+
+@pytest.mark.parametrize('tag', ['f32', 'f64'])
+def test_bounds_use_the_float32_bound(golden, tag):
+    """filters.within_bounds (filters.py:85-113) compares with torch.tensor(bound), a float32 scalar: O.within_bounds on
+    tables whose values and ratios equal float32(bound), its neighbours and the unrounded bound, against the live
+    reference's filter_eigenvalue / filter_eigenvalue_ratio masks."""
+    g = golden('filters_edge')
+    ev = t(g[tag + '_eigvals'])
+    nn = lambda b: None if b != b else b
+    for (e, lo, hi), want in zip(g['value_cases'].tolist(), g[tag + '_value_masks']):
+        assert np.array_equal(npy(O.within_bounds(ev[:, int(e)], lo, hi)), want), (e, lo, hi)
+        assert np.array_equal(npy(O.within_bounds(ev[:, int(e)], nn(lo), nn(hi))), want), (e, lo, hi)
+    for (i, j, lo, hi), want in zip(g['ratio_cases'].tolist(), g[tag + '_ratio_masks']):
+        assert np.array_equal(npy(O.within_bounds(ev[:, int(i)] / ev[:, int(j)], lo, hi)), want), (i, j, lo, hi)
+    assert np.array_equal(npy(O.local_mask(ev, g['value_cases'][:3].tolist(), None)), g[tag + '_values_all'])
+    assert np.array_equal(npy(O.local_mask(ev, None, g['ratio_cases'][:3].tolist())), g[tag + '_ratios_all'])
+    # the comparison with the Python float, which the fixture must tell apart
+    plain = npy((ev[:, 0].double() >= 0.0004) & (ev[:, 0].double() <= 0.1))
+    assert (plain != g[tag + '_value_masks'][0]).sum() >= 10
+    # torch.tensor(0.0004) lies below 0.0004 and torch.tensor(0.1) above 0.1: the rounded bounds KEEP these values
+    lo32, hi32 = float(np.float32(0.0004)), float(np.float32(0.1))
+    assert lo32 < 0.0004 and hi32 > 0.1
+    x = torch.tensor([lo32, hi32], dtype=ev.dtype)
+    assert O.within_bounds(x, 0.0004, 0.1).tolist() == [True, True]
