@@ -29,6 +29,10 @@ DC_ICP_STATE_COUNT, DC_ICP_STATE_POSE, DC_ICP_STATE_PRIOR, DC_ICP_STATE_PAIRS, D
 DC_ICP_MAX_SMOOTH, DC_ICP_PARTIALS = 8, 30
 # include/dc_hip.h: limits and layout of dc_bias_accumulate's out
 DC_BIAS_MAX_BINS, DC_BIAS_MAX_TERMS, DC_BIAS_TOTALS, DC_BIAS_BIN_COLS = 256, 4, 5, 9
+# include/dc_hip.h: finite-beam rendering
+DC_BEAM_MAX_SAMPLES = 64
+BEAM_DETECTIONS = {'mean': 0, 'quantile': 1}
+BEAM_WEIGHTS = {'uniform': 0, 'lambert': 1}
 ICP_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'singular', -3: 'not_finite', -4: 'bound'}
 
 _LIB = None
@@ -153,6 +157,9 @@ _SIGNATURES = {
     'dc_bvh_build': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dc_raycast': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     'dc_raycast_rays': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp]),
+    'dc_beam_subrays': (_i32, [_vp, _vp, _i32, _i64, _vp, _i32, _f64, _f64, _vp, _vp, _vp]),
+    'dc_raycast_beams': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _f64, _i32,
+                                _i32, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dc_bias_workspace_bytes': (_sz, [_i32, _i32]),
     'dc_bias_accumulate': (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     'dc_mesh_closest': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp]),

@@ -7,6 +7,7 @@
 #include "dc_slam_math.h"
 #include "dc_trimath.h"
 #include "dc_biasmath.h"
+#include "dc_beammath.h"
 
 extern "C" {
 
@@ -169,5 +170,29 @@ int dc_host_bias_accumulate(const void* depth, const void* inc_est, int dtype, c
 
 // bin of the true incidence angle g (dc_biasmath.h)
 int dc_host_bias_bin(double g, int n_bins) { return dc::bias_bin(g, n_bins); }
+
+// dc_beam_subrays on host arrays (dc_beammath.h): vps / dirs double [n,3], pattern double [n_samples,3] -> origins / dirs double
+// [n, n_samples, 3]
+void dc_host_beam_subrays(const double* vps, const double* dirs, int64_t n, const double* pattern, int n_samples, double r0, double spread,
+                          double* origins_out, double* dirs_out) {
+  for (int64_t i = 0; i < n; ++i) {
+    const dc::BeamFrame f = dc::beam_frame(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    for (int j = 0; j < n_samples; ++j)
+      dc::beam_subray(f, vps[3 * i], vps[3 * i + 1], vps[3 * i + 2], pattern[3 * j], pattern[3 * j + 1], r0, spread,
+                      origins_out + 3 * (i * n_samples + j), dirs_out + 3 * (i * n_samples + j));
+  }
+}
+
+// the reduction of dc_raycast_beams on n bundles of sub-ray returns [n, n_samples] (dc_beammath.h), with its argument checks
+int dc_host_beam_select(const int32_t* sub_face, const double* sub_t, const double* sub_w, int64_t n, int n_samples, int detection, double tau,
+                        int min_hits, int32_t* face_out, double* depth_out, int32_t* n_hits_out) {
+  if (n < 0 || n_samples < 1 || n_samples > DC_BEAM_MAX_SAMPLES || (n_samples & (n_samples - 1)) != 0 || !(tau > 0.0) || !(tau <= 1.0) ||
+      min_hits < 1 || min_hits > n_samples || (detection != DC_BEAM_MEAN && detection != DC_BEAM_QUANTILE))
+    return DC_ERR_ARG;
+  for (int64_t i = 0; i < n; ++i)
+    dc::beam_select(sub_face + i * n_samples, sub_t + i * n_samples, sub_w + i * n_samples, n_samples, detection, tau, min_hits, face_out + i,
+                    depth_out + i, n_hits_out + i);
+  return DC_OK;
+}
 
 }  // extern "C"

@@ -22,7 +22,13 @@
 //
 // dc_raycast_rays casts the rays of measured clouds (per-ray view point and direction, per-scan pose) through the same device
 // function (cast_ray) and adds the true incidence angle on the winning triangle: the ground truth of eval_bias.
+//
+// dc_raycast_beams renders finite beams: a bundle of S sub-rays per beam (dc_beammath.h) goes through cast_ray, one lane per sub-ray,
+// and the S consecutive lanes of a beam reduce their returns to one return with cross-lane reads only (rules: dc_beammath.h).  S is
+// a power of two <= 64, so a wavefront holds 64 / S whole beams; the lanes past the last beam stay in the kernel as misses until
+// the reduction is done, because a cross-lane read from a lane that has left returns garbage.
 #include "dc_common.h"
+#include "dc_beammath.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
 #include "../../include/dc_hip.h"
@@ -351,6 +357,167 @@ __global__ void __launch_bounds__(kCastBlock) raycast_rays_kernel(const int32_t*
   inc_out[g] = inc;
 }
 
+// The footprint pattern travels in the kernel's arguments (HOST array at the C ABI): no copy, no workspace.
+struct BeamPattern {
+  double v[3 * DC_BEAM_MAX_SAMPLES];          // rows (px, py, weight)
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBuildBlock) beam_subrays_kernel(const T* __restrict__ vps, const T* __restrict__ dirs, int64_t total,
+                                                                   BeamPattern pat, int n_samples, double r0, double spread,
+                                                                   double* __restrict__ origins_out, double* __restrict__ dirs_out) {
+  const int64_t g = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (g >= total) return;
+  const int64_t i = g / n_samples;
+  const int j = (int)(g - i * n_samples);
+  const dc::BeamFrame f = dc::beam_frame((double)dirs[3 * i], (double)dirs[3 * i + 1], (double)dirs[3 * i + 2]);
+  double o[3], D[3];
+  dc::beam_subray(f, (double)vps[3 * i], (double)vps[3 * i + 1], (double)vps[3 * i + 2], pat.v[3 * j], pat.v[3 * j + 1], r0, spread, o, D);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    origins_out[3 * g + a] = o[a];
+    dirs_out[3 * g + a] = D[a];
+  }
+}
+
+// One lane per sub-ray; sub-ray g = beam (g >> log2s), sample (g & (S - 1)).  kCastBlock is a multiple of 64 and S divides 64, so
+// the S lanes of a beam are consecutive lanes of one wavefront, starting at a multiple of S.
+template <typename T>
+__global__ void __launch_bounds__(kCastBlock) raycast_beams_kernel(
+    const int32_t* __restrict__ child, const float* __restrict__ node_box, const double* __restrict__ leaf_tri,
+    const int32_t* __restrict__ leaf_face, int64_t n, const T* __restrict__ vps, const T* __restrict__ dirs, int64_t n_beams,
+    const int64_t* __restrict__ scan_offset, const double* __restrict__ poses, int n_scans, BeamPattern pat, int log2s, double r0,
+    double spread, const double* __restrict__ t_min_beam, double t_min, int cull, int weight_kind, int detection, double tau, int min_hits,
+    int32_t* __restrict__ face_out, double* __restrict__ depth_out, int32_t* __restrict__ n_hits_out, int32_t* __restrict__ sub_face,
+    double* __restrict__ sub_t, double* __restrict__ sub_w) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  const int S = 1 << log2s;
+  const int64_t i = g >> log2s;
+  const int j = (int)(g & (S - 1));
+  const bool live = i < n_beams;                  // the other lanes are misses; they stay for the cross-lane part
+  int32_t face = -1;
+  double t = INFINITY, w = 0.0;
+  if (live) {
+    int lo = 0, hi = n_scans;                     // the last s in [0, n_scans) with scan_offset[s] <= i (scan 0 when there is none)
+    while (hi - lo > 1) {
+      const int mid = lo + (hi - lo) / 2;
+      if (scan_offset[mid] <= i) lo = mid; else hi = mid;
+    }
+    const double* M = poses + 16 * (int64_t)lo;
+    const dc::BeamFrame f = dc::beam_frame((double)dirs[3 * i], (double)dirs[3 * i + 1], (double)dirs[3 * i + 2]);
+    if (f.ok) {
+      double o[3], D[3];
+      dc::beam_subray(f, (double)vps[3 * i], (double)vps[3 * i + 1], (double)vps[3 * i + 2], pat.v[3 * j], pat.v[3 * j + 1], r0, spread, o,
+                      D);
+      const double s0 = D[0], s1 = D[1], s2 = D[2];
+      const double v0 = o[0], v1 = o[1], v2 = o[2];
+      // the expressions of raycast_rays_kernel, literally
+      const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
+      const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
+      const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
+      const double o0 = (M[0] * v0 + M[1] * v1 + M[2] * v2) + M[3];
+      const double o1 = (M[4] * v0 + M[5] * v1 + M[6] * v2) + M[7];
+      const double o2 = (M[8] * v0 + M[9] * v1 + M[10] * v2) + M[11];
+      const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min_beam ? t_min_beam[i] : t_min, cull,
+                                stack, lane);
+      if (best.leaf >= 0) {
+        w = pat.v[3 * j + 2];
+        if (weight_kind == DC_BEAM_LAMBERT) {
+          const double* tri = leaf_tri + 9 * (int64_t)best.leaf;
+          const double e10 = tri[3] - tri[0], e11 = tri[4] - tri[1], e12 = tri[5] - tri[2];
+          const double e20 = tri[6] - tri[0], e21 = tri[7] - tri[1], e22 = tri[8] - tri[2];
+          const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
+          const double c = fabs(n0 * d0 + n1 * d1 + n2 * d2) / (sqrt(n0 * n0 + n1 * n1 + n2 * n2) * sqrt(d0 * d0 + d1 * d1 + d2 * d2));
+          w *= fmin(1.0, c);                          // 0 / 0 on a face of zero area: NaN, not a hit
+        }
+        if (dc::beam_is_hit(best.face, w)) {
+          face = best.face;
+          t = best.t;
+        } else {
+          w = 0.0;
+        }
+      }
+    }
+    if (sub_face) {
+      sub_face[g] = face;
+      sub_t[g] = t;
+      sub_w[g] = w;
+    }
+  }
+
+  // ---- the bundle's reduction: every lane of the wavefront is here ----
+  const int wl = lane & 63, base = wl & ~(S - 1);
+  const uint64_t group = S == 64 ? ~0ull : ((1ull << S) - 1ull);
+  const uint64_t hits = (__ballot(face >= 0) >> base) & group;
+  const int n_hits = __popcll(hits);
+  double total = 0.0, depth = INFINITY;
+  if (detection == DC_BEAM_MEAN) {
+    double swt = 0.0;
+    for (int k = 0; k < S; ++k) {                     // ascending j, one term at a time
+      const double tk = __shfl(t, base + k), wk = __shfl(w, base + k);
+      if ((hits >> k) & 1ull) {
+        total += wk;
+        swt += wk * tk;
+      }
+    }
+    depth = swt / total;
+  } else {
+    int rank = 0;                                     // place of this lane's hit in the order by (t, j)
+    for (int k = 0; k < S; ++k) {
+      const double tk = __shfl(t, base + k);
+      rank += (((hits >> k) & 1ull) && dc::beam_before(tk, k, t, j)) ? 1 : 0;
+    }
+    int src = j;                                      // the sample at place j of that order
+    for (int k = 0; k < S; ++k) {
+      const int rk = __shfl(rank, base + k);
+      if (((hits >> k) & 1ull) && rk == j) src = k;
+    }
+    const double ts = __shfl(t, base + src), ws = __shfl(w, base + src);
+    double c = 0.0, cj = 0.0;                         // the running weight, added one at a time in that order: every lane of the beam
+    for (int m = 0; m < S; ++m) {                     // forms the same sequence, lane j keeps c_j
+      const double wm = __shfl(ws, base + m);
+      if (m < n_hits) c += wm;
+      if (m == j) cj = c;
+    }
+    total = c;
+    const uint64_t reached = (__ballot(j < n_hits && dc::beam_reached(cj, tau, total)) >> base) & group;
+    const int first = reached ? __ffsll((unsigned long long)reached) - 1 : 0;
+    const double tq = __shfl(ts, base + first);
+    if (reached) depth = tq;
+  }
+  const bool miss = dc::beam_is_miss(n_hits, min_hits, total);
+  int best_k = -1;
+  double best_dist = INFINITY;
+  for (int k = 0; k < S; ++k) {
+    const double tk = __shfl(t, base + k);
+    if ((hits >> k) & 1ull) {
+      const double dist = fabs(tk - depth);
+      if (dc::beam_closer(dist, best_dist)) { best_dist = dist; best_k = k; }
+    }
+  }
+  const int32_t fk = __shfl(face, base + (best_k >= 0 ? best_k : 0));
+  if (live && j == 0) {
+    const bool ok = !miss && best_k >= 0;
+    face_out[i] = ok ? fk : -1;
+    depth_out[i] = ok ? depth : INFINITY;
+    n_hits_out[i] = n_hits;
+  }
+}
+
+// the checks dc_beam_subrays and dc_raycast_beams share; fills `pat`
+inline bool beam_pattern_ok(const double* pattern, int n_samples, double r0, double spread, BeamPattern* pat) {
+  if (!pattern || n_samples < 1 || n_samples > DC_BEAM_MAX_SAMPLES) return false;
+  if (!(r0 >= 0.0) || !(spread >= 0.0) || !std::isfinite(r0) || !std::isfinite(spread)) return false;
+  for (int k = 0; k < 3 * DC_BEAM_MAX_SAMPLES; ++k) pat->v[k] = 0.0;
+  for (int k = 0; k < 3 * n_samples; ++k) {
+    if (!std::isfinite(pattern[k]) || (k % 3 == 2 && pattern[k] < 0.0)) return false;
+    pat->v[k] = pattern[k];
+  }
+  return true;
+}
+
 inline unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 }  // namespace
@@ -433,6 +600,56 @@ int dc_raycast_rays(const int32_t* child, const float* node_box, const double* l
     raycast_rays_kernel<double><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
         child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, n, scan_offset, poses, n_scans, t_min, cull,
         face_out, t_out, inc_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_beam_subrays(const void* vps, const void* dirs, int dtype, int64_t n, const double* pattern, int n_samples, double r0, double spread,
+                    double* origins_out, double* dirs_out, dcStream_t stream) {
+  BeamPattern pat;
+  if (n < 0 || !beam_pattern_ok(pattern, n_samples, r0, spread, &pat)) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (!vps || !dirs || !origins_out || !dirs_out || n > (int64_t)1 << 55) return DC_ERR_ARG;
+  const int64_t total = n * n_samples;
+  if (dtype == DC_F32)
+    beam_subrays_kernel<float><<<grid_of(total, kBuildBlock), kBuildBlock, 0, (hipStream_t)stream>>>(
+        (const float*)vps, (const float*)dirs, total, pat, n_samples, r0, spread, origins_out, dirs_out);
+  else
+    beam_subrays_kernel<double><<<grid_of(total, kBuildBlock), kBuildBlock, 0, (hipStream_t)stream>>>(
+        (const double*)vps, (const double*)dirs, total, pat, n_samples, r0, spread, origins_out, dirs_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_raycast_beams(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                     const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                     const double* pattern, int n_samples, double r0, double spread, const double* t_min_beam, double t_min, int cull,
+                     int weight_kind, int detection, double tau, int min_hits, int32_t* face_out, double* depth_out, int32_t* n_hits_out,
+                     int32_t* sub_face, double* sub_t, double* sub_w, dcStream_t stream) {
+  if (n_faces < 1 || n < 0 || n_scans < 0 || !node_box || !leaf_tri || !leaf_face || (n_faces > 1 && !child) || !(t_min == t_min))
+    return DC_ERR_ARG;
+  BeamPattern pat;
+  if (!beam_pattern_ok(pattern, n_samples, r0, spread, &pat) || (n_samples & (n_samples - 1)) != 0) return DC_ERR_ARG;
+  if (!(tau > 0.0) || !(tau <= 1.0) || min_hits < 1 || min_hits > n_samples) return DC_ERR_ARG;
+  if ((weight_kind != DC_BEAM_UNIFORM && weight_kind != DC_BEAM_LAMBERT) || (detection != DC_BEAM_MEAN && detection != DC_BEAM_QUANTILE))
+    return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (n_scans < 1 || !vps || !dirs || !scan_offset || !poses || !face_out || !depth_out || !n_hits_out || n > (int64_t)1 << 55)
+    return DC_ERR_ARG;
+  if (sub_face && (!sub_t || !sub_w)) return DC_ERR_ARG;
+  int log2s = 0;
+  while ((1 << log2s) < n_samples) ++log2s;
+  const int64_t total = n * n_samples;
+  if (dtype == DC_F32)
+    raycast_beams_kernel<float><<<grid_of(total, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const float*)vps, (const float*)dirs, n, scan_offset, poses, n_scans, pat, log2s, r0,
+        spread, t_min_beam, t_min, cull, weight_kind, detection, tau, min_hits, face_out, depth_out, n_hits_out, sub_face, sub_t, sub_w);
+  else
+    raycast_beams_kernel<double><<<grid_of(total, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, n, scan_offset, poses, n_scans, pat, log2s,
+        r0, spread, t_min_beam, t_min, cull, weight_kind, detection, tau, min_hits, face_out, depth_out, n_hits_out, sub_face, sub_t, sub_w);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

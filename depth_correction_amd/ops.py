@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
 ]
 
@@ -1135,6 +1135,106 @@ def raycast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, cull=True):
                                 ptr(vps), ptr(dirs), code, n, ptr(off), ptr(poses), s, tm, 1 if cull else 0, ptr(face), ptr(t),
                                 ptr(inc), stream_ptr()), 'dc_raycast_rays')
     return face, t, inc
+
+
+def _beam_pattern_arg(pattern, r0, spread, power_of_two):
+    """The footprint pattern as a host float64 [S,3] array, checked the way the library checks it."""
+    import numpy as np
+    pat = np.ascontiguousarray(np.asarray(pattern.detach().cpu() if isinstance(pattern, torch.Tensor) else pattern, dtype=np.float64))
+    if pat.ndim != 2 or pat.shape[1] != 3 or not 1 <= pat.shape[0] <= nv.DC_BEAM_MAX_SAMPLES:
+        raise ValueError('pattern must be [S,3] rows (px, py, weight) with 1 <= S <= %d, got shape %s' % (nv.DC_BEAM_MAX_SAMPLES, pat.shape))
+    s = pat.shape[0]
+    if power_of_two and s & (s - 1):
+        raise ValueError('the number of samples per beam must be a power of two, got %d' % s)
+    if not np.isfinite(pat).all() or (pat[:, 2] < 0).any():
+        raise ValueError('pattern entries must be finite and the weights non-negative')
+    r0, spread = float(r0), float(spread)
+    if not (0.0 <= r0 < float('inf')) or not (0.0 <= spread < float('inf')):
+        raise ValueError('r0 and spread must be finite and >= 0, got %r, %r' % (r0, spread))
+    return pat, r0, spread
+
+
+@on_device
+def beam_subrays(vps, dirs, pattern, r0, spread):
+    """Sub-rays of finite beams (dc_beam_subrays): beam i (view point vps[i], direction dirs[i], f32 | f64 [N,3], sensor frame) and the
+    pattern rows (px, py, weight) [S,3] (host array, units of the 1/e^2 radius) -> (origins f64 [N,S,3], directions f64 [N,S,3]) in
+    the sensor frame: origin v + r0 q and direction d + spread q, q = px e1 + py e2 in the beam's frame (include/dc_hip.h).  The
+    directions are not normalised: a cast's t along them is the axial depth."""
+    need(dirs, (None, 3), name='dirs')
+    dev = dirs.device
+    n = dirs.shape[0]
+    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
+    code = dtype_code(dirs)
+    pat, r0, spread = _beam_pattern_arg(pattern, r0, spread, False)
+    s = pat.shape[0]
+    origins = torch.empty((n, s, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((n, s, 3), dtype=torch.float64, device=dev)
+    if n == 0:
+        return origins, out
+    check(lib().dc_beam_subrays(ptr(vps), ptr(dirs), code, n, pat.ctypes.data_as(ctypes.c_void_p), s, r0, spread, ptr(origins), ptr(out),
+                                stream_ptr()), 'dc_beam_subrays')
+    return origins, out
+
+
+@on_device
+def raycast_beams(bvh, vps, dirs, scan_offset, poses, pattern, r0, spread, t_min=0.0, cull=True, weight='uniform', detection='quantile',
+                  tau=None, min_hits=1, want_samples=False):
+    """One return per finite beam (dc_raycast_beams): the S sub-rays of beam_subrays are cast like raycast_rays' rays (scan_offset
+    counts beams: S+1 integers from 0 to N as a sequence, checked here, or an int64 device tensor, taken as it is; poses f64 [S,4,4])
+    and reduced in the same launch -> (face i32 [N] (-1 = miss), depth f64 [N] axial depth in metres (inf on a miss), n_hits i32 [N]).
+    ``weight``: 'uniform' | 'lambert' (the pattern weight times the cosine of incidence); ``detection``: 'quantile' (the t of the
+    first hit, ordered by depth, at which the running weight reaches ``tau`` of the total: tau = 1/S (the default) the first return,
+    0.5 the weighted median, 1 the last return) | 'mean' (weighted mean depth).  A beam with fewer than ``min_hits`` hits is a miss.
+    ``t_min``: a float, or a device tensor f64 [N] of per-beam near clips.  ``want_samples`` adds (sub_face i32 [N,S], sub_t f64
+    [N,S], sub_w f64 [N,S]) of every sub-ray (-1 / inf / 0 for one that is not a hit)."""
+    dev = bvh.leaf_face.device
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n = dirs.shape[0]
+    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
+    code = dtype_code(dirs)
+    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
+    s = poses.shape[0]
+    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
+        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)      # clamped by the kernel, as in raycast_rays
+    else:
+        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
+        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    if n and s < 1:
+        raise ValueError('beams need at least one pose')
+    pat, r0, spread = _beam_pattern_arg(pattern, r0, spread, True)
+    ns = pat.shape[0]
+    if weight not in nv.BEAM_WEIGHTS:
+        raise ValueError('weight must be one of %s, got %r' % (sorted(nv.BEAM_WEIGHTS), weight))
+    if detection not in nv.BEAM_DETECTIONS:
+        raise ValueError('detection must be one of %s, got %r' % (sorted(nv.BEAM_DETECTIONS), detection))
+    tau = 1.0 / ns if tau is None else float(tau)
+    if not 0.0 < tau <= 1.0:
+        raise ValueError('tau must lie in (0, 1], got %r' % (tau,))
+    if isinstance(min_hits, bool) or int(min_hits) != min_hits or not 1 <= int(min_hits) <= ns:
+        raise ValueError('min_hits must be an int in 1 .. %d, got %r' % (ns, min_hits))
+    if isinstance(t_min, torch.Tensor):
+        tm_beam, tm = need(t_min, (n,), dtype=torch.float64, name='t_min', device=dev), 0.0
+    else:
+        tm_beam, tm = None, float(t_min)
+        if tm != tm:
+            raise ValueError('t_min must not be NaN')
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    depth = torch.empty((n,), dtype=torch.float64, device=dev)
+    n_hits = torch.empty((n,), dtype=torch.int32, device=dev)
+    sub = ()
+    if want_samples:
+        sub = (torch.empty((n, ns), dtype=torch.int32, device=dev), torch.empty((n, ns), dtype=torch.float64, device=dev),
+               torch.empty((n, ns), dtype=torch.float64, device=dev))
+    if n:
+        off = off.to(dev)
+        nf = bvh.n_faces
+        check(lib().dc_raycast_beams(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                                     ptr(vps), ptr(dirs), code, n, ptr(off), ptr(poses), s, pat.ctypes.data_as(ctypes.c_void_p), ns, r0,
+                                     spread, ptr(tm_beam), tm, 1 if cull else 0, nv.BEAM_WEIGHTS[weight], nv.BEAM_DETECTIONS[detection], tau,
+                                     int(min_hits), ptr(face), ptr(depth), ptr(n_hits), ptr(sub[0]) if sub else None,
+                                     ptr(sub[1]) if sub else None, ptr(sub[2]) if sub else None, stream_ptr()), 'dc_raycast_beams')
+    return (face, depth, n_hits) + sub
 
 
 # ------------------------------------------------------------------------------------------------

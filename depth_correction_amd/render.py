@@ -3,6 +3,9 @@
 The reference composes a scan of ``num_segments`` perspective renders of pytorch3d's rasteriser, one segment at a time on the
 host.  Here every ray of every pose is cast in one launch against an LBVH of the mesh (``dc_raycast``); the rays restate the
 reference's cameras (``lidar_directions``).  Compaction, the sensor-frame transform and the field assembly use torch.
+
+With a ``BeamModel`` a pixel is a finite beam instead of a thin ray: a bundle of sub-rays over the laser's footprint, cast and
+reduced to one return in one launch (``dc_raycast_beams``; DESIGN "Finite-beam rendering").
 """
 from __future__ import annotations
 
@@ -18,7 +21,8 @@ from numpy.lib.recfunctions import unstructured_to_structured
 
 from .dataset import TransformingDataset
 
-__all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'DepthBiasDataset', 'mesh_dir']
+__all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'DepthBiasDataset', 'mesh_dir',
+           'BeamModel']
 
 Z_CLIP = 1e-3          # pytorch3d RasterizationSettings(z_clip_value=1e-3) of the reference
 
@@ -83,14 +87,59 @@ def _device(mesh_device):
     return dev
 
 
+class BeamModel(object):
+    """A finite laser beam for the renderer: ``samples`` sub-rays (a power of two <= 64) over the footprint sensor.beam_pattern(samples,
+    rho_max), aperture radius ``r0`` and half divergence ``divergence`` (both 1/e^2; from ``sensor``'s waist_radius and divergence
+    unless given), so that the footprint radius at the axial depth z is r0 + z tan(divergence).  ``detection`` 'quantile' returns the
+    depth at which the running weight of the returns, ordered by depth, reaches ``tau`` of the total (None: 1 / samples, the first
+    return); 'mean' their weighted mean.  ``weight`` 'uniform' | 'lambert'; a beam with fewer than ``min_hits`` returns is dropped."""
+
+    def __init__(self, sensor=None, samples=16, rho_max=1.5, detection='quantile', tau=None, weight='uniform', min_hits=1, r0=None,
+                 divergence=None):
+        from . import _native as nv
+        from .sensor import Sensors, beam_pattern
+        sensor = Sensors.OUSTER if sensor is None else sensor
+        samples = int(samples)
+        if not 1 <= samples <= nv.DC_BEAM_MAX_SAMPLES or samples & (samples - 1):
+            raise ValueError('samples must be a power of two in 1 .. %d, got %d' % (nv.DC_BEAM_MAX_SAMPLES, samples))
+        if detection not in nv.BEAM_DETECTIONS:
+            raise ValueError('detection must be one of %s, got %r' % (sorted(nv.BEAM_DETECTIONS), detection))
+        if weight not in nv.BEAM_WEIGHTS:
+            raise ValueError('weight must be one of %s, got %r' % (sorted(nv.BEAM_WEIGHTS), weight))
+        self.sensor, self.samples, self.rho_max = sensor, samples, float(rho_max)
+        self.detection, self.weight = detection, weight
+        self.tau = 1.0 / samples if tau is None else float(tau)
+        if not 0.0 < self.tau <= 1.0:
+            raise ValueError('tau must lie in (0, 1], got %r' % (tau,))
+        self.min_hits = int(min_hits)
+        if not 1 <= self.min_hits <= samples:
+            raise ValueError('min_hits must lie in 1 .. %d, got %r' % (samples, min_hits))
+        self.r0 = float(sensor.waist_radius if r0 is None else r0)
+        self.divergence = float(sensor.divergence if divergence is None else divergence)
+        if not (0.0 <= self.r0 < math.inf) or not (0.0 <= self.divergence < math.pi / 2):
+            raise ValueError('r0 must be finite and >= 0 and divergence in [0, pi/2), got %r, %r' % (self.r0, self.divergence))
+        self.spread = math.tan(self.divergence)
+        self.pattern = beam_pattern(samples, self.rho_max)
+        self.pattern.flags.writeable = False
+
+    def cache_key(self):
+        """Directory component of RenderedMeshDataset's cache: every parameter a rendered cloud depends on."""
+        return 'beam_s_%i_rho_%r_%s_tau_%r_%s_hits_%i_r0_%r_div_%r' % (self.samples, self.rho_max, self.detection, self.tau, self.weight,
+                                                                      self.min_hits, self.r0, self.divergence)
+
+
 _DT = np.dtype([(f, np.float64) for f in ('x', 'y', 'z', 'vp_x', 'vp_y', 'vp_z', 'normal_x', 'normal_y', 'normal_z')])
 
 
-def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True):
+def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None):
     """Scans of ``mesh`` (mesh.TriangleMesh) from every pose of ``poses`` [P,4,4] (world from sensor) in one cast: a list of P
     structured arrays of RenderedMeshDataset.cloud_dtype in the sensor frame (vp = 0, normals rotated into it), misses dropped,
-    points in lidar_directions' order.  The hit point is v0 + u (v1 - v0) + v (v2 - v0) in fp64 from the face's vertices."""
+    points in lidar_directions' order.  The hit point is v0 + u (v1 - v0) + v (v2 - v0) in fp64 from the face's vertices.
+    With ``beam`` (a BeamModel) every pixel is a finite beam along the same direction: the point is the beam's depth times the
+    direction, the normal that of the face of the return nearest to that depth, and a beam without a return is dropped."""
     from .ops import raycast
+    if beam is not None:
+        return _render_beam_clouds(mesh, poses, fov, size, num_segments, device, cull, beam)
     dev = _device(device)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     dirs_h, tmin_h = lidar_directions(size=size, fov=fov, num_segments=num_segments)
@@ -116,23 +165,54 @@ def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segmen
     return out
 
 
-def render_lidar_cloud(mesh, pose, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True):
+def _render_beam_clouds(mesh, poses, fov, size, num_segments, device, cull, beam):
+    """render_lidar_clouds with a BeamModel: every pose and pattern ray in one raycast_beams call."""
+    from .ops import raycast_beams
+    if not isinstance(beam, BeamModel):
+        raise TypeError('beam must be a BeamModel or None, got %s' % type(beam).__name__)
+    dev = _device(device)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    dirs_h, tmin_h = lidar_directions(size=size, fov=fov, num_segments=num_segments)
+    verts, faces, normals, bvh = mesh.on_device(dev)
+    dev = verts.device
+    n_poses, n_rays = poses.shape[0], dirs_h.shape[0]
+    dirs = torch.as_tensor(np.array(dirs_h), device=dev).repeat(n_poses, 1)
+    t_min = torch.as_tensor(np.array(tmin_h), device=dev).repeat(n_poses)
+    P = torch.as_tensor(poses, device=dev)
+    face, depth, _ = raycast_beams(bvh, torch.zeros_like(dirs), dirs, [n_rays * p for p in range(n_poses + 1)], P, beam.pattern, beam.r0,
+                                   beam.spread, t_min=t_min, cull=cull, weight=beam.weight, detection=beam.detection, tau=beam.tau,
+                                   min_hits=beam.min_hits)
+    dhat = dirs / torch.sqrt((dirs * dirs).sum(dim=1, keepdim=True))
+    out = []
+    for p in range(n_poses):
+        rows = slice(p * n_rays, (p + 1) * n_rays)
+        keep = face[rows] >= 0
+        f = face[rows][keep].long()
+        xs = depth[rows][keep][:, None] * dhat[rows][keep]
+        ns = normals[f] @ P[p, :3, :3]
+        arr = torch.cat([xs, torch.zeros_like(xs), ns], dim=1).cpu().numpy()
+        out.append(unstructured_to_structured(np.ascontiguousarray(arr), dtype=_DT))
+    return out
+
+
+def render_lidar_cloud(mesh, pose, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None):
     """One scan (render_lidar_clouds of one pose)."""
     return render_lidar_clouds(mesh, np.asarray(pose, dtype=np.float64)[None], fov=fov, size=size, num_segments=num_segments,
-                               device=device, cull=cull)[0]
+                               device=device, cull=cull, beam=beam)[0]
 
 
 class RenderedMeshDataset(object):
     """Lidar scans rendered from a mesh at given poses (dataset.py:490-716).  ``name``: an absolute mesh path, a path relative to
     mesh_dir(), or ``rendered_mesh/<mesh>[/<params>]`` with params such as ``n_10_size_64_512_fov_45_360``.  Poses from
     ``poses`` [N,4,4] or ``poses_path`` (a poses CSV, scan_io.read_poses_csv).  All poses are rendered in one cast at the first
-    cloud asked for; ``cache`` reads and writes ``cloud_%05i.bin`` files (np.tofile of cloud_dtype) under ``cache_dir``."""
+    cloud asked for; ``cache`` reads and writes ``cloud_%05i.bin`` files (np.tofile of cloud_dtype) under ``cache_dir``.  ``beam``
+    (a BeamModel) renders finite beams; their cache lives in a directory of its own, named by the beam's parameters."""
 
     dataset_name = 'rendered_mesh'
     cloud_dtype = _DT
 
     def __init__(self, name, n=None, size=(64, 512), fov=(45., 360.), num_segments=16, poses_path=None, poses=None, cache=False,
-                 device='cuda', cache_dir=None):
+                 device='cuda', cache_dir=None, beam=None):
         from .mesh import load_mesh
         from .scan_io import read_poses_csv
         from .utils import hashable
@@ -155,6 +235,9 @@ class RenderedMeshDataset(object):
         if n is not None and not (isinstance(n, int) and n > 0):
             raise ValueError('n must be a positive int, got %r' % (n,))
         _check_pattern(tuple(fov), tuple(size), num_segments)
+        if beam is not None and not isinstance(beam, BeamModel):
+            raise TypeError('beam must be a BeamModel or None, got %s' % type(beam).__name__)
+        self.beam = beam
         self.hash_name = ''
         if poses is None:
             if not poses_path:
@@ -230,8 +313,10 @@ class RenderedMeshDataset(object):
         return path
 
     def cloud_path(self, id):
-        return os.path.join(self.dataset_dir(), 'hash_%s_size_%i_%i_fov_%.0f_%.0f' % (self.hash_name, *self.size, *self.fov),
-                            'cloud_%05i.bin' % id)
+        params = os.path.join(self.dataset_dir(), 'hash_%s_size_%i_%i_fov_%.0f_%.0f' % (self.hash_name, *self.size, *self.fov))
+        if self.beam is not None:
+            params = os.path.join(params, self.beam.cache_key())
+        return os.path.join(params, 'cloud_%05i.bin' % id)
 
     def _render_all(self):
         """Every pose's scan, in one cast (the files of the cache are read instead where present)."""
@@ -245,7 +330,7 @@ class RenderedMeshDataset(object):
             todo = [id for id, c in enumerate(clouds) if c is None]
             if todo:
                 rendered = render_lidar_clouds(self.get_mesh(), self.poses[todo], fov=self.fov, size=self.size,
-                                               num_segments=self.num_segments, device=self.device)
+                                               num_segments=self.num_segments, device=self.device, beam=self.beam)
                 for id, c in zip(todo, rendered):
                     clouds[id] = c
                     if self.cache:

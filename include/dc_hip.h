@@ -821,6 +821,48 @@ int dc_raycast_rays(const int32_t* child, const float* node_box, const double* l
                     const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
                     double t_min, int cull, int32_t* face_out, double* t_out, double* inc_out, dcStream_t stream);
 
+/* ---- finite-beam rendering (dc_raycast.hip; per-beam arithmetic and the reduction rules in csrc/dc_beammath.h; DESIGN "Finite-beam
+ * rendering") ----
+ * A beam is a bundle of n_samples sub-rays, one per row (px, py, weight) of `pattern` (HOST double [n_samples,3], in units of the
+ * 1/e^2 radius; every entry finite, weight >= 0).  Beam i has the view point vps[i] and the direction s = dirs[i] (DC_F32 | DC_F64
+ * [n,3], sensor frame, scan-major; fp32 is converted exactly); all arithmetic is fp64 without fused multiply-adds:
+ *   d = s / sqrt(s . s);  a = the unit axis k of the smallest |d_k| (ties: the lower k);  e1 = (a x d) / |a x d|;  e2 = d x e1;
+ *   sample j:  q = px e1 + py e2,  origin v + r0 q,  direction D = d + spread q  (spread = tan of the half divergence; D is not
+ *   normalised and D . d = 1, so the cast's t is the axial depth along the beam, in metres).
+ * A beam whose direction is zero or not finite is a miss and its emitted sub-rays are NaN.  0 <= r0, spread, both finite.
+ * dc_beam_subrays writes the sub-rays (sensor frame) to origins_out / dirs_out double [n, n_samples, 3]; 1 <= n_samples <=
+ * DC_BEAM_MAX_SAMPLES.  n == 0 launches nothing. */
+#ifndef DC_BEAM_MAX_SAMPLES
+#define DC_BEAM_MAX_SAMPLES 64
+#define DC_BEAM_MEAN 0
+#define DC_BEAM_QUANTILE 1
+#define DC_BEAM_UNIFORM 0
+#define DC_BEAM_LAMBERT 1
+#endif
+int dc_beam_subrays(const void* vps, const void* dirs, int dtype, int64_t n, const double* pattern, int n_samples, double r0, double spread,
+                    double* origins_out, double* dirs_out, dcStream_t stream);
+/* One return per beam.  Sub-ray j of beam i goes into the mesh frame with dc_raycast_rays' expressions (scan_offset DEVICE int64
+ * [n_scans+1] counts beams; poses DEVICE double [n_scans,4,4]) and through the same device function with the beam's near clip
+ * (t_min_beam DEVICE double [n], or NULL: t_min) and dc_raycast's culling, so its face and t are bit-equal to dc_raycast_rays on the
+ * sub-rays dc_beam_subrays emits.  Its weight is w_j = the pattern weight (DC_BEAM_UNIFORM), times min(1, |n . D| / (|n| |D|)) on the
+ * winning triangle (DC_BEAM_LAMBERT: dc_raycast_rays' expression without the arccos).  A sub-ray that misses, or whose weight is not
+ * finite, is not a hit.  H = the hits, n_hits_out[i] = |H| (int32 [n]).  The beam is a miss (face_out -1, depth_out +inf) when
+ * n_hits < min_hits or the total weight is not > 0.  Otherwise
+ *   DC_BEAM_MEAN:      depth = (sum_{j in H} w_j t_j) / (sum_{j in H} w_j), both sums in ascending j, one term at a time;
+ *   DC_BEAM_QUANTILE:  H ordered by (t_j, j) ascending, c_m = the running sum of the weights in that order, added one at a time;
+ *                      depth = the t of the first m with c_m >= tau c_last  (tau = 1 / n_samples: the first return; 0.5: the
+ *                      weighted median; 1: the last return);
+ *   face_out[i] = the face of the hit with the smallest |t_j - depth|, ties to the lower j.
+ * sub_face int32 / sub_t / sub_w double [n, n_samples] (all three or none): every sub-ray's face, t and weight, -1 / +inf / 0 for one
+ * that is not a hit.  n_samples a power of two in 1 .. DC_BEAM_MAX_SAMPLES (the lanes of a beam share a wavefront), tau in (0, 1],
+ * min_hits in 1 .. n_samples, known kinds (DC_ERR_ARG otherwise).  One launch, no workspace, no atomics: bit-reproducible.  n == 0
+ * launches nothing. */
+int dc_raycast_beams(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                     const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                     const double* pattern, int n_samples, double r0, double spread, const double* t_min_beam, double t_min, int cull,
+                     int weight_kind, int detection, double tau, int min_hits, int32_t* face_out, double* depth_out, int32_t* n_hits_out,
+                     int32_t* sub_face, double* sub_t, double* sub_w, dcStream_t stream);
+
 /* ---- depth bias against the mesh (depth_correction_amd/csrc/dc_bias.hip, per-ray terms in dc_biasmath.h; DESIGN "Depth bias against
  * the mesh") ----
  * Per ray i of n: d = depth[i], g_est = inc_est[i] (DC_F32 | DC_F64 [n]; inc_est optional), the cast's face[i], t = t_true[i],
