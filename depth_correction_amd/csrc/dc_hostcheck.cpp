@@ -8,6 +8,7 @@
 #include "dc_trimath.h"
 #include "dc_biasmath.h"
 #include "dc_beammath.h"
+#include "dc_raymath.h"
 
 extern "C" {
 
@@ -193,6 +194,59 @@ int dc_host_beam_select(const int32_t* sub_face, const double* sub_t, const doub
     dc::beam_select(sub_face + i * n_samples, sub_t + i * n_samples, sub_w + i * n_samples, n_samples, detection, tau, min_hits, face_out + i,
                     depth_out + i, n_hits_out + i);
   return DC_OK;
+}
+
+// ---- the BVH ray caster's per-ray arithmetic (dc_raymath.h) --------------------------------------------------------------------------
+// leaf boxes of the triangles tri [n,9] -> box f32 [n,6] (lo xyz, hi xyz), as fit_kernel writes them
+void dc_host_ray_boxes(const double* tri, int64_t n, float* box) {
+  for (int64_t i = 0; i < n; ++i) dc::leaf_box(tri + 9 * i, box + 6 * i);
+}
+
+// box_entry of n (ray, box) pairs: o / d f64 [n,3] (world frame), box f32 [n,6], t_far f32 [n] -> tn f32 [n] (+inf: rejected)
+void dc_host_ray_box_entry(const double* o, const double* d, const float* box, const float* t_far, int64_t n, float* tn) {
+  for (int64_t i = 0; i < n; ++i) {
+    dc::Ray64 r64;
+    dc::Ray32 r32;
+    dc::ray_setup(d[3 * i], d[3 * i + 1], d[3 * i + 2], o[3 * i], o[3 * i + 1], o[3 * i + 2], r64, r32);
+    tn[i] = dc::box_entry(box + 6 * i, r32, t_far[i]);
+  }
+}
+
+// the t_far the traversal prunes with once its best hit lies at t [n]
+void dc_host_ray_prune_far(const double* t, int64_t n, float* t_far) {
+  for (int64_t i = 0; i < n; ++i) t_far[i] = dc::prune_far(t[i]);
+}
+
+// The oracle of dc_raycast / dc_raycast_rays: test_triangle on every face of tri [F,9] in row order (face_id [F] the index each
+// row reports, ascending for the tie rule to be the kernels'), no tree -> face i32 [R] (-1), t f64 [R] (inf), u / v f64 [R] (0).
+void dc_host_ray_cast_brute(const double* tri, const int32_t* face_id, int64_t n_faces, const double* o, const double* d, const double* t_min,
+                            int64_t n_rays, int cull, int32_t* face, double* t, double* u, double* v) {
+  for (int64_t i = 0; i < n_rays; ++i) {
+    dc::Ray64 r64;
+    dc::Ray32 r32;
+    dc::ray_setup(d[3 * i], d[3 * i + 1], d[3 * i + 2], o[3 * i], o[3 * i + 1], o[3 * i + 2], r64, r32);
+    dc::Hit best;
+    best.t = INFINITY;
+    best.u = best.v = 0.0;
+    best.face = -1;
+    best.leaf = -1;
+    for (int64_t f = 0; f < n_faces; ++f) dc::test_triangle(tri + 9 * f, face_id[f], (int32_t)f, r64, t_min[i], cull != 0, best);
+    face[i] = best.face;
+    t[i] = best.t;
+    u[i] = best.u;
+    v[i] = best.v;
+  }
+}
+
+// test_triangle pair by pair: ray i against triangle i (tri [n,9]) -> hit u8 [n], t / u / v f64 [n] (inf, 0, 0 without a hit)
+void dc_host_ray_test_pairs(const double* tri, const double* o, const double* d, const double* t_min, int64_t n, int cull, uint8_t* hit,
+                            double* t, double* u, double* v) {
+  const int32_t zero = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    int32_t f;
+    dc_host_ray_cast_brute(tri + 9 * i, &zero, 1, o + 3 * i, d + 3 * i, t_min + i, 1, cull, &f, t + i, u + i, v + i);
+    hit[i] = f == 0;
+  }
 }
 
 }  // extern "C"

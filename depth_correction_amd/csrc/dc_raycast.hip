@@ -11,14 +11,19 @@
 // Node numbering: internal nodes 0 .. n-2 (root 0), leaf i is node n-1+i; with one face the root is leaf 0.  The tree's depth is
 // at most 63: a child's keys share a strictly longer prefix than its parent's, and the 64-bit keys start with two zero bits.
 //
-// Closest-hit cast (dc_raycast): one lane per ray, every (pose, ray) pair in one launch.  The boxes are tested in fp32 (slab test;
-// the exit distance is scaled by 1 + 2^-20, Ize 2013's 1 + 2 gamma_3 with headroom for the fp32 rounding of the direction, and
-// the boxes grow by 2^-22 |origin| for the rounding of the origin), so no box a ray touches in exact arithmetic is rejected.  The
-// nearer child is visited first; the other goes on a per-lane stack in LDS (depth 64, lane-minor so that a wavefront's pushes hit
-// 64 distinct banks).  Triangles are tested in fp64 with the watertight test of Woop, Benthin and Wald (JCGT 2013): a ray through
-// a shared edge or vertex hits at least one of the faces around it (no FMA contraction there, see test_triangle).  A hit counts
-// when t > t_min (and dot(n, d) < 0 with culling); the smallest t wins, equal t the lower face index -- independent of the
-// traversal order, so results are bitwise reproducible.
+// Closest-hit cast (dc_raycast): one lane per ray, every (pose, ray) pair in one launch.  The per-ray arithmetic is dc_raymath.h (host
+// and device).  The boxes are tested in fp32 (slab test; the exit distance is scaled by 1 + 2^-20, Ize 2013's 1 + 2 gamma_3 with
+// headroom for the fp32 rounding of the direction; the boxes grow by 2^-22 |origin|, at least 1e-20, for the rounding of the
+// origin; a direction component below 1e-30 counts as 1e-30, so that a ray running exactly on a slab's boundary stays in it up
+// to t = 1e10; and the best hit's t prunes with the same 1 + 2^-20, because the fp32 entry distance of a flat box met face-on can
+// exceed the exact hit distance by a few 2^-24).  The nearer child is visited first; the other goes on a per-lane stack in LDS
+// (depth 64, lane-minor so that a wavefront's pushes hit 64 distinct banks).  Triangles are tested in fp64 with the watertight
+// test of Woop, Benthin and Wald (JCGT 2013), no FMA contraction there (see test_triangle).  A hit counts when t > t_min (and
+// dot(n, d) < 0 with culling).  Guaranteed, and pinned by tests/test_raycast_host.py and tests/test_gpu_raycast_edge.py:
+//   1. no box is rejected that holds a face test_triangle reports a hit on, before the first hit and under the pruning rule;
+//   2. so the cast returns what test_triangle over every face in index order returns: the smallest t, on equal t the lower face
+//      index, independent of the tree and of the traversal order, bitwise reproducible and equal to the host build's answer;
+//   3. a ray through a shared edge or vertex hits at least one of the faces around it.
 //
 // dc_raycast_rays casts the rays of measured clouds (per-ray view point and direction, per-scan pose) through the same device
 // function (cast_ray) and adds the true incidence angle on the winning triangle: the ground truth of eval_bias.
@@ -29,6 +34,7 @@
 // the reduction is done, because a cross-lane read from a lane that has left returns garbage.
 #include "dc_common.h"
 #include "dc_beammath.h"
+#include "dc_raymath.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
 #include "../../include/dc_hip.h"
@@ -128,11 +134,7 @@ __global__ void __launch_bounds__(kBuildBlock) fit_kernel(const double* __restri
 #pragma unroll
   for (int k = 0; k < 9; ++k) leaf_tri[9 * i + k] = v[k];
   int64_t node = (n - 1) + i;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    node_box[6 * node + a] = __double2float_rd(fmin(fmin(v[a], v[3 + a]), v[6 + a]));
-    node_box[6 * node + 3 + a] = __double2float_ru(fmax(fmax(v[a], v[3 + a]), v[6 + a]));
-  }
+  dc::leaf_box(v, node_box + 6 * node);
   node = parent[node];
   while (node >= 0) {
     __threadfence();                                        // this child's box is visible before the counter says so
@@ -148,70 +150,11 @@ __global__ void __launch_bounds__(kBuildBlock) fit_kernel(const double* __restri
   }
 }
 
-struct Ray32 {
-  float o[3], inv[3], margin;
-};
-
-// entry distance of the box of `node` (>= 0), or +inf when the ray misses it before t_far
-__device__ __forceinline__ float box_entry(const float* __restrict__ node_box, int64_t node, const Ray32& r, float t_far) {
-  const float* b = node_box + 6 * node;
-  float tn = 0.0f, tf = t_far;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float t0 = (b[a] - r.margin - r.o[a]) * r.inv[a];
-    const float t1 = (b[3 + a] + r.margin - r.o[a]) * r.inv[a];
-    tn = fmaxf(tn, fminf(t0, t1));
-    tf = fminf(tf, fmaxf(t0, t1) * (1.0f + 0x1p-20f));
-  }
-  return tn <= tf ? tn : INFINITY;
-}
-
-struct Hit {
-  double t, u, v;
-  int32_t face;
-  int32_t leaf;                 // the winning leaf (row of leaf_tri), -1 without a hit
-};
-
-// A ray in the frame of the watertight test: axes permuted to (kx, ky, kz), kz the dominant one.  Scalars only: the compiler turns
-// a select between elements of a private array into a runtime index, and a runtime-indexed private array lives in scratch memory.
-struct Ray64 {
-  double d0, d1, d2;            // direction (world frame), for the culling test
-  double ox, oy, oz;            // origin, permuted
-  double sx, sy, sz;            // shear constants
-  int kx, ky, kz;
-};
-
-__device__ __forceinline__ double pick(int k, double a, double b, double c) { return k == 0 ? a : (k == 1 ? b : c); }
-
-// Woop, Benthin, Wald 2013 in fp64; t, u (weight of v1), v (weight of v2) of a hit with t > t_min that beats `best`
-__device__ __forceinline__ void test_triangle(const double* __restrict__ tri, int32_t face, int32_t leaf, const Ray64& r, double t_min,
-                                              bool cull, Hit& best) {
-  // no fused multiply-adds here: watertightness needs the edge function of a shared edge to be computed as the exact negation
-  // of the neighbour's (fl(a b) - fl(c d) = -(fl(c d) - fl(a b)); fma(a, b, -fl(c d)) is not -fma(c, d, -fl(a b)))
-#pragma clang fp contract(off)
-  const double t0 = tri[0], t1 = tri[1], t2 = tri[2], t3 = tri[3], t4 = tri[4], t5 = tri[5], t6 = tri[6], t7 = tri[7], t8 = tri[8];
-  const double Az = pick(r.kz, t0, t1, t2) - r.oz, Bz = pick(r.kz, t3, t4, t5) - r.oz, Cz = pick(r.kz, t6, t7, t8) - r.oz;
-  const double Ax = (pick(r.kx, t0, t1, t2) - r.ox) - r.sx * Az, Ay = (pick(r.ky, t0, t1, t2) - r.oy) - r.sy * Az;
-  const double Bx = (pick(r.kx, t3, t4, t5) - r.ox) - r.sx * Bz, By = (pick(r.ky, t3, t4, t5) - r.oy) - r.sy * Bz;
-  const double Cx = (pick(r.kx, t6, t7, t8) - r.ox) - r.sx * Cz, Cy = (pick(r.ky, t6, t7, t8) - r.oy) - r.sy * Cz;
-  const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-  if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return;
-  const double det = U + V + W;
-  if (det == 0.0) return;
-  const double T = U * (r.sz * Az) + V * (r.sz * Bz) + W * (r.sz * Cz);
-  const double t = T / det;
-  if (!(t > t_min) || t > best.t || (t == best.t && face >= best.face)) return;
-  if (cull) {
-    const double e10 = t3 - t0, e11 = t4 - t1, e12 = t5 - t2, e20 = t6 - t0, e21 = t7 - t1, e22 = t8 - t2;
-    const double nd = (e11 * e22 - e12 * e21) * r.d0 + (e12 * e20 - e10 * e22) * r.d1 + (e10 * e21 - e11 * e20) * r.d2;
-    if (!(nd < 0.0)) return;
-  }
-  best.t = t;
-  best.u = V / det;
-  best.v = W / det;
-  best.face = face;
-  best.leaf = leaf;
-}
+using dc::Hit;
+using dc::Ray32;
+using dc::Ray64;
+using dc::box_entry;
+using dc::test_triangle;
 
 // Closest hit of one ray (origin o, direction d, both fp64 world frame) over the tree: the traversal both cast kernels share.
 // `stack` is the block's LDS stack (kStackDepth x kCastBlock, lane-minor); best.leaf is the winning leaf's row of leaf_tri.
@@ -220,36 +163,8 @@ __device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const
                                         double d1, double d2, double o0, double o1, double o2, double tmin, int cull, int32_t* stack,
                                         int lane) {
   Ray64 ray64;
-  ray64.d0 = d0;
-  ray64.d1 = d1;
-  ray64.d2 = d2;
-  // watertight test set-up: kz = dominant axis, (kx, ky) keep the winding
-  const double ad0 = fabs(ray64.d0), ad1 = fabs(ray64.d1), ad2 = fabs(ray64.d2);
-  const int kz = ad0 >= ad1 ? (ad0 >= ad2 ? 0 : 2) : (ad1 >= ad2 ? 1 : 2);
-  int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-  const double dz = pick(kz, ray64.d0, ray64.d1, ray64.d2);
-  if (dz < 0.0) { const int s = kx; kx = ky; ky = s; }
-  ray64.kx = kx;
-  ray64.ky = ky;
-  ray64.kz = kz;
-  ray64.sz = 1.0 / dz;
-  ray64.sx = pick(kx, ray64.d0, ray64.d1, ray64.d2) * ray64.sz;
-  ray64.sy = pick(ky, ray64.d0, ray64.d1, ray64.d2) * ray64.sz;
-  ray64.ox = pick(kx, o0, o1, o2);
-  ray64.oy = pick(ky, o0, o1, o2);
-  ray64.oz = pick(kz, o0, o1, o2);
   Ray32 ray;
-  const double oo[3] = {o0, o1, o2}, dd[3] = {ray64.d0, ray64.d1, ray64.d2};
-  float omax = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    ray.o[a] = (float)oo[a];
-    omax = fmaxf(omax, fabsf(ray.o[a]));
-    float da = (float)dd[a];
-    if (fabsf(da) < 1e-20f) da = copysignf(1e-20f, da);
-    ray.inv[a] = 1.0f / da;
-  }
-  ray.margin = fmaxf(omax * 0x1p-22f, 1e-30f);
+  dc::ray_setup(d0, d1, d2, o0, o1, o2, ray64, ray);
 
   Hit best;
   best.t = INFINITY;
@@ -258,15 +173,15 @@ __device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const
   best.leaf = -1;
   int sp = 0;
   int64_t node = 0;
-  bool live = box_entry(node_box, 0, ray, INFINITY) < INFINITY;
+  bool live = box_entry(node_box, ray, INFINITY) < INFINITY;
   while (live) {
     if (node >= n - 1) {
       const int64_t leaf = node - (n - 1);
       test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], (int32_t)leaf, ray64, tmin, cull != 0, best);
     } else {
-      const float t_far = __double2float_ru(best.t);
+      const float t_far = dc::prune_far(best.t);
       const int64_t ca = child[2 * node], cb = child[2 * node + 1];
-      const float ta = box_entry(node_box, ca, ray, t_far), tb = box_entry(node_box, cb, ray, t_far);
+      const float ta = box_entry(node_box + 6 * ca, ray, t_far), tb = box_entry(node_box + 6 * cb, ray, t_far);
       if (ta < INFINITY || tb < INFINITY) {
         if (ta < INFINITY && tb < INFINITY) {
           const bool a_first = ta <= tb;
@@ -284,7 +199,7 @@ __device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const
     while (sp > 0) {
       --sp;
       node = sp < kStackDepth ? stack[sp * kCastBlock + lane] : 0;
-      if (box_entry(node_box, node, ray, __double2float_ru(best.t)) < INFINITY) { live = true; break; }
+      if (box_entry(node_box + 6 * node, ray, dc::prune_far(best.t)) < INFINITY) { live = true; break; }
     }
   }
   return best;
