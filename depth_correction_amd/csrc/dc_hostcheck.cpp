@@ -9,6 +9,7 @@
 #include "dc_biasmath.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
+#include "dc_planemath.h"
 
 extern "C" {
 
@@ -247,6 +248,218 @@ void dc_host_ray_test_pairs(const double* tri, const double* o, const double* d,
     dc_host_ray_cast_brute(tri + 9 * i, &zero, 1, o + 3 * i, d + 3 * i, t_min + i, 1, cull, &f, t + i, u + i, v + i);
     hit[i] = f == 0;
   }
+}
+
+// ---- plane neighbourhoods (dc_planemath.h) -------------------------------------------------------------------------------------------
+namespace {
+inline void host_load3(const void* p, int dtype, int64_t i, double* x) {
+  if (dtype == DC_F32) dc::load3((const float*)p, i, x);
+  else dc::load3((const double*)p, i, x);
+}
+inline double host_load1(const void* p, int dtype, int64_t i) { return dtype == DC_F32 ? (double)((const float*)p)[i] : ((const double*)p)[i]; }
+// the kernels' fixed-order tree over the kPlaneBlock values of one block
+inline double host_tree(double* sh) {
+  for (int s = dc::kPlaneBlock / 2; s > 0; s >>= 1)
+    for (int t = 0; t < s; ++t) sh[t] += sh[t + s];
+  return sh[0];
+}
+}  // namespace
+
+// the plane through p [9] (three points) -> pl [4]; returns 1 for a valid hypothesis
+int dc_host_plane_from_points(const double* p, int distinct, double* pl) { return dc::plane_from_points(p, p + 3, p + 6, distinct != 0, pl) ? 1 : 0; }
+
+// the inlier predicate of the plane pl [4] on x f64 [n,3] -> out u8 [n]
+void dc_host_plane_inliers(const double* pl, const double* x, int64_t n, double thresh, uint8_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = dc::plane_inlier(pl, x + 3 * i, thresh) ? 1 : 0;
+}
+
+// The oracle of dc_ransac_score: every hypothesis against every remaining point, no blocks, no LDS -> hyp [H,4], anchor [H,3],
+// valid [H], counts [H] (-1 for a degenerate hypothesis), best [2].  0, or 1 for arguments dc_ransac_score refuses.
+int dc_host_ransac_round(const void* points, int dtype, const int32_t* rem, int64_t n_rem, int64_t seed, int64_t round, int H, double thresh,
+                         double* hyp, double* anchor, int32_t* valid, int32_t* counts, int32_t* best) {
+  if (!points || !rem || !hyp || !anchor || !valid || !counts || !best) return 1;
+  if (n_rem < 3 || n_rem > INT32_MAX || H < 1 || H > 1024 || !(thresh >= 0.0)) return 1;
+  if (dtype != DC_F32 && dtype != DC_F64) return 1;
+  int64_t key = INT64_MIN;
+  for (int h = 0; h < H; ++h) {
+    int64_t j[3];
+    dc::ransac_draw((uint64_t)seed, round, h, n_rem, j);
+    double p[3][3];
+    for (int t = 0; t < 3; ++t) host_load3(points, dtype, (int64_t)rem[j[t]], p[t]);
+    const bool ok = dc::plane_from_points(p[0], p[1], p[2], j[0] != j[1] && j[0] != j[2] && j[1] != j[2], hyp + 4 * h);
+    for (int a = 0; a < 3; ++a) anchor[3 * h + a] = p[0][a];
+    valid[h] = ok ? 1 : 0;
+    int32_t c = 0;
+    for (int64_t i = 0; i < n_rem; ++i) {
+      double x[3];
+      host_load3(points, dtype, (int64_t)rem[i], x);
+      c += dc::plane_inlier(hyp + 4 * h, x, thresh) ? 1 : 0;
+    }
+    const int64_t k = dc::ransac_best_key(c, ok, H, h);
+    counts[h] = ok ? c : -1;
+    key = k > key ? k : key;
+  }
+  dc::ransac_best_decode(key, H, best);
+  return 0;
+}
+
+// the blocks of dc_ransac_refit's moments kernel (dc_ransac_refit_partial_count of the product library)
+int dc_host_ransac_refit_partial_count(int64_t n_rem) {
+  const int64_t b = (n_rem + dc::kPlaneBlock - 1) / dc::kPlaneBlock;
+  return (int)(b < 1 ? 1 : (b > dc::kRefitBlocksMax ? dc::kRefitBlocksMax : b));
+}
+
+// The oracle of dc_ransac_refit with the kernel's order of summation: every block's threads stride over the remaining points, the
+// 256-thread tree, then the blocks in order -> totals [10] (optional), params [4], mask u8 [n_rem]
+int dc_host_ransac_refit(const void* points, int dtype, const int32_t* rem, int64_t n_rem, const double* hyp, const double* anchor,
+                         const int32_t* best, double thresh, double* totals, double* params, uint8_t* mask) {
+  if (!points || !rem || !hyp || !anchor || !best || !params || !mask) return 1;
+  if (n_rem < 1 || n_rem > INT32_MAX || !(thresh >= 0.0)) return 1;
+  if (dtype != DC_F32 && dtype != DC_F64) return 1;
+  const int nblk = dc_host_ransac_refit_partial_count(n_rem);
+  const int h = best[0];
+  const double* pl = hyp + 4 * h;
+  const double* a = anchor + 3 * h;
+  double tot[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  static thread_local double sh[10][dc::kPlaneBlock];
+  for (int b = 0; b < nblk; ++b) {
+    for (int t = 0; t < dc::kPlaneBlock; ++t) {
+      double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int64_t i = (int64_t)b * dc::kPlaneBlock + t; i < n_rem; i += (int64_t)nblk * dc::kPlaneBlock) {
+        double x[3];
+        host_load3(points, dtype, (int64_t)rem[i], x);
+        if (dc::plane_inlier(pl, x, thresh)) dc::refit_moments_add(x, a, v);
+      }
+      for (int k = 0; k < 10; ++k) sh[k][t] = v[k];
+    }
+    for (int k = 0; k < 10; ++k) tot[k] += host_tree(sh[k]);
+  }
+  if (totals)
+    for (int k = 0; k < 10; ++k) totals[k] = tot[k];
+  dc::plane_refit(tot, a, params);
+  for (int64_t i = 0; i < n_rem; ++i) {
+    double x[3];
+    host_load3(points, dtype, (int64_t)rem[i], x);
+    mask[i] = dc::plane_inlier(params, x, thresh) ? 1 : 0;
+  }
+  return 0;
+}
+
+// the refit's eigenvector step alone: C [6] (xx xy xz yy yz zz) -> nv [3], before the sign rule and the normalisation
+void dc_host_smallest_eigvec_jacobi(const double* C, double* nv) { dc::smallest_eigvec_jacobi(C, nv); }
+
+// plane_refit on ten given moments
+void dc_host_plane_refit(const double* v, const double* anchor, double* params) { dc::plane_refit(v, anchor, params); }
+
+// Sequential DBSCAN on the padded neighbour table nbr [m,K] (rows end with -1; a row holds the point itself): core = at least
+// min_pts entries, union-find over the core-core edges in row order with the smaller root on top, so a component's label is its
+// smallest index; a non-core point takes the smallest label among its core neighbours -> label [m] (-1 noise), best [2]
+int dc_host_dbscan(const int32_t* nbr, int64_t m, int K, int min_pts, int32_t* label, int32_t* best) {
+  if (!nbr || !label || !best || m < 1 || m > INT32_MAX || K < 1 || min_pts < 1) return 1;
+  int32_t* par = new int32_t[m];
+  int32_t* size = new int32_t[m];
+  uint8_t* core = new uint8_t[m];
+  for (int64_t i = 0; i < m; ++i) {
+    int c = 0;
+    for (int k = 0; k < K; ++k) c += nbr[i * K + k] >= 0;
+    core[i] = c >= min_pts;
+    par[i] = (int32_t)i;
+    size[i] = 0;
+  }
+  auto find = [&](int32_t x) {
+    while (par[x] != x) { par[x] = par[par[x]]; x = par[x]; }
+    return x;
+  };
+  for (int64_t i = 0; i < m; ++i) {
+    if (!core[i]) continue;
+    for (int k = 0; k < K; ++k) {
+      const int32_t j = nbr[i * K + k];
+      if (j < 0) break;
+      if (j == i || !core[j]) continue;
+      const int32_t ri = find((int32_t)i), rj = find(j);
+      if (ri != rj) par[ri > rj ? ri : rj] = ri > rj ? rj : ri;
+    }
+  }
+  for (int64_t i = 0; i < m; ++i) {
+    int32_t l = -1;
+    if (core[i]) {
+      l = find((int32_t)i);
+    } else {
+      for (int k = 0; k < K; ++k) {
+        const int32_t j = nbr[i * K + k];
+        if (j < 0) break;
+        if (!core[j]) continue;
+        const int32_t lj = find(j);
+        if (l < 0 || lj < l) l = lj;
+      }
+    }
+    label[i] = l;
+    if (l >= 0) ++size[l];
+  }
+  best[0] = -1;
+  best[1] = 0;
+  for (int64_t l = 0; l < m; ++l)
+    if (size[l] > best[1]) { best[0] = (int32_t)l; best[1] = size[l]; }
+  delete[] par;
+  delete[] size;
+  delete[] core;
+  return 0;
+}
+
+// model_eval and model_dw at (d, g): out [3 + n_terms] <- d', dd'/dd, dd'/dg, dd'/dw_k
+void dc_host_plane_model(int kind, int n_terms, const double* w, const double* e, double d, double g, double* out) {
+  dc::ModelParams mp;
+  dc::load_model_params(kind, n_terms, w, e, mp);
+  out[0] = dc::model_eval(mp, d, g, out + 1, out + 2);
+  if (kind != DC_MODEL_NONE)
+    for (int k = 0; k < n_terms; ++k) out[3 + k] = dc::model_dw(mp, k, d, g);
+}
+
+// dc_plane_moments_fwd for one plane: the rows idx [n] of the cloud (vps / dirs [N,3], depth [N], `dtype`), normal [3] -> cov [9],
+// mean [3], x f64 [n,3] (optional: the corrected points).  The moments are summed in index order about the first point.
+int dc_host_plane_moments_fwd(const void* vps, const void* dirs, const void* depth, int dtype, const int32_t* idx, int64_t n, const double* normal,
+                              int kind, int n_terms, const double* w, const double* e, double* cov, double* mean, double* x_out) {
+  if (!vps || !dirs || !depth || !idx || !normal || !cov || !mean || n < 1 || n_terms < 0 || n_terms > DC_MAX_MODEL_TERMS) return 1;
+  if (kind < DC_MODEL_NONE || kind > DC_MODEL_LAST || (kind != DC_MODEL_NONE && !w)) return 1;
+  dc::ModelParams mp;
+  dc::load_model_params(kind, n_terms, w, e, mp);
+  dc::PlanePoint q;
+  double a[3], v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t r = 0; r < n; ++r) {
+    if (dtype == DC_F32) dc::plane_point((const float*)vps, (const float*)dirs, (const float*)depth, (int64_t)idx[r], normal, mp, q);
+    else dc::plane_point((const double*)vps, (const double*)dirs, (const double*)depth, (int64_t)idx[r], normal, mp, q);
+    if (r == 0)
+      for (int k = 0; k < 3; ++k) a[k] = q.x[k];
+    dc::plane_moments_add(q.x, a, v);
+    if (x_out)
+      for (int k = 0; k < 3; ++k) x_out[3 * r + k] = q.x[k];
+  }
+  dc::plane_cov_finish(v, (double)n, a, cov, mean);
+  return 0;
+}
+
+// dc_plane_moments_bwd for one plane: mean [3] of the forward, gcov [9] -> g_vps / g_dirs f64 [n,3], g_depth f64 [n] (per row of idx,
+// before the rounding to the cloud's dtype), g_w [n_terms] (summed in index order)
+int dc_host_plane_moments_bwd(const void* vps, const void* dirs, const void* depth, int dtype, const int32_t* idx, int64_t n, const double* normal,
+                              int kind, int n_terms, const double* w, const double* e, const double* mean, const double* gcov, double* g_vps,
+                              double* g_dirs, double* g_depth, double* g_w) {
+  if (!vps || !dirs || !depth || !idx || !normal || !mean || !gcov || !g_vps || !g_dirs || !g_depth || n < 1) return 1;
+  if (n_terms < 0 || n_terms > DC_MAX_MODEL_TERMS || (n_terms > 0 && !g_w)) return 1;
+  if (kind < DC_MODEL_NONE || kind > DC_MODEL_LAST || (kind != DC_MODEL_NONE && !w)) return 1;
+  dc::ModelParams mp;
+  dc::load_model_params(kind, n_terms, w, e, mp);
+  double M[3][3];
+  dc::plane_bwd_matrix(gcov, (double)(n - 1), M);
+  for (int k = 0; k < n_terms; ++k) g_w[k] = 0.0;
+  dc::PlanePoint q;
+  for (int64_t r = 0; r < n; ++r) {
+    if (dtype == DC_F32) dc::plane_point((const float*)vps, (const float*)dirs, (const float*)depth, (int64_t)idx[r], normal, mp, q);
+    else dc::plane_point((const double*)vps, (const double*)dirs, (const double*)depth, (int64_t)idx[r], normal, mp, q);
+    const double gdp = dc::plane_bwd_point(q, normal, M, mean, kind, g_vps + 3 * r, g_dirs + 3 * r, g_depth + r);
+    if (kind != DC_MODEL_NONE)
+      for (int k = 0; k < n_terms; ++k) g_w[k] += gdp * dc::model_dw(mp, k, q.d, q.g);
+  }
+  return 0;
 }
 
 }  // extern "C"

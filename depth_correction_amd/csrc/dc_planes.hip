@@ -12,32 +12,28 @@
 //     j_t = splitmix64(seed ^ (m << 40) ^ (h << 2) ^ t) mod n_remaining       (uint64 arithmetic)
 //     p_t = x[remaining[j_t]] in fp64; u = p1 - p0, v = p2 - p0, c = u x v
 //     degenerate (score -1) when two j_t coincide or |c| <= 1e-12 |u| |v|; else n = c / |c|, d = -n . p0
-//   a point is an inlier when |n . x + d| <= thresh (fp64 whatever the cloud's dtype); counts are integer sums, the best
+//   a point is an inlier when |fma(n2, x2, fma(n1, x1, n0 x0)) + d| <= thresh (fp64 whatever the cloud's dtype); counts are integer sums, the best
 //   hypothesis has the largest count, ties go to the lowest h.  All H hypotheses are scored (no adaptive early stop).
 // Refit: fp64 centroid and covariance of the inliers (per-block partials summed in block order; no float atomics), n = the
-//   eigenvector of the smallest eigenvalue (dc_eig3.h), its largest-magnitude component made positive, d = -n . centroid;
-//   the inliers are selected again with the refined plane.
+//   eigenvector of the smallest eigenvalue (cyclic Jacobi, dc_planemath.h), its largest-magnitude component made positive,
+//   d = -n . centroid; the inliers are selected again with the refined plane.
+// The per-element arithmetic (hypothesis, inlier predicate with its stated operation order, best key, refit, model, plane point,
+// covariance, per-point backward) lives in dc_planemath.h, host and device; everything up to the refit is bit-identical on both.
 // DBSCAN: core = >= min_pts neighbours within eps (itself included); components over core-core edges by union-find
 //   (atomicMin hooking of the larger root under the smaller one + pointer jumping, until nothing changes): every label is
 //   the smallest index of its component whatever the schedule.  A non-core point takes the smallest label among its core
 //   neighbours, or is noise (-1).  The largest cluster wins, ties to the smaller label.
 #include "dc_common.h"
 #include "../../include/dc_hip.h"
-#include "dc_pointmath.h"
-#include "dc_rng.h"
+#include "dc_planemath.h"
 
 namespace dc {
 
 namespace {
-constexpr int kPBlock = 256;                 // threads of every kernel here (4 waves of 64)
+constexpr int kPBlock = kPlaneBlock;         // threads of every kernel here (4 waves of 64)
 constexpr int kPWaves = kPBlock / 64;
 constexpr int kScorePts = 4;                 // points per thread of the scoring kernel
 constexpr int kMaxHyp = 1024;                // LDS: 32 B of plane + 16 B of per-wave counts per hypothesis
-
-template <typename T>
-__device__ __forceinline__ void load3(const T* p, int64_t i, double* x) {
-  x[0] = (double)p[i * 3]; x[1] = (double)p[i * 3 + 1]; x[2] = (double)p[i * 3 + 2];
-}
 
 // fixed-order tree over the block: the same sum for the same inputs whatever the schedule
 template <int NV>
@@ -62,28 +58,14 @@ __global__ __launch_bounds__(kPBlock) void ransac_hyp_kernel(const T* __restrict
   const int h = blockIdx.x * kPBlock + threadIdx.x;
   if (h >= H) return;
   int64_t j[3];
-  for (int t = 0; t < 3; ++t)
-    j[t] = (int64_t)(splitmix64(seed ^ ((uint64_t)round << 40) ^ ((uint64_t)h << 2) ^ (uint64_t)t) % (uint64_t)n_rem);
+  ransac_draw(seed, round, h, n_rem, j);
   double p[3][3];
   for (int t = 0; t < 3; ++t) load3(pts, (int64_t)rem[j[t]], p[t]);
-  const double u[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-  const double v[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-  const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-  const double nc = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-  const double nu = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), nv = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  const bool ok = j[0] != j[1] && j[0] != j[2] && j[1] != j[2] && nc > 1e-12 * nu * nv;
-  double n[3] = {0.0, 0.0, 0.0}, d = (double)INFINITY;             // a degenerate plane has no inlier
-  if (ok) {
-    n[0] = c[0] / nc; n[1] = c[1] / nc; n[2] = c[2] / nc;
-    d = -(n[0] * p[0][0] + n[1] * p[0][1] + n[2] * p[0][2]);
-  }
-  hyp[h * 4] = n[0]; hyp[h * 4 + 1] = n[1]; hyp[h * 4 + 2] = n[2]; hyp[h * 4 + 3] = d;
+  double pl[4];
+  const bool ok = plane_from_points(p[0], p[1], p[2], j[0] != j[1] && j[0] != j[2] && j[1] != j[2], pl);
+  hyp[h * 4] = pl[0]; hyp[h * 4 + 1] = pl[1]; hyp[h * 4 + 2] = pl[2]; hyp[h * 4 + 3] = pl[3];
   anchor[h * 3] = p[0][0]; anchor[h * 3 + 1] = p[0][1]; anchor[h * 3 + 2] = p[0][2];
   valid[h] = ok ? 1 : 0;
-}
-
-__device__ __forceinline__ bool inlier(const double* pl, const double* x, double thresh) {
-  return fabs(pl[0] * x[0] + pl[1] * x[1] + pl[2] * x[2] + pl[3]) <= thresh;
 }
 
 // every hypothesis against kPBlock * kScorePts remaining points per block: per-wave ballot counts in LDS, one integer atomic
@@ -109,7 +91,7 @@ __global__ __launch_bounds__(kPBlock) void ransac_score_kernel(const T* __restri
     const double* pl = s_hyp + 4 * h;
     int c = 0;
 #pragma unroll
-    for (int q = 0; q < kScorePts; ++q) c += __popcll(__ballot(inlier(pl, x[q], thresh)));
+    for (int q = 0; q < kScorePts; ++q) c += __popcll(__ballot(plane_inlier(pl, x[q], thresh)));
     if (lane == 0) s_cnt[wave * H + h] = c;
   }
   __syncthreads();
@@ -126,9 +108,8 @@ __global__ __launch_bounds__(kPBlock) void ransac_best_kernel(int32_t* __restric
   __shared__ int64_t s_key[kPBlock];
   int64_t key = INT64_MIN;
   for (int h = threadIdx.x; h < H; h += kPBlock) {
-    const int32_t c = valid[h] ? counts[h] : -1;
+    const int64_t k = ransac_best_key(counts[h], valid[h] != 0, H, h);
     if (!valid[h]) counts[h] = -1;
-    const int64_t k = ((int64_t)c << 32) | (int64_t)(uint32_t)(H - 1 - h);
     key = k > key ? k : key;
   }
   s_key[threadIdx.x] = key;
@@ -137,11 +118,7 @@ __global__ __launch_bounds__(kPBlock) void ransac_best_kernel(int32_t* __restric
     if (threadIdx.x < s && s_key[threadIdx.x + s] > s_key[threadIdx.x]) s_key[threadIdx.x] = s_key[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    const int64_t k = s_key[0];
-    best[0] = H - 1 - (int32_t)(uint32_t)(k & 0xffffffffll);
-    best[1] = (int32_t)(k >> 32);
-  }
+  if (threadIdx.x == 0) ransac_best_decode(s_key[0], H, best);
 }
 
 // inlier moments of the best hypothesis about its first sample point: [count, s(3), S(6)] per block
@@ -158,10 +135,8 @@ __global__ __launch_bounds__(kPBlock) void ransac_moments_kernel(const T* __rest
   for (int64_t i = (int64_t)blockIdx.x * kPBlock + threadIdx.x; i < n_rem; i += (int64_t)gridDim.x * kPBlock) {
     double x[3];
     load3(pts, (int64_t)rem[i], x);
-    if (!inlier(pl, x, thresh)) continue;
-    const double dx = x[0] - a[0], dy = x[1] - a[1], dz = x[2] - a[2];
-    v[0] += 1.0; v[1] += dx; v[2] += dy; v[3] += dz;
-    v[4] += dx * dx; v[5] += dx * dy; v[6] += dx * dz; v[7] += dy * dy; v[8] += dy * dz; v[9] += dz * dz;
+    if (!plane_inlier(pl, x, thresh)) continue;
+    refit_moments_add(x, a, v);
   }
   block_sum<10>(sh, v);
   if (threadIdx.x == 0)
@@ -174,23 +149,7 @@ __global__ void ransac_refit_kernel(const double* __restrict__ partials, int nbl
   double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = 0; b < nblk; ++b)
     for (int k = 0; k < 10; ++k) v[k] += partials[b * 10 + k];
-  const int h = best[0];
-  const double n = v[0];
-  const double m[3] = {v[1] / n, v[2] / n, v[3] / n};
-  const double C[6] = {v[4] / n - m[0] * m[0], v[5] / n - m[0] * m[1], v[6] / n - m[0] * m[2],
-                       v[7] / n - m[1] * m[1], v[8] / n - m[1] * m[2], v[9] / n - m[2] * m[2]};
-  double lam[3], V[3][3];
-  eig3_sym<double>(C[0], C[1], C[2], C[3], C[4], C[5], lam, V);
-  double nv[3] = {V[0][0], V[0][1], V[0][2]};
-  const double inv = 1.0 / sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-  int kmax = 0;
-  for (int k = 1; k < 3; ++k)
-    if (fabs(nv[k]) > fabs(nv[kmax])) kmax = k;
-  const double sg = nv[kmax] < 0.0 ? -inv : inv;
-  for (int k = 0; k < 3; ++k) nv[k] *= sg;
-  const double c[3] = {anchor[h * 3] + m[0], anchor[h * 3 + 1] + m[1], anchor[h * 3 + 2] + m[2]};
-  params[0] = nv[0]; params[1] = nv[1]; params[2] = nv[2];
-  params[3] = -(nv[0] * c[0] + nv[1] * c[1] + nv[2] * c[2]);
+  plane_refit(v, anchor + best[0] * 3, params);
 }
 
 template <typename T>
@@ -202,7 +161,7 @@ __global__ __launch_bounds__(kPBlock) void plane_select_kernel(const T* __restri
   double x[3];
   load3(pts, (int64_t)rem[i], x);
   const double pl[4] = {params[0], params[1], params[2], params[3]};
-  mask[i] = inlier(pl, x, thresh) ? 1 : 0;
+  mask[i] = plane_inlier(pl, x, thresh) ? 1 : 0;
 }
 
 // ---- DBSCAN -------------------------------------------------------------------------------------------------------
@@ -285,65 +244,6 @@ __global__ __launch_bounds__(kPBlock) void db_best_kernel(const int32_t* __restr
 }
 
 // ---- plane moments: forward and backward ---------------------------------------------------------------------------
-__device__ __forceinline__ void load_model_params(int kind, int n_terms, const double* w, const double* e, ModelParams& mp) {
-  mp.kind = kind;
-  mp.n_terms = n_terms;
-#pragma unroll
-  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) {
-    mp.w[k] = (k < n_terms && w) ? w[k] : 0.0;
-    mp.e[k] = (k < n_terms && e) ? e[k] : 0.0;
-  }
-}
-
-// d'(d, gamma) and its partial derivatives (the polynomial kinds: model.py:181-199, 243-261; the others: model_depth)
-__device__ __forceinline__ double model_eval(const ModelParams& mp, double d, double g, double* dd, double* dg) {
-  const int kind = mp.kind;
-  if (kind == DC_MODEL_NONE) { *dd = 1.0; *dg = 0.0; return d; }
-  if (kind == DC_MODEL_LINEAR) { *dd = mp.w[0]; *dg = mp.w[1]; return mp.w[0] * d + mp.w[1] * g + mp.w[2]; }
-  if (kind == DC_MODEL_INVCOS || kind == DC_MODEL_SCALED_INVCOS) {
-    const double c = cos(g), s = sin(g);
-    const double t = mp.w[0] * s / (c * c);                  // d/dg (w0 / cos g); |cos g| = cos g on [0, pi/2]
-    if (kind == DC_MODEL_INVCOS) { *dd = 1.0; *dg = -t; return d - mp.w[0] / c; }
-    const double f = 1.0 - mp.w[0] / fabs(c);
-    *dd = f; *dg = -d * t;
-    return d * f;
-  }
-  double b = 0.0, db = 0.0;
-#pragma unroll
-  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k)
-    if (k < mp.n_terms) {
-      b += pow_term(g, mp.e[k]) * mp.w[k];
-      if (mp.e[k] != 0.0) db += mp.w[k] * mp.e[k] * pow_term(g, mp.e[k] - 1.0);
-    }
-  if (kind == DC_MODEL_SCALED_POLYNOMIAL) { *dd = 1.0 - b; *dg = -d * db; return d * (1.0 - b); }
-  *dd = 1.0; *dg = -db;
-  return d - b;
-}
-
-// dd'/dw_k
-__device__ __forceinline__ double model_dw(const ModelParams& mp, int k, double d, double g) {
-  if (mp.kind == DC_MODEL_POLYNOMIAL) return -pow_term(g, mp.e[k]);
-  if (mp.kind == DC_MODEL_SCALED_POLYNOMIAL) return -d * pow_term(g, mp.e[k]);
-  return model_dw_other(mp, k, d, g);
-}
-
-struct PlanePoint {
-  double vp[3], dir[3], d, c, g, dp, ddp_dd, ddp_dg, x[3];
-};
-
-template <typename T>
-__device__ __forceinline__ void plane_point(const T* vps, const T* dirs, const T* depth, int64_t i, const double* n,
-                                            const ModelParams& mp, PlanePoint& q) {
-  load3(vps, i, q.vp);
-  load3(dirs, i, q.dir);
-  q.d = (double)depth[i];
-  q.c = q.dir[0] * n[0] + q.dir[1] * n[1] + q.dir[2] * n[2];
-  const double a = fabs(q.c);
-  q.g = acos(a > 1.0 ? 1.0 : a);
-  q.dp = model_eval(mp, q.d, q.g, &q.ddp_dd, &q.ddp_dg);
-  for (int k = 0; k < 3; ++k) q.x[k] = q.vp[k] + q.dp * q.dir[k];
-}
-
 // per block: [s(3), S(6)] of x - anchor over its chunk of one plane (anchor = the plane's first point)
 template <typename T>
 __global__ __launch_bounds__(kPBlock) void plane_fwd_kernel(const T* __restrict__ vps, const T* __restrict__ dirs, const T* __restrict__ depth,
@@ -364,10 +264,7 @@ __global__ __launch_bounds__(kPBlock) void plane_fwd_kernel(const T* __restrict_
   double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int32_t r = begin + threadIdx.x; r < stop; r += kPBlock) {
     plane_point(vps, dirs, depth, (int64_t)idx[r], n, mp, q);
-    const double dx = q.x[0] - a[0], dy = q.x[1] - a[1], dz = q.x[2] - a[2];
-    v[0] += dx; v[1] += dy; v[2] += dz;
-    v[3] = fma(dx, dx, v[3]); v[4] = fma(dx, dy, v[4]); v[5] = fma(dx, dz, v[5]);
-    v[6] = fma(dy, dy, v[6]); v[7] = fma(dy, dz, v[7]); v[8] = fma(dz, dz, v[8]);
+    plane_moments_add(q.x, a, v);
   }
   block_sum<9>(sh, v);
   if (threadIdx.x == 0)
@@ -391,16 +288,7 @@ __global__ void plane_fwd_finish_kernel(const T* __restrict__ vps, const T* __re
   double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = pblk[p]; b < pblk[p + 1]; ++b)
     for (int k = 0; k < 9; ++k) v[k] += partials[(int64_t)b * 9 + k];
-  const double n = (double)(pptr[p + 1] - pptr[p]);
-  const double s[3] = {v[0], v[1], v[2]};
-  const double f = 1.0 / (n - 1.0);                       // n = 1: inf * 0 = NaN, like torch.cov of one observation
-  const double C[6] = {(v[3] - s[0] * s[0] / n) * f, (v[4] - s[0] * s[1] / n) * f, (v[5] - s[0] * s[2] / n) * f,
-                       (v[6] - s[1] * s[1] / n) * f, (v[7] - s[1] * s[2] / n) * f, (v[8] - s[2] * s[2] / n) * f};
-  double* o = cov + (int64_t)p * 9;
-  o[0] = C[0]; o[1] = C[1]; o[2] = C[2];
-  o[3] = C[1]; o[4] = C[3]; o[5] = C[4];
-  o[6] = C[2]; o[7] = C[4]; o[8] = C[5];
-  for (int k = 0; k < 3; ++k) mean[p * 3 + k] = q.x[k] + s[k] / n;
+  plane_cov_finish(v, (double)(pptr[p + 1] - pptr[p]), q.x, cov + (int64_t)p * 9, mean + p * 3);
 }
 
 // dL/dx = (G + G^T) (x - mean) / (n - 1), chained through x = vp + d'(d, gamma) dir, gamma = arccos |dir . n|
@@ -420,11 +308,8 @@ __global__ __launch_bounds__(kPBlock) void plane_bwd_kernel(const T* __restrict_
   const int32_t begin = blk_begin[blockIdx.x], stop = min(begin + chunk, pptr[p + 1]);
   const double n[3] = {normals[p * 3], normals[p * 3 + 1], normals[p * 3 + 2]};
   const double mu[3] = {mean[p * 3], mean[p * 3 + 1], mean[p * 3 + 2]};
-  const double f = 1.0 / (double)(pptr[p + 1] - pptr[p] - 1);
-  const double* G = gcov + (int64_t)p * 9;
   double M[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) M[r][c] = (G[r * 3 + c] + G[c * 3 + r]) * f;
+  plane_bwd_matrix(gcov + (int64_t)p * 9, (double)(pptr[p + 1] - pptr[p] - 1), M);
   double gw[DC_MAX_MODEL_TERMS];
 #pragma unroll
   for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) gw[k] = 0.0;
@@ -432,19 +317,13 @@ __global__ __launch_bounds__(kPBlock) void plane_bwd_kernel(const T* __restrict_
   for (int32_t r = begin + threadIdx.x; r < stop; r += kPBlock) {
     const int64_t i = (int64_t)idx[r];
     plane_point(vps, dirs, depth, i, n, mp, q);
-    const double dx[3] = {q.x[0] - mu[0], q.x[1] - mu[1], q.x[2] - mu[2]};
-    double gx[3];
-    for (int k = 0; k < 3; ++k) gx[k] = M[k][0] * dx[0] + M[k][1] * dx[1] + M[k][2] * dx[2];
-    const double gdp = gx[0] * q.dir[0] + gx[1] * q.dir[1] + gx[2] * q.dir[2];
-    // d gamma / d dir = -sign(c) / sqrt(1 - c^2) n  (zero where the arccos has no derivative)
-    const double s2 = 1.0 - q.c * q.c;
-    const double sgn = q.c > 0.0 ? 1.0 : (q.c < 0.0 ? -1.0 : 0.0);
-    const double gg = (s2 > 0.0 && mp.kind != DC_MODEL_NONE) ? gdp * q.ddp_dg * (-sgn / sqrt(s2)) : 0.0;
+    double gx[3], gd[3], gdep;
+    const double gdp = plane_bwd_point(q, n, M, mu, mp.kind, gx, gd, &gdep);
     for (int k = 0; k < 3; ++k) {
       g_vps[i * 3 + k] = (T)gx[k];
-      g_dirs[i * 3 + k] = (T)(gx[k] * q.dp + gg * n[k]);
+      g_dirs[i * 3 + k] = (T)gd[k];
     }
-    g_depth[i] = (T)(gdp * q.ddp_dd);
+    g_depth[i] = (T)gdep;
     if (mp.kind != DC_MODEL_NONE) {
 #pragma unroll
       for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k)

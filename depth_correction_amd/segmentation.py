@@ -235,6 +235,9 @@ class _PlaneCSR(object):
         device = torch.device(device)
         sizes = [int(len(i)) for i in indices]
         self.n_planes = len(sizes)
+        if min(sizes, default=1) < 1:
+            # the kernels anchor a plane's moments at its first point: idx[ptr[p]] must exist
+            raise ValueError('plane %d has no indices' % sizes.index(0))
         self.ptr = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), device=device)
         self.idx = (torch.cat([torch.as_tensor(i, device=device) for i in indices]) if sizes else
                     torch.empty((0,), dtype=torch.int64, device=device)).to(torch.int32).contiguous()

@@ -169,3 +169,184 @@ def host_ray_test_pairs(lib, tri, o, d, t_min, cull):
     lib.dc_host_ray_test_pairs(tri.ctypes.data, o.ctypes.data, d.ctypes.data, t_min.ctypes.data, n, 1 if cull else 0, hit.ctypes.data,
                                t.ctypes.data, u.ctypes.data, v.ctypes.data)
     return hit.astype(bool), t, u, v
+
+
+# ---- the plane neighbourhoods' host build (dc_planemath.h; test_planes_host.py, test_gpu_planes_edge.py) ----------------------------
+def planes_host_lib():
+    """hostcheck_lib() with the plane exports (rebuilt when the library at hand predates them)."""
+    import ctypes
+    lib = hostcheck_lib()
+    if not hasattr(lib, 'dc_host_smallest_eigvec_jacobi'):
+        import __graft_entry__ as ge
+        ge.build()
+        lib = hostcheck_lib()
+    vp, i64, ci, f64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
+    lib.dc_host_plane_from_points.argtypes = [vp, ci, vp]
+    lib.dc_host_plane_inliers.restype = None
+    lib.dc_host_plane_inliers.argtypes = [vp, vp, i64, f64, vp]
+    lib.dc_host_ransac_round.argtypes = [vp, ci, vp, i64, i64, i64, ci, f64, vp, vp, vp, vp, vp]
+    lib.dc_host_ransac_refit_partial_count.argtypes = [i64]
+    lib.dc_host_ransac_refit.argtypes = [vp, ci, vp, i64, vp, vp, vp, f64, vp, vp, vp]
+    lib.dc_host_smallest_eigvec_jacobi.restype = None
+    lib.dc_host_smallest_eigvec_jacobi.argtypes = [vp, vp]
+    lib.dc_host_plane_refit.restype = None
+    lib.dc_host_plane_refit.argtypes = [vp, vp, vp]
+    lib.dc_host_dbscan.argtypes = [vp, i64, ci, ci, vp, vp]
+    lib.dc_host_plane_model.restype = None
+    lib.dc_host_plane_model.argtypes = [ci, ci, vp, vp, f64, f64, vp]
+    lib.dc_host_plane_moments_fwd.argtypes = [vp, vp, vp, ci, vp, i64, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.dc_host_plane_moments_bwd.argtypes = [vp, vp, vp, ci, vp, i64, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    return lib
+
+
+def _cloud_arg(x):
+    x = np.ascontiguousarray(x)
+    assert x.dtype in (np.float32, np.float64)
+    return x, 0 if x.dtype == np.float32 else 1
+
+
+def _signed64(v):
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def host_plane_from_points(lib, p, distinct=True):
+    """(valid, pl f64 [4]) of the plane through the three points p [3,3]."""
+    p = _c64(p, 9)
+    pl = np.empty(4)
+    ok = lib.dc_host_plane_from_points(p.ctypes.data, 1 if distinct else 0, pl.ctypes.data)
+    return bool(ok), pl
+
+
+def host_plane_inliers(lib, pl, x, thresh):
+    pl, x = _c64(pl, 4), _c64(x, 3)
+    out = np.empty(x.shape[0], dtype=np.uint8)
+    lib.dc_host_plane_inliers(pl.ctypes.data, x.ctypes.data, x.shape[0], float(thresh), out.ctypes.data)
+    return out.astype(bool)
+
+
+def host_ransac_round(lib, x, rem, seed, m, H, thresh):
+    """The brute-force oracle of one RANSAC round -> dict(hyp [H,4], anchor [H,3], valid [H], counts [H], best [2])."""
+    x, dt = _cloud_arg(x)
+    rem = np.ascontiguousarray(rem, dtype=np.int32)
+    o = dict(hyp=np.empty((H, 4)), anchor=np.empty((H, 3)), valid=np.empty(H, np.int32), counts=np.empty(H, np.int32),
+             best=np.empty(2, np.int32))
+    rc = lib.dc_host_ransac_round(x.ctypes.data, dt, rem.ctypes.data, len(rem), _signed64(seed), int(m), int(H), float(thresh),
+                                  o['hyp'].ctypes.data, o['anchor'].ctypes.data, o['valid'].ctypes.data, o['counts'].ctypes.data,
+                                  o['best'].ctypes.data)
+    assert rc == 0
+    return o
+
+
+def host_ransac_refit(lib, x, rem, rnd, thresh):
+    """The refit oracle for the round `rnd` (a dict of host_ransac_round, or the device's buffers as numpy arrays): the moments in the
+    kernel's block order -> (totals [10], params [4], mask bool [n_rem])."""
+    x, dt = _cloud_arg(x)
+    rem = np.ascontiguousarray(rem, dtype=np.int32)
+    hyp, anchor = _c64(rnd['hyp'], 4), _c64(rnd['anchor'], 3)
+    best = np.ascontiguousarray(rnd['best'], dtype=np.int32)
+    tot, params, mask = np.empty(10), np.empty(4), np.empty(len(rem), np.uint8)
+    rc = lib.dc_host_ransac_refit(x.ctypes.data, dt, rem.ctypes.data, len(rem), hyp.ctypes.data, anchor.ctypes.data, best.ctypes.data,
+                                  float(thresh), tot.ctypes.data, params.ctypes.data, mask.ctypes.data)
+    assert rc == 0
+    return tot, params, mask.astype(bool)
+
+
+def host_smallest_eigvec(lib, cov6):
+    """The refit's eigenvector step on C (xx xy xz yy yz zz): the vector before the sign rule and the normalisation."""
+    c, out = _c64(cov6, 6), np.empty(3)
+    lib.dc_host_smallest_eigvec_jacobi(c.ctypes.data, out.ctypes.data)
+    return out
+
+
+def host_plane_refit(lib, moments, anchor):
+    v, a, out = _c64(moments, 10), _c64(anchor, 3), np.empty(4)
+    lib.dc_host_plane_refit(v.ctypes.data, a.ctypes.data, out.ctypes.data)
+    return out
+
+
+def host_dbscan(lib, table, min_points):
+    """Sequential DBSCAN on the padded neighbour table int32 [m,K] -> (labels [m], best label, its size)."""
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    m, k = table.shape
+    labels, best = np.empty(m, np.int32), np.empty(2, np.int32)
+    assert lib.dc_host_dbscan(table.ctypes.data, m, k, int(min_points), labels.ctypes.data, best.ctypes.data) == 0
+    return labels, int(best[0]), int(best[1])
+
+
+def host_plane_model(lib, code, w, e, d, g):
+    """model_eval / model_dw -> (d', dd'/dd, dd'/dg, dd'/dw [P])."""
+    w, e = _c64(w, 1).reshape(-1), _c64(e, 1).reshape(-1)
+    out = np.zeros(3 + len(w))
+    lib.dc_host_plane_model(int(code), len(w), w.ctypes.data if len(w) else None, e.ctypes.data if len(e) else None, float(d), float(g),
+                            out.ctypes.data)
+    return out[0], out[1], out[2], out[3:]
+
+
+def _model_arg(w, e):
+    if w is None:
+        return 0, None, None, None, None
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+    e = np.zeros_like(w) if e is None else np.ascontiguousarray(np.asarray(e, dtype=np.float64).reshape(-1))
+    return len(w), w, e, w.ctypes.data, e.ctypes.data
+
+
+def host_plane_moments(lib, vps, dirs, depth, idx, normal, code, w=None, e=None, gcov=None):
+    """One plane through the host build: dict(cov [3,3], mean [3], x [n,3]) and, with gcov [3,3], g_vps / g_dirs [n,3], g_depth [n],
+    g_w [P] (float64, before the rounding to the cloud's dtype)."""
+    vps, dt = _cloud_arg(vps)
+    dirs, depth = np.ascontiguousarray(dirs, dtype=vps.dtype), np.ascontiguousarray(depth, dtype=vps.dtype).reshape(-1)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    n = len(idx)
+    nrm = _c64(normal, 3)
+    nt, wv, ev, wp, ep = _model_arg(w, e)
+    cov, mean, x = np.empty((3, 3)), np.empty(3), np.empty((n, 3))
+    rc = lib.dc_host_plane_moments_fwd(vps.ctypes.data, dirs.ctypes.data, depth.ctypes.data, dt, idx.ctypes.data, n, nrm.ctypes.data,
+                                       int(code), nt, wp, ep, cov.ctypes.data, mean.ctypes.data, x.ctypes.data)
+    assert rc == 0
+    out = dict(cov=cov, mean=mean, x=x)
+    if gcov is not None:
+        g = _c64(gcov, 9)
+        gv, gd, gdep, gw = np.empty((n, 3)), np.empty((n, 3)), np.empty(n), np.zeros(max(nt, 1))
+        rc = lib.dc_host_plane_moments_bwd(vps.ctypes.data, dirs.ctypes.data, depth.ctypes.data, dt, idx.ctypes.data, n, nrm.ctypes.data,
+                                           int(code), nt, wp, ep, mean.ctypes.data, g.ctypes.data, gv.ctypes.data, gd.ctypes.data,
+                                           gdep.ctypes.data, gw.ctypes.data)
+        assert rc == 0
+        out.update(g_vps=gv, g_dirs=gd, g_depth=gdep, g_w=gw[:nt])
+    return out
+
+
+def host_fit_planes(lib, x, distance_threshold, min_support=3, max_iterations=1000, max_models=10, eps=None, seed=0, min_points=10):
+    """The loop of segmentation.fit_planes with every round's RANSAC and refit from the header oracle (the kernels' own arithmetic,
+    bit for bit) and the clustering from planes_reference.dbscan -> (params list of f64 [4], indices list of int64 arrays)."""
+    import planes_reference as R
+    x = np.ascontiguousarray(x)
+    rem = np.arange(len(x), dtype=np.int32)
+    params, indices = [], []
+    m = 0
+    while len(rem) >= 3:
+        rnd = host_ransac_round(lib, x, rem, seed, m, max_iterations, distance_threshold)
+        m += 1
+        if rnd['best'][1] < min_support:
+            break
+        _, plane, mask = host_ransac_refit(lib, x, rem, rnd, distance_threshold)
+        support = rem[mask]
+        if len(support) < min_support:
+            break
+        keep = support
+        if eps:
+            labels, lbl, size = R.dbscan(x[support].astype(np.float64), eps, min_points)
+            if size < min_support:
+                rem = rem[~mask]
+                if len(rem) < min_support:
+                    break
+                continue
+            keep = support[labels == lbl]
+        params.append(plane)
+        indices.append(keep.astype(np.int64))
+        if max_models is not None and len(params) == max_models:
+            break
+        rem = rem[~np.isin(rem, keep)]
+        if len(rem) < min_support:
+            break
+    return params, indices

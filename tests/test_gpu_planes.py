@@ -50,6 +50,7 @@ def test_ransac_round_matches_numpy(dtype):
         r = np.abs(xd @ pl[0] + pl[1])
         want[h] = int((r <= thr).sum())
         border = int((np.abs(r - thr) < 1e-12).sum())
+        assert border <= 1e-3 * n, (h, border)                    # at most 0.1 % of the points may lie on the border at all
         assert abs(int(counts[h]) - want[h]) <= border, (h, counts[h], want[h])
     assert h_gpu == int(np.argmax(want)) and c_gpu == want.max()
     # refit: least-squares plane of the inliers, largest component positive, inliers selected again
@@ -65,7 +66,7 @@ def test_ransac_round_matches_numpy(dtype):
     r = np.abs(xd @ ref[:3] + ref[3])
     sel = mask.cpu().numpy().astype(bool)
     diff = sel != (r <= thr)
-    assert not diff.any() or np.all(np.abs(r[diff] - thr) < 1e-12)
+    assert diff.sum() <= 1e-3 * n and (not diff.any() or np.all(np.abs(r[diff] - thr) < 1e-12))
 
 
 def test_dbscan_matches_ckdtree():
