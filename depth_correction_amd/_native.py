@@ -173,6 +173,8 @@ _SIGNATURES = {
     'dc_icp_accumulate': (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
     'dc_icp_finish': (_i32, [_vp, _i32, _i64, _f64, _f64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp]),
     'dc_map_select': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
+    'dc_dyn_directions': (_i32, [_vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp]),
+    'dc_dyn_update': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
 }
 
 

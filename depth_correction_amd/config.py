@@ -216,6 +216,18 @@ class Config(object):
         self.slam_min_overlap = 0.9             # map_update_overlap
         self.slam_min_dist_new_point = 0.1      # min_dist_new_point
         self.slam_sensor_max_range = 25.0       # sensor_max_range
+        # dynamic points in the map (launch/slam.launch compute_prob_dynamic and its parameters; DESIGN "Dynamic points in the map").
+        # slam.launch runs with compute_prob_dynamic on; the three switches are off here so that existing results and timings stand.
+        self.slam_compute_prob_dynamic = False  # update the map points' probabilities of being dynamic before every map update
+        self.slam_dynamic_every_scan = False    # ... and for registered scans whose overlap skips the map update (run_slam)
+        self.slam_cut_dynamic = False           # keep points with P >= threshold out of the ICP's reference cloud
+        self.slam_prior_dynamic = 0.6           # prior_dynamic
+        self.slam_threshold_dynamic = 0.9       # threshold_dynamic
+        self.slam_beam_half_angle = 0.01        # beam_half_angle
+        self.slam_epsilon_a = 0.01              # epsilon_a
+        self.slam_epsilon_d = 0.01              # epsilon_d
+        self.slam_alpha = 0.8                   # alpha
+        self.slam_beta = 0.99                   # beta
         # map accuracy against the ground-truth mesh (eval.eval_map, DESIGN "Map accuracy"; not in the reference's Config):
         # eval_map appends to map_eval_csv; map_eval_poses 'dataset' (the poses the dataset yields) or 'slam' (the poses run_slam
         # estimates); the quantile of trimmed_mean; samples of the mesh for completeness_mean (0 = not computed)

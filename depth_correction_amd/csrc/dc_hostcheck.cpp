@@ -10,6 +10,7 @@
 #include "dc_beammath.h"
 #include "dc_raymath.h"
 #include "dc_planemath.h"
+#include "dc_dynmath.h"
 
 extern "C" {
 
@@ -460,6 +461,31 @@ int dc_host_plane_moments_bwd(const void* vps, const void* dirs, const void* dep
       for (int k = 0; k < n_terms; ++k) g_w[k] += gdp * dc::model_dw(mp, k, q.d, q.g);
   }
   return 0;
+}
+
+// ---- dynamic-point probabilities (dc_dynmath.h) --------------------------------------------------------------------------------------
+// dc_dyn_directions on host arrays: the same loop over dyn_direction; pose NULL is the reading form
+void dc_host_dyn_directions(const double* points, int64_t n, const double* pose, double max_range, double* dirs_out, double* depth_out,
+                            uint8_t* valid_out) {
+  for (int64_t i = 0; i < n; ++i) {
+    double d[3], x[3];
+    valid_out[i] = dc::dyn_direction(pose, points + 3 * i, max_range, d, x, depth_out + i, dirs_out + 3 * i) ? 1 : 0;
+  }
+}
+
+// dc_dyn_update on host arrays: the same argument checks and the same per-entry function.  0, or DC_ERR_ARG.
+int dc_host_dyn_update(const double* map_points, const double* map_normals, int64_t n_map, const double* pose, const double* reading, int64_t m,
+                       const int32_t* rows, const int32_t* match_idx, const double* match_chord, int64_t n_rows, double chord_max,
+                       double epsilon_a, double epsilon_d, double alpha, double beta, double threshold, double max_range, double* prob,
+                       uint8_t* seen_out) {
+  const dc::DynParams prm{chord_max, epsilon_a, epsilon_d, alpha, beta, threshold, max_range};
+  if (n_rows < 0 || n_map < 0 || m < 0 || !dc::dyn_params_ok(prm)) return DC_ERR_ARG;
+  if (n_rows == 0) return DC_OK;
+  if (!map_points || !map_normals || !pose || !reading || !rows || !match_idx || !match_chord || !prob) return DC_ERR_ARG;
+  for (int64_t i = 0; i < n_rows; ++i)
+    dc::dyn_update_entry(prm, map_points, map_normals, n_map, pose, reading, m, (int64_t)rows[i], (int64_t)match_idx[i], match_chord[i], prob,
+                         seen_out);
+  return DC_OK;
 }
 
 }  // extern "C"

@@ -318,6 +318,8 @@ def eval_slam(cfg: Config, test_datasets=None, model=None):
         r_angle, t_norm, rel_angle, rel_offset = res['errors'] = slam_errors(res['slam'], res['gt'], res['path_lengths'])
         print('Average error: rot. %.6f deg. (%.3f deg/m), transl. %.6f m (%.3f %%).'
               % (np.degrees(r_angle), np.degrees(rel_angle), t_norm, 100. * rel_offset))
+        if cfg.slam_compute_prob_dynamic and res['info']:
+            print('Dynamic map points: %d of %d.' % (res['info'][-1]['dynamic'], res['info'][-1]['map_size']))
         append(cfg.slam_eval_csv, '%s %.9f %.9f %.9f %.9f\n' % (name, r_angle, t_norm, rel_angle, rel_offset))
         if cfg.slam_poses_csv:
             if os.path.exists(cfg.slam_poses_csv):

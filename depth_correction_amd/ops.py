@@ -18,6 +18,7 @@ __all__ = [
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
+    'dyn_directions', 'dyn_update',
 ]
 
 
@@ -1468,3 +1469,52 @@ def map_select(reading, normals, depth, pose, dist1, min_dist, max_range):
     check(lib().dc_map_select(ptr(reading), ptr(normals), ptr(depth), m, ptr(pose), ptr(dist1), float(min_dist), float(max_range),
                               ptr(mask), ptr(pts), ptr(nrm), stream_ptr()), 'dc_map_select')
     return mask.view(torch.bool), pts, nrm
+
+
+# ------------------------------------------------------------------------------------------------
+# Dynamic points in the map (csrc/dc_dynamic.hip, slam.IcpMapper.update_dynamic; DESIGN "Dynamic points in the map")
+# ------------------------------------------------------------------------------------------------
+@on_device
+def dyn_directions(points, pose=None, max_range=0.0):
+    """(dirs f64 [N,3], depth f64 [N], valid bool [N]) of points f64 [N,3] as the sensor at pose f64 device [4,4] sees them; pose None:
+    the points are in the sensor frame.  valid = depth finite, > 0 and <= max_range (<= 0 or inf: no bound); invalid rows have a zero
+    direction (dc_dyn_directions)."""
+    need(points, (None, 3), dtype=torch.float64, name='points')
+    dev = points.device
+    if pose is not None:
+        need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    max_range = float(max_range)
+    if max_range != max_range:
+        raise ValueError('max_range must not be NaN')
+    n = points.shape[0]
+    dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    depth = torch.empty((n,), dtype=torch.float64, device=dev)
+    valid = torch.empty((n,), dtype=torch.uint8, device=dev)
+    check(lib().dc_dyn_directions(ptr(points), n, ptr(pose), max_range, ptr(dirs), ptr(depth), ptr(valid), stream_ptr()), 'dc_dyn_directions')
+    return dirs, depth, valid.view(torch.bool)
+
+
+@on_device
+def dyn_update(map_points, map_normals, pose, reading, rows, match_idx, match_chord, chord_max, epsilon_a, epsilon_d, alpha, beta, threshold,
+               max_range, prob, seen=None):
+    """Visibility test and Bayesian update of prob f64 [N] (in place) for the map rows ``rows`` (int32 [R], strictly ascending --
+    the caller's contract: a thread owns its row) matched to the reading rows ``match_idx`` (int32 [R], rows of reading f64 [M,3]) at
+    the chords ``match_chord`` (f64 [R]); ``seen`` (uint8 [N], zeroed by the caller, optional) gets 1 occluded / 2 updated
+    (dc_dyn_update)."""
+    need(map_points, (None, 3), dtype=torch.float64, name='map_points')
+    dev = map_points.device
+    n = map_points.shape[0]
+    need(map_normals, (n, 3), dtype=torch.float64, name='map_normals', device=dev)
+    need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    need(reading, (None, 3), dtype=torch.float64, name='reading', device=dev)
+    need(rows, (None,), dtype=torch.int32, name='rows', device=dev)
+    r = rows.shape[0]
+    need(match_idx, (r,), dtype=torch.int32, name='match_idx', device=dev)
+    need(match_chord, (r,), dtype=torch.float64, name='match_chord', device=dev)
+    need(prob, (n,), dtype=torch.float64, name='prob', device=dev)
+    if seen is not None:
+        need(seen, (n,), dtype=torch.uint8, name='seen', device=dev)
+    check(lib().dc_dyn_update(ptr(map_points), ptr(map_normals), n, ptr(pose), ptr(reading), reading.shape[0], ptr(rows), ptr(match_idx),
+                              ptr(match_chord), r, float(chord_max), float(epsilon_a), float(epsilon_d), float(alpha), float(beta),
+                              float(threshold), float(max_range), ptr(prob), ptr(seen), stream_ptr()), 'dc_dyn_update')
+    return prob

@@ -21,8 +21,8 @@ from numpy.lib.recfunctions import unstructured_to_structured
 
 from .dataset import TransformingDataset
 
-__all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'DepthBiasDataset', 'mesh_dir',
-           'BeamModel']
+__all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'MovingObjectDataset', 'DepthBiasDataset',
+           'mesh_dir', 'BeamModel']
 
 Z_CLIP = 1e-3          # pytorch3d RasterizationSettings(z_clip_value=1e-3) of the reference
 
@@ -344,6 +344,79 @@ class RenderedMeshDataset(object):
 
     def cloud_pose(self, id):
         return self.poses[id]
+
+
+class MovingObjectDataset(object):
+    """Lidar scans of a scene in which objects move: ``static_mesh`` (mesh.TriangleMesh) merged, scan by scan, with every object of
+    ``objects`` -- a list of (TriangleMesh, object_poses [N,4,4]), world from object per scan -- and rendered from ``poses`` [N,4,4]
+    (world from sensor) with render_lidar_clouds, one BVH per scan.  Yields (cloud of RenderedMeshDataset.cloud_dtype, pose) like
+    RenderedMeshDataset; ``get_mesh()`` is the static mesh, the ground truth that does not move.  Nothing is cached."""
+
+    dataset_name = 'moving_object'
+    cloud_dtype = _DT
+
+    def __init__(self, static_mesh, objects, poses, size=(64, 512), fov=(45., 360.), num_segments=16, device='cuda', beam=None):
+        from .mesh import TriangleMesh
+        _check_pattern(tuple(fov), tuple(size), num_segments)
+        if beam is not None and not isinstance(beam, BeamModel):
+            raise TypeError('beam must be a BeamModel or None, got %s' % type(beam).__name__)
+        if not isinstance(static_mesh, TriangleMesh):
+            raise TypeError('static_mesh must be a TriangleMesh, got %s' % type(static_mesh).__name__)
+        self.poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        self.objects = []
+        for obj, obj_poses in objects:
+            if not isinstance(obj, TriangleMesh):
+                raise TypeError('every object must be a (TriangleMesh, poses) pair, got %s' % type(obj).__name__)
+            obj_poses = np.asarray(obj_poses, dtype=np.float64).reshape(-1, 4, 4)
+            if obj_poses.shape[0] != self.poses.shape[0]:
+                raise ValueError('an object has %d poses, the dataset %d scans' % (obj_poses.shape[0], self.poses.shape[0]))
+            self.objects.append((obj, obj_poses))
+        self.static_mesh = static_mesh
+        self.size, self.fov, self.num_segments, self.device, self.beam = tuple(size), tuple(fov), num_segments, device, beam
+        self.ids = list(range(len(self.poses)))
+
+    def get_mesh(self):
+        return self.static_mesh
+
+    def scene_mesh(self, id):
+        """The static mesh and every object at its pose of scan ``id``, as one mesh (mesh._merge: identical vertices shared)."""
+        from .mesh import TriangleMesh, _merge
+        parts = [(np.asarray(self.static_mesh.vertices, dtype=np.float64), np.asarray(self.static_mesh.faces))]
+        for obj, obj_poses in self.objects:
+            T = obj_poses[id]
+            v = np.asarray(obj.vertices, dtype=np.float64)
+            parts.append((np.matmul(v, T[:3, :3].T) + T[:3, 3], np.asarray(obj.faces)))
+        return TriangleMesh(*_merge(parts))
+
+    def local_cloud(self, id):
+        return render_lidar_clouds(self.scene_mesh(id), self.poses[id][None], fov=self.fov, size=self.size, num_segments=self.num_segments,
+                                   device=self.device, beam=self.beam)[0]
+
+    def cloud_pose(self, id):
+        return self.poses[id]
+
+    def __getitem__(self, i):
+        if isinstance(i, (int, np.integer)):
+            id = self.ids[i]
+            return self.local_cloud(id), self.cloud_pose(id)
+        ds = copy(self)
+        if isinstance(i, (list, tuple)):
+            ds.ids = [self.ids[j] for j in i]
+        elif isinstance(i, slice):
+            ds.ids = self.ids[i]
+        else:
+            raise ValueError('Invalid index: %s.' % i)
+        return ds
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self[i]
+
+    def __str__(self):
+        return MovingObjectDataset.dataset_name
 
 
 class DepthBiasDataset(TransformingDataset):

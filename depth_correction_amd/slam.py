@@ -4,7 +4,8 @@ ICP mapper configured like the reference's norlab_icp_mapper (config/slam/icp.ya
 The mapper is a restatement of that configuration, not libpointmatcher; DESIGN "SLAM evaluation" states the algorithm and its
 deviations.  Its device state is the map (points and the normals of the scans they came from), the map's k-NN grid and one
 registration's state; an ICP iteration runs on the device without the host (csrc/dc_slam.hip), which reads one status word every
-``status_every`` iterations.
+``status_every`` iterations.  With cfg.slam_compute_prob_dynamic every map point also carries the probability that it belongs to
+something that moved (csrc/dc_dynamic.hip, DESIGN "Dynamic points in the map").
 """
 from __future__ import annotations
 
@@ -16,8 +17,8 @@ from . import ops
 from .config import Config, SLAM
 from .utils import delta_transform, rotation_angle, translation_norm
 
-__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'mapper_input', 'odometry_cov', 'odometry_poses', 'path_lengths',
-           'run_slam', 'slam_errors']
+__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'dynamic_params', 'mapper_input', 'odometry_cov', 'odometry_poses',
+           'path_lengths', 'run_slam', 'slam_errors']
 
 # launches of one ICP iteration: dc_knn_grid_query 3 (moved queries, the 16-lanes-per-query search, the tail search), dc_quantile 18
 # (a state memset, 8 x histogram + pick, next value, threshold), dc_icp_accumulate 1, dc_icp_finish 1
@@ -101,6 +102,31 @@ def mapper_input(cloud, model, cfg: Config):
     return DepthCloud.from_structured_array(cloud, dtype=np.float64, device=cfg.device)
 
 
+def dynamic_params(cfg: Config):
+    """The parameters of the dynamic-point rule from cfg, checked (ValueError): dict(prior, threshold, beam_half_angle, chord_max,
+    epsilon_a, epsilon_d, alpha, beta, max_range) with chord_max = 2 sin(beam_half_angle), the chord of twice the half angle."""
+    import math
+    p = dict(prior=float(cfg.slam_prior_dynamic), threshold=float(cfg.slam_threshold_dynamic), beam_half_angle=float(cfg.slam_beam_half_angle),
+             epsilon_a=float(cfg.slam_epsilon_a), epsilon_d=float(cfg.slam_epsilon_d), alpha=float(cfg.slam_alpha), beta=float(cfg.slam_beta),
+             max_range=float(cfg.slam_sensor_max_range))
+    if not 0.0 < p['beam_half_angle'] < math.pi / 2:
+        raise ValueError('slam_beam_half_angle must lie in (0, pi/2), got %r' % p['beam_half_angle'])
+    for name in ('epsilon_a', 'epsilon_d'):
+        if not (p[name] >= 0.0 and math.isfinite(p[name])):
+            raise ValueError('slam_%s must be finite and >= 0, got %r' % (name, p[name]))
+    for name in ('alpha', 'beta'):
+        if not 0.0 < p[name] < 1.0:
+            raise ValueError('slam_%s must lie in (0, 1), got %r' % (name, p[name]))
+    if not 0.0 < p['threshold'] <= 1.0:
+        raise ValueError('slam_threshold_dynamic must lie in (0, 1], got %r' % p['threshold'])
+    if not 0.0 <= p['prior'] <= 1.0:
+        raise ValueError('slam_prior_dynamic must lie in [0, 1], got %r' % p['prior'])
+    if math.isnan(p['max_range']):
+        raise ValueError('slam_sensor_max_range must not be NaN')
+    p['chord_max'] = 2.0 * math.sin(p['beam_half_angle'])
+    return p
+
+
 class MapperScan(object):
     """A reading as the ICP uses it: points fp64 [M,3] in the sensor frame, their normals [M,3] (k nearest neighbours inside the scan,
     oriented toward the sensor: input_filters.yaml) and depths [M]."""
@@ -117,7 +143,9 @@ class IcpMapper(object):
 
     ``register(scan, prior)`` -> (pose, info): the registered pose (the prior when the registration fails: info['ok'] is False) and
     info (status, iterations, overlap, pairs, sse); ``update(scan, pose, overlap=None)`` adds the reading points that are new to the
-    map; ``map_points()`` -> (points, normals) of the map."""
+    map; ``map_points()`` -> (points, normals) of the map.  ``update_dynamic(scan, pose)`` updates the map points' probabilities of
+    being dynamic (``map_dynamic()``) from a registered scan; ``update`` runs it first when cfg.slam_compute_prob_dynamic is set, and
+    with cfg.slam_cut_dynamic the registration matches against the points below cfg.slam_threshold_dynamic only."""
 
     def __init__(self, cfg: Config, device=None, status_every=4):
         if not (1 <= int(cfg.icp_smooth_length) <= nv.DC_ICP_MAX_SMOOTH):
@@ -131,6 +159,14 @@ class IcpMapper(object):
         self.n_map = 0
         self._pts = torch.empty((0, 3), dtype=torch.float64, device=self.device)
         self._nrm = torch.empty((0, 3), dtype=torch.float64, device=self.device)
+        self._prob = torch.empty((0,), dtype=torch.float64, device=self.device)
+        self.dyn = dynamic_params(cfg) if (cfg.slam_compute_prob_dynamic or cfg.slam_cut_dynamic) else None
+        self.n_dynamic = 0             # map points with P >= threshold (a host count, refreshed by update_dynamic and update)
+        self.last_dyn = None           # what the last update() got from update_dynamic, None when it did not run
+        self._dyn_ws = None            # workspace of the reading directions' grid
+        self._eye = None
+        self._version = 0              # counts the changes of the map and of its probabilities
+        self._ref = None               # the reference cloud of slam_cut_dynamic: dict(version, grid, points, normals, rows)
         self.grid = None
         self.grid_builds = 0
         self.state = torch.zeros((nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, device=self.device)
@@ -182,7 +218,9 @@ class IcpMapper(object):
             return prior.copy(), self._info('empty')
         if self.n_map == 0:
             return prior.copy(), self._info('init')
-        self._ensure_grid(m)
+        grid, map_pts, map_nrm, _ = self.reference(m)
+        if grid is None:
+            return prior.copy(), self._info('too_few_pairs')
         dev, k = self.device, self.knn
         prior_d = torch.as_tensor(prior, device=dev)
         idx = torch.empty((m, k), dtype=torch.int32, device=dev)
@@ -190,14 +228,13 @@ class IcpMapper(object):
         thr = torch.empty((1,), dtype=torch.float64, device=dev)
         partials = torch.empty((ops.icp_blocks(m), nv.DC_ICP_PARTIALS), dtype=torch.float64, device=dev)
         pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
-        map_pts, map_nrm = self._pts[:self.n_map], self._nrm[:self.n_map]
         cos_min = float(np.cos(cfg.icp_max_normal_angle))
         ops.icp_init(prior_d, self.state, self.status)
         done = 0
         code = 0
         while done < cfg.icp_max_iters:
             for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
-                self.iteration(scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min)
+                self.iteration(scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, grid=grid)
                 done += 1
             st = self.status.cpu()
             self.host_reads += 1
@@ -212,10 +249,12 @@ class IcpMapper(object):
             return prior.copy(), info
         return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
 
-    def iteration(self, scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, kept=None):
-        """One ICP iteration, queued on the stream: match, trimmed threshold, pairs and partials, solve and update."""
+    def iteration(self, scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, kept=None, grid=None):
+        """One ICP iteration, queued on the stream: match, trimmed threshold, pairs and partials, solve and update.  ``grid`` is the
+        grid of ``map_pts`` (the whole map's unless given: reference())."""
         cfg = self.cfg
-        ops.knn_grid_query(self.grid, scan.points, pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx, dist=dist)
+        ops.knn_grid_query(self.grid if grid is None else grid, scan.points, pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx,
+                           dist=dist)
         ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
         ops.icp_accumulate(scan.points, scan.normals, map_pts, map_nrm, idx, dist, thr, cos_min, self.state, self.status, partials,
                            kept=kept)
@@ -231,6 +270,79 @@ class IcpMapper(object):
                                        ws=self.grid.ws if self.grid is not None else None)
         self.grid_builds += 1
 
+    def reference(self, m):
+        """(grid, points, normals, rows) the registration of an m-point scan matches against: the whole map (rows None), or with
+        cfg.slam_cut_dynamic the map rows ``rows`` (int32, ascending) whose P < threshold, compacted, with a grid of their own (the
+        effect of a CutAtDescriptorThreshold filter on the reference cloud), rebuilt when the map or a probability changed.  grid is
+        None when no static point is left."""
+        n = self.n_map
+        if not self.cfg.slam_cut_dynamic or self.n_dynamic == 0:
+            self._ensure_grid(m)
+            return self.grid, self._pts[:n], self._nrm[:n], None
+        ref = self._ref
+        if ref is None or ref['version'] != self._version or (ref['grid'] is not None and ref['grid'].n_query_max < m):
+            (pts, nrm), rows = ops.compact_rows(self._prob[:n] < self.dyn['threshold'], [self._pts[:n], self._nrm[:n]], want_index=True)
+            old = ref['grid'] if ref is not None else None
+            grid = None
+            if pts.shape[0] > 0:
+                grid = ops.knn_grid_build(pts, max(m, old.n_query_max if old is not None else 0), self.knn,
+                                          ws=old.ws if old is not None else None)
+                self.grid_builds += 1
+            ref = self._ref = dict(version=self._version, grid=grid, points=pts, normals=nrm, rows=rows)
+        return ref['grid'], ref['points'], ref['normals'], ref['rows']
+
+    # ---- dynamic points -------------------------------------------------------------------------------------------------------
+    def update_dynamic(self, scan, pose, timer=None):
+        """Update the map points' probabilities of being dynamic from ``scan`` registered at ``pose`` (DESIGN "Dynamic points in the
+        map"): directions of the map points in range as the sensor sees them, each one's nearest reading direction within the
+        beam (the grid k-NN over the reading's unit vectors), then the visibility test and the Bayesian update of the matched rows.
+        Returns dict(in_range, matched, occluded, updated, dynamic): map points in range, matched to a beam, of those behind the
+        beam's return / updated, and the map points with P >= threshold afterwards.  ``timer`` (optional) is called with a stage
+        name after every stage (tools/dynamic_bench.py)."""
+        prm = self.dyn if self.dyn is not None else dynamic_params(self.cfg)
+        self.dyn = prm
+        tick = timer if timer is not None else (lambda stage: None)
+        scan = self.prepare(scan)
+        n, m = self.n_map, len(scan)
+        out = dict(in_range=0, matched=0, occluded=0, updated=0, dynamic=self.n_dynamic)
+        if n == 0 or m == 0:
+            return out
+        dev = self.device
+        pose_d = torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(4, 4), device=dev)
+        map_pts, map_nrm, prob = self._pts[:n], self._nrm[:n], self._prob[:n]
+        u, _, u_ok = ops.dyn_directions(map_pts, pose_d, prm['max_range'])
+        v, _, v_ok = ops.dyn_directions(scan.points, None, 0.0)
+        tick('directions')
+        (u,), rows = ops.compact_rows(u_ok, [u], want_index=True)
+        (v,), vrows = ops.compact_rows(v_ok, [v], want_index=True)
+        tick('compaction')
+        out['in_range'] = int(u.shape[0])
+        if u.shape[0] == 0 or v.shape[0] == 0:
+            return out
+        grid = ops.knn_grid_build(v, u.shape[0], 1, ws=self._dyn_ws)
+        self._dyn_ws = grid.ws
+        tick('grid_build')
+        if self._eye is None:
+            self._eye = torch.eye(4, dtype=torch.float64, device=dev)
+        chord, idx = ops.knn_grid_query(grid, u, self._eye, 1, r=prm['chord_max'])
+        chord, idx = chord.reshape(-1), idx.reshape(-1)
+        match = torch.where(idx >= 0, vrows[idx.clamp(min=0).long()], idx)          # compacted reading rows -> rows of the scan
+        tick('query')
+        seen = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        ops.dyn_update(map_pts, map_nrm, pose_d, scan.points, rows, match, chord, prm['chord_max'], prm['epsilon_a'], prm['epsilon_d'],
+                       prm['alpha'], prm['beta'], prm['threshold'], prm['max_range'], prob, seen)
+        counts = torch.stack([(idx >= 0).sum(), (seen == 1).sum(), (seen == 2).sum(), (prob >= prm['threshold']).sum()]).cpu()
+        tick('update')
+        out['matched'], out['occluded'], out['updated'], out['dynamic'] = (int(c) for c in counts)
+        self.n_dynamic = out['dynamic']
+        if out['updated'] > 0:
+            self._version += 1
+        return out
+
+    def map_dynamic(self):
+        """P fp64 [N]: every map point's probability of being dynamic (the prior where nothing was computed)."""
+        return self._prob[:self.n_map]
+
     def update(self, scan, pose, overlap=None):
         """Add the reading points of ``scan`` at ``pose`` whose nearest map point is farther than cfg.slam_min_dist_new_point and whose
         depth is <= cfg.slam_sensor_max_range -- unless ``overlap`` (of its registration) is >= cfg.slam_min_overlap.  The first scan
@@ -238,9 +350,13 @@ class IcpMapper(object):
         cfg = self.cfg
         scan = self.prepare(scan)
         m = len(scan)
+        self.last_dyn = None
         if m == 0 or (self.n_map > 0 and overlap is not None and overlap >= cfg.slam_min_overlap):
             return 0
         pose_d = torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(4, 4), device=self.device)
+        if cfg.slam_compute_prob_dynamic and self.n_map > 0:
+            # norlab's order: the probabilities of the points the map has, then the new points appended with the prior
+            self.last_dyn = self.update_dynamic(scan, pose)
         dist1 = None
         if self.n_map > 0:
             self._ensure_grid(m)
@@ -255,26 +371,36 @@ class IcpMapper(object):
         need = self.n_map + added
         if need > self._pts.shape[0]:
             cap = max(need, 2 * self._pts.shape[0])
-            for name in ('_pts', '_nrm'):
+            for name in ('_pts', '_nrm', '_prob'):
                 old = getattr(self, name)
-                grown = torch.empty((cap, 3), dtype=torch.float64, device=self.device)
+                grown = torch.empty((cap,) + tuple(old.shape[1:]), dtype=torch.float64, device=self.device)
                 grown[:self.n_map] = old[:self.n_map]
                 setattr(self, name, grown)
         self._pts[self.n_map:need] = new_pts
         self._nrm[self.n_map:need] = new_nrm
+        prior = float(cfg.slam_prior_dynamic)
+        self._prob[self.n_map:need] = prior
+        if self.dyn is not None and prior >= self.dyn['threshold']:
+            self.n_dynamic += added
         self.n_map = need
+        self._version += 1
         self._ensure_grid(m)
         return added
 
-    def map_points(self):
-        """(points, normals) fp64 [N,3] of the map (world frame)."""
-        return self._pts[:self.n_map], self._nrm[:self.n_map]
+    def map_points(self, static_only=False):
+        """(points, normals) fp64 [N,3] of the map (world frame); ``static_only``: the rows with P < cfg.slam_threshold_dynamic."""
+        pts, nrm = self._pts[:self.n_map], self._nrm[:self.n_map]
+        if not static_only:
+            return pts, nrm
+        pts, nrm = ops.compact_rows(self._prob[:self.n_map] < float(self.cfg.slam_threshold_dynamic), [pts, nrm])
+        return pts, nrm
 
 
 def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     """The mapper over one sequence with the perturbed odometry of cfg.odom_cov (robot_data): prior[i] = slam[i-1] odom[i-1]^-1 odom[i],
-    slam[0] = odom[0] = gt[0]; a failed registration keeps its prior and leaves the map as it is.  Returns dict(slam, odom, gt
-    [N,4,4], path_lengths [N], info [N dicts], ids)."""
+    slam[0] = odom[0] = gt[0]; a failed registration keeps its prior and leaves the map and its probabilities as they are.  Every info
+    has ``dynamic`` (map points with P >= cfg.slam_threshold_dynamic) and ``dyn`` (update_dynamic's counts, None when it did not run).
+    Returns dict(slam, odom, gt [N,4,4], path_lengths [N], info [N dicts], ids)."""
     if cfg.slam not in SLAM:
         raise ValueError('unknown SLAM pipeline %r; available: %s' % (cfg.slam, ', '.join(SLAM)))
     items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in dataset]
@@ -288,12 +414,16 @@ def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
         prior = odom[0] if i == 0 else np.matmul(slam[i - 1], delta_transform(odom[i - 1], odom[i]))
         scan = mapper.prepare(mapper_input(cloud, model, cfg))
         pose, info = mapper.register(scan, prior)
+        mapper.last_dyn = None
         if info['ok']:
             info['added'] = mapper.update(scan, pose, overlap=info['overlap'] if info['status'] != 'init' else None)
+            if cfg.slam_compute_prob_dynamic and cfg.slam_dynamic_every_scan and mapper.last_dyn is None and info['status'] != 'init':
+                mapper.last_dyn = mapper.update_dynamic(scan, pose)         # the overlap skipped the map update
         else:
             print('SLAM: registration of scan %d failed (%s); keeping the odometry prior.' % (i, info['status']))
             info['added'] = 0
         info['map_size'] = mapper.n_map
+        info['dynamic'], info['dyn'] = mapper.n_dynamic, mapper.last_dyn
         slam[i] = pose
         infos.append(info)
         if verbose:

@@ -977,6 +977,37 @@ int dc_icp_finish(const double* partials, int n_blocks, int64_t m, double min_ro
 int dc_map_select(const double* reading, const double* normals, const double* depth, int64_t m, const double* pose, const double* dist1,
                   double min_dist, double max_range, uint8_t* mask_out, double* points_out, double* normals_out, dcStream_t stream);
 
+/* ---- dynamic points in the map (depth_correction_amd/csrc/dc_dynamic.hip, dc_dynmath.h; the rule and its deviations in DESIGN
+ * "Dynamic points in the map"): launch/slam.launch compute_prob_dynamic, after Pomerleau et al., "Long-term 3D map maintenance in
+ * dynamic environments" (ICRA 2014).  All fp64, sums and products unfused and in the order written.  One update = dc_dyn_directions
+ * (map, reading) + dc_compact_rows of the valid rows + dc_knn_grid_build over the reading directions + dc_knn_grid_query (k = 1,
+ * r = chord_max, identity pose) of the map directions + dc_dyn_update. ----
+ * Direction and depth of points fp64 [n,3] as the sensor at pose (DEVICE double [16], row-major, world from sensor) sees them:
+ * d = q - t, x_r = (R[0][r] d0 + R[1][r] d1) + R[2][r] d2, depth = sqrt((x0^2 + x1^2) + x2^2), dir = x / depth.  pose NULL: the points
+ * are in the sensor frame (x = q; the reading).  valid_out uint8 [n] = depth finite, > 0 and <= max_range (max_range <= 0 or inf: no
+ * bound); an invalid row's direction is zero, its depth what the arithmetic gave.  dirs_out fp64 [n,3], depth_out fp64 [n].  One
+ * launch, no workspace; n == 0 launches nothing. */
+int dc_dyn_directions(const double* points, int64_t n, const double* pose, double max_range, double* dirs_out, double* depth_out,
+                      uint8_t* valid_out, dcStream_t stream);
+/* Visibility test and Bayesian update of the map points rows[i] (int32 [n_rows], strictly ascending map rows: a thread owns its
+ * row of prob) against the reading point match_idx[i] (int32, a row of reading fp64 [m,3], sensor frame) whose direction is the
+ * nearest one at the chord match_chord[i] (fp64).  Left untouched: match_idx < 0 or >= m, a chord not < chord_max (= 2 sin(beam
+ * half angle), 0 < chord_max < 2), a row outside [0, n_map), a map point whose recomputed depth rho is not finite, not > 0 or
+ * > max_range, a reading point whose depth r is not finite or not > 0.  With delta = |p - x|, d_max = epsilon_a r and eps = 1e-4:
+ * not (r + epsilon_d) + d_max >= rho: occluded, prob kept, seen 1.  Otherwise seen 2 and
+ *   w_v = eps + (1 - eps) |n . d| / rho, w_d1 = eps + (1 - eps) (1 - c / chord_max), offset = delta - epsilon_d,
+ *   w_d2 = eps (delta < epsilon_d or rho > r) | eps + (1 - eps) offset / d_max (offset < d_max) | 1,
+ *   w_p2 = 1 (delta < epsilon_d) | eps + (1 - eps) (1 - offset / d_max) (offset < d_max) | eps,  c2 = w_v w_d1, c1 = 1 - c2,
+ *   P < threshold: pd = c1 P + (c2 w_d2) ((1 - alpha) (1 - P) + beta P), ps = c1 (1 - P) + (c2 w_p2) (alpha (1 - P) + (1 - beta) P);
+ *   else pd = 1 - eps, ps = eps;  P <- pd / (pd + ps).
+ * epsilon_a, epsilon_d >= 0 and finite, 0 < alpha, beta < 1, 0 < threshold <= 1 (DC_ERR_ARG otherwise).  prob fp64 [n_map] in / out;
+ * seen_out uint8 [n_map] (optional, zeroed by the caller) gets 1 / 2.  One launch; no allocation, copy or host read; n_rows == 0
+ * launches nothing. */
+int dc_dyn_update(const double* map_points, const double* map_normals, int64_t n_map, const double* pose, const double* reading, int64_t m,
+                  const int32_t* rows, const int32_t* match_idx, const double* match_chord, int64_t n_rows, double chord_max, double epsilon_a,
+                  double epsilon_d, double alpha, double beta, double threshold, double max_range, double* prob, uint8_t* seen_out,
+                  dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
