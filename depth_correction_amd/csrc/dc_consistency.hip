@@ -1032,1823 +1032,16 @@ __global__ __launch_bounds__(kBlock) void consistency_bwd_runs_kernel(
   if (in.dirs) reduce_param_grads<T>(in, active, want_e, want_pose, gw, ge, gT, scan, lds, partials, blk);
 }
 
-// ================================================================================================
-// Basis form of the iteration (fixed poses, fixed exponents): every model of the reference is affine in its weights
-// (Polynomial d' = d - sum w_k g^e_k, ScaledPolynomial d' = d (1 - sum w_k g^e_k), Linear, InvCos, ScaledInvCos:
-// model.py:113-349), so the world point of ray j is
-//     x_j(w) = X0_j + (sum_k w_k c_kj) u_j,     X0_j = R (vp + d0 dir) + t,   u_j = R dir,   c_kj = dd'/dw_k   (zero outside the local mask)
-// with X0, u and c constant while the poses do not move.  They are computed once (points_basis_kernel); an iteration then
-// needs no pass over the points to refresh x: the forward forms the rows it stages (and its centre) from the basis rows on
-// the fly, the backward its own point, and the chain to the weights is dL/dw_k = sum_j (g_j . u_j) c_kj -- no model, no
-// pose, no incidence angles in the loop.  X0 lives on the q32 grid, u and c in float32 (the correction sum w c is
-// centimetres, so its fp32 rounding is ~1e-9 m, far below the grid).  A coordinate is the grid value
-// X0 + rint((sum w_k c_k) u / step): the same integer for every block that forms it, rounded twice (X0 and the increment)
-// instead of once.  A row is 24 + 4 P bytes: 32 for the two-term models, one aligned sector per gathered point.
-// ================================================================================================
-struct PointBasis {
-  const void* __restrict__ rows;       // [n, 6 + P] words: X0, u, c_0 .. c_{P-1} (Basis<PT>: int32 / float32 bits for q32, fp64 for double)
-  const double* __restrict__ w;        // [P] device weights of this evaluation
-  int n_terms;
-  double w_scale;                      // weights are staged as w_k * w_scale: 1 / grid step for q32, 1 for fp64 points
-};
+}  // namespace dc
 
-// s_w[k] = w_k * w_scale for the lanes of the block (call before a barrier); coherent: the weights were written by other
-// blocks of this very launch (chained steps), so the load must not be served by this XCD's L2
-__device__ __forceinline__ void stage_weights(const PointBasis& pb, double* s_w, bool coherent = false) {
-  if ((int)threadIdx.x < pb.n_terms) {
-    const double w = coherent ? __hip_atomic_load(pb.w + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : pb.w[threadIdx.x];
-    s_w[threadIdx.x] = w * pb.w_scale;
-  }
-}
+// The basis form, the chained steps, the one-pass step kernels and the one-pass pose kernel live in headers of their own; they are
+// parts of this translation unit (they use the tables and gather helpers above) and are included in the order they build on each other.
+#include "dc_cons_basis.h"
+#include "dc_cons_chain.h"
+#include "dc_cons_step.h"
+#include "dc_cons_pose.h"
 
-// Row layout and arithmetic of the basis per point format.  q32 (float32 clouds): X0 on the fixed-point grid, u and c in
-// float32 (the correction sum w c is centimetres, so its fp32 rounding is ~1e-9 m, far below the grid); a coordinate is
-// X0 + rint((sum w_k c_k) u / step).  double (float64 clouds, the reference's default float_type): everything fp64,
-// x = X0 + (sum w_k c_k) u -- the same point as R (vp + d' dir) + t up to the order of the fp64 operations.
-template <typename PT> struct Basis;
-template <> struct Basis<q32> {
-  using T = float;                                       // dtype of the cloud's arrays
-  // P > 0: term count known at compile time (one contiguous row, loads issued together), P = 0: run-time count
-  template <int P>
-  static __device__ __forceinline__ Pt<q32>::Raw point(const PointBasis& pb, const double* wq, int64_t row) {
-    const int np = P > 0 ? P : pb.n_terms;
-    const int32_t* r = static_cast<const int32_t*>(pb.rows) + row * (6 + np);
-    int32_t q[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) q[c] = r[c];
-    // float32 throughout (one formula for every kernel that forms a point from its basis row, so that all of them form the
-    // same integer): the correction sum is < 2^20 grid steps, its float32 rounding a few hundredths of a step
-    float sc = 0.0f;
-    if constexpr (P > 0) {
-      float c[P];
-#pragma unroll
-      for (int k = 0; k < P; ++k) c[k] = __int_as_float(r[6 + k]);
-#pragma unroll
-      for (int k = 0; k < P; ++k) sc = fmaf((float)wq[k], c[k], sc);
-    } else {
-      for (int k = 0; k < np; ++k) sc = fmaf((float)wq[k], __int_as_float(r[6 + k]), sc);
-    }
-    Pt<q32>::Raw o;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) o.v[a] = q[a] + (int32_t)rintf(sc * __int_as_float(q[3 + a]));
-    return o;
-  }
-  static __device__ __forceinline__ void stage(int4* tile, int, int t, const Pt<q32>::Raw& r) { tile[t] = make_int4(r.v[0], r.v[1], r.v[2], 0); }
-  // gw[k] += (g . u_j) c_kj for the point's own row (g in metres^-1 units of the loss)
-  template <int NP>
-  static __device__ __forceinline__ void chain(const PointBasis& pb, int np, int64_t j, const double* g, double* gw) {
-    const int32_t* r = static_cast<const int32_t*>(pb.rows) + j * (6 + np);
-    const double gu = g[0] * (double)__int_as_float(r[3]) + g[1] * (double)__int_as_float(r[4]) + g[2] * (double)__int_as_float(r[5]);
-#pragma unroll
-    for (int k = 0; k < NP; ++k)
-      if (k < np) gw[k] = gu * (double)__int_as_float(r[6 + k]);
-  }
-  static __device__ __forceinline__ void write(void* rows, int64_t i, int nt, const double* x0, const double* u, const QParams& qp) {
-    int32_t* r = static_cast<int32_t*>(rows) + i * (6 + nt);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      r[a] = quantize(x0[a], qp.origin[a], qp.inv_scale, qp.flag);
-      r[3 + a] = __float_as_int((float)u[a]);
-    }
-  }
-  static __device__ __forceinline__ void write_term(void* rows, int64_t i, int nt, int k, double c) {
-    static_cast<int32_t*>(rows)[i * (6 + nt) + 6 + k] = __float_as_int((float)c);
-  }
-};
-template <> struct Basis<double> {
-  using T = double;
-  template <int P>
-  static __device__ __forceinline__ Pt<double>::Raw point(const PointBasis& pb, const double* wq, int64_t row) {
-    const int np = P > 0 ? P : pb.n_terms;
-    const double* r = static_cast<const double*>(pb.rows) + row * (6 + np);
-    double q[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) q[c] = r[c];
-    double sc = 0.0;
-    if constexpr (P > 0) {
-      double c[P];
-#pragma unroll
-      for (int k = 0; k < P; ++k) c[k] = r[6 + k];
-#pragma unroll
-      for (int k = 0; k < P; ++k) sc += wq[k] * c[k];
-    } else {
-      for (int k = 0; k < np; ++k) sc += wq[k] * r[6 + k];
-    }
-    Pt<double>::Raw o;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) o.v[a] = q[a] + sc * q[3 + a];
-    return o;
-  }
-  // 32-B rows, piece-major like stage_rows<2>: (x, y) at tile[t], (z, -) at tile[cap + t]
-  static __device__ __forceinline__ void stage(int4* tile, int cap, int t, const Pt<double>::Raw& r) {
-    tile[t] = make_int4(__double2loint(r.v[0]), __double2hiint(r.v[0]), __double2loint(r.v[1]), __double2hiint(r.v[1]));
-    tile[cap + t] = make_int4(__double2loint(r.v[2]), __double2hiint(r.v[2]), 0, 0);
-  }
-  template <int NP>
-  static __device__ __forceinline__ void chain(const PointBasis& pb, int np, int64_t j, const double* g, double* gw) {
-    const double* r = static_cast<const double*>(pb.rows) + j * (6 + np);
-    const double gu = g[0] * r[3] + g[1] * r[4] + g[2] * r[5];
-#pragma unroll
-    for (int k = 0; k < NP; ++k)
-      if (k < np) gw[k] = gu * r[6 + k];
-  }
-  static __device__ __forceinline__ void write(void* rows, int64_t i, int nt, const double* x0, const double* u, const QParams&) {
-    double* r = static_cast<double*>(rows) + i * (6 + nt);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { r[a] = x0[a]; r[3 + a] = u[a]; }
-  }
-  static __device__ __forceinline__ void write_term(void* rows, int64_t i, int nt, int k, double c) {
-    static_cast<double*>(rows)[i * (6 + nt) + 6 + k] = c;
-  }
-};
-
-// the lane's centre from the staged rows (row `t` of the block's distinct list)
-template <typename PT>
-__device__ __forceinline__ typename Pt<PT>::Raw staged_point(const int4* tile, int cap, int t) {
-  int4 piece[Pt<PT>::kRow16];
-  read_row<Pt<PT>::kRow16>(tile, cap, (uint32_t)t * 16u, piece);
-  return Pt<PT>::from_row(piece);
-}
-
-// X0, u and c of every point (once per pose set): the same inputs and arithmetic as points_fwd_kernel.
-template <typename PT>
-__global__ __launch_bounds__(kBlock) void points_basis_kernel(PointInputs in, int64_t n, QParams qp, void* __restrict__ rows) {
-  using T = typename Basis<PT>::T;
-  __shared__ double s_pose[kLdsScans * 12];
-  const PoseTile poses = stage_poses(in, s_pose);
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  ModelParams mp;
-  load_model(in, mp);
-  double vp[3], dr[3], T12[12];
-  if (in.vps) Row3<T, 3>::load((const T*)in.vps, i, vp, qp);
-  else { vp[0] = vp[1] = vp[2] = 0.0; }
-  Row3<T, 3>::load((const T*)in.dirs, i, dr, qp);
-  const double d = (double)((const T*)in.depth)[i];
-  const bool lm = in.lmask ? in.lmask[i] != 0 : true;
-  const double inc = (mp.kind != DC_MODEL_NONE && lm) ? (double)((const T*)in.inc)[i] : 0.0;
-  load_pose(in, poses, in.scan_id ? in.scan_id[i] : 0, T12);
-  double vr[3], drr[3], x0[3];
-  rot3(T12, vp, vr);
-  vr[0] += T12[3]; vr[1] += T12[7]; vr[2] += T12[11];
-  rot3(T12, dr, drr);
-  const bool on = mp.kind != DC_MODEL_NONE && lm;
-  const double d0 = (on && mp.kind == DC_MODEL_LINEAR) ? 0.0 : d;      // d' at w = 0
-#pragma unroll
-  for (int a = 0; a < 3; ++a) x0[a] = vr[a] + d0 * drr[a];
-  Basis<PT>::write(rows, i, mp.n_terms, x0, drr, qp);
-#pragma unroll
-  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) {
-    if (k < mp.n_terms) {
-      double dk = 0.0;                                                  // dd'/dw_k
-      if (on) {
-        if (mp.kind > DC_MODEL_SCALED_POLYNOMIAL) dk = model_dw_other(mp, k, d, inc);
-        else dk = (mp.kind == DC_MODEL_SCALED_POLYNOMIAL ? -d : -1.0) * pow_term(inc, mp.e[k]);
-      }
-      Basis<PT>::write_term(rows, i, mp.n_terms, k, dk);
-    }
-  }
-}
-
-template <typename PT, bool FULL_EIG, int NS, int P>
-__global__ __launch_bounds__(kBlock) void consistency_fwd_basis_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, int cap, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, const typename Basis<PT>::T* __restrict__ offset, LossParams lp, QParams qp, PT* __restrict__ rec,
-    typename Basis<PT>::T* __restrict__ pointwise, typename Basis<PT>::T* __restrict__ eigvals, double* __restrict__ partials) {
-  using T = typename Basis<PT>::T;
-  extern __shared__ int4 tile[];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  const int64_t blk = xcd_block(nblocks);
-  double acc2[2] = {0.0, 0.0};
-  const int32_t s0 = blk >= 0 ? tab.slot_ptr[blk] : 0;
-  // a table with another slot count than the launch was specialised for (not a table of [rows, NS]): fail loudly
-  const bool bad = blk >= 0 && tab.slot_ptr[blk + 1] - s0 != NS;
-  if (blk >= 0 && !bad) {
-    const int64_t i = blk * kBlock + threadIdx.x;
-    const bool live = i < n;
-    const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-    uint32_t pre[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) pre[q] = (uint32_t)lrow[q * kBlock];
-    stage_weights(pb, s_w);
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    // the block's own rows sit contiguously in its list (k-NN: every point is its own neighbour): the centre comes from LDS
-    const int32_t own = (own_base && !centre_idx) ? own_base[blk] : -1;
-    __syncthreads();
-    double wq[P > 0 ? P : DC_MAX_MODEL_TERMS];
-#pragma unroll
-    for (int k = 0; k < (P > 0 ? P : DC_MAX_MODEL_TERMS); ++k) wq[k] = (P > 0 || k < pb.n_terms) ? s_w[k] : 0.0;
-    for (int t = threadIdx.x; t < nd; t += kBlock)
-      Basis<PT>::stage(tile, cap, t, Basis<PT>::template point<P>(pb, wq, tab.blk_ids[base + t]));
-    typename Pt<PT>::Raw ci;
-    if (own < 0) ci = Basis<PT>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
-    __syncthreads();
-    if (own >= 0) ci = staged_point<PT>(tile, cap, own + (live ? (int)threadIdx.x : 0));
-    if (live) {
-      CovAcc acc;
-      cov_init(acc);
-      uint32_t mx = pre[0];
-#pragma unroll
-      for (int q = 1; q < NS; ++q) mx = max(mx, pre[q]);
-      int n_have;
-      if (__any((int)(mx == kNoLoc))) n_have = gather_fixed<PT, NS, true>(tile, cap, ci, pre, acc);
-      else n_have = gather_fixed<PT, NS, false>(tile, cap, ci, pre, acc);
-      acc.W = (double)n_have;
-      consistency_point<T, PT, FULL_EIG>(acc, ci, i, mask, offset, lp, qp, rec, pointwise, eigvals, acc2);
-    }
-  } else {
-    __syncthreads();
-    __syncthreads();
-  }
-  if (bad) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  wave_partials<2>(acc2, partials);
-}
-
-// The same for any slot count (radius neighbourhoods: the reference's default nn_r = 0.25, K = the largest count; or the
-// run-time-slot ablation): the slot loop of consistency_fwd_staged_kernel over rows formed from the basis.
-template <typename PT, bool FULL_EIG, int P>
-__global__ __launch_bounds__(kBlock) void consistency_fwd_basis_slots_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, int cap, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, const typename Basis<PT>::T* __restrict__ offset, LossParams lp, QParams qp, PT* __restrict__ rec,
-    typename Basis<PT>::T* __restrict__ pointwise, typename Basis<PT>::T* __restrict__ eigvals, double* __restrict__ partials) {
-  using T = typename Basis<PT>::T;
-  extern __shared__ int4 tile[];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  const int64_t blk = xcd_block(nblocks);
-  double acc2[2] = {0.0, 0.0};
-  const int64_t i = blk * kBlock + threadIdx.x;
-  const bool live = blk >= 0 && i < n;
-  int32_t nslots = 0, own = -1;
-  const uint16_t* lrow = tab.loc;
-  uint32_t pre[kPreSlots];
-  stage_weights(pb, s_w);
-  if (blk >= 0) {
-    const int32_t s0 = tab.slot_ptr[blk];
-    nslots = tab.slot_ptr[blk + 1] - s0;
-    lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < kPreSlots; ++q) pre[q] = (live && q < nslots) ? (uint32_t)lrow[q * kBlock] : kNoLoc;
-    own = (own_base && !centre_idx) ? own_base[blk] : -1;
-  }
-  __syncthreads();
-  double wq[P > 0 ? P : DC_MAX_MODEL_TERMS];
-#pragma unroll
-  for (int k = 0; k < (P > 0 ? P : DC_MAX_MODEL_TERMS); ++k) wq[k] = (P > 0 || k < pb.n_terms) ? s_w[k] : 0.0;
-  typename Pt<PT>::Raw ci;
-  if (blk >= 0) {
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    for (int t = threadIdx.x; t < nd; t += kBlock)
-      Basis<PT>::stage(tile, cap, t, Basis<PT>::template point<P>(pb, wq, tab.blk_ids[base + t]));
-    if (own < 0) ci = Basis<PT>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
-  }
-  __syncthreads();
-  if (live) {
-    if (own >= 0) ci = staged_point<PT>(tile, cap, own + (int)threadIdx.x);
-    CovAcc acc;
-    cov_init(acc);
-    bool miss = false;
-#pragma unroll
-    for (int q = 0; q < kPreSlots; ++q) miss |= (q < nslots) && pre[q] == kNoLoc;
-    int n_have = 0;
-    if (__any((int)miss)) n_have = gather_slots<PT, true>(tile, cap, ci, pre, nslots, acc);
-    else n_have = gather_slots<PT, false>(tile, cap, ci, pre, nslots, acc);
-    for (int q = kPreSlots; q < nslots; ++q) {             // K > 16: one slot at a time
-      const uint32_t l = lrow[q * kBlock];
-      n_have += slot_add<PT, true>(tile, cap, ci, l, acc);
-    }
-    acc.W = (double)n_have;
-    consistency_point<T, PT, FULL_EIG>(acc, ci, i, mask, offset, lp, qp, rec, pointwise, eigvals, acc2);
-  }
-  wave_partials<2>(acc2, partials);
-}
-
-// torch.optim.Adam (single-tensor path, no amsgrad) for one fp64 parameter; grad is scaled first.
-struct AdamArgs {
-  double* p; double* m; double* v;     // parameters, exp_avg, exp_avg_sq (p == nullptr: no update)
-  int n;
-  double grad_scale, lr, b1, b2, eps, weight_decay, bias1, bias2_sqrt;
-};
-// (p0, m0, v0: the parameter's state, loaded by the caller -- early, so the trip hides behind its own work)
-__device__ __forceinline__ void adam_apply(const AdamArgs& a, int i, double grad, double p0, double m0, double v0) {
-  double g = grad * a.grad_scale;
-  if (a.weight_decay != 0.0) g += a.weight_decay * p0;
-  const double mi = m0 + (g - m0) * (1.0 - a.b1);                   // exp_avg.lerp_(grad, 1 - beta1)
-  const double vi = v0 * a.b2 + (1.0 - a.b2) * g * g;               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-  a.m[i] = mi; a.v[i] = vi;
-  const double denom = sqrt(vi) / a.bias2_sqrt + a.eps;
-  a.p[i] = p0 + (-(a.lr / a.bias1)) * (mi / denom);
-}
-__device__ __forceinline__ void adam_update(const AdamArgs& a, int i, double grad) { adam_apply(a, i, grad, a.p[i], a.m[i], a.v[i]); }
-
-// ---- chained steps: the previous evaluation's final sums inside the next evaluation's launch -----------------------------
-// A dependent reduction launch after a kernel that filled every L2 costs ~9 us, an eighth of a C2 step.  In a chain
-// of steps the launch of step t + 1 therefore starts with `n_front` leading blocks that finish step t: block a < 2 + P sums
-// column a of step t's partial rows (one per BLOCK in this mode: 7.8 k rows, one trip for 256 lanes), writes out_prev[a],
-// takes weight (a - 2)'s Adam step and raises ready[parity]; the other blocks fetch everything that does not depend on the
-// weights, then wait for ready[parity] == P.  The leading blocks are dispatched first and need nothing from the waiting ones,
-// so they always finish; the wait is bounded all the same (a grid must drain).  parity alternates per launch: this launch
-// clears the other flag and writes its own partial rows to the other buffer.  The last step of a chain is finished by the
-// ordinary reduction launch (flush).
-struct StepChain {
-  int32_t* ready;            // 64 bytes, zero before the first launch of a chain (the published weights, chain_publish); nullptr: ordinary
-                             // launch (per-wavefront rows)
-  uint32_t stamp;            // this launch's number: what marks a published word as belonging to it
-  int parity, has_prev, n_front, n_out;
-  int reverse;               // this launch walks every XCD's share of the blocks backwards (chain_block_of)
-  const double* prev;        // the previous launch's rows [(2 + P)][prev_rows]
-  int64_t prev_rows;
-  const double* grad_sum;    // or: the previous evaluation's dL/dw already summed (over the ranks: an all-reduce ran in between);
-                             // the leading blocks then only take the Adam update (out_prev is not written)
-  double* out_prev;          // [n_out] <- sums of the previous evaluation (slots beyond 2 + P: 0)
-  double* w_prev_out;        // [P] or nullptr <- the weights the previous evaluation used (a training log records them: train.py)
-  int32_t* status;           // bit 0: a point left the q32 extent (read); bit 1: a wait for the weights ran out (raised here)
-  int spin_limit;            // polls a waiting block makes before it gives up (dc_set_option(5, n); 0: gives up at once)
-  const double* w_now;       // the caller's weights (what a launch with nothing to finish publishes)
-  const int32_t* prev_status;  // linked chains: the status word of the sequence whose rows are finished (nullptr: `status`)
-  const double* acc_in;      // [2 + P] or nullptr: added to the previous launch's sums (the sequences of ONE loss evaluated launch after
-                             // launch: the running sums of the step's earlier sequences)
-  AdamArgs adam;             // the update the previous evaluation's gradient feeds (bias corrections of ITS step)
-  const uint8_t* blk_skip;   // [blocks] or nullptr: blocks none of whose centres is inside the loss mask (dcSequenceDesc.blk_skip): they add
-                             // nothing to the loss, the count or dL/dw and are treated like the padding blocks of the last round
-};
-constexpr int32_t kStatusChainTimeout = 2;     // (bit 0: q32 overflow, raised by quantize())
-constexpr int kChainFront = 8;             // leading blocks of a chained launch (a multiple of the XCD count)
-
-// The logical block of this workgroup (xcd_block_of); -1: padding.  Every other launch of a chain of fixed-K steps walks its XCD's
-// share of the blocks BACKWARDS: the basis rows are the same in every step, an XCD's 4 MB of L2 still holds the rows of the last
-// ~260 blocks it finished, and a launch's first round -- 1 536 blocks that all start by fetching rows -- is its slowest
-// (profiles/r04_block_trace.md: 12 us per block against 7.7 later on).  Walking back, the first round finds its rows in L2:
-// C2 step 42.8 -> 41.4 us.  Block -> row of the partial sums is by grid position either way, so the order of the final
-// additions differs between the two directions by rounding only (deterministic: the direction is the launch's parity).
-__device__ __forceinline__ int64_t chain_block_of(const StepChain& ch, bool chained, int64_t nblocks) {
-  const int64_t b = (int64_t)blockIdx.x - (chained ? ch.n_front : 0);
-  if (!(chained && ch.reverse)) return xcd_block_of(b, nblocks);
-  const int64_t per = (nblocks + kXcds - 1) / kXcds;
-  const int64_t logical = (b % kXcds) * per + (per - 1 - b / kXcds);
-  return logical < nblocks ? logical : -1;
-}
-
-// Weight k of a chained launch, published by the leading block that finished it and picked up by every other block in ONE
-// memory trip: the double travels as two 64-bit words {low half | stamp}, {high half | stamp} (8-byte accesses are single-copy
-// atomic), the stamp being the launch's number -- a word carrying it can only be this launch's.  (Rounds 2-4: a counter raised
-// after a fence, polled, and then the weights loaded: two dependent trips through the fabric in front of every block's staging.)
-__device__ __forceinline__ void chain_publish(const StepChain& ch, int k, double w) {
-  unsigned long long* pub = reinterpret_cast<unsigned long long*>(ch.ready);
-  const unsigned long long st = (unsigned long long)ch.stamp << 32;
-  __hip_atomic_store(pub + 2 * k, st | (unsigned)__double2loint(w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(pub + 2 * k + 1, st | (unsigned)__double2hiint(w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int P>
-__device__ __forceinline__ void chain_front_block(const StepChain& ch, double* lds /* [kBlock / kWave] in LDS */) {
-  const int a = blockIdx.x;
-  if (a == 0 && ch.has_prev && !ch.grad_sum)
-    for (int z = 2 + P + threadIdx.x; z < ch.n_out; z += kBlock) ch.out_prev[z] = 0.0;
-  if (a >= 2 + P) return;
-  if (ch.grad_sum) {                     // the sums exist already: weight a - 2's update, then publish
-    if (a >= 2 && threadIdx.x == 0) {
-      if (ch.has_prev && ch.adam.p) adam_update(ch.adam, a - 2, ch.grad_sum[a - 2]);
-      const double wk = ch.adam.p ? ch.adam.p[a - 2] : ch.w_now[a - 2];
-      chain_publish(ch, a - 2, wk);
-      if (ch.w_prev_out) ch.w_prev_out[a - 2] = wk;      // (this form records the weights THIS evaluation uses: its sums are current)
-    }
-    return;
-  }
-  const bool step = ch.has_prev && ch.adam.p && a >= 2 && threadIdx.x == 0;
-  const int32_t* st_prev = ch.prev_status ? ch.prev_status : ch.status;
-  const bool flagged = ch.has_prev && a == 0 && threadIdx.x == 0 && st_prev &&
-                       __hip_atomic_load(st_prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-  double p0 = 0.0, m0 = 0.0, v0 = 0.0;
-  if (step) {
-    p0 = ch.adam.p[a - 2]; m0 = ch.adam.m[a - 2]; v0 = ch.adam.v[a - 2];
-    if (ch.w_prev_out) ch.w_prev_out[a - 2] = p0;
-  }
-  double s = 0.0;
-  if (ch.has_prev) {
-    const double* p = ch.prev + (int64_t)a * ch.prev_rows;
-    constexpr int U = 32;
-    for (int64_t r0 = threadIdx.x; r0 < ch.prev_rows; r0 += (int64_t)U * kBlock) {
-      double v[U];
-#pragma unroll
-      for (int u_ = 0; u_ < U; ++u_) v[u_] = (r0 + (int64_t)u_ * kBlock < ch.prev_rows) ? p[r0 + (int64_t)u_ * kBlock] : 0.0;
-#pragma unroll
-      for (int w_ = U / 2; w_ > 0; w_ >>= 1) {
-#pragma unroll
-        for (int u_ = 0; u_ < w_; ++u_) v[u_] += v[u_ + w_];
-      }
-      s += v[0];
-    }
-    s = wave_sum(s);
-  }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) lds[wave] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (ch.has_prev) {
-      double t = 0.0;
-      for (int wv = 0; wv < kBlock / kWave; ++wv) t += lds[wv];
-      if (ch.acc_in) t += ch.acc_in[a];                      // (read before out_prev is written: the two may be one buffer)
-      if (flagged) t = __longlong_as_double(0x7ff8000000000000ll);
-      ch.out_prev[a] = t;
-      if (step) adam_apply(ch.adam, a - 2, t, p0, m0, v0);
-    }
-    // weight a - 2 is final for this launch (the value just stored, or the caller's when there was nothing to finish)
-    if (a >= 2) chain_publish(ch, a - 2, step ? ch.adam.p[a - 2] : ch.w_now[a - 2]);
-  }
-}
-
-// chain_front_block on its own: finishes the last launch of a linked chain (dc_sequence_chain_flush_linked)
-template <int P>
-__global__ __launch_bounds__(kBlock) void chain_front_only_kernel(StepChain ch) {
-  __shared__ double s_front[kBlock / kWave];
-  chain_front_block<P>(ch, s_front);
-}
-
-// s_w[k] <- w_k * w_scale of this launch for the lanes of the block, as soon as its leading blocks have published them
-// (bounded wait); *s_ok <- 0 when a wait ran out.  Every thread of the block calls it; the caller's barrier follows.
-template <int P>
-__device__ __forceinline__ void chain_weights(const StepChain& ch, double w_scale, double* s_w, int* s_ok) {
-  const int tid = threadIdx.x;
-  if (tid == 0) *s_ok = 1;
-  if (tid < 2 * P) {
-    const unsigned long long* pub = reinterpret_cast<const unsigned long long*>(ch.ready) + tid;
-    unsigned long long word = 0;
-    bool ok = false;
-    for (int spin = 0; spin < ch.spin_limit; ++spin) {
-      // (relaxed: an agent-scope acquire would invalidate this XCD's L2 on every poll -- nothing else is read through it)
-      word = __hip_atomic_load(pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((uint32_t)(word >> 32) == ch.stamp) { ok = true; break; }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    const int half = (int)(uint32_t)word;
-    const int other = __shfl_xor(half, 1, kWave);                       // lanes 2k / 2k + 1: low / high half of weight k
-    if ((tid & 1) == 0) s_w[tid >> 1] = (ok ? __hiloint2double(other, half) : __longlong_as_double(0x7ff8000000000000ll)) * w_scale;
-    // a wait that ran out poisons this launch's sums (NaN) AND says so: the status word tells it apart from a q32 overflow
-    if (!ok) {
-      *s_ok = 0;
-      if (ch.status) atomicOr(ch.status, kStatusChainTimeout);
-    }
-  }
-}
-
-// ---- loss AND dL/dw in one pass (forward-mode accumulation) -------------------------------------------------------------
-// With only the P model weights to differentiate, the reverse pass over the transposed table is not needed:
-//     dL/dw_k = sum_i sum_{j in N(i)} (dl_i/dx_j) . (dx_j/dw_k),   dl_i/dx_j = c1_i (v0_i . d) v0_i - c2_i d,  d = x_j - cmean_i,
-//     dx_j/dw_k = c_kj u_j
-// is a second sweep of centre i over its OWN neighbours, whose rows (x_j and now also u_j, c_kj) already sit in LDS.  No
-// backward record is written or read (64 + 64 MB per iteration at C2), no transposed table, no second launch; the terms
-// are the ones the backward kernel adds up, grouped by centre instead of by point, with c1 / c2 / cmean in fp64.
-// Staged row (piece-major, 16-B pieces; piece 0 starts with the point in its usual row format, so the first sweep and the
-// centre read it as before):  q32: {x0, x1, x2, u0 | u1, u2, c0, c1 | c2}, x on the grid, u / c float32 bits;
-// double: {x0, x1 | x2, u0' u1' | u2', c0', c1', c2'} (u', c': float32 copies for the second sweep).
-template <typename PT, int P> struct StepRow;
-template <int P> struct StepRow<q32, P> {
-  static constexpr int kPieces = (6 + P + 3) / 4;
-  struct Raw { int32_t q[6 + P]; };                       // a basis row as fetched (before the weights are known)
-  static __device__ __forceinline__ Raw fetch(const PointBasis& pb, int64_t row) {
-    const int32_t* r = static_cast<const int32_t*>(pb.rows) + row * (6 + P);
-    Raw o;
-#pragma unroll
-    for (int c = 0; c < 6 + P; ++c) o.q[c] = r[c];
-    return o;
-  }
-  static __device__ __forceinline__ void stage(const PointBasis& pb, const double* wq, int64_t row, int4* tile, int cap, int t) {
-    place(fetch(pb, row), wq, tile, cap, t);
-  }
-  static __device__ __forceinline__ void place(const Raw& raw, const double* wq, int4* tile, int cap, int t) {
-    const int32_t* q = raw.q;
-    float sc = 0.0f;                                      // exactly Basis<q32>::point's arithmetic
-#pragma unroll
-    for (int k = 0; k < P; ++k) sc = fmaf((float)wq[k], __int_as_float(q[6 + k]), sc);
-    int32_t x[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = q[a] + (int32_t)rintf(sc * __int_as_float(q[3 + a]));
-    tile[t] = make_int4(x[0], x[1], x[2], q[3]);
-    tile[cap + t] = make_int4(q[4], q[5], q[6], P > 1 ? q[P > 1 ? 7 : 6] : 0);
-    if constexpr (P > 2) tile[2 * cap + t] = make_int4(q[8], 0, 0, 0);
-  }
-  // the neighbourhood mean in the staged rows' units: x_i + cm (grid steps; exact in fp64)
-  static __device__ __forceinline__ void mean_of(const Pt<q32>::Raw& ci, const double* cm, double* mean) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) mean[a] = (double)ci.v[a] + cm[a];
-  }
-  // e = x_j - mean (grid steps), u_j, c_kj of the staged row at byte offset `off`
-  static __device__ __forceinline__ void load(const int4* tile, int cap, uint32_t off, const double* mean, double* e, double* u, double* c) {
-    const char* row = reinterpret_cast<const char*>(tile) + off;
-    const int4 p0 = *reinterpret_cast<const int4*>(row);
-    const int4 p1 = *reinterpret_cast<const int4*>(row + (size_t)cap * 16);
-    e[0] = (double)p0.x - mean[0]; e[1] = (double)p0.y - mean[1]; e[2] = (double)p0.z - mean[2];
-    u[0] = (double)__int_as_float(p0.w); u[1] = (double)__int_as_float(p1.x); u[2] = (double)__int_as_float(p1.y);
-    c[0] = (double)__int_as_float(p1.z);
-    if constexpr (P > 1) c[1] = (double)__int_as_float(p1.w);
-    if constexpr (P > 2) c[2] = (double)__int_as_float(reinterpret_cast<const int4*>(row + (size_t)cap * 32)->x);
-  }
-};
-template <int P> struct StepRow<double, P> {
-  // Staged row of a float64 cloud (round 5): {x0, x1 | x2, u0' u1' | u2', c0', c1', c2'} -- the point in fp64 as before (the first
-  // sweep and the centre read pieces 0 and 1: the loss is what it was, bit for bit), u and c as float32 COPIES for the second sweep:
-  // 48 B instead of 64, three LDS reads per neighbour there instead of four.  The kernel is bound by LDS reads at random rows
-  // (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.62, LDS busy two thirds of the launch).  The point itself is formed from the
-  // fp64 basis row; the float32 copies enter dL/dw only: a relative rounding of 6e-8 per term, of random sign over 2e7 terms.
-  static constexpr int kPieces = 3;
-  static_assert(P <= 3, "three float32 weights' terms fit the third piece");
-  static __device__ __forceinline__ int4 pack(double a, double b) {
-    return make_int4(__double2loint(a), __double2hiint(a), __double2loint(b), __double2hiint(b));
-  }
-  struct Raw { double q[6 + P]; };
-  static __device__ __forceinline__ Raw fetch(const PointBasis& pb, int64_t row) {
-    const double* r = static_cast<const double*>(pb.rows) + row * (6 + P);
-    Raw o;
-#pragma unroll
-    for (int c = 0; c < 6 + P; ++c) o.q[c] = r[c];
-    return o;
-  }
-  static __device__ __forceinline__ void stage(const PointBasis& pb, const double* wq, int64_t row, int4* tile, int cap, int t) {
-    place(fetch(pb, row), wq, tile, cap, t);
-  }
-  static __device__ __forceinline__ void place(const Raw& raw, const double* wq, int4* tile, int cap, int t) {
-    double q[9];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) q[c] = c < 6 + P ? raw.q[c] : 0.0;
-    double sc = 0.0;
-#pragma unroll
-    for (int k = 0; k < P; ++k) sc += wq[k] * q[6 + k];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) q[a] += sc * q[3 + a];
-    tile[t] = pack(q[0], q[1]);
-    tile[cap + t] = make_int4(__double2loint(q[2]), __double2hiint(q[2]), __float_as_int((float)q[3]), __float_as_int((float)q[4]));
-    tile[2 * cap + t] = make_int4(__float_as_int((float)q[5]), __float_as_int((float)q[6]), __float_as_int((float)q[7]), __float_as_int((float)q[8]));
-  }
-  static __device__ __forceinline__ void mean_of(const Pt<double>::Raw& ci, const double* cm, double* mean) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) mean[a] = ci.v[a] + cm[a];
-  }
-  static __device__ __forceinline__ void load(const int4* tile, int cap, uint32_t off, const double* mean, double* e, double* u, double* c) {
-    const char* row = reinterpret_cast<const char*>(tile) + off;
-    const int4 p0 = *reinterpret_cast<const int4*>(row);
-    const int4 p1 = *reinterpret_cast<const int4*>(row + (size_t)cap * 16);
-    const int4 p2 = *reinterpret_cast<const int4*>(row + (size_t)cap * 32);
-    e[0] = __hiloint2double(p0.y, p0.x) - mean[0]; e[1] = __hiloint2double(p0.w, p0.z) - mean[1]; e[2] = __hiloint2double(p1.y, p1.x) - mean[2];
-    u[0] = (double)__int_as_float(p1.z); u[1] = (double)__int_as_float(p1.w); u[2] = (double)__int_as_float(p2.x);
-    c[0] = (double)__int_as_float(p2.y);
-    if constexpr (P > 1) c[1] = (double)__int_as_float(p2.z);
-    if constexpr (P > 2) c[2] = (double)__int_as_float(p2.w);
-  }
-};
-
-// one neighbour's share of dL/dw: gw[k] += t c_kj, t = c1 (v . e)(v . u_j) - c2 (e . u_j); have = false: nothing
-template <typename PT, int P>
-__device__ __forceinline__ void chain_term(const int4* tile, int cap, uint32_t off, bool have, const double* mean, const double* v,
-                                           double c1, double c2, double* gw) {
-  double e[3], u[3], c[P];
-  StepRow<PT, P>::load(tile, cap, have ? off : 0u, mean, e, u, c);
-  const double al = v[0] * e[0] + v[1] * e[1] + v[2] * e[2];
-  const double be = v[0] * u[0] + v[1] * u[1] + v[2] * u[2];
-  const double ga = e[0] * u[0] + e[1] * u[1] + e[2] * u[2];
-  double tj = c1 * al * be - c2 * ga;
-  if (!have) tj = 0.0;
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = fma(tj, c[k], gw[k]);
-}
-
-// everything of a centre after its moments are gathered: covariance -> smallest eigenpair -> loss (acc2) and the
-// coefficients of its neighbours' terms; an empty neighbourhood (NaN mean, zero coefficients) contributes exactly nothing
-template <typename PT>
-__device__ __forceinline__ void step_point(CovAcc& acc, bool m, const LossParams& lp, const QParams& qp, double* acc2, double* cm,
-                                           double* v0, double* c1, double* c2) {
-  cov_same_weights(acc);
-  const double u = Pt<PT>::unit(qp);
-  double moff[3], C[6], D, omega, lam0, tr;
-  cov_finish(acc, 0.0, moff, cm, C, &D, &omega, u * u);
-  eig3_smallest_r2(C[0], C[1], C[2], C[3], C[4], C[5], &lam0, v0, &tr);      // (the A-B baseline form, dc_set_option(6, 0))
-  const double l = loss_and_coeffs(lp, lam0, tr, D, 0.0, m, c1, c2);
-  const bool drop = loss_dropped(lp, l);
-  if (drop) *c1 = *c2 = 0.0;
-  if (m && !drop) { acc2[0] = l; acc2[1] = 1.0; }
-  if (!(*c1 != 0.0 || *c2 != 0.0)) { cm[0] = cm[1] = cm[2] = 0.0; v0[0] = v0[1] = v0[2] = 0.0; }
-}
-
-// ---- the slimmer forms of the one-pass kernel's per-centre work (VAR bits of consistency_step_basis_kernel) ----------------
-constexpr int kVarF32Sweep = 1;     // second sweep in float32 (q32 points: differences, u and c are float32-exact already)
-constexpr int kVarSlimTail = 2;     // covariance -> eigenpair -> loss without the intermediate normalisations (eig3_smallest_unit)
-constexpr int kVarDppSums = 4;      // wavefront sums through DPP row operations instead of ds_bpermute shuffles
-constexpr int kStepVar = kVarF32Sweep | kVarSlimTail | kVarDppSums;     // what every instantiation but the A-B baseline (0) uses
-
-// Covariance, smallest eigenpair, loss and the coefficients c1, c2 of a centre from its moments about the centre point.
-// The covariance is only ever needed divided by its trace (eig3_smallest_unit), so the Bessel / unit factor f = unit^2 / D
-// multiplies the trace alone; `full` (wave-uniform): every lane of the wavefront has all NS neighbours, W and D are constants.
-template <typename PT, int NS>
-__device__ __forceinline__ void step_point2(const CovAcc& acc, int n_have, bool full, bool m, const LossParams& lp, const QParams& qp,
-                                            double* acc2, double* cm, double* v0, double* c1, double* c2, double* sum_e2 = nullptr) {
-  const double u = Pt<PT>::unit(qp);
-  double invW, D, invD;
-  if (full) {
-    invW = 1.0 / NS; D = NS - 1.0; invD = 1.0 / (NS - 1.0);
-  } else {
-    const double W = (double)n_have;
-    invW = recip1_(W);                                  // W = 0: inf * 0 -> NaN mean, like the reference's 0 / 0
-    D = W - 1.0;
-    D = D < 1e-6 ? 1e-6 : D;
-    invD = recip1_(D);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) cm[a] = acc.s[a] * invW;
-  double Cp[6];
-  Cp[0] = fma(-acc.s[0], cm[0], acc.S[0]); Cp[1] = fma(-acc.s[0], cm[1], acc.S[1]); Cp[2] = fma(-acc.s[0], cm[2], acc.S[2]);
-  Cp[3] = fma(-acc.s[1], cm[1], acc.S[3]); Cp[4] = fma(-acc.s[1], cm[2], acc.S[4]); Cp[5] = fma(-acc.s[2], cm[2], acc.S[5]);
-  const double mp = (Cp[0] + Cp[3]) + Cp[5];            // trace in the units of the differences
-  if (sum_e2) *sum_e2 = mp;                             // = sum_j |x_j - mean|^2
-  const double f = (u * u) * invD;
-  const double tr = mp * f;
-  double lam_rel, inv_tr;
-  if (!(mp > 0.0) || !(mp < (double)INFINITY)) {
-    const bool zero = (mp == 0.0) && Cp[1] == 0.0 && Cp[2] == 0.0 && Cp[4] == 0.0;
-    lam_rel = zero ? 0.0 : (double)NAN;
-    inv_tr = 1e6;                                       // tr is 0 (or NaN): the clamp of loss.py:253 applies
-    v0[0] = 1.0; v0[1] = 0.0; v0[2] = 0.0;
-  } else {
-    const double inv_m = recip1_(mp);
-    eig3_smallest_unit<!std::is_same<PT, q32>::value>(Cp[0] * inv_m, Cp[1] * inv_m, Cp[2] * inv_m, Cp[3] * inv_m, Cp[4] * inv_m, Cp[5] * inv_m,
-                                                       &lam_rel, v0);
-    const double inv_u2 = std::is_same<PT, q32>::value ? qp.inv_scale * qp.inv_scale : 1.0;
-    inv_tr = inv_m * (D * inv_u2);                      // 1 / tr = 1 / (mp f)
-  }
-  const double lam0 = lam_rel * tr;
-  // loss_and_coeffs with the reciprocals at hand
-  double raw, g_vv = 0.0, g_eye = 0.0;
-  if (lp.kind == DC_LOSS_MIN_EIGVAL) {
-    if (lp.normalization) {
-      const double inv = tr < 1e-6 ? 1e6 : inv_tr;      // 1 / clamp(tr, 1e-6); NaN compares false
-      raw = lam0 * inv;
-      g_vv = inv;
-      g_eye = (tr > 1e-6) ? -raw * inv : 0.0;
-    } else {
-      raw = lam0;
-      g_vv = 1.0;
-    }
-  } else {
-    raw = tr;
-    g_eye = 1.0;
-  }
-  double l = raw;
-  double a = (m && l > 0.0) ? 1.0 : 0.0;
-  l = l > 0.0 ? l : (l != l ? l : 0.0);
-  if (lp.sqrt_) {
-    const double sq = sqrt(l);
-    a = (l > 0.0) ? a * 0.5 / sq : 0.0;
-    l = sq;
-  }
-  const bool drop = loss_dropped(lp, l);                    // (skip_nans / only_finite: not part of the reduction at all)
-  const double fd = drop ? 0.0 : 2.0 * a * invD;
-  *c1 = fd * g_vv;
-  *c2 = -fd * g_eye;
-  if (m && !drop) { acc2[0] = l; acc2[1] = 1.0; }
-  // an empty neighbourhood (NaN mean) must contribute nothing to the second sweep: only possible when slots are missing
-  if (!full && !(*c1 != 0.0 || *c2 != 0.0)) { cm[0] = cm[1] = cm[2] = 0.0; v0[0] = v0[1] = v0[2] = 0.0; }
-}
-
-// One neighbour's share of dL/dw in float32 (q32 rows): the difference to the centre is an exact int32, u and c are float32
-// words already, and the per-centre factors are rounded once; the lane's sums stay float32 over its K neighbours and join the
-// fp64 reduction afterwards.  vs = c1 v0, vu = v0, both float32.
-template <int P>
-__device__ __forceinline__ void chain_term_f32(const int4* tile, int cap, uint32_t off, bool have, const Pt<q32>::Raw& ci, const float* cmf,
-                                               const float* vs, const float* vu, float c2f, float* gw) {
-  const char* row = reinterpret_cast<const char*>(tile) + (have ? off : 0u);
-  const int4 p0 = *reinterpret_cast<const int4*>(row);
-  const int4 p1 = *reinterpret_cast<const int4*>(row + (size_t)cap * 16);
-  const float e0 = (float)(p0.x - ci.v[0]) - cmf[0], e1 = (float)(p0.y - ci.v[1]) - cmf[1], e2 = (float)(p0.z - ci.v[2]) - cmf[2];
-  const float u0 = __int_as_float(p0.w), u1 = __int_as_float(p1.x), u2 = __int_as_float(p1.y);
-  const float al = fmaf(vs[2], e2, fmaf(vs[1], e1, vs[0] * e0));
-  const float be = fmaf(vu[2], u2, fmaf(vu[1], u1, vu[0] * u0));
-  const float ga = fmaf(e2, u2, fmaf(e1, u1, e0 * u0));
-  float tj = fmaf(al, be, -(c2f * ga));
-  if (!have) tj = 0.0f;
-  gw[0] = fmaf(tj, __int_as_float(p1.z), gw[0]);
-  if constexpr (P > 1) gw[1] = fmaf(tj, __int_as_float(p1.w), gw[1]);
-  if constexpr (P > 2) gw[2] = fmaf(tj, __int_as_float(reinterpret_cast<const int4*>(row + (size_t)cap * 32)->x), gw[2]);
-}
-
-// the second sweep over the slots beyond the first 16, in the same trips of eight; a trip's float32 sums join the fp64 sums trip by
-// trip (a row of two hundred neighbours is too long for one float32 running sum)
-template <int P>
-__device__ __forceinline__ void chain_tail_f32(const int4* tile, int cap, const uint16_t* lrow, int nslots, bool packed, const Pt<q32>::Raw& ci,
-                                               const float* cmf, const float* vs, const float* vu, float c2f, double* gw) {
-  uint32_t nxt[kTrip];
-#pragma unroll
-  for (int u_ = 0; u_ < kTrip; ++u_) nxt[u_] = (kPreSlots + u_ < nslots) ? (uint32_t)lrow[(kPreSlots + u_) * kBlock] : kNoLoc;
-  for (int q0 = kPreSlots; q0 < nslots; q0 += kTrip) {
-    uint32_t l[kTrip];
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) l[u_] = nxt[u_];
-    if (packed && __all((int)(l[0] == kNoLoc))) break;
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) nxt[u_] = (q0 + kTrip + u_ < nslots) ? (uint32_t)lrow[(q0 + kTrip + u_) * kBlock] : kNoLoc;
-    float g[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) g[k] = 0.0f;
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) chain_term_f32<P>(tile, cap, l[u_], l[u_] != kNoLoc, ci, cmf, vs, vu, c2f, g);
-#pragma unroll
-    for (int k = 0; k < P; ++k) gw[k] += (double)g[k];
-  }
-}
-template <typename PT, int P>
-__device__ __forceinline__ void chain_tail(const int4* tile, int cap, const uint16_t* lrow, int nslots, bool packed, const double* mean,
-                                           const double* v0, double c1, double c2, double* gw) {
-  uint32_t nxt[kTrip];
-#pragma unroll
-  for (int u_ = 0; u_ < kTrip; ++u_) nxt[u_] = (kPreSlots + u_ < nslots) ? (uint32_t)lrow[(kPreSlots + u_) * kBlock] : kNoLoc;
-  for (int q0 = kPreSlots; q0 < nslots; q0 += kTrip) {
-    uint32_t l[kTrip];
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) l[u_] = nxt[u_];
-    if (packed && __all((int)(l[0] == kNoLoc))) break;
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) nxt[u_] = (q0 + kTrip + u_ < nslots) ? (uint32_t)lrow[(q0 + kTrip + u_) * kBlock] : kNoLoc;
-#pragma unroll
-    for (int u_ = 0; u_ < kTrip; ++u_) chain_term<PT, P>(tile, cap, l[u_], l[u_] != kNoLoc, mean, v0, c1, c2, gw);
-  }
-}
-
-// (Round 5, measured and dropped for float64 rows: loss AND dL/dw from ONE sweep.  t_j is bilinear in (1, cm) x d_j, so with
-//  A_k = sum c_kj u_j, B_k = sum c_kj (d_j . u_j), M_k = sum c_kj u_j d_j^T the second sweep collapses to
-//  c1 (v^T M_k v - (v . cm)(v . A_k)) - c2 (B_k - cm . A_k): every staged row read once, 64 B per neighbour instead of 96.  But the 26
-//  fp64 accumulators beside the moments cost the occupancy the LDS saving was meant to buy: 246 registers = two wavefronts per SIMD and
-//  101 us; held to 168 registers (three per SIMD) 117 us, against 69 us for the two sweeps at 126 registers.)
-// ---- wavefront sums through DPP -------------------------------------------------------------------------------------------
-// One 32-bit half of a double moved by a DPP row operation (quad permutes, rotations inside a row of 16 lanes)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  // (every lane has a source under these controls; bound_ctrl only spares the `old` operand its initialisation)
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-constexpr int kDppXor1 = 0xB1;      // quad_perm:[1,0,3,2]
-constexpr int kDppXor2 = 0x4E;      // quad_perm:[2,3,0,1]
-constexpr int kDppRor4 = 0x124;     // row_ror:4
-constexpr int kDppRor8 = 0x128;     // row_ror:8
-constexpr int kDppShl4 = 0x104;     // row_shl:4 (lane l reads lane l + 4 of its row)
-constexpr int kDppQuad3 = 0xFF;     // quad_perm:[3,3,3,3]
-// Four values per lane -> lane l < 4 of the wavefront holds the total of value bitrev2(l) (as wave_sum_packed<4>): two quad
-// steps that also halve what a lane carries, two rotations inside the rows, two cross-row exchanges.
-__device__ __forceinline__ double wave_sum4_dpp(double* v) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const bool up1 = (lane & 1) != 0, up2 = (lane & 2) != 0;
-  // bit 0: this lane keeps values {0, 1} (bit clear) or {2, 3} (bit set), the partner the others
-  const double k0 = up1 ? v[2] : v[0], g0 = up1 ? v[0] : v[2];
-  const double k1 = up1 ? v[3] : v[1], g1 = up1 ? v[1] : v[3];
-  const double a0 = k0 + dpp_f64<kDppXor1>(g0);
-  const double a1 = k1 + dpp_f64<kDppXor1>(g1);
-  // bit 1: keeps the first of its two (bit clear) or the second
-  const double kk = up2 ? a1 : a0, gg = up2 ? a0 : a1;
-  double r = kk + dpp_f64<kDppXor2>(gg);
-  r += dpp_f64<kDppRor4>(r);
-  r += dpp_f64<kDppRor8>(r);
-  r += __shfl_xor(r, 16, kWave);
-  r += __shfl_xor(r, 32, kWave);
-  return r;
-}
-
-// {sum loss, count} -> p_fwd columns, dL/dw -> p_bwd columns (same row stride: one row per wavefront), through one packed
-// wavefront reduction of the 2 + P values
-template <int P, bool DPP = false>
-__device__ __forceinline__ void step_partials(const double* acc2, const double* gw, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-                                              bool per_block = false, int n_front = 0) {
-  constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8;
-  __shared__ double s_comb[kWavesPerBlock][NP2];
-  double v[NP2];
-  v[0] = acc2[0]; v[1] = acc2[1];
-#pragma unroll
-  for (int k = 0; k < NP2 - 2; ++k) v[2 + k] = k < P ? gw[k] : 0.0;
-  double tot;
-  if constexpr (DPP && NP2 == 4) tot = wave_sum4_dpp(v);
-  else tot = wave_sum_packed<NP2>(v);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  int64_t rs = (int64_t)gridDim.x * kWavesPerBlock, row = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (per_block) {
-    // chained steps: one row per block (a quarter of the rows for the next launch's leading blocks to sum)
-    if (lane < NP2) s_comb[wave][lane] = tot;
-    __syncthreads();
-    if (wave != 0) return;
-    if (lane < NP2) tot = (s_comb[0][lane] + s_comb[1][lane]) + (s_comb[2][lane] + s_comb[3][lane]);
-    rs = (int64_t)gridDim.x - n_front;
-    row = (int64_t)blockIdx.x - n_front;
-  }
-  if (lane < NP2) {
-    const int q = packed_value_of_lane<NP2>(lane);
-    if (q < 2) p_fwd[q * rs + row] = tot;
-    else if (q < NV) p_bwd[(q - 2) * rs + row] = tot;
-  }
-}
-
-// partial rows: columns {sum loss, count} at p_fwd (stride gridDim * 4) and [0, P) dL/dw at p_bwd (same stride)
-template <typename PT, int NS, int P, int VAR = 0>
-__global__ __launch_bounds__(kBlock) void consistency_step_basis_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, int cap, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-    StepChain ch) {
-  extern __shared__ int4 tile[];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  __shared__ int s_ok;
-  __shared__ double s_front[kBlock / kWave];
-  const bool chained = ch.ready != nullptr;
-  if (chained && (int)blockIdx.x < ch.n_front) { chain_front_block<P>(ch, s_front); return; }
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  int64_t blk = chain_block_of(ch, chained, nblocks);
-  if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
-  double acc2[2] = {0.0, 0.0}, gw[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  const int32_t s0 = blk >= 0 ? tab.slot_ptr[blk] : 0;
-  bool bad = blk >= 0 && tab.slot_ptr[blk + 1] - s0 != NS;
-  if (blk >= 0 && !bad) {
-    const int64_t i = blk * kBlock + threadIdx.x;
-    const bool live = i < n;
-    const bool in_mask = live && (mask ? mask[i] != 0 : true);
-    const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-    uint32_t pre[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) pre[q] = (uint32_t)lrow[q * kBlock];
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    const int32_t own = (own_base && !centre_idx) ? own_base[blk] : -1;
-    double wq[P];
-    if (chained) {
-      // the weights of this launch come from its leading blocks: fetch the rows this lane stages (the first two: a block
-      // lists ~1.5 distinct rows per lane) BEFORE waiting for them, so that the wait hides behind the fetch or vice versa
-      // (a wait that never ends poisons the sums instead of hanging)
-      typename StepRow<PT, P>::Raw r0, r1;
-      const int t0 = threadIdx.x, t1 = threadIdx.x + kBlock;
-      if (t0 < nd) r0 = StepRow<PT, P>::fetch(pb, tab.blk_ids[base + t0]);
-      if (t1 < nd) r1 = StepRow<PT, P>::fetch(pb, tab.blk_ids[base + t1]);
-      chain_weights<P>(ch, pb.w_scale, s_w, &s_ok);
-      __syncthreads();
-      if (!s_ok) bad = true;
-#pragma unroll
-      for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      if (t0 < nd) StepRow<PT, P>::place(r0, wq, tile, cap, t0);
-      if (t1 < nd) StepRow<PT, P>::place(r1, wq, tile, cap, t1);
-      for (int t = threadIdx.x + 2 * kBlock; t < nd; t += kBlock) StepRow<PT, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-    } else {
-      stage_weights(pb, s_w);
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      for (int t = threadIdx.x; t < nd; t += kBlock) StepRow<PT, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-    }
-    typename Pt<PT>::Raw ci;
-    if (own < 0) ci = Basis<PT>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
-    __syncthreads();
-    if (own >= 0) ci = staged_point<PT>(tile, cap, own + (live ? (int)threadIdx.x : 0));
-    if (live && (!mask || __any((int)in_mask))) {        // (a wavefront of masked-out centres only: nothing to add, see consistency_step_q32_kernel)
-      CovAcc acc;
-      cov_init(acc);
-      uint32_t mx = pre[0];
-#pragma unroll
-      for (int q = 1; q < NS; ++q) mx = max(mx, pre[q]);
-      const bool any_miss = __any((int)(mx == kNoLoc)) != 0;
-      int n_have;
-      if (any_miss) n_have = gather_fixed<PT, NS, true>(tile, cap, ci, pre, acc);
-      else n_have = gather_fixed<PT, NS, false>(tile, cap, ci, pre, acc);
-      acc.W = (double)n_have;
-      double cm[3], v0[3], c1, c2;
-      if constexpr ((VAR & kVarSlimTail) != 0) step_point2<PT, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
-      else step_point<PT>(acc, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
-      const double u = Pt<PT>::unit(qp);
-      if constexpr ((VAR & kVarF32Sweep) != 0 && std::is_same<PT, q32>::value) {
-        // second sweep in float32 (see chain_term_f32); the lane's sums join the fp64 reduction
-        float cmf[3], vs[3], vu[3], gwf[P];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1 * v0[a]); vu[a] = (float)v0[a]; }
-        const float c2f = (float)c2;
-#pragma unroll
-        for (int k = 0; k < P; ++k) gwf[k] = 0.0f;
-        // (groups of four with a scheduling fence between them: left alone, the compiler requests all 2 NS row pieces up
-        // front -- 80 registers -- and the kernel drops from 6 to 4 wavefronts per SIMD)
-        if (any_miss) {
-#pragma unroll
-          for (int q = 0; q < NS; ++q) {
-            if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-            chain_term_f32<P>(tile, cap, pre[q], pre[q] != kNoLoc, ci, cmf, vs, vu, c2f, gwf);
-          }
-        } else {
-#pragma unroll
-          for (int q = 0; q < NS; ++q) {
-            if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-            chain_term_f32<P>(tile, cap, pre[q], true, ci, cmf, vs, vu, c2f, gwf);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k] * u;
-      } else {
-        double mean[3];
-        StepRow<PT, P>::mean_of(ci, cm, mean);
-        // second sweep over the same slots (full wavefronts skip the validity selects)
-        if (any_miss) {
-#pragma unroll
-          for (int q = 0; q < NS; ++q) chain_term<PT, P>(tile, cap, pre[q], pre[q] != kNoLoc, mean, v0, c1, c2, gw);
-        } else {
-#pragma unroll
-          for (int q = 0; q < NS; ++q) chain_term<PT, P>(tile, cap, pre[q], true, mean, v0, c1, c2, gw);
-        }
-#pragma unroll
-        for (int k = 0; k < P; ++k) gw[k] *= u;            // differences were in grid steps
-      }
-    }
-  }
-  if (bad) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, (VAR & kVarDppSums) != 0>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
-}
-
-// ---- the one-pass kernel for q32 points and a fixed slot count: what a C2 step runs ----------------------------------------
-// Same table, same basis rows, same staged rows {x0 x1 x2 u0 | u1 u2 c0 c1 | c2} (StepRow<q32, P>) and same sums as
-// consistency_step_basis_kernel<q32, NS, P>; what differs is where the instructions go (the kernel issues VALU instructions
-// ~98 % of its time -- rocprofv3 SQ_ACTIVE_INST_VALU -- so its duration IS its instruction count, at one wave64 VALU instruction
-// per four cycles per SIMD whatever the type: tools/ubench/valu_rates.hip):
-//  * the tile is STATIC LDS of kStepQ32Cap rows: its address and the piece stride are immediates of the ds_read instructions and
-//    the table's 16-bit byte offset is the address register as it stands (dynamic LDS costs a v_add per row piece: 30 per centre);
-//  * the per-centre tail is step_point2 (eig3_smallest_unit: adjugate eigenvector, reciprocals with one Newton step, the
-//    deflation path only for needles);
-//  * the second sweep is float32 (the difference to the centre is an exact int32, u and c are float32 words, the per-centre
-//    factors are rounded once);
-//  * the wavefront sums go through DPP row operations.
-// A fp64-difference row format ({x - ref} as doubles: no int -> fp conversions in the sweeps, 80 instructions fewer) was measured
-// and dropped: 48-B rows make the kernel LDS-bound (SQ_LDS_IDX_ACTIVE 87 % of its duration, 56 % of it bank conflicts of the
-// random row reads: 61 us against 52).
-constexpr int kStepQ32Cap = 512;          // rows of the static LDS tile (16 KB + 8 KB for a third piece: six blocks per CU); a second
-                                          // instantiation takes 768 rows (24 KB: still six blocks per CU for one or two weights); tables with
-                                          // more distinct rows per block take consistency_step_basis_kernel
-
-// second sweep, one neighbour (float32): gw[k] += c_kj (c1 (v . e_j)(v . u_j) - c2 (e_j . u_j)); vs = c1 v0, vu = v0
-typedef float float2v __attribute__((ext_vector_type(2)));
-template <int P, int CAP>
-__device__ __forceinline__ void chain_term_q32(const int4* tile, uint32_t off, bool have, const Pt<q32>::Raw& ci, const float* cmf, const float* vs,
-                                               const float* vu, float c2f, float* gw) {
-  const char* row = reinterpret_cast<const char*>(tile) + (have ? off : 0u);
-  const int4 p0 = *reinterpret_cast<const int4*>(row);
-  const int4 p1 = *reinterpret_cast<const int4*>(row + (size_t)CAP * 16);
-  // (two-wide float operations where the operands already sit in neighbouring registers: v_pk_add_f32 / v_pk_fma_f32 issue two
-  //  operations in one slot)
-  const float2v e01 = float2v{(float)(p0.x - ci.v[0]), (float)(p0.y - ci.v[1])} - float2v{cmf[0], cmf[1]};
-  const float e0 = e01.x, e1 = e01.y, e2 = (float)(p0.z - ci.v[2]) - cmf[2];
-  const float u0 = __int_as_float(p0.w), u1 = __int_as_float(p1.x), u2 = __int_as_float(p1.y);
-  const float al = fmaf(vs[2], e2, fmaf(vs[1], e1, vs[0] * e0));                       // c1 (v . e_j)
-  const float be = fmaf(vu[2], u2, fmaf(vu[1], u1, vu[0] * u0));                       // v . u_j
-  const float ga = fmaf(e2, u2, fmaf(e1, u1, e0 * u0));                                // e_j . u_j
-  float tj = fmaf(al, be, -(c2f * ga));
-  if (!have) tj = 0.0f;
-  if constexpr (P == 2) {
-    float2v g = float2v{gw[0], gw[1]};
-    g = __builtin_elementwise_fma(float2v{tj, tj}, float2v{__int_as_float(p1.z), __int_as_float(p1.w)}, g);
-    gw[0] = g.x; gw[1] = g.y;
-  } else {
-    gw[0] = fmaf(tj, __int_as_float(p1.z), gw[0]);
-    if constexpr (P > 1) gw[1] = fmaf(tj, __int_as_float(p1.w), gw[1]);
-    if constexpr (P > 2) gw[2] = fmaf(tj, __int_as_float(reinterpret_cast<const int4*>(row + (size_t)CAP * 32)->x), gw[2]);
-  }
-}
-
-// (six wavefronts per SIMD: left alone the kernel takes 81 VGPRs -- one allocation granule over the 80 of six wavefronts, i.e. FIVE per SIMD;
-//  at 79 + 12 B of scratch a step takes 44.4 instead of 47.2 us.  Seven -- 71 VGPRs, 44 B of scratch -- take 50.9 us.)
-// Diagnostic build only (-DDC_BLOCK_TRACE, tools/block_trace.py): every block of the two one-pass step kernels records where and
-// when it ran -- {XCC | HW_ID, start, end} on the 100 MHz constant clock -- so that the schedule of a launch can be drawn (which
-// CU got how many blocks, when each CU ran dry).  The product library is built without it: the macros expand to nothing.
-#ifdef DC_BLOCK_TRACE
-__device__ unsigned long long* g_block_trace = nullptr;
-#define DC_TRACE_BEGIN() const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime()
-#define DC_TRACE_END() do { if (threadIdx.x == 0 && g_block_trace) { \
-    unsigned long long* tr_ = g_block_trace + 4 * (size_t)blockIdx.x; \
-    tr_[0] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4); \
-    tr_[1] = trace_t0; tr_[2] = __builtin_amdgcn_s_memrealtime(); tr_[3] = 1; } } while (0)
-#else
-#define DC_TRACE_BEGIN() do {} while (0)
-#define DC_TRACE_END() do {} while (0)
-#endif
-
-template <int NS, int P, int CAP>
-__global__ __launch_bounds__(kBlock, (StepRow<q32, P>::kPieces * CAP * 16 <= 25 * 1024 ? 6 : 4)) void consistency_step_q32_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-    StepChain ch) {
-  constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8;
-  constexpr int cap = CAP;
-  __shared__ int4 tile[StepRow<q32, P>::kPieces * CAP];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  __shared__ double s_front[kWavesPerBlock];
-  __shared__ double s_comb[kWavesPerBlock * NP2];
-  __shared__ int s_ok[2];
-  DC_TRACE_BEGIN();
-  const bool chained = ch.ready != nullptr;
-  if (chained && (int)blockIdx.x < ch.n_front) { chain_front_block<P>(ch, s_front); return; }
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  int64_t blk = chain_block_of(ch, chained, nblocks);
-  if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
-  double acc2[2] = {0.0, 0.0}, gw[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  const int32_t s0 = blk >= 0 ? tab.slot_ptr[blk] : 0;
-  bool bad = blk >= 0 && tab.slot_ptr[blk + 1] - s0 != NS;
-  if (blk >= 0 && !bad) {
-    const int64_t i = blk * kBlock + threadIdx.x;
-    const bool live = i < n;
-    const bool in_mask = live && (mask ? mask[i] != 0 : true);
-    const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-    uint32_t pre[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) pre[q] = (uint32_t)lrow[q * kBlock];
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    const int32_t own = (own_base && !centre_idx) ? own_base[blk] : -1;
-    double wq[P];
-    if (chained) {
-      // fetch the rows this lane stages before waiting for the weights of this launch (consistency_step_basis_kernel)
-      typename StepRow<q32, P>::Raw r0, r1;
-      const int t0 = threadIdx.x, t1 = threadIdx.x + kBlock;
-      if (t0 < nd) r0 = StepRow<q32, P>::fetch(pb, tab.blk_ids[base + t0]);
-      if (t1 < nd) r1 = StepRow<q32, P>::fetch(pb, tab.blk_ids[base + t1]);
-      chain_weights<P>(ch, pb.w_scale, s_w, s_ok);
-      __syncthreads();
-      if (!s_ok[0]) bad = true;
-#pragma unroll
-      for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      if (t0 < nd) StepRow<q32, P>::place(r0, wq, tile, cap, t0);
-      if (t1 < nd) StepRow<q32, P>::place(r1, wq, tile, cap, t1);
-      for (int t = threadIdx.x + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-    } else {
-      stage_weights(pb, s_w);
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      for (int t = threadIdx.x; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-    }
-    Pt<q32>::Raw ci;
-    if (own < 0) ci = Basis<q32>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
-    __syncthreads();
-    if (own >= 0) ci = staged_point<q32>(tile, cap, own + (live ? (int)threadIdx.x : 0));
-    // a wavefront whose centres are ALL outside the loss mask adds nothing to the loss, the count or dL/dw (every term carries the
-    // centre's mask): it has staged its rows and is done.  The plan groups masked-out points at the end of every block, so
-    // these are whole wavefronts (bench.py reports their share).
-    if (live && (!mask || __any((int)in_mask))) {
-      CovAcc acc;
-      cov_init(acc);
-      // positions are multiples of 16, the empty-slot mark 0xFFFF is not: bit 0 of the OR of a lane's positions tells
-      uint32_t mo = pre[0];
-#pragma unroll
-      for (int q = 1; q < NS; ++q) mo |= pre[q];
-      const bool any_miss = __any((int)(mo & 1u)) != 0;
-      int n_have;
-      if (any_miss) n_have = gather_fixed<q32, NS, true>(tile, cap, ci, pre, acc);
-      else n_have = gather_fixed<q32, NS, false>(tile, cap, ci, pre, acc);
-      acc.W = (double)n_have;
-      double cm[3], v0[3], c1, c2;
-      step_point2<q32, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
-      float cmf[3], vs[3], vu[3], gwf[P];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1 * v0[a]); vu[a] = (float)v0[a]; }
-      const float c2f = (float)c2;
-#pragma unroll
-      for (int k = 0; k < P; ++k) gwf[k] = 0.0f;
-      // (groups of four with a scheduling fence between them: left alone, the compiler requests every row piece up front
-      // and the kernel loses wavefronts per SIMD to the registers)
-      if (any_miss) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-          if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-          chain_term_q32<P, CAP>(tile, pre[q], pre[q] != kNoLoc, ci, cmf, vs, vu, c2f, gwf);
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-          if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-          chain_term_q32<P, CAP>(tile, pre[q], true, ci, cmf, vs, vu, c2f, gwf);
-        }
-      }
-      const double u = qp.scale;
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k] * u;          // differences were in grid steps
-    }
-  }
-  if (bad) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  // ---- {sum loss, count, dL/dw} of the wavefront (one row per wavefront; chained: per block), as step_partials
-  double v[NP2];
-  v[0] = acc2[0]; v[1] = acc2[1];
-#pragma unroll
-  for (int k = 0; k < NP2 - 2; ++k) v[2 + k] = k < P ? gw[k] : 0.0;
-  double tot;
-  if constexpr (NP2 == 4) tot = wave_sum4_dpp(v);
-  else tot = wave_sum_packed<NP2>(v);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  int64_t rs = (int64_t)gridDim.x * kWavesPerBlock, row = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (chained) {
-    if (lane < NP2) s_comb[wave * NP2 + lane] = tot;
-    __syncthreads();
-    if (wave != 0) return;
-    if (lane < NP2) tot = (s_comb[lane] + s_comb[NP2 + lane]) + (s_comb[2 * NP2 + lane] + s_comb[3 * NP2 + lane]);
-    rs = (int64_t)gridDim.x - ch.n_front;
-    row = (int64_t)blockIdx.x - ch.n_front;
-  }
-  if (lane < NP2) {
-    const int q = packed_value_of_lane<NP2>(lane);
-    if (q < 2) p_fwd[q * rs + row] = tot;
-    else if (q < NV) p_bwd[(q - 2) * rs + row] = tot;
-  }
-  DC_TRACE_END();
-}
-
-// the same for any slot count (radius neighbourhoods): run-time slot loops, as consistency_fwd_basis_slots_kernel
-template <typename PT, int P>
-__global__ __launch_bounds__(kBlock) void consistency_step_basis_slots_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, int cap, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-    StepChain ch, int packed) {
-  extern __shared__ int4 tile[];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  __shared__ int s_ok;
-  __shared__ double s_front[kBlock / kWave];
-  const bool chained = ch.ready != nullptr;
-  if (chained && (int)blockIdx.x < ch.n_front) { chain_front_block<P>(ch, s_front); return; }
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  int64_t blk = xcd_block_of((int64_t)blockIdx.x - (chained ? ch.n_front : 0), nblocks);
-  if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
-  double acc2[2] = {0.0, 0.0}, gw[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  const int64_t i = blk * kBlock + threadIdx.x;
-  const bool live = blk >= 0 && i < n;
-  int32_t nslots = 0, own = -1, base = 0, nd = 0;
-  const uint16_t* lrow = tab.loc;
-  uint32_t pre[kPreSlots];
-  if (blk >= 0) {
-    const int32_t s0 = tab.slot_ptr[blk];
-    nslots = tab.slot_ptr[blk + 1] - s0;
-    lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < kPreSlots; ++q) pre[q] = (live && q < nslots) ? (uint32_t)lrow[q * kBlock] : kNoLoc;
-    own = (own_base && !centre_idx) ? own_base[blk] : -1;
-    base = tab.blk_ptr[blk];
-    nd = tab.blk_ptr[blk + 1] - base;
-  }
-  double wq[P];
-  bool timed_out = false;
-  typename Pt<PT>::Raw ci;
-  if (chained) {                           // as in consistency_step_basis_kernel: fetch, wait for the weights, place
-    typename StepRow<PT, P>::Raw r0, r1;
-    const int t0 = threadIdx.x, t1 = threadIdx.x + kBlock;
-    if (t0 < nd) r0 = StepRow<PT, P>::fetch(pb, tab.blk_ids[base + t0]);
-    if (t1 < nd) r1 = StepRow<PT, P>::fetch(pb, tab.blk_ids[base + t1]);
-    chain_weights<P>(ch, pb.w_scale, s_w, &s_ok);
-    __syncthreads();
-    timed_out = !s_ok;
-#pragma unroll
-    for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-    if (t0 < nd) StepRow<PT, P>::place(r0, wq, tile, cap, t0);
-    if (t1 < nd) StepRow<PT, P>::place(r1, wq, tile, cap, t1);
-    for (int t = threadIdx.x + 2 * kBlock; t < nd; t += kBlock) StepRow<PT, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-  } else {
-    stage_weights(pb, s_w);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-    for (int t = threadIdx.x; t < nd; t += kBlock) StepRow<PT, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
-  }
-  if (blk >= 0 && own < 0) ci = Basis<PT>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
-  __syncthreads();
-  if (live) {
-    if (own >= 0) ci = staged_point<PT>(tile, cap, own + (int)threadIdx.x);
-    CovAcc acc;
-    cov_init(acc);
-    bool miss = false;
-#pragma unroll
-    for (int q = 0; q < kPreSlots; ++q) miss |= (q < nslots) && pre[q] == kNoLoc;
-    int n_have = 0;
-    if (__any((int)miss)) n_have = gather_slots<PT, true>(tile, cap, ci, pre, nslots, acc);
-    else n_have = gather_slots<PT, false>(tile, cap, ci, pre, nslots, acc);
-    if (nslots > kPreSlots) n_have += gather_tail<PT>(tile, cap, ci, lrow, nslots, packed != 0, acc);
-    acc.W = (double)n_have;
-    double cm[3], v0[3], c1, c2;
-    step_point2<PT, 2>(acc, n_have, false, mask ? mask[i] != 0 : true, lp, qp, acc2, cm, v0, &c1, &c2);
-    const double u = Pt<PT>::unit(qp);
-    if constexpr (std::is_same<PT, q32>::value) {
-      float cmf[3], vs[3], vu[3], gwf[P];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1 * v0[a]); vu[a] = (float)v0[a]; }
-      const float c2f = (float)c2;
-#pragma unroll
-      for (int k = 0; k < P; ++k) gwf[k] = 0.0f;
-#pragma unroll
-      for (int q = 0; q < kPreSlots; ++q)
-        if (q < nslots) chain_term_f32<P>(tile, cap, pre[q], pre[q] != kNoLoc, ci, cmf, vs, vu, c2f, gwf);
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k];
-      if (nslots > kPreSlots) chain_tail_f32<P>(tile, cap, lrow, nslots, packed != 0, ci, cmf, vs, vu, c2f, gw);
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] *= u;
-    } else {
-      double mean[3];
-      StepRow<PT, P>::mean_of(ci, cm, mean);
-#pragma unroll
-      for (int q = 0; q < kPreSlots; ++q)
-        if (q < nslots) chain_term<PT, P>(tile, cap, pre[q], pre[q] != kNoLoc, mean, v0, c1, c2, gw);
-      if (nslots > kPreSlots) chain_tail<PT, P>(tile, cap, lrow, nslots, packed != 0, mean, v0, c1, c2, gw);
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] *= u;
-    }
-  }
-  if (timed_out) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, true>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
-}
-
-// ---- the one-pass kernel for ball neighbourhoods on float32 clouds (round 4) ------------------------------------------------
-// The reference's default neighbourhood is a ball (nn_type = ball, nn_r = 0.25 m, config.py:187-189; 0.4 m in train_demo:61-63):
-// on voxel-filtered scans a row has 70-200 neighbours, so the time is the two sweeps over the slots, not the per-centre tail.
-// consistency_step_basis_slots_kernel spent ~58 VALU instructions per (centre, neighbour) pair at 0.65 of the issue peak; the
-// arithmetic needs ~40.  What went:
-//   * validity handling: an empty slot reads the lane's OWN row, whose difference to the centre is exactly zero -- one select on
-//     the 16-bit position instead of selects on every coordinate and a count; the number of neighbours is the row's length
-//     (dcBlockTable.row_ptr);
-//   * address arithmetic: the tile's row capacity is a template argument, so the second piece of a row is an immediate off the
-//     16-bit position;
-//   * the dependent {position load, row read} pair per slot: trips of eight, the next trip's positions requested before the
-//     rows of this one are read, and a wavefront stops at ITS longest row, not the block's;
-//   * the first-sixteen-slots special case (registers kept across the per-centre tail).
-// The second sweep accumulates float32 per trip and fp64 across trips.  Same sums as the slots kernel to the rounding of that
-// order of additions.
-template <int P, int CAP>
-__global__ __launch_bounds__(kBlock, (CAP <= 1024 ? 5 : 4)) void consistency_step_ragged_q32_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, const int32_t* __restrict__ row_ptr, int64_t n,
-    const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-    StepChain ch) {
-  using Row = StepRow<q32, P>;
-  extern __shared__ int4 tile[];                   // Row::kPieces * CAP rows of 16 B (dynamic: up to 128 KB, see ragged_launch)
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  __shared__ int s_ok;
-  __shared__ double s_front[kBlock / kWave];
-  DC_TRACE_BEGIN();
-  const bool chained = ch.ready != nullptr;
-  if (chained && (int)blockIdx.x < ch.n_front) { chain_front_block<P>(ch, s_front); return; }
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  int64_t blk = xcd_block_of((int64_t)blockIdx.x - (chained ? ch.n_front : 0), nblocks);
-  if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
-  double acc2[2] = {0.0, 0.0}, gw[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  const int64_t i = blk * kBlock + threadIdx.x;
-  const bool live = blk >= 0 && i < n;
-  int32_t nslots = 0, own = 0, base = 0, nd = 0, deg = 0;
-  const uint16_t* lrow = tab.loc;
-  uint32_t first[kTrip];
-  if (blk >= 0) {
-    const int32_t s0 = tab.slot_ptr[blk];
-    nslots = tab.slot_ptr[blk + 1] - s0;
-    lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-    if (live) deg = row_ptr[i + 1] - row_ptr[i];
-    own = own_base[blk];
-    base = tab.blk_ptr[blk];
-    nd = tab.blk_ptr[blk + 1] - base;
-  }
-  const uint32_t own_off = (uint32_t)(own + (int)threadIdx.x) * 16u;      // where padding slots point (and idle lanes read)
-#pragma unroll
-  for (int u_ = 0; u_ < kTrip; ++u_) first[u_] = (live && nslots > 0) ? (uint32_t)lrow[u_ * kBlock] : kNoLoc;     // (slot counts are multiples of 8)
-  double wq[P];
-  bool timed_out = false;
-  if (chained) {                           // as in consistency_step_basis_kernel: fetch, wait for the weights, place
-    typename Row::Raw r0, r1;
-    const int t0 = threadIdx.x, t1 = threadIdx.x + kBlock;
-    if (t0 < nd) r0 = Row::fetch(pb, tab.blk_ids[base + t0]);
-    if (t1 < nd) r1 = Row::fetch(pb, tab.blk_ids[base + t1]);
-    chain_weights<P>(ch, pb.w_scale, s_w, &s_ok);
-    __syncthreads();
-    timed_out = !s_ok;
-#pragma unroll
-    for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-    if (t0 < nd) Row::place(r0, wq, tile, CAP, t0);
-    if (t1 < nd) Row::place(r1, wq, tile, CAP, t1);
-    for (int t = threadIdx.x + 2 * kBlock; t < nd; t += kBlock) Row::stage(pb, wq, tab.blk_ids[base + t], tile, CAP, t);
-  } else {
-    stage_weights(pb, s_w);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-    for (int t = threadIdx.x; t < nd; t += kBlock) Row::stage(pb, wq, tab.blk_ids[base + t], tile, CAP, t);
-  }
-  __syncthreads();
-  const bool in_mask = live && (mask ? mask[i] != 0 : true);
-  if (live && (!mask || __any((int)in_mask))) {          // (a wavefront of masked-out centres only: nothing to add, see consistency_step_q32_kernel)
-    const char* tb = reinterpret_cast<const char*>(tile);
-    const Pt<q32>::Raw ci = Pt<q32>::from_row(reinterpret_cast<const int4*>(tb + own_off));
-    // the longest row among this wavefront's lanes bounds its trips
-    int wmax = deg;
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off, kWave));
-    wmax = __builtin_amdgcn_readfirstlane(min(wmax, nslots));      // (uniform: scalar loop control)
-    CovAcc acc;
-    cov_init(acc);
-    // one trip: the eight rows at positions l[] into the moments; the NEXT trip's positions (pn, immediates off one pointer) are
-    // requested first.  Slot counts are multiples of eight and the table ends with eight rows of slack: no guards.
-    auto sweep1 = [&](const uint32_t* l, uint32_t* nx, const uint16_t* pn) {
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_) nx[u_] = (uint32_t)pn[u_ * kBlock];
-      int4 r[kTrip];
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_) r[u_] = *reinterpret_cast<const int4*>(tb + (l[u_] == kNoLoc ? own_off : l[u_]));
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_)
-        cov_add_d(acc, (double)(r[u_].x - ci.v[0]), (double)(r[u_].y - ci.v[1]), (double)(r[u_].z - ci.v[2]));
-    };
-    {
-      uint32_t la[kTrip], lb[kTrip];
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_) la[u_] = first[u_];
-      const uint16_t* pn = lrow + kTrip * kBlock;
-      for (int q0 = 0; q0 < wmax; q0 += 2 * kTrip) {        // two trips per iteration: the position registers alternate, no moves
-        sweep1(la, lb, pn);
-        pn += kTrip * kBlock;
-        if (q0 + kTrip >= wmax) break;
-        sweep1(lb, la, pn);
-        pn += kTrip * kBlock;
-      }
-    }
-    acc.W = (double)deg;
-    double cm[3], v0[3], c1, c2;
-    step_point2<q32, 2>(acc, deg, false, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
-    const double u = Pt<q32>::unit(qp);
-    float cmf[3], vs[3], vu[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1 * v0[a]); vu[a] = (float)v0[a]; }
-    const float c2f = (float)c2;
-    // (two neighbours per packed float32 instruction: v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 do two lanes' worth of work in
-    // one issue slot -- the arithmetic of a neighbour's term drops from ~24 to ~15 instructions)
-    auto sweep2 = [&](const uint32_t* l, uint32_t* nx, const uint16_t* pn) {
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_) nx[u_] = (uint32_t)pn[u_ * kBlock];
-      float2v g[P];
-#pragma unroll
-      for (int k = 0; k < P; ++k) g[k] = float2v{0.0f, 0.0f};
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; u_ += 2) {
-        const bool ha = l[u_] != kNoLoc, hb = l[u_ + 1] != kNoLoc;      // (packed rows: the same as slot < deg)
-        const char* ra = tb + (ha ? l[u_] : own_off);
-        const char* rb = tb + (hb ? l[u_ + 1] : own_off);
-        const int4 a0 = *reinterpret_cast<const int4*>(ra), a1 = *reinterpret_cast<const int4*>(ra + CAP * 16);
-        const int4 b0 = *reinterpret_cast<const int4*>(rb), b1 = *reinterpret_cast<const int4*>(rb + CAP * 16);
-        const float2v e0 = float2v{(float)(a0.x - ci.v[0]), (float)(b0.x - ci.v[0])} - float2v{cmf[0], cmf[0]};
-        const float2v e1 = float2v{(float)(a0.y - ci.v[1]), (float)(b0.y - ci.v[1])} - float2v{cmf[1], cmf[1]};
-        const float2v e2 = float2v{(float)(a0.z - ci.v[2]), (float)(b0.z - ci.v[2])} - float2v{cmf[2], cmf[2]};
-        const float2v u0 = float2v{__int_as_float(a0.w), __int_as_float(b0.w)};
-        const float2v u1 = float2v{__int_as_float(a1.x), __int_as_float(b1.x)};
-        const float2v u2 = float2v{__int_as_float(a1.y), __int_as_float(b1.y)};
-        const float2v al = __builtin_elementwise_fma(float2v{vs[2], vs[2]}, e2, __builtin_elementwise_fma(float2v{vs[1], vs[1]}, e1, float2v{vs[0], vs[0]} * e0));
-        const float2v be = __builtin_elementwise_fma(float2v{vu[2], vu[2]}, u2, __builtin_elementwise_fma(float2v{vu[1], vu[1]}, u1, float2v{vu[0], vu[0]} * u0));
-        const float2v ga = __builtin_elementwise_fma(e2, u2, __builtin_elementwise_fma(e1, u1, e0 * u0));
-        float2v tj = __builtin_elementwise_fma(al, be, -(float2v{c2f, c2f} * ga));
-        tj = float2v{ha ? tj.x : 0.0f, hb ? tj.y : 0.0f};           // an empty slot (the lane's own row) is not a neighbour
-        g[0] = __builtin_elementwise_fma(tj, float2v{__int_as_float(a1.z), __int_as_float(b1.z)}, g[0]);
-        if constexpr (P > 1) g[1] = __builtin_elementwise_fma(tj, float2v{__int_as_float(a1.w), __int_as_float(b1.w)}, g[1]);
-        if constexpr (P > 2)
-          g[2] = __builtin_elementwise_fma(tj, float2v{__int_as_float(reinterpret_cast<const int4*>(ra + CAP * 32)->x),
-                                                       __int_as_float(reinterpret_cast<const int4*>(rb + CAP * 32)->x)}, g[2]);
-      }
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] += (double)(g[k].x + g[k].y);
-    };
-    {
-      uint32_t la[kTrip], lb[kTrip];
-#pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_) la[u_] = first[u_];
-      const uint16_t* pn = lrow + kTrip * kBlock;
-      for (int q0 = 0; q0 < wmax; q0 += 2 * kTrip) {
-        sweep2(la, lb, pn);
-        pn += kTrip * kBlock;
-        if (q0 + kTrip >= wmax) break;
-        sweep2(lb, la, pn);
-        pn += kTrip * kBlock;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) gw[k] *= u;
-  }
-  if (timed_out) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, true>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
-  DC_TRACE_END();
-}
-
-// ================================================================================================
-// Pose mode in ONE pass (round 4): loss, dL/dw AND dL/d[R|t] of every scan from one launch
-// ================================================================================================
-// train() with pose corrections (train.py:300-312, eval.py:68-82; scripts/model_poses_learning:71) moves the poses every
-// iteration, so the basis rows of the model-only step (X0 = R x + t) are stale after every step and the general path ran three
-// full passes: dc_points_fwd (22 us) -> forward writing a record per centre (46) -> backward over the transposed table with
-// per-scan sums (86; 113 in round 3).  Here one kernel does it:
-//   * LOCAL basis rows (dc_points_local_basis, once per exponent set): {d0, dir, c_k, scan} in the SENSOR frame -- 32 B, nothing
-//     in them depends on a pose.  Staging forms a row's world point with the CURRENT pose and weights: d' = d0 + sum w_k c_k,
-//     x = R_s (d' dir) + t_s on the q32 grid, u = R_s dir; the sweeps then run as in consistency_step_q32_kernel.
-//     The rows are stored PER BLOCK in the order of its list (24 B each, 1.75 x the points at C2; the scan of a row is a byte of
-//     dcPoseTable.row_scan): staging reads them as one contiguous, coalesced stream -- as gathers through the id list they cost
-//     two dependent memory latencies and ~2.3 cycles of the CU's address pipeline per row.
-//   * reverse mode INSIDE the block for the poses: in the second sweep every centre ADDS its edges' gradients
-//     g_ij = c1_i (v0_i . e) v0_i - c2_i e, e = x_j - mean_i, to the staged rows' sums in LDS (chain_term_pose: 64-bit integer
-//     atomics under a per-block power-of-two scale, so the order they land in does not matter).  Rows shared by several blocks
-//     get a partial sum in each; the sums over blocks are the reduction's.
-//   * the block's distinct rows are listed BY SCAN (dcPoseTable.ids: (scan, id) order, row_seg = where each scan starts), so
-//     dL/d[R|t]_s = (sum_j g_j (x_j - t_s)^T) R_s | sum_j g_j runs over a contiguous row range of the tile: eight lanes per scan,
-//     fixed order, one row of the row-major pose partials per block.  Bitwise reproducible like everything else.
-// 154 us of kernels in three launches -> one launch; see DESIGN 4 for the measured time.
-struct PoseTab {
-  const int32_t* __restrict__ blk_ptr;     // [blocks + 1], the forward table's
-  const int32_t* __restrict__ ids;         // distinct rows of every block in (scan, id) order
-  const uint16_t* __restrict__ loc;        // [blocks * K][256]: 16 x position in that order, 0xFFFF = empty slot
-  const uint16_t* __restrict__ own_pos;    // [N]: 16 x position of the point's own row in its block's list
-  const uint16_t* __restrict__ row_seg;    // [blocks][S + 1]: first row of every scan in the block's list; [S] = the row count
-  const uint8_t* __restrict__ row_scan;    // the scan of every listed row (parallel to ids)
-};
-constexpr int kPoseCap = 512;              // rows of the static tile (the table builder refuses blocks with longer lists)
-
-// Per block: (scan, id) order of its distinct rows, remapped positions, own positions.  info[0] <- 1 when a
-// block cannot take the pose kernel (more than kPoseCap rows, or a block whose list misses one of its own rows).
-template <int K>
-__global__ __launch_bounds__(kBlock) void pose_table_kernel(BlockTab tab, const int32_t* __restrict__ own_base,
-                                                            const int32_t* __restrict__ scan_id, int64_t n, int n_scans,
-                                                            int32_t* __restrict__ ids_out, uint16_t* __restrict__ loc_out,
-                                                            uint16_t* __restrict__ own_pos, uint16_t* __restrict__ row_seg,
-                                                            uint8_t* __restrict__ row_scan, int32_t* __restrict__ info) {
-  __shared__ int32_t s_id[kPoseCap];
-  __shared__ uint8_t s_scan[kPoseCap];
-  __shared__ uint16_t s_new[kPoseCap];
-  __shared__ int s_start[kMaxBlockScans + 1];
-  const int64_t b = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int32_t base = tab.blk_ptr[b], nd = tab.blk_ptr[b + 1] - base;
-  const int32_t own = own_base[b];
-  if (nd > kPoseCap || own < 0 || tab.slot_ptr[b + 1] - tab.slot_ptr[b] != K) {        // block-uniform
-    if (tid == 0) atomicMax(info, 1);
-    return;
-  }
-  if (tid <= n_scans) s_start[tid] = 0;
-  __syncthreads();
-  for (int t = tid; t < nd; t += kBlock) {
-    const int32_t id = tab.blk_ids[base + t];
-    const int sc = scan_id ? scan_id[id] : 0;
-    s_id[t] = id;
-    s_scan[t] = (uint8_t)sc;
-    atomicAdd(&s_start[sc + 1], 1);                      // histogram, shifted by one for the prefix
-  }
-  __syncthreads();
-  if (tid == 0) for (int q = 0; q < n_scans; ++q) s_start[q + 1] += s_start[q];
-  __syncthreads();
-  for (int t = tid; t < nd; t += kBlock) {
-    const int sc = s_scan[t];
-    int rank = 0;
-    for (int t2 = 0; t2 < t; ++t2) rank += s_scan[t2] == sc ? 1 : 0;      // stable: ascending id inside a scan
-    const int p = s_start[sc] + rank;
-    s_new[t] = (uint16_t)p;
-    ids_out[base + p] = s_id[t];
-    row_scan[base + p] = (uint8_t)sc;
-  }
-  if (tid <= n_scans) row_seg[b * (n_scans + 1) + tid] = (uint16_t)s_start[tid];
-  __syncthreads();
-  const int64_t i = b * kBlock + tid;
-  if (i < n) own_pos[i] = (uint16_t)(s_new[own + tid] << 4);
-  const uint16_t* lrow = tab.loc + (int64_t)tab.slot_ptr[b] * kBlock + tid;
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-    const uint16_t l = lrow[q * kBlock];
-    loc_out[((int64_t)b * K + q) * kBlock + tid] = l == 0xFFFF ? (uint16_t)0xFFFF : (uint16_t)(s_new[l >> 4] << 4);
-  }
-}
-
-// {d0, dir, c_0, c_1}: the pose-independent part of a ray (sensor frame; viewpoints at the sensor origin), 6 words.  One workgroup
-// per block of the pose table writes the rows of the block's list, in its order, at rows [blk_ptr[b], blk_ptr[b + 1]).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void points_local_basis_kernel(PointInputs in, PoseTab tab, int32_t* __restrict__ rows) {
-  const int64_t b = blockIdx.x;
-  const int32_t base = tab.blk_ptr[b], nd = tab.blk_ptr[b + 1] - base;
-  ModelParams mp;
-  load_model(in, mp);
-  for (int t = threadIdx.x; t < nd; t += kBlock) {
-    const int64_t i = tab.ids[base + t];
-    const T* dp = (const T*)in.dirs + i * 3;
-    const double d = (double)((const T*)in.depth)[i];
-    const bool lm = in.lmask ? in.lmask[i] != 0 : true;
-    const bool on = mp.kind != DC_MODEL_NONE && lm;
-    const double inc = on ? (double)((const T*)in.inc)[i] : 0.0;
-    const double d0 = (on && mp.kind == DC_MODEL_LINEAR) ? 0.0 : d;
-    float c[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (k < mp.n_terms && on) {
-        const double dk = mp.kind > DC_MODEL_SCALED_POLYNOMIAL ? model_dw_other(mp, k, d, inc)
-                                                               : (mp.kind == DC_MODEL_SCALED_POLYNOMIAL ? -d : -1.0) * pow_term(inc, mp.e[k]);
-        c[k] = (float)dk;
-      }
-    }
-    int2* r = reinterpret_cast<int2*>(rows) + 3 * (int64_t)(base + t);
-    r[0] = make_int2(__float_as_int((float)d0), __float_as_int((float)dp[0]));
-    r[1] = make_int2(__float_as_int((float)dp[1]), __float_as_int((float)dp[2]));
-    r[2] = make_int2(__float_as_int(c[0]), __float_as_int(c[1]));
-  }
-}
-
-// second sweep of the pose kernel, one neighbour: chain_term_q32 plus the edge's gradient g_ij = al v0 - c2 e_j ADDED to the
-// neighbour's row of the block's gradient planes.  The sums are 64-bit integers, so the order the wavefronts' LDS atomics land in
-// does not matter (bit-reproducible); the coefficients arrive scaled by the block's power of two S with |g_ij| S < 2^50, and
-// double(g) + 1.5 2^52 holds round(g) in its mantissa: the bit pattern minus that of 1.5 2^52 (low word zero) IS the integer.
-template <int P, int CAP>
-__device__ __forceinline__ void chain_term_pose(const int4* tile, unsigned long long* s_g, uint32_t off, bool have, const Pt<q32>::Raw& ci,
-                                                const float* cmf, const float* vs, const float* vu, float c2f, float* gw) {
-  const char* row = reinterpret_cast<const char*>(tile) + (have ? off : 0u);
-  const int4 p0 = *reinterpret_cast<const int4*>(row);
-  const int4 p1 = *reinterpret_cast<const int4*>(row + (size_t)CAP * 16);
-  const float2v e01 = float2v{(float)(p0.x - ci.v[0]), (float)(p0.y - ci.v[1])} - float2v{cmf[0], cmf[1]};
-  const float e0 = e01.x, e1 = e01.y, e2 = (float)(p0.z - ci.v[2]) - cmf[2];
-  const float u0 = __int_as_float(p0.w), u1 = __int_as_float(p1.x), u2 = __int_as_float(p1.y);
-  const float al = fmaf(vs[2], e2, fmaf(vs[1], e1, vs[0] * e0));                       // c1 (v . e_j)
-  const float g0 = fmaf(al, vu[0], -(c2f * e0)), g1 = fmaf(al, vu[1], -(c2f * e1)), g2 = fmaf(al, vu[2], -(c2f * e2));
-  float tj = fmaf(g2, u2, fmaf(g1, u1, g0 * u0));                                      // g_ij . u_j
-  if (!have) tj = 0.0f;
-  if constexpr (P == 2) {
-    float2v g = float2v{gw[0], gw[1]};
-    g = __builtin_elementwise_fma(float2v{tj, tj}, float2v{__int_as_float(p1.z), __int_as_float(p1.w)}, g);
-    gw[0] = g.x; gw[1] = g.y;
-  } else {
-    gw[0] = fmaf(tj, __int_as_float(p1.z), gw[0]);
-  }
-  if (have) {
-    constexpr double kMagic = 6755399441055744.0;                                      // 1.5 2^52
-    unsigned long long* cell = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s_g) + (off >> 1));
-    const float gg[3] = {g0, g1, g2};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const unsigned long long bits = (unsigned long long)__double_as_longlong((double)gg[a] + kMagic) - 0x4338000000000000ull;
-      atomicAdd(cell + a * CAP, bits);
-    }
-  }
-}
-
-// Pose-mode evaluation in ONE launch (float32 sequences, [rows, K] tables, no exponent gradients).  A block stages its distinct
-// rows from the pose-independent local basis rows {d0, dir, c0, c1, scan} with the CURRENT poses and weights, runs the step kernel's
-// two sweeps, and in the second sweep every centre adds its edges' gradients to the block's per-row gradient planes in LDS
-// (chain_term_pose); the rows of one scan are contiguous in the block's list (dc_pose_table_build), so dL/d[R|t]_s of the block
-// is a sum over a row range: one row [12 S] of the row-major pose partials per block, summed by reduce_eval_kernel.
-template <int NS, int P>
-__global__ __launch_bounds__(kBlock, 4) void consistency_step_pose_kernel(
-    const int32_t* __restrict__ lrows, PoseTab tab, const double* __restrict__ poses, int n_scans, const double* __restrict__ w,
-    int64_t n, const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd) {
-  constexpr int CAP = kPoseCap;
-  __shared__ int4 tile[2 * CAP];                            // piece 0 {X, u0} | piece 1 {u1, u2, c0, c1}
-  __shared__ unsigned long long s_g[3 * CAP];               // three planes: the rows' gradient sums (64-bit integers)
-  __shared__ double s_pose[kLdsScans * 12];
-  __shared__ float s_bound[kWavesPerBlock];
-  const int tid = threadIdx.x;
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  const int64_t blk = xcd_block(nblocks);
-  // one partial row per block in every column: {sum loss, count} at p_fwd, dL/dw, zeros for dL/de, the 12 S pose sums at p_bwd.  The
-  // eight rows of a 64-byte line are blocks of ONE XCD (blockIdx & 7), so the line is completed in that XCD's L2, and the
-  // reduction reads every column as one contiguous run.
-  const int64_t rs = (int64_t)gridDim.x;
-  double* pcol = p_bwd + 2 * P * rs + (int64_t)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  double acc2[2] = {0.0, 0.0}, gw[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  if (blk < 0) {                                            // padding block of the last round (block-uniform): zero rows
-    for (int item = tid; item < 12 * n_scans; item += kBlock) pcol[item * rs] = 0.0;
-  } else {
-    for (int t = tid; t < n_scans * 12; t += kBlock) s_pose[t] = poses[t];
-    double wq[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) wq[k] = w[k];
-    const int64_t i = blk * kBlock + tid;
-    const bool live = i < n;
-    const bool in_mask = live && (mask ? mask[i] != 0 : true);
-    const uint16_t* lrow = tab.loc + (blk * NS) * kBlock + tid;
-    uint32_t pre[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) pre[q] = live ? (uint32_t)lrow[q * kBlock] : kNoLoc;
-    const uint32_t own = live ? (uint32_t)tab.own_pos[i] : 0u;
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    // the (at most two) rows this thread stages, in flight before anything else: the block's rows are one contiguous stream
-    static_assert(CAP == 2 * kBlock, "two staged rows per thread");
-    int2 rw[2][3];
-    int rsc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = tid + j * kBlock < nd ? tid + j * kBlock : 0;
-      const int2* src = reinterpret_cast<const int2*>(lrows) + 3 * (int64_t)(base + t);
-      rw[j][0] = src[0]; rw[j][1] = src[1]; rw[j][2] = src[2];
-      rsc[j] = tab.row_scan[base + t];
-    }
-    for (int t = tid; t < 3 * CAP; t += kBlock) s_g[t] = 0ull;
-    __syncthreads();                                        // the poses are in LDS
-    // ---- staging: the world point of every distinct row from its local basis row, the current pose and weights ----
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = tid + j * kBlock;
-      if (t >= nd) continue;
-      const float c0 = __int_as_float(rw[j][2].x), c1f = __int_as_float(rw[j][2].y);
-      const int sc = rsc[j];
-      double dp = (double)__int_as_float(rw[j][0].x) + wq[0] * (double)c0;
-      if constexpr (P > 1) dp += wq[1] * (double)c1f;
-      const double dl[3] = {(double)__int_as_float(rw[j][0].y), (double)__int_as_float(rw[j][1].x), (double)__int_as_float(rw[j][1].y)};
-      const double* Tp = s_pose + sc * 12;
-      double u[3], x[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        u[a] = Tp[4 * a] * dl[0] + Tp[4 * a + 1] * dl[1] + Tp[4 * a + 2] * dl[2];
-        x[a] = Tp[4 * a + 3] + dp * u[a];
-      }
-      tile[t] = make_int4(quantize(x[0], qp.origin[0], qp.inv_scale, qp.flag), quantize(x[1], qp.origin[1], qp.inv_scale, qp.flag),
-                          quantize(x[2], qp.origin[2], qp.inv_scale, qp.flag), __float_as_int((float)u[0]));
-      tile[CAP + t] = make_int4(__float_as_int((float)u[1]), __float_as_int((float)u[2]), rw[j][2].x, rw[j][2].y);
-    }
-    __syncthreads();
-    // ---- the centre: moments, smallest eigenpair, loss (as consistency_step_q32_kernel) and a bound of its edges' gradients ----
-    const bool work = live && (!mask || __any((int)in_mask));
-    Pt<q32>::Raw ci;
-    double cm[3] = {0.0, 0.0, 0.0}, v0[3] = {0.0, 0.0, 0.0}, c1 = 0.0, c2 = 0.0;
-    float bound = 0.0f;
-    if (work) {
-      const char* tb = reinterpret_cast<const char*>(tile);
-      ci = Pt<q32>::from_row(reinterpret_cast<const int4*>(tb + own));
-      CovAcc acc;
-      cov_init(acc);
-      uint32_t mo = pre[0];
-#pragma unroll
-      for (int q = 1; q < NS; ++q) mo |= pre[q];
-      const bool any_miss = __any((int)(mo & 1u)) != 0;
-      int n_have;
-      if (any_miss) n_have = gather_fixed<q32, NS, true>(tile, CAP, ci, pre, acc);
-      else n_have = gather_fixed<q32, NS, false>(tile, CAP, ci, pre, acc);
-      acc.W = (double)n_have;
-      double se2;
-      step_point2<q32, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2, &se2);
-      // |g_ij| <= (|c1| + |c2|) |e_j| and |e_j|^2 <= sum_j |e_j|^2 (at least one grid unit, so that c S stays finite)
-      const float r = sqrtf((float)se2);
-      bound = (float)(fabs(c1) + fabs(c2)) * (r > 1.0f ? r : 1.0f);
-    }
-    bound = bound == bound ? bound : INFINITY;              // a NaN coefficient poisons the block's sums like an infinite one
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o, kWave));
-    if ((tid & (kWave - 1)) == 0) s_bound[tid / kWave] = bound;
-    __syncthreads();
-    bound = s_bound[0];
-#pragma unroll
-    for (int q = 1; q < kWavesPerBlock; ++q) bound = fmaxf(bound, s_bound[q]);
-    const bool poisoned = !(bound < INFINITY);              // block-uniform
-    int sh = 0;
-    if (bound > 0.0f && !poisoned) {
-      int ex;
-      (void)frexpf(bound, &ex);                             // bound < 2^ex
-      sh = 50 - ex;
-      sh = sh > 100 ? 100 : sh;
-    }
-    const double S = ldexp(1.0, sh), invS = ldexp(1.0, -sh);
-    // ---- second sweep: dL/dw of the centre, and its edges' gradients into the rows' planes ----
-    if (work && !poisoned) {
-      float cmf[3], vs[3], vu[3], gwf[P];
-      const double c1s = c1 * S;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1s * v0[a]); vu[a] = (float)v0[a]; }
-      const float c2f = (float)(c2 * S);
-#pragma unroll
-      for (int k = 0; k < P; ++k) gwf[k] = 0.0f;
-      if (__any((int)(c1 != 0.0 || c2 != 0.0))) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-          if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-          chain_term_pose<P, CAP>(tile, s_g, pre[q], pre[q] != kNoLoc && (c1 != 0.0 || c2 != 0.0), ci, cmf, vs, vu, c2f, gwf);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k] * (qp.scale * invS);
-    }
-    __syncthreads();                                        // every edge has been added
-    // ---- dL/d[R|t]_s = sum_j g_j (x) [x_local_j, 1] over the rows of scan s, contiguous in the block's list.  With
-    //      x_local = R^T (x - t) the sum is (sum_j g_j (x_j - t)^T) R: eight lanes per scan (n_scans <= 32) take every eighth row
-    //      each and sum g (x) q and g over them -- q the row's grid coordinates, g its three integer sums, all in LDS -- the eight
-    //      lanes' twelve sums are added by DPP quad / row operations that also halve what a lane carries (as wave_sum4_dpp), and
-    //      lanes 0..2 of the eight finish row a of [dL/dR | dL/dt] with the scan's pose ----
-    {
-      const uint16_t* seg = tab.row_seg + blk * (n_scans + 1);
-      const int sc = tid >> 3, part = tid & 7;
-      const bool mine = sc < n_scans;
-      const int end = mine ? (int)seg[sc + 1] : 0;
-      // slot (p & 1) 6 + (p >> 1) 3 + c ends on lane p of the eight: lanes 0..2 get {sum g_a q_c}, a = p; lane 3 {sum g_a}
-      double sacc[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) sacc[q] = 0.0;
-      for (int p = mine ? (int)seg[sc] + part : 0; p < end; p += 8) {
-        const int4 xr = tile[p];
-        const double qd[3] = {(double)xr.x, (double)xr.y, (double)xr.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const unsigned long long bits = s_g[a * CAP + p];
-          const double g = fma((double)(int)(uint32_t)(bits >> 32), 4294967296.0, (double)(uint32_t)bits);
-#pragma unroll
-          for (int c = 0; c < 3; ++c) sacc[(a & 1) * 6 + (a >> 1) * 3 + c] = fma(g, qd[c], sacc[(a & 1) * 6 + (a >> 1) * 3 + c]);
-          sacc[9 + a] += g;                                 // lane 3: (3 & 1) 6 + (3 >> 1) 3 = 9
-        }
-      }
-      const bool up1 = (part & 1) != 0, up2 = (part & 2) != 0;
-      double h[6], r3[3], gs[3];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) h[q] = (up1 ? sacc[6 + q] : sacc[q]) + dpp_f64<kDppXor1>(up1 ? sacc[q] : sacc[6 + q]);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        r3[q] = (up2 ? h[3 + q] : h[q]) + dpp_f64<kDppXor2>(up2 ? h[q] : h[3 + q]);
-        r3[q] += dpp_f64<kDppShl4>(r3[q]);                  // lanes 0..3 of the eight: + lanes 4..7
-        gs[q] = dpp_f64<kDppQuad3>(r3[q]);                  // {sum g_a} from lane 3 of the quad
-      }
-      if (mine && part < 3) {
-        const double unscale = qp.scale * invS;             // the block's gradient unit
-        const double* Tp = s_pose + sc * 12;
-        const double ga = (part == 0 ? gs[0] : (part == 1 ? gs[1] : gs[2])) * unscale;
-        double m[3];                                        // row a of sum_j g_j (x_j - t)^T
-#pragma unroll
-        for (int c = 0; c < 3; ++c) m[c] = fma(r3[c] * unscale, qp.scale, ga * (qp.origin[c] - Tp[4 * c + 3]));
-        double* dst = pcol + (sc * 12 + part * 4) * rs;
-#pragma unroll
-        for (int b2 = 0; b2 < 3; ++b2) {
-          const double v = fma(m[2], Tp[8 + b2], fma(m[1], Tp[4 + b2], m[0] * Tp[b2]));
-          dst[b2 * rs] = poisoned ? (double)NAN : v;
-        }
-        dst[3 * rs] = poisoned ? (double)NAN : ga;
-      }
-    }
-  }
-  // {sum loss, count, dL/dw} of the wavefront; the exponent-gradient columns [P, 2P) of this evaluation are zero
-  if (tid < P) p_bwd[(P + tid) * rs + blockIdx.x] = 0.0;
-  step_partials<P, true>(acc2, gw, p_fwd, p_bwd, true, 0);
-}
-
-// Backward in basis form over a run table: the point itself and the chain to the weights come from the basis rows.
-// partial rows: [0, P) dL/dw (the exponent slots [P, 2P) are written as zeros).
-template <typename PT, int P>
-__global__ __launch_bounds__(kBlock) void consistency_bwd_basis_kernel(
-    PointBasis pb, const PT* __restrict__ rec, RunTab tab, int cap, int64_t n, QParams qp, double* __restrict__ partials) {
-  constexpr int RR = RecRaw<PT>::kRow16;
-  constexpr int NP = P > 0 ? P : DC_MAX_MODEL_TERMS;
-  extern __shared__ int4 tile[];
-  __shared__ double s_w[DC_MAX_MODEL_TERMS];
-  const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  const int64_t blk = xcd_block(nblocks);
-  double gw[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) gw[k] = 0.0;
-  const int64_t j = blk * kBlock + threadIdx.x;
-  const bool active = blk >= 0 && j < n;
-  uint2 pre[kPreRuns];
-  int32_t nruns = 0;
-  uint32_t nd = 0;
-  const uint2* runs = reinterpret_cast<const uint2*>(tab.loc);
-  if (blk >= 0) {
-    if (active) {
-      const int32_t r0 = tab.run_ptr[j];
-      nruns = tab.run_ptr[j + 1] - r0;
-      runs += r0;
-    }
-#pragma unroll
-    for (int t = 0; t < kPreRuns; ++t) pre[t] = t < nruns ? runs[t] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-    stage_weights(pb, s_w);
-    nd = (uint32_t)stage_rows<RR>(tab.blk_ptr, tab.blk_ids, blk, reinterpret_cast<const int4*>(rec), tile, cap);
-    if (threadIdx.x < RR) tile[threadIdx.x * cap + nd] = make_int4(0, 0, 0, 0);
-  }
-  const uint32_t nd16 = nd * 16u;
-  __syncthreads();
-  if (active) {
-    double wq[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) wq[k] = (P > 0 || k < pb.n_terms) ? s_w[k] : 0.0;
-    const typename Pt<PT>::Raw cj = Basis<PT>::template point<P>(pb, wq, j);
-    double g[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int t = 0; t < kPreRuns; ++t)
-      if (__any((int)(t < nruns))) run_edges<PT>(tile, cap, pre[t], nd16, cj, g);
-    if (__any((int)(nruns > kPreRuns))) {
-      uint2 nxt = kPreRuns < nruns ? runs[kPreRuns] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-      for (int t = kPreRuns; __any((int)(t < nruns)); ++t) {
-        const uint2 r = nxt;
-        nxt = t + 1 < nruns ? runs[t + 1] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-        run_edges<PT>(tile, cap, r, nd16, cj, g);
-      }
-    }
-    const double u = Pt<PT>::unit(qp);
-    g[0] *= u; g[1] *= u; g[2] *= u;
-    // u_j and c_j again (the row is still in the cache): holding them across the edge loop costs a wavefront of occupancy
-    Basis<PT>::template chain<NP>(pb, P > 0 ? P : pb.n_terms, j, g, gw);
-  }
-  // per-wavefront partial rows, as reduce_param_grads writes them
-  const int64_t rs = (int64_t)gridDim.x * kWavesPerBlock;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  double* prow = partials + (int64_t)blockIdx.x * kWavesPerBlock + wave;
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    if (k < pb.n_terms) {
-      const double sw = wave_sum(gw[k]);
-      if (lane == 0) { prow[k * rs] = sw; prow[(pb.n_terms + k) * rs] = 0.0; }
-    }
-  }
-}
+namespace dc {
 
 // Quantile-inlier gating of the pointwise loss (loss.py:256-277) for the fused path: `raw` is the forward's raw loss
 // (DC_LOSS_RAW_POINTWISE), *threshold the bound the caller derived from it (quantile x multiplier, or the given maximum).
@@ -3045,16 +1238,24 @@ using namespace dc;
   } while (0)
 
 static inline int64_t n_blocks(int64_t n) { return (n + kBlock - 1) / kBlock; }
-// dc_set_option(0, 1): ignore block tables, gather from global memory (A-B measurements); process-wide, read per launch
-static std::atomic<bool> g_no_reverse{false};        // dc_set_option(8, 1): every launch of a chain walks the blocks forwards (A-B, chain_block_of)
-static std::atomic<bool> g_pose_three_pass{false};   // dc_set_option(7, 1): pose gradients through the three-kernel general path (A-B, tests)
+// The A-B switches of dc_set_option: process-wide, read once per launch
+// dc_set_option(0, 1): ignore block tables, gather from global memory
 static std::atomic<bool> g_no_tab{false};
+// dc_set_option(1, 1): run-time slot loop instead of the fixed-K forward kernels
 static std::atomic<int> g_fwd_generic{0};
-static std::atomic<bool> g_two_pass{false};     // dc_set_option(4, 1): basis form with separate forward and backward kernels
-static std::atomic<int> g_step_var{1};          // dc_set_option(6, v): 1 = consistency_step_q32_kernel for float32 clouds with a [rows, K] table (default),
-                                                // 7 = consistency_step_basis_kernel<.., kStepVar> for them too, 0 = its round-2 form (K = 10, P = 2 only: A-B baseline)
-static std::atomic<int> g_chain_spin{1 << 22};  // dc_set_option(5, n): polls of a chained launch's wait for its weights (tests force 0)
-static std::atomic<bool> g_no_basis{false};    // dc_set_option(3, 1): ignore a sequence's basis rows (general path)    // dc_set_option(1, 1): run-time slot loop instead of the fixed-K forward kernels
+// dc_set_option(3, 1): ignore a sequence's basis rows (general path)
+static std::atomic<bool> g_no_basis{false};
+// dc_set_option(4, 1): basis form with separate forward and backward kernels
+static std::atomic<bool> g_two_pass{false};
+// dc_set_option(5, n): polls of a chained launch's wait for its weights (tests force 0)
+static std::atomic<int> g_chain_spin{1 << 22};
+// dc_set_option(6, v): 1 = consistency_step_q32_kernel for float32 clouds with a [rows, K] table (default), 7 =
+// consistency_step_basis_kernel<.., kStepVar> for them too, 0 = its round-2 form (K = 10, P = 2 only: A-B baseline)
+static std::atomic<int> g_step_var{1};
+// dc_set_option(7, 1): pose gradients through the three-kernel general path (A-B, tests)
+static std::atomic<bool> g_pose_three_pass{false};
+// dc_set_option(8, 1): every launch of a chain walks the blocks forwards (A-B, chain_block_of)
+static std::atomic<bool> g_no_reverse{false};
 
 // consistency_step_ragged_q32_kernel with a tile of CAP rows: more than 64 KB of LDS per block needs the attribute (once per
 // instantiation, process and device).  Capacities up to the table's own limit (4095 rows), so every ball-neighbourhood table that can be
@@ -3455,13 +1656,14 @@ int dc_points_bwd(const void* grad_points, const int32_t* perm, int stride, int 
   return DC_OK;
 }
 
-// option 0: 1 = ignore block tables and gather from global memory (ablation / A-B measurements), 0 = default.
 #ifdef DC_BLOCK_TRACE
 int dc_debug_block_trace(void* buf) {        // diagnostic build only: [4 x grid] uint64 (or null to stop recording)
   unsigned long long* p = (unsigned long long*)buf;
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(dc::g_block_trace), &p, sizeof(p));
 }
 #endif
+// option 0: 1 = ignore block tables and gather from global memory (ablation / A-B measurements), 0 = default; the other options are
+// listed at the switches above use_table and in dc_hip.h.
 // The switches exist for A-B measurements and for the tests that hold one path against another; a process that has not asked for them
 // (DC_ENABLE_ABLATIONS=1 in its environment when the library is first used) cannot change them: the product has no mutable
 // process-wide state.

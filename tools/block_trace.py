@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Schedule of ONE launch of a one-pass step kernel, from the diagnostic build of the library (csrc/dc_consistency.hip with
--DDC_BLOCK_TRACE: every block records {XCC | HW_ID, start, end} on the 100 MHz constant clock):
+-DDC_BLOCK_TRACE: every block records {XCC | HW_ID, start, end} on the 100 MHz constant clock; the DC_TRACE_* macros and the step
+kernels they sit in are in csrc/dc_cons_step.h, a part of that translation unit):
 
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DDC_BLOCK_TRACE -Iinclude -c depth_correction_amd/csrc/dc_consistency.hip -o build/dc_consistency_trace.o
     hipcc -shared -fPIC --offload-arch=gfx950 -o build/libdc_hip_trace.so build/dc_consistency_trace.o <the other objects of depth_correction_amd/lib/obj>

@@ -3,7 +3,8 @@
 
     python3 tools/isa_sections.py <mangled-name fragment> [out.md]      e.g.  consistency_step_q32_kernelILi10ELi2E
 
-Compiles csrc/dc_consistency.hip for gfx950 with -save-temps into a scratch directory, cuts the kernel out of the .s and
+Compiles csrc/dc_consistency.hip (one translation unit: the one-pass step and pose kernels live in the dc_cons_*.h headers it
+includes) for gfx950 with -save-temps into a scratch directory, cuts the kernel out of the .s and
 prints, per basic block of at least `--min` instructions, the number of VALU instructions by class (fp64 / fp32 / integer-and-
 move), LDS, vector-memory and scalar instructions, plus the register / LDS footprint from the kernel descriptor."""
 import argparse
