@@ -18,10 +18,12 @@ __all__ = ['bias_eval_csv', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', '
 
 class _Names(type):
     def __iter__(cls):
-        return iter(v for k, v in vars(cls).items() if not k.startswith('_') and isinstance(v, str))
+        # the names a default sweep runs (Config.eval_losses = list(Loss)); ``_unlisted`` names are members that a sweep must ask for
+        skip = vars(cls).get('_unlisted', ())
+        return iter(v for k, v in vars(cls).items() if not k.startswith('_') and isinstance(v, str) and v not in skip)
 
     def __contains__(cls, item):
-        return item in list(iter(cls))
+        return item in list(iter(cls)) or item in vars(cls).get('_unlisted', ())
 
 
 class NeighborhoodType(metaclass=_Names):
@@ -33,6 +35,8 @@ class Loss(metaclass=_Names):
     min_eigval_loss = 'min_eigval_loss'
     trace_loss = 'trace_loss'
     icp_loss = 'icp_loss'
+    mesh_loss = 'mesh_loss'          # supervised: distance to the dataset's ground-truth mesh (loss.mesh_loss)
+    _unlisted = ('mesh_loss',)       # needs a dataset with a mesh: not part of the default eval_losses sweep
 
 
 class Model(metaclass=_Names):

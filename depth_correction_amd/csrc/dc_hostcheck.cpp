@@ -6,6 +6,7 @@
 #include "dc_pointmath.h"
 #include "dc_slam_math.h"
 #include "dc_trimath.h"
+#include "dc_meshloss_math.h"
 #include "dc_biasmath.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
@@ -120,6 +121,11 @@ int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double m
 // taken (dc::kTri*); returns the squared distance the kernel compares
 double dc_host_closest_on_triangle(const double* tri, const double* p, double* closest, int* region) {
   return dc::closest_on_triangle(tri, p, closest, region);
+}
+
+// dc_mesh_loss's per-point term: x [3], c [3] -> *r = |x - c|, grad [3] = dl/dx; returns l = r (r^2 with `squared`)
+double dc_host_mesh_loss_term(const double* x, const double* c, int squared, double* r, double* grad) {
+  return dc::mesh_loss_term(x, c, squared != 0, r, grad);
 }
 
 // dc_mesh_sample's sample i of `seed` on the triangle tri [9]: u [3] <- the three uniforms, p [3] <- the point

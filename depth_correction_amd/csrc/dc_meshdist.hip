@@ -3,8 +3,9 @@
 // surveyed ground-truth cloud (scripts/mapping_accuracy:82-118); with rendered-mesh datasets the ground truth is the mesh itself.
 //
 // dc_mesh_closest: one lane per query, one launch, no workspace.  Depth-first walk with the nearer child first and the other on a
-// per-lane stack in LDS (depth 64, lane-minor: the layout of raycast_kernel).  A node is visited only while a LOWER BOUND of the
-// squared distance from the query to its box is not above the best squared distance so far.  Triangles are tested in fp64
+// per-lane stack in LDS (depth 64, lane-minor: the layout of raycast_kernel); the walk itself is dc_meshwalk.h's, which dc_mesh_loss
+// shares.  A node is visited only while a LOWER BOUND of the squared distance from the query to its box is not above the best
+// squared distance so far.  Triangles are tested in fp64
 // (dc_trimath.h); the smallest d^2 wins, equal d^2 the lower face index, so the result does not depend on the traversal order.
 //
 // The box bound, in fp32 (next to the ray rule in dc_raycast.hip's header: no box a ray touches is rejected; here: no box that holds
@@ -28,31 +29,13 @@
 #include "dc_common.h"
 #include "dc_hostutil.h"
 #include "dc_trimath.h"
+#include "dc_meshwalk.h"
 #include "../../include/dc_hip.h"
-#include <float.h>
 
 namespace {
 
 constexpr int kClosestBlock = 128;
-constexpr int kStackDepth = 64;
 constexpr int kSampleBlock = 256;
-
-struct Query32 {
-  float p[3], margin;
-};
-
-// lower bound of the squared distance from the query to the box of `node` (derivation: file header)
-__device__ __forceinline__ float box_bound(const float* __restrict__ node_box, int64_t node, const Query32& q) {
-  const float* b = node_box + 6 * node;
-  float s = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float g = fmaxf(fmaxf(b[a] - q.p[a], q.p[a] - b[3 + a]), 0.0f);
-    const float h = fmaxf(g - q.margin, 0.0f);
-    s = __fadd_rn(s, __fmul_rn(h, h));             // explicit roundings: the derivation counts them (no contraction)
-  }
-  return __fmul_rn(s, 1.0f - 0x1p-20f);
-}
 
 template <typename T>
 __global__ void __launch_bounds__(kClosestBlock) mesh_closest_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
@@ -60,7 +43,7 @@ __global__ void __launch_bounds__(kClosestBlock) mesh_closest_kernel(const int32
                                                                     int64_t n, const T* __restrict__ points, int64_t n_points, double limit2,
                                                                     double max_dist, int32_t* __restrict__ face_out,
                                                                     double* __restrict__ dist_out, double* __restrict__ closest_out) {
-  __shared__ int32_t stack[kStackDepth * kClosestBlock];
+  __shared__ int32_t stack[dc::kWalkStackDepth * kClosestBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kClosestBlock + lane;
   if (g >= n_points) return;
@@ -69,55 +52,8 @@ __global__ void __launch_bounds__(kClosestBlock) mesh_closest_kernel(const int32
   int32_t best_face = -1;
   int64_t best_leaf = -1;
   if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-    Query32 q;
-    float pmax = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      q.p[a] = fminf(fmaxf((float)p[a], -FLT_MAX), FLT_MAX);
-      pmax = fmaxf(pmax, fabsf(q.p[a]));
-    }
-    q.margin = fmaxf(pmax * 0x1p-23f, 1e-30f);
-    int sp = 0;
-    int64_t node = 0;
-    bool live = box_bound(node_box, 0, q) <= __double2float_ru(best);
-    while (live) {
-      if (node >= n - 1) {
-        const int64_t leaf = node - (n - 1);
-        double tri[9], c[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) tri[k] = leaf_tri[9 * leaf + k];
-        const double d2 = dc::closest_on_triangle(tri, p, c, nullptr);
-        const int32_t face = leaf_face[leaf];
-        if (d2 < best || (d2 == best && (best_face < 0 || face < best_face))) {      // a NaN never wins
-          best = d2;
-          best_face = face;
-          best_leaf = leaf;
-        }
-      } else {
-        const float lim = __double2float_ru(best);
-        const int64_t ca = child[2 * node], cb = child[2 * node + 1];
-        const float ba = box_bound(node_box, ca, q), bb = box_bound(node_box, cb, q);
-        const bool go_a = ba <= lim, go_b = bb <= lim;
-        if (go_a || go_b) {
-          if (go_a && go_b) {
-            const bool a_first = ba <= bb;
-            if (sp < kStackDepth) stack[sp * kClosestBlock + lane] = (int32_t)(a_first ? cb : ca);     // sp < 64 always (depth <= 63)
-            ++sp;
-            node = a_first ? ca : cb;
-          } else {
-            node = go_a ? ca : cb;
-          }
-          continue;
-        }
-      }
-      // next postponed node whose box may still hold a face as near as the best one
-      live = false;
-      while (sp > 0) {
-        --sp;
-        node = sp < kStackDepth ? stack[sp * kClosestBlock + lane] : 0;
-        if (box_bound(node_box, node, q) <= __double2float_ru(best)) { live = true; break; }
-      }
-    }
+    const dc::Query32 q = dc::mesh_query(p);
+    dc::mesh_walk<kClosestBlock>(child, node_box, leaf_tri, leaf_face, n, p, q, stack, lane, best, best_face, best_leaf);
   }
   double dist = INFINITY, c[3] = {NAN, NAN, NAN};
   if (best_face >= 0) {

@@ -167,6 +167,12 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
         return loss, loss_cloud, poses_upd, feat
 
+    if cfg.loss == 'mesh_loss':
+        # supervised: masks[i] = (the sequence's ground-truth mesh, point mask or None) -- see mesh_masks
+        loss, loss_cloud = loss_fun(clouds, poses_upd, model, masks=masks)
+        feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
+        return loss, loss_cloud, poses_upd, feat
+
     if fused_supported(clouds, model, cfg):
         # masks are established once (train.py:212-215); when absent they come from one un-fused evaluation
         if not masks or masks[0] is None:
@@ -203,6 +209,20 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         masks = [global_cloud_mask(cloud, cloud.mask if hasattr(cloud, 'mask') else None, cfg) for cloud in feat_clouds]
     loss, loss_cloud = loss_fun(feat_clouds, mask=masks, offset=offsets)
     return loss, loss_cloud, poses_upd, feat_clouds
+
+
+def mesh_masks(datasets, names, all_clouds):
+    """mesh_loss's per-sequence ``masks``: (the dataset's ground-truth mesh, the scans' masks concatenated -- the points the model
+    corrects -- or None when no scan has one)."""
+    out = []
+    for ds, name, clouds in zip(datasets, names, all_clouds):
+        mesh = _dataset_mesh(ds, name, who='mesh_loss')
+        point_mask = None
+        if any(c.mask is not None for c in clouds):
+            point_mask = torch.cat([c.mask if c.mask is not None else torch.ones((len(c),), dtype=torch.bool, device=c.dirs.device)
+                                    for c in clouds])
+        out.append((mesh, point_mask))
+    return out
 
 
 def _load_test_sequences(cfg: Config, test_datasets):
@@ -263,6 +283,8 @@ def eval_loss(cfg: Config, test_datasets=None, test_ns=None, model=None, loss_fu
     assert callable(loss_fun)
     test_clouds, test_poses = _load_test_sequences(cfg, test_datasets)
     test_masks = [None] * len(test_datasets)
+    if cfg.loss == 'mesh_loss':
+        test_masks = mesh_masks(test_datasets, test_names, test_clouds)
     test_pose_deltas = _test_pose_deltas(cfg, test_datasets)
     if test_ns is None:
         test_ns = [establish_neighborhoods(clouds=clouds, poses=poses, cfg=cfg) for clouds, poses in zip(test_clouds, test_poses)]
@@ -603,7 +625,7 @@ def _landscape_kernel(clouds, poses_upd, masks, ns, model, w, cfg: Config):
 def _loop_count(views, cfg: Config):
     """Entries behind the loop's mean: the fused views' counts, else the loss clouds' entries (loss.reduce keeps the finite /
     non-NaN ones under only_finite / skip_nans); nan for the ICP loss, which is no mean over points."""
-    if cfg.loss == 'icp_loss':
+    if cfg.loss in ('icp_loss', 'mesh_loss'):                 # (mesh_loss: the mean of the sequences' means)
         return float('nan')
     kw = cfg.loss_kwargs
     total = 0.0

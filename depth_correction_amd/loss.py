@@ -7,6 +7,8 @@ Two execution paths produce the same numbers:
     of loss.py:250-289 on ``cloud.eigvals`` / ``cloud.cov`` (small ``[M]`` tensors), differentiable down to the
     points through dc_features_bwd.  All of the reference's options are available here (mask, offset, sqrt,
     normalisation, quantile inliers, reductions).
+``mesh_loss`` is the supervised counterpart: the mean distance of the corrected, posed points to a ground-truth mesh, forward
+and backward (weights, exponents, poses) out of one dc_mesh_loss call per sequence.
 ``icp_loss`` with precomputed correspondences runs as one kernel per scan pair (dc_p2plane_sequence for
 point-to-plane, dc_p2point_sequence for point-to-point distances) including its backward to the model weights and
 poses; ``point_to_point_dist`` as a metric on GPU clouds (scripts/model_poses_learning:142-146) uses the same kernel.
@@ -24,7 +26,7 @@ from .plan import PlanRegistry
 from .segmentation import Planes
 from .utils import trace
 
-__all__ = ['batch_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'min_eigval_loss', 'point_to_plane_dist',
+__all__ = ['batch_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'mesh_loss', 'min_eigval_loss', 'point_to_plane_dist',
            'point_to_point_dist', 'reduce', 'Reduction', 'trace_loss', 'icp_correspondences']
 
 
@@ -340,8 +342,151 @@ def icp_loss(clouds, poses=None, model=None, masks=None, **kwargs):
     return loss / len(clouds), loss_cloud
 
 
+# ---- supervised loss against a ground-truth mesh -------------------------------------------------------------------
+class _MeshLossSequence(torch.autograd.Function):
+    """mesh_loss of one sequence through dc_mesh_loss: forward and backward come out of the same host call."""
+
+    @staticmethod
+    def forward(ctx, w, exponent, poses, plan, kind, squared, max_dist):
+        P12 = poses.detach().to(torch.float64)[:, :3, :].reshape(-1, 12).contiguous()
+        wv = None if w is None else w.detach().reshape(-1).to(torch.float64).contiguous()
+        ev = None if exponent is None else exponent.detach().reshape(-1).to(torch.float64).contiguous()
+        want_e = isinstance(exponent, torch.Tensor) and bool(ctx.needs_input_grad[1])
+        out = plan.eval(P12, kind, wv, ev, squared=squared, max_dist=max_dist, want_exponent=want_e)
+        ctx.save_for_backward(out)
+        ctx.meta = (None if w is None else (w.shape, w.dtype), poses.dtype, poses.shape[0],
+                    exponent.shape if isinstance(exponent, torch.Tensor) else None)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        out, = ctx.saved_tensors
+        wmeta, pdt, ns, eshape = ctx.meta
+        nt = (out.numel() - 4 - 12 * ns) // 2
+        gw = ge = gT = None
+        if wmeta is not None and ctx.needs_input_grad[0]:
+            gw = (g * out[4:4 + nt]).reshape(wmeta[0]).to(wmeta[1])
+        if eshape is not None and ctx.needs_input_grad[1]:
+            ge = (g * out[4 + nt:4 + 2 * nt]).reshape(eshape)
+        if ctx.needs_input_grad[2]:
+            gT = torch.zeros((ns, 4, 4), dtype=torch.float64, device=out.device)
+            gT[:, :3, :] = (g * out[4 + 2 * nt:]).reshape(ns, 3, 4)
+            gT = gT.to(pdt)
+        return gw, ge, gT, None, None, None, None
+
+
+class _MeshLossPlan(object):
+    """What is constant over the optimisation of one sequence against its mesh: the scans' fields concatenated scan-major, the
+    scan offsets, the mesh's tree, the loss mask, the workspace -- and the leaf hint, which starts at -1 and is carried from one
+    evaluation to the next (a point's nearest face changes little between two optimiser steps)."""
+
+    def __init__(self, seq_clouds, mesh, point_mask, with_model):
+        dev = seq_clouds[0].dirs.device
+        sizes = [len(c) for c in seq_clouds]
+
+        def rows(field, width):
+            parts = [getattr(c, field).detach().expand(n, width) for c, n in zip(seq_clouds, sizes)]
+            return torch.cat(parts).contiguous()
+        vps = rows('vps', 3) if any(bool(c.vps.any()) for c in seq_clouds) else None
+        inc = lmask = None
+        if with_model:
+            if any(c.inc_angles is None for c in seq_clouds):
+                raise ValueError('the model needs incidence angles')
+            inc = rows('inc_angles', 1)
+            if any(c.mask is not None for c in seq_clouds):
+                lmask = torch.cat([c.mask if c.mask is not None else torch.ones((n,), dtype=torch.bool, device=dev)
+                                   for c, n in zip(seq_clouds, sizes)]).contiguous()
+        self.ps = ops.PointSet(vps, rows('dirs', 3), rows('depth', 1), inc, lmask)
+        self.n, self.n_scans, self.device = self.ps.n, len(sizes), dev
+        ptr_host = [0]
+        for n in sizes:
+            ptr_host.append(ptr_host[-1] + n)
+        self.scan_ptr = torch.tensor(ptr_host, dtype=torch.int64, device=dev)
+        self.mesh = mesh
+        self.bvh = mesh.on_device(dev)[3]
+        self.mask = None if point_mask is None else torch.as_tensor(point_mask, device=dev).to(torch.bool).contiguous()
+        self.leaf_hint = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self._ws = {}
+
+    def eval(self, poses12, kind=None, w=None, e=None, squared=False, max_dist=None, want_exponent=False, want_points=False):
+        nt = 0 if not kind else w.numel()
+        ws = self._ws.get(nt)
+        if ws is None:
+            ws = self._ws[nt] = ops.mesh_loss_workspace(self.n, self.n_scans, nt, self.device)
+        return ops.mesh_loss(self.bvh, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, squared=squared, max_dist=max_dist,
+                             leaf_hint=self.leaf_hint, want_points=want_points, want_exponent=want_exponent, ws=ws)
+
+
+_mesh_plans = PlanRegistry()
+
+
+def _mesh_sequence_plan(seq_clouds, mesh, point_mask, with_model):
+    fields = [t for c in seq_clouds for t in (c.vps, c.dirs, c.depth, c.inc_angles, c.mask)] + [point_mask, mesh]
+    return _mesh_plans.get(fields, (bool(with_model),), lambda: _MeshLossPlan(seq_clouds, mesh, point_mask, with_model))
+
+
+def _unfused_mesh_sequence(seq_clouds, seq_poses, model, mesh, point_mask, squared, max_dist):
+    """The same loss from tensor operations: x in fp64 through the model and the poses, the closest points (detached) from
+    ops.mesh_closest, l = |x - c|, torch autograd.  For models without a kernel kind, and what the fused form is tested against."""
+    dev = seq_clouds[0].dirs.device
+    parts = []
+    for i, c in enumerate(seq_clouds):
+        c64 = DepthCloud(vps=c.vps.double(), dirs=c.dirs.double(), depth=c.depth.double(),
+                         inc_angles=None if c.inc_angles is None else c.inc_angles.double(), mask=c.mask)
+        if model is not None:
+            c64 = model(c64)
+        if seq_poses is not None:
+            c64 = c64.transform(seq_poses[i].double())
+        parts.append(c64.vps + c64.depth * c64.dirs)
+    x = torch.cat(parts)
+    bvh = mesh.on_device(dev)[3]
+    face, _, closest = ops.mesh_closest(bvh, x.detach().contiguous(), max_dist=max_dist)
+    used = face >= 0
+    if point_mask is not None:
+        used = used & torch.as_tensor(point_mask, device=dev).to(torch.bool)
+    d = x[used] - closest[used]
+    sq = (d * d).sum(dim=-1)
+    if squared:
+        return sq.mean()
+    # r = 0 has no direction: zero gradient there (sqrt'(0) is infinite), as in the kernel
+    pos = sq > 0
+    return (torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))) * pos).mean()
+
+
+def mesh_loss(clouds, poses=None, model=None, masks=None, **kwargs):
+    """Supervised loss against ground-truth meshes over lists of sequences of scans: the mean distance of the corrected, posed
+    points of a sequence to its mesh (``mesh_squared``: the mean squared distance; ``mesh_max_dist``: points farther away are left
+    out), averaged over the sequences like icp_loss.  ``masks[i]`` = (mesh.TriangleMesh, bool point mask [N_i] or None) of sequence
+    ``i``.  Differentiable to the model's weights and exponents and to the poses; GPU clouds with a kernel model (or none) and
+    poses take one dc_mesh_loss call per sequence (``fused=False`` forces the tensor form)."""
+    if not clouds or not clouds[0]:
+        raise ValueError('mesh_loss needs at least one sequence with one scan')
+    if not clouds[0][0].dirs.is_cuda:
+        raise RuntimeError('mesh_loss: the clouds must live on the GPU (depth_correction_amd has no CPU path)')
+    if masks is None or len(masks) != len(clouds):
+        raise ValueError('mesh_loss needs masks[i] = (mesh, point mask or None) for every sequence')
+    squared, max_dist = bool(kwargs.get('mesh_squared', False)), kwargs.get('mesh_max_dist')
+    kind = getattr(model, 'kernel_kind', None) if model is not None else None
+    fused = kwargs.get('fused', True) and poses is not None and (model is None or kind)
+    loss, loss_cloud = 0., []
+    for i, seq in enumerate(clouds):
+        mesh, point_mask = masks[i] if isinstance(masks[i], (tuple, list)) else (masks[i], None)
+        if mesh is None or not hasattr(mesh, 'on_device'):
+            raise ValueError('mesh_loss: sequence %d has no ground-truth mesh (masks[%d] = (mesh, point mask))' % (i, i))
+        if fused:
+            w, e = model.kernel_params() if kind else (None, None)
+            plan = _mesh_sequence_plan(seq, mesh, point_mask, bool(kind))
+            seq_poses = poses[i] if isinstance(poses[i], torch.Tensor) else torch.stack(list(poses[i]))
+            loss_seq = _MeshLossSequence.apply(w, e, seq_poses, plan, kind, squared, max_dist)
+        else:
+            loss_seq = _unfused_mesh_sequence(seq, None if poses is None else poses[i], model, mesh, point_mask, squared, max_dist)
+        loss = loss + loss_seq
+        loss_cloud.append(_MovedClouds(seq, None if poses is None else poses[i], model, loss))
+    return loss / len(clouds), loss_cloud
+
+
 def loss_by_name(name):
-    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss')
+    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss', 'mesh_loss')
     return globals()[name]
 
 

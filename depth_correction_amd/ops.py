@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update',
 ]
@@ -1319,6 +1319,76 @@ def mesh_closest(bvh, points, max_dist=None, want_closest=True):
     check(lib().dc_mesh_closest(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
                                 ptr(points), code, n, md, ptr(face), ptr(dist), ptr(closest), stream_ptr()), 'dc_mesh_closest')
     return face, dist, closest
+
+
+def mesh_loss_workspace(n, n_scans, n_terms, device):
+    """Workspace of mesh_loss for the given sizes (uint8 tensor)."""
+    return _ws(lib().dc_mesh_loss_workspace_bytes(int(n), int(n_scans), int(n_terms)), device)
+
+
+def _check_scan_ptr(ps, scan_ptr):
+    """scan_ptr int64 [S+1] on the points' device, ascending from 0 to ps.n: read back once per (PointSet, tensor) -- the kernel lays
+    its blocks out from it."""
+    need(scan_ptr, (None,), dtype=torch.int64, name='scan_ptr', device=ps.device)
+    if scan_ptr.shape[0] < 2:
+        raise ValueError('scan_ptr needs at least two entries ([S+1]), got %d' % scan_ptr.shape[0])
+    seen = getattr(ps, '_scan_ptr_checked', None)
+    if seen is None or seen[0] is not scan_ptr or seen[1] != scan_ptr._version:
+        host = scan_ptr.tolist()
+        if host[0] != 0 or host[-1] != ps.n or any(b < a for a, b in zip(host, host[1:])):
+            raise ValueError('scan_ptr must ascend from 0 to the number of points (%d), got %s' % (ps.n, host))
+        ps._scan_ptr_checked = (scan_ptr, scan_ptr._version)
+    return scan_ptr.shape[0] - 1
+
+
+@on_device
+def mesh_loss(bvh, ps, scan_ptr, poses12, model_kind=None, w=None, e=None, mask=None, squared=False, max_dist=None, leaf_hint=None,
+              want_points=False, want_exponent=False, out=None, ws=None):
+    """Mean distance of the corrected, posed points of a sequence to the mesh behind ``bvh`` (mesh.MeshBVH), with its gradient, in
+    one host call (dc_mesh_loss).  ``ps``: PointSet of the scans' sensor-frame fields, scan-major (its lmask: the points the model
+    corrects; its scan_id is not used); ``scan_ptr`` int64 [S+1]: scan s holds the points scan_ptr[s] .. scan_ptr[s+1]; ``poses12``
+    f64 [S,12].  ``mask`` bool [N]: the points that enter the loss; ``max_dist``: points farther from the mesh are left out (gated).
+    Returns out f64 [4 + 2P + 12 S] = {mean loss, used, gated, invalid, dL/dw, dL/dexponent (zero unless ``want_exponent``),
+    dL/d[R|t]}; with ``want_points`` also (face i32 [N], dist f64 [N], closest f64 [N,3]) -- what mesh_closest gives for the
+    points, -1 / inf / NaN where a point is not used.  ``leaf_hint`` int32 [N] is read and written: the winning leaves of the last
+    call shorten the walk of this one and never change a bit of a result (start it at -1)."""
+    dev = bvh.leaf_face.device
+    if ps.device != dev:
+        raise RuntimeError('points are on %s, the mesh on %s' % (ps.device, dev))
+    kind, nt, w, e = _model_args(model_kind, w, e, ps)
+    ns = _check_scan_ptr(ps, scan_ptr)
+    need(poses12, (ns, 12), dtype=torch.float64, name='poses[S,12]', device=dev)
+    if mask is not None:
+        need(mask, (ps.n,), dtype=torch.bool, name='mask', device=dev)
+    if leaf_hint is not None:
+        need(leaf_hint, (ps.n,), dtype=torch.int32, name='leaf_hint', device=dev)
+    md = 0.0 if max_dist is None else float(max_dist)
+    if md != md:
+        raise ValueError('max_dist must not be NaN')
+    n_out = 4 + 2 * nt + 12 * ns
+    if out is None:
+        out = torch.empty((n_out,), dtype=torch.float64, device=dev)
+    else:
+        need(out, (n_out,), dtype=torch.float64, name='out', device=dev)
+    nbytes = lib().dc_mesh_loss_workspace_bytes(ps.n, ns, nt)
+    if ws is None:
+        ws = _ws(nbytes, dev)
+    else:
+        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
+        if ws.shape[0] < nbytes:
+            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    face = dist = closest = None
+    if want_points:
+        face = torch.empty((ps.n,), dtype=torch.int32, device=dev)
+        dist = torch.empty((ps.n,), dtype=torch.float64, device=dev)
+        closest = torch.empty((ps.n, 3), dtype=torch.float64, device=dev)
+    nf = bvh.n_faces
+    check(lib().dc_mesh_loss(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                             ptr(ps.vps), ptr(ps.dirs), ptr(ps.depth), ptr(ps.inc), ptr(ps.lmask), ptr(mask), dtype_code(ps.dirs), ps.n,
+                             ptr(scan_ptr), ptr(poses12), ns, kind, nt, ptr(w), ptr(e), int(bool(want_exponent)), int(bool(squared)), md,
+                             ptr(leaf_hint), ptr(face), ptr(dist), ptr(closest), ptr(out), ptr(ws), ws.shape[0], stream_ptr()),
+          'dc_mesh_loss')
+    return (out, face, dist, closest) if want_points else out
 
 
 @on_device

@@ -906,6 +906,30 @@ int dc_bias_accumulate(const void* depth, const void* inc_est, int dtype, const 
 int dc_mesh_closest(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
                     const void* points, int dtype, int64_t n_points, double max_dist, int32_t* face_out, double* dist_out,
                     double* closest_out, dcStream_t stream);
+/* ---- supervised training against the mesh (depth_correction_amd/csrc/dc_meshloss.hip; DESIGN "Supervised training against the
+ * mesh") ----
+ * The mean distance of the corrected, posed points of a sequence to the mesh behind the arrays of dc_bvh_build, and its gradient, in
+ * one call (a walk kernel and a one-block finishing kernel; no atomics: the same inputs give the same bits).  Point j of scan s
+ * (points scan-major: scan s holds the points scan_ptr[s] .. scan_ptr[s+1], DEVICE int64 [n_scans+1], ascending from 0 to n; NULL with
+ * n_scans == 1) is x_j = R_s (vp_j + d'_j dir_j) + t_s exactly as dc_points_fwd forms it in fp64 (vps NULL: the origin; lmask: the
+ * points the model corrects; poses DEVICE double [n_scans,12], NULL: identity; w, e DEVICE double [n_terms]).  c_j = the closest
+ * point of the mesh by dc_mesh_closest's walk and tie rule, r_j = |x_j - c_j|, l_j = r_j (r_j^2 with squared).  A point is USED when
+ * mask (uint8 [n], optional) holds it, x_j is finite and, with max_dist > 0 and finite, r_j <= max_dist; a point in the mask is
+ * otherwise counted gated (beyond max_dist) or invalid (not finite).
+ * out double [4 + 2 n_terms + 12 n_scans] = {L = sum l / M, M = used, gated, invalid, dL/dw, dL/dexponent (zero unless
+ * want_exponent), dL/d[R|t] per scan row-major 3 x 4}; M == 0: L = NaN, zero gradients.
+ * leaf_hint int32 [n] (optional, read and written): a value in [0, n_faces) is a LEAF of the tree whose triangle is tested before
+ * the walk starts -- it shortens the walk and never changes a bit of any output; anything else is ignored.  Written back: the
+ * winning leaf of a used point, -1 otherwise.  face_out int32 [n], dist_out double [n], closest_out double [n,3] (each optional):
+ * what dc_mesh_closest gives for x_j at this max_dist; -1 / +inf / NaN for a point that is not used.
+ * ws: dc_mesh_loss_workspace_bytes(n, n_scans, n_terms) bytes (DC_ERR_WORKSPACE).  NaN max_dist: DC_ERR_ARG.  n == 0: L = NaN, zero
+ * counts and gradients; a scan without points is legal.  No allocation, copy or synchronisation. */
+size_t dc_mesh_loss_workspace_bytes(int64_t n, int n_scans, int n_terms);
+int dc_mesh_loss(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                 const void* vps, const void* dirs, const void* depth, const void* inc, const uint8_t* lmask, const uint8_t* mask,
+                 int dtype, int64_t n, const int64_t* scan_ptr, const double* poses, int n_scans, int model_kind, int n_terms,
+                 const double* w, const double* e, int want_exponent, int squared, double max_dist, int32_t* leaf_hint,
+                 int32_t* face_out, double* dist_out, double* closest_out, double* out, void* ws, size_t ws_bytes, dcStream_t stream);
 /* n_samples area-weighted samples of the mesh verts double [.,3], faces int32 [n_faces,3] with area_cdf double [n_faces] the
  * inclusive prefix sum of the face areas (last entry > 0).  Sample i: u_t = (splitmix64(splitmix64(seed) + 4 i + t) >> 11) 2^-53 for
  * t = 0, 1, 2 (uint64, wrapping); face = the first f with u_0 area_cdf[n_faces-1] < area_cdf[f]; s = sqrt(u_1), point =
