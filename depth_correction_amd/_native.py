@@ -166,6 +166,9 @@ _SIGNATURES = {
     'dc_mesh_loss_workspace_bytes': (_sz, [_i64, _i32, _i32]),
     'dc_mesh_loss': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
                             _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_cloud_loss_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'dc_cloud_loss': (_i32, [_vp, _sz, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                             _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dc_mesh_sample': (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'dc_knn_grid_build': (_i32, [_vp, _i32, _i32, _i64, _i64, _i32, _f64, _vp, _sz, _vp]),
     'dc_knn_grid_query': (_i32, [_i64, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _sz, _vp]),

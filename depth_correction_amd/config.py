@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['bias_eval_csv', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
+__all__ = ['bias_eval_csv', 'CLOUD_LOSS_DEFAULTS', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
            'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
@@ -36,7 +36,8 @@ class Loss(metaclass=_Names):
     trace_loss = 'trace_loss'
     icp_loss = 'icp_loss'
     mesh_loss = 'mesh_loss'          # supervised: distance to the dataset's ground-truth mesh (loss.mesh_loss)
-    _unlisted = ('mesh_loss',)       # needs a dataset with a mesh: not part of the default eval_losses sweep
+    cloud_loss = 'cloud_loss'        # supervised: distance to the dataset's surveyed cloud (loss.cloud_loss)
+    _unlisted = ('mesh_loss', 'cloud_loss')   # need a dataset with a mesh / a survey: not part of the default eval_losses sweep
 
 
 class Model(metaclass=_Names):
@@ -126,6 +127,10 @@ def slam_poses_csv(log_dir: str, name: str, slam: str):
     return path
 
 
+# the keys loss.cloud_loss reads from Config.loss_kwargs and their defaults (None: required)
+CLOUD_LOSS_DEFAULTS = {'cloud_point_to_plane': True, 'cloud_squared': False, 'cloud_max_dist': None, 'cloud_inlier_ratio': 1.0}
+
+
 class Config(object):
     def __init__(self, **kwargs):
         self.random_seed = 135
@@ -182,6 +187,11 @@ class Config(object):
         self.loss_offset = False
         self.loss_kwargs = {'sqrt': False, 'normalization': True, 'inlier_max_loss': None, 'inlier_loss_mult': 1.0,
                             'inlier_ratio': 1.0, 'icp_inlier_ratio': 0.3, 'icp_point_to_plane': True}
+        # cloud_loss reads its own keys from loss_kwargs with these defaults (CLOUD_LOSS_DEFAULTS; the default dict above, hence
+        # every written YAML, stays as it was): cloud_point_to_plane True, cloud_squared False, cloud_inlier_ratio 1.0 and
+        # cloud_max_dist, which has no default and must be set.  cloud_samples: the points of the survey a mesh dataset samples
+        # from its mesh (SurveyCloud.from_mesh) when it has no survey of its own
+        self.cloud_samples = 200000
         self.n_opt_iters = 100
         self.optimizer = 'Adam'
         self.optimizer_args = []

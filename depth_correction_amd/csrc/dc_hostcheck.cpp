@@ -7,6 +7,7 @@
 #include "dc_slam_math.h"
 #include "dc_trimath.h"
 #include "dc_meshloss_math.h"
+#include "dc_cloudloss_math.h"
 #include "dc_biasmath.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
@@ -126,6 +127,12 @@ double dc_host_closest_on_triangle(const double* tri, const double* p, double* c
 // dc_mesh_loss's per-point term: x [3], c [3] -> *r = |x - c|, grad [3] = dl/dx; returns l = r (r^2 with `squared`)
 double dc_host_mesh_loss_term(const double* x, const double* c, int squared, double* r, double* grad) {
   return dc::mesh_loss_term(x, c, squared != 0, r, grad);
+}
+
+// dc_cloud_loss's per-point term: x [3], y [3] (the survey point), n [3] (its normal, read with `plane`) -> *r (n . (x - y), or
+// |x - y|), grad [3] = dl/dx; returns l = |r| (r^2 with `squared`)
+double dc_host_cloud_loss_term(const double* x, const double* y, const double* n, int plane, int squared, double* r, double* grad) {
+  return dc::cloud_loss_term(x, y, n, plane != 0, squared != 0, r, grad);
 }
 
 // dc_mesh_sample's sample i of `seed` on the triangle tri [9]: u [3] <- the three uniforms, p [3] <- the point

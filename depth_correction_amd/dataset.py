@@ -121,6 +121,13 @@ class MeshDataset(PlaneDataset):
     def get_mesh(self):
         return self.mesh
 
+    def get_survey(self, n_samples=None, seed=None):
+        """The mesh as a surveyed cloud (survey.mesh_survey): ``n_samples`` (Config.cloud_samples) samples with the face normals."""
+        from .survey import SURVEY_SEED, mesh_survey
+        return mesh_survey(self, n_samples, SURVEY_SEED if seed is None else seed)
+
+    survey = property(lambda self: self.get_survey())
+
     def local_cloud(self, i):
         rng = np.random.default_rng(i)                       # dataset.py:269-286 (choice over the index range)
         sel = rng.choice(self.n_pts, size=self.n_pts // self.n_poses, replace=False)

@@ -167,8 +167,8 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
         return loss, loss_cloud, poses_upd, feat
 
-    if cfg.loss == 'mesh_loss':
-        # supervised: masks[i] = (the sequence's ground-truth mesh, point mask or None) -- see mesh_masks
+    if cfg.loss in ('mesh_loss', 'cloud_loss'):
+        # supervised: masks[i] = (the sequence's ground-truth mesh / survey, point mask or None) -- see mesh_masks, survey_masks
         loss, loss_cloud = loss_fun(clouds, poses_upd, model, masks=masks)
         feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
         return loss, loss_cloud, poses_upd, feat
@@ -222,6 +222,34 @@ def mesh_masks(datasets, names, all_clouds):
             point_mask = torch.cat([c.mask if c.mask is not None else torch.ones((len(c),), dtype=torch.bool, device=c.dirs.device)
                                     for c in clouds])
         out.append((mesh, point_mask))
+    return out
+
+
+def _dataset_survey(ds, name, cfg=None, who='cloud_loss', required=True):
+    """The dataset's surveyed cloud: its own ``survey`` attribute when it carries one, else what get_survey(cfg.cloud_samples) samples
+    from its mesh (MeshDataset, RenderedMeshDataset; reached through the Forwarding wrappers)."""
+    get = getattr(ds, 'get_survey', None)
+    if callable(get):
+        return get(getattr(cfg, 'cloud_samples', None) if cfg is not None else None)
+    own = getattr(ds, 'survey', None)
+    if own is not None and hasattr(own, 'on_device') and hasattr(own, 'normals'):
+        return own
+    if required:
+        raise ValueError('dataset %s gives no surveyed cloud (no survey attribute, no get_survey()): %s needs one' % (name, who))
+    return None
+
+
+def survey_masks(datasets, names, all_clouds, cfg=None):
+    """cloud_loss's per-sequence ``masks``: (the dataset's survey.SurveyCloud, the scans' masks concatenated -- the points the model
+    corrects -- or None when no scan has one)."""
+    out = []
+    for ds, name, clouds in zip(datasets, names, all_clouds):
+        survey = _dataset_survey(ds, name, cfg)
+        point_mask = None
+        if any(c.mask is not None for c in clouds):
+            point_mask = torch.cat([c.mask if c.mask is not None else torch.ones((len(c),), dtype=torch.bool, device=c.dirs.device)
+                                    for c in clouds])
+        out.append((survey, point_mask))
     return out
 
 
@@ -285,6 +313,8 @@ def eval_loss(cfg: Config, test_datasets=None, test_ns=None, model=None, loss_fu
     test_masks = [None] * len(test_datasets)
     if cfg.loss == 'mesh_loss':
         test_masks = mesh_masks(test_datasets, test_names, test_clouds)
+    elif cfg.loss == 'cloud_loss':
+        test_masks = survey_masks(test_datasets, test_names, test_clouds, cfg)
     test_pose_deltas = _test_pose_deltas(cfg, test_datasets)
     if test_ns is None:
         test_ns = [establish_neighborhoods(clouds=clouds, poses=poses, cfg=cfg) for clouds, poses in zip(test_clouds, test_poses)]
@@ -401,7 +431,12 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
     test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
     results = []
     for name, ds in zip(test_names, test_datasets):
-        mesh = _dataset_mesh(ds, name)
+        if callable(getattr(ds, 'get_mesh', None)):
+            mesh = _dataset_mesh(ds, name)
+        else:                                      # a survey and no mesh: the accuracy against the surveyed cloud
+            mesh = _dataset_survey(ds, name, cfg, who='eval_map', required=False)
+            if mesh is None:
+                mesh = _dataset_mesh(ds, name)     # (raises: neither)
         items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in ds]
         poses = run_slam(ds, model, cfg)['slam'] if cfg.map_eval_poses == 'slam' else [pose for _, pose in items]
         moved = []
@@ -625,7 +660,7 @@ def _landscape_kernel(clouds, poses_upd, masks, ns, model, w, cfg: Config):
 def _loop_count(views, cfg: Config):
     """Entries behind the loop's mean: the fused views' counts, else the loss clouds' entries (loss.reduce keeps the finite /
     non-NaN ones under only_finite / skip_nans); nan for the ICP loss, which is no mean over points."""
-    if cfg.loss in ('icp_loss', 'mesh_loss'):                 # (mesh_loss: the mean of the sequences' means)
+    if cfg.loss in ('icp_loss', 'mesh_loss', 'cloud_loss'):   # (mesh_loss, cloud_loss: the mean of the sequences' means)
         return float('nan')
     kw = cfg.loss_kwargs
     total = 0.0

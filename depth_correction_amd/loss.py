@@ -9,6 +9,8 @@ Two execution paths produce the same numbers:
     normalisation, quantile inliers, reductions).
 ``mesh_loss`` is the supervised counterpart: the mean distance of the corrected, posed points to a ground-truth mesh, forward
 and backward (weights, exponents, poses) out of one dc_mesh_loss call per sequence.
+``cloud_loss`` is the same against a surveyed point cloud (survey.SurveyCloud): point-to-plane or point-to-point distances to the
+nearest survey points, gated and trimmed, out of one dc_cloud_loss call per sequence.
 ``icp_loss`` with precomputed correspondences runs as one kernel per scan pair (dc_p2plane_sequence for
 point-to-plane, dc_p2point_sequence for point-to-point distances) including its backward to the model weights and
 poses; ``point_to_point_dist`` as a metric on GPU clouds (scripts/model_poses_learning:142-146) uses the same kernel.
@@ -26,7 +28,7 @@ from .plan import PlanRegistry
 from .segmentation import Planes
 from .utils import trace
 
-__all__ = ['batch_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'mesh_loss', 'min_eigval_loss', 'point_to_plane_dist',
+__all__ = ['batch_loss', 'cloud_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'mesh_loss', 'min_eigval_loss', 'point_to_plane_dist',
            'point_to_point_dist', 'reduce', 'Reduction', 'trace_loss', 'icp_correspondences']
 
 
@@ -381,6 +383,12 @@ class _MeshLossPlan(object):
     evaluation to the next (a point's nearest face changes little between two optimiser steps)."""
 
     def __init__(self, seq_clouds, mesh, point_mask, with_model):
+        self._fields(seq_clouds, point_mask, with_model)
+        self.mesh = mesh
+        self.bvh = mesh.on_device(self.device)[3]
+        self.leaf_hint = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+
+    def _fields(self, seq_clouds, point_mask, with_model):
         dev = seq_clouds[0].dirs.device
         sizes = [len(c) for c in seq_clouds]
 
@@ -402,10 +410,7 @@ class _MeshLossPlan(object):
         for n in sizes:
             ptr_host.append(ptr_host[-1] + n)
         self.scan_ptr = torch.tensor(ptr_host, dtype=torch.int64, device=dev)
-        self.mesh = mesh
-        self.bvh = mesh.on_device(dev)[3]
         self.mask = None if point_mask is None else torch.as_tensor(point_mask, device=dev).to(torch.bool).contiguous()
-        self.leaf_hint = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
         self._ws = {}
 
     def eval(self, poses12, kind=None, w=None, e=None, squared=False, max_dist=None, want_exponent=False, want_points=False):
@@ -485,8 +490,157 @@ def mesh_loss(clouds, poses=None, model=None, masks=None, **kwargs):
     return loss / len(clouds), loss_cloud
 
 
+# ---- supervised loss against a surveyed point cloud ----------------------------------------------------------------
+class _CloudLossSequence(torch.autograd.Function):
+    """cloud_loss of one sequence through dc_cloud_loss: forward and backward come out of the same host call."""
+
+    @staticmethod
+    def forward(ctx, w, exponent, poses, plan, kind, opts):
+        P12 = poses.detach().to(torch.float64)[:, :3, :].reshape(-1, 12).contiguous()
+        wv = None if w is None else w.detach().reshape(-1).to(torch.float64).contiguous()
+        ev = None if exponent is None else exponent.detach().reshape(-1).to(torch.float64).contiguous()
+        want_e = isinstance(exponent, torch.Tensor) and bool(ctx.needs_input_grad[1])
+        out = plan.eval(P12, kind, wv, ev, want_exponent=want_e, **dict(opts))
+        ctx.save_for_backward(out)
+        ctx.meta = (None if w is None else (w.shape, w.dtype), poses.dtype, poses.shape[0],
+                    exponent.shape if isinstance(exponent, torch.Tensor) else None)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        out, = ctx.saved_tensors
+        wmeta, pdt, ns, eshape = ctx.meta
+        nt = (out.numel() - 6 - 12 * ns) // 2
+        gw = ge = gT = None
+        if wmeta is not None and ctx.needs_input_grad[0]:
+            gw = (g * out[6:6 + nt]).reshape(wmeta[0]).to(wmeta[1])
+        if eshape is not None and ctx.needs_input_grad[1]:
+            ge = (g * out[6 + nt:6 + 2 * nt]).reshape(eshape)
+        if ctx.needs_input_grad[2]:
+            gT = torch.zeros((ns, 4, 4), dtype=torch.float64, device=out.device)
+            gT[:, :3, :] = (g * out[6 + 2 * nt:]).reshape(ns, 3, 4)
+            gT = gT.to(pdt)
+        return gw, ge, gT, None, None, None
+
+
+class _CloudLossPlan(_MeshLossPlan):
+    """What is constant over the optimisation of one sequence against its survey: the scans' fields concatenated scan-major, the
+    scan offsets, the survey's device copies with their grid (built once, its query buffer sized here), the loss mask, the
+    workspace."""
+
+    def __init__(self, seq_clouds, survey, point_mask, with_model):
+        self._fields(seq_clouds, point_mask, with_model)
+        self.survey = survey
+        self.survey_dev = survey.on_device(self.device).reserve(self.n)
+
+    def eval(self, poses12, kind=None, w=None, e=None, plane=True, squared=False, max_dist=None, inlier_ratio=1.0, want_exponent=False,
+             want_points=False):
+        nt = 0 if not kind else w.numel()
+        ws = self._ws.get(nt)
+        if ws is None:
+            ws = self._ws[nt] = ops.cloud_loss_workspace(self.n, self.n_scans, nt, self.device)
+        return ops.cloud_loss(self.survey_dev, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, plane=plane, squared=squared,
+                              max_dist=max_dist, inlier_ratio=inlier_ratio, want_points=want_points, want_exponent=want_exponent, ws=ws)
+
+
+_cloud_plans = PlanRegistry()
+
+
+def _cloud_sequence_plan(seq_clouds, survey, point_mask, with_model):
+    fields = [t for c in seq_clouds for t in (c.vps, c.dirs, c.depth, c.inc_angles, c.mask)] + [point_mask, survey]
+    return _cloud_plans.get(fields, (bool(with_model),), lambda: _CloudLossPlan(seq_clouds, survey, point_mask, with_model))
+
+
+def _posed_points64(seq_clouds, seq_poses, model, keep=None):
+    """x in fp64 through the model and the poses, scan-major (torch autograd); ``keep`` [N] bool: only these rows are formed (a row
+    with a NaN input would otherwise put 0 x NaN into the pose gradient)."""
+    parts, off = [], 0
+    for i, c in enumerate(seq_clouds):
+        n = len(c)
+        c64 = DepthCloud(vps=c.vps.double().expand(n, 3), dirs=c.dirs.double(), depth=c.depth.double(),
+                         inc_angles=None if c.inc_angles is None else c.inc_angles.double(), mask=c.mask)
+        if keep is not None and not bool(keep[off:off + n].all()):
+            c64 = c64[keep[off:off + n]]
+        off += n
+        if model is not None:
+            c64 = model(c64)
+        if seq_poses is not None:
+            c64 = c64.transform(seq_poses[i].double())
+        parts.append(c64.vps + c64.depth * c64.dirs)
+    return torch.cat(parts)
+
+
+def _unfused_cloud_sequence(seq_clouds, seq_poses, model, survey, point_mask, plane, squared, max_dist, inlier_ratio):
+    """The same loss from tensor operations: x in fp64 through the model and the poses, the nearest survey points (detached) from
+    ops.knn, the inlier threshold from ops.quantile, torch autograd.  For models without a kernel kind, and what the fused form is
+    tested against."""
+    dev = seq_clouds[0].dirs.device
+    with torch.no_grad():
+        keep = torch.cat([torch.isfinite(c.vps.expand(len(c), 3)).all(dim=1) & torch.isfinite(c.dirs).all(dim=1)
+                          & torch.isfinite(c.depth).reshape(-1) for c in seq_clouds])
+    x = _posed_points64(seq_clouds, seq_poses, model, keep)
+    sd = survey.on_device(dev)
+    in_mask = torch.ones((x.shape[0],), dtype=torch.bool, device=dev) if point_mask is None \
+        else torch.as_tensor(point_mask, device=dev).to(torch.bool)[keep]
+    query = torch.where(in_mask[:, None], x.detach(), torch.full_like(x, float('nan'))).contiguous()
+    dist, idx = ops.knn(sd.points, 1, r=float(max_dist), query=query)
+    dist, idx = dist[:, 0].contiguous(), idx[:, 0]
+    used = (idx >= 0) & in_mask & torch.isfinite(x.detach()).all(dim=1)
+    if inlier_ratio < 1.0 and bool(used.any()):
+        used = used & (dist <= ops.quantile(dist, inlier_ratio))
+    j = idx[used].long()
+    d = x[used] - sd.points[j]
+    if plane:
+        r = (sd.normals[j] * d).sum(dim=-1)
+        return (r * r).mean() if squared else r.abs().mean()          # (abs: zero gradient at r = 0, as in the kernel)
+    sq = (d * d).sum(dim=-1)
+    if squared:
+        return sq.mean()
+    pos = sq > 0
+    return (torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))) * pos).mean()
+
+
+def cloud_loss(clouds, poses=None, model=None, masks=None, **kwargs):
+    """Supervised loss against surveyed clouds over lists of sequences of scans: the mean distance of the corrected, posed points of
+    a sequence to their nearest survey points -- to the planes through them (``cloud_point_to_plane``, default True) or to the points
+    themselves; ``cloud_squared`` (False): the mean squared distance; ``cloud_max_dist`` (required): points without a survey point
+    within it are left out; ``cloud_inlier_ratio`` (1.0): below 1, points whose nearest-neighbour distance exceeds that quantile of the
+    matched distances are left out (the reference's inlier rule, loss.py:440-452) -- averaged over the sequences like icp_loss.
+    ``masks[i]`` = (survey.SurveyCloud, bool point mask [N_i] or None) of sequence ``i``.  Differentiable to the model's weights and
+    exponents and to the poses, the correspondences held constant; GPU clouds with a kernel model (or none) and poses take one
+    dc_cloud_loss call per sequence (``fused=False`` forces the tensor form)."""
+    if not clouds or not clouds[0]:
+        raise ValueError('cloud_loss needs at least one sequence with one scan')
+    if not clouds[0][0].dirs.is_cuda:
+        raise RuntimeError('cloud_loss: the clouds must live on the GPU (depth_correction_amd has no CPU path)')
+    if masks is None or len(masks) != len(clouds):
+        raise ValueError('cloud_loss needs masks[i] = (survey, point mask or None) for every sequence')
+    max_dist = kwargs.get('cloud_max_dist')
+    if max_dist is None:
+        raise ValueError("cloud_loss needs loss_kwargs['cloud_max_dist'] (metres, finite, > 0)")
+    opts = dict(plane=bool(kwargs.get('cloud_point_to_plane', True)), squared=bool(kwargs.get('cloud_squared', False)),
+                max_dist=float(max_dist), inlier_ratio=float(kwargs.get('cloud_inlier_ratio', 1.0)))
+    kind = getattr(model, 'kernel_kind', None) if model is not None else None
+    fused = kwargs.get('fused', True) and poses is not None and (model is None or kind)
+    loss, loss_cloud = 0., []
+    for i, seq in enumerate(clouds):
+        survey, point_mask = masks[i] if isinstance(masks[i], (tuple, list)) else (masks[i], None)
+        if survey is None or not hasattr(survey, 'on_device') or not hasattr(survey, 'normals'):
+            raise ValueError('cloud_loss: sequence %d has no surveyed cloud (masks[%d] = (survey, point mask))' % (i, i))
+        if fused:
+            w, e = model.kernel_params() if kind else (None, None)
+            plan = _cloud_sequence_plan(seq, survey, point_mask, bool(kind))
+            seq_poses = poses[i] if isinstance(poses[i], torch.Tensor) else torch.stack(list(poses[i]))
+            loss_seq = _CloudLossSequence.apply(w, e, seq_poses, plan, kind, tuple(sorted(opts.items())))
+        else:
+            loss_seq = _unfused_cloud_sequence(seq, None if poses is None else poses[i], model, survey, point_mask, **opts)
+        loss = loss + loss_seq
+        loss_cloud.append(_MovedClouds(seq, None if poses is None else poses[i], model, loss))
+    return loss / len(clouds), loss_cloud
+
+
 def loss_by_name(name):
-    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss', 'mesh_loss')
+    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss', 'mesh_loss', 'cloud_loss')
     return globals()[name]
 
 

@@ -23,7 +23,7 @@ import torch
 from . import ops
 
 __all__ = ['bias_statistics', 'chamfer_distance', 'depth_bias', 'fit_bias', 'fitted_model', 'map_accuracy', 'map_statistics',
-           'point_to_mesh_distance']
+           'point_to_cloud_distance', 'point_to_mesh_distance']
 
 BIAS_TOTALS, BIAS_BIN_COLS = 5, 9                    # include/dc_hip.h: DC_BIAS_TOTALS, DC_BIAS_BIN_COLS
 BIAS_TOTAL_NAMES = ('rays', 'masked', 'hits', 'used', 'beyond_gate')
@@ -82,6 +82,27 @@ def point_to_mesh_distance(points, mesh, max_dist=None, return_closest=False):
     return (dist, face, closest) if return_closest else dist
 
 
+def point_to_cloud_distance(points, survey, max_dist=None, return_closest=False):
+    """Distance from every point (tensor [N,3] on a GPU, or a DepthCloud's points) to the nearest point of ``survey``
+    (survey.SurveyCloud) -> [N] in the dtype of the points (computed in fp64) through the survey's cached grid (built once; what
+    chamfer_distance rebuilds at every call); with ``return_closest`` also the survey indices i32 [N] and the nearest points f64
+    [N,3].  ``max_dist``: farther points get inf (index -1, nearest point NaN), as does a row holding a NaN or an infinity."""
+    pts = _map_points(points)
+    sd = survey.on_device(pts.device).reserve(pts.shape[0])
+    n = pts.shape[0]
+    if n == 0:
+        dist, idx = pts.new_zeros((0,), dtype=torch.float64), torch.zeros((0,), dtype=torch.int32, device=pts.device)
+    else:
+        dist, idx = ops.knn_grid_query(sd.grid, pts.to(torch.float64).contiguous(), sd.identity_pose(), 1, r=max_dist)
+        dist, idx = dist[:, 0], idx[:, 0]
+        dist = torch.where(idx >= 0, dist, torch.full_like(dist, float('inf')))
+    if not return_closest:
+        return dist.to(pts.dtype)
+    closest = sd.points[idx.clamp(min=0).long()]
+    closest = torch.where((idx >= 0)[:, None], closest, torch.full_like(closest, float('nan')))
+    return dist.to(pts.dtype), idx, closest
+
+
 def _np_quantile(v, ratio):
     return torch.quantile(v, ratio) if v.numel() else v.new_tensor(float('nan'))
 
@@ -108,12 +129,18 @@ def map_statistics(dist, signed=None, inlier_ratio=0.8, quantile=None):
 
 
 def map_accuracy(points, mesh, inlier_ratio=0.8, n_samples=None, seed=135):
-    """Accuracy of a map (points [N,3] on a GPU or a DepthCloud, world frame) against the ground-truth ``mesh``: dict of floats
+    """Accuracy of a map (points [N,3] on a GPU or a DepthCloud, world frame) against the ground-truth ``mesh`` (or a
+    survey.SurveyCloud: nearest-point distances, signed_mean NaN, no completeness_mean): dict of floats
     n, mean, rms, median, max, trimmed_mean (what point_to_point_dist with icp_inlier_ratio = 0.8 reports in
     scripts/mapping_accuracy:112-115) and signed_mean, the mean of n_face . (p - closest): which side of the surface the map
     sits on (at edges and vertices the sign is that of the winning face).  With ``n_samples`` also completeness_mean: the
     chamfer distance from mesh.sample(n_samples, seed) to the map -- surface the map does not cover."""
     pts = _map_points(points)
+    if hasattr(mesh, 'normals') and not hasattr(mesh, 'faces'):
+        # a survey.SurveyCloud in place of the mesh (scripts/mapping_accuracy:82-118 as it stands): the same statistics of the
+        # nearest-point distances; no surface, hence no side (signed_mean NaN) and no completeness
+        dist = point_to_cloud_distance(pts, mesh)
+        return map_statistics(dist, None, inlier_ratio, quantile=lambda v, r: ops.quantile(v.contiguous(), r))
     dist, face, closest = point_to_mesh_distance(pts, mesh, return_closest=True)
     normals = mesh.on_device(pts.device)[2]
     signed = ((pts.to(torch.float64) - closest) * normals[face.clamp(min=0).long()]).sum(dim=1)

@@ -16,7 +16,7 @@ __all__ = [
     'knn', 'radius_neighbors', 'knn_transpose', 'BlockTable', 'block_table', 'table_to_csr', 'spatial_order', 'points_fwd', 'points_bwd', 'features_fwd',
     'features_bwd', 'consistency_fwd', 'consistency_bwd', 'mask_bounds', 'valid_count', 'dispersion', 'p2plane_pair', 'p2point_pair',
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
-    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace',
+    'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace', 'cloud_loss', 'cloud_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update',
 ]
@@ -1470,6 +1470,65 @@ def quantile(v, ratio, stop=None, out=None, ws=None):
     out = torch.empty((1,), dtype=torch.float64, device=v.device) if out is None else need(out, (1,), torch.float64, 'out', v.device)
     check(lib().dc_quantile(ptr(v), n, float(ratio), ptr(stop), ptr(out), ptr(ws), ws.numel(), stream_ptr()), 'dc_quantile')
     return out
+
+
+def cloud_loss_workspace(n, n_scans, n_terms, device):
+    """Workspace of cloud_loss for the given sizes (uint8 tensor)."""
+    return _ws(lib().dc_cloud_loss_workspace_bytes(int(n), int(n_scans), int(n_terms)), device)
+
+
+@on_device
+def cloud_loss(survey_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=None, mask=None, plane=True, squared=False, max_dist=None,
+               inlier_ratio=1.0, want_points=False, want_exponent=False, out=None, ws=None):
+    """Mean point-to-plane (``plane``) or point-to-point distance of the corrected, posed points of a sequence to their nearest points
+    of a surveyed cloud, with its gradient, in one host call (dc_cloud_loss).  ``survey_dev``: survey.SurveyOnDevice (points, unit
+    normals, the persistent k-NN grid); ``ps``, ``scan_ptr``, ``poses12``, ``mask`` as for mesh_loss.  ``max_dist`` (required, finite,
+    > 0): points without a survey point within it are gated; ``inlier_ratio`` < 1: points whose nearest-neighbour distance exceeds
+    that quantile of the matched distances are trimmed.  Returns out f64 [6 + 2P + 12 S] = {mean loss, used, gated, trimmed, invalid,
+    threshold, dL/dw, dL/dexponent (zero unless ``want_exponent``), dL/d[R|t]}; with ``want_points`` also (idx i32 [N], dist f64 [N],
+    resid f64 [N]) -- the survey point, its distance and the residual r of every used point, -1 / inf / NaN elsewhere."""
+    dev = survey_dev.device
+    if ps.device != dev:
+        raise RuntimeError('points are on %s, the survey on %s' % (ps.device, dev))
+    kind, nt, w, e = _model_args(model_kind, w, e, ps)
+    ns = _check_scan_ptr(ps, scan_ptr)
+    need(poses12, (ns, 12), dtype=torch.float64, name='poses[S,12]', device=dev)
+    if mask is not None:
+        need(mask, (ps.n,), dtype=torch.bool, name='mask', device=dev)
+    if max_dist is None:
+        raise ValueError('cloud_loss needs max_dist (finite, > 0)')
+    md, ratio = float(max_dist), float(inlier_ratio)
+    if not (md > 0.0 and md < float('inf')):
+        raise ValueError('max_dist must be finite and > 0, got %r' % (max_dist,))
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError('inlier_ratio must lie in [0, 1], got %r' % (inlier_ratio,))
+    need(survey_dev.points, (None, 3), dtype=torch.float64, name='survey points', device=dev)
+    need(survey_dev.normals, (survey_dev.points.shape[0], 3), dtype=torch.float64, name='survey normals', device=dev)
+    survey_dev.reserve(ps.n)
+    grid = survey_dev.grid
+    n_out = 6 + 2 * nt + 12 * ns
+    if out is None:
+        out = torch.empty((n_out,), dtype=torch.float64, device=dev)
+    else:
+        need(out, (n_out,), dtype=torch.float64, name='out', device=dev)
+    nbytes = lib().dc_cloud_loss_workspace_bytes(ps.n, ns, nt)
+    if ws is None:
+        ws = _ws(nbytes, dev)
+    else:
+        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
+        if ws.shape[0] < nbytes:
+            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    idx = dist = resid = None
+    if want_points:
+        idx = torch.empty((ps.n,), dtype=torch.int32, device=dev)
+        dist = torch.empty((ps.n,), dtype=torch.float64, device=dev)
+        resid = torch.empty((ps.n,), dtype=torch.float64, device=dev)
+    check(lib().dc_cloud_loss(ptr(grid.ws), grid.ws.numel(), grid.n_query_max, ptr(survey_dev.points), ptr(survey_dev.normals), grid.n,
+                              ptr(ps.vps), ptr(ps.dirs), ptr(ps.depth), ptr(ps.inc), ptr(ps.lmask), ptr(mask), dtype_code(ps.dirs), ps.n,
+                              ptr(scan_ptr), ptr(poses12), ns, kind, nt, ptr(w), ptr(e), int(bool(want_exponent)), int(bool(plane)),
+                              int(bool(squared)), md, ratio, ptr(idx), ptr(dist), ptr(resid), ptr(out), ptr(ws), ws.shape[0],
+                              stream_ptr()), 'dc_cloud_loss')
+    return (out, idx, dist, resid) if want_points else out
 
 
 def icp_blocks(m):

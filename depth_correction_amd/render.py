@@ -269,6 +269,13 @@ class RenderedMeshDataset(object):
             self._state['mesh'] = self._load_mesh(self.path)
         return self._state['mesh']
 
+    def get_survey(self, n_samples=None, seed=None):
+        """The mesh as a surveyed cloud (survey.mesh_survey): ``n_samples`` (Config.cloud_samples) samples with the face normals."""
+        from .survey import SURVEY_SEED, mesh_survey
+        return mesh_survey(self, n_samples, SURVEY_SEED if seed is None else seed, device=self.device)
+
+    survey = property(lambda self: self.get_survey())
+
     def __getitem__(self, i):
         if isinstance(i, (int, np.integer)):
             id = self.ids[i]

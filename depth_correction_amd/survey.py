@@ -1,0 +1,157 @@
+"""Surveyed point clouds as ground truth (the FEE corridor's ``global_cloud``, datasets/fee_corridor.py:169-178,240-248; the board
+cloud of scripts/map_bias_removal:579-737).
+
+``SurveyCloud`` has the role ``mesh.TriangleMesh`` has for the rendered datasets: float64 points ``[M,3]`` and unit normals
+``[M,3]`` kept where they were given (host or device) and, on demand, on a GPU together with the k-NN grid of one
+``dc_knn_grid_build`` -- built once and searched by every ``dc_cloud_loss`` / ``metrics.point_to_cloud_distance`` call after it.
+The orientation of a normal is irrelevant (the plane residual is taken by absolute value).  Rows whose normal is not finite
+can never be matched by the plane form: they are dropped at construction (``n_dropped``).
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+import torch
+
+__all__ = ['SurveyCloud', 'SurveyOnDevice', 'mesh_survey', 'DEFAULT_SAMPLES', 'SURVEY_SEED']
+
+DEFAULT_SAMPLES = 200000       # Config.cloud_samples
+SURVEY_SEED = 135              # the fixed seed of the surveys the mesh datasets sample
+
+
+class SurveyOnDevice(object):
+    """Device copies of a survey and its persistent grid: points / normals f64 [M,3], ``grid`` (ops.KnnGrid, k = 1)."""
+
+    def __init__(self, points, normals, grid):
+        self.points, self.normals, self.grid = points, normals, grid
+        self.device = points.device
+        self._pose = None
+
+    @property
+    def n(self):
+        return self.points.shape[0]
+
+    def identity_pose(self):
+        if self._pose is None:
+            self._pose = torch.eye(4, dtype=torch.float64, device=self.device)
+        return self._pose
+
+    def reserve(self, n_query):
+        """The grid's query buffer holds ``n_query_max`` rows: rebuild the grid (the same grid, a larger buffer) when more are
+        asked for.  A plan asks once, before training starts."""
+        if n_query > self.grid.n_query_max:
+            from . import ops
+            self.grid = ops.knn_grid_build(self.points, int(n_query), 1)
+        return self
+
+
+class SurveyCloud(object):
+    """float64 points [M,3] and unit normals [M,3] of a surveyed cloud."""
+
+    MIN_QUERIES = 1 << 16          # rows of the grid's query buffer on first use (SurveyOnDevice.reserve grows it)
+
+    def __init__(self, points, normals):
+        points, normals = torch.as_tensor(points), torch.as_tensor(normals)
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
+            raise ValueError('points must be a non-empty [M,3] array, got shape %s' % (tuple(points.shape),))
+        if normals.shape != points.shape:
+            raise ValueError('normals must have the shape of points %s, got %s' % (tuple(points.shape), tuple(normals.shape)))
+        points = points.detach().to(torch.float64)
+        normals = normals.detach().to(device=points.device, dtype=torch.float64)
+        if not bool(torch.isfinite(points).all()):
+            raise ValueError('survey points must be finite')
+        keep = torch.isfinite(normals).all(dim=1)
+        self.n_dropped = int((~keep).sum())
+        if self.n_dropped:
+            warnings.warn('SurveyCloud: dropped %d of %d points whose normal is not finite' % (self.n_dropped, points.shape[0]))
+            points, normals = points[keep], normals[keep]
+            if points.shape[0] == 0:
+                raise ValueError('no survey point has a finite normal')
+        norm = torch.linalg.norm(normals, dim=1, keepdim=True)
+        if bool((norm == 0).any()):
+            raise ValueError('survey normals must not be zero')
+        self.points = points.contiguous()
+        self.normals = (normals / norm).contiguous()
+        self._device = {}
+
+    def __len__(self):
+        return self.points.shape[0]
+
+    def __repr__(self):
+        return 'SurveyCloud(%d points%s)' % (len(self), ', %d dropped' % self.n_dropped if self.n_dropped else '')
+
+    @property
+    def bounds(self):
+        return self.points.min(dim=0).values.cpu().numpy(), self.points.max(dim=0).values.cpu().numpy()
+
+    # ---- constructors ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def from_points(points, normals=None, nn_k=None, nn_r=None, device='cuda'):
+        """Survey of points [M,3]; without ``normals`` they are computed once by the package's feature kernels over the ``nn_k``
+        nearest neighbours / the ball ``nn_r`` (as DepthCloud.update_all; default nn_k = 10) on ``device`` -- a point with too few
+        neighbours for a plane gets a NaN normal and is dropped."""
+        if normals is None:
+            from .depth_cloud import DepthCloud
+            dev = torch.device(device)
+            if dev.type != 'cuda' or not torch.cuda.is_available():
+                raise RuntimeError('computing survey normals needs a GPU: depth_correction_amd has no CPU path (or pass normals)')
+            pts = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float64).contiguous()
+            cloud = DepthCloud.from_points(pts)
+            if not nn_k and not nn_r:
+                nn_k = 10
+            cloud.update_all(k=nn_k or None, r=nn_r or None)
+            points, normals = pts, cloud.normals.detach()
+        return SurveyCloud(points, normals)
+
+    @staticmethod
+    def from_file(path, nn_k=None, nn_r=None, device='cuda'):
+        """Survey of an ``.npz`` cloud (scan_io.read_points_npz: a plain [M,3+] array, or the structured layout of
+        fee_corridor.py:35-38 with x, y, z and optionally normal_x, normal_y, normal_z)."""
+        from numpy.lib.recfunctions import structured_to_unstructured
+        from .scan_io import read_points_npz
+        arr = read_points_npz(path)
+        normals = None
+        if arr.dtype.names:
+            if 'normal_x' in arr.dtype.names:
+                normals = structured_to_unstructured(arr[['normal_x', 'normal_y', 'normal_z']]).astype(np.float64)
+            arr = structured_to_unstructured(arr[['x', 'y', 'z']])
+        pts = np.ascontiguousarray(arr[:, :3], dtype=np.float64)
+        return SurveyCloud.from_points(pts, normals, nn_k=nn_k, nn_r=nn_r, device=device)
+
+    @staticmethod
+    def from_mesh(mesh, n_samples, seed=135, device='cuda'):
+        """``n_samples`` area-weighted samples of a mesh.TriangleMesh with the normals of the sampled faces (TriangleMesh.sample): a
+        survey whose true surface is known."""
+        pts, normals, _ = mesh.sample(int(n_samples), seed=seed, device=device)
+        return SurveyCloud(pts, normals)
+
+    # ---- device side ----------------------------------------------------------------------------------------------------------
+    def on_device(self, device):
+        """SurveyOnDevice on ``device`` (a GPU): the copies and the grid are made once."""
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('a survey is searched on a GPU (device %s): depth_correction_amd has no CPU path' % device)
+        if not torch.cuda.is_available():
+            raise RuntimeError('a survey is searched on a GPU, and torch sees none: depth_correction_amd has no CPU path')
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        got = self._device.get(device)
+        if got is None:
+            from . import ops
+            p = self.points.to(device).contiguous()
+            n = self.normals.to(device).contiguous()
+            got = self._device[device] = SurveyOnDevice(p, n, ops.knn_grid_build(p, self.MIN_QUERIES, 1))
+        return got
+
+
+def mesh_survey(ds, n_samples=None, seed=SURVEY_SEED, device=None):
+    """The survey a mesh dataset (one with get_mesh()) samples from its mesh: SurveyCloud.from_mesh(mesh, n_samples, seed), built at
+    the first call and kept per (n_samples, seed) -- in the state the dataset's slices share, when it has one."""
+    n = int(n_samples or DEFAULT_SAMPLES)
+    state = getattr(ds, '_state', None)
+    cache = state.setdefault('surveys', {}) if isinstance(state, dict) else ds.__dict__.setdefault('_surveys', {})
+    got = cache.get((n, int(seed)))
+    if got is None:
+        got = cache[(n, int(seed))] = SurveyCloud.from_mesh(ds.get_mesh(), n, seed=int(seed), device=device or getattr(ds, 'device', 'cuda'))
+    return got

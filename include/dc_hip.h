@@ -976,6 +976,32 @@ int dc_knn_grid_query(int64_t n, int64_t n_query_max, const double* query, int64
 size_t dc_quantile_workspace_bytes(void);
 int dc_quantile(const double* v, int64_t n, double ratio, const int32_t* stop, double* threshold_out, void* ws, size_t ws_bytes,
                 dcStream_t stream);
+/* ---- supervised training against a surveyed cloud (depth_correction_amd/csrc/dc_cloudloss.hip; DESIGN "Supervised training
+ * against a surveyed cloud"; what scripts/map_bias_removal:579-737 trains with point_to_plane_dist(clouds=[cloud_corr, board_cloud],
+ * icp_inlier_ratio=1.0) and datasets/fee_corridor.py:240-248 reports against the surveyed global cloud) ----
+ * The mean distance of the corrected, posed points of a sequence to their nearest survey points, and its gradient, in one call (no
+ * floating-point atomics: the same inputs give the same bits).  The points and the model follow dc_mesh_loss: point j of scan s is
+ * x_j = R_s (vp_j + d'_j dir_j) + t_s exactly as dc_points_fwd forms it in fp64 (scan_ptr DEVICE int64 [n_scans+1], ascending from 0
+ * to n, NULL with n_scans == 1).  The survey: map_points / map_normals DEVICE double [n_map,3] (unit normals, read with `plane`
+ * only) and grid_ws, the workspace dc_knn_grid_build(map_points, 3, DC_F64, n_map, n_query_max, 1, ...) left its grid in (n <=
+ * n_query_max; the call uses the grid's query buffer, the grid itself is only read).
+ * y_j = the 1-NN of x_j by dc_knn_grid_query with k = 1, r = max_dist (its bits: smallest d^2, a tie to the lower index, d^2 <
+ * max_dist^2); max_dist must be finite and > 0, inlier_ratio in [0, 1] (DC_ERR_ARG).  A point in mask (uint8 [n], optional) is
+ * INVALID (x_j not finite), GATED (no survey point within max_dist), TRIMMED (inlier_ratio < 1 and |x_j - y_j| > dc_quantile of the
+ * matched distances at inlier_ratio) or USED.  plane: r_j = n_y . (x_j - y_j), l_j = |r_j|; otherwise r_j = l_j = |x_j - y_j|;
+ * squared: l_j = r_j^2.  The correspondence is a constant of the gradient; dl/dx = 0 where l = 0.
+ * out double [6 + 2 n_terms + 12 n_scans] = {L = sum l / M, M = used, gated, trimmed, invalid, threshold (+inf with inlier_ratio ==
+ * 1 or n == 0), dL/dw, dL/dexponent (zero unless want_exponent), dL/d[R|t] per scan row-major 3 x 4}; M == 0: L = NaN, zero
+ * gradients.  idx_out int32 [n], dist_out double [n] (|x_j - y_j|), resid_out double [n] (r_j), each optional: -1 / +inf / NaN for a
+ * point that is not used.  ws: dc_cloud_loss_workspace_bytes(n, n_scans, n_terms) bytes (DC_ERR_WORKSPACE).  n == 0 and scans
+ * without points are legal.  No allocation, copy or synchronisation. */
+size_t dc_cloud_loss_workspace_bytes(int64_t n, int n_scans, int n_terms);
+int dc_cloud_loss(void* grid_ws, size_t grid_ws_bytes, int64_t n_query_max, const double* map_points, const double* map_normals,
+                  int64_t n_map, const void* vps, const void* dirs, const void* depth, const void* inc, const uint8_t* lmask,
+                  const uint8_t* mask, int dtype, int64_t n, const int64_t* scan_ptr, const double* poses, int n_scans, int model_kind,
+                  int n_terms, const double* w, const double* e, int want_exponent, int plane, int squared, double max_dist,
+                  double inlier_ratio, int32_t* idx_out, double* dist_out, double* resid_out, double* out, void* ws, size_t ws_bytes,
+                  dcStream_t stream);
 /* Blocks of dc_icp_accumulate for m reading points (partials double [blocks * DC_ICP_PARTIALS]). */
 int dc_icp_blocks(int64_t m);
 /* state double [DC_ICP_STATE_COUNT] <- the prior (DEVICE double [16]) as estimate and bound origin, history cleared; status int32 [4]
