@@ -19,25 +19,40 @@ namespace dc {
 
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
 template <typename R> DC_HD R rsqrt_(R x) { return (R)rsqrt((double)x); }       // v_rsq_f64 + refinement, no division
-// 1 / x for a normal, finite, non-zero x (counts, traces, clamped denominators): v_rcp_f64 (~2^-26) and two
-// Newton steps instead of the IEEE division sequence (div_scale x2, rcp, fma x5, div_fmas, div_fixup); <= 1 ulp.
+// 1 / x for a normal, finite, non-zero x (counts, traces, clamped denominators): v_rcp_f64 and two Newton steps instead of the IEEE
+// division sequence (div_scale x2, rcp, fma x5, div_fmas, div_fixup); <= 1 ulp.
+// Measured on an MI355X over 2^20 arguments: v_rcp_f64 is within 4.6e-8 (2^-24.4) and v_rsq_f64 within 5.2e-8 (2^-24.2) of the
+// exact value; one Newton step leaves 2.1e-15 and 4.1e-15, two leave the rounding of the last operation (1.4e-16 for the root).
 DC_HD double recip_(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
   return fma(fma(-x, r, 1.0), r, r);
 }
-// the same with ONE Newton step (v_rcp_f64 is good to ~2^-26, so ~2^-52 afterwards) and the raw instruction (a correction
-// term that is itself ~1e-6 of its sum needs no more); rsqrt likewise
+// the same with ONE Newton step (a few 1e-15 relative: for a factor that scales its result as a whole, like the reciprocal of a
+// trace, or that normalises a vector of which the direction is used, or whose length error is budgeted: see rsqrt2_) and the raw instruction (a correction term that is itself
+// ~1e-6 of its sum needs no more); rsqrt likewise
 DC_HD double recip1_(double x) {
   const double r = __builtin_amdgcn_rcp(x);
   return fma(fma(-x, r, 1.0), r, r);
 }
 DC_HD double rcp_raw_(double x) { return __builtin_amdgcn_rcp(x); }
-DC_HD double rsq_raw_(double x) { return __builtin_amdgcn_rsq(x); }              // v_rsq_f64 as it stands (~2^-26)
+DC_HD double rsq_raw_(double x) { return __builtin_amdgcn_rsq(x); }              // v_rsq_f64 as it stands (~2^-24)
 DC_HD double rsqrt1_(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   const double e = fma(-x * y, y, 1.0);          // 1 - x y^2
   return fma(0.5 * y, e, y);
+}
+// TWO Newton steps: for a factor whose error reaches an eigenvalue at first order (the basis of eig3_sym_v2's 2x2 problem).  A vector
+// normalised with rsqrt1_ is off unit length by up to 4e-15, which is harmless where only its direction or a Rayleigh CORRECTION uses
+// it, but u . A u of such a vector is off by twice that times the eigenvalue: with one step eig3_sym_v2 reached 1.0e-14 lam_max on
+// isotropic neighbourhoods of 16 points, where eig3_sym is at 5e-15 (tests/test_gpu_eig_spectra.py).
+// (The deflation branch of eig3_smallest_unit keeps one step for iso: there w = iso x u inherits iso's length error, so m11 = w . A w
+// and m01 carry it at first order too -- up to 2 * 4e-15 lam1, 3.5e-15 lam_max where lam1 / lam_max ~ 0.44 (cos 3 ang ~ 0.999);
+// 2.4e-15 measured, inside the 1e-14 contract, and needles, lam1 << lam_max, do not feel it.)
+DC_HD double rsqrt2_(double x) {
+  double y = __builtin_amdgcn_rsq(x);
+  y = fma(0.5 * y, fma(-x * y, y, 1.0), y);
+  return fma(0.5 * y, fma(-x * y, y, 1.0), y);
 }
 // cos for the root estimate (argument in [0, pi], result only seeds a Newton step): the hardware cosine.  cosf() would
 // drag in the large-argument range reduction (~250 instructions, computed for every lane because it is select-based).
@@ -52,6 +67,7 @@ DC_HD double recip1_(double x) { return 1.0 / x; }
 DC_HD double rcp_raw_(double x) { return 1.0 / x; }
 DC_HD double rsq_raw_(double x) { return 1.0 / sqrt(x); }
 DC_HD double rsqrt1_(double x) { return 1.0 / sqrt(x); }
+DC_HD double rsqrt2_(double x) { return 1.0 / sqrt(x); }
 DC_HD float cos_est_(float x) { return cosf(x); }
 DC_HD float sqrt_est_(float x) { return sqrtf(x); }
 DC_HD float rcp_est_(float x) { return 1.0f / x; }
@@ -327,8 +343,10 @@ DC_HD void eig3_smallest_unit(double a00, double a01, double a02, double a11, do
 // from the pieces of eig3_smallest_unit: exact power-of-two scaling (frexp / ldexp: no reciprocal, no rounding), the root
 // estimate in float32 on B / p (the degree-7 polynomial in sqrt(1 - |half|): the isolated root always sits on the
 // well-conditioned side, and the largest root of B is minus the smallest root of -B), one fp64 Halley step on det(A - l I)
-// from the adjugate, the adjugate's best column as eigenvector, a Rayleigh correction, v_rsq_f64 + one Newton step for every
-// normalisation.  ~270 instructions; pinned against LAPACK by the same host families as eig3_sym (tests/test_hostcheck.py).
+// from the adjugate, the adjugate's best column as eigenvector, a Rayleigh correction, v_rsq_f64 + Newton steps for every
+// normalisation (two where the factor's error would reach an eigenvalue, one for the last pair's coordinates).  ~280 instructions;
+// pinned against LAPACK by the same host families as eig3_sym (tests/test_hostcheck.py) and, on the device, against an exact
+// reference by tests/test_gpu_eig_spectra.py.
 DC_HD void eig3_sym_v2(double a00, double a01, double a02, double a11, double a12, double a22, double* lam, double (*V)[3]) {
   double m = fmax(fmax(fabs(a00), fabs(a11)), fabs(a22));
   m = fmax(m, fmax(fabs(a01), fmax(fabs(a02), fabs(a12))));
@@ -396,7 +414,7 @@ DC_HD void eig3_sym_v2(double a00, double a01, double a02, double a11, double a1
   iso[2] = s0 ? M02 : (s1 ? M12 : M22);
   const double n2 = iso[0] * iso[0] + iso[1] * iso[1] + iso[2] * iso[2];
   if (n2 > 0.0) {
-    const double inv = rsqrt1_(n2);
+    const double inv = rsqrt2_(n2);               // (iso, u and w = iso x u carry the 2x2 problem: unit to the last bit, see rsqrt2_)
     iso[0] *= inv; iso[1] *= inv; iso[2] *= inv;
   } else {
     iso[0] = 1.0; iso[1] = 0.0; iso[2] = 0.0;
@@ -412,10 +430,10 @@ DC_HD void eig3_sym_v2(double a00, double a01, double a02, double a11, double a1
   // orthonormal basis (u, w) of the complement, the exact 2x2 problem there
   double u[3], w[3];
   if (fabs(iso[0]) > fabs(iso[1])) {
-    const double inv = rsqrt1_(iso[0] * iso[0] + iso[2] * iso[2]);
+    const double inv = rsqrt2_(iso[0] * iso[0] + iso[2] * iso[2]);
     u[0] = -iso[2] * inv; u[1] = 0.0; u[2] = iso[0] * inv;
   } else {
-    const double inv = rsqrt1_(iso[1] * iso[1] + iso[2] * iso[2]);
+    const double inv = rsqrt2_(iso[1] * iso[1] + iso[2] * iso[2]);
     u[0] = 0.0; u[1] = iso[2] * inv; u[2] = -iso[1] * inv;
   }
   cross3(iso, u, w);
@@ -430,7 +448,7 @@ DC_HD void eig3_sym_v2(double a00, double a01, double a02, double a11, double a1
   const double m11 = w[0] * aw0 + w[1] * aw1 + w[2] * aw2;
   const double h = (m00 - m11) * 0.5, mean = (m00 + m11) * 0.5;
   const double r2 = h * h + m01 * m01;
-  const double rad = r2 > 0.0 ? r2 * rsqrt1_(r2) : 0.0;
+  const double rad = r2 > 0.0 ? r2 * rsqrt2_(r2) : 0.0;
   double l_hi = mean + rad, l_lo = mean - rad;
   double ca, cb;
   {

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import dc_oracle as O
+import eig_cases as cases
 from helpers import t, npy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,10 +34,7 @@ def _eig(host, C, solver='dc_host_eig3'):
     return lam, vec.reshape(-1, 3, 3)
 
 
-def _spd(rng, lams):
-    Q, _ = np.linalg.qr(rng.normal(size=(len(lams), 3, 3)))
-    C = np.einsum('nij,nj,nkj->nik', Q, lams, Q)
-    return 0.5 * (C + C.transpose(0, 2, 1))
+_spd = cases.spd
 
 
 @pytest.mark.parametrize('solver', ['dc_host_eig3', 'dc_host_eig3_v2'])
@@ -47,22 +45,7 @@ def test_eig3_matches_lapack(host, case, solver):
     the reference's known-answer test asks for 1e-6 / 1e-5 (loss.py:731-735)."""
     rng = np.random.default_rng(0)
     n = 5000
-    u = rng.uniform
-    lams = {'generic': u(0, 1, (n, 3)),
-            'planar': np.stack([10 ** u(-10, -3, n), u(0.3, 1, n), u(0.3, 1, n)], 1),
-            'needle': np.stack([10 ** u(-10, -4, n), 10 ** u(-10, -4, n), u(0.3, 1, n)], 1),
-            'double_lo': np.stack([np.full(n, 0.2), np.full(n, 0.2), u(0.3, 1, n)], 1),
-            'double_hi': np.stack([u(0.01, 0.2, n), np.full(n, 0.5), np.full(n, 0.5)], 1),
-            'isotropic': np.full((n, 3), 0.37),
-            # anisotropy from round-off level up to 1e-6 of the scale; spectra with det(B) on either side of zero (where the
-            # solvers switch the eigenvalue they isolate); edge-like spectra
-            'near_isotropic': 0.37 * (1.0 + 10 ** u(-16, -6, (n, 1)) * u(-1, 1, (n, 3))),
-            'edge': np.stack([10 ** u(-8, -3, n), 10 ** u(-3, -0.5, n), u(0.3, 1, n)], 1),
-            'sign_switch': np.stack([0.5 - u(0.1, 0.4, n), 0.5 + u(-1e-7, 1e-7, n), 0.5 + u(0.1, 0.4, n)], 1),
-            'tiny': u(0, 1, (n, 3)) * 1e-14, 'huge': u(0, 1, (n, 3)) * 1e12}[case]
-    if case == 'sign_switch':
-        lams[:, 2] = 1.0 - lams[:, 0]                                  # symmetric about the middle one: det(B) ~ 0
-    lams = np.sort(lams, axis=1)
+    lams = cases.family_lams(case, n, rng)                         # (the spectrum families live in eig_cases.py)
     C = _spd(rng, lams)
     lam, V = _eig(host, C, solver)
     ref = np.linalg.eigh(C)[0]
@@ -89,21 +72,7 @@ def test_eig3_smallest_matches_lapack(host, case, solver):
     the isolate-largest-then-deflate path (kDeflateHalf); eigenvector residual small wherever lam0 is separated."""
     rng = np.random.default_rng(1)
     n = 20000
-    u = rng.uniform
-    if case in ('threshold', 'threshold_unit'):
-        # scaled spectra 2 cos(ang + 2 pi k / 3) with cos(3 ang) swept across the switch at 0.9 (eig3_smallest: deflation;
-        # eig3_smallest_unit: second Newton step) and across 0.999 (eig3_smallest_unit: deflation)
-        ang = np.arccos(u(0.85, 0.95, n) if case == 'threshold' else u(0.99, 0.99999, n)) / 3
-        beta = np.stack([2 * np.cos(ang + 2 * np.pi / 3), 2 * np.cos(ang - 2 * np.pi / 3), 2 * np.cos(ang)], 1)
-        lams = 1.0 + 0.3 * beta
-    else:
-        lams = {'generic': u(0, 1, (n, 3)),
-                'planar': np.stack([10 ** u(-10, -3, n), u(0.3, 1, n), u(0.3, 1, n)], 1),
-                'needle': np.stack([10 ** u(-10, -4, n), 10 ** u(-10, -4, n), u(0.3, 1, n)], 1),
-                'edge': np.stack([10 ** u(-8, -3, n), 10 ** u(-3, -0.5, n), u(0.3, 1, n)], 1),
-                'double_hi': np.stack([u(0.01, 0.2, n), np.full(n, 0.5), np.full(n, 0.5)], 1),
-                'tiny': u(0, 1, (n, 3)) * 1e-14, 'huge': u(0, 1, (n, 3)) * 1e12}[case]
-    lams = np.sort(lams, axis=1)
+    lams = cases.family_lams(case, n, rng)
     C = _spd(rng, lams)
     lam0, v0, tr = _eig_smallest(host, C, solver)
     ref, refV = np.linalg.eigh(C)
