@@ -181,6 +181,17 @@ _SIGNATURES = {
     'dc_map_select': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     'dc_dyn_directions': (_i32, [_vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp]),
     'dc_dyn_update': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    # range-image neighbourhoods (csrc/dc_rangeimage.hip)
+    'dc_range_project_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'dc_range_project': (_i32, [_vp, _i32, _i32, _vp, _i32, _i64, _i32, _i32, _f64, _f64, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_range_organize_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'dc_range_organize': (_i32, [_vp, _i32, _i32, _vp, _i32, _i64, _i32, _i32, _f64, _f64, _i32, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_range_from_grid': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_range_index_image': (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    'dc_image_features_fwd': (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    'dc_image_shadow_mask': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _vp]),
 }
 
 

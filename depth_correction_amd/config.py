@@ -160,6 +160,15 @@ class Config(object):
         self.num_ransac_iters = 500
         self.ransac_model_size = 3
         self.nn_scale = None
+        # neighbourhoods of the per-scan stages (local_feature_cloud, hence correct_cloud and IcpMapper.prepare): 'ball' (nn_k / nn_r,
+        # the reference's) or 'image' -- the scan organised on a spherical image_size = [H, W] grid over image_fov = [up, down] degrees
+        # (scripts/depth_denoising:44-91), neighbours from the image_window = [ah, aw] half extents around a pixel, gated at nn_r
+        # (range_image.py, DESIGN "Range-image neighbourhoods"; not in the reference's Config)
+        self.local_nn_type = 'ball'
+        self.image_size = [128, 1024]
+        self.image_fov = [45., -45.]
+        self.image_wrap = True
+        self.image_window = [2, 2]
         # filters (:204-218)
         self.shadow_neighborhood_angle = 0.017453
         self.shadow_angle_bounds = []

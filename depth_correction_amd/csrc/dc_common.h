@@ -43,3 +43,6 @@
 #define DC_MODEL_LAST DC_MODEL_SCALED_INVCOS
 
 #define DC_MAX_MODEL_TERMS 8
+
+// Range-image windows (dc_rangeimage_math.h; scripts/depth_denoising:44-91): at most this many slots, (2 ah + 1)(2 aw + 1)
+#define DC_IMAGE_MAX_WINDOW 121

@@ -13,6 +13,7 @@
 #include "dc_raymath.h"
 #include "dc_planemath.h"
 #include "dc_dynmath.h"
+#include "dc_rangeimage_math.h"
 
 extern "C" {
 
@@ -498,6 +499,63 @@ int dc_host_dyn_update(const double* map_points, const double* map_normals, int6
   for (int64_t i = 0; i < n_rows; ++i)
     dc::dyn_update_entry(prm, map_points, map_normals, n_map, pose, reading, m, (int64_t)rows[i], (int64_t)match_idx[i], match_chord[i], prob,
                          seen_out);
+  return DC_OK;
+}
+
+// ---- range-image neighbourhoods (dc_rangeimage_math.h) -----------------------------------------------------------------------------
+// range_pixel of sensor-frame points fp64 [n,3]: pixel_out int32 [n] (r W + c or -1), depth_out fp64 [n] (optional)
+void dc_host_range_pixel(const double* points, int64_t n, int rows, int cols, double fov_up, double fov_down, int clamp, double min_depth,
+                         int32_t* pixel_out, double* depth_out) {
+  const dc::RangeGrid g{rows, cols, fov_up, fov_down, 1};
+  for (int64_t i = 0; i < n; ++i) {
+    double d;
+    pixel_out[i] = dc::range_pixel(g, points[3 * i], points[3 * i + 1], points[3 * i + 2], clamp, min_depth, &d);
+    if (depth_out) depth_out[i] = d;
+  }
+}
+
+// the slot list of pixel (r, c): slots_out int32 [(2 ah + 1)(2 aw + 1)] in window order, -1 outside the image.  The number of slots, or
+// DC_ERR_ARG for a window the grid does not admit.
+int dc_host_image_window(int rows, int cols, int wrap, int r, int c, int ah, int aw, int32_t* slots_out) {
+  const dc::RangeGrid g{rows, cols, 1.0, -1.0, wrap};
+  if (!dc::range_grid_ok(g) || !dc::image_window_ok(g, ah, aw) || r < 0 || r >= rows || c < 0 || c >= cols) return DC_ERR_ARG;
+  int slot = 0;
+  for (int dr = -ah; dr <= ah; ++dr)
+    for (int dc_ = -aw; dc_ <= aw; ++dc_) slots_out[slot++] = dc::image_window_pixel(g, r, c, dr, dc_);
+  return slot;
+}
+
+// membership of one slot
+int dc_host_image_member(int occupied, int centre, const double* xi, const double* xj, double r) {
+  return dc::image_member(occupied != 0, centre != 0, xi, xj, r) ? 1 : 0;
+}
+
+// dc_range_project's winner rule as a host loop: the two passes in sequence (the minimum of the depth keys, then the lowest index among
+// the points at the minimum).  points fp64 [n,3] in the sensor frame; pixel_out int32 [n], index_image int32 [H W], range_image fp64 [H W].
+int dc_host_range_project(const double* points, int64_t n, int rows, int cols, double fov_up, double fov_down, int clamp, double min_depth,
+                          int32_t* pixel_out, int32_t* index_image, double* range_image) {
+  const dc::RangeGrid g{rows, cols, fov_up, fov_down, 1};
+  if (!dc::range_grid_ok(g) || n < 0 || n >= (int64_t)0x7f000000) return DC_ERR_ARG;
+  const int64_t hw = (int64_t)rows * cols;
+  uint64_t* keys = new uint64_t[hw];
+  for (int64_t p = 0; p < hw; ++p) { keys[p] = DC_RANGE_EMPTY_KEY; index_image[p] = 0x7f7f7f7f; }
+  for (int64_t i = 0; i < n; ++i) {
+    double d;
+    const int32_t p = pixel_out[i] = dc::range_pixel(g, points[3 * i], points[3 * i + 1], points[3 * i + 2], clamp, min_depth, &d);
+    if (p >= 0 && dc::range_depth_key(d) < keys[p]) keys[p] = dc::range_depth_key(d);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t p = pixel_out[i];
+    if (p < 0) continue;
+    const double d = dc::range_depth(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+    if (dc::range_depth_key(d) == keys[p] && (int32_t)i < index_image[p]) index_image[p] = (int32_t)i;
+  }
+  for (int64_t p = 0; p < hw; ++p) {
+    const bool empty = keys[p] == DC_RANGE_EMPTY_KEY;
+    if (empty) index_image[p] = -1;
+    if (range_image) range_image[p] = empty ? -1.0 : dc::range_key_depth(keys[p]);
+  }
+  delete[] keys;
   return DC_OK;
 }
 

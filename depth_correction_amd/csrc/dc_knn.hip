@@ -22,6 +22,7 @@
 #include "dc_device.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
+#include "dc_shadow_pair.h"
 
 namespace dc {
 
@@ -398,14 +399,7 @@ __device__ __forceinline__ bool find_cell(const CellTable& t, int32_t x, int32_t
   return true;
 }
 
-// cKDTree's squared distance: products and sums individually rounded, in axis order.
-__device__ __forceinline__ double sqdist(const double* a, const double* b) {
-  const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
-  double s = __dmul_rn(d0, d0);
-  s = __dadd_rn(s, __dmul_rn(d1, d1));
-  s = __dadd_rn(s, __dmul_rn(d2, d2));
-  return s;
-}
+// (sqdist, cKDTree's squared distance: dc_shadow_pair.h)
 
 // Visit the cells of the cube shell at Chebyshev distance r around cell c.
 template <typename F>
@@ -1198,19 +1192,12 @@ __global__ __launch_bounds__(kBlock) void shadow_group_kernel(const double* __re
   const double q[3] = {sp[tc * 3], sp[tc * 3 + 1], sp[tc * 3 + 2]};
   const int64_t i = sids[tc];
   const double r2 = rad * rad;
-  const T eps = (T)1e-8;
-  const T xi0 = x[i * 3], xi1 = x[i * 3 + 1], xi2 = x[i * 3 + 2];
-  const T* o = vps + (vps_rows == 1 ? 0 : i * 3);
-  T a0 = o[0] - xi0, a1 = o[1] - xi1, a2 = o[2] - xi2;
-  const T na = sqrt(fma(a2, a2, fma(a1, a1, a0 * a0)));       // torch's norm: an fma chain (see shadow_mask_kernel)
-  const T da = na > eps ? na : eps;
-  a0 /= da; a1 /= da; a2 /= da;
+  ShadowRay<T> ray;                                            // (the pair test: dc_shadow_pair.h)
+  shadow_ray_init(ray, x, vps, vps_rows, i);
   // The extreme ANGLES are the arc cosines of the extreme COSINES (acos does not increase anywhere): the walk keeps the largest and the
   // smallest cosine and takes two arc cosines per ray at the end instead of one per neighbour (a fifth of the kernel's instructions,
   // which it issues at 0.86 of the VALU rate).  A cosine an ulp outside [-1, 1] or a NaN -- whose arc cosine is NaN in the reference's
   // row -- removes the ray as before.
-  T cmax = -(T)INFINITY, cmin = (T)INFINITY;
-  bool bad = false;
   int32_t c[3];
   cell_of(g, q, c);
   const bool finite_q = isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
@@ -1250,27 +1237,16 @@ __global__ __launch_bounds__(kBlock) void shadow_group_kernel(const double* __re
         const int32_t p = has ? b_src + (jj - excl_src) : 0;
         const double pp[3] = {sp[(int64_t)p * 3], sp[(int64_t)p * 3 + 1], sp[(int64_t)p * 3 + 2]};
         const int64_t jn = sids[p];
-        if (has && sqdist(pp, q) <= r2) {
-          T b0 = x[jn * 3] - xi0, b1 = x[jn * 3 + 1] - xi1, b2 = x[jn * 3 + 2] - xi2;
-          const T nb = sqrt(fma(b2, b2, fma(b1, b1, b0 * b0)));
-          const T db = nb > eps ? nb : eps;
-          b0 /= db; b1 /= db; b2 /= db;
-          const T cs = a0 * b0 + a1 * b1 + a2 * b2;
-          bad = bad || !(cs >= (T)-1 && cs <= (T)1);
-          cmax = cs > cmax ? cs : cmax;
-          cmin = cs < cmin ? cs : cmin;
-        }
+        if (has && sqdist(pp, q) <= r2) shadow_ray_meet(ray, x, jn);
       }
     }
     if (!done && (shell_bound(g, q, c, r) > rad || !shell_in_grid(g, c, r + 1))) done = true;
   }
-  row_min_max(cmin, cmax);
-  const bool none = cmin > cmax;                     // no neighbour met
-  const T amin = none ? (T)INFINITY : (T)acos(cmax), amax = none ? -(T)INFINITY : (T)acos(cmin);
-  const unsigned long long bm = __ballot(bad);
+  row_min_max(ray.cmin, ray.cmax);
+  const unsigned long long bm = __ballot(ray.bad);
   const bool row_bad = ((unsigned)(bm >> row_lane0) & 0xffffu) != 0u;
   // a ray with no neighbour at all (not even itself: non-finite direction) has an all-fill row in the reference: kept
-  if (valid && sub == 0) mask[i] = (!row_bad && (amin > amax ? lo <= hi : (amin >= lo && amax <= hi))) ? 1 : 0;
+  if (valid && sub == 0) mask[i] = shadow_ray_kept(ray.cmin, ray.cmax, row_bad, lo, hi) ? 1 : 0;
 }
 
 // ---- radius search: count, then fill (ascending index, -1 padded) ------------------------------------

@@ -19,6 +19,7 @@ __all__ = [
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace', 'cloud_loss', 'cloud_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update',
+    'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
 
@@ -722,6 +723,34 @@ def compact_rows(mask, fields, want_index=False):
     m = int(count.item())
     outs = [o[:m] for o in outs]
     return (outs, index[:m]) if want_index else outs
+
+
+@on_device
+def compact_rows_device(mask, fields):
+    """``compact_rows`` without the read-back: (full-size outputs whose first ``count`` rows are the kept ones, ``count`` device
+    int64 [1]) -- for callers that keep issuing work and size their tensors later."""
+    n = mask.shape[0]
+    need(mask, (n,), dtype=torch.bool, name='mask')
+    dev = mask.device
+    if len(fields) > 8:
+        raise ValueError('at most 8 fields per call')
+    srcs, outs, rb = [], [], []
+    for f in fields:
+        if f.shape[0] != n or f.device != dev:
+            raise ValueError('every field needs %d rows on %s' % (n, dev))
+        f = f.contiguous()
+        srcs.append(f)
+        outs.append(torch.empty_like(f))
+        rb.append(f.element_size() * (f.numel() // n if n else 1))
+    count = torch.empty((1,), dtype=torch.int64, device=dev)
+    nf = len(srcs)
+    a_src = (ctypes.c_void_p * max(nf, 1))(*[ptr(f) for f in srcs])
+    a_dst = (ctypes.c_void_p * max(nf, 1))(*[ptr(f) for f in outs])
+    a_rb = (ctypes.c_int32 * max(nf, 1))(*rb)
+    nbytes = lib().dc_compact_rows_workspace_bytes(n)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_compact_rows(ptr(mask), n, nf, a_src, a_dst, a_rb, None, ptr(count), ptr(ws), nbytes, stream_ptr()), 'dc_compact_rows')
+    return outs, count
 
 
 @on_device
@@ -1647,3 +1676,162 @@ def dyn_update(map_points, map_normals, pose, reading, rows, match_idx, match_ch
                               ptr(match_chord), r, float(chord_max), float(epsilon_a), float(epsilon_d), float(alpha), float(beta),
                               float(threshold), float(max_range), ptr(prob), ptr(seen), stream_ptr()), 'dc_dyn_update')
     return prob
+
+
+# ------------------------------------------------------------------------------------------------
+# range-image neighbourhoods (csrc/dc_rangeimage.hip; range_image.py holds the grid and the cloud-level functions)
+# ------------------------------------------------------------------------------------------------
+def _grid_args(grid):
+    return int(grid.rows), int(grid.cols), float(grid.fov_up), float(grid.fov_down), int(bool(grid.wrap))
+
+
+def _range_vps(vps, points, n):
+    if vps is None:
+        return None, 0
+    vps = vps.reshape(-1, 3)
+    need(vps, (None, 3), dtype=points.dtype, name='vps', device=points.device)
+    if vps.shape[0] not in (1, n):
+        raise ValueError('vps must have 1 or %d rows' % n)
+    return vps, vps.shape[0]
+
+
+@on_device
+def range_project(points, grid, vps=None, clamp=True, min_depth=0.0):
+    """(pixel int32 [N], index_image int32 [H,W], range_image [H,W]) of sensor-frame points [N, >=3] on a spherical grid
+    (dc_range_project): the reference's range_projection (scripts/depth_denoising:44-91) with the winner of every pixel -- the
+    nearest point, ties to the lower index -- kept as an index."""
+    need(points, (None, None), name='points')
+    n, stride = points.shape
+    if stride < 3:
+        raise ValueError('points need at least 3 columns')
+    dev = points.device
+    rows, cols, up, down, wrap = _grid_args(grid)
+    vps, vps_rows = _range_vps(vps, points, n)
+    pixel = torch.empty((n,), dtype=torch.int32, device=dev)
+    index_image = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+    range_image = torch.empty((rows, cols), dtype=points.dtype, device=dev)
+    nbytes = lib().dc_range_project_workspace_bytes(n, rows, cols)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_range_project(ptr(points), stride, dtype_code(points), ptr(vps), vps_rows, n, rows, cols, up, down, wrap, int(bool(clamp)),
+                                 float(min_depth), ptr(pixel), ptr(index_image), ptr(range_image), ptr(ws), nbytes, stream_ptr()),
+          'dc_range_project')
+    return pixel, index_image, range_image
+
+
+def _organized_outputs(rows_max, hw_shape, dtype, dev, want_index, want_range):
+    out = dict(vps=torch.empty((rows_max, 3), dtype=dtype, device=dev), dirs=torch.empty((rows_max, 3), dtype=dtype, device=dev),
+               depth=torch.empty((rows_max, 1), dtype=dtype, device=dev), points=torch.empty((rows_max, 3), dtype=dtype, device=dev),
+               pixel=torch.empty((rows_max,), dtype=torch.int32, device=dev),
+               index=torch.empty((rows_max,), dtype=torch.int32, device=dev) if want_index else None,
+               index_image=torch.empty(hw_shape, dtype=torch.int32, device=dev),
+               range_image=torch.empty(hw_shape, dtype=dtype, device=dev) if want_range else None,
+               count=torch.empty((1,), dtype=torch.int64, device=dev))
+    return out
+
+
+@on_device
+def range_organize(points, grid, vps=None, clamp=True, min_depth=0.0, dtype=None, want_index=False, want_range=False):
+    """Projection + the winners compacted in ascending pixel order (dc_range_organize).  Returns a dict of FULL-SIZE buffers
+    (min(N, H W) rows: vps, dirs, depth [.,1], points, pixel, index | None), index_image [H,W] pointing at the compact rows,
+    range_image | None and ``count`` (device int64 [1]): nothing is read back here -- the caller slices once it knows the count."""
+    need(points, (None, None), name='points')
+    n, stride = points.shape
+    if stride < 3:
+        raise ValueError('points need at least 3 columns')
+    dev = points.device
+    dtype = points.dtype if dtype is None else dtype
+    rows, cols, up, down, wrap = _grid_args(grid)
+    vps, vps_rows = _range_vps(vps, points, n)
+    out = _organized_outputs(min(n, rows * cols), (rows, cols), dtype, dev, want_index, want_range)
+    nbytes = lib().dc_range_organize_workspace_bytes(n, rows, cols)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_range_organize(ptr(points), stride, dtype_code(points), ptr(vps), vps_rows, n, rows, cols, up, down, wrap, int(bool(clamp)),
+                                  float(min_depth), nv.DC_F32 if dtype == torch.float32 else nv.DC_F64, ptr(out['vps']), ptr(out['dirs']),
+                                  ptr(out['depth']), ptr(out['points']), ptr(out['pixel']), ptr(out['index']), ptr(out['index_image']),
+                                  ptr(out['range_image']), ptr(out['count']), ptr(ws), nbytes, stream_ptr()), 'dc_range_organize')
+    return out
+
+
+@on_device
+def range_from_grid(points, rows, cols, vps=None, min_depth=0.0, dtype=None, want_index=False, want_range=False):
+    """The same outputs for an H x W array of points [H W, >=3] in row-major order (dc_range_from_grid): no projection, a pixel is
+    occupied when its ray is finite and deeper than ``min_depth``."""
+    need(points, (rows * cols, None), name='points')
+    stride = points.shape[1]
+    if stride < 3:
+        raise ValueError('points need at least 3 columns')
+    dev = points.device
+    dtype = points.dtype if dtype is None else dtype
+    vps, vps_rows = _range_vps(vps, points, rows * cols)
+    out = _organized_outputs(rows * cols, (rows, cols), dtype, dev, want_index, want_range)
+    nbytes = lib().dc_range_organize_workspace_bytes(0, rows, cols)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_range_from_grid(ptr(points), stride, dtype_code(points), ptr(vps), vps_rows, int(rows), int(cols), float(min_depth),
+                                   nv.DC_F32 if dtype == torch.float32 else nv.DC_F64, ptr(out['vps']), ptr(out['dirs']), ptr(out['depth']),
+                                   ptr(out['points']), ptr(out['pixel']), ptr(out['index']), ptr(out['index_image']), ptr(out['range_image']),
+                                   ptr(out['count']), ptr(ws), nbytes, stream_ptr()), 'dc_range_from_grid')
+    return out
+
+
+@on_device
+def range_index_image(pixel, rows, cols, count=None):
+    """int32 [H,W]: index_image[pixel[i]] = i, -1 elsewhere (dc_range_index_image); ``count`` (device int64 [1]) bounds the rows."""
+    need(pixel, (None,), dtype=torch.int32, name='pixel')
+    index_image = torch.empty((int(rows), int(cols)), dtype=torch.int32, device=pixel.device)
+    check(lib().dc_range_index_image(ptr(pixel), pixel.shape[0], ptr(count), int(rows), int(cols), ptr(index_image), stream_ptr()),
+          'dc_range_index_image')
+    return index_image
+
+
+@on_device
+def image_features_fwd(points, dirs, pixel, index_image, grid, window, r=None, want=('mean', 'cov', 'eigvals', 'eigvecs', 'normals',
+                                                                                     'inc_angles'),
+                       want_nvalid=True, want_neighbors=True, count=None):
+    """dc_features_fwd's outputs on the window neighbourhoods of an organised cloud, one launch (dc_image_features_fwd).  ``window`` =
+    (ah, aw) half extents, ``r`` the 3-D radius gate (None / <= 0 / inf: none).  Returns a dict with the wanted fields, ``nvalid``
+    int32 [M] and ``neighbors`` int32 [M, (2 ah + 1)(2 aw + 1)] (-1 padded in place)."""
+    need(points, (None, 3), name='points')
+    m = points.shape[0]
+    dev, dt = points.device, points.dtype
+    need(dirs, (m, 3), dtype=dt, name='dirs', device=dev)
+    need(pixel, (None,), dtype=torch.int32, name='pixel', device=dev)
+    if pixel.shape[0] < m:
+        raise ValueError('pixel has %d rows, the cloud %d' % (pixel.shape[0], m))
+    rows, cols, _, _, wrap = _grid_args(grid)
+    need(index_image, (rows, cols), dtype=torch.int32, name='index_image', device=dev)
+    ah, aw = int(window[0]), int(window[1])
+    k = (2 * ah + 1) * (2 * aw + 1)
+    shapes = dict(mean=(m, 3), cov=(m, 3, 3), eigvals=(m, 3), eigvecs=(m, 3, 3), normals=(m, 3), inc_angles=(m, 1))
+    out = {f: (torch.empty(shapes[f], dtype=dt, device=dev) if f in want else None) for f in shapes}
+    nvalid = torch.empty((m,), dtype=torch.int32, device=dev) if want_nvalid else None
+    nbr = torch.empty((m, max(k, 1)), dtype=torch.int32, device=dev) if want_neighbors else None
+    check(lib().dc_image_features_fwd(ptr(points), ptr(dirs), dtype_code(points), ptr(pixel), ptr(index_image), m, ptr(count), rows, cols, wrap,
+                                      ah, aw, float(r) if r else 0.0, ptr(out['mean']), ptr(out['cov']), ptr(out['eigvals']),
+                                      ptr(out['eigvecs']), ptr(out['normals']), ptr(out['inc_angles']), ptr(nvalid), ptr(nbr), stream_ptr()),
+          'dc_image_features_fwd')
+    out.update(nvalid=nvalid, neighbors=nbr)
+    return out
+
+
+@on_device
+def image_shadow_mask(points, vps, dirs, pixel, index_image, grid, window, r, lo, hi, count=None):
+    """bool [M]: dc_shadow_filter's mask with the candidates taken from the image window (dc_image_shadow_mask); rows at and beyond
+    ``count`` (device int64 [1]) are False."""
+    need(points, (None, 3), name='points')
+    m = points.shape[0]
+    dev, dt = points.device, points.dtype
+    vps = vps.reshape(-1, 3)
+    need(vps, (None, 3), dtype=dt, name='vps', device=dev)
+    need(dirs, (m, 3), dtype=dt, name='dirs', device=dev)
+    if vps.shape[0] not in (1, m):
+        raise ValueError('vps must have 1 or %d rows' % m)
+    need(pixel, (None,), dtype=torch.int32, name='pixel', device=dev)
+    if pixel.shape[0] < m:
+        raise ValueError('pixel has %d rows, the cloud %d' % (pixel.shape[0], m))
+    rows, cols, _, _, wrap = _grid_args(grid)
+    need(index_image, (rows, cols), dtype=torch.int32, name='index_image', device=dev)
+    mask = torch.empty((m,), dtype=torch.bool, device=dev)
+    check(lib().dc_image_shadow_mask(ptr(points), ptr(vps), vps.shape[0], ptr(dirs), dtype_code(points), ptr(pixel), ptr(index_image), m,
+                                     ptr(count), rows, cols, wrap, int(window[0]), int(window[1]), float(r), float(lo), float(hi), ptr(mask),
+                                     stream_ptr()), 'dc_image_shadow_mask')
+    return mask

@@ -40,6 +40,8 @@ def _and_mask(cloud, mask):
 
 def local_feature_cloud(cloud, cfg: Config):
     """Scan -> DepthCloud with neighbours, features and the planarity mask (preproc.py:35-64)."""
+    if getattr(cfg, 'local_nn_type', 'ball') == 'image':
+        return _image_feature_cloud(cloud, cfg)
     if isinstance(cloud, torch.Tensor):
         # raw rows [N, >=3] already on the device (what the node holds after the upload of a message)
         if cloud.is_cuda and cloud.dim() == 2 and cloud.dtype in (torch.float32, torch.float64) and cfg.shadow_angle_bounds:
@@ -93,6 +95,11 @@ def _with_features(cloud, cfg: Config, points_current=False):
         cloud.update_features(scale=None)
     else:
         cloud.update_all(k=cfg.nn_k, r=cfg.nn_r)
+    return _bounds_mask(cloud, cfg)
+
+
+def _bounds_mask(cloud, cfg: Config):
+    """The eigenvalue and eigenvalue-ratio bounds ANDed into cloud.mask (preproc.py:52-63)."""
     if cloud.eigvals.is_cuda and not cfg.log_filters and (cfg.eigenvalue_bounds or cfg.eigenvalue_ratio_bounds):
         # the same masks without the ones / and passes between them: every bound in one kernel (dc_mask_bounds_multi), or one kernel per
         # bound ANDed in place (dc_mask_bounds) beyond eight
@@ -115,6 +122,39 @@ def _with_features(cloud, cfg: Config, points_current=False):
     if cfg.eigenvalue_ratio_bounds:
         _and_mask(cloud, filter_eigenvalue_ratios(cloud, cfg.eigenvalue_ratio_bounds, only_mask=True, log=cfg.log_filters))
     return cloud
+
+
+def _image_feature_cloud(source, cfg: Config):
+    """local_feature_cloud with ``local_nn_type = 'image'``: the scan is organised on the spherical grid of the configuration
+    (image_size, image_fov, image_wrap; one point per pixel, the nearest), the scan-shadow mask comes from an image window, the
+    neighbourhoods are the ``image_window`` around every pixel gated at ``nn_r`` (range_image.py, csrc/dc_rangeimage.hip).  The
+    stages are issued back to back with the survivor count on the device; it is read ONCE, when the cloud's tensors are sized.
+    Accepts raw device rows [N, >=3], a plain or structured array (an H x W one of the grid's shape is taken pixel by pixel) or a
+    DepthCloud.  Results are not those of ball neighbourhoods (DESIGN "Range-image neighbourhoods")."""
+    from . import ops, range_image as ri
+    from .filters import _shadow_bounds
+    grid = ri.SphericalGrid.from_config(cfg)
+    window = ri.check_window(grid, cfg.image_window)
+    with torch.no_grad():
+        out = ri.organize_buffers(source, grid, dtype=cfg.torch_float_type(), device=cfg.device)
+        count, pixel, index_image = out['count'], out['pixel'], out['index_image']
+        vps, dirs, depth, points = out['vps'], out['dirs'], out['depth'], out['points']
+        if cfg.shadow_angle_bounds:
+            lo, hi, _ = _shadow_bounds(cfg.shadow_angle_bounds)
+            angle = float(cfg.shadow_neighborhood_angle)
+            keep = ops.image_shadow_mask(points, vps, dirs, pixel, index_image, grid, ri.shadow_window(grid, angle), _chord(angle), lo, hi,
+                                         count=count)
+            # (rows beyond the count carry 0 in the mask: the compaction needs no count, and dropping rows keeps the pixel order)
+            (vps, dirs, depth, points, pixel), count = ops.compact_rows_device(keep, [vps, dirs, depth, points, pixel])
+            index_image = ops.range_index_image(pixel, grid.rows, grid.cols, count=count)
+        f = ops.image_features_fwd(points, dirs, pixel, index_image, grid, window, r=cfg.nn_r, count=count)
+        m = int(count.item())                              # the one read
+    if cfg.log_filters and cfg.shadow_angle_bounds:
+        print('%i points kept on the %i x %i image (one per pixel, shadow points removed).' % (m, grid.rows, grid.cols))
+    cloud = DepthCloud(vps[:m], dirs[:m], depth[:m], points=points[:m], mean=f['mean'][:m], cov=f['cov'][:m], eigvals=f['eigvals'][:m],
+                       eigvecs=f['eigvecs'][:m], normals=f['normals'][:m], inc_angles=f['inc_angles'][:m], neighbors=f['neighbors'][:m])
+    cloud.pixel, cloud.grid, cloud.index_image, cloud.nvalid = pixel[:m], grid, index_image, f['nvalid'][:m]
+    return _bounds_mask(cloud, cfg)
 
 
 def offset_cloud(clouds, model):

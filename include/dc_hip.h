@@ -42,6 +42,7 @@ extern "C" {
 #define DC_MODEL_SCALED_INVCOS 5     /* w = [p0]: d' = d (1 - p0 / |cos(gamma)|)    (model.py:316-349) */
 #define DC_MODEL_LAST DC_MODEL_SCALED_INVCOS
 #define DC_MAX_MODEL_TERMS 8
+#define DC_IMAGE_MAX_WINDOW 121 /* slots of the largest image window, (2 ah + 1)(2 aw + 1): dc_image_features_fwd, dc_image_shadow_mask */
 #define DC_OK 0
 #define DC_ERR_ARG (-1)
 #define DC_ERR_DTYPE (-2)
@@ -1057,6 +1058,61 @@ int dc_dyn_update(const double* map_points, const double* map_normals, int64_t n
                   const int32_t* rows, const int32_t* match_idx, const double* match_chord, int64_t n_rows, double chord_max, double epsilon_a,
                   double epsilon_d, double alpha, double beta, double threshold, double max_range, double* prob, uint8_t* seen_out,
                   dcStream_t stream);
+
+/* ---- range-image neighbourhoods (depth_correction_amd/csrc/dc_rangeimage.hip, dc_rangeimage_math.h; DESIGN "Range-image
+ * neighbourhoods"): a scan as an organised H x W cloud.  The reference's sensor delivers H x W clouds and its scripts flatten them
+ * (`if cloud.ndim == 2: cloud = cloud.reshape((-1,))`); scripts/depth_denoising:44-91 (range_projection), :94-116 (depth_to_points)
+ * and scripts/compare_to_ddd work on the spherical range image.  Grid: rows H, cols W, fov_up / fov_down in degrees, wrap != 0:
+ * windows wrap over the column seam (rows never wrap).
+ * Pixel of a sensor-frame point p (fp64, range_projection's operation order): depth = |p|, yaw = -atan2(y, x),
+ * pitch = asin(z / (depth + 1e-8)), col = floor(0.5 (yaw / pi + 1) W), row = floor((1 - (pitch + |fov_down|) / fov) H), both clamped
+ * into the image; clamp == 0: a row outside the image rejects the point instead (columns span the full turn and are always clamped).
+ * Rejected too: a NaN or an infinity among the coordinates, a depth that is not > min_depth (min_depth 0: zero depth).
+ * points [n, stride] of `dtype`; vps NULL, one row (vps_rows 1) or n rows [n,3], subtracted (in fp64) before projecting.
+ * pixel int32 [n] = r W + c or -1; index_image int32 [H W] = the point that won the pixel or -1; range_image [H W] of `dtype`
+ * (optional) = the winner's depth or -1.  The nearest point wins, an exact depth tie goes to the lower index: an unsigned 64-bit
+ * atomicMin on the order-preserving bits of the fp64 depth, then an atomicMin of the index among the points at the minimum --
+ * deterministic whatever the dispatch order.  Four launches and two fills. */
+size_t dc_range_project_workspace_bytes(int64_t n, int rows, int cols);
+int dc_range_project(const void* points, int stride, int dtype, const void* vps, int vps_rows, int64_t n, int rows, int cols, double fov_up,
+                     double fov_down, int wrap, int clamp, double min_depth, int32_t* pixel, int32_t* index_image, void* range_image, void* ws,
+                     size_t ws_bytes, dcStream_t stream);
+/* The same projection followed by a compaction of the winners in ascending pixel order (an exclusive scan of the occupancy flags):
+ * vps_out / dirs_out / points_out [m,3], depth_out [m] of out_dtype -- DepthCloud.from_points' fields (depth_cloud.py:592-638) and
+ * points = vps + depth * dirs --, pixel_out int32 [m] ascending, index_out int32 [m] (optional) the input row of every survivor,
+ * *count_out = m (DEVICE int64).  index_image is rewritten to point at the compact rows.  The outputs need min(n, H W) rows. */
+size_t dc_range_organize_workspace_bytes(int64_t n, int rows, int cols);
+int dc_range_organize(const void* points, int stride, int in_dtype, const void* vps, int vps_rows, int64_t n, int rows, int cols, double fov_up,
+                      double fov_down, int wrap, int clamp, double min_depth, int out_dtype, void* vps_out, void* dirs_out, void* depth_out,
+                      void* points_out, int32_t* pixel_out, int32_t* index_out, int32_t* index_image, void* range_image, int64_t* count_out,
+                      void* ws, size_t ws_bytes, dcStream_t stream);
+/* A sensor that delivers the H x W array itself: points [H W, stride] in row-major order IS the pixel order, no projection.  A pixel is
+ * occupied when its ray is finite and deeper than min_depth.  Outputs as dc_range_organize (H W rows); workspace:
+ * dc_range_organize_workspace_bytes(0, rows, cols). */
+int dc_range_from_grid(const void* points, int stride, int in_dtype, const void* vps, int vps_rows, int rows, int cols, double min_depth,
+                       int out_dtype, void* vps_out, void* dirs_out, void* depth_out, void* points_out, int32_t* pixel_out, int32_t* index_out,
+                       int32_t* index_image, void* range_image, int64_t* count_out, void* ws, size_t ws_bytes, dcStream_t stream);
+/* index_image int32 [H W] of a cloud that carries its pixels: -1, then index_image[pixel[i]] = i for i < min(m, *count) (count: DEVICE
+ * int64 or NULL).  Rows dropped from an organised cloud keep the pixel order; this rebuilds the image for what is left. */
+int dc_range_index_image(const int32_t* pixel, int64_t m, const int64_t* count, int rows, int cols, int32_t* index_image, dcStream_t stream);
+/* dc_features_fwd's outputs (all optional: mean [m,3], cov [m,9], eigvals [m,3] ascending, eigvecs [m,9], normals [m,3],
+ * inc_angles [m], nvalid int32 [m]) on WINDOW neighbourhoods of an organised cloud (points, dirs [m,3] of `dtype`, pixel [m],
+ * index_image [H W] with index_image[pixel[i]] == i), in ONE launch.  Window: half extents (ah, aw), slots in row-major window order
+ * (dr = -ah..ah outer, dc = -aw..aw inner, centre included); rows outside the image are missing, columns wrap or are missing
+ * according to `wrap`; 2 ah + 1 <= H, 2 aw + 1 <= W and (2 ah + 1)(2 aw + 1) <= 121 (DC_ERR_ARG otherwise: no pixel twice in a
+ * window).  A slot is a member when its pixel is occupied and |x_j - x_i|^2 <= r^2 in fp64 (r <= 0 or infinite: no gate); the centre
+ * always is.  nbr_out int32 [m, (2 ah + 1)(2 aw + 1)] (optional): the membership table, -1 padded in place.  Validity weights,
+ * the degenerate-denominator clamp, n <- -sign(dir . n) n and inc = arccos |dir . n| as dc_features_fwd.  count (DEVICE int64 or
+ * NULL): rows at and beyond *count are not written. */
+int dc_image_features_fwd(const void* points, const void* dirs, int dtype, const int32_t* pixel, const int32_t* index_image, int64_t m,
+                          const int64_t* count, int rows, int cols, int wrap, int ah, int aw, double r, void* mean, void* cov, void* eigvals,
+                          void* eigvecs, void* normals, void* inc_angles, int32_t* nvalid, int32_t* nbr_out, dcStream_t stream);
+/* dc_shadow_filter's mask (filters.py:257-309 on direction neighbourhoods of chord radius r) with the candidates taken from the image
+ * window: the same inclusion test on the directions and the same pair test, so the same mask whenever the window holds every
+ * direction neighbour.  mask_out uint8 [m]; rows at and beyond *count (DEVICE int64 or NULL) get 0.  One launch, no table. */
+int dc_image_shadow_mask(const void* points, const void* vps, int vps_rows, const void* dirs, int dtype, const int32_t* pixel,
+                         const int32_t* index_image, int64_t m, const int64_t* count, int rows, int cols, int wrap, int ah, int aw, double r,
+                         double lo, double hi, uint8_t* mask_out, dcStream_t stream);
 
 #ifdef __cplusplus
 }
