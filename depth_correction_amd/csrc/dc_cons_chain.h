@@ -81,6 +81,11 @@ __device__ __forceinline__ void chain_publish(const StepChain& ch, int k, double
   __hip_atomic_store(pub + 2 * k + 1, st | (unsigned)__double2hiint(w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// lane `l`'s value of v, the same for every lane of the wavefront (all of them active)
+__device__ __forceinline__ double lane_value_f64(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
 template <int P>
 __device__ __forceinline__ void chain_front_block(const StepChain& ch, double* lds /* [kBlock / kWave] in LDS */) {
   const int a = blockIdx.x;
@@ -96,23 +101,31 @@ __device__ __forceinline__ void chain_front_block(const StepChain& ch, double* l
     }
     return;
   }
-  const bool step = ch.has_prev && ch.adam.p && a >= 2 && threadIdx.x == 0;
+  const bool step_blk = ch.has_prev && ch.adam.p && a >= 2;
+  const bool step = step_blk && threadIdx.x == 0;
   const int32_t* st_prev = ch.prev_status ? ch.prev_status : ch.status;
   const bool flagged = ch.has_prev && a == 0 && threadIdx.x == 0 && st_prev &&
                        __hip_atomic_load(st_prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-  double p0 = 0.0, m0 = 0.0, v0 = 0.0;
-  if (step) {
-    p0 = ch.adam.p[a - 2]; m0 = ch.adam.m[a - 2]; v0 = ch.adam.v[a - 2];
-    if (ch.w_prev_out) ch.w_prev_out[a - 2] = p0;
+  // the parameter's state {p, m, v} is loaded by lanes 0, 1, 2 -- ONE register pair beside the 32 doubles in flight below, not
+  // three in lane 0 (the block shares the step kernels' register allocation) -- and handed to lane 0 after the sum
+  double st = 0.0;
+  if (step_blk && threadIdx.x < 3) {
+    const double* src = threadIdx.x == 0 ? ch.adam.p : threadIdx.x == 1 ? ch.adam.m : ch.adam.v;
+    st = src[a - 2];
+    if (threadIdx.x == 0 && ch.w_prev_out) ch.w_prev_out[a - 2] = st;
   }
   double s = 0.0;
   if (ch.has_prev) {
-    const double* p = ch.prev + (int64_t)a * ch.prev_rows;
     constexpr int U = 32;
-    for (int64_t r0 = threadIdx.x; r0 < ch.prev_rows; r0 += (int64_t)U * kBlock) {
+    const int64_t rows = ch.prev_rows;
+    const uint32_t tid = threadIdx.x;
+    // (the trip's first row and what is left of the column are the same for the whole block: scalar; a lane adds 32-bit offsets)
+    for (int64_t b0 = 0; b0 < rows; b0 += (int64_t)U * kBlock) {
+      const double* p = ch.prev + (int64_t)a * rows + b0;
+      const uint32_t left = rows - b0 < (int64_t)U * kBlock ? (uint32_t)(rows - b0) : (uint32_t)(U * kBlock);
       double v[U];
 #pragma unroll
-      for (int u_ = 0; u_ < U; ++u_) v[u_] = (r0 + (int64_t)u_ * kBlock < ch.prev_rows) ? p[r0 + (int64_t)u_ * kBlock] : 0.0;
+      for (int u_ = 0; u_ < U; ++u_) v[u_] = (tid + (uint32_t)(u_ * kBlock) < left) ? p[tid + (uint32_t)(u_ * kBlock)] : 0.0;
 #pragma unroll
       for (int w_ = U / 2; w_ > 0; w_ >>= 1) {
 #pragma unroll
@@ -125,6 +138,7 @@ __device__ __forceinline__ void chain_front_block(const StepChain& ch, double* l
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if (lane == 0) lds[wave] = s;
   __syncthreads();
+  const double p0 = lane_value_f64(st, 0), m0 = lane_value_f64(st, 1), v0 = lane_value_f64(st, 2);     // (wavefront 0's are the state)
   if (threadIdx.x == 0) {
     if (ch.has_prev) {
       double t = 0.0;

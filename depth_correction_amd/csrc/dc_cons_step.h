@@ -323,6 +323,29 @@ __device__ __forceinline__ double wave_sum4_dpp(double* v) {
   return r;
 }
 
+// wave_sum_packed<8> with every level in registers of its own (the in-place form indexes its array by a lane-dependent address: 80 B
+// of scratch in the three-weight step kernels): the same selects, exchanges and additions in the same order
+__device__ __forceinline__ double wave_sum8_regs(const double* v) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const bool up1 = (lane & 1) != 0, up2 = (lane & 2) != 0, up4 = (lane & 4) != 0;
+  double a[4], b[2];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double keep = up1 ? v[k + 4] : v[k], give = up1 ? v[k] : v[k + 4];
+    a[k] = keep + __shfl_xor(give, 1, kWave);
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const double keep = up2 ? a[k + 2] : a[k], give = up2 ? a[k] : a[k + 2];
+    b[k] = keep + __shfl_xor(give, 2, kWave);
+  }
+  const double keep = up4 ? b[1] : b[0], give = up4 ? b[0] : b[1];
+  double r = keep + __shfl_xor(give, 4, kWave);
+#pragma unroll
+  for (int off = 8; off < kWave; off <<= 1) r += __shfl_xor(r, off, kWave);
+  return r;
+}
+
 // {sum loss, count} -> p_fwd columns, dL/dw -> p_bwd columns (same row stride: one row per wavefront), through one packed
 // wavefront reduction of the 2 + P values
 template <int P, bool DPP = false>
@@ -521,8 +544,59 @@ __device__ __forceinline__ void chain_term_q32(const int4* tile, uint32_t off, b
   }
 }
 
-// (six wavefronts per SIMD: left alone the kernel takes 81 VGPRs -- one allocation granule over the 80 of six wavefronts, i.e. FIVE per SIMD;
-//  at 79 + 12 B of scratch a step takes 44.4 instead of 47.2 us.  Seven -- 71 VGPRs, 44 B of scratch -- take 50.9 us.)
+// Blocks per CU the kernel is built for.  Seven need <= 72 VGPRs (512 per SIMD lane / 7, in granules of 8), <= 96 SGPRs (256-thread
+// blocks are admitted up to 800 / (ceil(sgpr / 16) 16 + 16) per CU: 6 at 97..112) and seven tiles in the 160 KiB of LDS: the 512-row
+// tile of one or two weights.  The 768-row tile and the third piece of three weights stay at six, the 768-row tile of three at four.
+// (Five against six wavefronts per SIMD: 47.2 against 44.4 us per step.)
+template <int P, int CAP> constexpr int step_q32_blocks() {
+  constexpr int lds = StepRow<q32, P>::kPieces * CAP * 16 + 512;      // the tile and the block's few small arrays
+  return 7 * lds <= 160 * 1024 ? 7 : 6 * lds <= 160 * 1024 ? 6 : 4;
+}
+// The lane's NS 16-bit tile positions two to a register (slot 2 j in the low half of word j): they live through both sweeps and the tail
+template <int Q> __device__ __forceinline__ uint32_t pre_at(const uint32_t* pk) { return (Q & 1) ? pk[Q >> 1] >> 16 : pk[Q >> 1] & 0xFFFFu; }
+// gather_fixed<q32, NS, MISS> over packed positions: the same reads, differences and additions in the same order
+template <int NS, bool MISS, int Q0 = 0>
+__device__ __forceinline__ int gather_fixed_pk(const int4* tile, const Pt<q32>::Raw& ci, const uint32_t* pk, CovAcc& acc) {
+  if constexpr (Q0 >= NS) return 0;
+  else {
+    constexpr int NQ = NS - Q0 < 4 ? NS - Q0 : 4;
+    uint32_t off[NQ];
+    off[0] = pre_at<Q0>(pk);
+    if constexpr (NQ > 1) off[1] = pre_at<Q0 + (NQ > 1 ? 1 : 0)>(pk);
+    if constexpr (NQ > 2) off[2] = pre_at<Q0 + (NQ > 2 ? 2 : 0)>(pk);
+    if constexpr (NQ > 3) off[3] = pre_at<Q0 + (NQ > 3 ? 3 : 0)>(pk);
+    Pt<q32>::Raw cj[NQ];
+    bool have[NQ];
+    int n_have = 0;
+#pragma unroll
+    for (int u_ = 0; u_ < NQ; ++u_) {
+      have[u_] = !MISS || off[u_] != kNoLoc;
+      int4 piece[1];
+      read_row<1>(tile, 0, have[u_] ? off[u_] : 0u, piece);
+      cj[u_] = Pt<q32>::from_row(piece);
+    }
+#pragma unroll
+    for (int u_ = 0; u_ < NQ; ++u_) {
+      double d[3];
+      Pt<q32>::delta(have[u_] ? cj[u_] : ci, ci, d);
+      cov_add_d(acc, d[0], d[1], d[2]);
+      n_have += have[u_] ? 1 : 0;
+    }
+    return n_have + gather_fixed_pk<NS, MISS, Q0 + 4>(tile, ci, pk, acc);
+  }
+}
+// the second sweep over packed positions, in groups of four with a scheduling fence between them (left alone, the compiler requests
+// every row piece up front and the kernel loses wavefronts per SIMD to the registers)
+template <int NS, int P, int CAP, bool MISS, int Q = 0>
+__device__ __forceinline__ void chain_sweep_pk(const int4* tile, const uint32_t* pk, const Pt<q32>::Raw& ci, const float* cmf, const float* vs,
+                                               const float* vu, float c2f, float* gwf) {
+  if constexpr (Q < NS) {
+    if constexpr (Q % 4 == 0 && Q > 0) __builtin_amdgcn_sched_barrier(0);
+    const uint32_t off = pre_at<Q>(pk);
+    chain_term_q32<P, CAP>(tile, off, !MISS || off != kNoLoc, ci, cmf, vs, vu, c2f, gwf);
+    chain_sweep_pk<NS, P, CAP, MISS, Q + 1>(tile, pk, ci, cmf, vs, vu, c2f, gwf);
+  }
+}
 // Diagnostic build only (-DDC_BLOCK_TRACE, tools/block_trace.py): every block of the two one-pass step kernels records where and
 // when it ran -- {XCC | HW_ID, start, end} on the 100 MHz constant clock -- so that the schedule of a launch can be drawn (which
 // CU got how many blocks, when each CU ran dry).  The product library is built without it: the macros expand to nothing.
@@ -538,8 +612,9 @@ __device__ unsigned long long* g_block_trace = nullptr;
 #define DC_TRACE_END() do {} while (0)
 #endif
 
-template <int NS, int P, int CAP>
-__global__ __launch_bounds__(kBlock, (StepRow<q32, P>::kPieces * CAP * 16 <= 25 * 1024 ? 6 : 4)) void consistency_step_q32_kernel(
+// BLOCKS: what the launch bounds ask for; dc_set_option(9, 1) runs the instantiation with six where the default is seven (A-B)
+template <int NS, int P, int CAP, int BLOCKS = step_q32_blocks<P, CAP>()>
+__global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
     PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, const int32_t* __restrict__ centre_idx, int64_t n,
     const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
     StepChain ch) {
@@ -556,28 +631,40 @@ __global__ __launch_bounds__(kBlock, (StepRow<q32, P>::kPieces * CAP * 16 <= 25 
   const int64_t nblocks = (n + kBlock - 1) / kBlock;
   int64_t blk = chain_block_of(ch, chained, nblocks);
   if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
-  double acc2[2] = {0.0, 0.0}, gw[P];
+  // the lane's loss and dL/dw; the COUNT is kept per wavefront: every lane adds 0 or 1, so the wavefront's total is the number of
+  // lanes that add 1 -- the same double as their sum in any order
+  double loss = 0.0, gw[P];
+  bool cnt_lane = false;
 #pragma unroll
   for (int k = 0; k < P; ++k) gw[k] = 0.0;
   const int32_t s0 = blk >= 0 ? tab.slot_ptr[blk] : 0;
   bool bad = blk >= 0 && tab.slot_ptr[blk + 1] - s0 != NS;
   if (blk >= 0 && !bad) {
-    const int64_t i = blk * kBlock + threadIdx.x;
-    const bool live = i < n;
-    const bool in_mask = live && (mask ? mask[i] != 0 : true);
-    const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock + threadIdx.x;
-    uint32_t pre[NS];
+    // (what is the same for the whole block stays in scalar registers -- the block's first index, its part of the masks and of the
+    // table -- and a lane adds its 32-bit position: no 64-bit lane index lives through the kernel)
+    const uint32_t tid = threadIdx.x;
+    const int64_t i0 = blk * kBlock, left = n - i0;
+    const uint32_t n_live = left < kBlock ? (uint32_t)left : (uint32_t)kBlock;
+    const bool live = tid < n_live;
+    const uint8_t* mask_blk = mask ? mask + i0 : nullptr;
+    const bool in_mask = live && (mask_blk ? mask_blk[tid] != 0 : true);
+    const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock;
+    constexpr int NW = (NS + 1) / 2;
+    uint32_t pk[NW];
 #pragma unroll
-    for (int q = 0; q < NS; ++q) pre[q] = (uint32_t)lrow[q * kBlock];
+    for (int j = 0; j < NW; ++j)
+      pk[j] = (uint32_t)lrow[(uint32_t)(2 * j * kBlock) + tid] |
+              (2 * j + 1 < NS ? (uint32_t)lrow[(uint32_t)((2 * j + 1 < NS ? 2 * j + 1 : 0) * kBlock) + tid] << 16 : 0u);
     const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
     const int32_t own = (own_base && !centre_idx) ? own_base[blk] : -1;
+    const int32_t* ids = tab.blk_ids + base;
     double wq[P];
     if (chained) {
       // fetch the rows this lane stages before waiting for the weights of this launch (consistency_step_basis_kernel)
       typename StepRow<q32, P>::Raw r0, r1;
-      const int t0 = threadIdx.x, t1 = threadIdx.x + kBlock;
-      if (t0 < nd) r0 = StepRow<q32, P>::fetch(pb, tab.blk_ids[base + t0]);
-      if (t1 < nd) r1 = StepRow<q32, P>::fetch(pb, tab.blk_ids[base + t1]);
+      const int t0 = (int)tid, t1 = (int)tid + kBlock;
+      if (t0 < nd) r0 = StepRow<q32, P>::fetch(pb, ids[t0]);
+      if (t1 < nd) r1 = StepRow<q32, P>::fetch(pb, ids[t1]);
       chain_weights<P>(ch, pb.w_scale, s_w, s_ok);
       __syncthreads();
       if (!s_ok[0]) bad = true;
@@ -585,71 +672,76 @@ __global__ __launch_bounds__(kBlock, (StepRow<q32, P>::kPieces * CAP * 16 <= 25 
       for (int k = 0; k < P; ++k) wq[k] = s_w[k];
       if (t0 < nd) StepRow<q32, P>::place(r0, wq, tile, cap, t0);
       if (t1 < nd) StepRow<q32, P>::place(r1, wq, tile, cap, t1);
-      for (int t = threadIdx.x + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
+      for (int t = (int)tid + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
     } else {
       stage_weights(pb, s_w);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      for (int t = threadIdx.x; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, tab.blk_ids[base + t], tile, cap, t);
+      for (int t = (int)tid; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
     }
     Pt<q32>::Raw ci;
-    if (own < 0) ci = Basis<q32>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)centre_idx[i] : i) : 0);
+    if (own < 0) ci = Basis<q32>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)(centre_idx + i0)[tid] : i0 + tid) : 0);
     __syncthreads();
-    if (own >= 0) ci = staged_point<q32>(tile, cap, own + (live ? (int)threadIdx.x : 0));
+    if (own >= 0) ci = staged_point<q32>(tile, cap, own + (live ? (int)tid : 0));
     // a wavefront whose centres are ALL outside the loss mask adds nothing to the loss, the count or dL/dw (every term carries the
     // centre's mask): it has staged its rows and is done.  The plan groups masked-out points at the end of every block, so
     // these are whole wavefronts (bench.py reports their share).
     if (live && (!mask || __any((int)in_mask))) {
       CovAcc acc;
       cov_init(acc);
-      // positions are multiples of 16, the empty-slot mark 0xFFFF is not: bit 0 of the OR of a lane's positions tells
-      uint32_t mo = pre[0];
+      // positions are multiples of 16, the empty-slot mark 0xFFFF is not: bit 0 of either half of the OR of a lane's words tells
+      uint32_t mo = pk[0];
 #pragma unroll
-      for (int q = 1; q < NS; ++q) mo |= pre[q];
-      const bool any_miss = __any((int)(mo & 1u)) != 0;
+      for (int j = 1; j < NW; ++j) mo |= pk[j];
+      const bool any_miss = __any((int)(mo & 0x00010001u)) != 0;
       int n_have;
-      if (any_miss) n_have = gather_fixed<q32, NS, true>(tile, cap, ci, pre, acc);
-      else n_have = gather_fixed<q32, NS, false>(tile, cap, ci, pre, acc);
+      if (any_miss) n_have = gather_fixed_pk<NS, true>(tile, ci, pk, acc);
+      else n_have = gather_fixed_pk<NS, false>(tile, ci, pk, acc);
       acc.W = (double)n_have;
-      double cm[3], v0[3], c1, c2;
+      double cm[3], v0[3], c1, c2, acc2[2] = {0.0, 0.0};
       step_point2<q32, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
+      loss = acc2[0];
+      cnt_lane = acc2[1] != 0.0;
       float cmf[3], vs[3], vu[3], gwf[P];
 #pragma unroll
       for (int a = 0; a < 3; ++a) { cmf[a] = (float)cm[a]; vs[a] = (float)(c1 * v0[a]); vu[a] = (float)v0[a]; }
       const float c2f = (float)c2;
 #pragma unroll
       for (int k = 0; k < P; ++k) gwf[k] = 0.0f;
-      // (groups of four with a scheduling fence between them: left alone, the compiler requests every row piece up front
-      // and the kernel loses wavefronts per SIMD to the registers)
-      if (any_miss) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-          if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-          chain_term_q32<P, CAP>(tile, pre[q], pre[q] != kNoLoc, ci, cmf, vs, vu, c2f, gwf);
-        }
+      // the centre is not carried through the tail (three registers at its widest point): the same words, read again
+      asm volatile("" ::: "memory");
+      Pt<q32>::Raw cs;
+      if (own >= 0) {
+        cs = staged_point<q32>(tile, cap, own + (int)tid);
       } else {
+        double w2[P];
 #pragma unroll
-        for (int q = 0; q < NS; ++q) {
-          if (q % 4 == 0 && q > 0) __builtin_amdgcn_sched_barrier(0);
-          chain_term_q32<P, CAP>(tile, pre[q], true, ci, cmf, vs, vu, c2f, gwf);
-        }
+        for (int k = 0; k < P; ++k) w2[k] = s_w[k];
+        cs = Basis<q32>::template point<P>(pb, w2, centre_idx ? (int64_t)(centre_idx + i0)[tid] : i0 + tid);
       }
+      if (any_miss) chain_sweep_pk<NS, P, CAP, true>(tile, pk, cs, cmf, vs, vu, c2f, gwf);
+      else chain_sweep_pk<NS, P, CAP, false>(tile, pk, cs, cmf, vs, vu, c2f, gwf);
       const double u = qp.scale;
 #pragma unroll
       for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k] * u;          // differences were in grid steps
     }
   }
-  if (bad) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  // ---- {sum loss, count, dL/dw} of the wavefront (one row per wavefront; chained: per block), as step_partials
+  const double nan_ = __longlong_as_double(0x7ff8000000000000ll);
+  if (bad) loss = nan_;
+  // ---- {sum loss, count, dL/dw} of the wavefront (one row per wavefront; chained: per block), as step_partials; the count's
+  // column of the packed reduction carries zeros and its lane takes the number of counting lanes instead (NaN when `bad`,
+  // as the sum of the lanes' NaNs was)
+  const double cnt = bad ? nan_ : (double)__popcll(__ballot((int)cnt_lane));
   double v[NP2];
-  v[0] = acc2[0]; v[1] = acc2[1];
+  v[0] = loss; v[1] = 0.0;
 #pragma unroll
   for (int k = 0; k < NP2 - 2; ++k) v[2 + k] = k < P ? gw[k] : 0.0;
   double tot;
   if constexpr (NP2 == 4) tot = wave_sum4_dpp(v);
-  else tot = wave_sum_packed<NP2>(v);
+  else tot = wave_sum8_regs(v);
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (packed_value_of_lane<NP2>(lane & (NP2 - 1)) == 1) tot = cnt;
   int64_t rs = (int64_t)gridDim.x * kWavesPerBlock, row = (int64_t)blockIdx.x * kWavesPerBlock + wave;
   if (chained) {
     if (lane < NP2) s_comb[wave * NP2 + lane] = tot;

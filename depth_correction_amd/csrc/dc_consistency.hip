@@ -1179,6 +1179,9 @@ static std::atomic<int> g_step_var{1};
 static std::atomic<bool> g_pose_three_pass{false};
 // dc_set_option(8, 1): every launch of a chain walks the blocks forwards (A-B, chain_block_of)
 static std::atomic<bool> g_no_reverse{false};
+// dc_set_option(9, 1): consistency_step_q32_kernel built for six blocks per CU where the default is built for seven (the 512-row tile,
+// one or two weights): the same body under __launch_bounds__(kBlock, 6) (A-B, tests); the other instantiations are not affected
+static std::atomic<bool> g_step_six{false};
 
 // consistency_step_ragged_q32_kernel with a tile of CAP rows: more than 64 KB of LDS per block needs the attribute (once per
 // instantiation, process and device).  Capacities up to the table's own limit (4095 rows), so every ball-neighbourhood table that can be
@@ -1601,6 +1604,7 @@ int dc_set_option(int option, int value) {
   if (option == 6) { g_step_var.store(value); return DC_OK; }
   if (option == 7) { g_pose_three_pass.store(value != 0); return DC_OK; }
   if (option == 8) { g_no_reverse.store(value != 0); return DC_OK; }
+  if (option == 9) { g_step_six.store(value != 0); return DC_OK; }
   return DC_ERR_ARG;
 }
 
@@ -1814,7 +1818,17 @@ static int sequence_eval_impl(const dcSequenceDesc* d, const double* w, const do
                                                  d->centre_idx, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch)
 #define STEPQ_P(NS, CAP) do { if (n_terms == 2) STEPQ_LAUNCH(NS, 2, CAP); else if (n_terms == 1) STEPQ_LAUNCH(NS, 1, CAP); else STEPQ_LAUNCH(NS, 3, CAP); } while (0)
 #define STEPQ_K(CAP) do { if (fixed_k == 10) STEPQ_P(10, CAP); else if (fixed_k == 4) STEPQ_P(4, CAP); else if (fixed_k == 8) STEPQ_P(8, CAP); else STEPQ_P(16, CAP); } while (0)
-        if (rows_s <= 512) STEPQ_K(512); else STEPQ_K(768);
+        // (dc_set_option(9, 1): the six-blocks-per-CU build of the instantiations whose default is seven)
+#define STEPQ_SIX(NS, P) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), grid, block, 0, stream, pb, tab, d->fwd_table->own_base, \
+                                         d->centre_idx, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch)
+#define STEPQ_SIX_P(NS) do { if (n_terms == 2) STEPQ_SIX(NS, 2); else STEPQ_SIX(NS, 1); } while (0)
+        static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
+                      "which instantiations dc_set_option(9, 1) has a six-block build of");
+        if (rows_s <= 512 && n_terms <= 2 && g_step_six.load()) {
+          if (fixed_k == 10) STEPQ_SIX_P(10); else if (fixed_k == 4) STEPQ_SIX_P(4); else if (fixed_k == 8) STEPQ_SIX_P(8); else STEPQ_SIX_P(16);
+        } else if (rows_s <= 512) STEPQ_K(512); else STEPQ_K(768);
+#undef STEPQ_SIX_P
+#undef STEPQ_SIX
 #undef STEPQ_K
 #undef STEPQ_P
 #undef STEPQ_LAUNCH

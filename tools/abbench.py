@@ -3,7 +3,8 @@
 builds the C2 sequence once, then for every `--var` value (dc_set_option(6, v)) times chained steps and compares the
 evaluation's sums with the first variant's.
 
-    python3 tools/abbench.py --var 0 1 3 7 [--rounds 5] [--steps 200] [--scans 10] [--points 200000] [--k 10]"""
+    python3 tools/abbench.py --var 0 1 3 7 [--rounds 5] [--steps 200] [--scans 10] [--points 200000] [--k 10]
+    python3 tools/abbench.py --opt 9 --var 0 1      (the step kernel built for seven resident blocks per CU against six)"""
 import argparse
 import json
 import os

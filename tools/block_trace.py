@@ -29,6 +29,7 @@ def main():
     ap.add_argument('--heavy-first', type=int, default=1)
     ap.add_argument('--points', type=int, default=200_000)
     ap.add_argument('--forwards', type=int, default=0, help='1: dc_set_option(8, 1), every launch of the chain walks the blocks forwards')
+    ap.add_argument('--six', type=int, default=0, help='1: dc_set_option(9, 1), the C2 step kernel built for six resident blocks per CU instead of seven')
     ap.add_argument('--lib', default=os.path.join(ROOT, 'build', 'libdc_hip_trace.so'))
     args = ap.parse_args()
     from depth_correction_amd import _native
@@ -49,6 +50,7 @@ def main():
     else:
         plan, info = build_sequence(scans, poses, k=10, dtype=torch.float32, device=dev)
     _native.lib().dc_set_option(8, int(args.forwards))
+    _native.lib().dc_set_option(9, int(args.six))
     tr = SequenceTrainer([plan], [1e-3, 2e-3], [2.0, 4.0], [info['poses']], lr=1e-3, chained=True)
     for _ in range(300):
         tr.step()
@@ -86,6 +88,24 @@ def main():
         last = np.array([t1[cuid == c].max() for c in ids]) - begin
         first = np.array([t0[cuid == c].min() for c in ids]) - begin
         q = lambda a: [round(float(v), 2) for v in np.percentile(a, [0, 10, 50, 90, 100])]
+
+        def resident(c):
+            """Largest number of blocks on CU c at the same time (a block that ends on the tick another starts has left)."""
+            ev = sorted([(s, 1) for s in t[cuid == c, 1]] + [(e, -1) for e in t[cuid == c, 2]])
+            return int(np.max(np.cumsum([d for _, d in ev])))
+        res = np.array([resident(c) for c in ids])
+
+        def time_at_levels():
+            """Share of the CUs' time (first start to last end of each CU) spent with 0, 1, 2, ... blocks resident."""
+            tot = {}
+            for c in ids:
+                ev = sorted([(s, 1) for s in t[cuid == c, 1]] + [(e, -1) for e in t[cuid == c, 2]])
+                lvl, last_t = 0, ev[0][0]
+                for tm, d in ev:
+                    tot[lvl] = tot.get(lvl, 0) + int(tm - last_t)
+                    lvl, last_t = lvl + d, tm
+            s = float(sum(tot.values()))
+            return {int(k): round(v / s, 4) for k, v in sorted(tot.items())}
         # where the dispatcher puts block g of the grid: the same CU as block g - 256 / g - 8?  (rows of the trace are blockIdx.x)
         full = buf.cpu().numpy()
         g = np.nonzero(full[:, 3] == 1)[0]
@@ -105,6 +125,7 @@ def main():
                     'cu_first_start_us': q(first), 'cu_last_end_us': q(last),
                     'cu_busy_block_us_sum': q(busy),
                     'blocks_started_after_half': int((t0 - begin > (end - begin) / 2).sum()),
+                    'max_blocks_resident_on_one_cu': int(res.max()), 'share_of_cu_time_by_resident_blocks': time_at_levels(), 'cus_by_max_resident_blocks': {int(v): int((res == v).sum()) for v in np.unique(res)},
                     'mean_concurrency': round(float(dur.sum() / (end - begin)), 1),
                     'placement': place, 'share_of_slot_time_idle_at_the_end': round(float(((end - begin) - last).sum() / (len(ids) * (end - begin))), 3)})
     print(json.dumps(out, indent=1))
