@@ -33,6 +33,11 @@ DC_BIAS_MAX_BINS, DC_BIAS_MAX_TERMS, DC_BIAS_TOTALS, DC_BIAS_BIN_COLS = 256, 4, 
 DC_BEAM_MAX_SAMPLES = 64
 BEAM_DETECTIONS = {'mean': 0, 'quantile': 1}
 BEAM_WEIGHTS = {'uniform': 0, 'lambert': 1}
+# include/dc_hip.h: the survey registration state (DC_ALIGN_STATE_*), its block partials, history row and status codes (DC_ALIGN_*)
+DC_ALIGN_STATE_COUNT, DC_ALIGN_STATE_POSE, DC_ALIGN_STATE_PRIOR, DC_ALIGN_STATE_THRESHOLD = 64, 0, 16, 32
+DC_ALIGN_STATE_PAIRS, DC_ALIGN_STATE_RMS, DC_ALIGN_STATE_D_ROT, DC_ALIGN_STATE_D_TRANS = 33, 34, 35, 36
+DC_ALIGN_PARTIALS, DC_ALIGN_HISTORY_COLS = 17, 5
+ALIGN_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'degenerate', -3: 'not_finite'}
 ICP_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'singular', -3: 'not_finite', -4: 'bound'}
 
 _LIB = None
@@ -192,6 +197,14 @@ _SIGNATURES = {
     'dc_image_features_fwd': (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
     'dc_image_shadow_mask': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _vp]),
+    # survey registration (csrc/dc_align.hip)
+    'dc_align_blocks': (_i32, [_i64]),
+    'dc_align_init': (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
+    'dc_align_accumulate': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'dc_align_finish': (_i32, [_vp, _i32, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    'dc_survey_align_workspace_bytes': (_sz, [_i64]),
+    'dc_survey_align': (_i32, [_vp, _sz, _i64, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
+                               _vp]),
 }
 
 

@@ -258,6 +258,11 @@ class Config(object):
         self.map_eval_poses = 'dataset'
         self.map_eval_inlier_ratio = 0.8
         self.map_eval_samples = 0
+        # map_eval_register: eval_map first registers the map to the dataset's survey (registration.register_cloud with
+        # register_kwargs; DESIGN "Survey registration") and takes the accuracy of the registered points -- for maps whose poses are
+        # not in the survey's frame
+        self.map_eval_register = False
+        self.register_kwargs = {'inlier_ratio': 0.8, 'max_dist': 1.0, 'n_iters': 50, 'min_rot': 1e-6, 'min_trans': 1e-6}
         # depth bias against the ground-truth mesh (eval.eval_bias, DESIGN "Depth bias against the mesh"; not in the reference's
         # Config): eval_bias appends a line per sequence to bias_eval_csv and writes the per-bin table to bias_eval_curve_csv; bins of
         # the true incidence angle over [0, pi/2]; rays with |d - t| above bias_eval_max_residual (metres) are left out; back-face

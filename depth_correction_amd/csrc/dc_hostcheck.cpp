@@ -14,6 +14,7 @@
 #include "dc_planemath.h"
 #include "dc_dynmath.h"
 #include "dc_rangeimage_math.h"
+#include "dc_align_math.h"
 
 extern "C" {
 
@@ -557,6 +558,29 @@ int dc_host_range_project(const double* points, int64_t n, int rows, int cols, d
   }
   delete[] keys;
   return DC_OK;
+}
+
+// ---- survey registration (dc_align_math.h; dc_align.hip's finish kernel) ----
+// The closed-form fit from the totals tot [17] and the origins o [6]: T [16], lam [4] descending; 1 = the rotation is not unique
+int dc_host_align_solve(const double* tot, const double* o, double* T, double* lam) { return dc::align_solve(tot, o, T, lam); }
+
+// Angle of Ra Rb^T for two row-major 4 x 4 transforms (atan2 of the axial vector and the trace)
+double dc_host_align_angle(const double* Ta, const double* Tb) { return dc::rotation_angle_between(Ta, 4, Tb, 4); }
+
+// dc_align_finish on the host: the same argument checks, the partials summed in the kernel's order, the same tail; state
+// [DC_ALIGN_STATE_COUNT], status [4] and history [n_history_rows, 5] (optional) are host arrays.  0, or 1 for refused arguments.
+int dc_host_align_finish(const double* partials, int n_blocks, const double* origins, double min_rot, double min_trans, int min_pairs,
+                         int max_iters, double* state, int32_t* status, double* history, int n_history_rows) {
+  if (!partials || !origins || !state || !status || n_blocks < 1 || n_blocks > dc::kAlignBlocksMax) return 1;
+  if (!(min_rot >= 0.0) || !(min_trans >= 0.0) || min_pairs < 3 || max_iters < 1 || n_history_rows < 0) return 1;
+  if (status[0] != 0) return 0;
+  double tot[DC_ALIGN_PARTIALS];
+  for (int q = 0; q < DC_ALIGN_PARTIALS; ++q) tot[q] = dc::align_block_sum(partials, n_blocks, q);
+  const dc::AlignParams prm{min_rot, min_trans, min_pairs, max_iters};
+  const int row = status[1];
+  double* hist = (history && row >= 0 && row < n_history_rows) ? history + (int64_t)row * DC_ALIGN_HISTORY_COLS : nullptr;
+  dc::align_finish_tail(tot, origins, prm, state, status, hist);
+  return 0;
 }
 
 }  // extern "C"

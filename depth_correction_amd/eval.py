@@ -355,6 +355,7 @@ def eval_slam(cfg: Config, test_datasets=None, model=None):
     import os
     from .io import append
     from .scan_io import write_poses_csv
+    from .registration import align_paths
     from .slam import run_slam, slam_errors
     if cfg.slam not in SLAM:
         raise ValueError('SLAM pipeline %r is not available here; available: %s' % (cfg.slam, ', '.join(SLAM)))
@@ -373,6 +374,9 @@ def eval_slam(cfg: Config, test_datasets=None, model=None):
         if cfg.slam_compute_prob_dynamic and res['info']:
             print('Dynamic map points: %d of %d.' % (res['info'][-1]['dynamic'], res['info'][-1]['map_size']))
         append(cfg.slam_eval_csv, '%s %.9f %.9f %.9f %.9f\n' % (name, r_angle, t_norm, rel_angle, rel_offset))
+        # the SLAM path rigidly aligned to the ground truth (scripts/paths_alignment): what is left is the path's shape error
+        res['aligned'] = align_paths(res['slam'], res['gt'], fix_reflection=True)
+        print('Aligned path error: rmse %.6f m (mean %.6f m).' % (res['aligned']['rmse'], res['aligned']['mean']))
         if cfg.slam_poses_csv:
             if os.path.exists(cfg.slam_poses_csv):
                 print('File with SLAM poses already exists: %s. It will be overwritten.' % cfg.slam_poses_csv)
@@ -420,8 +424,11 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
     instead of a surveyed cloud): each scan goes through slam.mapper_input (depth and grid filters, the correction by ``model``,
     from the configuration unless given), is moved by its pose -- ``cfg.map_eval_poses`` 'dataset': the poses the dataset yields,
     'slam': the poses slam.run_slam estimates -- the clouds are concatenated and voxel-filtered with filter_grid(keep='first') at
-    cfg.grid_res (mapping_accuracy:106; skipped when 0), and metrics.map_accuracy is taken.  Appends ``name n mean rms median
-    trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and returns the per-sequence dicts."""
+    cfg.grid_res (mapping_accuracy:106; skipped when 0), and metrics.map_accuracy is taken.  With ``cfg.map_eval_register`` the
+    filtered map is first registered to the dataset's survey (its own, or the one sampled from its mesh) by
+    registration.register_cloud(**cfg.register_kwargs), the accuracy is that of the registered points and ``res['registration']``
+    holds the Registration.  Appends ``name n mean rms median trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and
+    returns the per-sequence dicts."""
     from .filters import filter_grid
     from .io import append
     from .metrics import map_accuracy
@@ -449,9 +456,19 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
         points = torch.cat(moved).contiguous() if moved else torch.empty((0, 3), dtype=torch.float64, device=cfg.device)
         if cfg.grid_res and cfg.grid_res > 0.0 and points.shape[0]:
             points = filter_grid(points, float(cfg.grid_res), keep='first').contiguous()
+        reg = None
+        if cfg.map_eval_register:
+            from .registration import register_cloud
+            reg = register_cloud(points, _dataset_survey(ds, name, cfg, who='eval_map with map_eval_register'), **dict(cfg.register_kwargs))
+            print('Registration of the map of %s to its survey: %s after %d iterations, %d pairs, rms %.6f m.'
+                  % (name, reg.status, reg.iterations, reg.pairs, reg.rms))
+            T = torch.as_tensor(reg.T, device=points.device)
+            points = (points @ T[:3, :3].t() + T[:3, 3]).contiguous()
         res = map_accuracy(points, mesh, inlier_ratio=cfg.map_eval_inlier_ratio, n_samples=cfg.map_eval_samples or None,
                            seed=cfg.random_seed)
         res['name'] = name
+        if reg is not None:
+            res['registration'] = reg
         print('Map accuracy on %s: %d points, mean %.6f m, rms %.6f m, median %.6f m, trimmed mean %.6f m, signed mean %.6f m.'
               % ((name, int(res['n'])) + tuple(res[f] for f in MAP_EVAL_FIELDS[1:])))
         if cfg.map_eval_csv:

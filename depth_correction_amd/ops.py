@@ -18,7 +18,8 @@ __all__ = [
     'IcpSequence', 'shadow_mask', 'shadow_filter', 'correct_depth', 'cloud_from_points', 'mask_bounds_all', 'compact_rows', 'to_points', 'valid_weights', 'scan_prefilter',
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace', 'cloud_loss', 'cloud_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
-    'dyn_directions', 'dyn_update',
+    'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
+    'survey_align_workspace',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -1558,6 +1559,132 @@ def cloud_loss(survey_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=Non
                               int(bool(squared)), md, ratio, ptr(idx), ptr(dist), ptr(resid), ptr(out), ptr(ws), ws.shape[0],
                               stream_ptr()), 'dc_cloud_loss')
     return (out, idx, dist, resid) if want_points else out
+
+
+# ------------------------------------------------------------------------------------------------
+# survey registration: trimmed closed-form ICP against a surveyed cloud (csrc/dc_align.hip, registration.py).  As for the SLAM
+# wrappers every output and workspace is the caller's: a queue of iterations allocates nothing and copies nothing.
+# ------------------------------------------------------------------------------------------------
+def align_blocks(n):
+    """Blocks (rows of partials) of align_accumulate for n query points (dc_align_blocks)."""
+    return int(lib().dc_align_blocks(int(n)))
+
+
+def _align_state_args(state, status, dev):
+    need(state, (nv.DC_ALIGN_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+
+
+@on_device
+def align_init(state, status, prior=None, history=None):
+    """state f64 [DC_ALIGN_STATE_COUNT] / status i32 [4] of a registration that starts from prior f64 device [4,4] (None: the
+    identity); history f64 [n_iters, 5] (optional) is filled with NaN (dc_align_init)."""
+    dev = state.device
+    _align_state_args(state, status, dev)
+    if prior is not None:
+        need(prior, (4, 4), dtype=torch.float64, name='prior', device=dev)
+    rows = 0
+    if history is not None:
+        need(history, (None, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, name='history', device=dev)
+        rows = history.shape[0]
+    check(lib().dc_align_init(ptr(prior), ptr(state), ptr(status), ptr(history) if rows else None, rows, stream_ptr()), 'dc_align_init')
+
+
+@on_device
+def align_accumulate(query, map_points, idx, dist, threshold, origins, partials, status=None, kept=None):
+    """Moments of the kept pairs (idx >= 0 and dist <= threshold) of query f64 [N,3] and map_points[idx] about origins f64 [6] -> block
+    partials f64 [align_blocks(N), DC_ALIGN_PARTIALS] (dc_align_accumulate); idx i32 / dist f64 [N] or [N,1] as knn_grid_query returns
+    them; ``kept`` (uint8 [N], optional) receives the kept flags; ``status`` (i32 [4], optional): nothing is done once it is set."""
+    dev = query.device
+    need(query, (None, 3), dtype=torch.float64, name='query')
+    n = query.shape[0]
+    if n < 1:
+        raise ValueError('align_accumulate needs at least one query point')
+    need(map_points, (None, 3), dtype=torch.float64, name='map_points', device=dev)
+    if map_points.shape[0] < 1:
+        raise ValueError('align_accumulate needs at least one map point')
+    if idx.dim() == 2:
+        idx, dist = idx.reshape(-1), dist.reshape(-1)
+    need(idx, (n,), dtype=torch.int32, name='idx', device=dev)
+    need(dist, (n,), dtype=torch.float64, name='dist', device=dev)
+    need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
+    need(origins, (6,), dtype=torch.float64, name='origins', device=dev)
+    nb = align_blocks(n)
+    need(partials, (nb, nv.DC_ALIGN_PARTIALS), dtype=torch.float64, name='partials', device=dev)
+    if status is not None:
+        need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    if kept is not None:
+        need(kept, (n,), dtype=torch.uint8, name='kept', device=dev)
+    check(lib().dc_align_accumulate(ptr(query), n, ptr(map_points), map_points.shape[0], ptr(idx), ptr(dist), ptr(threshold), ptr(origins),
+                                    ptr(status), ptr(partials), nb, ptr(kept), stream_ptr()), 'dc_align_accumulate')
+
+
+@on_device
+def align_finish(partials, origins, state, status, min_rot=0.0, min_trans=0.0, min_pairs=3, max_iters=1, history=None):
+    """Sum the partials, fit, update and check one registration iteration in one block (dc_align_finish); history f64 [rows, 5]
+    (optional): the row of this iteration is written."""
+    dev = partials.device
+    need(partials, (None, nv.DC_ALIGN_PARTIALS), dtype=torch.float64, name='partials')
+    need(origins, (6,), dtype=torch.float64, name='origins', device=dev)
+    _align_state_args(state, status, dev)
+    rows = 0
+    if history is not None:
+        need(history, (None, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, name='history', device=dev)
+        rows = history.shape[0]
+    check(lib().dc_align_finish(ptr(partials), partials.shape[0], ptr(origins), float(min_rot), float(min_trans), int(min_pairs),
+                                int(max_iters), ptr(state), ptr(status), ptr(history) if rows else None, rows, stream_ptr()), 'dc_align_finish')
+
+
+def survey_align_workspace(n, device):
+    """Workspace of survey_align for n query points (uint8 tensor)."""
+    return _ws(lib().dc_survey_align_workspace_bytes(int(n)), device)
+
+
+@on_device
+def survey_align(survey_dev, query, origins, prior=None, inlier_ratio=1.0, max_dist=None, n_iters=100, min_rot=0.0, min_trans=0.0,
+                 min_pairs=3, state=None, status=None, history=None, ws=None):
+    """A whole trimmed closed-form ICP of query f64 [N,3] (N >= 1) against ``survey_dev`` (survey.SurveyOnDevice) queued on the stream
+    in one host call (dc_survey_align): n_iters x {knn_grid_query, quantile, align_accumulate, align_finish}, which return at once
+    after the status word is set.  origins f64 device [6] = (o_p, o_y); prior f64 device [4,4] (None: the identity).  Returns (state
+    f64 [DC_ALIGN_STATE_COUNT], status i32 [4], history f64 [n_iters, 5]) -- device tensors, nothing is read back."""
+    dev = survey_dev.device
+    need(query, (None, 3), dtype=torch.float64, name='query', device=dev)
+    n = query.shape[0]
+    if n < 1:
+        raise ValueError('survey_align needs at least one query point')
+    if max_dist is None:
+        raise ValueError('survey_align needs max_dist (finite, > 0)')
+    md, ratio, n_iters, min_pairs = float(max_dist), float(inlier_ratio), int(n_iters), int(min_pairs)
+    if not (md > 0.0 and md < float('inf')):
+        raise ValueError('max_dist must be finite and > 0, got %r' % (max_dist,))
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError('inlier_ratio must lie in (0, 1], got %r' % (inlier_ratio,))
+    if n_iters < 1 or min_pairs < 3 or not float(min_rot) >= 0.0 or not float(min_trans) >= 0.0:
+        raise ValueError('survey_align needs n_iters >= 1, min_pairs >= 3 and min_rot, min_trans >= 0')
+    need(origins, (6,), dtype=torch.float64, name='origins', device=dev)
+    if prior is not None:
+        need(prior, (4, 4), dtype=torch.float64, name='prior', device=dev)
+    need(survey_dev.points, (None, 3), dtype=torch.float64, name='survey points', device=dev)
+    survey_dev.reserve(n)
+    grid = survey_dev.grid
+    state = torch.empty((nv.DC_ALIGN_STATE_COUNT,), dtype=torch.float64, device=dev) if state is None else state
+    status = torch.empty((4,), dtype=torch.int32, device=dev) if status is None else status
+    _align_state_args(state, status, dev)
+    if history is None:
+        history = torch.empty((n_iters, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, device=dev)
+    else:
+        need(history, (n_iters, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, name='history', device=dev)
+    nbytes = lib().dc_survey_align_workspace_bytes(n)
+    if ws is None:
+        ws = _ws(nbytes, dev)
+    else:
+        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
+        if ws.shape[0] < nbytes:
+            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    check(lib().dc_survey_align(ptr(grid.ws), grid.ws.numel(), grid.n_query_max, ptr(survey_dev.points), grid.n, ptr(query), n, ptr(prior),
+                                ratio, md, n_iters, float(min_rot), float(min_trans), min_pairs, ptr(origins), ptr(state), ptr(status),
+                                ptr(history), ptr(ws), ws.shape[0], stream_ptr()), 'dc_survey_align')
+    return state, status, history
 
 
 def icp_blocks(m):

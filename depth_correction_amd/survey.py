@@ -27,6 +27,7 @@ class SurveyOnDevice(object):
         self.points, self.normals, self.grid = points, normals, grid
         self.device = points.device
         self._pose = None
+        self._origin = None
 
     @property
     def n(self):
@@ -36,6 +37,13 @@ class SurveyOnDevice(object):
         if self._pose is None:
             self._pose = torch.eye(4, dtype=torch.float64, device=self.device)
         return self._pose
+
+    def origin(self):
+        """Centre of the survey's bounds, f64 device [3] (computed on the device, once): the origin registration takes the survey's
+        moments about."""
+        if self._origin is None:
+            self._origin = 0.5 * (self.points.amin(dim=0) + self.points.amax(dim=0))
+        return self._origin
 
     def reserve(self, n_query):
         """The grid's query buffer holds ``n_query_max`` rows: rebuild the grid (the same grid, a larger buffer) when more are
@@ -125,6 +133,22 @@ class SurveyCloud(object):
         survey whose true surface is known."""
         pts, normals, _ = mesh.sample(int(n_samples), seed=seed, device=device)
         return SurveyCloud(pts, normals)
+
+    # ---- registration (registration.py; DESIGN "Survey registration") ------------------------------------------------------------
+    def register(self, points, **kw):
+        """registration.register_cloud(points, self, **kw): the Registration whose ``T`` takes ``points`` into this survey's frame."""
+        from .registration import register_cloud
+        return register_cloud(points, self, **kw)
+
+    def transformed(self, T):
+        """A new SurveyCloud whose points are ``T`` (4 x 4 rigid) applied to these and whose normals are rotated with them; it has a
+        device cache (copies and grid) of its own."""
+        T = torch.as_tensor(T.detach().cpu() if isinstance(T, torch.Tensor) else np.asarray(T, dtype=np.float64), dtype=torch.float64)
+        if T.shape != (4, 4):
+            raise ValueError('T must be a 4 x 4 transform, got shape %s' % (tuple(T.shape),))
+        T = T.to(self.points.device)
+        R, t = T[:3, :3], T[:3, 3]
+        return SurveyCloud(self.points @ R.T + t, self.normals @ R.T)
 
     # ---- device side ----------------------------------------------------------------------------------------------------------
     def on_device(self, device):

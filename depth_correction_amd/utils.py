@@ -12,7 +12,7 @@ import time
 
 import torch
 
-__all__ = ['covs', 'trace', 'timing', 'rotation_angle', 'translation_norm', 'transform_inv', 'delta_transform', 'hashable']
+__all__ = ['covs', 'trace', 'timing', 'rotation_angle', 'translation_norm', 'transform_inv', 'delta_transform', 'hashable', 'absolute_orientation']
 
 
 def timing(f):
@@ -105,3 +105,9 @@ def hashable(obj):
     if isinstance(obj, np.ndarray):
         return hashable(obj.tolist())
     return obj
+
+
+def absolute_orientation(x, y, fix_reflection=False):
+    """utils.py:253-304 of the reference: registration.absolute_orientation under the name callers of the reference import."""
+    from .registration import absolute_orientation as fit
+    return fit(x, y, fix_reflection=fix_reflection)
