@@ -23,6 +23,7 @@
 #include "dc_device.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
+#include "dc_cons_chain.h"      // StepHdr
 
 namespace dc {
 
@@ -220,6 +221,42 @@ __global__ __launch_bounds__(kBlock) void bt_block_group_kernel(const int32_t* _
   }
 }
 
+// The per-block step headers (StepHdr, dc_cons_chain.h) of a slot-layout table: one wavefront per 256-point block gathers the
+// block's entries of slot_ptr, blk_ptr, own_base and blk_skip and ballots its 256 mask bytes into four words; lanes 0..15 write
+// the record's sixteen 32-bit words (one 64-byte store per block).
+__global__ __launch_bounds__(kBlock) void bt_step_header_kernel(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ slot_ptr,
+                                                                const int32_t* __restrict__ own_base, const uint8_t* __restrict__ mask,
+                                                                const uint8_t* __restrict__ blk_skip, int64_t n, int64_t n_blocks,
+                                                                uint32_t* __restrict__ hdr) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (b >= n_blocks) return;                                 // (wavefront-uniform)
+  const int64_t i0 = b * kBlock, left = n - i0;
+  const int32_t n_live = left < kBlock ? (int32_t)left : kBlock;
+  uint64_t word[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int l = w * kWave + lane;
+    word[w] = __ballot((int)(l < n_live && (mask ? mask[i0 + l] != 0 : true)));
+  }
+  const int32_t s0 = slot_ptr[b], base = blk_ptr[b];
+  uint32_t v;
+  switch (lane) {
+    case 0: v = (uint32_t)s0; break;
+    case 1: v = (uint32_t)(slot_ptr[b + 1] - s0); break;
+    case 2: v = (uint32_t)base; break;
+    case 3: v = (uint32_t)(blk_ptr[b + 1] - base); break;
+    case 4: v = (uint32_t)(own_base ? own_base[b] : -1); break;
+    case 5: v = (blk_skip && blk_skip[b]) ? (uint32_t)kStepHdrSkip : 0u; break;
+    case 6: v = (uint32_t)n_live; break;
+    case 7: v = 0u; break;
+    default: {
+      const uint64_t m = word[((lane - 8) >> 1) & 3];
+      v = (lane & 1) ? (uint32_t)(m >> 32) : (uint32_t)m;
+    }
+  }
+  if (lane < 16) hdr[b * 16 + lane] = v;
+}
 
 // ---- [rows, K] tables, K <= 16: every block on its own, in LDS ---------------------------------------------------------------------
 // The radix-sort build above moves every (block, id) reference through five sort passes, a scan and a scatter (1.8 ms for the
@@ -481,6 +518,18 @@ int dc_block_table_own_base(const int32_t* blk_ptr, const int32_t* blk_ids, int6
   const int64_t nb = blocks_of(n_rows);
   if (nb == 0) return DC_OK;
   hipLaunchKernelGGL(bt_own_base_kernel, dim3(grid_of(nb)), dim3(kBlock), 0, stream, blk_ptr, blk_ids, n_rows, nb, own_base);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_step_header_build(const dcBlockTable* table, int64_t n_rows, const uint8_t* mask, const uint8_t* blk_skip, void* hdr_out,
+                         hipStream_t stream) {
+  if (!table || n_rows < 0 || table->layout != DC_TABLE_SLOTS || !table->blk_ptr || !table->slot_ptr) return DC_ERR_ARG;
+  const int64_t nb = blocks_of(n_rows);
+  if (nb == 0) return DC_OK;
+  if (!hdr_out || ((uintptr_t)hdr_out & 63)) return DC_ERR_ARG;
+  hipLaunchKernelGGL(bt_step_header_kernel, dim3((unsigned)((nb + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, stream,
+                     table->blk_ptr, table->slot_ptr, table->own_base, mask, blk_skip, n_rows, nb, (uint32_t*)hdr_out);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

@@ -1,5 +1,6 @@
 // Chained steps: the Adam update and the final sums of one evaluation inside the launch of the next (StepChain, the leading blocks,
-// the published weights and the wait for them).  A part of dc_consistency.hip, included after dc_cons_basis.h.
+// the published weights and the wait for them), and the step kernel's per-block header (StepHdr).  A part of dc_consistency.hip, included
+// after dc_cons_basis.h; dc_blocktab.hip includes it for StepHdr's layout (it needs dc_device.h only).
 #pragma once
 
 namespace dc {
@@ -53,7 +54,22 @@ struct StepChain {
   const uint8_t* blk_skip;   // [blocks] or nullptr: blocks none of whose centres is inside the loss mask (dcSequenceDesc.blk_skip): they add
                              // nothing to the loss, the count or dL/dw and are treated like the padding blocks of the last round
 };
-constexpr int32_t kStatusChainTimeout = 2;     // (bit 0: q32 overflow, raised by quantize())
+// What a block of consistency_step_q32_kernel needs before it can fetch anything, as ONE 64-byte record per 256-point block
+// (dcSequenceDesc.step_hdr, built by dc_step_header_build in dc_blocktab.hip, which includes this file for the layout): the
+// block's entries of slot_ptr, blk_ptr, own_base and blk_skip and its 256 mask bytes were five arrays and six dependent trips;
+// the first 32 bytes are one scalar load, a wavefront's in_mask word a second, issued together.
+struct alignas(64) StepHdr {
+  int32_t s0, nslots;        // slot_ptr[blk], slot_ptr[blk + 1] - slot_ptr[blk]
+  int32_t base, nd;          // blk_ptr[blk], blk_ptr[blk + 1] - blk_ptr[blk]
+  int32_t own;               // own_base[blk], or -1 (no own_base: a table for a compact centre list)
+  int32_t flags;             // bit 0 (kStepHdrSkip): no centre of the block is inside the loss mask (blk_skip[blk])
+  int32_t n_live;            // min(256, n - 256 blk)
+  int32_t reserved;
+  uint64_t in_mask[4];       // bit l of word w: lane 64 w + l is live and inside the mask (no mask: live)
+};
+static_assert(sizeof(StepHdr) == 64, "one record per cache-line half: a block's header never straddles two");
+constexpr int32_t kStepHdrSkip = 1;
+constexpr int32_t kStatusChainTimeout = 2;    // (bit 0: q32 overflow, raised by quantize())
 constexpr int kChainFront = 8;             // leading blocks of a chained launch (a multiple of the XCD count)
 
 // The logical block of this workgroup (xcd_block_of); -1: padding.  Every other launch of a chain of fixed-K steps walks its XCD's

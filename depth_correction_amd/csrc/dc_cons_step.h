@@ -615,9 +615,8 @@ __device__ unsigned long long* g_block_trace = nullptr;
 // BLOCKS: what the launch bounds ask for; dc_set_option(9, 1) runs the instantiation with six where the default is seven (A-B)
 template <int NS, int P, int CAP, int BLOCKS = step_q32_blocks<P, CAP>()>
 __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
-    PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, const int32_t* __restrict__ centre_idx, int64_t n,
-    const uint8_t* __restrict__ mask, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
-    StepChain ch) {
+    PointBasis pb, BlockTab tab, const StepHdr* __restrict__ hdr, const int32_t* __restrict__ centre_idx, int64_t n,
+    LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd, StepChain ch) {
   constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8;
   constexpr int cap = CAP;
   __shared__ int4 tile[StepRow<q32, P>::kPieces * CAP];
@@ -629,25 +628,33 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
   const bool chained = ch.ready != nullptr;
   if (chained && (int)blockIdx.x < ch.n_front) { chain_front_block<P>(ch, s_front); return; }
   const int64_t nblocks = (n + kBlock - 1) / kBlock;
-  int64_t blk = chain_block_of(ch, chained, nblocks);
-  if (blk >= 0 && ch.blk_skip && ch.blk_skip[blk]) blk = -1;            // no centre of this block is inside the loss mask
+  const int64_t blk = chain_block_of(ch, chained, nblocks);
   // the lane's loss and dL/dw; the COUNT is kept per wavefront: every lane adds 0 or 1, so the wavefront's total is the number of
   // lanes that add 1 -- the same double as their sum in any order
   double loss = 0.0, gw[P];
   bool cnt_lane = false;
 #pragma unroll
   for (int k = 0; k < P; ++k) gw[k] = 0.0;
-  const int32_t s0 = blk >= 0 ? tab.slot_ptr[blk] : 0;
-  bool bad = blk >= 0 && tab.slot_ptr[blk + 1] - s0 != NS;
-  if (blk >= 0 && !bad) {
-    // (what is the same for the whole block stays in scalar registers -- the block's first index, its part of the masks and of the
-    // table -- and a lane adds its 32-bit position: no 64-bit lane index lives through the kernel)
+  // the block's header (StepHdr): ONE scalar load of its 64 bytes, waited for once -- everything below hangs on it and on nothing else
+  // the block has to fetch first.  (The wavefront's mask word is picked from the four by scalar selects: as a second load at a
+  // computed offset the compiler made it wait for the first.)
+  typedef int32_t int16v __attribute__((ext_vector_type(16)));
+  int16v hw = {0, 0, 0, 0, 0, kStepHdrSkip, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (blk >= 0) hw = *reinterpret_cast<const int16v*>(hdr + blk);
+  const int wave_s = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+  const uint32_t in_lo = (uint32_t)(wave_s == 0 ? hw[8] : wave_s == 1 ? hw[10] : wave_s == 2 ? hw[12] : hw[14]);
+  const uint32_t in_hi = (uint32_t)(wave_s == 0 ? hw[9] : wave_s == 1 ? hw[11] : wave_s == 2 ? hw[13] : hw[15]);
+  const uint64_t in_word = ((uint64_t)in_hi << 32) | in_lo;
+  const int32_t s0 = hw[0], base = hw[2], nd = hw[3], own = hw[4];
+  const bool skip = (hw[5] & kStepHdrSkip) != 0;                       // padding, or no centre of this block is inside the loss mask
+  bool bad = !skip && hw[1] != NS;
+  if (!skip && !bad) {
+    // (what is the same for the whole block stays in scalar registers -- the block's first index, its part of the table -- and a
+    // lane adds its 32-bit position: no 64-bit lane index lives through the kernel)
     const uint32_t tid = threadIdx.x;
-    const int64_t i0 = blk * kBlock, left = n - i0;
-    const uint32_t n_live = left < kBlock ? (uint32_t)left : (uint32_t)kBlock;
-    const bool live = tid < n_live;
-    const uint8_t* mask_blk = mask ? mask + i0 : nullptr;
-    const bool in_mask = live && (mask_blk ? mask_blk[tid] != 0 : true);
+    const int64_t i0 = blk * kBlock;
+    const bool live = tid < (uint32_t)hw[6];
+    const bool in_mask = ((in_word >> (tid & (kWave - 1))) & 1ull) != 0;
     const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock;
     constexpr int NW = (NS + 1) / 2;
     uint32_t pk[NW];
@@ -655,8 +662,6 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
     for (int j = 0; j < NW; ++j)
       pk[j] = (uint32_t)lrow[(uint32_t)(2 * j * kBlock) + tid] |
               (2 * j + 1 < NS ? (uint32_t)lrow[(uint32_t)((2 * j + 1 < NS ? 2 * j + 1 : 0) * kBlock) + tid] << 16 : 0u);
-    const int32_t base = tab.blk_ptr[blk], nd = tab.blk_ptr[blk + 1] - base;
-    const int32_t own = (own_base && !centre_idx) ? own_base[blk] : -1;
     const int32_t* ids = tab.blk_ids + base;
     double wq[P];
     if (chained) {
@@ -686,8 +691,8 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
     if (own >= 0) ci = staged_point<q32>(tile, cap, own + (live ? (int)tid : 0));
     // a wavefront whose centres are ALL outside the loss mask adds nothing to the loss, the count or dL/dw (every term carries the
     // centre's mask): it has staged its rows and is done.  The plan groups masked-out points at the end of every block, so
-    // these are whole wavefronts (bench.py reports their share).
-    if (live && (!mask || __any((int)in_mask))) {
+    // these are whole wavefronts (bench.py reports their share).  (The wavefront's mask word is zero: a scalar test.)
+    if (live && in_word != 0) {
       CovAcc acc;
       cov_init(acc);
       // positions are multiples of 16, the empty-slot mark 0xFFFF is not: bit 0 of either half of the OR of a lane's words tells

@@ -1795,7 +1795,13 @@ static int sequence_eval_impl(const dcSequenceDesc* d, const double* w, const do
       const dim3 grid((unsigned)(g_blocks + (chain ? kChainFront : 0)));
       const int var = g_step_var.load();
       // float32 clouds with a [rows, K] table: the kernel with fp64 row differences in LDS (48-B rows + its scratch, all dynamic)
-      const bool q32_step = q32_pts && var == 1 && (fixed_k == 10 || fixed_k == 4 || fixed_k == 8 || fixed_k == 16) && rows_s <= 768;
+      // the block headers of the table this pass stages from (dcSequenceDesc.step_hdr: fwd_table_loss's where the descriptor has one);
+      // a caller without them takes consistency_step_basis_kernel, which reads the tables themselves and returns the same sums
+      // (the pass over fwd_table_loss arrives here with that table as fwd_table and no fwd_table_loss; with a compact centre list the
+      // kernel takes the centres by index: a header that names own rows does not describe that)
+      const bool hdr_ok = !d->fwd_table_loss && !(d->centre_idx && d->fwd_table->own_base);
+      const StepHdr* step_hdr = hdr_ok ? static_cast<const StepHdr*>(d->step_hdr) : nullptr;
+      const bool q32_step = q32_pts && var == 1 && (fixed_k == 10 || fixed_k == 4 || fixed_k == 8 || fixed_k == 16) && rows_s <= 768 && step_hdr;
       const bool ragged_step = ragged_ok;
       if (ragged_step) {
         ProfScope prof(1);
@@ -1814,13 +1820,13 @@ static int sequence_eval_impl(const dcSequenceDesc* d, const double* w, const do
       } else if (q32_step) {
         ProfScope prof(1);
         static_assert(kStepQ32Cap == 512, "the profiler names the instantiation by its literal arguments");
-#define STEPQ_LAUNCH(NS, P, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), grid, block, 0, stream, pb, tab, d->fwd_table->own_base, \
-                                                 d->centre_idx, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch)
+#define STEPQ_LAUNCH(NS, P, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), grid, block, 0, stream, pb, tab, step_hdr, \
+                                                 d->centre_idx, n_rows, lp, qp, p_fwd, p_bwd, ch)
 #define STEPQ_P(NS, CAP) do { if (n_terms == 2) STEPQ_LAUNCH(NS, 2, CAP); else if (n_terms == 1) STEPQ_LAUNCH(NS, 1, CAP); else STEPQ_LAUNCH(NS, 3, CAP); } while (0)
 #define STEPQ_K(CAP) do { if (fixed_k == 10) STEPQ_P(10, CAP); else if (fixed_k == 4) STEPQ_P(4, CAP); else if (fixed_k == 8) STEPQ_P(8, CAP); else STEPQ_P(16, CAP); } while (0)
         // (dc_set_option(9, 1): the six-blocks-per-CU build of the instantiations whose default is seven)
-#define STEPQ_SIX(NS, P) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), grid, block, 0, stream, pb, tab, d->fwd_table->own_base, \
-                                         d->centre_idx, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch)
+#define STEPQ_SIX(NS, P) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), grid, block, 0, stream, pb, tab, step_hdr, \
+                                         d->centre_idx, n_rows, lp, qp, p_fwd, p_bwd, ch)
 #define STEPQ_SIX_P(NS) do { if (n_terms == 2) STEPQ_SIX(NS, 2); else STEPQ_SIX(NS, 1); } while (0)
         static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
                       "which instantiations dc_set_option(9, 1) has a six-block build of");

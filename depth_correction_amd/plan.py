@@ -288,6 +288,16 @@ class SequencePlan:
             if self.fwd_table_loss is not None:
                 rows_per_block = np.diff(self.fwd_table_loss.blk_ptr.cpu().numpy())
                 self.fwd_rows_active_loss = int(rows_per_block[keep].max()) if keep.any() else 0
+        # what a block of the one-pass step kernel reads first, one 64-byte record per block (dcSequenceDesc.step_hdr): from the table
+        # that evaluation stages from, this mask and these skipped blocks -- built here, where they are
+        self.step_hdr = None
+        ft = self.fwd_table_loss or self.fwd_table
+        if ft is not None and ft.slot_ptr is not None:
+            self.step_hdr = torch.empty((max((nbr.shape[0] + 255) // 256, 1), 16), dtype=torch.int32, device=dev)
+            m8 = None if mask is None else mask.view(torch.uint8)
+            skip = self.blk_skip if (mask is not None and self.centre_idx is None) else None
+            check(lib().dc_step_header_build(ft.ref(), nbr.shape[0], ptr(m8), ptr(skip), ptr(self.step_hdr), stream_ptr()),
+                  'dc_step_header_build')
         mark('plan_block_tables')
         self.count = float(nbr.shape[0] if mask is None else int(mask.sum().item()))
 
@@ -372,6 +382,7 @@ class SequencePlan:
             d.scan_seg = p(getattr(self, 'scan_seg', None))
             skip = getattr(self, 'blk_skip', None) if (self.mask is not None and self.centre_idx is None) else None
             d.blk_skip, d.fwd_rows_active = p(skip), int(getattr(self, 'fwd_rows_active', 0)) if skip is not None else 0
+            d.step_hdr = p(getattr(self, 'step_hdr', None))
             d.model_kind = nv.MODEL_KINDS[self.model_kind] if n_terms > 0 else 0
             d.n_terms = n_terms
             d.loss_kind, d.normalization, d.sqrt_ = nv.LOSS_KINDS[self.loss], int(self.normalization), int(self.sqrt)

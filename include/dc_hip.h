@@ -238,6 +238,13 @@ typedef struct dcBlockTable {
 } dcBlockTable;
 int dc_block_table_slots(const int32_t* row_ptr, int64_t n_rows, int k, int32_t* slot_cnt_ws, int32_t* slot_ptr,
                          dcStream_t stream);
+/* The per-block headers of the one-pass step kernel (dcSequenceDesc.step_hdr) of a DC_TABLE_SLOTS table over n_rows rows: hdr_out
+ * [ceil(n_rows / 256)] records of 64 bytes, 64-byte aligned -- int32 {slot_ptr[b], slot_ptr[b + 1] - slot_ptr[b], blk_ptr[b],
+ * blk_ptr[b + 1] - blk_ptr[b], own_base[b] (-1 without own_base), flags (bit 0: blk_skip[b]), min(256, n_rows - 256 b), 0} and
+ * uint64 [4]: bit l of word w set when row 256 b + 64 w + l exists and mask (uint8 [n_rows], NULL: every row) is non-zero there.
+ * blk_skip: uint8 [blocks] or NULL (dc_block_group).  Valid for exactly these arrays: build it again when one of them changes. */
+int dc_step_header_build(const dcBlockTable* table, int64_t n_rows, const uint8_t* mask, const uint8_t* blk_skip, void* hdr_out,
+                         dcStream_t stream);
 size_t dc_block_table_workspace_bytes(int64_t n_refs);
 /* A-B switch (measurements, tests; process-wide, not thread-safe like dc_set_option): 0 = [rows, K] tables through the radix-sort
  * build as well; returns the previous setting.  Default 1: K = 4 / 8 / 10 / 16 tables are built block by block in LDS. */
@@ -581,6 +588,14 @@ typedef struct dcSequenceDesc {
                                       gather: shorter lists per block.  Every other evaluation keeps reading fwd_table */
   int32_t fwd_rows_active_loss;    /* fwd_rows_active of fwd_table_loss */
   int32_t reserved3;
+  const void* step_hdr;            /* [ceil(n / 256)] 64-byte records, 64-byte aligned (dc_step_header_build), or NULL.  Each holds what a block
+                                      of the one-pass step kernel of float32 clouds (consistency_step_q32_kernel) reads before it can
+                                      fetch anything: its entries of slot_ptr, blk_ptr, own_base and blk_skip and its mask as bits.  It
+                                      must be built from the table the one-pass evaluation stages from -- fwd_table_loss where the
+                                      descriptor has one, else fwd_table -- with this descriptor's mask, blk_skip and n (n_centres rows
+                                      and no mask with centre_idx), and goes stale whenever that table, the mask or blk_skip is
+                                      rebuilt.  NULL (a caller with a descriptor of its own): dc_sequence_eval and dc_sequence_step* take
+                                      consistency_step_basis_kernel there, which reads the tables themselves and returns the same sums */
 } dcSequenceDesc;
 
 /* Doubles of dcSequenceDesc.partials for a sequence of n points evaluated with up to n_terms weights and n_scans poses:
