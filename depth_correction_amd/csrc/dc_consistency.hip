@@ -24,6 +24,7 @@
 #include "dc_pointmath.h"
 #include "dc_prof.h"
 #include "dc_points_dev.h"
+#include "dc_cons_route.h"
 #include "../../include/dc_hip.h"
 
 namespace dc {
@@ -1207,34 +1208,42 @@ static int ragged_launch(dim3 grid, hipStream_t stream, hipEvent_t ev0, hipEvent
   return DC_OK;
 }
 
-// a usable table of the wanted layout -> LDS bytes / rows of the staged tile (+ `extra_rows`), which must fit `lds_limit`
-static bool use_table(const dcBlockTable* t, int layout, int stride, uint32_t row_bytes, int extra_rows, size_t lds_limit,
-                      size_t* lds_bytes, int* lds_rows) {
-  if (!t || g_no_tab.load() || stride != 4 || t->layout != layout || !t->blk_ptr || !t->loc || t->max_rows < 0) return false;
-  if (layout == DC_TABLE_SLOTS ? !t->slot_ptr : !t->run_ptr) return false;
-  if (t->max_rows > 0 && !t->blk_ids) return false;
-  const size_t rows = (size_t)t->max_rows + extra_rows + (t->max_rows + extra_rows == 0 ? 1 : 0);
-  const size_t need = rows * row_bytes;
-  if (need > lds_limit || t->max_rows >= 0xFFF) return false;       // positions are 16 x row in 16 bits
-  *lds_bytes = need;
-  *lds_rows = (int)rows;
-  return true;
+// dc_cons_route.h restates what the device headers own: every constant and row size it uses is held against the definition here
+static_assert(kRouteBlock == kBlock && kRouteXcds == kXcds && kRouteWavesPerBlock == kWavesPerBlock && kRouteLdsScans == kLdsScans &&
+              kRouteMaxBlockScans == kMaxBlockScans && kRouteStepQ32Cap == kStepQ32Cap && kRouteChainFront == kChainFront, "dc_cons_route.h");
+static_assert(route_xcd_grid(1) == xcd_grid(1) && route_xcd_grid(8) == xcd_grid(8) && route_xcd_grid(7813) == xcd_grid(7813), "dc_cons_route.h");
+static_assert(route_step_row_bytes(false, 1) == StepRow<q32, 1>::kPieces * 16 && route_step_row_bytes(false, 2) == StepRow<q32, 2>::kPieces * 16 &&
+              route_step_row_bytes(false, 3) == StepRow<q32, 3>::kPieces * 16 && route_step_row_bytes(true, 1) == StepRow<double, 1>::kPieces * 16 &&
+              route_step_row_bytes(true, 2) == StepRow<double, 2>::kPieces * 16 && route_step_row_bytes(true, 3) == StepRow<double, 3>::kPieces * 16, "dc_cons_route.h");
+static_assert(route_x_row_bytes(false) == RowBytes<q32>::x && route_x_row_bytes(true) == RowBytes<double>::x &&
+              route_rec_row_bytes(false) == RowBytes<q32>::rec && route_rec_row_bytes(true) == RowBytes<double>::rec, "dc_cons_route.h");
+
+// the switches the route reads, once per call
+static inline RouteOptions route_options() {
+  RouteOptions o;
+  o.no_tab = g_no_tab.load(); o.fwd_generic = g_fwd_generic.load(); o.no_basis = g_no_basis.load(); o.two_pass = g_two_pass.load();
+  o.step_var = g_step_var.load(); o.pose_three_pass = g_pose_three_pass.load(); o.step_six = g_step_six.load();
+  return o;
 }
+
+// The instantiation ladders, written once: M(value, ...) for K = 10 / 4 / 8 / 16 and for one or two weights; OTHER (a statement, may be
+// empty) is what any other value runs -- the slot-loop kernel, the instantiations for three weights where a kernel has them.
+#define DC_SWITCH_K(k, OTHER, M, ...) \
+  do { switch (k) { case 10: M(10, __VA_ARGS__); break; case 4: M(4, __VA_ARGS__); break; case 8: M(8, __VA_ARGS__); break; \
+                    case 16: M(16, __VA_ARGS__); break; default: { OTHER; } } } while (0)
+#define DC_SWITCH_P(p, OTHER, M, ...) \
+  do { if ((p) == 2) M(2, __VA_ARGS__); else if ((p) == 1) M(1, __VA_ARGS__); else { OTHER; } } while (0)
 
 extern "C" {
 
 int dc_version(void) { return 100; }
 
-int64_t dc_partial_rows(int64_t n) { return xcd_grid(n_blocks(n)) * kWavesPerBlock; }
+int64_t dc_partial_rows(int64_t n) { return route_xcd_grid(route_blocks(n)) * kRouteWavesPerBlock; }
 
 int dc_param_grad_count(int n_terms, int n_scans) { return 2 * n_terms + 12 * n_scans; }
 
 // ordinary evaluations: rows x (2 + 2 P + 12 S) columns; chained steps: two buffers of (2 + P) columns behind them (chain_buffer)
-int64_t dc_sequence_partials_count(int64_t n, int n_terms, int n_scans) {
-  if (n < 0 || n_terms < 0 || n_scans < 0) return 0;
-  const int64_t rows = xcd_grid(n_blocks(n)) * kWavesPerBlock;
-  return rows * (2 + 2 * (int64_t)n_terms + 12 * (int64_t)n_scans) + 2 * (2 + (int64_t)n_terms) * rows;
-}
+int64_t dc_sequence_partials_count(int64_t n, int n_terms, int n_scans) { return route_partials_count(n, n_terms, n_scans); }
 
 static PointInputs make_inputs(const void* vps, const void* dirs, const void* depth, const void* inc,
                                const uint8_t* lmask, const int32_t* scan_id, const double* poses, int n_scans,
@@ -1371,7 +1380,7 @@ static int consistency_fwd_impl(const void* points, int stride, int dtype, int p
   BlockTab tab{};
   size_t lds_bytes = 0;
   int lds_rows = 0;
-  const bool staged = use_table(table, DC_TABLE_SLOTS, stride, point_fmt == DC_F64 ? 32u : 16u, 0, 60 * 1024, &lds_bytes, &lds_rows);
+  const bool staged = use_table(table, g_no_tab.load(), DC_TABLE_SLOTS, stride, point_fmt == DC_F64 ? 32u : 16u, 0, 60 * 1024, &lds_bytes, &lds_rows);
   if (staged) tab = BlockTab{table->blk_ptr, table->blk_ids, table->slot_ptr, table->loc};
   const int fixed_k = g_fwd_generic.load() ? 0 : k;        // a table of [rows, k] has k slots in every block
   if (!staged && !nbr) return table ? DC_ERR_UNSUPPORTED : DC_ERR_ARG;
@@ -1384,28 +1393,23 @@ static int consistency_fwd_impl(const void* points, int stride, int dtype, int p
   dim3 grid((unsigned)rows), block(kBlock);
 #define FWD_ARGS(T, PT) (const PT*)points, nbr, centre_idx, n, k, mask, (const T*)offset, lp, qp, (PT*)rec, (T*)pointwise, (T*)eigvals, partials_ws
 #define FWD_STAGED_ARGS(T, PT) (const PT*)points, tab, lds_rows, centre_idx, n, mask, (const T*)offset, lp, qp, (PT*)rec, (T*)pointwise, (T*)eigvals, partials_ws
-#define FWD_FIXED(T, PT, NS) \
-  do { \
-    if (eigvals) DC_TIMED_LAUNCH((consistency_fwd_fixed_kernel<T, PT, true, NS>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT)); \
-    else DC_TIMED_LAUNCH((consistency_fwd_fixed_kernel<T, PT, false, NS>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT)); \
-  } while (0)
+#define DC_SWITCH_EIG(M, ...) do { if (eigvals) M(true, __VA_ARGS__); else M(false, __VA_ARGS__); } while (0)
+#define FWD_FIXED(EIG, T, PT, NS) DC_TIMED_LAUNCH((consistency_fwd_fixed_kernel<T, PT, EIG, NS>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT))
+#define FWD_STAGED(EIG, T, PT) DC_TIMED_LAUNCH((consistency_fwd_staged_kernel<T, PT, EIG>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT))
+#define FWD_GATHER(EIG, T, PT, S) DC_TIMED_LAUNCH((consistency_fwd_kernel<T, PT, S, EIG>), grid, block, 0, stream, FWD_ARGS(T, PT))
+#define FWD_FIXED_K(NS, T, PT) DC_SWITCH_EIG(FWD_FIXED, T, PT, NS)
 #define LAUNCH(T, PT, S) \
   do { \
-    if (S == 4 && staged) { /* padded rows + block table: gathers served from LDS */ \
-      if (fixed_k == 10) FWD_FIXED(T, PT, 10); \
-      else if (fixed_k == 4) FWD_FIXED(T, PT, 4); \
-      else if (fixed_k == 8) FWD_FIXED(T, PT, 8); \
-      else if (fixed_k == 16) FWD_FIXED(T, PT, 16); \
-      else if (eigvals) DC_TIMED_LAUNCH((consistency_fwd_staged_kernel<T, PT, true>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT)); \
-      else DC_TIMED_LAUNCH((consistency_fwd_staged_kernel<T, PT, false>), grid, block, lds_bytes, stream, FWD_STAGED_ARGS(T, PT)); \
-    } else { \
-      if (eigvals) DC_TIMED_LAUNCH((consistency_fwd_kernel<T, PT, S, true>), grid, block, 0, stream, FWD_ARGS(T, PT)); \
-      else DC_TIMED_LAUNCH((consistency_fwd_kernel<T, PT, S, false>), grid, block, 0, stream, FWD_ARGS(T, PT)); \
-    } \
+    if (S == 4 && staged) DC_SWITCH_K(fixed_k, DC_SWITCH_EIG(FWD_STAGED, T, PT), FWD_FIXED_K, T, PT);   /* padded rows + block table: gathers served from LDS */ \
+    else DC_SWITCH_EIG(FWD_GATHER, T, PT, S); \
   } while (0)
   { ProfScope prof(1); DC_DISPATCH_FMT(dtype, point_fmt, stride, LAUNCH); }
 #undef LAUNCH
+#undef FWD_FIXED_K
+#undef FWD_GATHER
+#undef FWD_STAGED
 #undef FWD_FIXED
+#undef DC_SWITCH_EIG
   DC_CHECK_LAUNCH();
   if (!reduce) return DC_OK;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(2), dim3(kRedBlock), 0, stream, partials_ws, rows * kWavesPerBlock, sums_out);
@@ -1439,8 +1443,9 @@ static int consistency_bwd_impl(const void* points, int stride, int dtype, int p
   // dynamic allocation (hipFuncSetAttribute below) -- one or two blocks per CU, but gathers from LDS: un-staged, the backward of the
   // r = 0.4 m table took 535 us
   const uint32_t rec_row = point_fmt == DC_F64 ? 64u : 32u;
-  const bool by_runs = !lane_perm && use_table(table, DC_TABLE_RUNS, stride, rec_row, 1, 128 * 1024, &lds_bytes, &lds_rows);
-  const bool staged = by_runs || (!lane_perm && use_table(table, DC_TABLE_SLOTS, stride, rec_row, 1, 44 * 1024, &lds_bytes, &lds_rows));
+  const bool no_tab = g_no_tab.load();
+  const bool by_runs = !lane_perm && use_table(table, no_tab, DC_TABLE_RUNS, stride, rec_row, 1, 128 * 1024, &lds_bytes, &lds_rows);
+  const bool staged = by_runs || (!lane_perm && use_table(table, no_tab, DC_TABLE_SLOTS, stride, rec_row, 1, 44 * 1024, &lds_bytes, &lds_rows));
   if (by_runs) rtab = RunTab{table->blk_ptr, table->blk_ids, table->run_ptr, table->loc};
   else if (staged) tab = BlockTab{table->blk_ptr, table->blk_ids, table->slot_ptr, table->loc};
   if (!staged && (!csr_ptr || !csr_src)) return table ? DC_ERR_UNSUPPORTED : DC_ERR_ARG;
@@ -1483,25 +1488,19 @@ static int consistency_bwd_impl(const void* points, int stride, int dtype, int p
 #define BWD_ARGS(T, PT) (const PT*)points, (const PT*)rec, csr_ptr, csr_src, lane_perm, n, in, qp, (T*)grad_points, partials_ws, n_acc, rec_bytes
 #define BWD_STAGED_ARGS(T, PT) (const PT*)points, (const PT*)rec, tab, lds_rows, n, in, qp, (T*)grad_points, partials_ws, n_acc
 #define BWD_RUNS_ARGS(T, PT) (const PT*)points, (const PT*)rec, rtab, lds_rows, n, in, qp, (T*)grad_points, partials_ws, n_acc
+  // the four (WANT_E, WANT_POSE) instantiations of a backward kernel
+#define DC_SWITCH_EP(M, ...) \
+  do { if (want_pose_grad && want_exponent_grad) M(true, true, __VA_ARGS__); else if (want_pose_grad) M(false, true, __VA_ARGS__); \
+       else if (want_exponent_grad) M(true, false, __VA_ARGS__); else M(false, false, __VA_ARGS__); } while (0)
+#define BWD_RUNS(E, PO, T, PT) DC_TIMED_LAUNCH((consistency_bwd_runs_kernel<T, PT, E, PO>), grid, block, lds_bytes, stream, BWD_RUNS_ARGS(T, PT))
+#define BWD_STAGED(E, PO, T, PT) DC_TIMED_LAUNCH((consistency_bwd_staged_kernel<T, PT, E, PO>), grid, block, lds_bytes, stream, BWD_STAGED_ARGS(T, PT))
+#define BWD_GATHER(E, PO, T, PT, S) DC_TIMED_LAUNCH((consistency_bwd_kernel<T, PT, S, E, PO>), grid, block, 0, stream, BWD_ARGS(T, PT))
+#define BWD_RUNS_LDS(E, PO, T, PT) e_ = hipFuncSetAttribute((const void*)consistency_bwd_runs_kernel<T, PT, E, PO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
 #define LAUNCH(T, PT, S) \
   do { \
-    if (S == 4 && by_runs) { \
-      if (want_pose_grad && want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_runs_kernel<T, PT, true, true>), grid, block, lds_bytes, stream, BWD_RUNS_ARGS(T, PT)); \
-      else if (want_pose_grad) DC_TIMED_LAUNCH((consistency_bwd_runs_kernel<T, PT, false, true>), grid, block, lds_bytes, stream, BWD_RUNS_ARGS(T, PT)); \
-      else if (want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_runs_kernel<T, PT, true, false>), grid, block, lds_bytes, stream, BWD_RUNS_ARGS(T, PT)); \
-      else DC_TIMED_LAUNCH((consistency_bwd_runs_kernel<T, PT, false, false>), grid, block, lds_bytes, stream, BWD_RUNS_ARGS(T, PT)); \
-    } else if (S == 4 && staged) { \
-      if (want_pose_grad && want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_staged_kernel<T, PT, true, true>), grid, block, lds_bytes, stream, BWD_STAGED_ARGS(T, PT)); \
-      else if (want_pose_grad) DC_TIMED_LAUNCH((consistency_bwd_staged_kernel<T, PT, false, true>), grid, block, lds_bytes, stream, BWD_STAGED_ARGS(T, PT)); \
-      else if (want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_staged_kernel<T, PT, true, false>), grid, block, lds_bytes, stream, BWD_STAGED_ARGS(T, PT)); \
-      else DC_TIMED_LAUNCH((consistency_bwd_staged_kernel<T, PT, false, false>), grid, block, lds_bytes, stream, BWD_STAGED_ARGS(T, PT)); \
-    } else \
-    { \
-      if (want_pose_grad && want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_kernel<T, PT, S, true, true>), grid, block, 0, stream, BWD_ARGS(T, PT)); \
-      else if (want_pose_grad) DC_TIMED_LAUNCH((consistency_bwd_kernel<T, PT, S, false, true>), grid, block, 0, stream, BWD_ARGS(T, PT)); \
-      else if (want_exponent_grad) DC_TIMED_LAUNCH((consistency_bwd_kernel<T, PT, S, true, false>), grid, block, 0, stream, BWD_ARGS(T, PT)); \
-      else DC_TIMED_LAUNCH((consistency_bwd_kernel<T, PT, S, false, false>), grid, block, 0, stream, BWD_ARGS(T, PT)); \
-    } \
+    if (S == 4 && by_runs) DC_SWITCH_EP(BWD_RUNS, T, PT); \
+    else if (S == 4 && staged) DC_SWITCH_EP(BWD_STAGED, T, PT); \
+    else DC_SWITCH_EP(BWD_GATHER, T, PT, S); \
   } while (0)
   if (by_runs && lds_bytes > 44 * 1024) {
     int attr_rc = DC_OK;
@@ -1509,10 +1508,7 @@ static int consistency_bwd_impl(const void* points, int stride, int dtype, int p
   do { \
     if (S == 4) { \
       hipError_t e_; \
-      if (want_pose_grad && want_exponent_grad) e_ = hipFuncSetAttribute((const void*)consistency_bwd_runs_kernel<T, PT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-      else if (want_pose_grad) e_ = hipFuncSetAttribute((const void*)consistency_bwd_runs_kernel<T, PT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-      else if (want_exponent_grad) e_ = hipFuncSetAttribute((const void*)consistency_bwd_runs_kernel<T, PT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-      else e_ = hipFuncSetAttribute((const void*)consistency_bwd_runs_kernel<T, PT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
+      DC_SWITCH_EP(BWD_RUNS_LDS, T, PT); \
       if (e_ != hipSuccess) attr_rc = (int)e_; \
     } \
   } while (0)
@@ -1522,6 +1518,11 @@ static int consistency_bwd_impl(const void* points, int stride, int dtype, int p
   }
   { ProfScope prof(2); DC_DISPATCH_FMT(dtype, point_fmt, stride, LAUNCH); }
 #undef LAUNCH
+#undef BWD_RUNS_LDS
+#undef BWD_GATHER
+#undef BWD_STAGED
+#undef BWD_RUNS
+#undef DC_SWITCH_EP
   DC_CHECK_LAUNCH();
   if (params && n_red > 0 && reduce) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(n_red), dim3(kRedBlock), 0, stream, partials_ws, prows, grads_out);
@@ -1589,7 +1590,7 @@ int dc_debug_block_trace(void* buf) {        // diagnostic build only: [4 x grid
 }
 #endif
 // option 0: 1 = ignore block tables and gather from global memory (ablation / A-B measurements), 0 = default; the other options are
-// listed at the switches above use_table and in dc_hip.h.
+// listed at the switches above route_options and in dc_hip.h.
 // The switches exist for A-B measurements and for the tests that hold one path against another; a process that has not asked for them
 // (DC_ENABLE_ABLATIONS=1 in its environment when the library is first used) cannot change them: the product has no mutable
 // process-wide state.
@@ -1677,8 +1678,9 @@ int dc_adam_step_device(double* param, const double* grad, double* exp_avg, doub
   return DC_OK;
 }
 
-// One evaluation of a whole sequence (eval.py:85-112 + backward) from a caller-filled descriptor: three kernels
-// (+ two fixed-order reductions).  out fp64 [2 + 2 P + 12 S] = {sum loss over mask, mask count, grads of the sum}.
+// One evaluation of a whole sequence (eval.py:85-112 + backward) from a caller-filled descriptor: dc_choose_route (dc_cons_route.h)
+// decides which kernels run, the launch functions below run them.  out fp64 [2 + 2 P + 12 S] = {sum loss over mask, mask count, grads
+// of the sum}.
 // a chained step (dc_sequence_step_chained): this launch also finishes the previous evaluation (StepChain)
 struct ChainCall {
   int32_t* ready;
@@ -1697,266 +1699,243 @@ struct ChainCall {
 // the two partial-row buffers of a chain: behind the columns ordinary evaluations use, so that an evaluation of the same
 // sequence between two chained steps (a validation pass, a lazily produced loss cloud) cannot overwrite a pending step
 static inline double* chain_buffer(const dcSequenceDesc* d, int n_terms, int parity) {
-  const int64_t rows = xcd_grid(n_blocks(d->n)) * kWavesPerBlock;
+  const int64_t rows = route_seq_rows(d).rows;
   const int n_acc = 2 * n_terms + 12 * d->n_scans;
   return d->partials + (int64_t)(2 + n_acc) * rows + (int64_t)parity * (2 + n_terms) * rows;
 }
+// what the leading blocks of a chained launch (or of the flush of a linked chain) need; the previous launch's rows are the call's
+// own (linked chains) or `own_prev`
+static StepChain make_chain(const ChainCall& c, int n_out, const double* own_prev, int64_t own_rows, int32_t* status, int spin_limit,
+                            const double* w_now, int reverse) {
+  StepChain ch{};
+  ch.ready = c.ready; ch.stamp = c.stamp; ch.parity = c.parity; ch.has_prev = c.has_prev; ch.n_front = kChainFront; ch.n_out = n_out;
+  ch.reverse = reverse;
+  ch.prev = c.prev_rows ? c.prev_rows : own_prev; ch.prev_rows = c.prev_rows ? c.prev_count : own_rows;
+  ch.grad_sum = c.grad_sum; ch.out_prev = c.out_prev; ch.w_prev_out = c.w_prev_out; ch.status = status; ch.spin_limit = spin_limit;
+  ch.w_now = w_now; ch.prev_status = c.prev_status; ch.acc_in = c.acc_in; ch.adam = c.adam_prev;
+  return ch;
+}
 
-static int sequence_eval_impl(const dcSequenceDesc* d, const double* w, const double* e, const double* poses, int want_grad,
-                              int want_exponent_grad, int want_pose_grad, double* out, hipStream_t stream,
-                              const AdamArgs& adam, const ChainCall* chain = nullptr, bool one_pass_only = false) {
-  if (!d || !out || !poses || !d->partials) return DC_ERR_ARG;
-  // the one-pass evaluation first tries the table that lists only what the centres INSIDE the mask gather (dcSequenceDesc.fwd_table_loss)
-  if (!one_pass_only && d->fwd_table_loss && d->mask && !d->centre_idx && want_grad && !want_exponent_grad && !want_pose_grad && d->basis &&
-      d->model_kind != DC_MODEL_NONE && d->n_terms >= 1 && d->n_terms <= 3 && d->n > 0) {
-    dcSequenceDesc dd = *d;
-    dd.fwd_table = d->fwd_table_loss;
-    dd.fwd_table_loss = nullptr;
-    dd.fwd_rows_active = d->fwd_rows_active_loss;
-    const int rc = sequence_eval_impl(&dd, w, e, poses, want_grad, want_exponent_grad, want_pose_grad, out, stream, adam, chain, true);
-    if (rc != DC_ERR_UNSUPPORTED) return rc;
-  }
-  const int stride = 4;
-  const int n_terms = d->model_kind == DC_MODEL_NONE ? 0 : d->n_terms;
-  const int n_acc = 2 * n_terms + 12 * d->n_scans;
-  if (d->n == 0) return (int)hipMemsetAsync(out, 0, (size_t)(2 + n_acc) * sizeof(double), stream);
-  if (d->partials_count < dc_sequence_partials_count(d->n, n_terms, d->n_scans)) return DC_ERR_WORKSPACE;
-  const int64_t n_rows = d->centre_idx ? d->n_centres : d->n;      // forward rows (centres); the backward runs over all points
-  if (d->centre_idx && (d->n_centres < 0 || d->n_centres > d->n)) return DC_ERR_ARG;
-  const int64_t rows = xcd_grid(n_blocks(d->n)) * kWavesPerBlock;      // partial rows: one per wavefront
-  double* p_fwd = d->partials;
-  double* p_bwd = d->partials + 2 * rows;
-  const int n_red = !want_grad ? 0 : (want_pose_grad ? n_acc : 2 * n_terms);
+// ---- the one-pass step kernels: what every launch takes, and one launch function per route kind ----------------------------------
+struct StepLaunch {
+  const dcSequenceDesc* d; hipStream_t stream; dim3 grid; PointBasis pb; BlockTab tab; LossParams lp; QParams qp; double *p_fwd, *p_bwd; StepChain ch;
+};
 
-  // ---- basis form: the basis rows of the current poses and exponents are valid (the caller says so by passing them), only the
-  // weights change between evaluations -> no pass over the points, no model / pose arithmetic in the loop
-  size_t lds_f = 0, lds_b = 0;
-  int rows_f = 0, rows_b = 0;
-  const bool q32_pts = d->point_fmt == DC_Q32 && d->dtype == DC_F32, f64_pts = d->point_fmt == DC_F64 && d->dtype == DC_F64;
-  // ball neighbourhoods on float32 clouds (a packed table from CSR lists that knows its rows' lengths): the ragged one-pass
-  // kernel, whose tile may take up to 128 KB of LDS
-  const int rag_pieces = n_terms <= 2 ? 2 : 3;
-  const int rag_rows = !d->fwd_table ? 0 : ((d->blk_skip && d->mask && !d->centre_idx && d->fwd_rows_active > 0 && d->fwd_rows_active < d->fwd_table->max_rows)
-                                              ? d->fwd_rows_active : d->fwd_table->max_rows);
-  const bool ragged_ok = q32_pts && d->fwd_table && d->fwd_table->layout == DC_TABLE_SLOTS && d->fwd_table->packed == 1 && d->fwd_table->row_ptr &&
-                         d->fwd_table->own_base && !d->centre_idx && d->fwd_table->max_rows > 0 && !g_no_tab.load() && g_step_var.load() != 8 &&
-                         (size_t)rag_rows * rag_pieces * 16 <= 128 * 1024 && rag_rows <= (n_terms <= 2 ? 4096 : 2560);
-  const bool basis_fwd = d->basis && (q32_pts || f64_pts) && n_terms > 0 && w &&
-                         !want_exponent_grad && !want_pose_grad && !g_no_basis.load() &&
-                         (use_table(d->fwd_table, DC_TABLE_SLOTS, stride, q32_pts ? 16u : 32u, 0, 60 * 1024, &lds_f, &rows_f) || (ragged_ok && want_grad && n_terms <= 3 && !g_two_pass.load()));
-  // loss and dL/dw in ONE pass (forward-mode) for up to three weights: no record, no backward launch, no transposed table
-  size_t lds_s = 0;
-  int rows_s = 0;
-  const unsigned step_row_bytes = 16u * (unsigned)(q32_pts ? (6 + n_terms + 3) / 4 : 3);        // StepRow<PT, P>::kPieces
-  // (the one-pass kernels never stage the blocks they skip: their tile is sized by the longest list among the others)
-  dcBlockTable ft_active{};
-  if (d->fwd_table) {
-    ft_active = *d->fwd_table;
-    if (d->blk_skip && d->mask && !d->centre_idx && d->fwd_rows_active > 0 && d->fwd_rows_active < ft_active.max_rows) ft_active.max_rows = d->fwd_rows_active;
-  }
-  const bool one_pass = basis_fwd && want_grad && n_terms <= 3 && !g_two_pass.load() &&
-                        (use_table(d->fwd_table ? &ft_active : nullptr, DC_TABLE_SLOTS, stride, step_row_bytes, 0, 60 * 1024, &lds_s, &rows_s) || ragged_ok);
-  // pose gradients (no exponent gradients) of a float32 sequence with a [rows, K] table whose pose tables and local basis rows the
-  // plan has built: one launch, no transposed lists (consistency_step_pose_kernel)
-  const bool pose_one_pass = want_grad && want_pose_grad && !want_exponent_grad && d->pose_table && d->local_basis && !d->vps && !d->centre_idx &&
-                             d->point_fmt == DC_Q32 && d->dtype == DC_F32 && (n_terms == 1 || n_terms == 2) && d->n_scans <= kLdsScans && w &&
-                             (d->k == 4 || d->k == 8 || d->k == 10 || d->k == 16) && !g_pose_three_pass.load();
-  // every other way to a gradient walks the transposed neighbour lists: the caller provides them on demand
-  if (want_grad && !one_pass && !pose_one_pass && (!d->csr_ptr || !d->csr_src)) return DC_ERR_BACKWARD_TABLES;
-  const bool basis = basis_fwd &&
-                     (!want_grad || one_pass || use_table(d->bwd_table, DC_TABLE_RUNS, stride, q32_pts ? 32u : 64u, 1, 44 * 1024, &lds_b, &rows_b));
-  const int fixed_k = g_fwd_generic.load() ? 0 : d->k;
-  // a chained step exists for the one-pass kernels only: the caller steps without a chain otherwise
-  if ((chain || one_pass_only) && !(basis && one_pass)) return DC_ERR_UNSUPPORTED;
-  if (basis) {
-    QParams qp;
-    int rc = make_qparams(d->point_fmt, d->dtype, stride, d->qparams, &qp);
-    if (rc) return rc;
-    PointBasis pb{d->basis, w, n_terms, q32_pts ? qp.inv_scale : 1.0};
-    const LossParams lp = make_loss_params(d->loss_kind & ~DC_LOSS_RAW_POINTWISE, d->normalization, d->sqrt_);
-    BlockTab tab{d->fwd_table->blk_ptr, d->fwd_table->blk_ids, d->fwd_table->slot_ptr, d->fwd_table->loc};
-    const dim3 block(kBlock);
-    if (one_pass) {
-      const int64_t g_blocks = xcd_grid(n_blocks(n_rows));
-      StepChain ch{};
-      ch.blk_skip = (d->mask && !d->centre_idx) ? d->blk_skip : nullptr;
-      if (chain) {
-        p_fwd = chain_buffer(d, n_terms, chain->parity);
-        p_bwd = p_fwd + 2 * g_blocks;
-        ch.ready = chain->ready; ch.parity = chain->parity; ch.has_prev = chain->has_prev; ch.n_front = kChainFront;
-        ch.n_out = 2 + n_acc; ch.prev = chain_buffer(d, n_terms, chain->parity ^ 1); ch.prev_rows = g_blocks;
-        if (chain->prev_rows) { ch.prev = chain->prev_rows; ch.prev_rows = chain->prev_count; }
-        ch.acc_in = chain->acc_in; ch.prev_status = chain->prev_status;
-        ch.out_prev = chain->out_prev; ch.w_prev_out = chain->w_prev_out; ch.status = d->status; ch.spin_limit = g_chain_spin.load(); ch.adam = chain->adam_prev;
-        ch.grad_sum = chain->grad_sum;
-        ch.stamp = chain->stamp; ch.w_now = w;
-        ch.reverse = (chain->parity && !g_no_reverse.load()) ? 1 : 0;
-      }
-      const dim3 grid((unsigned)(g_blocks + (chain ? kChainFront : 0)));
-      const int var = g_step_var.load();
-      // float32 clouds with a [rows, K] table: the kernel with fp64 row differences in LDS (48-B rows + its scratch, all dynamic)
-      // the block headers of the table this pass stages from (dcSequenceDesc.step_hdr: fwd_table_loss's where the descriptor has one);
-      // a caller without them takes consistency_step_basis_kernel, which reads the tables themselves and returns the same sums
-      // (the pass over fwd_table_loss arrives here with that table as fwd_table and no fwd_table_loss; with a compact centre list the
-      // kernel takes the centres by index: a header that names own rows does not describe that)
-      const bool hdr_ok = !d->fwd_table_loss && !(d->centre_idx && d->fwd_table->own_base);
-      const StepHdr* step_hdr = hdr_ok ? static_cast<const StepHdr*>(d->step_hdr) : nullptr;
-      const bool q32_step = q32_pts && var == 1 && (fixed_k == 10 || fixed_k == 4 || fixed_k == 8 || fixed_k == 16) && rows_s <= 768 && step_hdr;
-      const bool ragged_step = ragged_ok;
-      if (ragged_step) {
-        ProfScope prof(1);
-        const int mr = rag_rows;
-        int rc = DC_OK;
+// ball neighbourhoods on float32 clouds: the tile may take up to 128 KB of LDS (ragged_launch)
+static int launch_step_ragged(const SeqRoute& r, const StepLaunch& a) {
+  ProfScope prof(1);
 #define RAGGED(P, CAP) (prof.name("(consistency_step_ragged_q32_kernel<" #P ", " #CAP ">)"), \
-                        ragged_launch<P, CAP>(grid, stream, prof.start(), prof.stop(), pb, tab, d->fwd_table, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch))
-#define RAGGED_CAPS(P) (mr <= 1024 ? RAGGED(P, 1024) : mr <= 1280 ? RAGGED(P, 1280) : mr <= 1600 ? RAGGED(P, 1600) : mr <= 2048 ? RAGGED(P, 2048) : \
-                        mr <= 2560 ? RAGGED(P, 2560) : RAGGED(P, 4096))
-        if (n_terms == 2) rc = RAGGED_CAPS(2);
-        else if (n_terms == 1) rc = RAGGED_CAPS(1);
-        else rc = mr <= 1024 ? RAGGED(3, 1024) : mr <= 1600 ? RAGGED(3, 1600) : RAGGED(3, 2560);
+                        ragged_launch<P, CAP>(a.grid, a.stream, prof.start(), prof.stop(), a.pb, a.tab, r.table, r.n_rows, a.d->mask, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch))
+#define RAGGED_CAPS(P, X) do { switch (r.cap) { case 1024: return RAGGED(P, 1024); case 1280: return RAGGED(P, 1280); case 1600: return RAGGED(P, 1600); \
+                                                case 2048: return RAGGED(P, 2048); case 2560: return RAGGED(P, 2560); default: return RAGGED(P, 4096); } } while (0)
+  DC_SWITCH_P(r.P, switch (r.cap) { case 1024: return RAGGED(3, 1024); case 1600: return RAGGED(3, 1600); default: return RAGGED(3, 2560); }, RAGGED_CAPS, 0);
 #undef RAGGED_CAPS
 #undef RAGGED
-        if (rc) return rc;
-      } else if (q32_step) {
-        ProfScope prof(1);
-        static_assert(kStepQ32Cap == 512, "the profiler names the instantiation by its literal arguments");
-#define STEPQ_LAUNCH(NS, P, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), grid, block, 0, stream, pb, tab, step_hdr, \
-                                                 d->centre_idx, n_rows, lp, qp, p_fwd, p_bwd, ch)
-#define STEPQ_P(NS, CAP) do { if (n_terms == 2) STEPQ_LAUNCH(NS, 2, CAP); else if (n_terms == 1) STEPQ_LAUNCH(NS, 1, CAP); else STEPQ_LAUNCH(NS, 3, CAP); } while (0)
-#define STEPQ_K(CAP) do { if (fixed_k == 10) STEPQ_P(10, CAP); else if (fixed_k == 4) STEPQ_P(4, CAP); else if (fixed_k == 8) STEPQ_P(8, CAP); else STEPQ_P(16, CAP); } while (0)
-        // (dc_set_option(9, 1): the six-blocks-per-CU build of the instantiations whose default is seven)
-#define STEPQ_SIX(NS, P) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), grid, block, 0, stream, pb, tab, step_hdr, \
-                                         d->centre_idx, n_rows, lp, qp, p_fwd, p_bwd, ch)
-#define STEPQ_SIX_P(NS) do { if (n_terms == 2) STEPQ_SIX(NS, 2); else STEPQ_SIX(NS, 1); } while (0)
-        static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
-                      "which instantiations dc_set_option(9, 1) has a six-block build of");
-        if (rows_s <= 512 && n_terms <= 2 && g_step_six.load()) {
-          if (fixed_k == 10) STEPQ_SIX_P(10); else if (fixed_k == 4) STEPQ_SIX_P(4); else if (fixed_k == 8) STEPQ_SIX_P(8); else STEPQ_SIX_P(16);
-        } else if (rows_s <= 512) STEPQ_K(512); else STEPQ_K(768);
-#undef STEPQ_SIX_P
-#undef STEPQ_SIX
-#undef STEPQ_K
-#undef STEPQ_P
-#undef STEPQ_LAUNCH
-      } else {
-        ProfScope prof(1);
-#define STEP_LAUNCH(K) DC_TIMED_LAUNCH(K, grid, block, lds_s, stream, pb, tab, d->fwd_table->own_base, rows_s, d->centre_idx, n_rows, \
-                                       d->mask, lp, qp, p_fwd, p_bwd, ch)
-#define STEP_NS(PT, P) do { if (fixed_k == 10 && P == 2 && var == 0) STEP_LAUNCH((consistency_step_basis_kernel<PT, 10, 2, 0>)); \
-                            else if (fixed_k == 10) STEP_LAUNCH((consistency_step_basis_kernel<PT, 10, P, kStepVar>)); \
-                            else if (fixed_k == 4) STEP_LAUNCH((consistency_step_basis_kernel<PT, 4, P, kStepVar>)); \
-                            else if (fixed_k == 8) STEP_LAUNCH((consistency_step_basis_kernel<PT, 8, P, kStepVar>)); \
-                            else if (fixed_k == 16) STEP_LAUNCH((consistency_step_basis_kernel<PT, 16, P, kStepVar>)); \
-                            else DC_TIMED_LAUNCH((consistency_step_basis_slots_kernel<PT, P>), grid, block, lds_s, stream, pb, tab, d->fwd_table->own_base, rows_s, \
-                                                 d->centre_idx, n_rows, d->mask, lp, qp, p_fwd, p_bwd, ch, d->fwd_table->packed); } while (0)
-#define STEP(PT) do { if (n_terms == 2) STEP_NS(PT, 2); else if (n_terms == 1) STEP_NS(PT, 1); else STEP_NS(PT, 3); } while (0)
-        if (q32_pts) STEP(q32); else STEP(double);
-#undef STEP
-#undef STEP_NS
-#undef STEP_LAUNCH
-      }
-      DC_CHECK_LAUNCH();
-      if (chain && chain->reduce_now) {        // several ranks: this evaluation's sums now (they go through an all-reduce next)
-        hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + n_terms), dim3(kRedBlock), 0, stream, p_fwd, p_bwd, g_blocks, g_blocks, n_terms,
-                           2 + n_acc, out, AdamArgs{}, (const int32_t*)d->status);
-        DC_CHECK_LAUNCH();
-      }
-      if (chain) return DC_OK;                 // its sums are taken by the next launch of the chain, or by the flush
-      const int64_t rows_g = (int64_t)grid.x * kWavesPerBlock;
-      hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + n_terms), dim3(kRedBlock), 0, stream, p_fwd, p_bwd, rows_g, rows_g, n_terms, 2 + n_acc, out,
-                         adam, (const int32_t*)d->status);
-      DC_CHECK_LAUNCH();
-      return DC_OK;
-    }
-    {
-      ProfScope prof(1);
-      const dim3 grid((unsigned)xcd_grid(n_blocks(n_rows)));
-#define FWD_BASIS_P(PT, T, NS, P) DC_TIMED_LAUNCH((consistency_fwd_basis_kernel<PT, false, NS, P>), grid, block, lds_f, stream, pb, tab, \
-                                                 d->fwd_table->own_base, rows_f, d->centre_idx, n_rows, d->mask, (const T*)nullptr, lp, qp, \
-                                                 (PT*)(want_grad ? d->rec : nullptr), (T*)nullptr, (T*)nullptr, p_fwd)
-#define FWD_BASIS_SLOTS(PT, T, P) DC_TIMED_LAUNCH((consistency_fwd_basis_slots_kernel<PT, false, P>), grid, block, lds_f, stream, pb, tab, \
-                                                 d->fwd_table->own_base, rows_f, d->centre_idx, n_rows, d->mask, (const T*)nullptr, lp, qp, \
-                                                 (PT*)(want_grad ? d->rec : nullptr), (T*)nullptr, (T*)nullptr, p_fwd)
-#define FWD_BASIS_NS(PT, T, P) do { if (fixed_k == 10) FWD_BASIS_P(PT, T, 10, P); else if (fixed_k == 4) FWD_BASIS_P(PT, T, 4, P); \
-                                    else if (fixed_k == 8) FWD_BASIS_P(PT, T, 8, P); else if (fixed_k == 16) FWD_BASIS_P(PT, T, 16, P); \
-                                    else FWD_BASIS_SLOTS(PT, T, P); } while (0)
-#define FWD_BASIS(PT, T) do { if (n_terms == 2) FWD_BASIS_NS(PT, T, 2); else if (n_terms == 1) FWD_BASIS_NS(PT, T, 1); \
-                              else if (n_terms == 3) FWD_BASIS_NS(PT, T, 3); else FWD_BASIS_NS(PT, T, 0); } while (0)
-      if (q32_pts) FWD_BASIS(q32, float); else FWD_BASIS(double, double);
-#undef FWD_BASIS
-#undef FWD_BASIS_NS
-#undef FWD_BASIS_SLOTS
-#undef FWD_BASIS_P
-    }
-    DC_CHECK_LAUNCH();
-    if (want_grad) {
-      RunTab rtab{d->bwd_table->blk_ptr, d->bwd_table->blk_ids, d->bwd_table->run_ptr, d->bwd_table->loc};
-      ProfScope prof(2);
-#define BWD_BASIS_P(PT, P) DC_TIMED_LAUNCH((consistency_bwd_basis_kernel<PT, P>), dim3((unsigned)xcd_grid(n_blocks(d->n))), block, lds_b, stream, pb, \
-                                          (const PT*)d->rec, rtab, rows_b, d->n, qp, p_bwd)
-#define BWD_BASIS(PT) do { if (n_terms == 2) BWD_BASIS_P(PT, 2); else if (n_terms == 1) BWD_BASIS_P(PT, 1); \
-                           else if (n_terms == 3) BWD_BASIS_P(PT, 3); else BWD_BASIS_P(PT, 0); } while (0)
-      if (q32_pts) BWD_BASIS(q32); else BWD_BASIS(double);
-#undef BWD_BASIS
-#undef BWD_BASIS_P
-      DC_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + n_red), dim3(kRedBlock), 0, stream, p_fwd, p_bwd,
-                       xcd_grid(n_blocks(n_rows)) * kWavesPerBlock, rows, n_red, 2 + n_acc, out, adam, (const int32_t*)d->status);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
-  }
+  return DC_OK;
+}
 
-  // pose gradients (no exponent gradients) of a float32 sequence with a [rows, K] table: everything in ONE launch
-  // (consistency_step_pose_kernel) when the plan has built the pose tables and the local basis rows for these exponents
-  if (pose_one_pass) {
-    QParams qp;
-    int rc = make_qparams(d->point_fmt, d->dtype, stride, d->qparams, &qp, d->status);
-    if (rc) return rc;
-    const dcPoseTable* pt = d->pose_table;
-    PoseTab tab{pt->blk_ptr, pt->ids, pt->loc, pt->own_pos, pt->row_seg, pt->row_scan};
-    const LossParams lp = make_loss_params(d->loss_kind & ~DC_LOSS_RAW_POINTWISE, d->normalization, d->sqrt_);
-    const dim3 grid((unsigned)xcd_grid(n_blocks(d->n))), block(kBlock);
-    {
-      ProfScope prof(1);
-#define POSE_NS(NS, P) DC_TIMED_LAUNCH((consistency_step_pose_kernel<NS, P>), grid, block, 0, stream, (const int32_t*)d->local_basis, tab, poses, d->n_scans, \
-                                       w, d->n, d->mask, lp, qp, p_fwd, p_bwd)
-#define POSE_P(NS) do { if (n_terms == 2) POSE_NS(NS, 2); else POSE_NS(NS, 1); } while (0)
-      if (d->k == 10) POSE_P(10); else if (d->k == 4) POSE_P(4); else if (d->k == 8) POSE_P(8); else POSE_P(16);
-#undef POSE_P
-#undef POSE_NS
-    }
-    DC_CHECK_LAUNCH();
-    const int64_t rows_b = xcd_grid(n_blocks(d->n));         // one row per block, every column contiguous
-    hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + n_acc), dim3(kRedBlock), 0, stream, p_fwd, p_bwd, rows_b, rows_b, n_acc, 2 + n_acc, out, adam,
-                       (const int32_t*)d->status, -1, 0);
-    DC_CHECK_LAUNCH();
-    return DC_OK;
+// float32 clouds with a [rows, K] table and block headers: fp64 row differences in a static LDS tile
+static int launch_step_q32(const SeqRoute& r, const StepLaunch& a) {
+  ProfScope prof(1);
+  const StepHdr* hdr = static_cast<const StepHdr*>(a.d->step_hdr);
+  const dim3 block(kBlock);
+  static_assert(kStepQ32Cap == 512, "the profiler names the instantiation by its literal arguments");
+  static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
+                "which instantiations dc_set_option(9, 1) has a six-block build of");
+#define STEPQ_TAIL a.pb, a.tab, hdr, a.d->centre_idx, r.n_rows, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
+#define STEPQ(P, NS, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), a.grid, block, 0, a.stream, STEPQ_TAIL)
+#define STEPQ_SIX(P, NS, X) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), a.grid, block, 0, a.stream, STEPQ_TAIL)
+#define STEPQ_P(NS, CAP) DC_SWITCH_P(r.P, STEPQ(3, NS, CAP), STEPQ, NS, CAP)
+#define STEPQ_SIX_P(NS, X) DC_SWITCH_P(r.P, , STEPQ_SIX, NS, X)
+  if (r.six) DC_SWITCH_K(r.k, , STEPQ_SIX_P, 0);             // (dc_set_option(9, 1): the six-blocks-per-CU build of the instantiations whose default is seven)
+  else if (r.cap == 512) DC_SWITCH_K(r.k, , STEPQ_P, 512);
+  else DC_SWITCH_K(r.k, , STEPQ_P, 768);
+#undef STEPQ_SIX_P
+#undef STEPQ_P
+#undef STEPQ_SIX
+#undef STEPQ
+#undef STEPQ_TAIL
+  return DC_OK;
+}
+
+// any [rows, K] table (float64 clouds; float32 ones without headers, with longer lists or under dc_set_option(6, ..)): the tables themselves
+#define STEP_TAIL a.pb, a.tab, r.table->own_base, r.rows_fwd, a.d->centre_idx, r.n_rows, a.d->mask, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
+static int launch_step_basis(const SeqRoute& r, const StepLaunch& a) {
+  ProfScope prof(1);
+  const dim3 block(kBlock);
+#define STEPB(P, NS, PT) DC_TIMED_LAUNCH((consistency_step_basis_kernel<PT, NS, P, kStepVar>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL)
+#define STEPB_P(NS, PT) DC_SWITCH_P(r.P, STEPB(3, NS, PT), STEPB, NS, PT)
+  if (r.round2 && r.f64) DC_TIMED_LAUNCH((consistency_step_basis_kernel<double, 10, 2, 0>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL);
+  else if (r.round2) DC_TIMED_LAUNCH((consistency_step_basis_kernel<q32, 10, 2, 0>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL);
+  else if (r.f64) DC_SWITCH_K(r.k, , STEPB_P, double);
+  else DC_SWITCH_K(r.k, , STEPB_P, q32);
+#undef STEPB_P
+#undef STEPB
+  return DC_OK;
+}
+
+// any other slot count: the run-time slot loop
+static int launch_step_slots(const SeqRoute& r, const StepLaunch& a) {
+  ProfScope prof(1);
+  const dim3 block(kBlock);
+#define STEPS(P, PT, X) DC_TIMED_LAUNCH((consistency_step_basis_slots_kernel<PT, P>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL, r.table->packed)
+  if (r.f64) DC_SWITCH_P(r.P, STEPS(3, double, 0), STEPS, double, 0);
+  else DC_SWITCH_P(r.P, STEPS(3, q32, 0), STEPS, q32, 0);
+#undef STEPS
+  return DC_OK;
+}
+#undef STEP_TAIL
+
+// loss and dL/dw in ONE pass (forward-mode) for up to three weights: no record, no backward launch, no transposed table; a chained
+// launch first finishes the evaluation before it
+static int run_one_pass(const SeqRoute& r, const dcSequenceDesc* d, const double* w, double* out, hipStream_t stream, const AdamArgs& adam,
+                        const ChainCall* chain) {
+  StepLaunch a{};
+  int rc = make_qparams(d->point_fmt, d->dtype, 4, d->qparams, &a.qp);
+  if (rc) return rc;
+  a.d = d; a.stream = stream; a.grid = dim3((unsigned)r.grid);
+  a.pb = PointBasis{d->basis, w, r.n_terms, r.f64 ? 1.0 : a.qp.inv_scale};
+  a.lp = make_loss_params(d->loss_kind & ~DC_LOSS_RAW_POINTWISE, d->normalization, d->sqrt_);
+  a.tab = BlockTab{r.table->blk_ptr, r.table->blk_ids, r.table->slot_ptr, r.table->loc};
+  a.p_fwd = chain ? chain_buffer(d, r.n_terms, chain->parity) : d->partials;
+  a.p_bwd = chain ? a.p_fwd + 2 * r.g_blocks : d->partials + 2 * r.rows;
+  if (chain) a.ch = make_chain(*chain, 2 + r.n_acc, chain_buffer(d, r.n_terms, chain->parity ^ 1), r.g_blocks, d->status, g_chain_spin.load(), w,
+                               (chain->parity && !g_no_reverse.load()) ? 1 : 0);
+  a.ch.blk_skip = (d->mask && !d->centre_idx) ? d->blk_skip : nullptr;
+  switch (r.kind) {
+    case ROUTE_STEP_RAGGED: rc = launch_step_ragged(r, a); break;
+    case ROUTE_STEP_Q32: rc = launch_step_q32(r, a); break;
+    case ROUTE_STEP_BASIS: rc = launch_step_basis(r, a); break;
+    default: rc = launch_step_slots(r, a); break;
   }
-  // (measured in round 4 and dropped: a forward that FORMS the rows it stages from the raw inputs -- model, pose, ray end point per
-  // staged row, the owning block writing x for the backward -- instead of dc_points_fwd + a forward over x.  It removes a 22 us launch
-  // and 48 B per point of traffic, but a block stages 1.47 rows per point and each costs five scattered loads and ~80 fp64
-  // instructions in front of the staging barrier: 106 us against 22 + 46.)
+  if (rc) return rc;
+  DC_CHECK_LAUNCH();
+  // a chain's sums are taken by its next launch, or by the flush; with several ranks this evaluation's sums are wanted now as well
+  // (they go through an all-reduce next)
+  if (chain && !chain->reduce_now) return DC_OK;
+  const int64_t rows_g = chain ? r.g_blocks : r.grid * kWavesPerBlock;
+  hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + r.n_terms), dim3(kRedBlock), 0, stream, a.p_fwd, a.p_bwd, rows_g, rows_g, r.n_terms, 2 + r.n_acc, out,
+                     chain ? AdamArgs{} : adam, (const int32_t*)d->status);
+  DC_CHECK_LAUNCH();
+  return DC_OK;
+}
+
+// the basis form with separate forward and backward kernels (forward only: a loss without gradients)
+static int run_two_pass(const SeqRoute& r, const dcSequenceDesc* d, const double* w, int want_grad, double* out, hipStream_t stream,
+                        const AdamArgs& adam) {
+  QParams qp;
+  int rc = make_qparams(d->point_fmt, d->dtype, 4, d->qparams, &qp);
+  if (rc) return rc;
+  const PointBasis pb{d->basis, w, r.n_terms, r.f64 ? 1.0 : qp.inv_scale};
+  const LossParams lp = make_loss_params(d->loss_kind & ~DC_LOSS_RAW_POINTWISE, d->normalization, d->sqrt_);
+  const BlockTab tab{r.table->blk_ptr, r.table->blk_ids, r.table->slot_ptr, r.table->loc};
+  const dim3 block(kBlock);
+  double *p_fwd = d->partials, *p_bwd = d->partials + 2 * r.rows;
+  {
+    ProfScope prof(1);
+    const dim3 grid((unsigned)r.g_blocks);
+#define FWDB_TAIL(PT, T) pb, tab, r.table->own_base, r.rows_fwd, d->centre_idx, r.n_rows, d->mask, (const T*)nullptr, lp, qp, \
+                         (PT*)(want_grad ? d->rec : nullptr), (T*)nullptr, (T*)nullptr, p_fwd
+#define FWDB(P, NS, PT, T) DC_TIMED_LAUNCH((consistency_fwd_basis_kernel<PT, false, NS, P>), grid, block, r.lds_fwd, stream, FWDB_TAIL(PT, T))
+#define FWDB_SLOTS(P, PT, T) DC_TIMED_LAUNCH((consistency_fwd_basis_slots_kernel<PT, false, P>), grid, block, r.lds_fwd, stream, FWDB_TAIL(PT, T))
+#define FWDB_P(NS, PT, T) DC_SWITCH_P(r.P, if (r.P == 3) FWDB(3, NS, PT, T); else FWDB(0, NS, PT, T), FWDB, NS, PT, T)
+#define FWDB_SLOTS_P(PT, T) DC_SWITCH_P(r.P, if (r.P == 3) FWDB_SLOTS(3, PT, T); else FWDB_SLOTS(0, PT, T), FWDB_SLOTS, PT, T)
+    if (r.f64) DC_SWITCH_K(r.k, FWDB_SLOTS_P(double, double), FWDB_P, double, double);
+    else DC_SWITCH_K(r.k, FWDB_SLOTS_P(q32, float), FWDB_P, q32, float);
+#undef FWDB_SLOTS_P
+#undef FWDB_P
+#undef FWDB_SLOTS
+#undef FWDB
+#undef FWDB_TAIL
+  }
+  DC_CHECK_LAUNCH();
+  if (want_grad) {
+    const RunTab rtab{d->bwd_table->blk_ptr, d->bwd_table->blk_ids, d->bwd_table->run_ptr, d->bwd_table->loc};
+    const dim3 grid((unsigned)(r.rows / kWavesPerBlock));
+    ProfScope prof(2);
+#define BWDB(P, PT, X) DC_TIMED_LAUNCH((consistency_bwd_basis_kernel<PT, P>), grid, block, r.lds_bwd, stream, pb, (const PT*)d->rec, rtab, r.rows_bwd, d->n, qp, p_bwd)
+    if (r.f64) DC_SWITCH_P(r.P, if (r.P == 3) BWDB(3, double, 0); else BWDB(0, double, 0), BWDB, double, 0);
+    else DC_SWITCH_P(r.P, if (r.P == 3) BWDB(3, q32, 0); else BWDB(0, q32, 0), BWDB, q32, 0);
+#undef BWDB
+    DC_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + r.n_red), dim3(kRedBlock), 0, stream, p_fwd, p_bwd, r.g_blocks * kWavesPerBlock, r.rows, r.n_red,
+                     2 + r.n_acc, out, adam, (const int32_t*)d->status);
+  DC_CHECK_LAUNCH();
+  return DC_OK;
+}
+
+// pose gradients (no exponent gradients) of a float32 sequence with a [rows, K] table: everything in ONE launch
+// (consistency_step_pose_kernel) when the plan has built the pose tables and the local basis rows for these exponents
+static int run_pose(const SeqRoute& r, const dcSequenceDesc* d, const double* w, const double* poses, double* out, hipStream_t stream,
+                    const AdamArgs& adam) {
+  QParams qp;
+  int rc = make_qparams(d->point_fmt, d->dtype, 4, d->qparams, &qp, d->status);
+  if (rc) return rc;
+  const dcPoseTable* pt = d->pose_table;
+  const PoseTab tab{pt->blk_ptr, pt->ids, pt->loc, pt->own_pos, pt->row_seg, pt->row_scan};
+  const LossParams lp = make_loss_params(d->loss_kind & ~DC_LOSS_RAW_POINTWISE, d->normalization, d->sqrt_);
+  const int64_t rows_b = r.rows / kWavesPerBlock;            // one row per block, every column contiguous
+  const dim3 grid((unsigned)rows_b), block(kBlock);
+  double *p_fwd = d->partials, *p_bwd = d->partials + 2 * r.rows;
+  {
+    ProfScope prof(1);
+#define POSE(P, NS, X) DC_TIMED_LAUNCH((consistency_step_pose_kernel<NS, P>), grid, block, 0, stream, (const int32_t*)d->local_basis, tab, poses, d->n_scans, \
+                                       w, d->n, d->mask, lp, qp, p_fwd, p_bwd)
+#define POSE_P(NS, X) DC_SWITCH_P(r.P, , POSE, NS, X)
+    DC_SWITCH_K(r.k, , POSE_P, 0);
+#undef POSE_P
+#undef POSE
+  }
+  DC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + r.n_acc), dim3(kRedBlock), 0, stream, p_fwd, p_bwd, rows_b, rows_b, r.n_acc, 2 + r.n_acc, out, adam,
+                     (const int32_t*)d->status, -1, 0);
+  DC_CHECK_LAUNCH();
+  return DC_OK;
+}
+
+// points, forward, backward: three kernels (+ the fixed-order reduction)
+// (measured in round 4 and dropped: a forward that FORMS the rows it stages from the raw inputs -- model, pose, ray end point per
+// staged row, the owning block writing x for the backward -- instead of dc_points_fwd + a forward over x.  It removes a 22 us launch
+// and 48 B per point of traffic, but a block stages 1.47 rows per point and each costs five scattered loads and ~80 fp64
+// instructions in front of the staging barrier: 106 us against 22 + 46.)
+static int run_general(const SeqRoute& r, const dcSequenceDesc* d, const double* w, const double* e, const double* poses, int want_grad,
+                       int want_exponent_grad, int want_pose_grad, double* out, hipStream_t stream, const AdamArgs& adam) {
+  const int stride = 4;
+  double *p_fwd = d->partials, *p_bwd = d->partials + 2 * r.rows;
   int rc = dc_points_fwd(d->vps, d->dirs, d->depth, d->inc, d->lmask, d->scan_id, poses, d->n_scans, d->model_kind,
                          d->n_terms, w, e, d->n, d->dtype, d->point_fmt, d->qparams, stride, d->x, nullptr, nullptr,
                          nullptr, d->status, stream);
   if (rc) return rc;
-  rc = consistency_fwd_impl(d->x, stride, d->dtype, d->point_fmt, d->qparams, d->nbr, d->centre_idx, d->fwd_table, n_rows, d->k, d->mask,
+  rc = consistency_fwd_impl(d->x, stride, d->dtype, d->point_fmt, d->qparams, d->nbr, d->centre_idx, d->fwd_table, r.n_rows, d->k, d->mask,
                             nullptr, d->loss_kind, d->normalization, d->sqrt_, want_grad ? d->rec : nullptr, nullptr, nullptr, p_fwd, out, stream,
                             false);
   if (!rc && want_grad)
     rc = consistency_bwd_impl(d->x, stride, d->dtype, d->point_fmt, d->qparams, d->rec, d->csr_ptr, d->csr_src, d->lane_perm,
                               d->bwd_table, d->n, d->vps, d->dirs, d->depth, d->inc, d->lmask, d->scan_id, poses, d->n_scans, d->model_kind,
                               d->n_terms, w, e, want_exponent_grad, want_pose_grad, nullptr, p_bwd, out + 2, stream, false,
-                              n_rows, d->scan_seg);
+                              r.n_rows, d->scan_seg);
   if (rc) return rc;
-  // (as consistency_bwd_impl decides: the grouped backward leaves the pose slots row-major, one row per block)
-  const bool grouped = want_grad && want_pose_grad && d->scan_seg && !d->lane_perm && d->n_scans <= kMaxBlockScans;
-  hipLaunchKernelGGL(reduce_eval_kernel, dim3(red_grid(n_red, grouped ? 2 * n_terms : -1, 12 * d->n_scans)), dim3(kRedBlock), 0, stream, p_fwd, p_bwd,
-                     xcd_grid(n_blocks(n_rows)) * kWavesPerBlock, rows, n_red, 2 + n_acc, out, adam, (const int32_t*)d->status,
-                     grouped ? 2 * n_terms : -1, 12 * d->n_scans);
+  const int pose_first = r.grouped ? 2 * r.n_terms : -1;     // the grouped backward leaves the pose slots row-major, one row per block
+  hipLaunchKernelGGL(reduce_eval_kernel, dim3(red_grid(r.n_red, pose_first, 12 * d->n_scans)), dim3(kRedBlock), 0, stream, p_fwd, p_bwd,
+                     r.g_blocks * kWavesPerBlock, r.rows, r.n_red, 2 + r.n_acc, out, adam, (const int32_t*)d->status, pose_first, 12 * d->n_scans);
   DC_CHECK_LAUNCH();
   return DC_OK;
+}
+
+static int sequence_eval_impl(const dcSequenceDesc* d, const double* w, const double* e, const double* poses, int want_grad,
+                              int want_exponent_grad, int want_pose_grad, double* out, hipStream_t stream,
+                              const AdamArgs& adam, const ChainCall* chain = nullptr) {
+  SeqRoute r;
+  const int rc = dc_choose_route_call(d, w, poses, out, want_grad, want_exponent_grad, want_pose_grad, chain != nullptr, route_options(), &r);
+  if (rc) return rc;
+  switch (r.kind) {
+    case ROUTE_EMPTY: return (int)hipMemsetAsync(out, 0, (size_t)(2 + r.n_acc) * sizeof(double), stream);
+    case ROUTE_STEP_RAGGED: case ROUTE_STEP_Q32: case ROUTE_STEP_BASIS: case ROUTE_STEP_SLOTS: return run_one_pass(r, d, w, out, stream, adam, chain);
+    case ROUTE_TWO_PASS: return run_two_pass(r, d, w, want_grad, out, stream, adam);
+    case ROUTE_POSE: return run_pose(r, d, w, poses, out, stream, adam);
+    default: return run_general(r, d, w, e, poses, want_grad, want_exponent_grad, want_pose_grad, out, stream, adam);
+  }
 }
 
 int dc_consistency_gate(const void* raw_pointwise, int dtype, int point_fmt, const uint8_t* mask, int64_t n,
@@ -1998,33 +1977,39 @@ int dc_sequence_step(const dcSequenceDesc* d, double* w, const double* e, const 
   return sequence_eval_impl(d, w, e, poses, 1, 0, 0, out, stream, a);
 }
 
-int dc_sequence_step_chained(const dcSequenceDesc* d, double* w, const double* e, const double* poses, double* exp_avg,
-                             double* exp_avg_sq, int64_t step, int has_prev, double grad_scale, double lr, double beta1, double beta2,
-                             double eps, double weight_decay, int32_t* ready, double* out_prev, hipStream_t stream) {
+// What the chained entry points share: the argument check, the ChainCall of launch `step` that finishes `has_prev` ? the launch before
+// it : nothing, the previous launch's rows where they are another sequence's (linked_call) and -- `update` -- the Adam step `step - 1`
+// its leading blocks take.
+static int linked_call(const dcSequenceDesc* d_prev, int prev_parity, int finish, const double* acc_in, int n_terms, ChainCall* c);
+static int chain_call(const dcSequenceDesc* d, double* w, double* exp_avg, double* exp_avg_sq, int64_t step, bool has_prev, bool update,
+                      double grad_scale, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t* ready, double* out_prev,
+                      ChainCall* c, const dcSequenceDesc* d_prev = nullptr, int prev_parity = 0, int finish = 0, const double* acc_in = nullptr) {
   if (!d || d->model_kind == DC_MODEL_NONE || d->n_terms < 1 || d->n == 0 || !ready || !out_prev || step < 1) return DC_ERR_ARG;
-  if (has_prev && step < 2) return DC_ERR_ARG;
-  ChainCall c{ready, (int)(step & 1), has_prev ? 1 : 0, out_prev, AdamArgs{}, nullptr, false};
-  c.stamp = (uint32_t)step;
-  if (has_prev) {
-    int rc = make_adam(w, exp_avg, exp_avg_sq, d->n_terms, step - 1, grad_scale, lr, beta1, beta2, eps, weight_decay, &c.adam_prev);
-    if (rc) return rc;
-  }
-  return sequence_eval_impl(d, w, e, poses, 1, 0, 0, out_prev, stream, AdamArgs{}, &c);
+  if (update && step < 2) return DC_ERR_ARG;
+  *c = ChainCall{ready, (int)(step & 1), has_prev ? 1 : 0, out_prev, AdamArgs{}, nullptr, false};
+  c->stamp = (uint32_t)step;
+  const int rc = linked_call(d_prev, prev_parity, finish, acc_in, d->n_terms, c);
+  if (rc || !update) return rc;
+  return make_adam(w, exp_avg, exp_avg_sq, d->n_terms, step - 1, grad_scale, lr, beta1, beta2, eps, weight_decay, &c->adam_prev);
 }
 
 int dc_sequence_step_chained_rec(const dcSequenceDesc* d, double* w, const double* e, const double* poses, double* exp_avg,
                                  double* exp_avg_sq, int64_t step, int has_prev, double grad_scale, double lr, double beta1, double beta2,
                                  double eps, double weight_decay, int32_t* ready, double* out_prev, double* w_used_prev,
                                  hipStream_t stream) {
-  if (!d || d->model_kind == DC_MODEL_NONE || d->n_terms < 1 || d->n == 0 || !ready || !out_prev || step < 1) return DC_ERR_ARG;
-  if (has_prev && step < 2) return DC_ERR_ARG;
-  ChainCall c{ready, (int)(step & 1), has_prev ? 1 : 0, out_prev, AdamArgs{}, nullptr, false, has_prev ? w_used_prev : nullptr};
-  c.stamp = (uint32_t)step;
-  if (has_prev) {
-    int rc = make_adam(w, exp_avg, exp_avg_sq, d->n_terms, step - 1, grad_scale, lr, beta1, beta2, eps, weight_decay, &c.adam_prev);
-    if (rc) return rc;
-  }
+  ChainCall c;
+  const int rc = chain_call(d, w, exp_avg, exp_avg_sq, step, has_prev != 0, has_prev != 0, grad_scale, lr, beta1, beta2, eps, weight_decay, ready,
+                            out_prev, &c);
+  if (rc) return rc;
+  c.w_prev_out = has_prev ? w_used_prev : nullptr;
   return sequence_eval_impl(d, w, e, poses, 1, 0, 0, out_prev, stream, AdamArgs{}, &c);
+}
+
+int dc_sequence_step_chained(const dcSequenceDesc* d, double* w, const double* e, const double* poses, double* exp_avg,
+                             double* exp_avg_sq, int64_t step, int has_prev, double grad_scale, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, int32_t* ready, double* out_prev, hipStream_t stream) {
+  return dc_sequence_step_chained_rec(d, w, e, poses, exp_avg, exp_avg_sq, step, has_prev, grad_scale, lr, beta1, beta2, eps, weight_decay, ready,
+                                      out_prev, nullptr, stream);
 }
 
 // ---- a chain over the SEVERAL sequences of one loss (train.py:172-175; eval.py:85-112 pools their sums) ---------------------------
@@ -2032,17 +2017,14 @@ int dc_sequence_step_chained_rec(const dcSequenceDesc* d, double* w, const doubl
 // of the previous step -- by summing ITS rows (d_prev, parity prev_parity) onto the running sums of the step (acc_in, NULL for the
 // step's second launch).  finish: 0 nothing is pending (the very first launch), 1 sum into out_prev (the running sums; may be
 // acc_in itself), 2 the sums complete a step: Adam update `step - 1` on w, out_prev <- the step's totals, w_used_prev.
-static int linked_call(const dcSequenceDesc* d, const dcSequenceDesc* d_prev, int prev_parity, int finish, const double* acc_in, int n_terms,
-                       ChainCall* c) {
+static int linked_call(const dcSequenceDesc* d_prev, int prev_parity, int finish, const double* acc_in, int n_terms, ChainCall* c) {
   if (finish == 0) return DC_OK;
   if (!d_prev || !d_prev->partials || d_prev->n_terms != n_terms || d_prev->n < 1) return DC_ERR_ARG;
   if (d_prev->partials_count < dc_sequence_partials_count(d_prev->n, n_terms, d_prev->n_scans)) return DC_ERR_WORKSPACE;
-  const int64_t n_rows = d_prev->centre_idx ? d_prev->n_centres : d_prev->n;
   c->prev_rows = chain_buffer(d_prev, n_terms, prev_parity & 1);
-  c->prev_count = xcd_grid(n_blocks(n_rows));
+  c->prev_count = route_seq_rows(d_prev).g_blocks;
   c->acc_in = acc_in;
   c->prev_status = d_prev->status;
-  (void)d;
   return DC_OK;
 }
 
@@ -2050,16 +2032,13 @@ int dc_sequence_step_linked(const dcSequenceDesc* d, const dcSequenceDesc* d_pre
                             double* w, const double* e, const double* poses, double* exp_avg, double* exp_avg_sq, int64_t step,
                             int64_t stamp, double grad_scale, double lr, double beta1, double beta2, double eps, double weight_decay,
                             int32_t* ready, double* out_prev, double* w_used_prev, hipStream_t stream) {
-  if (!d || d->model_kind == DC_MODEL_NONE || d->n_terms < 1 || d->n == 0 || !ready || !out_prev || step < 1 || stamp < 1) return DC_ERR_ARG;
-  if (finish < 0 || finish > 2 || (finish == 2 && step < 2)) return DC_ERR_ARG;
-  ChainCall c{ready, (int)(step & 1), finish ? 1 : 0, out_prev, AdamArgs{}, nullptr, false, finish == 2 ? w_used_prev : nullptr};
-  c.stamp = (uint32_t)stamp;
-  int rc = linked_call(d, d_prev, prev_parity, finish, acc_in, d->n_terms, &c);
+  if (stamp < 1 || finish < 0 || finish > 2) return DC_ERR_ARG;
+  ChainCall c;
+  const int rc = chain_call(d, w, exp_avg, exp_avg_sq, step, finish != 0, finish == 2, grad_scale, lr, beta1, beta2, eps, weight_decay, ready, out_prev,
+                            &c, d_prev, prev_parity, finish, acc_in);
   if (rc) return rc;
-  if (finish == 2) {
-    rc = make_adam(w, exp_avg, exp_avg_sq, d->n_terms, step - 1, grad_scale, lr, beta1, beta2, eps, weight_decay, &c.adam_prev);
-    if (rc) return rc;
-  }
+  c.stamp = (uint32_t)stamp;
+  c.w_prev_out = finish == 2 ? w_used_prev : nullptr;
   return sequence_eval_impl(d, w, e, poses, 1, 0, 0, out_prev, stream, AdamArgs{}, &c);
 }
 
@@ -2069,15 +2048,12 @@ int dc_sequence_chain_flush_linked(const dcSequenceDesc* d_prev, int prev_parity
                                    double eps, double weight_decay, int32_t* ready, double* out, hipStream_t stream) {
   if (!d_prev || d_prev->model_kind == DC_MODEL_NONE || d_prev->n_terms < 1 || d_prev->n_terms > 3 || !ready || !out || step < 1) return DC_ERR_ARG;
   ChainCall c{ready, 0, 1, out, AdamArgs{}, nullptr, false, nullptr};
-  int rc = linked_call(d_prev, d_prev, prev_parity, 2, acc_in, d_prev->n_terms, &c);
+  c.stamp = (uint32_t)stamp;
+  int rc = linked_call(d_prev, prev_parity, 2, acc_in, d_prev->n_terms, &c);
   if (rc) return rc;
   rc = make_adam(w, exp_avg, exp_avg_sq, d_prev->n_terms, step, grad_scale, lr, beta1, beta2, eps, weight_decay, &c.adam_prev);
   if (rc) return rc;
-  StepChain ch{};
-  ch.ready = ready; ch.stamp = (uint32_t)stamp; ch.parity = 0; ch.has_prev = 1; ch.n_front = kChainFront;
-  ch.n_out = 2 + 2 * d_prev->n_terms + 12 * d_prev->n_scans;
-  ch.prev = c.prev_rows; ch.prev_rows = c.prev_count; ch.acc_in = acc_in; ch.out_prev = out; ch.w_prev_out = nullptr; ch.status = d_prev->status;
-  ch.spin_limit = 0; ch.adam = c.adam_prev; ch.grad_sum = nullptr; ch.w_now = w; ch.prev_status = d_prev->status;
+  const StepChain ch = make_chain(c, 2 + 2 * d_prev->n_terms + 12 * d_prev->n_scans, nullptr, 0, d_prev->status, 0, w, 0);
   const int P = d_prev->n_terms;
   if (P == 1) hipLaunchKernelGGL(chain_front_only_kernel<1>, dim3(kChainFront), dim3(kBlock), 0, stream, ch);
   else if (P == 2) hipLaunchKernelGGL(chain_front_only_kernel<2>, dim3(kChainFront), dim3(kBlock), 0, stream, ch);
@@ -2094,8 +2070,7 @@ int dc_sequence_chain_flush(const dcSequenceDesc* d, double* w, double* exp_avg,
   if (rc) return rc;
   const int n_terms = d->n_terms, n_acc = 2 * n_terms + 12 * d->n_scans;
   if (!d->partials || d->partials_count < dc_sequence_partials_count(d->n, n_terms, d->n_scans)) return DC_ERR_WORKSPACE;
-  const int64_t n_rows = d->centre_idx ? d->n_centres : d->n;
-  const int64_t g_blocks = xcd_grid(n_blocks(n_rows));
+  const int64_t g_blocks = route_seq_rows(d).g_blocks;
   const double* buf = chain_buffer(d, n_terms, (int)(step & 1));
   hipLaunchKernelGGL(reduce_eval_kernel, dim3(2 + n_terms), dim3(kRedBlock), 0, stream, buf, buf + 2 * g_blocks, g_blocks, g_blocks,
                      n_terms, 2 + n_acc, out, a, (const int32_t*)d->status);
@@ -2107,14 +2082,11 @@ int dc_sequence_eval_after_update(const dcSequenceDesc* d, double* w, const doub
                                   double* exp_avg_sq, int64_t step, const double* grad_sum, double grad_scale, double lr, double beta1,
                                   double beta2, double eps, double weight_decay, int32_t* ready, double* out, double* w_used,
                                   hipStream_t stream) {
-  if (!d || d->model_kind == DC_MODEL_NONE || d->n_terms < 1 || d->n == 0 || !ready || !out || step < 1) return DC_ERR_ARG;
-  if (grad_sum && step < 2) return DC_ERR_ARG;
-  ChainCall c{ready, (int)(step & 1), grad_sum ? 1 : 0, out, AdamArgs{}, grad_sum ? grad_sum : w, true, w_used};
-  c.stamp = (uint32_t)step;
-  if (grad_sum) {
-    int rc = make_adam(w, exp_avg, exp_avg_sq, d->n_terms, step - 1, grad_scale, lr, beta1, beta2, eps, weight_decay, &c.adam_prev);
-    if (rc) return rc;
-  }
+  ChainCall c;
+  const int rc = chain_call(d, w, exp_avg, exp_avg_sq, step, grad_sum != nullptr, grad_sum != nullptr, grad_scale, lr, beta1, beta2, eps, weight_decay,
+                            ready, out, &c);
+  if (rc) return rc;
+  c.grad_sum = grad_sum ? grad_sum : w; c.reduce_now = true; c.w_prev_out = w_used;
   return sequence_eval_impl(d, w, e, poses, 1, 0, 0, out, stream, AdamArgs{}, &c);
 }
 

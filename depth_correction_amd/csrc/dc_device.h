@@ -25,7 +25,7 @@ __device__ __forceinline__ int64_t xcd_block_of(int64_t b, int64_t n_logical) {
   const int64_t logical = (b % kXcds) * per + b / kXcds;
   return logical < n_logical ? logical : -1;
 }
-inline int64_t xcd_grid(int64_t n_logical) { return ((n_logical + kXcds - 1) / kXcds) * kXcds; }
+constexpr int64_t xcd_grid(int64_t n_logical) { return ((n_logical + kXcds - 1) / kXcds) * kXcds; }
 
 // ---- xyz rows: element stride 3 (API tensors) or 4 (padded internal layout) ------------------------
 // Point formats: float, double, or q32 (fixed point, DC_Q32).  All loads return fp64 absolute coordinates.

@@ -15,8 +15,36 @@
 #include "dc_dynmath.h"
 #include "dc_rangeimage_math.h"
 #include "dc_align_math.h"
+#include "dc_cons_route.h"
 
 extern "C" {
+
+// the kernel route of a sequence evaluation (dc_cons_route.h: what sequence_eval_impl runs before it launches anything); nothing behind
+// the descriptor's pointers is read.  has_*: which of w / poses / out the call passes; options int [7] = {no_tab, fwd_generic, no_basis,
+// two_pass, step_var, pose_three_pass, step_six}; out int64 [22], in the order of the assignments below.  Returns the call's status.
+int dc_host_choose_route(const dcSequenceDesc* d, int has_w, int has_poses, int has_out, int want_grad, int want_exponent_grad,
+                         int want_pose_grad, int chained, const int* options, int64_t* out) {
+  dc::RouteOptions o;
+  o.no_tab = options[0] != 0; o.fwd_generic = options[1]; o.no_basis = options[2] != 0; o.two_pass = options[3] != 0;
+  o.step_var = options[4]; o.pose_three_pass = options[5] != 0; o.step_six = options[6] != 0;
+  static const double dummy = 0.0;
+  dc::SeqRoute r;
+  const int rc = dc::dc_choose_route_call(d, has_w ? &dummy : nullptr, has_poses ? &dummy : nullptr, has_out ? &dummy : nullptr, want_grad,
+                                          want_exponent_grad, want_pose_grad, chained != 0, o, &r);
+  const int64_t v[22] = {r.kind, r.f64, r.k, r.P, r.cap, r.six, r.round2, r.table_loss, r.use_hdr, r.max_rows, (int64_t)r.lds_fwd, r.rows_fwd,
+                         (int64_t)r.lds_bwd, r.rows_bwd, r.grouped, r.n_terms, r.n_acc, r.n_red, r.n_rows, r.g_blocks, r.rows, r.grid};
+  for (int i = 0; i < 22; ++i) out[i] = v[i];
+  return rc;
+}
+
+// use_table of dc_cons_route.h (the chooser and consistency_fwd_impl / consistency_bwd_impl share it): out int64 [2] = {LDS bytes, rows}
+int dc_host_use_table(const dcBlockTable* t, int no_tab, int layout, int stride, int row_bytes, int extra_rows, int64_t lds_limit, int64_t* out) {
+  size_t bytes = 0;
+  int rows = 0;
+  const bool ok = dc::use_table(t, no_tab != 0, layout, stride, (uint32_t)row_bytes, extra_rows, (size_t)lds_limit, &bytes, &rows);
+  out[0] = (int64_t)bytes; out[1] = rows;
+  return ok ? 1 : 0;
+}
 
 // cov: [n,6] (xx xy xz yy yz zz) -> lam [n,3], vec [n,9] (vec[i, k*3 + c] = component c of eigenvector k)
 void dc_host_eig3(const double* cov, long n, double* lam, double* vec) {
