@@ -239,6 +239,10 @@ class Config(object):
         self.slam_min_overlap = 0.9             # map_update_overlap
         self.slam_min_dist_new_point = 0.1      # min_dist_new_point
         self.slam_sensor_max_range = 25.0       # sensor_max_range
+        # moving sweeps (DESIGN "Moving-sweep rendering and de-skew"; not in the reference's Config): run_slam de-skews every scan that
+        # has sweep times with the constant-velocity twist of its prior motion times slam_sweep_fraction before the mapper sees it
+        self.slam_deskew = False
+        self.slam_sweep_fraction = 1.0
         # dynamic points in the map (launch/slam.launch compute_prob_dynamic and its parameters; DESIGN "Dynamic points in the map").
         # slam.launch runs with compute_prob_dynamic on; the three switches are off here so that existing results and timings stand.
         self.slam_compute_prob_dynamic = False  # update the map points' probabilities of being dynamic before every map update

@@ -11,6 +11,7 @@
 #include "dc_biasmath.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
+#include "dc_sweepmath.h"
 #include "dc_planemath.h"
 #include "dc_dynmath.h"
 #include "dc_rangeimage_math.h"
@@ -239,6 +240,18 @@ int dc_host_beam_select(const int32_t* sub_face, const double* sub_t, const doub
     dc::beam_select(sub_face + i * n_samples, sub_t + i * n_samples, sub_w + i * n_samples, n_samples, detection, tau, min_hits, face_out + i,
                     depth_out + i, n_hits_out + i);
   return DC_OK;
+}
+
+// The moving-sweep map on host arrays (dc_sweepmath.h): row i of x double [n,3] at sweep time tau[i] under the twist row twist_index[i]
+// (int32 [n]) of twists double [., 6] -> point_out = D(tau) x, dir_out = Exp(tau w) x, double [n,3] each (either may be NULL)
+void dc_host_sweep_apply(const double* x, const double* tau, const int32_t* twist_index, const double* twists, int64_t n, double* point_out,
+                         double* dir_out) {
+  for (int64_t i = 0; i < n; ++i) {
+    const double* tw = twists + 6 * (int64_t)twist_index[i];
+    const dc::SweepRot r = dc::sweep_rot(tau[i], tw[3], tw[4], tw[5]);
+    if (point_out) dc::sweep_point(r, tau[i], tw[0], tw[1], tw[2], x[3 * i], x[3 * i + 1], x[3 * i + 2], point_out + 3 * i);
+    if (dir_out) dc::sweep_rotate(r, x[3 * i], x[3 * i + 1], x[3 * i + 2], dir_out + 3 * i);
+  }
 }
 
 // ---- the BVH ray caster's per-ray arithmetic (dc_raymath.h) --------------------------------------------------------------------------

@@ -32,9 +32,13 @@
 // and the S consecutive lanes of a beam reduce their returns to one return with cross-lane reads only (rules: dc_beammath.h).  S is
 // a power of two <= 64, so a wavefront holds 64 / S whole beams; the lanes past the last beam stay in the kernel as misses until
 // the reduction is done, because a cross-lane read from a lane that has left returns garbage.
+//
+// dc_raycast_sweep renders a moving sweep: every lane first forms its ray at its own sweep time (dc_sweepmath.h) in the start frame
+// of its scan, then is one of raycast_rays_kernel's lanes; dc_sweep_rays writes those rays out instead of casting them.
 #include "dc_common.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
+#include "dc_sweepmath.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
 #include "../../include/dc_hip.h"
@@ -156,6 +160,38 @@ using dc::Ray64;
 using dc::box_entry;
 using dc::test_triangle;
 
+// A sensor-frame ray in the world: direction R s and origin R v + t of the pose M (4 x 4, row-major).  Every cast kernel forms its ray
+// here, with the multiply-adds written out, so that kernels given the same ray cast the same bits: left to the compiler, the
+// contraction of M[0] * s0 + M[1] * s1 + M[2] * s2 is chosen per call site (it depends on where s comes from -- a load, a conversion
+// from fp32, the sweep arithmetic).  The order is the one the fp64 thin casts were built with.
+__device__ __forceinline__ void pose_dir(const double* __restrict__ M, double s0, double s1, double s2, double& d0, double& d1, double& d2) {
+#pragma clang fp contract(off)
+  d0 = fma(M[2], s2, fma(M[0], s0, M[1] * s1));
+  d1 = fma(M[6], s2, fma(M[4], s0, M[5] * s1));
+  d2 = fma(M[10], s2, fma(M[9], s1, M[8] * s0));
+}
+
+__device__ __forceinline__ void pose_point(const double* __restrict__ M, double v0, double v1, double v2, double& o0, double& o1, double& o2) {
+#pragma clang fp contract(off)
+  o0 = fma(M[2], v2, fma(M[0], v0, M[1] * v1)) + M[3];
+  o1 = fma(M[6], v2, fma(M[4], v0, M[5] * v1)) + M[7];
+  o2 = fma(M[10], v2, fma(M[8], v0, M[9] * v1)) + M[11];
+}
+
+// |n . d| / (|n| |d|) on the triangle tri [9] with n = (v1 - v0) x (v2 - v0): the cosine of the incidence angle of the world-frame
+// direction d (0 / 0 on a face of zero area: NaN).  Written out for the same reason as pose_dir, in the order raycast_rays_kernel<double>
+// was built with; dc_raycast_rays and dc_raycast_sweep take its arccos, dc_raycast_beams weights a sub-ray with it.
+__device__ __forceinline__ double incidence_cos(const double* __restrict__ tri, double d0, double d1, double d2) {
+#pragma clang fp contract(off)
+  const double e10 = tri[3] - tri[0], e11 = tri[4] - tri[1], e12 = tri[5] - tri[2];
+  const double e20 = tri[6] - tri[0], e21 = tri[7] - tri[1], e22 = tri[8] - tri[2];
+  const double n0 = fma(e11, e22, -(e12 * e21)), n1 = fma(e12, e20, -(e10 * e22)), n2 = fma(e10, e21, -(e11 * e20));
+  const double nd = fma(n2, d2, fma(n0, d0, n1 * d1));
+  const double nn = fma(n2, n2, fma(n0, n0, n1 * n1));
+  const double dd = fma(d2, d2, fma(d0, d0, d1 * d1));
+  return fabs(nd) / (sqrt(nn) * sqrt(dd));
+}
+
 // Closest hit of one ray (origin o, direction d, both fp64 world frame) over the tree: the traversal both cast kernels share.
 // `stack` is the block's LDS stack (kStackDepth x kCastBlock, lane-minor); best.leaf is the winning leaf's row of leaf_tri.
 __device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const float* __restrict__ node_box,
@@ -218,9 +254,8 @@ __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __re
   const int64_t p = g / n_rays, r = g - p * n_rays;
   const double* M = poses + 16 * p;
   const double s0 = dirs[3 * r], s1 = dirs[3 * r + 1], s2 = dirs[3 * r + 2];
-  const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
-  const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
-  const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
+  double d0, d1, d2;
+  pose_dir(M, s0, s1, s2, d0, d1, d2);
   const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, M[3], M[7], M[11], t_min[r], cull, stack, lane);
   face_out[g] = best.face;
   t_out[g] = best.t;
@@ -251,24 +286,14 @@ __global__ void __launch_bounds__(kCastBlock) raycast_rays_kernel(const int32_t*
   const double* M = poses + 16 * (int64_t)lo;
   const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
   const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
-  const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
-  const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
-  const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
-  const double o0 = (M[0] * v0 + M[1] * v1 + M[2] * v2) + M[3];
-  const double o1 = (M[4] * v0 + M[5] * v1 + M[6] * v2) + M[7];
-  const double o2 = (M[8] * v0 + M[9] * v1 + M[10] * v2) + M[11];
+  double d0, d1, d2, o0, o1, o2;
+  pose_dir(M, s0, s1, s2, d0, d1, d2);
+  pose_point(M, v0, v1, v2, o0, o1, o2);
   const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min, cull, stack, lane);
   face_out[g] = best.face;
   t_out[g] = best.t;
   double inc = NAN;
-  if (best.leaf >= 0) {
-    const double* tri = leaf_tri + 9 * (int64_t)best.leaf;
-    const double e10 = tri[3] - tri[0], e11 = tri[4] - tri[1], e12 = tri[5] - tri[2];
-    const double e20 = tri[6] - tri[0], e21 = tri[7] - tri[1], e22 = tri[8] - tri[2];
-    const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
-    const double c = fabs(n0 * d0 + n1 * d1 + n2 * d2) / (sqrt(n0 * n0 + n1 * n1 + n2 * n2) * sqrt(d0 * d0 + d1 * d1 + d2 * d2));
-    inc = acos(fmin(1.0, c));                       // 0 / 0 on a face of zero area: NaN
-  }
+  if (best.leaf >= 0) inc = acos(fmin(1.0, incidence_cos(leaf_tri + 9 * (int64_t)best.leaf, d0, d1, d2)));   // zero area: NaN
   inc_out[g] = inc;
 }
 
@@ -328,25 +353,15 @@ __global__ void __launch_bounds__(kCastBlock) raycast_beams_kernel(
                       D);
       const double s0 = D[0], s1 = D[1], s2 = D[2];
       const double v0 = o[0], v1 = o[1], v2 = o[2];
-      // the expressions of raycast_rays_kernel, literally
-      const double d0 = M[0] * s0 + M[1] * s1 + M[2] * s2;
-      const double d1 = M[4] * s0 + M[5] * s1 + M[6] * s2;
-      const double d2 = M[8] * s0 + M[9] * s1 + M[10] * s2;
-      const double o0 = (M[0] * v0 + M[1] * v1 + M[2] * v2) + M[3];
-      const double o1 = (M[4] * v0 + M[5] * v1 + M[6] * v2) + M[7];
-      const double o2 = (M[8] * v0 + M[9] * v1 + M[10] * v2) + M[11];
+      double d0, d1, d2, o0, o1, o2;                 // the ray of raycast_rays_kernel
+      pose_dir(M, s0, s1, s2, d0, d1, d2);
+      pose_point(M, v0, v1, v2, o0, o1, o2);
       const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min_beam ? t_min_beam[i] : t_min, cull,
                                 stack, lane);
       if (best.leaf >= 0) {
         w = pat.v[3 * j + 2];
-        if (weight_kind == DC_BEAM_LAMBERT) {
-          const double* tri = leaf_tri + 9 * (int64_t)best.leaf;
-          const double e10 = tri[3] - tri[0], e11 = tri[4] - tri[1], e12 = tri[5] - tri[2];
-          const double e20 = tri[6] - tri[0], e21 = tri[7] - tri[1], e22 = tri[8] - tri[2];
-          const double n0 = e11 * e22 - e12 * e21, n1 = e12 * e20 - e10 * e22, n2 = e10 * e21 - e11 * e20;
-          const double c = fabs(n0 * d0 + n1 * d1 + n2 * d2) / (sqrt(n0 * n0 + n1 * n1 + n2 * n2) * sqrt(d0 * d0 + d1 * d1 + d2 * d2));
-          w *= fmin(1.0, c);                          // 0 / 0 on a face of zero area: NaN, not a hit
-        }
+        if (weight_kind == DC_BEAM_LAMBERT)           // 0 / 0 on a face of zero area: NaN, not a hit
+          w *= fmin(1.0, incidence_cos(leaf_tri + 9 * (int64_t)best.leaf, d0, d1, d2));
         if (dc::beam_is_hit(best.face, w)) {
           face = best.face;
           t = best.t;
@@ -419,6 +434,79 @@ __global__ void __launch_bounds__(kCastBlock) raycast_beams_kernel(
     depth_out[i] = ok ? depth : INFINITY;
     n_hits_out[i] = n_hits;
   }
+}
+
+// The ray of a moving sweep in the start frame of its scan (dc_sweepmath.h): origin D(tau) vp, direction Exp(tau w) dir.  The scan is
+// found as in raycast_rays_kernel; tw is its row of twists (v, w), tg the ray's sweep time.
+template <typename T>
+__device__ __forceinline__ int sweep_ray(const T* __restrict__ vps, const T* __restrict__ dirs, double tg, int64_t g,
+                                         const int64_t* __restrict__ scan_offset, const double* __restrict__ twists, int n_scans, double* o,
+                                         double* D) {
+  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
+  }
+  const double* tw = twists + 6 * (int64_t)lo;
+  const dc::SweepRot r = dc::sweep_rot(tg, tw[3], tw[4], tw[5]);
+  dc::sweep_point(r, tg, tw[0], tw[1], tw[2], (double)vps[3 * g], (double)vps[3 * g + 1], (double)vps[3 * g + 2], o);
+  dc::sweep_rotate(r, (double)dirs[3 * g], (double)dirs[3 * g + 1], (double)dirs[3 * g + 2], D);
+  return lo;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kBuildBlock) sweep_rays_kernel(const T* __restrict__ vps, const T* __restrict__ dirs,
+                                                                 const double* __restrict__ tau, int64_t total,
+                                                                 const int64_t* __restrict__ scan_offset, const double* __restrict__ twists,
+                                                                 int n_scans, double* __restrict__ origins_out, double* __restrict__ dirs_out) {
+  const int64_t g = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (g >= total) return;
+  double o[3], D[3];
+  sweep_ray(vps, dirs, tau[g], g, scan_offset, twists, n_scans, o, D);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    origins_out[3 * g + a] = o[a];
+    dirs_out[3 * g + a] = D[a];
+  }
+}
+
+// dc_raycast_sweep: sweep_ray, then raycast_rays_kernel's body on that ray.  A ray whose tau is not finite is a miss without a cast
+// (its ray is NaN, which cast_ray would carry through every box of the tree to the same miss).
+template <typename T>
+__global__ void __launch_bounds__(kCastBlock) raycast_sweep_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                                                   const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
+                                                                   int64_t n, const T* __restrict__ vps, const T* __restrict__ dirs,
+                                                                   const double* __restrict__ tau, int64_t total,
+                                                                   const int64_t* __restrict__ scan_offset, const double* __restrict__ poses,
+                                                                   const double* __restrict__ twists, int n_scans,
+                                                                   const double* __restrict__ t_min_ray, double t_min, int cull,
+                                                                   int32_t* __restrict__ face_out, double* __restrict__ t_out,
+                                                                   double* __restrict__ inc_out) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  if (g >= total) return;
+  int32_t face = -1;
+  double t = INFINITY, inc = NAN;
+  const double tg = tau[g];
+  if (isfinite(tg)) {
+    double o[3], D[3];
+    const int s = sweep_ray(vps, dirs, tg, g, scan_offset, twists, n_scans, o, D);
+    const double* M = poses + 16 * (int64_t)s;
+    const double s0 = D[0], s1 = D[1], s2 = D[2];
+    const double v0 = o[0], v1 = o[1], v2 = o[2];
+    double d0, d1, d2, o0, o1, o2;                   // the ray of raycast_rays_kernel
+    pose_dir(M, s0, s1, s2, d0, d1, d2);
+    pose_point(M, v0, v1, v2, o0, o1, o2);
+    const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min_ray ? t_min_ray[g] : t_min, cull, stack,
+                              lane);
+    face = best.face;
+    t = best.t;
+    if (best.leaf >= 0) inc = acos(fmin(1.0, incidence_cos(leaf_tri + 9 * (int64_t)best.leaf, d0, d1, d2)));   // zero area: NaN
+  }
+  face_out[g] = face;
+  t_out[g] = t;
+  inc_out[g] = inc;
 }
 
 // the checks dc_beam_subrays and dc_raycast_beams share; fills `pat`
@@ -565,6 +653,43 @@ int dc_raycast_beams(const int32_t* child, const float* node_box, const double* 
     raycast_beams_kernel<double><<<grid_of(total, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
         child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, n, scan_offset, poses, n_scans, pat, log2s,
         r0, spread, t_min_beam, t_min, cull, weight_kind, detection, tau, min_hits, face_out, depth_out, n_hits_out, sub_face, sub_t, sub_w);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_sweep_rays(const void* vps, const void* dirs, int dtype, const double* tau, int64_t n, const int64_t* scan_offset, const double* twists,
+                  int n_scans, double* origins_out, double* dirs_out, dcStream_t stream) {
+  if (n < 0 || n_scans < 0) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (n_scans < 1 || !vps || !dirs || !tau || !scan_offset || !twists || !origins_out || !dirs_out) return DC_ERR_ARG;
+  if (dtype == DC_F32)
+    sweep_rays_kernel<float><<<grid_of(n, kBuildBlock), kBuildBlock, 0, (hipStream_t)stream>>>(
+        (const float*)vps, (const float*)dirs, tau, n, scan_offset, twists, n_scans, origins_out, dirs_out);
+  else
+    sweep_rays_kernel<double><<<grid_of(n, kBuildBlock), kBuildBlock, 0, (hipStream_t)stream>>>(
+        (const double*)vps, (const double*)dirs, tau, n, scan_offset, twists, n_scans, origins_out, dirs_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_raycast_sweep(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                     const void* vps, const void* dirs, int dtype, const double* tau, int64_t n, const int64_t* scan_offset,
+                     const double* poses, const double* twists, int n_scans, const double* t_min_ray, double t_min, int cull,
+                     int32_t* face_out, double* t_out, double* inc_out, dcStream_t stream) {
+  if (n_faces < 1 || n < 0 || n_scans < 0 || !node_box || !leaf_tri || !leaf_face || (n_faces > 1 && !child) || !(t_min == t_min))
+    return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (n_scans < 1 || !vps || !dirs || !tau || !scan_offset || !poses || !twists || !face_out || !t_out || !inc_out) return DC_ERR_ARG;
+  if (dtype == DC_F32)
+    raycast_sweep_kernel<float><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const float*)vps, (const float*)dirs, tau, n, scan_offset, poses, twists, n_scans,
+        t_min_ray, t_min, cull, face_out, t_out, inc_out);
+  else
+    raycast_sweep_kernel<double><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, tau, n, scan_offset, poses, twists, n_scans,
+        t_min_ray, t_min, cull, face_out, t_out, inc_out);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

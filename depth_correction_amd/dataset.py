@@ -20,8 +20,8 @@ import numpy as np
 from numpy.lib.recfunctions import unstructured_to_structured, merge_arrays
 
 __all__ = ['PlaneDataset', 'MeshDataset', 'RoomBoxDataset', 'KittiLikeDataset', 'create_dataset', 'add_depth_noise', 'Forwarding',
-           'TransformingDataset', 'FilteredDataset', 'NoisyPoseDataset', 'NoisyDepthDataset', 'noisy_dataset', 'euler_matrix',
-           'RenderedMeshDataset', 'DepthBiasDataset', 'render_lidar_cloud', 'render_lidar_clouds', 'lidar_directions']
+           'TransformingDataset', 'FilteredDataset', 'DeskewedDataset', 'NoisyPoseDataset', 'NoisyDepthDataset', 'noisy_dataset',
+           'euler_matrix', 'RenderedMeshDataset', 'DepthBiasDataset', 'render_lidar_cloud', 'render_lidar_clouds', 'lidar_directions']
 
 
 def _structured(xyz, normals=None):
@@ -318,6 +318,57 @@ class FilteredDataset(TransformingDataset):
     def transform_cloud(self, cloud, **kwargs):
         from .preproc import filtered_cloud
         return filtered_cloud(cloud, self.cfg)
+
+
+class DeskewedDataset(TransformingDataset):
+    """Raw moving-sweep clouds (the field ``t``: RenderedMeshDataset with a SweepModel) taken into the frame of their pose by
+    preproc.deskew_cloud.  ``fraction`` and ``ref`` as in render.SweepModel.  ``twists`` [N,6] per inter-scan period, one row per
+    pose of the whole trajectory (``dataset.poses``, rows taken by scan id) or one per item of ``dataset``; or None: the twists the scans
+    were rendered with where ``dataset`` has a SweepModel (``dataset.sweep``: its twists, or those of ``dataset.poses``; ``fraction``
+    and ``ref`` must then be the model's, ValueError otherwise), else constant velocity between the poses (sweep.twists_from_poses).
+    A slice of a RenderedMeshDataset keeps every pose, so ds[1:3] and ds[::2] are de-skewed with the twists of the whole trajectory,
+    as they were rendered; a dataset without ``poses`` offers only the poses of its items, and a slice of it gets the twists between
+    those.  A cloud without ``t`` passes unchanged."""
+
+    def __init__(self, dataset, twists=None, fraction=1.0, ref=0.0, device=None):
+        from .sweep import check_fraction_ref, twists_from_poses
+        super().__init__(dataset)
+        self.fraction, self.ref = check_fraction_ref(fraction, ref)
+        self.device = device
+        ids = list(getattr(dataset, 'ids', range(len(dataset))))
+        whole = getattr(dataset, 'poses', None)                       # every pose of the trajectory, by id, where the dataset keeps them
+        whole = None if whole is None else np.asarray(whole, dtype=np.float64).reshape(-1, 4, 4)
+        if whole is not None and not all(isinstance(id, (int, np.integer)) and 0 <= id < len(whole) for id in ids):
+            whole = None
+        model = getattr(dataset, 'sweep', None)
+        if twists is None and model is not None and whole is not None:
+            if (self.fraction, self.ref) != (model.fraction, model.ref):
+                raise ValueError('the dataset was rendered with fraction %r and ref %r, asked to de-skew with %r and %r (give twists to '
+                                 'de-skew with another motion)' % (model.fraction, model.ref, self.fraction, self.ref))
+            rows = model.scan_twists(whole)
+        elif twists is None:
+            poses = whole if whole is not None else (np.stack([dataset.cloud_pose(id) for id in ids]) if ids else np.zeros((0, 4, 4)))
+            rows = twists_from_poses(poses, self.fraction)
+        else:
+            rows = self.fraction * np.asarray(twists, dtype=np.float64).reshape(-1, 6)
+            if rows.shape[0] != len(ids) and (whole is None or rows.shape[0] != len(whole)):
+                raise ValueError('%d twists for %d scans' % (rows.shape[0], len(ids)))
+            if whole is not None and rows.shape[0] != len(whole):
+                whole = None                                           # one row per item
+        by_id = whole is not None
+        self.twists = np.stack([rows[id] for id in ids]) if by_id and ids else rows[:len(ids)]      # one row per item, in item order
+        self._row = {id: row for row, id in enumerate(ids)}
+
+    def transform_cloud(self, cloud, item=None, **kwargs):
+        from .preproc import deskew_cloud
+        if 't' not in (getattr(cloud.dtype, 'names', None) or ()):
+            return cloud
+        if item is None:
+            raise ValueError('de-skewing needs to know which scan the cloud is (keyword item): use indexing, iteration or local_cloud(id)')
+        return deskew_cloud(cloud, self.twists[item], ref=self.ref, device=self.device or getattr(self.target, 'device', None))
+
+    def local_cloud(self, id):
+        return self.transform_cloud(self.target.local_cloud(id), item=self._row[id])
 
 
 def euler_matrix(ai, aj, ak):

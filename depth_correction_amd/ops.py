@@ -1269,6 +1269,120 @@ def raycast_beams(bvh, vps, dirs, scan_offset, poses, pattern, r0, spread, t_min
 
 
 # ------------------------------------------------------------------------------------------------
+# moving-sweep rendering and de-skew (dc_raycast.hip, dc_sweep.hip; the model: include/dc_hip.h)
+# ------------------------------------------------------------------------------------------------
+def _sweep_args(rows, tau, scan_offset, twists, poses=None):
+    """The checks sweep_rays, raycast_sweep and deskew share, all ValueError and all made before anything is uploaded or launched:
+    ``rows`` ((name, tensor [N,3] or None) pairs, the first one present), tau [N], twists [S,6] finite with |w| <= pi (checked on the
+    host copy), poses [S,4,4] where given, and raycast_rays' check of scan_offset.  -> (n, s, offsets on the device, twists f64 on the
+    device).  The twists are checked and uploaded at every call (S x 48 bytes); twists given as a device tensor are read back for the
+    check first, which synchronises: keep them on the host."""
+    import math
+    import numpy as np
+    first = rows[0][1]
+    if not isinstance(first, torch.Tensor) or first.dim() != 2 or first.shape[1] != 3:
+        raise ValueError('%s must be a tensor [N,3]' % rows[0][0])
+    n = first.shape[0]
+    for name, a in rows[1:]:
+        if a is not None and (not isinstance(a, torch.Tensor) or tuple(a.shape) != (n, 3)):
+            raise ValueError('%s must be a tensor [%d,3] like %s' % (name, n, rows[0][0]))
+    if not isinstance(tau, torch.Tensor) or tuple(tau.shape) != (n,):
+        raise ValueError('tau must be a tensor of %d sweep times, got %s' % (n, tuple(tau.shape) if isinstance(tau, torch.Tensor) else type(tau)))
+    tw = np.asarray(twists.detach().cpu() if isinstance(twists, torch.Tensor) else twists, dtype=np.float64)
+    if tw.ndim != 2 or tw.shape[1] != 6:
+        raise ValueError('twists must be [S,6] rows (v, w), got shape %s' % (tw.shape,))
+    if not np.isfinite(tw).all():
+        raise ValueError('twists must be finite')
+    if tw.shape[0] and float(np.linalg.norm(tw[:, 3:], axis=1).max()) > math.pi:
+        raise ValueError('the rotation of a twist must not exceed pi, got %r' % float(np.linalg.norm(tw[:, 3:], axis=1).max()))
+    s = tw.shape[0]
+    if poses is not None and (not isinstance(poses, torch.Tensor) or tuple(poses.shape) != (s, 4, 4)):
+        raise ValueError('poses must be a tensor [%d,4,4], one per twist' % s)
+    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
+        # offsets already on the device are not read back, as in raycast_rays: the kernels clamp the scan index
+        if tuple(scan_offset.shape) != (s + 1,):
+            raise ValueError('scan_offset has shape %s, expected %s' % (tuple(scan_offset.shape), (s + 1,)))
+        off = scan_offset
+    else:
+        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
+        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    if n and s < 1:
+        raise ValueError('rays need at least one scan')
+    dev = need(first, name=rows[0][0]).device
+    for name, a in rows[1:]:
+        if a is not None:
+            need(a, dtype=first.dtype, name=name, device=dev)
+    need(tau, dtype=torch.float64, name='tau', device=dev)
+    if poses is not None:
+        need(poses, dtype=torch.float64, name='poses', device=dev)
+    off = need(off, dtype=torch.int64, name='scan_offset', device=dev) if off.is_cuda else off.to(dev)
+    return n, s, off, torch.as_tensor(np.ascontiguousarray(tw), device=dev)
+
+
+@on_device
+def sweep_rays(vps, dirs, tau, scan_offset, twists):
+    """Rays of a moving sweep in the start frame of their scan (dc_sweep_rays): ray i (vps[i], dirs[i], f32 | f64 [N,3], instantaneous
+    sensor frame) taken at the sweep time tau[i] (f64 [N]) of the scan s with scan_offset[s] <= i < scan_offset[s+1] under twists[s]
+    ([S,6]: v, w; a host array, or a device tensor at the price of a synchronising read-back; checked on the host: finite, |w| <= pi) -> (origins f64 [N,3] = D(tau) vp, directions f64 [N,3] =
+    Exp(tau w) dir), D(tau) = [Exp(tau w) | tau v]."""
+    n, s, off, tw = _sweep_args((('dirs', dirs), ('vps', vps)), tau, scan_offset, twists)
+    dev = dirs.device
+    code = dtype_code(dirs)
+    origins = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    if n == 0:
+        return origins, out
+    check(lib().dc_sweep_rays(ptr(vps), ptr(dirs), code, ptr(tau), n, ptr(off), ptr(tw), s, ptr(origins), ptr(out), stream_ptr()),
+          'dc_sweep_rays')
+    return origins, out
+
+
+@on_device
+def raycast_sweep(bvh, vps, dirs, tau, scan_offset, poses, twists, t_min=0.0, cull=True):
+    """The cast of a moving sweep (dc_raycast_sweep): sweep_rays' ray i, posed by poses[s] (f64 [S,4,4], world from sensor at sweep
+    time 0), through raycast_rays' traversal -> (face i32 [N], t f64 [N], inc f64 [N]), bit-equal to raycast_rays on sweep_rays'
+    output.  ``t_min``: a float, or a device tensor f64 [N] of per-ray near clips.  A ray whose tau is not finite is a miss.  One
+    launch."""
+    n, s, off, tw = _sweep_args((('dirs', dirs), ('vps', vps)), tau, scan_offset, twists, poses=poses)
+    dev = bvh.leaf_face.device
+    need(dirs, name='dirs', device=dev)
+    code = dtype_code(dirs)
+    if isinstance(t_min, torch.Tensor):
+        tm_ray, tm = need(t_min, (n,), dtype=torch.float64, name='t_min', device=dev), 0.0
+    else:
+        tm_ray, tm = None, float(t_min)
+        if tm != tm:
+            raise ValueError('t_min must not be NaN')
+    face = torch.empty((n,), dtype=torch.int32, device=dev)
+    t = torch.empty((n,), dtype=torch.float64, device=dev)
+    inc = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n == 0:
+        return face, t, inc
+    nf = bvh.n_faces
+    check(lib().dc_raycast_sweep(ptr(bvh.child) if nf > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_tri), ptr(bvh.leaf_face), nf,
+                                 ptr(vps), ptr(dirs), code, ptr(tau), n, ptr(off), ptr(poses), ptr(tw), s, ptr(tm_ray), tm,
+                                 1 if cull else 0, ptr(face), ptr(t), ptr(inc), stream_ptr()), 'dc_raycast_sweep')
+    return face, t, inc
+
+
+@on_device
+def deskew(points, tau, scan_offset, twists, vps=None, normals=None):
+    """De-skew (dc_deskew): point i measured at the sweep time tau[i] (f64 [N]) in the instantaneous sensor frame, under the twist of
+    its scan (``scan_offset`` / ``twists`` as in sweep_rays) -> (points', vps', normals') f64 [N,3] in the scan's start frame:
+    x' = D(tau) x, vp' = D(tau) vp, n' = Exp(tau w) n; None for an input that is None.  Rigid per point: depth and incidence angle
+    are kept."""
+    n, s, off, tw = _sweep_args((('points', points), ('vps', vps), ('normals', normals)), tau, scan_offset, twists)
+    dev = points.device
+    code = dtype_code(points)
+    outs = [torch.empty((n, 3), dtype=torch.float64, device=dev) if a is not None else None for a in (points, vps, normals)]
+    if n:
+        check(lib().dc_deskew(ptr(points), ptr(vps), ptr(normals), code, ptr(tau), n, ptr(off), ptr(tw), s, ptr(outs[0]), ptr(outs[1]),
+                              ptr(outs[2]), stream_ptr()), 'dc_deskew')
+    return tuple(outs)
+
+
+# ------------------------------------------------------------------------------------------------
 # depth bias against the mesh (dc_bias.hip)
 # ------------------------------------------------------------------------------------------------
 def bias_out_count(n_bins, n_terms):

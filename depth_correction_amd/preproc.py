@@ -13,7 +13,7 @@ from .filters import (filter_depth, filter_eigenvalue_ratios, filter_eigenvalues
                       filter_valid_neighbors, within_bounds)
 from .transform import xyz_axis_angle_to_matrix
 
-__all__ = ['compute_neighborhood_features', 'establish_neighborhoods', 'filtered_cloud', 'global_cloud',
+__all__ = ['compute_neighborhood_features', 'deskew_cloud', 'establish_neighborhoods', 'filtered_cloud', 'global_cloud',
            'global_cloud_mask', 'local_feature_cloud', 'offset_cloud']
 
 
@@ -30,6 +30,50 @@ def filtered_cloud(cloud, cfg: Config):
         cloud = filter_grid(cloud, grid_res=cfg.grid_res, keep='random', log=cfg.log_filters,
                             rng=np.random.default_rng(cfg.random_seed))
     return cloud
+
+
+def deskew_cloud(cloud, twist, ref=0.0, device=None):
+    """A raw moving-sweep scan taken into the sensor frame at the sweep time ``ref`` (DESIGN "Moving-sweep rendering and de-skew"):
+    ``cloud`` is a structured array with the field ``t`` (the sweep time of every point, render_lidar_clouds with a SweepModel), or a
+    pair (points [N,3], t [N]); ``twist`` [6] = (v, w) of the sweep in the frame at its start.  D(ref)^-1 D(tau) = D(tau - ref) under
+    the twist (Exp(-ref w) v, w) (sweep.shifted_twist), so the times are shifted, v is rotated and one kernel does the rest
+    (ops.deskew).  Returns the same structured dtype with x, y, z, vp_* and normal_* replaced and ``t`` kept, or the points [N,3]."""
+    from . import ops
+    from .sweep import shifted_twist
+    from numpy.lib.recfunctions import structured_to_unstructured
+    tw = np.asarray(twist, dtype=np.float64)
+    if tw.shape != (6,):
+        raise ValueError('twist must be [6] = (v, w), got shape %s' % (tw.shape,))
+    ref = float(ref)
+    if not 0.0 <= ref <= 1.0:
+        raise ValueError('ref must lie in [0, 1], got %r' % (ref,))
+    names = getattr(getattr(cloud, 'dtype', None), 'names', None)
+    if names:
+        if 't' not in names:
+            raise ValueError("the cloud has no field 't' (the sweep time of every point)")
+        grab = lambda fields: np.ascontiguousarray(structured_to_unstructured(cloud[fields], dtype=np.float64)).reshape(-1, 3)
+        pts, t = grab(['x', 'y', 'z']), np.asarray(cloud['t'], dtype=np.float64).reshape(-1)
+        vps = grab(['vp_x', 'vp_y', 'vp_z']) if 'vp_x' in names else None
+        nrm = grab(['normal_x', 'normal_y', 'normal_z']) if 'normal_x' in names else None
+    else:
+        if not isinstance(cloud, (tuple, list)) or len(cloud) != 2:
+            raise ValueError("cloud must be a structured array with the field 't' or a pair (points, t)")
+        pts = np.ascontiguousarray(np.asarray(cloud[0], dtype=np.float64)).reshape(-1, 3)
+        t, vps, nrm = np.asarray(cloud[1], dtype=np.float64).reshape(-1), None, None
+    if t.shape[0] != pts.shape[0]:
+        raise ValueError('%d sweep times for %d points' % (t.shape[0], pts.shape[0]))
+    dev = torch.device(device if device is not None else 'cuda')
+    up = lambda a: None if a is None else torch.as_tensor(a, device=dev).contiguous()
+    x, v, m = ops.deskew(up(pts), up(t - ref), [0, pts.shape[0]], shifted_twist(tw, ref)[None], vps=up(vps), normals=up(nrm))
+    if not names:
+        return x.cpu().numpy()
+    out = cloud.copy()
+    for fields, a in ((('x', 'y', 'z'), x), (('vp_x', 'vp_y', 'vp_z'), v), (('normal_x', 'normal_y', 'normal_z'), m)):
+        if a is not None:
+            a = a.cpu().numpy()
+            for k, f in enumerate(fields):
+                out[f] = a[:, k]
+    return out
 
 
 def _and_mask(cloud, mask):

@@ -6,6 +6,9 @@ reference's cameras (``lidar_directions``).  Compaction, the sensor-frame transf
 
 With a ``BeamModel`` a pixel is a finite beam instead of a thin ray: a bundle of sub-rays over the laser's footprint, cast and
 reduced to one return in one launch (``dc_raycast_beams``; DESIGN "Finite-beam rendering").
+
+With a ``SweepModel`` the sensor moves while it sweeps its field of view: every ray is cast at its own sweep time from where the
+sensor stands then (``dc_raycast_sweep``; DESIGN "Moving-sweep rendering and de-skew").
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from numpy.lib.recfunctions import unstructured_to_structured
 from .dataset import TransformingDataset
 
 __all__ = ['lidar_directions', 'render_lidar_cloud', 'render_lidar_clouds', 'RenderedMeshDataset', 'MovingObjectDataset', 'DepthBiasDataset',
-           'mesh_dir', 'BeamModel']
+           'mesh_dir', 'BeamModel', 'SweepModel']
 
 Z_CLIP = 1e-3          # pytorch3d RasterizationSettings(z_clip_value=1e-3) of the reference
 
@@ -128,16 +131,83 @@ class BeamModel(object):
                                                                       self.min_hits, self.r0, self.divergence)
 
 
+class SweepModel(object):
+    """A sensor that moves while it sweeps its field of view (the motion model: sweep.py).  ``twists`` [N,6] (v, w per scan: the motion
+    over one inter-scan period, in the frame at the sweep's start), or None: from the dataset's poses under constant velocity
+    (sweep.twists_from_poses).  ``fraction`` in (0, 1], the part of the inter-scan period the sweep takes, scales v and w.  ``ref`` in
+    [0, 1] is the sweep time at which the dataset's pose holds: the sweep starts at T_i D(ref)^-1.  ``direction`` 'ccw' | 'cw': the
+    way the azimuth runs with time (sweep_times).  The model speaks of a whole trajectory: ``scan_twists(poses)`` wants one row of
+    ``twists`` per pose given, and with ``twists=None`` the twists are those between the poses given -- a subset of a trajectory's poses
+    gives other twists than the trajectory (RenderedMeshDataset always casts every pose and keeps the clouds asked for).
+    With a field of view narrower than 360 degrees the half segment of columns before the pattern's first yaw gets tau just below 1
+    (sweep_times clamps the wrapped azimuth) although a real sensor takes those columns first: they carry the whole sweep's motion."""
+
+    def __init__(self, twists=None, fraction=1.0, direction='ccw', ref=0.0):
+        from .sweep import check_fraction_ref
+        self.fraction, self.ref = check_fraction_ref(fraction, ref)
+        if direction not in ('ccw', 'cw'):
+            raise ValueError("direction must be 'ccw' or 'cw', got %r" % (direction,))
+        self.direction = direction
+        if twists is not None:
+            twists = np.array(twists, dtype=np.float64)
+            if twists.ndim != 2 or twists.shape[1] != 6 or not np.isfinite(twists).all():
+                raise ValueError('twists must be finite [N,6] rows (v, w), got shape %s' % (twists.shape,))
+            if twists.shape[0] and self.fraction * np.linalg.norm(twists[:, 3:], axis=1).max() > math.pi:
+                raise ValueError('the rotation of a sweep must not exceed pi')
+            twists.flags.writeable = False
+        self.twists = twists
+
+    @staticmethod
+    def sweep_times(dirs, fov, direction='ccw'):
+        """Per-ray sweep time in [0, 1) of lidar_directions' rays from their azimuth (sweep.sweep_times)."""
+        from .sweep import sweep_times
+        return sweep_times(dirs, fov, direction)
+
+    def scan_twists(self, poses):
+        """The sweeps' twists [N,6] for the scans at ``poses`` [N,4,4], ``fraction`` applied."""
+        from .sweep import twists_from_poses
+        poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if self.twists is None:
+            return twists_from_poses(poses, self.fraction)
+        if self.twists.shape[0] != poses.shape[0]:
+            raise ValueError('%d twists for %d poses' % (self.twists.shape[0], poses.shape[0]))
+        return self.fraction * self.twists
+
+    def start_poses(self, poses, twists):
+        """World from sensor at sweep time 0: T_i D(ref)^-1 (numpy)."""
+        from .sweep import sweep_matrix
+        poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        if self.ref == 0.0:
+            return poses.copy()
+        return np.stack([T @ np.linalg.inv(sweep_matrix(tw, self.ref)) for T, tw in zip(poses, twists)]) if len(poses) else poses.copy()
+
+    def cache_key(self):
+        """Directory component of RenderedMeshDataset's cache: every parameter a rendered cloud depends on."""
+        from .utils import hashable
+        tw = 'poses' if self.twists is None else str(abs(hash(hashable(self.twists))))
+        return 'sweep_tw_%s_frac_%r_%s_ref_%r' % (tw, self.fraction, self.direction, self.ref)
+
+
 _DT = np.dtype([(f, np.float64) for f in ('x', 'y', 'z', 'vp_x', 'vp_y', 'vp_z', 'normal_x', 'normal_y', 'normal_z')])
+_DT_SWEEP = np.dtype(_DT.descr + [('t', np.float64)])            # a moving sweep's cloud: the sweep time of every point
 
 
-def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None):
+def render_lidar_clouds(mesh, poses, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None, sweep=None):
     """Scans of ``mesh`` (mesh.TriangleMesh) from every pose of ``poses`` [P,4,4] (world from sensor) in one cast: a list of P
     structured arrays of RenderedMeshDataset.cloud_dtype in the sensor frame (vp = 0, normals rotated into it), misses dropped,
     points in lidar_directions' order.  The hit point is v0 + u (v1 - v0) + v (v2 - v0) in fp64 from the face's vertices.
     With ``beam`` (a BeamModel) every pixel is a finite beam along the same direction: the point is the beam's depth times the
-    direction, the normal that of the face of the return nearest to that depth, and a beam without a return is dropped."""
+    direction, the normal that of the face of the return nearest to that depth, and a beam without a return is dropped.
+    With ``sweep`` (a SweepModel) the sensor moves during the scan and ``poses`` -- the whole trajectory: the twists are taken between
+    them, or row by row from sweep.twists -- hold at the sweep time sweep.ref: every ray is cast
+    from where the sensor stands at its own sweep time, and the cloud is the raw sweep as a driver reports it -- the point is t times
+    the direction in the ray's own instantaneous frame (vp = 0, the normal rotated into that frame), with the field ``t`` the sweep
+    time (dtype cloud_dtype + t).  preproc.deskew_cloud takes it into the frame of the pose."""
     from .ops import raycast
+    if sweep is not None:
+        if beam is not None:
+            raise ValueError('a moving sweep of finite beams is not provided: give sweep or beam, not both')
+        return _render_sweep_clouds(mesh, poses, fov, size, num_segments, device, cull, sweep)
     if beam is not None:
         return _render_beam_clouds(mesh, poses, fov, size, num_segments, device, cull, beam)
     dev = _device(device)
@@ -195,10 +265,45 @@ def _render_beam_clouds(mesh, poses, fov, size, num_segments, device, cull, beam
     return out
 
 
-def render_lidar_cloud(mesh, pose, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None):
+def _render_sweep_clouds(mesh, poses, fov, size, num_segments, device, cull, sweep):
+    """render_lidar_clouds with a SweepModel: every pose and pattern ray in one raycast_sweep call."""
+    from .ops import raycast_sweep, sweep_rays
+    if not isinstance(sweep, SweepModel):
+        raise TypeError('sweep must be a SweepModel or None, got %s' % type(sweep).__name__)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    twists = sweep.scan_twists(poses)
+    start = sweep.start_poses(poses, twists)
+    dev = _device(device)
+    dirs_h, tmin_h = lidar_directions(size=size, fov=fov, num_segments=num_segments)
+    tau_h = sweep.sweep_times(dirs_h, fov, sweep.direction)
+    verts, faces, normals, bvh = mesh.on_device(dev)
+    dev = verts.device
+    n_poses, n_rays = poses.shape[0], dirs_h.shape[0]
+    dirs = torch.as_tensor(np.array(dirs_h), device=dev).repeat(n_poses, 1)
+    t_min = torch.as_tensor(np.array(tmin_h), device=dev).repeat(n_poses)
+    tau = torch.as_tensor(tau_h, device=dev).repeat(n_poses)
+    P = torch.as_tensor(start, device=dev)
+    offsets = [n_rays * p for p in range(n_poses + 1)]
+    face, t, _ = raycast_sweep(bvh, torch.zeros_like(dirs), dirs, tau, offsets, P, twists, t_min=t_min, cull=cull)
+    hit = face >= 0
+    # the face normal in the start frame of its scan, then into the ray's own frame: Exp(-tau w) R_s^T n
+    scan = torch.arange(n_poses, device=dev).repeat_interleave(n_rays)
+    n_start = torch.einsum('nji,nj->ni', P[scan, :3, :3], normals[face.clamp(min=0).long()]).contiguous()
+    _, n_own = sweep_rays(torch.zeros_like(n_start), n_start, -tau, offsets, twists)
+    xs = t[:, None] * dirs
+    arr = torch.cat([xs, torch.zeros_like(xs), n_own, tau[:, None]], dim=1)
+    out = []
+    for p in range(n_poses):
+        rows = slice(p * n_rays, (p + 1) * n_rays)
+        a = arr[rows][hit[rows]].cpu().numpy()
+        out.append(unstructured_to_structured(np.ascontiguousarray(a), dtype=_DT_SWEEP))
+    return out
+
+
+def render_lidar_cloud(mesh, pose, fov=(90., 360.), size=(64, 512), num_segments=32, device='cuda', cull=True, beam=None, sweep=None):
     """One scan (render_lidar_clouds of one pose)."""
     return render_lidar_clouds(mesh, np.asarray(pose, dtype=np.float64)[None], fov=fov, size=size, num_segments=num_segments,
-                               device=device, cull=cull, beam=beam)[0]
+                               device=device, cull=cull, beam=beam, sweep=sweep)[0]
 
 
 class RenderedMeshDataset(object):
@@ -206,13 +311,15 @@ class RenderedMeshDataset(object):
     mesh_dir(), or ``rendered_mesh/<mesh>[/<params>]`` with params such as ``n_10_size_64_512_fov_45_360``.  Poses from
     ``poses`` [N,4,4] or ``poses_path`` (a poses CSV, scan_io.read_poses_csv).  All poses are rendered in one cast at the first
     cloud asked for; ``cache`` reads and writes ``cloud_%05i.bin`` files (np.tofile of cloud_dtype) under ``cache_dir``.  ``beam``
-    (a BeamModel) renders finite beams; their cache lives in a directory of its own, named by the beam's parameters."""
+    (a BeamModel) renders finite beams; their cache lives in a directory of its own, named by the beam's parameters.  ``sweep`` (a
+    SweepModel) renders moving sweeps: the poses hold at the sweep time sweep.ref, the clouds are raw sweeps with the field ``t``
+    (``cloud_dtype`` of the instance gains it), cached in a directory named by the sweep's parameters."""
 
     dataset_name = 'rendered_mesh'
     cloud_dtype = _DT
 
     def __init__(self, name, n=None, size=(64, 512), fov=(45., 360.), num_segments=16, poses_path=None, poses=None, cache=False,
-                 device='cuda', cache_dir=None, beam=None):
+                 device='cuda', cache_dir=None, beam=None, sweep=None):
         from .mesh import load_mesh
         from .scan_io import read_poses_csv
         from .utils import hashable
@@ -237,7 +344,13 @@ class RenderedMeshDataset(object):
         _check_pattern(tuple(fov), tuple(size), num_segments)
         if beam is not None and not isinstance(beam, BeamModel):
             raise TypeError('beam must be a BeamModel or None, got %s' % type(beam).__name__)
-        self.beam = beam
+        if sweep is not None and not isinstance(sweep, SweepModel):
+            raise TypeError('sweep must be a SweepModel or None, got %s' % type(sweep).__name__)
+        if sweep is not None and beam is not None:
+            raise ValueError('a moving sweep of finite beams is not provided: give sweep or beam, not both')
+        self.beam, self.sweep = beam, sweep
+        if sweep is not None:
+            self.cloud_dtype = _DT_SWEEP
         self.hash_name = ''
         if poses is None:
             if not poses_path:
@@ -323,6 +436,8 @@ class RenderedMeshDataset(object):
         params = os.path.join(self.dataset_dir(), 'hash_%s_size_%i_%i_fov_%.0f_%.0f' % (self.hash_name, *self.size, *self.fov))
         if self.beam is not None:
             params = os.path.join(params, self.beam.cache_key())
+        if self.sweep is not None:
+            params = os.path.join(params, self.sweep.cache_key())
         return os.path.join(params, 'cloud_%05i.bin' % id)
 
     def _render_all(self):
@@ -333,11 +448,17 @@ class RenderedMeshDataset(object):
             if self.cache:
                 for id in range(len(self.poses)):
                     if os.path.exists(self.cloud_path(id)):
-                        clouds[id] = np.fromfile(self.cloud_path(id), dtype=RenderedMeshDataset.cloud_dtype)
+                        clouds[id] = np.fromfile(self.cloud_path(id), dtype=self.cloud_dtype)
             todo = [id for id, c in enumerate(clouds) if c is None]
             if todo:
-                rendered = render_lidar_clouds(self.get_mesh(), self.poses[todo], fov=self.fov, size=self.size,
-                                               num_segments=self.num_segments, device=self.device, beam=self.beam)
+                if self.sweep is not None:
+                    # a sweep's twist comes from the next scan's pose: every pose goes into the cast, the clouds asked for are kept
+                    rendered = render_lidar_clouds(self.get_mesh(), self.poses, fov=self.fov, size=self.size,
+                                                   num_segments=self.num_segments, device=self.device, sweep=self.sweep)
+                    rendered = [rendered[id] for id in todo]
+                else:
+                    rendered = render_lidar_clouds(self.get_mesh(), self.poses[todo], fov=self.fov, size=self.size,
+                                                   num_segments=self.num_segments, device=self.device, beam=self.beam)
                 for id, c in zip(todo, rendered):
                     clouds[id] = c
                     if self.cache:
@@ -362,8 +483,10 @@ class MovingObjectDataset(object):
     dataset_name = 'moving_object'
     cloud_dtype = _DT
 
-    def __init__(self, static_mesh, objects, poses, size=(64, 512), fov=(45., 360.), num_segments=16, device='cuda', beam=None):
+    def __init__(self, static_mesh, objects, poses, size=(64, 512), fov=(45., 360.), num_segments=16, device='cuda', beam=None, sweep=None):
         from .mesh import TriangleMesh
+        if sweep is not None:
+            raise ValueError('MovingObjectDataset does not render moving sweeps (objects that move during a sweep are not provided)')
         _check_pattern(tuple(fov), tuple(size), num_segments)
         if beam is not None and not isinstance(beam, BeamModel):
             raise TypeError('beam must be a BeamModel or None, got %s' % type(beam).__name__)

@@ -400,6 +400,8 @@ def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     """The mapper over one sequence with the perturbed odometry of cfg.odom_cov (robot_data): prior[i] = slam[i-1] odom[i-1]^-1 odom[i],
     slam[0] = odom[0] = gt[0]; a failed registration keeps its prior and leaves the map and its probabilities as they are.  Every info
     has ``dynamic`` (map points with P >= cfg.slam_threshold_dynamic) and ``dyn`` (update_dynamic's counts, None when it did not run).
+    With cfg.slam_deskew a cloud that carries sweep times (the field ``t``) is de-skewed before anything else sees it, with the twist
+    of slam[i-1]^-1 prior[i] times cfg.slam_sweep_fraction (preproc.deskew_cloud; the poses hold at the sweep's start).
     Returns dict(slam, odom, gt [N,4,4], path_lengths [N], info [N dicts], ids)."""
     if cfg.slam not in SLAM:
         raise ValueError('unknown SLAM pipeline %r; available: %s' % (cfg.slam, ', '.join(SLAM)))
@@ -412,6 +414,13 @@ def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     infos = []
     for i, (cloud, _) in enumerate(items):
         prior = odom[0] if i == 0 else np.matmul(slam[i - 1], delta_transform(odom[i - 1], odom[i]))
+        if cfg.slam_deskew and 't' in (getattr(getattr(cloud, 'dtype', None), 'names', None) or ()):
+            # constant velocity: the sweep's twist is that of the motion from the last estimate to this prior (scan 0: the odometry's
+            # first step; a single scan: none), times the part of the period the sweep takes
+            from .preproc import deskew_cloud
+            from .sweep import motion_twist
+            step = delta_transform(slam[i - 1], prior) if i > 0 else (delta_transform(odom[0], odom[1]) if len(items) > 1 else np.eye(4))
+            cloud = deskew_cloud(cloud, float(cfg.slam_sweep_fraction) * motion_twist(step), device=mapper.device)
         scan = mapper.prepare(mapper_input(cloud, model, cfg))
         pose, info = mapper.register(scan, prior)
         mapper.last_dyn = None

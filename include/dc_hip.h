@@ -881,6 +881,34 @@ int dc_raycast_beams(const int32_t* child, const float* node_box, const double* 
                      int weight_kind, int detection, double tau, int min_hits, int32_t* face_out, double* depth_out, int32_t* n_hits_out,
                      int32_t* sub_face, double* sub_t, double* sub_w, dcStream_t stream);
 
+/* ---- moving-sweep rendering and de-skew (dc_raycast.hip, dc_sweep.hip; per-point arithmetic in csrc/dc_sweepmath.h; DESIGN
+ * "Moving-sweep rendering and de-skew") ----
+ * Scan s has a start pose T_s (world from sensor at sweep time tau = 0) and a twist (v_s, w_s) (twists DEVICE double [n_scans,6]:
+ * translation, then axis-angle; expressed in the start frame, covering the whole sweep, |w_s| <= pi: the caller's duty).  At sweep
+ * time tau the sensor stands at T_s D(tau), D(tau) = [Exp(tau w_s) | tau v_s]: rotation and translation interpolated separately,
+ * not the SE(3) exponential.  Per point, with a = tau w, th = |a|, all in fp64 without fused multiply-adds:
+ *   D(tau) x = x + A (a x x) + B (a x (a x x)) + tau v,   A = sin th / th,  B = (sin(th/2) / (th/2))^2 / 2;   th < 2^-26: A = 1, B = 1/2.
+ * Directions and normals take the rotation only.  tau (DEVICE double [n]) is any finite double per point; a tau that is not finite
+ * gives NaN outputs, and in the cast a miss (face -1, t +inf, inc NaN).  scan_offset DEVICE int64 [n_scans+1] as in dc_raycast_rays
+ * (empty scans allowed, the scan index is clamped); vps / dirs / points / normals DC_F32 | DC_F64 [n,3], fp32 converted exactly.
+ * dc_sweep_rays writes ray i in the start frame of its scan: origins_out = D(tau_i) vps[i], dirs_out = Exp(tau_i w) dirs[i], double
+ * [n,3].  n == 0 launches nothing. */
+int dc_sweep_rays(const void* vps, const void* dirs, int dtype, const double* tau, int64_t n, const int64_t* scan_offset, const double* twists,
+                  int n_scans, double* origins_out, double* dirs_out, dcStream_t stream);
+/* The cast of a moving sweep: every lane forms its ray as dc_sweep_rays does, takes it to the world with dc_raycast_rays' expressions
+ * (poses DEVICE double [n_scans,4,4] = the start poses) and goes through the same device function and the same incidence-angle
+ * expression with the ray's near clip (t_min_ray DEVICE double [n], or NULL: t_min), so face_out / t_out / inc_out are bit-equal to
+ * dc_raycast_rays on the rays dc_sweep_rays emits.  One launch for every scan and ray, no workspace, no atomics. */
+int dc_raycast_sweep(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n_faces,
+                     const void* vps, const void* dirs, int dtype, const double* tau, int64_t n, const int64_t* scan_offset,
+                     const double* poses, const double* twists, int n_scans, const double* t_min_ray, double t_min, int cull,
+                     int32_t* face_out, double* t_out, double* inc_out, dcStream_t stream);
+/* De-skew: x' = D(tau) x, vp' = D(tau) vp, n' = Exp(tau w) n take a point measured at sweep time tau into the start frame of its
+ * scan.  vps and normals may be NULL, each together with its output; outputs double [n,3]; with DC_F64 an output may be its input.
+ * The map is rigid per point: |x' - vp'| = |x - vp|, and the angle between x' - vp' and n' is that between x - vp and n. */
+int dc_deskew(const void* points, const void* vps, const void* normals, int dtype, const double* tau, int64_t n, const int64_t* scan_offset,
+              const double* twists, int n_scans, double* points_out, double* vps_out, double* normals_out, dcStream_t stream);
+
 /* ---- depth bias against the mesh (depth_correction_amd/csrc/dc_bias.hip, per-ray terms in dc_biasmath.h; DESIGN "Depth bias against
  * the mesh") ----
  * Per ray i of n: d = depth[i], g_est = inc_est[i] (DC_F32 | DC_F64 [n]; inc_est optional), the cast's face[i], t = t_true[i],
