@@ -170,6 +170,10 @@ _SIGNATURES = {
     'dc_raycast_sweep': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _f64, _i32, _vp, _vp, _vp,
                                 _vp]),
     'dc_deskew': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'dc_surfel_bvh_workspace_bytes': (_sz, [_i64]),
+    'dc_surfel_bvh_build': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'dc_surfel_cast_rays': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp,
+                                   _vp, _vp]),
     'dc_bias_workspace_bytes': (_sz, [_i32, _i32]),
     'dc_bias_accumulate': (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     'dc_mesh_closest': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp]),

@@ -276,6 +276,16 @@ class Config(object):
         self.bias_eval_bins = 18
         self.bias_eval_max_residual = None
         self.bias_eval_cull = True
+        # bias_eval_against: 'auto' (the mesh when the dataset has get_mesh(), else its survey), 'mesh' or 'survey' (a mesh dataset's
+        # survey is the one sampled from its mesh: the validation path).  Against a survey the rays are cast on its surfels
+        # (metrics.depth_bias' surfel_* arguments; DESIGN "Depth bias against a surveyed cloud"): radius None = scale x the distance
+        # to the k-th nearest other survey point; window in metres behind the first disk; the blend's normal gate in radians
+        self.bias_eval_against = 'auto'
+        self.bias_eval_surfel_radius = None
+        self.bias_eval_surfel_k = 10
+        self.bias_eval_surfel_scale = 1.0
+        self.bias_eval_surfel_window = 0.1
+        self.bias_eval_surfel_max_normal_angle = 0.7853981633974483      # pi / 4
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse

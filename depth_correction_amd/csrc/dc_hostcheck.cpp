@@ -12,6 +12,7 @@
 #include "dc_beammath.h"
 #include "dc_raymath.h"
 #include "dc_sweepmath.h"
+#include "dc_surfelmath.h"
 #include "dc_planemath.h"
 #include "dc_dynmath.h"
 #include "dc_rangeimage_math.h"
@@ -306,6 +307,54 @@ void dc_host_ray_test_pairs(const double* tri, const double* o, const double* d,
     hit[i] = f == 0;
   }
 }
+
+// ---- the surfel ray caster's per-ray arithmetic (dc_surfelmath.h) -------------------------------------------------------------------
+// leaf boxes of the disks (points / normals f64 [n,3], radii f64 [n]) -> box f32 [n,6], as surfel_fit_kernel writes them
+void dc_host_surfel_boxes(const double* points, const double* normals, const double* radii, int64_t n, float* box) {
+  for (int64_t i = 0; i < n; ++i) dc::disk_box(points + 3 * i, normals + 3 * i, radii[i], box + 6 * i);
+}
+
+// test_disk pair by pair: ray i (o / d f64 [n,3]) against row i of disk f64 [n,8] -> hit u8 [n], t / r2 f64 [n] as computed (whatever
+// the verdict)
+void dc_host_surfel_test_pairs(const double* disk, const double* o, const double* d, const double* t_min, int64_t n, uint8_t* hit, double* t,
+                               double* r2) {
+  for (int64_t i = 0; i < n; ++i) {
+    const dc::SurfelRay r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+    hit[i] = dc::disk_hit(disk + dc::kDiskRow * i, r, t_min[i], t[i], r2[i]) ? 1 : 0;
+  }
+}
+
+// The oracle of dc_surfel_cast_rays: both passes over every row of disk [n_disks,8] in row order (index [n_disks] the survey index each
+// row reports, ascending for the tie rule to be the kernel's), no tree.
+void dc_host_surfel_cast_brute(const double* disk, const int32_t* index, int64_t n_disks, const double* o, const double* d, int64_t n_rays,
+                               double t_min, double window, double min_cos, int32_t* index_out, double* t_first_out, double* t_out,
+                               double* inc_out, int32_t* count_out) {
+  for (int64_t i = 0; i < n_rays; ++i) {
+    const dc::SurfelRay r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+    dc::SurfelHit best;
+    best.t = INFINITY;
+    best.r2 = 0.0;
+    best.index = -1;
+    best.leaf = -1;
+    for (int64_t j = 0; j < n_disks; ++j) dc::test_disk(disk + dc::kDiskRow * j, index[j], (int32_t)j, r, t_min, best);
+    dc::SurfelBlend blend;
+    dc::blend_init(blend);
+    const double* first = disk + dc::kDiskRow * (int64_t)(best.leaf >= 0 ? best.leaf : 0);
+    if (best.leaf >= 0 && window > 0.0)
+      for (int64_t j = 0; j < n_disks; ++j)
+        dc::blend_disk(disk + dc::kDiskRow * j, j == best.leaf, first, r, t_min, best.t, best.t + window, min_cos, blend);
+    index_out[i] = best.index;
+    t_first_out[i] = best.t;
+    dc::surfel_finish(best, first, blend, r, t_out[i], inc_out[i], count_out[i]);
+  }
+}
+
+// acos01 of x [n], and the header's error counts (units of 2^-52) for k members
+void dc_host_surfel_acos(const double* x, int64_t n, double* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = dc::acos01(x[i]);
+}
+double dc_host_surfel_t_err(int k, double t, double t1) { return dc::surfel_t_err(k, t, t1); }
+double dc_host_surfel_cos_err(int k, double kappa) { return dc::surfel_cos_err(k, kappa); }
 
 // ---- plane neighbourhoods (dc_planemath.h) -------------------------------------------------------------------------------------------
 namespace {

@@ -35,10 +35,16 @@
 //
 // dc_raycast_sweep renders a moving sweep: every lane first forms its ray at its own sweep time (dc_sweepmath.h) in the start frame
 // of its scan, then is one of raycast_rays_kernel's lanes; dc_sweep_rays writes those rays out instead of casting them.
+//
+// dc_surfel_bvh_build / dc_surfel_cast_rays cast the same measured rays against a surveyed cloud, every survey point an oriented disk
+// (dc_surfelmath.h): the same LBVH over the disks' boxes (karras_kernel as it is), a second walker next to cast_ray (surfel_walk) with
+// the disk test at the leaves, and a second walk that blends the disks within a depth window behind the first hit.  cast_ray and the
+// five kernels above are untouched.
 #include "dc_common.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
 #include "dc_sweepmath.h"
+#include "dc_surfelmath.h"
 #include "dc_hostutil.h"
 #include "dc_sort.h"
 #include "../../include/dc_hip.h"
@@ -509,6 +515,155 @@ __global__ void __launch_bounds__(kCastBlock) raycast_sweep_kernel(const int32_t
   inc_out[g] = inc;
 }
 
+// ---- surfels: a surveyed cloud as oriented disks (dc_surfelmath.h) ------------------------------------------------------------------
+using dc::SurfelBlend;
+using dc::SurfelHit;
+using dc::SurfelRay;
+using dc::kDiskRow;
+
+__global__ void __launch_bounds__(kBuildBlock) surfel_morton_kernel(const double* __restrict__ points, int64_t n, SceneBox box,
+                                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (i >= n) return;
+  uint32_t code = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) code |= expand_bits10(quantise10(points[3 * i + a], box.lo[a], box.scale[a])) << (2 - a);
+  keys[i] = ((uint64_t)code << 32) | (uint64_t)(uint32_t)i;
+  vals[i] = (uint32_t)i;
+}
+
+// fit_kernel with disk_box at the leaves; leaf i also writes its disk's row of leaf_disk
+__global__ void __launch_bounds__(kBuildBlock) surfel_fit_kernel(const double* __restrict__ points, const double* __restrict__ normals,
+                                                                 const double* __restrict__ radii, int64_t n,
+                                                                 const int32_t* __restrict__ leaf_index, const int32_t* __restrict__ child,
+                                                                 const int32_t* __restrict__ parent, int32_t* __restrict__ counter,
+                                                                 float* node_box, double* __restrict__ leaf_disk) {
+  const int64_t i = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t s = leaf_index[i];
+  double p[3], nv[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p[a] = points[3 * s + a];
+    nv[a] = normals[3 * s + a];
+  }
+  const double rho = radii[s];
+  double* row = leaf_disk + kDiskRow * i;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    row[a] = p[a];
+    row[3 + a] = nv[a];
+  }
+  row[6] = rho * rho;
+  row[7] = 0.0;
+  int64_t node = (n - 1) + i;
+  dc::disk_box(p, nv, rho, node_box + 6 * node);
+  node = parent[node];
+  while (node >= 0) {
+    __threadfence();                                        // this child's box is visible before the counter says so
+    if (atomicAdd(&counter[node], 1) == 0) return;          // the sibling is still on its way: it fits the parent
+    __threadfence();
+    const int64_t a0 = child[2 * node], b0 = child[2 * node + 1];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      node_box[6 * node + a] = fminf(load_box(node_box + 6 * a0 + a), load_box(node_box + 6 * b0 + a));
+      node_box[6 * node + 3 + a] = fmaxf(load_box(node_box + 6 * a0 + 3 + a), load_box(node_box + 6 * b0 + 3 + a));
+    }
+    node = parent[node];
+  }
+}
+
+// cast_ray's walk over a tree of disks.  Pass 1 (kBlend false) keeps the closest hit in `best` and prunes with it.  Pass 2 (kBlend
+// true) adds every member of the blend to `blend` under the fixed bound prune_far(t_end): prune_far does not decrease, and a member's
+// t is at most t_end, so property 1 keeps every member's boxes.  The order of the walk depends on the tree and the ray alone.
+template <bool kBlend>
+__device__ __forceinline__ void surfel_walk(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                            const double* __restrict__ leaf_disk, const int32_t* __restrict__ leaf_index, int64_t n,
+                                            const SurfelRay& sr, const Ray32& ray, double tmin, SurfelHit& best, double t_end, double min_cos,
+                                            SurfelBlend& blend, int32_t* stack, int lane) {
+  const float t_fixed = kBlend ? dc::prune_far(t_end) : INFINITY;
+  const double* first = leaf_disk + kDiskRow * (int64_t)(kBlend ? best.leaf : 0);
+  int sp = 0;
+  int64_t node = 0;
+  bool live = box_entry(node_box, ray, t_fixed) < INFINITY;
+  while (live) {
+    if (node >= n - 1) {
+      const int64_t leaf = node - (n - 1);
+      if (kBlend) dc::blend_disk(leaf_disk + kDiskRow * leaf, leaf == best.leaf, first, sr, tmin, best.t, t_end, min_cos, blend);
+      else dc::test_disk(leaf_disk + kDiskRow * leaf, leaf_index[leaf], (int32_t)leaf, sr, tmin, best);
+    } else {
+      const float t_far = kBlend ? t_fixed : dc::prune_far(best.t);
+      const int64_t ca = child[2 * node], cb = child[2 * node + 1];
+      const float ta = box_entry(node_box + 6 * ca, ray, t_far), tb = box_entry(node_box + 6 * cb, ray, t_far);
+      if (ta < INFINITY || tb < INFINITY) {
+        if (ta < INFINITY && tb < INFINITY) {
+          const bool a_first = ta <= tb;
+          if (sp < kStackDepth) stack[sp * kCastBlock + lane] = (int32_t)(a_first ? cb : ca);    // sp < 64 always (depth <= 63)
+          ++sp;
+          node = a_first ? ca : cb;
+        } else {
+          node = ta < INFINITY ? ca : cb;
+        }
+        continue;
+      }
+    }
+    live = false;
+    while (sp > 0) {
+      --sp;
+      node = sp < kStackDepth ? stack[sp * kCastBlock + lane] : 0;
+      if (box_entry(node_box + 6 * node, ray, kBlend ? t_fixed : dc::prune_far(best.t)) < INFINITY) { live = true; break; }
+    }
+  }
+}
+
+// dc_surfel_cast_rays: the ray of raycast_rays_kernel, the closest disk, then (window > 0) the blend over the disks behind it
+template <typename T>
+__global__ void __launch_bounds__(kCastBlock) surfel_cast_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
+                                                                 const double* __restrict__ leaf_disk, const int32_t* __restrict__ leaf_index,
+                                                                 int64_t n, const T* __restrict__ vps, const T* __restrict__ dirs,
+                                                                 int64_t total, const int64_t* __restrict__ scan_offset,
+                                                                 const double* __restrict__ poses, int n_scans, double t_min, double window,
+                                                                 double min_cos, int32_t* __restrict__ index_out,
+                                                                 double* __restrict__ t_first_out, double* __restrict__ t_out,
+                                                                 double* __restrict__ inc_out, int32_t* __restrict__ count_out) {
+  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  const int lane = threadIdx.x;
+  const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
+  if (g >= total) return;
+  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
+  }
+  const double* M = poses + 16 * (int64_t)lo;
+  const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
+  const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
+  SurfelRay sr;
+  pose_dir(M, s0, s1, s2, sr.d0, sr.d1, sr.d2);
+  pose_point(M, v0, v1, v2, sr.o0, sr.o1, sr.o2);
+  Ray64 ray64;
+  Ray32 ray;
+  dc::ray_setup(sr.d0, sr.d1, sr.d2, sr.o0, sr.o1, sr.o2, ray64, ray);
+  SurfelHit best;
+  best.t = INFINITY;
+  best.r2 = 0.0;
+  best.index = -1;
+  best.leaf = -1;
+  SurfelBlend blend;
+  dc::blend_init(blend);
+  surfel_walk<false>(child, node_box, leaf_disk, leaf_index, n, sr, ray, t_min, best, 0.0, 0.0, blend, stack, lane);
+  if (best.leaf >= 0 && window > 0.0)
+    surfel_walk<true>(child, node_box, leaf_disk, leaf_index, n, sr, ray, t_min, best, best.t + window, min_cos, blend, stack, lane);
+  double t, inc;
+  int32_t count;
+  dc::surfel_finish(best, leaf_disk + kDiskRow * (int64_t)(best.leaf >= 0 ? best.leaf : 0), blend, sr, t, inc, count);
+  index_out[g] = best.index;
+  t_first_out[g] = best.t;
+  t_out[g] = t;
+  inc_out[g] = inc;
+  count_out[g] = count;
+}
+
 // the checks dc_beam_subrays and dc_raycast_beams share; fills `pat`
 inline bool beam_pattern_ok(const double* pattern, int n_samples, double r0, double spread, BeamPattern* pat) {
   if (!pattern || n_samples < 1 || n_samples > DC_BEAM_MAX_SAMPLES) return false;
@@ -690,6 +845,68 @@ int dc_raycast_sweep(const int32_t* child, const float* node_box, const double* 
     raycast_sweep_kernel<double><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
         child, node_box, leaf_tri, leaf_face, n_faces, (const double*)vps, (const double*)dirs, tau, n, scan_offset, poses, twists, n_scans,
         t_min_ray, t_min, cull, face_out, t_out, inc_out);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+size_t dc_surfel_bvh_workspace_bytes(int64_t n) { return dc_bvh_workspace_bytes(n); }
+
+int dc_surfel_bvh_build(const double* points, const double* normals, const double* radii, int64_t n, const double* scene_box,
+                        int32_t* leaf_index, int32_t* child, int32_t* parent, float* node_box, double* leaf_disk, void* ws, size_t ws_bytes,
+                        dcStream_t stream_) {
+  if (n < 1 || n > (int64_t)INT32_MAX / 2 || !points || !normals || !radii || !scene_box || !leaf_index || (n > 1 && !child) || !parent ||
+      !node_box || !leaf_disk)                                              // one disk: the root is a leaf and child has no rows
+    return DC_ERR_ARG;
+  if (!ws || ws_bytes < dc_surfel_bvh_workspace_bytes(n)) return DC_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  SceneBox box;
+  for (int a = 0; a < 3; ++a) {
+    const double ext = scene_box[3 + a] - scene_box[a];
+    if (!(ext >= 0.0)) return DC_ERR_ARG;
+    box.lo[a] = scene_box[a];
+    box.scale[a] = ext > 0.0 ? 1024.0 / ext : 0.0;
+  }
+  dc::Carver c(ws);
+  uint64_t* keys_in = c.take<uint64_t>(n);
+  uint64_t* keys_out = c.take<uint64_t>(n);
+  uint32_t* vals_in = c.take<uint32_t>(n);
+  int32_t* counter = c.take<int32_t>(n);
+  const size_t sort_bytes = dc::sort_pairs_bytes((size_t)n, 64);
+  void* sort_tmp = c.take<char>(sort_bytes);
+  DC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t), stream));                    // the root has no parent
+  DC_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t) * n, stream));
+  surfel_morton_kernel<<<grid_of(n, kBuildBlock), kBuildBlock, 0, stream>>>(points, n, box, keys_in, vals_in);
+  DC_HIP(hipGetLastError());
+  DC_HIP(dc::sort_pairs_u64(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, leaf_index, (size_t)n, 0, 62, stream));
+  if (n > 1) {
+    karras_kernel<<<grid_of(n - 1, kBuildBlock), kBuildBlock, 0, stream>>>(keys_out, n, child, parent);
+    DC_HIP(hipGetLastError());
+  }
+  surfel_fit_kernel<<<grid_of(n, kBuildBlock), kBuildBlock, 0, stream>>>(points, normals, radii, n, leaf_index, child, parent, counter,
+                                                                        node_box, leaf_disk);
+  DC_HIP(hipGetLastError());
+  return DC_OK;
+}
+
+int dc_surfel_cast_rays(const int32_t* child, const float* node_box, const double* leaf_disk, const int32_t* leaf_index, int64_t n_disks,
+                        const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                        double t_min, double window, double min_cos, int32_t* index_out, double* t_first_out, double* t_out, double* inc_out,
+                        int32_t* count_out, dcStream_t stream) {
+  if (n_disks < 1 || n < 0 || n_scans < 0 || !node_box || !leaf_disk || !leaf_index || (n_disks > 1 && !child) || !(t_min == t_min) ||
+      !(window >= 0.0) || !(min_cos >= 0.0) || !(min_cos < 1.0))
+    return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (n == 0) return DC_OK;
+  if (n_scans < 1 || !vps || !dirs || !scan_offset || !poses || !index_out || !t_first_out || !t_out || !inc_out || !count_out)
+    return DC_ERR_ARG;
+  if (dtype == DC_F32)
+    surfel_cast_kernel<float><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_disk, leaf_index, n_disks, (const float*)vps, (const float*)dirs, n, scan_offset, poses, n_scans, t_min, window,
+        min_cos, index_out, t_first_out, t_out, inc_out, count_out);
+  else
+    surfel_cast_kernel<double><<<grid_of(n, kCastBlock), kCastBlock, 0, (hipStream_t)stream>>>(
+        child, node_box, leaf_disk, leaf_index, n_disks, (const double*)vps, (const double*)dirs, n, scan_offset, poses, n_scans, t_min,
+        window, min_cos, index_out, t_first_out, t_out, inc_out, count_out);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

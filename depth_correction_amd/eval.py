@@ -526,8 +526,19 @@ def write_bias_curve_csv(path, name, res):
     append(path, ''.join(lines))
 
 
+def _bias_truth(ds, name, cfg):
+    """What eval_bias casts the rays of ``ds`` against (cfg.bias_eval_against): its mesh, or its surveyed cloud."""
+    against = cfg.bias_eval_against
+    if against == 'mesh' or (against == 'auto' and callable(getattr(ds, 'get_mesh', None))):
+        return _dataset_mesh(ds, name, 'eval_bias')
+    survey = _dataset_survey(ds, name, cfg, who='eval_bias', required=against == 'survey')
+    return survey if survey is not None else _dataset_mesh(ds, name, 'eval_bias')          # 'auto' with neither: raises
+
+
 def eval_bias(cfg: Config, test_datasets=None, model=None):
-    """Depth bias of every test sequence against its dataset's mesh (what scripts/bias_estimation and depth_bias.py measure with a
+    """Depth bias of every test sequence against its dataset's ground truth (cfg.bias_eval_against: the mesh, or the surveyed cloud
+    through its surfels -- metrics.depth_bias, DESIGN "Depth bias against a surveyed cloud" -- for a dataset such as the FEE corridor
+    that has a survey and no mesh).  Against the mesh (what scripts/bias_estimation and depth_bias.py measure with a
     board; DESIGN "Depth bias against the mesh"): each scan goes through preproc.filtered_cloud and local_feature_cloud -- the
     estimated incidence angles and the planarity mask train() sees -- and its rays are cast in the mesh frame with the poses the
     dataset yields.  Only ground-truth poses are meaningful here: with any other pose the difference to the mesh measures the pose
@@ -539,8 +550,10 @@ def eval_bias(cfg: Config, test_datasets=None, model=None):
     from .io import append
     from .metrics import depth_bias, fit_bias
     from .preproc import filtered_cloud
+    if cfg.bias_eval_against not in ('auto', 'mesh', 'survey'):
+        raise ValueError("bias_eval_against must be 'auto', 'mesh' or 'survey', got %r" % (cfg.bias_eval_against,))
     test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
-    meshes = [_dataset_mesh(ds, name, 'eval_bias') for name, ds in zip(test_names, test_datasets)]
+    meshes = [_bias_truth(ds, name, cfg) for name, ds in zip(test_names, test_datasets)]
     if torch.device(cfg.device).type != 'cuda':
         raise RuntimeError('eval_bias needs a GPU (cfg.device %s): depth_correction_amd has no CPU path' % (cfg.device,))
     results = []
@@ -550,7 +563,9 @@ def eval_bias(cfg: Config, test_datasets=None, model=None):
             clouds.append(local_feature_cloud(filtered_cloud(cloud, cfg), cfg))
             poses.append(np.asarray(pose, dtype=np.float64))
         res = depth_bias(clouds, np.stack(poses), mesh, model=model, bins=cfg.bias_eval_bins, max_residual=cfg.bias_eval_max_residual,
-                         cull=cfg.bias_eval_cull)
+                         cull=cfg.bias_eval_cull, surfel_radius=cfg.bias_eval_surfel_radius, surfel_k=cfg.bias_eval_surfel_k,
+                         surfel_scale=cfg.bias_eval_surfel_scale, surfel_window=cfg.bias_eval_surfel_window,
+                         surfel_max_normal_angle=cfg.bias_eval_surfel_max_normal_angle)
         fit = res['fit'] = fit_bias(res, res['fit_class'], res['fit_exponent'])
         res['name'] = name
         b, a = res['before']['overall'], (res['after'] or {}).get('overall')

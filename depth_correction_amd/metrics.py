@@ -211,9 +211,11 @@ def _fit_basis(model, fit_class, fit_exponent):
     return fit_class, [float(e) for e in fit_exponent]
 
 
-def depth_bias(clouds, poses, mesh, model=None, bins=18, max_residual=None, cull=True, fit_class=None, fit_exponent=None):
-    """Depth error of every ray of the DepthClouds ``clouds`` (one sequence, on a GPU, sensor frame) against ``mesh``
-    (mesh.TriangleMesh, the frame of ``poses`` [S,4,4]: world from sensor; only ground-truth poses give a meaningful answer), as a
+def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cull=True, fit_class=None, fit_exponent=None,
+               surfel_radius=None, surfel_k=10, surfel_scale=1.0, surfel_window=0.1, surfel_max_normal_angle=math.pi / 4):
+    """Depth error of every ray of the DepthClouds ``clouds`` (one sequence, on a GPU, sensor frame) against ``truth``
+    (mesh.TriangleMesh or survey.SurveyCloud, the frame of ``poses`` [S,4,4]: world from sensor; only ground-truth poses give a
+    meaningful answer), as a
     function of the TRUE incidence angle.  The rays (vps, dirs) are cast once (ops.raycast_rays: true depth t and true angle per
     ray); the clouds' ``mask`` and ``inc_angles`` are used when present.  Statistics (bias_statistics) are taken of the depths as
     given -> ``before`` and, with a ``model``, of the depths of ``model(cloud)`` -> ``after`` (else None), in ``bins`` equal bins of
@@ -221,7 +223,14 @@ def depth_bias(clouds, poses, mesh, model=None, bins=18, max_residual=None, cull
     missed what it holds) are counted and left out.  ``before['out']`` / ``after['out']`` keep the raw sums with the normal equations
     of fit_bias for ``fit_class`` / ``fit_exponent`` (default: the model's class and exponents when it is a polynomial, else
     ScaledPolynomial with [2, 4]).  ``face`` / ``t`` / ``inc`` are the cast's per-ray outputs, ``inc_est`` / ``mask`` and
-    ``before['depth']`` / ``after['depth']`` the per-ray inputs of the sums, all scan-major in the order of ``clouds``."""
+    ``before['depth']`` / ``after['depth']`` the per-ray inputs of the sums, all scan-major in the order of ``clouds``.
+
+    Against a SurveyCloud the rays are cast on its surfels (SurveyCloud.surfels(radius=``surfel_radius``, k=``surfel_k``,
+    scale=``surfel_scale``); ops.surfel_cast_rays): ``t`` / ``inc`` are the blend of the disks within ``surfel_window`` metres
+    behind the first one whose normals lie within ``surfel_max_normal_angle`` of its normal -- the first disk alone is biased
+    towards the sensor by the survey's noise, growing with the incidence angle (DESIGN "Depth bias against a surveyed cloud") --,
+    ``face`` holds the survey index of the first disk, and the result gains ``t_first`` (its depth) and ``count`` (disks blended per
+    ray).  Disks are two-sided: ``cull`` is ignored."""
     clouds = list(clouds)
     if not clouds:
         raise ValueError('depth_bias needs at least one cloud')
@@ -236,8 +245,18 @@ def depth_bias(clouds, poses, mesh, model=None, bins=18, max_residual=None, cull
                         device=dev).contiguous()
     if T.shape[0] != len(clouds):
         raise ValueError('%d clouds but %d poses' % (len(clouds), T.shape[0]))
-    bvh = mesh.on_device(dev)[3]
-    face, t, inc = ops.raycast_rays(bvh, vps, dirs, offsets, T, t_min=0.0, cull=cull)
+    extra = {}
+    if hasattr(truth, 'surfels'):
+        angle = float(surfel_max_normal_angle)
+        if not 0.0 < angle <= math.pi / 2:
+            raise ValueError('surfel_max_normal_angle must lie in (0, pi/2], got %r' % (surfel_max_normal_angle,))
+        bvh = truth.surfels(dev, radius=surfel_radius, k=surfel_k, scale=surfel_scale)
+        face, t_first, t, inc, count = ops.surfel_cast_rays(bvh, vps, dirs, offsets, T, t_min=0.0, window=surfel_window,
+                                                            min_cos=max(math.cos(angle), 0.0))
+        extra = dict(t_first=t_first, count=count)
+    else:
+        bvh = truth.on_device(dev)[3]
+        face, t, inc = ops.raycast_rays(bvh, vps, dirs, offsets, T, t_min=0.0, cull=cull)
     inc_est = _cat_field(clouds, 'inc_angles', 0)
     mask = None
     if any(c.mask is not None for c in clouds):
@@ -256,6 +275,7 @@ def depth_bias(clouds, poses, mesh, model=None, bins=18, max_residual=None, cull
 
     res = dict(bins=int(bins), bin_edges=torch.linspace(0.0, math.pi / 2, int(bins) + 1, dtype=torch.float64), fit_class=fit_class,
                fit_exponent=fit_exponent, face=face, t=t, inc=inc, inc_est=inc_est, mask=mask, before=stats(clouds), after=None)
+    res.update(extra)
     if model is not None:
         with torch.no_grad():
             res['after'] = stats([model(c) for c in clouds])

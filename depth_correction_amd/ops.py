@@ -1168,6 +1168,90 @@ def raycast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, cull=True):
     return face, t, inc
 
 
+@on_device
+def surfel_bvh_build(points, normals, radii, scene_box):
+    """LBVH over the surfels of a surveyed cloud: the two-sided disks (points[i], normals[i], radii[i]), f64 [M,3] / [M,3] / [M]
+    (radii finite and > 0 and normals finite and non-zero, checked here), in the box ``scene_box`` (6 floats: lo xyz, hi xyz) ->
+    survey.SurfelBVH (leaf_index i32 [M], child i32 [M-1,2], parent i32 [2M-1], node_box f32 [2M-1,6], leaf_disk f64 [M,8])."""
+    import numpy as np
+    from .survey import SurfelBVH
+    need(points, (None, 3), dtype=torch.float64, name='points')
+    dev = points.device
+    m = points.shape[0]
+    need(normals, (m, 3), dtype=torch.float64, name='normals', device=dev)
+    need(radii, (m,), dtype=torch.float64, name='radii', device=dev)
+    if m == 0:
+        raise ValueError('surfel_bvh_build needs at least one point')
+    if not bool((torch.isfinite(radii) & (radii > 0)).all()):
+        raise ValueError('surfel radii must be finite and > 0')
+    if not bool(torch.isfinite(points).all()):
+        raise ValueError('surfel points must be finite')
+    if not bool((torch.isfinite(normals).all(dim=1) & (normals != 0).any(dim=1)).all()):
+        raise ValueError('surfel normals must be finite and not zero')
+    box = np.ascontiguousarray(np.asarray(scene_box, dtype=np.float64).reshape(6))
+    if not (np.isfinite(box).all() and (box[3:] >= box[:3]).all()):
+        raise ValueError('scene_box must be finite with hi >= lo, got %s' % box)
+    leaf_index = torch.empty((m,), dtype=torch.int32, device=dev)
+    child = torch.empty((max(m - 1, 0), 2), dtype=torch.int32, device=dev)
+    parent = torch.empty((2 * m - 1,), dtype=torch.int32, device=dev)
+    node_box = torch.empty((2 * m - 1, 6), dtype=torch.float32, device=dev)
+    leaf_disk = torch.empty((m, 8), dtype=torch.float64, device=dev)
+    nbytes = lib().dc_surfel_bvh_workspace_bytes(m)
+    ws = _ws(nbytes, dev)
+    check(lib().dc_surfel_bvh_build(ptr(points), ptr(normals), ptr(radii), m, box.ctypes.data_as(ctypes.c_void_p), ptr(leaf_index),
+                                    ptr(child) if m > 1 else None, ptr(parent), ptr(node_box), ptr(leaf_disk), ptr(ws), nbytes,
+                                    stream_ptr()), 'dc_surfel_bvh_build')
+    return SurfelBVH(leaf_index, child, parent, node_box, leaf_disk)
+
+
+SURFEL_MIN_COS = 0.7071067811865476          # cos(pi / 4): the default normal gate of the surfel blend
+
+
+@on_device
+def surfel_cast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, window=0.0, min_cos=SURFEL_MIN_COS):
+    """The rays of raycast_rays (same arguments, same checks) against a survey.SurfelBVH -> (index i32 [N] the survey index of the
+    closest disk (-1 = miss), t_first f64 [N] its t (inf), t f64 [N] the blended depth, inc f64 [N] the incidence angle on the
+    blended normal (NaN on a miss), count i32 [N] the number of blended disks (0 on a miss)).  The blend takes the disks the ray hits
+    within ``window`` (>= 0, along the ray in units of |dirs[i]|) behind the first hit whose normal lies within acos(``min_cos``)
+    (0 <= min_cos < 1) of the first hit's, weighted 1 - r^2 / rho^2; window = 0: t = t_first, inc on the first disk, count 1.
+    One launch (dc_surfel_cast_rays)."""
+    dev = bvh.leaf_index.device
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n = dirs.shape[0]
+    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
+    code = dtype_code(dirs)
+    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
+    s = poses.shape[0]
+    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
+        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)       # as raycast_rays: not read back
+    else:
+        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
+        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    if n and s < 1:
+        raise ValueError('rays need at least one pose')
+    tm, win, mc = float(t_min), float(window), float(min_cos)
+    if tm != tm:
+        raise ValueError('t_min must not be NaN')
+    if not win >= 0.0:
+        raise ValueError('window must be >= 0, got %r' % (window,))
+    if not 0.0 <= mc < 1.0:
+        raise ValueError('min_cos must lie in [0, 1), got %r' % (min_cos,))
+    index = torch.empty((n,), dtype=torch.int32, device=dev)
+    t_first = torch.empty((n,), dtype=torch.float64, device=dev)
+    t = torch.empty((n,), dtype=torch.float64, device=dev)
+    inc = torch.empty((n,), dtype=torch.float64, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return index, t_first, t, inc, count
+    off = off.to(dev)
+    m = bvh.n_disks
+    check(lib().dc_surfel_cast_rays(ptr(bvh.child) if m > 1 else None, ptr(bvh.node_box), ptr(bvh.leaf_disk), ptr(bvh.leaf_index), m,
+                                    ptr(vps), ptr(dirs), code, n, ptr(off), ptr(poses), s, tm, win, mc, ptr(index), ptr(t_first), ptr(t),
+                                    ptr(inc), ptr(count), stream_ptr()), 'dc_surfel_cast_rays')
+    return index, t_first, t, inc, count
+
+
 def _beam_pattern_arg(pattern, r0, spread, power_of_two):
     """The footprint pattern as a host float64 [S,3] array, checked the way the library checks it."""
     import numpy as np

@@ -14,10 +14,27 @@ import warnings
 import numpy as np
 import torch
 
-__all__ = ['SurveyCloud', 'SurveyOnDevice', 'mesh_survey', 'DEFAULT_SAMPLES', 'SURVEY_SEED']
+__all__ = ['SurfelBVH', 'SurveyCloud', 'SurveyOnDevice', 'mesh_survey', 'DEFAULT_SAMPLES', 'SURVEY_SEED']
 
 DEFAULT_SAMPLES = 200000       # Config.cloud_samples
 SURVEY_SEED = 135              # the fixed seed of the surveys the mesh datasets sample
+
+
+class SurfelBVH(object):
+    """Device arrays of ``dc_surfel_bvh_build`` (layout: include/dc_hip.h): the survey's points as oriented disks, for
+    ops.surfel_cast_rays.  ``radii`` f64 [M] are the radii it was built with (survey order), when the builder kept them."""
+
+    def __init__(self, leaf_index, child, parent, node_box, leaf_disk, radii=None):
+        self.leaf_index, self.child, self.parent, self.node_box, self.leaf_disk = leaf_index, child, parent, node_box, leaf_disk
+        self.radii = radii
+
+    @property
+    def n_disks(self):
+        return self.leaf_index.shape[0]
+
+    @property
+    def device(self):
+        return self.leaf_index.device
 
 
 class SurveyOnDevice(object):
@@ -82,6 +99,7 @@ class SurveyCloud(object):
         self.points = points.contiguous()
         self.normals = (normals / norm).contiguous()
         self._device = {}
+        self._surfels = {}
 
     def __len__(self):
         return self.points.shape[0]
@@ -166,6 +184,40 @@ class SurveyCloud(object):
             p = self.points.to(device).contiguous()
             n = self.normals.to(device).contiguous()
             got = self._device[device] = SurveyOnDevice(p, n, ops.knn_grid_build(p, self.MIN_QUERIES, 1))
+        return got
+
+    def surfels(self, device, radius=None, k=10, scale=1.0):
+        """SurfelBVH of the survey on ``device`` (a GPU), built once per device and argument set: every point with its normal is a
+        disk (DESIGN "Depth bias against a surveyed cloud").  A float ``radius`` is every disk's; None gives point i ``scale`` times
+        the distance to its ``k``-th nearest other survey point (ops.knn on the survey itself), so that under uniform sampling about
+        k disks cover every surface point."""
+        if radius is not None:
+            radius = float(radius)
+            if not (radius > 0.0 and radius < float('inf')):
+                raise ValueError('surfel radius must be finite and > 0, got %r' % (radius,))
+        dev = self.on_device(device)
+        if radius is not None:
+            key = (dev.device, radius, None, None)
+        else:
+            k, scale = int(k), float(scale)
+            if not 1 <= k <= 63:
+                raise ValueError('surfel k must be in 1..63, got %r' % (k,))
+            if not (scale > 0.0 and scale < float('inf')):
+                raise ValueError('surfel scale must be finite and > 0, got %r' % (scale,))
+            if len(self) <= k:
+                raise ValueError('a survey of %d points has no %d-th nearest other point: give a radius' % (len(self), k))
+            key = (dev.device, None, k, scale)
+        got = self._surfels.get(key)
+        if got is None:
+            from . import ops
+            if radius is not None:
+                radii = torch.full((dev.n,), radius, dtype=torch.float64, device=dev.device)
+            else:
+                dist, _ = ops.knn(dev.points, k + 1)                    # column 0 is the point itself
+                radii = (scale * dist[:, k]).contiguous()
+            box = torch.cat([dev.points.amin(dim=0), dev.points.amax(dim=0)]).cpu().numpy()
+            got = self._surfels[key] = ops.surfel_bvh_build(dev.points, dev.normals, radii, box)
+            got.radii = radii
         return got
 
 

@@ -909,6 +909,35 @@ int dc_raycast_sweep(const int32_t* child, const float* node_box, const double* 
 int dc_deskew(const void* points, const void* vps, const void* normals, int dtype, const double* tau, int64_t n, const int64_t* scan_offset,
               const double* twists, int n_scans, double* points_out, double* vps_out, double* normals_out, dcStream_t stream);
 
+/* ---- surfel ray casting: the rays of measured clouds against a surveyed cloud (csrc/dc_surfelmath.h) ----
+ * Survey point i with its normal and a radius is the two-sided disk (p_i, n_i, rho_i > 0); n is used as given.  A ray o + t d hits
+ * it when den = n . d != 0, t = n . (p - o) / den lies in (t_min, inf) and |t d - (p - o)|^2 <= rho^2 (the rim counts; anything
+ * not finite is a miss).  The closest hit is the smallest t, on equal t the lower survey index, independent of the tree.
+ *
+ * dc_surfel_bvh_build: the LBVH of dc_bvh_build over the disks (Morton key of the centre in scene_box HOST double [6] with the index
+ * in the low word, the same sort and node numbering, deterministic); the leaf boxes are the disks' exact spans
+ * rho sqrt(n_b^2 + n_c^2) / |n| per axis, grown by 2^-48 (|p|_1 + rho) and rounded outward to fp32, so no box rejects a disk the
+ * test accepts.  points / normals DEVICE double [n,3], radii DEVICE double [n] (finite and > 0: the caller's duty) -> leaf_index
+ * int32 [n] (the survey index of leaf i), child int32 [n-1,2] (may be NULL for n = 1), parent int32 [2n-1], node_box float
+ * [2n-1,6], leaf_disk double [n,8] = (p, n, rho^2, 0) per leaf.  ws: dc_surfel_bvh_workspace_bytes(n).
+ *
+ * dc_surfel_cast_rays: one lane per ray with dc_raycast_rays' arguments and expressions for the ray (scan by clamped bisection of
+ * scan_offset DEVICE int64 [n_scans+1], poses DEVICE double [n_scans,4,4], vps / dirs float | double [n,3]).  Pass 1 finds the
+ * closest hit: index_out (-1 = miss), t_first_out (+inf).  With window > 0 (units of |d| along the ray) a second walk blends the
+ * disks with a hit, t <= t_first + window and |n_i . n_1| / (|n_i| |n_1|) >= min_cos (in [0, 1); the first hit always belongs):
+ * weights w = 1 - r^2 / rho^2, t_out = t_first + sum w (t - t_first) / sum w, the normal sum w s_i n_i / |n_i| with s_i = +-1 towards
+ * n_1, inc_out the incidence angle on it, count_out the number of members.  window = 0: t_out = t_first_out, inc_out on n_1,
+ * count_out = 1.  A miss gives t_out +inf, inc_out NaN, count_out 0.  The sums run in the order of the walk, a function of the tree
+ * and the ray alone: bit-reproducible.  n = 0 returns DC_OK.  No workspace, no atomics. */
+size_t dc_surfel_bvh_workspace_bytes(int64_t n);
+int dc_surfel_bvh_build(const double* points, const double* normals, const double* radii, int64_t n, const double* scene_box,
+                        int32_t* leaf_index, int32_t* child, int32_t* parent, float* node_box, double* leaf_disk, void* ws, size_t ws_bytes,
+                        dcStream_t stream);
+int dc_surfel_cast_rays(const int32_t* child, const float* node_box, const double* leaf_disk, const int32_t* leaf_index, int64_t n_disks,
+                        const void* vps, const void* dirs, int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans,
+                        double t_min, double window, double min_cos, int32_t* index_out, double* t_first_out, double* t_out, double* inc_out,
+                        int32_t* count_out, dcStream_t stream);
+
 /* ---- depth bias against the mesh (depth_correction_amd/csrc/dc_bias.hip, per-ray terms in dc_biasmath.h; DESIGN "Depth bias against
  * the mesh") ----
  * Per ray i of n: d = depth[i], g_est = inc_est[i] (DC_F32 | DC_F64 [n]; inc_est optional), the cast's face[i], t = t_true[i],
