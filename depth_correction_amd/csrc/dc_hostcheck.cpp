@@ -2,6 +2,7 @@
 // Lets the CPU test-suite pin the eigen-solver and the covariance / loss / backward-coefficient
 // arithmetic against LAPACK and the oracle without a GPU.  Never loaded by depth_correction_amd.
 #include "dc_common.h"
+#include "dc_bvh.h"
 #include "dc_eig3.h"
 #include "dc_pointmath.h"
 #include "dc_slam_math.h"
@@ -284,11 +285,7 @@ void dc_host_ray_cast_brute(const double* tri, const int32_t* face_id, int64_t n
     dc::Ray64 r64;
     dc::Ray32 r32;
     dc::ray_setup(d[3 * i], d[3 * i + 1], d[3 * i + 2], o[3 * i], o[3 * i + 1], o[3 * i + 2], r64, r32);
-    dc::Hit best;
-    best.t = INFINITY;
-    best.u = best.v = 0.0;
-    best.face = -1;
-    best.leaf = -1;
+    dc::Hit best = dc::no_hit();
     for (int64_t f = 0; f < n_faces; ++f) dc::test_triangle(tri + 9 * f, face_id[f], (int32_t)f, r64, t_min[i], cull != 0, best);
     face[i] = best.face;
     t[i] = best.t;
@@ -331,11 +328,7 @@ void dc_host_surfel_cast_brute(const double* disk, const int32_t* index, int64_t
                                double* inc_out, int32_t* count_out) {
   for (int64_t i = 0; i < n_rays; ++i) {
     const dc::SurfelRay r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]};
-    dc::SurfelHit best;
-    best.t = INFINITY;
-    best.r2 = 0.0;
-    best.index = -1;
-    best.leaf = -1;
+    dc::SurfelHit best = dc::no_surfel_hit();
     for (int64_t j = 0; j < n_disks; ++j) dc::test_disk(disk + dc::kDiskRow * j, index[j], (int32_t)j, r, t_min, best);
     dc::SurfelBlend blend;
     dc::blend_init(blend);
@@ -346,6 +339,48 @@ void dc_host_surfel_cast_brute(const double* disk, const int32_t* index, int64_t
     index_out[i] = best.index;
     t_first_out[i] = best.t;
     dc::surfel_finish(best, first, blend, r, t_out[i], inc_out[i], count_out[i]);
+  }
+}
+
+// ---- the one tree walk (dc_bvh.h) ----------------------------------------------------------------------------------------------------
+// cast_ray on the host: bvh_walk (BLOCK = 1, lane 0) with the kernels' TriVisitor over a tree passed in as arrays (child i32 [n-1,2],
+// node_box f32 [2n-1,6], leaf_tri f64 [n,9], leaf_face i32 [n]); outputs as dc_host_ray_cast_brute
+void dc_host_ray_cast_walk(const int32_t* child, const float* node_box, const double* leaf_tri, const int32_t* leaf_face, int64_t n,
+                           const double* o, const double* d, const double* t_min, int64_t n_rays, int cull, int32_t* face, double* t, double* u,
+                           double* v) {
+  int32_t stack[dc::kBvhStackDepth];
+  for (int64_t i = 0; i < n_rays; ++i) {
+    dc::TriVisitor vis = {node_box, leaf_tri, leaf_face, t_min[i], cull != 0};
+    dc::ray_setup(d[3 * i], d[3 * i + 1], d[3 * i + 2], o[3 * i], o[3 * i + 1], o[3 * i + 2], vis.ray64, vis.ray);
+    vis.best = dc::no_hit();
+    dc::bvh_walk<1>(child, n, stack, 0, vis);
+    face[i] = vis.best.face, t[i] = vis.best.t, u[i] = vis.best.u, v[i] = vis.best.v;
+  }
+}
+
+// surfel_cast_kernel on the host: both walks with the kernel's DiskVisitor over a tree of disks (leaf_disk f64 [n,8], leaf_index i32 [n]);
+// outputs as dc_host_surfel_cast_brute, the blend summed in the order of the walk
+void dc_host_surfel_cast_walk(const int32_t* child, const float* node_box, const double* leaf_disk, const int32_t* leaf_index, int64_t n,
+                              const double* o, const double* d, int64_t n_rays, double t_min, double window, double min_cos,
+                              int32_t* index_out, double* t_first_out, double* t_out, double* inc_out, int32_t* count_out) {
+  int32_t stack[dc::kBvhStackDepth];
+  for (int64_t i = 0; i < n_rays; ++i) {
+    const dc::SurfelRay r = {o[3 * i], o[3 * i + 1], o[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2]};
+    dc::Ray64 ray64;
+    dc::Ray32 ray;
+    dc::ray_setup(r.d0, r.d1, r.d2, r.o0, r.o1, r.o2, ray64, ray);
+    dc::SurfelHit best = dc::no_surfel_hit();
+    dc::SurfelBlend blend;
+    dc::blend_init(blend);
+    dc::DiskVisitor<false> first = {node_box, leaf_disk, leaf_index, r, ray, t_min, 0.0, 0.0, best, blend};
+    dc::bvh_walk<1>(child, n, stack, 0, first);
+    if (best.leaf >= 0 && window > 0.0) {
+      dc::DiskVisitor<true> rest = {node_box, leaf_disk, leaf_index, r, ray, t_min, best.t + window, min_cos, best, blend};
+      dc::bvh_walk<1>(child, n, stack, 0, rest);
+    }
+    index_out[i] = best.index;
+    t_first_out[i] = best.t;
+    dc::surfel_finish(best, leaf_disk + dc::kDiskRow * (int64_t)(best.leaf >= 0 ? best.leaf : 0), blend, r, t_out[i], inc_out[i], count_out[i]);
   }
 }
 

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <atomic>
 #include "dc_common.h"
+#include "dc_bvh.h"
 #include "../../include/dc_hip.h"
 #include "dc_device.h"
 #include "dc_hostutil.h"
@@ -1557,22 +1558,13 @@ __global__ void lattice_setup_kernel(const double* __restrict__ part, int n_part
   }
 }
 
-__device__ __forceinline__ int scan_of_row(const int64_t* __restrict__ scan_ptr, int n_scans, int64_t i) {
-  int lo = 0, hi = n_scans;                       // scan_ptr[lo] <= i < scan_ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (scan_ptr[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void lattice_shift_kernel(const T* __restrict__ xyz, int64_t n, const int64_t* __restrict__ scan_ptr,
                                                                int n_scans, const double* __restrict__ offsets,
                                                                double* __restrict__ shifted, int32_t* __restrict__ info) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  const int s = scan_of_row(scan_ptr, n_scans, i);
+  const int s = dc::scan_of(scan_ptr, n_scans, i);
   bool exact = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -1590,7 +1582,7 @@ __global__ __launch_bounds__(kBlock) void lattice_localize_kernel(int32_t* __res
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= n * k) return;
   const int64_t i = e / k;
-  const int s = scan_of_row(scan_ptr, n_scans, i);
+  const int s = dc::scan_of(scan_ptr, n_scans, i);
   const int32_t v = nbr[e];
   if (v < 0) return;
   const int64_t b = scan_ptr[s], en = scan_ptr[s + 1];
@@ -1609,7 +1601,7 @@ __global__ void extent_finish_kernel(const double* __restrict__ part, int n_part
 // out[i] = the scan of row i (scan_ptr: [n_scans + 1] ascending row offsets)
 __global__ __launch_bounds__(kBlock) void scan_ids_kernel(const int64_t* __restrict__ scan_ptr, int n_scans, int64_t n, int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) out[i] = scan_of_row(scan_ptr, n_scans, i);
+  if (i < n) out[i] = dc::scan_of(scan_ptr, n_scans, i);
 }
 
 }  // namespace dc

@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(kClosestBlock) mesh_closest_kernel(const int32
                                                                     int64_t n, const T* __restrict__ points, int64_t n_points, double limit2,
                                                                     double max_dist, int32_t* __restrict__ face_out,
                                                                     double* __restrict__ dist_out, double* __restrict__ closest_out) {
-  __shared__ int32_t stack[dc::kWalkStackDepth * kClosestBlock];
+  __shared__ int32_t stack[dc::kBvhStackDepth * kClosestBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kClosestBlock + lane;
   if (g >= n_points) return;

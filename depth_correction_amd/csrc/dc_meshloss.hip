@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(kLossBlock) mesh_loss_kernel(MeshArrays mesh, 
                                                                int32_t* __restrict__ leaf_hint, int32_t* __restrict__ face_out,
                                                                double* __restrict__ dist_out, double* __restrict__ closest_out,
                                                                double* __restrict__ partials) {
-  __shared__ int32_t stack[kWalkStackDepth * kLossBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kLossBlock];
   __shared__ double s_pose[12];
   __shared__ double s_red[kLossWaves][kMaxCols];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;

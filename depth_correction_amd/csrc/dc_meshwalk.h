@@ -1,6 +1,6 @@
 // The nearest-triangle walk over the LBVH of dc_raycast.hip, shared by dc_mesh_closest (dc_meshdist.hip) and dc_mesh_loss
-// (dc_meshloss.hip): ONE copy of the box bound, of the leaf test with its tie rule and of the depth-first loop, so the two entry
-// points cannot drift apart.  The rule and the derivation of the fp32 box bound are in dc_meshdist.hip's header comment.
+// (dc_meshloss.hip): ONE copy of the box bound and of the leaf test with its tie rule, so the two entry points cannot drift apart; the
+// depth-first loop is dc::bvh_walk (dc_bvh.h), the ray casts' too.  The rule and the derivation of the fp32 box bound are in dc_meshdist.hip's header comment.
 //
 // State of a walk: best (d^2 of the best face so far, or the caller's bound before the first), best_face (mesh numbering, -1 = none)
 // and best_leaf (its leaf, what closest_on_triangle is run on again for the closest point).  mesh_walk_leaf folds one leaf into the
@@ -11,12 +11,11 @@
 // distance with a lower index is still seen.
 #pragma once
 #include "dc_common.h"
+#include "dc_bvh.h"
 #include "dc_trimath.h"
 #include <float.h>
 
 namespace dc {
-
-constexpr int kWalkStackDepth = 64;      // per-lane stack in LDS, lane-minor: int32 [kWalkStackDepth * BLOCK]
 
 struct Query32 {
   float p[3], margin;
@@ -63,44 +62,32 @@ __device__ __forceinline__ void mesh_walk_leaf(const double* __restrict__ leaf_t
   }
 }
 
-// Depth-first from the root with the nearer child first and the other on this lane's stack (stack[sp * BLOCK + lane]); n = number of
-// faces (leaves are the nodes n - 1 .. 2 n - 2).  No barrier inside: lanes of a block may call it or not.
+// The walk as a visitor of bvh_walk (dc_bvh.h): a box is admitted when its bound is not above the best d^2 (rounded up to fp32), the
+// bound orders the children, a leaf is mesh_walk_leaf.
+struct MeshVisitor {
+  const float* __restrict__ node_box;
+  const double* __restrict__ leaf_tri;
+  const int32_t* __restrict__ leaf_face;
+  const double* p; const Query32& q;
+  double& best;                 // best, best_face, best_leaf: the state of the header comment
+  int32_t& best_face;
+  int64_t& best_leaf;
+
+  __device__ __forceinline__ bool enter(int64_t node, float& key) const {
+    key = box_bound(node_box, node, q);
+    return key <= __double2float_ru(best);
+  }
+  __device__ __forceinline__ void leaf(int64_t leaf) { mesh_walk_leaf(leaf_tri, leaf_face, leaf, p, best, best_face, best_leaf); }
+};
+
+// n = number of faces; stack: int32 [kBvhStackDepth * BLOCK] in LDS.  No barrier inside: lanes of a block may call it or not.
 template <int BLOCK>
 __device__ __forceinline__ void mesh_walk(const int32_t* __restrict__ child, const float* __restrict__ node_box,
                                           const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face, int64_t n,
                                           const double* p, const Query32& q, int32_t* stack, int lane, double& best, int32_t& best_face,
                                           int64_t& best_leaf) {
-  int sp = 0;
-  int64_t node = 0;
-  bool live = box_bound(node_box, 0, q) <= __double2float_ru(best);
-  while (live) {
-    if (node >= n - 1) {
-      mesh_walk_leaf(leaf_tri, leaf_face, node - (n - 1), p, best, best_face, best_leaf);
-    } else {
-      const float lim = __double2float_ru(best);
-      const int64_t ca = child[2 * node], cb = child[2 * node + 1];
-      const float ba = box_bound(node_box, ca, q), bb = box_bound(node_box, cb, q);
-      const bool go_a = ba <= lim, go_b = bb <= lim;
-      if (go_a || go_b) {
-        if (go_a && go_b) {
-          const bool a_first = ba <= bb;
-          if (sp < kWalkStackDepth) stack[sp * BLOCK + lane] = (int32_t)(a_first ? cb : ca);     // sp < 64 always (depth <= 63)
-          ++sp;
-          node = a_first ? ca : cb;
-        } else {
-          node = go_a ? ca : cb;
-        }
-        continue;
-      }
-    }
-    // next postponed node whose box may still hold a face as near as the best one
-    live = false;
-    while (sp > 0) {
-      --sp;
-      node = sp < kWalkStackDepth ? stack[sp * BLOCK + lane] : 0;
-      if (box_bound(node_box, node, q) <= __double2float_ru(best)) { live = true; break; }
-    }
-  }
+  MeshVisitor vis = {node_box, leaf_tri, leaf_face, p, q, best, best_face, best_leaf};
+  bvh_walk<BLOCK>(child, n, stack, lane, vis);
 }
 
 }  // namespace dc

@@ -16,8 +16,8 @@
 // headroom for the fp32 rounding of the direction; the boxes grow by 2^-22 |origin|, at least 1e-20, for the rounding of the
 // origin; a direction component below 1e-30 counts as 1e-30, so that a ray running exactly on a slab's boundary stays in it up
 // to t = 1e10; and the best hit's t prunes with the same 1 + 2^-20, because the fp32 entry distance of a flat box met face-on can
-// exceed the exact hit distance by a few 2^-24).  The nearer child is visited first; the other goes on a per-lane stack in LDS
-// (depth 64, lane-minor so that a wavefront's pushes hit 64 distinct banks).  Triangles are tested in fp64 with the watertight
+// exceed the exact hit distance by a few 2^-24).  The walk is dc::bvh_walk (dc_bvh.h: the nearer child first, the other on a per-lane
+// stack in LDS) with dc::TriVisitor (dc_raymath.h) deciding which boxes to enter.  Triangles are tested in fp64 with the watertight
 // test of Woop, Benthin and Wald (JCGT 2013), no FMA contraction there (see test_triangle).  A hit counts when t > t_min (and
 // dot(n, d) < 0 with culling).  Guaranteed, and pinned by tests/test_raycast_host.py and tests/test_gpu_raycast_edge.py:
 //   1. no box is rejected that holds a face test_triangle reports a hit on, before the first hit and under the pruning rule;
@@ -37,10 +37,11 @@
 // of its scan, then is one of raycast_rays_kernel's lanes; dc_sweep_rays writes those rays out instead of casting them.
 //
 // dc_surfel_bvh_build / dc_surfel_cast_rays cast the same measured rays against a surveyed cloud, every survey point an oriented disk
-// (dc_surfelmath.h): the same LBVH over the disks' boxes (karras_kernel as it is), a second walker next to cast_ray (surfel_walk) with
-// the disk test at the leaves, and a second walk that blends the disks within a depth window behind the first hit.  cast_ray and the
-// five kernels above are untouched.
+// (dc_surfelmath.h): the same build over the disks' boxes (build_tree; only the Morton keys and the leaves differ) and the same walk
+// with dc::DiskVisitor -- the disk test at the leaves, then a second walk that blends the disks within a depth window behind the first
+// hit.  The nearest-triangle queries (dc_meshwalk.h) are a third visitor of that one walk.
 #include "dc_common.h"
+#include "dc_bvh.h"
 #include "dc_beammath.h"
 #include "dc_raymath.h"
 #include "dc_sweepmath.h"
@@ -53,7 +54,7 @@ namespace {
 
 constexpr int kBuildBlock = 256;
 constexpr int kCastBlock = 128;
-constexpr int kStackDepth = 64;
+using dc::kBvhStackDepth;
 
 __device__ __forceinline__ uint32_t expand_bits10(uint32_t v) {
   v &= 0x3ffu;
@@ -75,20 +76,27 @@ struct SceneBox {
   double scale[3];        // 1024 / extent (0 for a flat axis)
 };
 
+// key and value of primitive i with the centre c [3]: (morton30(c in the scene box) << 32) | i
+__device__ __forceinline__ void morton_key(const double* c, const SceneBox& box, int64_t i, uint64_t* __restrict__ keys,
+                                           uint32_t* __restrict__ vals) {
+  uint32_t code = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) code |= expand_bits10(quantise10(c[a], box.lo[a], box.scale[a])) << (2 - a);
+  keys[i] = ((uint64_t)code << 32) | (uint64_t)(uint32_t)i;
+  vals[i] = (uint32_t)i;
+}
+
 __global__ void __launch_bounds__(kBuildBlock) morton_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces,
                                                              int64_t n, SceneBox box, uint64_t* __restrict__ keys,
                                                              uint32_t* __restrict__ vals) {
   const int64_t f = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
   if (f >= n) return;
-  uint32_t code = 0;
+  double c[3];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double c = (verts[3 * (int64_t)faces[3 * f] + a] + verts[3 * (int64_t)faces[3 * f + 1] + a] +
-                      verts[3 * (int64_t)faces[3 * f + 2] + a]) * (1.0 / 3.0);
-    code |= expand_bits10(quantise10(c, box.lo[a], box.scale[a])) << (2 - a);
-  }
-  keys[f] = ((uint64_t)code << 32) | (uint64_t)(uint32_t)f;
-  vals[f] = (uint32_t)f;
+  for (int a = 0; a < 3; ++a)
+    c[a] = (verts[3 * (int64_t)faces[3 * f] + a] + verts[3 * (int64_t)faces[3 * f + 1] + a] + verts[3 * (int64_t)faces[3 * f + 2] + a]) *
+           (1.0 / 3.0);
+  morton_key(c, box, f, keys, vals);
 }
 
 // length of the common prefix of keys i and j, -1 outside [0, n)
@@ -125,10 +133,6 @@ __global__ void __launch_bounds__(kBuildBlock) karras_kernel(const uint64_t* __r
   parent[right] = (int32_t)i;
 }
 
-__device__ __forceinline__ float load_box(const float* p) {
-  return __uint_as_float(__hip_atomic_load((const uint32_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 __global__ void __launch_bounds__(kBuildBlock) fit_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces, int64_t n,
                                                           const int32_t* __restrict__ leaf_face, const int32_t* __restrict__ child,
                                                           const int32_t* __restrict__ parent, int32_t* __restrict__ counter,
@@ -143,28 +147,13 @@ __global__ void __launch_bounds__(kBuildBlock) fit_kernel(const double* __restri
     for (int a = 0; a < 3; ++a) v[3 * c + a] = verts[3 * (int64_t)faces[3 * f + c] + a];
 #pragma unroll
   for (int k = 0; k < 9; ++k) leaf_tri[9 * i + k] = v[k];
-  int64_t node = (n - 1) + i;
-  dc::leaf_box(v, node_box + 6 * node);
-  node = parent[node];
-  while (node >= 0) {
-    __threadfence();                                        // this child's box is visible before the counter says so
-    if (atomicAdd(&counter[node], 1) == 0) return;          // the sibling is still on its way: it fits the parent
-    __threadfence();
-    const int64_t a0 = child[2 * node], b0 = child[2 * node + 1];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      node_box[6 * node + a] = fminf(load_box(node_box + 6 * a0 + a), load_box(node_box + 6 * b0 + a));
-      node_box[6 * node + 3 + a] = fmaxf(load_box(node_box + 6 * a0 + 3 + a), load_box(node_box + 6 * b0 + 3 + a));
-    }
-    node = parent[node];
-  }
+  dc::leaf_box(v, node_box + 6 * ((n - 1) + i));
+  dc::bvh_fit_climb((n - 1) + i, child, parent, counter, node_box);
 }
 
 using dc::Hit;
 using dc::Ray32;
 using dc::Ray64;
-using dc::box_entry;
-using dc::test_triangle;
 
 // A sensor-frame ray in the world: direction R s and origin R v + t of the pose M (4 x 4, row-major).  Every cast kernel forms its ray
 // here, with the multiply-adds written out, so that kernels given the same ray cast the same bits: left to the compiler, the
@@ -198,53 +187,28 @@ __device__ __forceinline__ double incidence_cos(const double* __restrict__ tri, 
   return fabs(nd) / (sqrt(nn) * sqrt(dd));
 }
 
-// Closest hit of one ray (origin o, direction d, both fp64 world frame) over the tree: the traversal both cast kernels share.
-// `stack` is the block's LDS stack (kStackDepth x kCastBlock, lane-minor); best.leaf is the winning leaf's row of leaf_tri.
+// The ray of a measured point in the world: view point vps[g] and direction dirs[g] (sensor frame, fp32 or fp64) under the pose M.
+// The beam and sweep kernels pass their own fp64 sub-ray (g = 0) and so cast the ray raycast_rays_kernel would.
+template <typename T>
+__device__ __forceinline__ void measured_ray(const T* __restrict__ vps, const T* __restrict__ dirs, int64_t g, const double* __restrict__ M,
+                                             double& d0, double& d1, double& d2, double& o0, double& o1, double& o2) {
+  const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
+  const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
+  pose_dir(M, s0, s1, s2, d0, d1, d2);
+  pose_point(M, v0, v1, v2, o0, o1, o2);
+}
+
+// Closest hit of one ray (origin o, direction d, both fp64 world frame) over the tree: the traversal every cast kernel shares.
+// `stack` is the block's LDS stack (kBvhStackDepth x kCastBlock, lane-minor); best.leaf is the winning leaf's row of leaf_tri.
 __device__ __forceinline__ Hit cast_ray(const int32_t* __restrict__ child, const float* __restrict__ node_box,
                                         const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face, int64_t n, double d0,
                                         double d1, double d2, double o0, double o1, double o2, double tmin, int cull, int32_t* stack,
                                         int lane) {
-  Ray64 ray64;
-  Ray32 ray;
-  dc::ray_setup(d0, d1, d2, o0, o1, o2, ray64, ray);
-
-  Hit best;
-  best.t = INFINITY;
-  best.u = best.v = 0.0;
-  best.face = -1;
-  best.leaf = -1;
-  int sp = 0;
-  int64_t node = 0;
-  bool live = box_entry(node_box, ray, INFINITY) < INFINITY;
-  while (live) {
-    if (node >= n - 1) {
-      const int64_t leaf = node - (n - 1);
-      test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], (int32_t)leaf, ray64, tmin, cull != 0, best);
-    } else {
-      const float t_far = dc::prune_far(best.t);
-      const int64_t ca = child[2 * node], cb = child[2 * node + 1];
-      const float ta = box_entry(node_box + 6 * ca, ray, t_far), tb = box_entry(node_box + 6 * cb, ray, t_far);
-      if (ta < INFINITY || tb < INFINITY) {
-        if (ta < INFINITY && tb < INFINITY) {
-          const bool a_first = ta <= tb;
-          if (sp < kStackDepth) stack[sp * kCastBlock + lane] = (int32_t)(a_first ? cb : ca);    // sp < 64 always (depth <= 63)
-          ++sp;
-          node = a_first ? ca : cb;
-        } else {
-          node = ta < INFINITY ? ca : cb;
-        }
-        continue;
-      }
-    }
-    // next postponed node whose box the ray still reaches before the best hit
-    live = false;
-    while (sp > 0) {
-      --sp;
-      node = sp < kStackDepth ? stack[sp * kCastBlock + lane] : 0;
-      if (box_entry(node_box + 6 * node, ray, dc::prune_far(best.t)) < INFINITY) { live = true; break; }
-    }
-  }
-  return best;
+  dc::TriVisitor vis = {node_box, leaf_tri, leaf_face, tmin, cull != 0};
+  dc::ray_setup(d0, d1, d2, o0, o1, o2, vis.ray64, vis.ray);
+  vis.best = dc::no_hit();
+  dc::bvh_walk<kCastBlock>(child, n, stack, lane, vis);
+  return vis.best;
 }
 
 __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
@@ -253,7 +217,7 @@ __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __re
                                                              int64_t n_rays, const double* __restrict__ poses, int64_t total, int cull,
                                                              int32_t* __restrict__ face_out, double* __restrict__ t_out,
                                                              double* __restrict__ bary_out) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kCastBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
   if (g >= total) return;
@@ -269,9 +233,7 @@ __global__ void __launch_bounds__(kCastBlock) raycast_kernel(const int32_t* __re
   bary_out[2 * g + 1] = best.v;
 }
 
-// The rays of measured clouds (dc_raycast_rays): per-ray view point and direction in the sensor frame of the ray's scan.  The scan is
-// found by bisection of scan_offset (a few loads of one small cached array per lane, against a traversal of hundreds); the index is
-// clamped to [0, n_scans), so offsets that do not span [0, n] cannot move a read outside poses.
+// The rays of measured clouds (dc_raycast_rays): per-ray view point and direction in the sensor frame of the ray's scan (dc::scan_of).
 template <typename T>
 __global__ void __launch_bounds__(kCastBlock) raycast_rays_kernel(const int32_t* __restrict__ child, const float* __restrict__ node_box,
                                                                   const double* __restrict__ leaf_tri, const int32_t* __restrict__ leaf_face,
@@ -280,21 +242,12 @@ __global__ void __launch_bounds__(kCastBlock) raycast_rays_kernel(const int32_t*
                                                                   const double* __restrict__ poses, int n_scans, double t_min, int cull,
                                                                   int32_t* __restrict__ face_out, double* __restrict__ t_out,
                                                                   double* __restrict__ inc_out) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kCastBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
   if (g >= total) return;
-  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
-  while (hi - lo > 1) {
-    const int mid = lo + (hi - lo) / 2;
-    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
-  }
-  const double* M = poses + 16 * (int64_t)lo;
-  const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
-  const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
   double d0, d1, d2, o0, o1, o2;
-  pose_dir(M, s0, s1, s2, d0, d1, d2);
-  pose_point(M, v0, v1, v2, o0, o1, o2);
+  measured_ray(vps, dirs, g, poses + 16 * (int64_t)dc::scan_of(scan_offset, n_scans, g), d0, d1, d2, o0, o1, o2);
   const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min, cull, stack, lane);
   face_out[g] = best.face;
   t_out[g] = best.t;
@@ -336,7 +289,7 @@ __global__ void __launch_bounds__(kCastBlock) raycast_beams_kernel(
     double spread, const double* __restrict__ t_min_beam, double t_min, int cull, int weight_kind, int detection, double tau, int min_hits,
     int32_t* __restrict__ face_out, double* __restrict__ depth_out, int32_t* __restrict__ n_hits_out, int32_t* __restrict__ sub_face,
     double* __restrict__ sub_t, double* __restrict__ sub_w) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kCastBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
   const int S = 1 << log2s;
@@ -346,22 +299,14 @@ __global__ void __launch_bounds__(kCastBlock) raycast_beams_kernel(
   int32_t face = -1;
   double t = INFINITY, w = 0.0;
   if (live) {
-    int lo = 0, hi = n_scans;                     // the last s in [0, n_scans) with scan_offset[s] <= i (scan 0 when there is none)
-    while (hi - lo > 1) {
-      const int mid = lo + (hi - lo) / 2;
-      if (scan_offset[mid] <= i) lo = mid; else hi = mid;
-    }
-    const double* M = poses + 16 * (int64_t)lo;
+    const double* M = poses + 16 * (int64_t)dc::scan_of(scan_offset, n_scans, i);
     const dc::BeamFrame f = dc::beam_frame((double)dirs[3 * i], (double)dirs[3 * i + 1], (double)dirs[3 * i + 2]);
     if (f.ok) {
       double o[3], D[3];
       dc::beam_subray(f, (double)vps[3 * i], (double)vps[3 * i + 1], (double)vps[3 * i + 2], pat.v[3 * j], pat.v[3 * j + 1], r0, spread, o,
                       D);
-      const double s0 = D[0], s1 = D[1], s2 = D[2];
-      const double v0 = o[0], v1 = o[1], v2 = o[2];
-      double d0, d1, d2, o0, o1, o2;                 // the ray of raycast_rays_kernel
-      pose_dir(M, s0, s1, s2, d0, d1, d2);
-      pose_point(M, v0, v1, v2, o0, o1, o2);
+      double d0, d1, d2, o0, o1, o2;
+      measured_ray(o, D, 0, M, d0, d1, d2, o0, o1, o2);
       const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min_beam ? t_min_beam[i] : t_min, cull,
                                 stack, lane);
       if (best.leaf >= 0) {
@@ -448,11 +393,7 @@ template <typename T>
 __device__ __forceinline__ int sweep_ray(const T* __restrict__ vps, const T* __restrict__ dirs, double tg, int64_t g,
                                          const int64_t* __restrict__ scan_offset, const double* __restrict__ twists, int n_scans, double* o,
                                          double* D) {
-  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
-  while (hi - lo > 1) {
-    const int mid = lo + (hi - lo) / 2;
-    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
-  }
+  const int lo = dc::scan_of(scan_offset, n_scans, g);
   const double* tw = twists + 6 * (int64_t)lo;
   const dc::SweepRot r = dc::sweep_rot(tg, tw[3], tw[4], tw[5]);
   dc::sweep_point(r, tg, tw[0], tw[1], tw[2], (double)vps[3 * g], (double)vps[3 * g + 1], (double)vps[3 * g + 2], o);
@@ -488,7 +429,7 @@ __global__ void __launch_bounds__(kCastBlock) raycast_sweep_kernel(const int32_t
                                                                    const double* __restrict__ t_min_ray, double t_min, int cull,
                                                                    int32_t* __restrict__ face_out, double* __restrict__ t_out,
                                                                    double* __restrict__ inc_out) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kCastBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
   if (g >= total) return;
@@ -498,12 +439,8 @@ __global__ void __launch_bounds__(kCastBlock) raycast_sweep_kernel(const int32_t
   if (isfinite(tg)) {
     double o[3], D[3];
     const int s = sweep_ray(vps, dirs, tg, g, scan_offset, twists, n_scans, o, D);
-    const double* M = poses + 16 * (int64_t)s;
-    const double s0 = D[0], s1 = D[1], s2 = D[2];
-    const double v0 = o[0], v1 = o[1], v2 = o[2];
-    double d0, d1, d2, o0, o1, o2;                   // the ray of raycast_rays_kernel
-    pose_dir(M, s0, s1, s2, d0, d1, d2);
-    pose_point(M, v0, v1, v2, o0, o1, o2);
+    double d0, d1, d2, o0, o1, o2;
+    measured_ray(o, D, 0, poses + 16 * (int64_t)s, d0, d1, d2, o0, o1, o2);
     const Hit best = cast_ray(child, node_box, leaf_tri, leaf_face, n, d0, d1, d2, o0, o1, o2, t_min_ray ? t_min_ray[g] : t_min, cull, stack,
                               lane);
     face = best.face;
@@ -525,11 +462,7 @@ __global__ void __launch_bounds__(kBuildBlock) surfel_morton_kernel(const double
                                                                     uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int64_t i = (int64_t)blockIdx.x * kBuildBlock + threadIdx.x;
   if (i >= n) return;
-  uint32_t code = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) code |= expand_bits10(quantise10(points[3 * i + a], box.lo[a], box.scale[a])) << (2 - a);
-  keys[i] = ((uint64_t)code << 32) | (uint64_t)(uint32_t)i;
-  vals[i] = (uint32_t)i;
+  morton_key(points + 3 * i, box, i, keys, vals);
 }
 
 // fit_kernel with disk_box at the leaves; leaf i also writes its disk's row of leaf_disk
@@ -556,64 +489,18 @@ __global__ void __launch_bounds__(kBuildBlock) surfel_fit_kernel(const double* _
   }
   row[6] = rho * rho;
   row[7] = 0.0;
-  int64_t node = (n - 1) + i;
-  dc::disk_box(p, nv, rho, node_box + 6 * node);
-  node = parent[node];
-  while (node >= 0) {
-    __threadfence();                                        // this child's box is visible before the counter says so
-    if (atomicAdd(&counter[node], 1) == 0) return;          // the sibling is still on its way: it fits the parent
-    __threadfence();
-    const int64_t a0 = child[2 * node], b0 = child[2 * node + 1];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      node_box[6 * node + a] = fminf(load_box(node_box + 6 * a0 + a), load_box(node_box + 6 * b0 + a));
-      node_box[6 * node + 3 + a] = fmaxf(load_box(node_box + 6 * a0 + 3 + a), load_box(node_box + 6 * b0 + 3 + a));
-    }
-    node = parent[node];
-  }
+  dc::disk_box(p, nv, rho, node_box + 6 * ((n - 1) + i));
+  dc::bvh_fit_climb((n - 1) + i, child, parent, counter, node_box);
 }
 
-// cast_ray's walk over a tree of disks.  Pass 1 (kBlend false) keeps the closest hit in `best` and prunes with it.  Pass 2 (kBlend
-// true) adds every member of the blend to `blend` under the fixed bound prune_far(t_end): prune_far does not decrease, and a member's
-// t is at most t_end, so property 1 keeps every member's boxes.  The order of the walk depends on the tree and the ray alone.
+// One pass of dc_surfel_cast_rays over the tree of disks (dc::DiskVisitor: the closest hit, or the blend behind it up to t_end)
 template <bool kBlend>
 __device__ __forceinline__ void surfel_walk(const int32_t* __restrict__ child, const float* __restrict__ node_box,
                                             const double* __restrict__ leaf_disk, const int32_t* __restrict__ leaf_index, int64_t n,
                                             const SurfelRay& sr, const Ray32& ray, double tmin, SurfelHit& best, double t_end, double min_cos,
                                             SurfelBlend& blend, int32_t* stack, int lane) {
-  const float t_fixed = kBlend ? dc::prune_far(t_end) : INFINITY;
-  const double* first = leaf_disk + kDiskRow * (int64_t)(kBlend ? best.leaf : 0);
-  int sp = 0;
-  int64_t node = 0;
-  bool live = box_entry(node_box, ray, t_fixed) < INFINITY;
-  while (live) {
-    if (node >= n - 1) {
-      const int64_t leaf = node - (n - 1);
-      if (kBlend) dc::blend_disk(leaf_disk + kDiskRow * leaf, leaf == best.leaf, first, sr, tmin, best.t, t_end, min_cos, blend);
-      else dc::test_disk(leaf_disk + kDiskRow * leaf, leaf_index[leaf], (int32_t)leaf, sr, tmin, best);
-    } else {
-      const float t_far = kBlend ? t_fixed : dc::prune_far(best.t);
-      const int64_t ca = child[2 * node], cb = child[2 * node + 1];
-      const float ta = box_entry(node_box + 6 * ca, ray, t_far), tb = box_entry(node_box + 6 * cb, ray, t_far);
-      if (ta < INFINITY || tb < INFINITY) {
-        if (ta < INFINITY && tb < INFINITY) {
-          const bool a_first = ta <= tb;
-          if (sp < kStackDepth) stack[sp * kCastBlock + lane] = (int32_t)(a_first ? cb : ca);    // sp < 64 always (depth <= 63)
-          ++sp;
-          node = a_first ? ca : cb;
-        } else {
-          node = ta < INFINITY ? ca : cb;
-        }
-        continue;
-      }
-    }
-    live = false;
-    while (sp > 0) {
-      --sp;
-      node = sp < kStackDepth ? stack[sp * kCastBlock + lane] : 0;
-      if (box_entry(node_box + 6 * node, ray, kBlend ? t_fixed : dc::prune_far(best.t)) < INFINITY) { live = true; break; }
-    }
-  }
+  dc::DiskVisitor<kBlend> vis = {node_box, leaf_disk, leaf_index, sr, ray, tmin, t_end, min_cos, best, blend};
+  dc::bvh_walk<kCastBlock>(child, n, stack, lane, vis);
 }
 
 // dc_surfel_cast_rays: the ray of raycast_rays_kernel, the closest disk, then (window > 0) the blend over the disks behind it
@@ -626,29 +513,16 @@ __global__ void __launch_bounds__(kCastBlock) surfel_cast_kernel(const int32_t* 
                                                                  double min_cos, int32_t* __restrict__ index_out,
                                                                  double* __restrict__ t_first_out, double* __restrict__ t_out,
                                                                  double* __restrict__ inc_out, int32_t* __restrict__ count_out) {
-  __shared__ int32_t stack[kStackDepth * kCastBlock];
+  __shared__ int32_t stack[kBvhStackDepth * kCastBlock];
   const int lane = threadIdx.x;
   const int64_t g = (int64_t)blockIdx.x * kCastBlock + lane;
   if (g >= total) return;
-  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
-  while (hi - lo > 1) {
-    const int mid = lo + (hi - lo) / 2;
-    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
-  }
-  const double* M = poses + 16 * (int64_t)lo;
-  const double s0 = (double)dirs[3 * g], s1 = (double)dirs[3 * g + 1], s2 = (double)dirs[3 * g + 2];
-  const double v0 = (double)vps[3 * g], v1 = (double)vps[3 * g + 1], v2 = (double)vps[3 * g + 2];
   SurfelRay sr;
-  pose_dir(M, s0, s1, s2, sr.d0, sr.d1, sr.d2);
-  pose_point(M, v0, v1, v2, sr.o0, sr.o1, sr.o2);
+  measured_ray(vps, dirs, g, poses + 16 * (int64_t)dc::scan_of(scan_offset, n_scans, g), sr.d0, sr.d1, sr.d2, sr.o0, sr.o1, sr.o2);
   Ray64 ray64;
   Ray32 ray;
   dc::ray_setup(sr.d0, sr.d1, sr.d2, sr.o0, sr.o1, sr.o2, ray64, ray);
-  SurfelHit best;
-  best.t = INFINITY;
-  best.r2 = 0.0;
-  best.index = -1;
-  best.leaf = -1;
+  SurfelHit best = dc::no_surfel_hit();
   SurfelBlend blend;
   dc::blend_init(blend);
   surfel_walk<false>(child, node_box, leaf_disk, leaf_index, n, sr, ray, t_min, best, 0.0, 0.0, blend, stack, lane);
@@ -678,6 +552,37 @@ inline bool beam_pattern_ok(const double* pattern, int n_samples, double r0, dou
 
 inline unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
+// What dc_bvh_build and dc_surfel_bvh_build share between argument check and fit kernel: scene box, workspace, the Morton keys
+// (`morton` launches the kernel that writes them), the sort into leaf_prim and the Karras tree.  *counter: the fit's zeroed counters.
+template <typename Morton>
+int build_tree(int64_t n, const double* scene_box, int32_t* leaf_prim, int32_t* child, int32_t* parent, void* ws, hipStream_t stream,
+               int32_t** counter, Morton morton) {
+  SceneBox box;
+  for (int a = 0; a < 3; ++a) {
+    const double ext = scene_box[3 + a] - scene_box[a];
+    if (!(ext >= 0.0)) return DC_ERR_ARG;
+    box.lo[a] = scene_box[a];
+    box.scale[a] = ext > 0.0 ? 1024.0 / ext : 0.0;
+  }
+  dc::Carver c(ws);
+  uint64_t* keys_in = c.take<uint64_t>(n);
+  uint64_t* keys_out = c.take<uint64_t>(n);
+  uint32_t* vals_in = c.take<uint32_t>(n);
+  *counter = c.take<int32_t>(n);
+  const size_t sort_bytes = dc::sort_pairs_bytes((size_t)n, 64);
+  void* sort_tmp = c.take<char>(sort_bytes);
+  DC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t), stream));                    // the root has no parent
+  DC_HIP(hipMemsetAsync(*counter, 0, sizeof(int32_t) * n, stream));
+  morton(box, keys_in, vals_in);
+  DC_HIP(hipGetLastError());
+  DC_HIP(dc::sort_pairs_u64(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, leaf_prim, (size_t)n, 0, 62, stream));
+  if (n > 1) {
+    karras_kernel<<<grid_of(n - 1, kBuildBlock), kBuildBlock, 0, stream>>>(keys_out, n, child, parent);
+    DC_HIP(hipGetLastError());
+  }
+  return DC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -700,29 +605,12 @@ int dc_bvh_build(const double* verts, int64_t n_verts, const int32_t* faces, int
     return DC_ERR_ARG;
   if (!ws || ws_bytes < dc_bvh_workspace_bytes(n_faces)) return DC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  SceneBox box;
-  for (int a = 0; a < 3; ++a) {
-    const double ext = scene_box[3 + a] - scene_box[a];
-    if (!(ext >= 0.0)) return DC_ERR_ARG;
-    box.lo[a] = scene_box[a];
-    box.scale[a] = ext > 0.0 ? 1024.0 / ext : 0.0;
-  }
-  dc::Carver c(ws);
-  uint64_t* keys_in = c.take<uint64_t>(n_faces);
-  uint64_t* keys_out = c.take<uint64_t>(n_faces);
-  uint32_t* vals_in = c.take<uint32_t>(n_faces);
-  int32_t* counter = c.take<int32_t>(n_faces);
-  const size_t sort_bytes = dc::sort_pairs_bytes((size_t)n_faces, 64);
-  void* sort_tmp = c.take<char>(sort_bytes);
-  DC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t), stream));                    // the root has no parent
-  DC_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t) * n_faces, stream));
-  morton_kernel<<<grid_of(n_faces, kBuildBlock), kBuildBlock, 0, stream>>>(verts, faces, n_faces, box, keys_in, vals_in);
-  DC_HIP(hipGetLastError());
-  DC_HIP(dc::sort_pairs_u64(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, leaf_face, (size_t)n_faces, 0, 62, stream));
-  if (n_faces > 1) {
-    karras_kernel<<<grid_of(n_faces - 1, kBuildBlock), kBuildBlock, 0, stream>>>(keys_out, n_faces, child, parent);
-    DC_HIP(hipGetLastError());
-  }
+  int32_t* counter;
+  const int rc = build_tree(n_faces, scene_box, leaf_face, child, parent, ws, stream, &counter,
+                            [&](const SceneBox& box, uint64_t* keys, uint32_t* vals) {
+                              morton_kernel<<<grid_of(n_faces, kBuildBlock), kBuildBlock, 0, stream>>>(verts, faces, n_faces, box, keys, vals);
+                            });
+  if (rc != DC_OK) return rc;
   fit_kernel<<<grid_of(n_faces, kBuildBlock), kBuildBlock, 0, stream>>>(verts, faces, n_faces, leaf_face, child, parent, counter, node_box,
                                                                        leaf_tri);
   DC_HIP(hipGetLastError());
@@ -859,29 +747,12 @@ int dc_surfel_bvh_build(const double* points, const double* normals, const doubl
     return DC_ERR_ARG;
   if (!ws || ws_bytes < dc_surfel_bvh_workspace_bytes(n)) return DC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  SceneBox box;
-  for (int a = 0; a < 3; ++a) {
-    const double ext = scene_box[3 + a] - scene_box[a];
-    if (!(ext >= 0.0)) return DC_ERR_ARG;
-    box.lo[a] = scene_box[a];
-    box.scale[a] = ext > 0.0 ? 1024.0 / ext : 0.0;
-  }
-  dc::Carver c(ws);
-  uint64_t* keys_in = c.take<uint64_t>(n);
-  uint64_t* keys_out = c.take<uint64_t>(n);
-  uint32_t* vals_in = c.take<uint32_t>(n);
-  int32_t* counter = c.take<int32_t>(n);
-  const size_t sort_bytes = dc::sort_pairs_bytes((size_t)n, 64);
-  void* sort_tmp = c.take<char>(sort_bytes);
-  DC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t), stream));                    // the root has no parent
-  DC_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t) * n, stream));
-  surfel_morton_kernel<<<grid_of(n, kBuildBlock), kBuildBlock, 0, stream>>>(points, n, box, keys_in, vals_in);
-  DC_HIP(hipGetLastError());
-  DC_HIP(dc::sort_pairs_u64(sort_tmp, sort_bytes, keys_in, keys_out, vals_in, leaf_index, (size_t)n, 0, 62, stream));
-  if (n > 1) {
-    karras_kernel<<<grid_of(n - 1, kBuildBlock), kBuildBlock, 0, stream>>>(keys_out, n, child, parent);
-    DC_HIP(hipGetLastError());
-  }
+  int32_t* counter;
+  const int rc = build_tree(n, scene_box, leaf_index, child, parent, ws, stream, &counter,
+                            [&](const SceneBox& box, uint64_t* keys, uint32_t* vals) {
+                              surfel_morton_kernel<<<grid_of(n, kBuildBlock), kBuildBlock, 0, stream>>>(points, n, box, keys, vals);
+                            });
+  if (rc != DC_OK) return rc;
   surfel_fit_kernel<<<grid_of(n, kBuildBlock), kBuildBlock, 0, stream>>>(points, normals, radii, n, leaf_index, child, parent, counter,
                                                                         node_box, leaf_disk);
   DC_HIP(hipGetLastError());

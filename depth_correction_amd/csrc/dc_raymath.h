@@ -152,4 +152,24 @@ DC_HD void test_triangle(const double* __restrict__ tri, int32_t face, int32_t l
   best.leaf = leaf;
 }
 
+// The closest-hit search as a visitor of bvh_walk (dc_bvh.h): a box is admitted when the ray enters it before prune_far of the best
+// hit so far, the entry distance orders the children, a leaf is test_triangle.  Set the rays with ray_setup and best to a miss.
+struct TriVisitor {
+  const float* __restrict__ node_box;
+  const double* __restrict__ leaf_tri;
+  const int32_t* __restrict__ leaf_face;
+  double t_min; bool cull;
+  Ray64 ray64;                  // the three below: set by the caller (ray_setup, no_hit) before the walk
+  Ray32 ray;
+  Hit best;
+
+  DC_HD bool enter(int64_t node, float& key) const {
+    key = box_entry(node_box + 6 * node, ray, prune_far(best.t));
+    return key < INFINITY;
+  }
+  DC_HD void leaf(int64_t leaf) { test_triangle(leaf_tri + 9 * leaf, leaf_face[leaf], (int32_t)leaf, ray64, t_min, cull, best); }
+};
+
+DC_HD Hit no_hit() { return Hit{INFINITY, 0.0, 0.0, -1, -1}; }
+
 }  // namespace dc

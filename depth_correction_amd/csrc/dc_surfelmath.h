@@ -218,6 +218,32 @@ DC_HD void blend_disk(const double* __restrict__ disk, bool is_first, const doub
   b.count += 1;
 }
 
+DC_HD SurfelHit no_surfel_hit() { return SurfelHit{INFINITY, 0.0, -1, -1}; }
+
+// The two passes as visitors of bvh_walk (dc_bvh.h) over a tree of disks.  Pass 1 (kBlend false) keeps the closest hit in `best` and
+// prunes with it, as TriVisitor does.  Pass 2 (kBlend true) adds every member of the blend to `blend` under the fixed bound
+// prune_far(t_end): prune_far does not decrease, and a member's t is at most t_end, so property 1 keeps every member's boxes.  The
+// order of the walk depends on the tree and the ray alone.  t_end and min_cos are read by pass 2 only.
+template <bool kBlend>
+struct DiskVisitor {
+  const float* __restrict__ node_box;
+  const double* __restrict__ leaf_disk;
+  const int32_t* __restrict__ leaf_index;
+  const SurfelRay& sr; const Ray32& ray;
+  double t_min, t_end, min_cos;
+  SurfelHit& best; SurfelBlend& blend;
+
+  DC_HD bool enter(int64_t node, float& key) const {
+    key = box_entry(node_box + 6 * node, ray, prune_far(kBlend ? t_end : best.t));
+    return key < INFINITY;
+  }
+  DC_HD void leaf(int64_t leaf) {
+    const double* disk = leaf_disk + kDiskRow * leaf;
+    if (kBlend) blend_disk(disk, leaf == best.leaf, leaf_disk + kDiskRow * (int64_t)best.leaf, sr, t_min, best.t, t_end, min_cos, blend);
+    else test_disk(disk, leaf_index[leaf], (int32_t)leaf, sr, t_min, best);
+  }
+};
+
 // the return of one ray: t, inc and count from the first hit (its row `first`) and the blend sums (count = 0: window = 0, no second pass)
 DC_HD void surfel_finish(const SurfelHit& best, const double* __restrict__ first, const SurfelBlend& b, const SurfelRay& r, double& t,
                          double& inc, int32_t& count) {

@@ -2,10 +2,11 @@
 // frame at sweep time 0 of its scan, x' = D(tau) x (dc_sweepmath.h: the arithmetic dc_sweep_rays and dc_raycast_sweep render with).
 // C ABI at the bottom (include/dc_hip.h); DESIGN "Moving-sweep rendering and de-skew".
 //
-// One lane per point, one launch for every scan: the scan is found by the clamped bisection of dc_raycast_rays (the index stays in
-// [0, n_scans), so offsets that do not span [0, n] cannot move a read outside twists).  A lane reads everything it needs before it
+// One lane per point, one launch for every scan: the scan is found by dc::scan_of (dc_bvh.h), the clamped bisection of dc_raycast_rays
+// (the index stays in [0, n_scans), so offsets that do not span [0, n] cannot move a read outside twists).  A lane reads everything it needs before it
 // writes, and no lane touches another's rows, so the outputs may be the inputs (DC_F64); the pointers are not __restrict__ for that.
 #include "dc_common.h"
+#include "dc_bvh.h"
 #include "dc_sweepmath.h"
 #include "dc_hostutil.h"
 #include "../../include/dc_hip.h"
@@ -21,12 +22,7 @@ __global__ void __launch_bounds__(kSweepBlock) deskew_kernel(const T* points, co
                                                              double* vps_out, double* normals_out) {
   const int64_t g = (int64_t)blockIdx.x * kSweepBlock + threadIdx.x;
   if (g >= total) return;
-  int lo = 0, hi = n_scans;                       // the last s in [0, n_scans) with scan_offset[s] <= g (scan 0 when there is none)
-  while (hi - lo > 1) {
-    const int mid = lo + (hi - lo) / 2;
-    if (scan_offset[mid] <= g) lo = mid; else hi = mid;
-  }
-  const double* tw = twists + 6 * (int64_t)lo;
+  const double* tw = twists + 6 * (int64_t)dc::scan_of(scan_offset, n_scans, g);
   const double tg = tau[g];
   const double t0 = tw[0], t1 = tw[1], t2 = tw[2];
   const dc::SweepRot r = dc::sweep_rot(tg, tw[3], tw[4], tw[5]);

@@ -1073,11 +1073,63 @@ class IcpSequence:
 # ------------------------------------------------------------------------------------------------
 # triangle-mesh ray casting (dc_raycast.hip)
 # ------------------------------------------------------------------------------------------------
+def _scene_box_arg(scene_box):
+    """``scene_box`` (6 floats: lo xyz, hi xyz) as the host float64 array the tree builds take."""
+    import numpy as np
+    box = np.ascontiguousarray(np.asarray(scene_box, dtype=np.float64).reshape(6))
+    if not (np.isfinite(box).all() and (box[3:] >= box[:3]).all()):
+        raise ValueError('scene_box must be finite with hi >= lo, got %s' % box)
+    return box
+
+
+def _tree_arrays(n, dev):                    # -> leaf index i32 [n], child i32 [n-1,2], parent i32 [2n-1], node_box f32 [2n-1,6]
+    return (torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((max(n - 1, 0), 2), dtype=torch.int32, device=dev),
+            torch.empty((2 * n - 1,), dtype=torch.int32, device=dev), torch.empty((2 * n - 1, 6), dtype=torch.float32, device=dev))
+
+
+def _scan_offset_arg(scan_offset, s, n, dev):
+    """s + 1 scan offsets from 0 to n.  An int64 device tensor is taken as it is, not read back (the kernels clamp the scan index: wrong
+    offsets give wrong poses, never a read outside a per-scan array; ``dev`` None: only its shape is checked).  A host sequence is checked."""
+    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
+        if dev is not None:
+            return need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)
+        if tuple(scan_offset.shape) != (s + 1,):
+            raise ValueError('scan_offset has shape %s, expected %s' % (tuple(scan_offset.shape), (s + 1,)))
+        return scan_offset
+    off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
+    if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+        raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    return off
+
+
+def _measured_rays_arg(dev, vps, dirs, scan_offset, poses, what='rays'):
+    """The checks raycast_rays, surfel_cast_rays and raycast_beams share -> (n, dtype code, s, scan offsets)."""
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n = dirs.shape[0]
+    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
+    code = dtype_code(dirs)
+    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
+    s = poses.shape[0]
+    off = _scan_offset_arg(scan_offset, s, n, dev)
+    if n and s < 1:
+        raise ValueError('%s need at least one pose' % what)
+    return n, code, s, off
+
+
+def _t_min_arg(t_min, n=None, dev=None):
+    """``t_min`` -> (per-ray device tensor f64 [n] or None, float): a tensor is taken per ray where ``n`` is given."""
+    if n is not None and isinstance(t_min, torch.Tensor):
+        return need(t_min, (n,), dtype=torch.float64, name='t_min', device=dev), 0.0
+    tm = float(t_min)
+    if tm != tm:
+        raise ValueError('t_min must not be NaN')
+    return None, tm
+
+
 @on_device
 def bvh_build(verts, faces, scene_box):
     """LBVH of verts f64 [V,3] / faces i32 [F,3] (indices checked here) in the box ``scene_box`` (6 floats: lo xyz, hi xyz) ->
     mesh.MeshBVH (leaf_face i32 [F], child i32 [F-1,2], parent i32 [2F-1], node_box f32 [2F-1,6], leaf_tri f64 [F,9])."""
-    import numpy as np
     from .mesh import MeshBVH
     need(verts, (None, 3), dtype=torch.float64, name='verts')
     need(faces, (None, 3), dtype=torch.int32, name='faces', device=verts.device)
@@ -1087,14 +1139,9 @@ def bvh_build(verts, faces, scene_box):
     lo, hi = int(faces.min()), int(faces.max())
     if lo < 0 or hi >= nv_:
         raise ValueError('face indices must lie in [0, %d), got [%d, %d]' % (nv_, lo, hi))
-    box = np.ascontiguousarray(np.asarray(scene_box, dtype=np.float64).reshape(6))
-    if not (np.isfinite(box).all() and (box[3:] >= box[:3]).all()):
-        raise ValueError('scene_box must be finite with hi >= lo, got %s' % box)
+    box = _scene_box_arg(scene_box)
     dev = verts.device
-    leaf_face = torch.empty((nf,), dtype=torch.int32, device=dev)
-    child = torch.empty((max(nf - 1, 0), 2), dtype=torch.int32, device=dev)
-    parent = torch.empty((2 * nf - 1,), dtype=torch.int32, device=dev)
-    node_box = torch.empty((2 * nf - 1, 6), dtype=torch.float32, device=dev)
+    leaf_face, child, parent, node_box = _tree_arrays(nf, dev)
     leaf_tri = torch.empty((nf, 9), dtype=torch.float64, device=dev)
     nbytes = lib().dc_bvh_workspace_bytes(nf)
     ws = _ws(nbytes, dev)
@@ -1136,25 +1183,8 @@ def raycast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, cull=True):
     of |dirs[i]| (inf on a miss), inc f64 [N] the incidence angle on the face that was hit (NaN on a miss)).  Hits count beyond
     ``t_min`` (and facing the ray with ``cull``); traversal and tie rule are raycast's.  One launch (dc_raycast_rays)."""
     dev = bvh.leaf_face.device
-    need(dirs, (None, 3), name='dirs', device=dev)
-    n = dirs.shape[0]
-    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
-    code = dtype_code(dirs)
-    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
-    s = poses.shape[0]
-    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
-        # offsets already on the device are not read back (no synchronisation): the kernel clamps the scan index, so wrong offsets
-        # give wrong poses, never a read outside ``poses``
-        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)
-    else:
-        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
-        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
-    if n and s < 1:
-        raise ValueError('rays need at least one pose')
-    tm = float(t_min)
-    if tm != tm:
-        raise ValueError('t_min must not be NaN')
+    n, code, s, off = _measured_rays_arg(dev, vps, dirs, scan_offset, poses)
+    tm = _t_min_arg(t_min)[1]
     face = torch.empty((n,), dtype=torch.int32, device=dev)
     t = torch.empty((n,), dtype=torch.float64, device=dev)
     inc = torch.empty((n,), dtype=torch.float64, device=dev)
@@ -1173,7 +1203,6 @@ def surfel_bvh_build(points, normals, radii, scene_box):
     """LBVH over the surfels of a surveyed cloud: the two-sided disks (points[i], normals[i], radii[i]), f64 [M,3] / [M,3] / [M]
     (radii finite and > 0 and normals finite and non-zero, checked here), in the box ``scene_box`` (6 floats: lo xyz, hi xyz) ->
     survey.SurfelBVH (leaf_index i32 [M], child i32 [M-1,2], parent i32 [2M-1], node_box f32 [2M-1,6], leaf_disk f64 [M,8])."""
-    import numpy as np
     from .survey import SurfelBVH
     need(points, (None, 3), dtype=torch.float64, name='points')
     dev = points.device
@@ -1188,13 +1217,8 @@ def surfel_bvh_build(points, normals, radii, scene_box):
         raise ValueError('surfel points must be finite')
     if not bool((torch.isfinite(normals).all(dim=1) & (normals != 0).any(dim=1)).all()):
         raise ValueError('surfel normals must be finite and not zero')
-    box = np.ascontiguousarray(np.asarray(scene_box, dtype=np.float64).reshape(6))
-    if not (np.isfinite(box).all() and (box[3:] >= box[:3]).all()):
-        raise ValueError('scene_box must be finite with hi >= lo, got %s' % box)
-    leaf_index = torch.empty((m,), dtype=torch.int32, device=dev)
-    child = torch.empty((max(m - 1, 0), 2), dtype=torch.int32, device=dev)
-    parent = torch.empty((2 * m - 1,), dtype=torch.int32, device=dev)
-    node_box = torch.empty((2 * m - 1, 6), dtype=torch.float32, device=dev)
+    box = _scene_box_arg(scene_box)
+    leaf_index, child, parent, node_box = _tree_arrays(m, dev)
     leaf_disk = torch.empty((m, 8), dtype=torch.float64, device=dev)
     nbytes = lib().dc_surfel_bvh_workspace_bytes(m)
     ws = _ws(nbytes, dev)
@@ -1216,23 +1240,8 @@ def surfel_cast_rays(bvh, vps, dirs, scan_offset, poses, t_min=0.0, window=0.0, 
     (0 <= min_cos < 1) of the first hit's, weighted 1 - r^2 / rho^2; window = 0: t = t_first, inc on the first disk, count 1.
     One launch (dc_surfel_cast_rays)."""
     dev = bvh.leaf_index.device
-    need(dirs, (None, 3), name='dirs', device=dev)
-    n = dirs.shape[0]
-    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
-    code = dtype_code(dirs)
-    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
-    s = poses.shape[0]
-    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
-        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)       # as raycast_rays: not read back
-    else:
-        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
-        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
-    if n and s < 1:
-        raise ValueError('rays need at least one pose')
-    tm, win, mc = float(t_min), float(window), float(min_cos)
-    if tm != tm:
-        raise ValueError('t_min must not be NaN')
+    n, code, s, off = _measured_rays_arg(dev, vps, dirs, scan_offset, poses)
+    tm, win, mc = _t_min_arg(t_min)[1], float(window), float(min_cos)
     if not win >= 0.0:
         raise ValueError('window must be >= 0, got %r' % (window,))
     if not 0.0 <= mc < 1.0:
@@ -1303,20 +1312,7 @@ def raycast_beams(bvh, vps, dirs, scan_offset, poses, pattern, r0, spread, t_min
     ``t_min``: a float, or a device tensor f64 [N] of per-beam near clips.  ``want_samples`` adds (sub_face i32 [N,S], sub_t f64
     [N,S], sub_w f64 [N,S]) of every sub-ray (-1 / inf / 0 for one that is not a hit)."""
     dev = bvh.leaf_face.device
-    need(dirs, (None, 3), name='dirs', device=dev)
-    n = dirs.shape[0]
-    need(vps, (n, 3), dtype=dirs.dtype, name='vps', device=dev)
-    code = dtype_code(dirs)
-    need(poses, (None, 4, 4), dtype=torch.float64, name='poses', device=dev)
-    s = poses.shape[0]
-    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
-        off = need(scan_offset, (s + 1,), dtype=torch.int64, name='scan_offset', device=dev)      # clamped by the kernel, as in raycast_rays
-    else:
-        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
-        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
-    if n and s < 1:
-        raise ValueError('beams need at least one pose')
+    n, code, s, off = _measured_rays_arg(dev, vps, dirs, scan_offset, poses, what='beams')
     pat, r0, spread = _beam_pattern_arg(pattern, r0, spread, True)
     ns = pat.shape[0]
     if weight not in nv.BEAM_WEIGHTS:
@@ -1328,12 +1324,7 @@ def raycast_beams(bvh, vps, dirs, scan_offset, poses, pattern, r0, spread, t_min
         raise ValueError('tau must lie in (0, 1], got %r' % (tau,))
     if isinstance(min_hits, bool) or int(min_hits) != min_hits or not 1 <= int(min_hits) <= ns:
         raise ValueError('min_hits must be an int in 1 .. %d, got %r' % (ns, min_hits))
-    if isinstance(t_min, torch.Tensor):
-        tm_beam, tm = need(t_min, (n,), dtype=torch.float64, name='t_min', device=dev), 0.0
-    else:
-        tm_beam, tm = None, float(t_min)
-        if tm != tm:
-            raise ValueError('t_min must not be NaN')
+    tm_beam, tm = _t_min_arg(t_min, n, dev)
     face = torch.empty((n,), dtype=torch.int32, device=dev)
     depth = torch.empty((n,), dtype=torch.float64, device=dev)
     n_hits = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -1382,15 +1373,7 @@ def _sweep_args(rows, tau, scan_offset, twists, poses=None):
     s = tw.shape[0]
     if poses is not None and (not isinstance(poses, torch.Tensor) or tuple(poses.shape) != (s, 4, 4)):
         raise ValueError('poses must be a tensor [%d,4,4], one per twist' % s)
-    if isinstance(scan_offset, torch.Tensor) and scan_offset.is_cuda:
-        # offsets already on the device are not read back, as in raycast_rays: the kernels clamp the scan index
-        if tuple(scan_offset.shape) != (s + 1,):
-            raise ValueError('scan_offset has shape %s, expected %s' % (tuple(scan_offset.shape), (s + 1,)))
-        off = scan_offset
-    else:
-        off = torch.as_tensor(scan_offset, dtype=torch.int64).reshape(-1)
-        if off.numel() != s + 1 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
-            raise ValueError('scan_offset must hold %d non-decreasing offsets from 0 to %d, got %s' % (s + 1, n, off.tolist()))
+    off = _scan_offset_arg(scan_offset, s, n, None)         # the device, and with it the rest of a device tensor's checks, come below
     if n and s < 1:
         raise ValueError('rays need at least one scan')
     dev = need(first, name=rows[0][0]).device
@@ -1432,12 +1415,7 @@ def raycast_sweep(bvh, vps, dirs, tau, scan_offset, poses, twists, t_min=0.0, cu
     dev = bvh.leaf_face.device
     need(dirs, name='dirs', device=dev)
     code = dtype_code(dirs)
-    if isinstance(t_min, torch.Tensor):
-        tm_ray, tm = need(t_min, (n,), dtype=torch.float64, name='t_min', device=dev), 0.0
-    else:
-        tm_ray, tm = None, float(t_min)
-        if tm != tm:
-            raise ValueError('t_min must not be NaN')
+    tm_ray, tm = _t_min_arg(t_min, n, dev)
     face = torch.empty((n,), dtype=torch.int32, device=dev)
     t = torch.empty((n,), dtype=torch.float64, device=dev)
     inc = torch.empty((n,), dtype=torch.float64, device=dev)

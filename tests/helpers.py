@@ -88,7 +88,7 @@ def raycast_host_lib():
     """hostcheck_lib() with the ray exports (rebuilt when the library at hand predates them)."""
     import ctypes
     lib = hostcheck_lib()
-    if not hasattr(lib, 'dc_host_ray_cast_brute'):
+    if not hasattr(lib, 'dc_host_ray_cast_walk'):
         import __graft_entry__ as ge
         ge.build()
         lib = hostcheck_lib()
@@ -103,6 +103,8 @@ def raycast_host_lib():
     lib.dc_host_ray_cast_brute.argtypes = [vp, vp, i64, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
     lib.dc_host_ray_test_pairs.restype = None
     lib.dc_host_ray_test_pairs.argtypes = [vp, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
+    lib.dc_host_ray_cast_walk.restype = None
+    lib.dc_host_ray_cast_walk.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
     return lib
 
 
@@ -156,6 +158,20 @@ def host_ray_cast_brute(lib, tri, o, d, t_min, cull, face_id=None, threads=8):
                                    1 if cull else 0, face[s:].ctypes.data, t[s:].ctypes.data, u[s:].ctypes.data, v[s:].ctypes.data)
     with ThreadPoolExecutor(threads) as pool:
         list(pool.map(run, range(0, n, step)))
+    return face, t, u, v
+
+
+def host_ray_cast_walk(lib, child, node_box, leaf_tri, leaf_face, o, d, t_min, cull):
+    """cast_ray on the host (dc::bvh_walk with the kernels' visitor) over the tree (child i32 [n-1,2], node_box f32 [2n-1,6], leaf_tri
+    [n,9], leaf_face i32 [n]) -> (face i32 [R], t, u, v f64 [R]), as host_ray_cast_brute."""
+    child, box = np.ascontiguousarray(child, dtype=np.int32), np.ascontiguousarray(node_box, dtype=np.float32)
+    tri, ids, o, d = _c64(leaf_tri, 9), np.ascontiguousarray(leaf_face, dtype=np.int32), _c64(o, 3), _c64(d, 3)
+    nf, n = tri.shape[0], o.shape[0]
+    assert child.shape == (nf - 1, 2) and box.shape == (2 * nf - 1, 6) and ids.shape == (nf,) and d.shape[0] == n
+    t_min = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float64), (n,)))
+    face, t, u, v = np.empty(n, np.int32), np.empty(n), np.empty(n), np.empty(n)
+    lib.dc_host_ray_cast_walk(child.ctypes.data, box.ctypes.data, tri.ctypes.data, ids.ctypes.data, nf, o.ctypes.data, d.ctypes.data,
+                              t_min.ctypes.data, n, 1 if cull else 0, face.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data)
     return face, t, u, v
 
 

@@ -5,6 +5,8 @@ oracle      the kernels' own test_triangle (host build of dc_raymath.h) applied 
 classify    an independent classifier that shares no arithmetic with the header: Moeller-Trumbore in numpy fp64 over all faces, in
             coordinates local to ``center``.  Per ray: clear hit, clear miss or borderline.
 check_bvh   the invariants of test_gpu_raycast.test_bvh_structure as a function.
+build_tree  trees of a chosen shape over given leaf boxes, in the library's node numbering: what the one walk (csrc/dc_bvh.h) is
+            run over in tests/test_bvh_walk_host.py and tests/test_gpu_bvh_walk.py.
 """
 import numpy as np
 
@@ -164,6 +166,36 @@ def check_bvh(bvh, mesh):
         depth += 1
         assert depth <= 64
     assert (node == 0).all()
+
+
+MAX_DEPTH = 63              # of a tree the walk may be given (csrc/dc_bvh.h: its stack holds one postponed node per level)
+
+
+def build_tree(leaf_box, comb=0):
+    """A binary tree over the leaves 0 .. n-1, in this order, with the boxes leaf_box f32 [n,6]: internal nodes 0 .. n-2 numbered in
+    pre-order (root 0), leaf i is node n-1+i, an inner box the exact min / max of its children's.  The first ``comb`` levels split off
+    the LAST leaf of their range as the second child (a left-deep comb: the rest is the first child), the levels below split at the
+    median.  -> (child i32 [n-1,2], parent i32 [2n-1], node_box f32 [2n-1,6], depth); the depth must not exceed MAX_DEPTH."""
+    leaf_box = np.asarray(leaf_box, dtype=np.float32).reshape(-1, 6)
+    n = len(leaf_box)
+    child, parent = np.zeros((n - 1, 2), dtype=np.int32), np.full(2 * n - 1, -1, dtype=np.int32)
+    box = np.concatenate([np.zeros((n - 1, 6), dtype=np.float32), leaf_box])
+    used, deepest = [0], [0]
+
+    def node(lo, hi, level):
+        deepest[0] = max(deepest[0], level)
+        if hi - lo == 1:
+            return n - 1 + lo
+        i = used[0]
+        used[0] += 1
+        mid = hi - 1 if level < comb else (lo + hi) // 2
+        a, b = node(lo, mid, level + 1), node(mid, hi, level + 1)
+        child[i], parent[[a, b]] = (a, b), i
+        box[i] = np.concatenate([np.minimum(box[a, :3], box[b, :3]), np.maximum(box[a, 3:], box[b, 3:])])
+        return i
+    node(0, n, 0)
+    assert deepest[0] <= MAX_DEPTH, deepest[0]
+    return child, parent, box, deepest[0]
 
 
 # ---- the scenes of tests/test_gpu_raycast_edge.py (checked on the host by tests/test_raycast_host.py) --------------------------------
@@ -398,6 +430,28 @@ def case_shape(shape):
     aimed = np.concatenate([np.tile(np.arange(500) >= 400, 3), np.zeros(200, dtype=bool)])
     case = Case('shape-%s' % shape, verts, faces, cull, scene_box=scene_box)
     return case.rays(np.zeros((len(dirs), 3)), dirs, counts, sensors, 0.0, aimed)
+
+
+def case_stack(n=64):
+    """``n`` faces of different shape in ONE plane (z = 2), all around the point below the sensor, the face order shuffled: a ray at
+    the middle enters every box at the same distance and hits every face at the same t up to rounding, so nothing is pruned and a
+    walk postpones one node per level.  Rays at the middle, at the rim (some faces only) and past every face."""
+    rng = np.random.default_rng(27)
+    k = 1.0 + rng.permutation(n)[:, None] * 2.0 ** -6
+    verts = np.stack([np.concatenate([-k, -k, np.full((n, 1), 2.0)], 1), np.concatenate([k, -k, np.full((n, 1), 2.0)], 1),
+                      np.concatenate([0 * k, k, np.full((n, 1), 2.0)], 1)], 1).reshape(-1, 3)
+    x = np.concatenate([rng.uniform(-0.3, 0.3, size=(120, 2)), rng.uniform(-2.2, 2.2, size=(120, 2))])
+    x = np.concatenate([x, np.full((len(x), 1), 2.0)], 1)
+    o = np.array([0.125, -0.25, 4.0])
+    case = Case('stack-%d' % n, verts, np.arange(3 * n).reshape(-1, 3), True)
+    return case.rays(np.zeros((len(x), 3)), _unit(x - o), [len(x)], [o], 0.0, False)
+
+
+def leaf_arrays(lib, case, order):
+    """(leaf_tri f64 [n,9], leaf_face i32 [n], leaf boxes f32 [n,6]) of ``case`` with the faces ``order`` at the leaves 0 .. n-1."""
+    from helpers import host_ray_boxes
+    tri = np.ascontiguousarray(np.asarray(case.verts, dtype=np.float64)[case.faces[order]].reshape(-1, 9))
+    return tri, np.asarray(order, dtype=np.int32), host_ray_boxes(lib, tri)
 
 
 def all_cases():

@@ -23,7 +23,7 @@ def surfel_host_lib():
     """helpers.raycast_host_lib() with the surfel exports (rebuilt when the library at hand predates them)."""
     from helpers import raycast_host_lib
     lib = raycast_host_lib()
-    if not hasattr(lib, 'dc_host_surfel_cast_brute'):
+    if not hasattr(lib, 'dc_host_surfel_cast_walk'):
         import __graft_entry__ as ge
         ge.build()
         lib = raycast_host_lib()
@@ -34,6 +34,8 @@ def surfel_host_lib():
     lib.dc_host_surfel_test_pairs.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
     lib.dc_host_surfel_cast_brute.restype = None
     lib.dc_host_surfel_cast_brute.argtypes = [vp, vp, i64, vp, vp, i64, f64, f64, f64, vp, vp, vp, vp, vp]
+    lib.dc_host_surfel_cast_walk.restype = None
+    lib.dc_host_surfel_cast_walk.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64, f64, f64, f64, vp, vp, vp, vp, vp]
     lib.dc_host_surfel_acos.restype = None
     lib.dc_host_surfel_acos.argtypes = [vp, i64, vp]
     lib.dc_host_surfel_t_err.restype = f64
@@ -89,6 +91,20 @@ def host_cast_brute(lib, rows, o, d, t_min, window, min_cos, index=None, threads
                                       inc[s:].ctypes.data, cnt[s:].ctypes.data)
     with ThreadPoolExecutor(threads) as pool:
         list(pool.map(run, range(0, n, step)))
+    return idx, t1, t, inc, cnt
+
+
+def host_cast_walk(lib, child, node_box, leaf_disk, leaf_index, o, d, t_min, window, min_cos):
+    """surfel_cast_kernel on the host (dc::bvh_walk with the kernel's visitors) over the tree (child i32 [m-1,2], node_box f32
+    [2m-1,6], leaf_disk [m,8], leaf_index i32 [m]) -> as host_cast_brute, the blend summed in the order of the walk."""
+    child, box = np.ascontiguousarray(child, dtype=np.int32), np.ascontiguousarray(node_box, dtype=np.float32)
+    rows, ids, o, d = _c64(leaf_disk, 8), np.ascontiguousarray(leaf_index, dtype=np.int32), _c64(o, 3), _c64(d, 3)
+    m, n = rows.shape[0], o.shape[0]
+    assert child.shape == (m - 1, 2) and box.shape == (2 * m - 1, 6) and ids.shape == (m,) and d.shape[0] == n
+    idx, t1, t, inc, cnt = np.empty(n, np.int32), np.empty(n), np.empty(n), np.empty(n), np.empty(n, np.int32)
+    lib.dc_host_surfel_cast_walk(child.ctypes.data, box.ctypes.data, rows.ctypes.data, ids.ctypes.data, m, o.ctypes.data, d.ctypes.data, n,
+                                 float(t_min), float(window), float(min_cos), idx.ctypes.data, t1.ctypes.data, t.ctypes.data,
+                                 inc.ctypes.data, cnt.ctypes.data)
     return idx, t1, t, inc, cnt
 
 
