@@ -27,6 +27,8 @@ MAX_MODEL_TERMS = 8
 # include/dc_hip.h: the ICP registration state (DC_ICP_STATE_*), its block partials and status codes (DC_ICP_*)
 DC_ICP_STATE_COUNT, DC_ICP_STATE_POSE, DC_ICP_STATE_PRIOR, DC_ICP_STATE_PAIRS, DC_ICP_STATE_SSE, DC_ICP_STATE_OVERLAP = 64, 0, 16, 48, 49, 50
 DC_ICP_MAX_SMOOTH, DC_ICP_PARTIALS = 8, 30
+# the twist state and block partials of the sweep-aware iteration (DC_ICP_CT_*)
+DC_ICP_CT_STATE_COUNT, DC_ICP_CT_STATE_TWIST, DC_ICP_CT_STATE_PRIOR_TWIST, DC_ICP_CT_PARTIALS = 16, 0, 6, 93
 # include/dc_hip.h: limits and layout of dc_bias_accumulate's out
 DC_BIAS_MAX_BINS, DC_BIAS_MAX_TERMS, DC_BIAS_TOTALS, DC_BIAS_BIN_COLS = 256, 4, 5, 9
 # include/dc_hip.h: finite-beam rendering
@@ -192,6 +194,9 @@ _SIGNATURES = {
     'dc_icp_init': (_i32, [_vp, _vp, _vp, _vp]),
     'dc_icp_accumulate': (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
     'dc_icp_finish': (_i32, [_vp, _i32, _i64, _f64, _f64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp]),
+    'dc_icp_ct_init': (_i32, [_vp, _vp, _vp]),
+    'dc_icp_ct_accumulate': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'dc_icp_ct_finish': (_i32, [_vp, _i32, _i64, _f64, _f64, _i32, _i32, _f64, _f64, _i32, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     'dc_map_select': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     'dc_dyn_directions': (_i32, [_vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp]),
     'dc_dyn_update': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),

@@ -243,6 +243,12 @@ class Config(object):
         # has sweep times with the constant-velocity twist of its prior motion times slam_sweep_fraction before the mapper sees it
         self.slam_deskew = False
         self.slam_sweep_fraction = 1.0
+        # sweep-aware registration (DESIGN "Sweep-aware registration"): the ICP estimates the twist of every scan that has sweep times
+        # together with its pose; that twist of the prior motion is then the prior twist.  Not together with slam_deskew.
+        self.slam_ct = False
+        self.slam_ct_prior = [1e-4, 1e-4]       # [beta_v, beta_w]: weight per kept pair of the twist's departure from its prior
+                                                # (measured, DESIGN: larger values pull the twist to a noisy odometry's)
+        self.slam_ct_max_twist = None           # [trans, rot] bound of that departure; None: [icp_max_translation, icp_max_rotation]
         # dynamic points in the map (launch/slam.launch compute_prob_dynamic and its parameters; DESIGN "Dynamic points in the map").
         # slam.launch runs with compute_prob_dynamic on; the three switches are off here so that existing results and timings stand.
         self.slam_compute_prob_dynamic = False  # update the map points' probabilities of being dynamic before every map update

@@ -151,6 +151,30 @@ int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double m
   return 0;
 }
 
+// dc_icp_ct_finish on the host, likewise: partials [n_blocks, DC_ICP_CT_PARTIALS], state [DC_ICP_STATE_COUNT], ct_state
+// [DC_ICP_CT_STATE_COUNT] and status [4] are host arrays.
+int dc_host_icp_ct_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
+                          double max_rot, double max_trans, int min_pairs, double beta_v, double beta_w, double max_twist_trans,
+                          double max_twist_rot, double* state, double* ct_state, int32_t* status) {
+  if (!partials || !state || !ct_state || !status || n_blocks < 1 || n_blocks > dc::kIcpBlocksMax || m < 0) return 1;
+  if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1 || !(beta_v >= 0.0) || !(beta_w >= 0.0)) return 1;
+  if (status[0] != 0) return 0;
+  double tot[DC_ICP_CT_PARTIALS], work[dc::kIcpCtWork];
+  for (int q = 0; q < DC_ICP_CT_PARTIALS; ++q) tot[q] = dc::icp_ct_block_sum(partials, n_blocks, q);
+  const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
+  const dc::IcpCtParams cp{beta_v, beta_w, max_twist_trans, max_twist_rot};
+  dc::icp_ct_finish_tail(tot, m, prm, cp, state, ct_state, status, work);
+  return 0;
+}
+
+// The left Jacobian of SO(3) (dc_sweepmath.h): J [9] row-major = J_l(a) for a [3]; u [3] (optional) -> jtu [3] = J_l(a)^T u.
+void dc_host_sweep_left_jacobian(const double* a, double* J, const double* u, double* jtu) {
+  const dc::SweepRot r = dc::sweep_rot(1.0, a[0], a[1], a[2]);
+  const dc::SweepJl j = dc::sweep_left_jacobian(r);
+  dc::sweep_jl_matrix(r, j, J);
+  if (u && jtu) dc::sweep_jl_transposed(r, j, u[0], u[1], u[2], jtu);
+}
+
 // dc_mesh_closest's per-triangle step: closest point of tri (a, b, c) [9] to p [3] -> closest [3], *region (optional) the branch
 // taken (dc::kTri*); returns the squared distance the kernel compares
 double dc_host_closest_on_triangle(const double* tri, const double* p, double* closest, int* region) {

@@ -159,4 +159,131 @@ DC_HD void icp_finish_tail(const double* tot, int64_t m, const IcpParams& prm, d
   if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;      // CounterTransformationChecker: stop, keep the estimate
 }
 
+// ---- the sweep-aware (12-dof) iteration: pose at the sweep's start and the twist (v, w) of the sweep; DESIGN "Sweep-aware
+// registration", include/dc_hip.h.  Unknowns in the order (d theta, d t, d v, d w). ----
+
+// JtJ packed as its upper triangle row by row: 78 entries.
+DC_HD int sym12_index(int r, int c) {
+  if (r > c) { const int t = r; r = c; c = t; }
+  return r * 12 - (r * (r - 1)) / 2 + (c - r);
+}
+
+// icp_solve6's factorisation and pivot rule for the 12 x 12 system (A row-major, full): x = -A^-1 b, 1 = singular.  L [144] and
+// y [12] are the caller's: the finish kernel keeps them in LDS, where a runtime index costs no private segment.
+DC_HD int icp_solve12(const double* A, const double* b12, double* x12, double* Lw, double* y, double rel_eps = 1e-12) {
+  double (*L)[12] = (double (*)[12])Lw;
+  double dmax = 0.0;
+  for (int i = 0; i < 12; ++i) dmax = fmax(dmax, fabs(A[i * 12 + i]));
+  if (!(dmax > 0.0) || !isfinite(dmax)) return 1;
+  for (int j = 0; j < 12; ++j) {
+    double s = A[j * 12 + j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    if (!(s > rel_eps * dmax) || !isfinite(s)) return 1;
+    const double d = sqrt(s);
+    L[j][j] = d;
+    for (int i = j + 1; i < 12; ++i) {
+      double t = A[i * 12 + j];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = t / d;
+    }
+  }
+  for (int i = 0; i < 12; ++i) {                 // L y = -b
+    double t = -b12[i];
+    for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
+    y[i] = t / L[i][i];
+  }
+  for (int i = 11; i >= 0; --i) {                // L^T x = y
+    double t = y[i];
+    for (int k = i + 1; k < 12; ++k) t -= L[k][i] * x12[k];
+    x12[i] = t / L[i][i];
+  }
+  return 0;
+}
+
+struct IcpCtParams {
+  double beta_v, beta_w;                  // the constant-velocity prior's weights (dimensionless, per kept pair)
+  double max_twist_trans, max_twist_rot;  // largest |v - v0| and |w - w0|
+};
+
+DC_HD double icp_norm3(const double* a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
+
+// The single-thread tail of dc_icp_ct_finish once the DC_ICP_CT_PARTIALS totals are complete; st is the 6-dof state
+// [DC_ICP_STATE_COUNT] (pose, prior, history, pairs / SSE / overlap as icp_finish_tail keeps them), ct the twist state
+// [DC_ICP_CT_STATE_COUNT].  The order of icp_finish_tail: count, record, DC_ICP_FAIL_PAIRS, the prior N beta (twist - prior twist)
+// added to the system, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE, DC_ICP_FAIL_BOUND (the pose bound, |w| > pi, the twist bound;
+// every failure leaves pose and twist as they were), pose, twist and history updated, DC_ICP_CONVERGED, DC_ICP_MAX_ITERS.
+constexpr int kIcpCtWork = 144 + 144 + 3 * 12;      // doubles of icp_ct_finish_tail's workspace: A, L, b, x, y
+
+DC_HD void icp_ct_finish_tail(const double* tot, int64_t m, const IcpParams& prm, const IcpCtParams& cp, double* st, double* ct,
+                              int32_t* status, double* work) {
+  const int iter = status[1] + 1;
+  status[1] = iter;
+  const double pairs = tot[90];
+  st[DC_ICP_STATE_PAIRS] = pairs;
+  st[DC_ICP_STATE_SSE] = tot[91];
+  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[92] / (double)m : 0.0;
+  if (pairs < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
+  double *A = work, *L = work + 144, *b = work + 288, *x = work + 300, *y = work + 312;
+  for (int r = 0; r < 12; ++r) {
+    for (int c = 0; c < 12; ++c) A[r * 12 + c] = tot[sym12_index(r, c)];
+    b[r] = tot[78 + r];
+  }
+  const double* tw = ct + DC_ICP_CT_STATE_TWIST;
+  const double* tw0 = ct + DC_ICP_CT_STATE_PRIOR_TWIST;
+  for (int q = 0; q < 6; ++q) {
+    const double wgt = pairs * (q < 3 ? cp.beta_v : cp.beta_w);
+    A[(6 + q) * 12 + 6 + q] += wgt;
+    b[6 + q] += wgt * (tw[q] - tw0[q]);
+  }
+  if (icp_solve12(A, b, x, L, y)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
+  double Tn[16], twn[6];
+  icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
+  for (int q = 0; q < 6; ++q) twn[q] = tw[q] + x[6 + q];
+  bool finite = true;
+  for (int q = 0; q < 12; ++q) finite = finite && isfinite(x[q]);
+  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
+  for (int q = 0; q < 6; ++q) finite = finite && isfinite(twn[q]);
+  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  double C[16];
+  rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);
+  const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
+  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
+  double dtw[6];
+  for (int q = 0; q < 6; ++q) dtw[q] = twn[q] - tw0[q];
+  if (!(icp_norm3(twn + 3) <= 3.14159265358979323846) || !(icp_norm3(dtw) <= cp.max_twist_trans) || !(icp_norm3(dtw + 3) <= cp.max_twist_rot)) {
+    status[0] = DC_ICP_FAIL_BOUND;
+    return;
+  }
+  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
+  for (int q = 0; q < 6; ++q) ct[DC_ICP_CT_STATE_TWIST + q] = twn[q];
+  const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
+  st[DC_ICP_STATE_HIST_ROT + slot] = fmax(icp_norm3(x), icp_norm3(x + 9));
+  st[DC_ICP_STATE_HIST_TRANS + slot] = fmax(icp_norm3(x + 3), icp_norm3(x + 6));
+  if (iter >= prm.smooth) {
+    double mr = 0.0, mt = 0.0;
+    for (int h = 0; h < prm.smooth; ++h) {
+      const int s = (iter - 1 - h) % DC_ICP_MAX_SMOOTH;
+      mr += st[DC_ICP_STATE_HIST_ROT + s];
+      mt += st[DC_ICP_STATE_HIST_TRANS + s];
+    }
+    mr /= (double)prm.smooth;
+    mt /= (double)prm.smooth;
+    if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
+  }
+  if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;
+}
+
+// icp_lane_sum / icp_block_sum for rows of DC_ICP_CT_PARTIALS values: the same order.
+DC_HD double icp_ct_lane_sum(const double* partials, int n_blocks, int q, int l) {
+  double s = 0.0;
+  for (int b = l; b < n_blocks; b += kIcpSumLanes) s += partials[(int64_t)b * DC_ICP_CT_PARTIALS + q];
+  return s;
+}
+
+DC_HD double icp_ct_block_sum(const double* partials, int n_blocks, int q) {
+  double tot = 0.0;
+  for (int l = 0; l < kIcpSumLanes; ++l) tot += icp_ct_lane_sum(partials, n_blocks, q, l);
+  return tot;
+}
+
 }  // namespace dc

@@ -87,4 +87,83 @@ DC_HD void sweep_point(const SweepRot& r, double tau, double v0, double v1, doub
   y[2] = y[2] + tau * v2;
 }
 
+// The left Jacobian of SO(3) at a = tau w (dc_icp_ct_accumulate: the derivative of Exp(tau w) x by w; DESIGN "Sweep-aware
+// registration"):  Exp(a + da) = Exp(J_l(a) da) Exp(a) to first order,
+//   J_l(a) = I + C1 [a]x + C2 [a]x^2,   C1 = (1 - cos th) / th^2 = (sin h / h)^2 / 2 = B of sweep_rot (no cancellation),
+//   C2 = (th - sin th) / th^3.
+// th - sin th cancels for small th (its rounding error is about u th against th^3 / 6), so below th = 1 C2 is its series
+//   1/6 - x/120 + x^2/5040 - ... + x^8 / 19!,  x = th^2,
+// nine terms in Horner's form: the first one left out, x^9 / 21!, is below 2e-20 at th = 1, a thousandth of a rounding of 1/6.  At
+// th >= 1 the difference is at least 0.158 and is formed directly.  th < 2^-26: J_l = I + [a]x / 2 (C1 = 1/2, C2 = 0; what is left
+// out, th^2 / 6, is below 2^-54).  NaN stays NaN.
+//
+// Error of an entry of J_l against the exact matrix of the same doubles a, th <= pi, counted as above in units of u = 2^-52:
+//   th: the squares 1/2 each and two sums 1/2 each, halved by the root, + 1/2:                                 |dth| <= 1.25 th
+//   q = sin h / h: argument |h cot h - 1| * 1.25 <= 1.25, sincos 2, quotient 1/2: 3.75;  C1 = q q / 2: 2 * 3.75 + 1/2 = 8 relative
+//   d = th - sin th with the same rounded th on both sides: (1 - cos th) th 1.25 + 2 sin th + d / 2; relative to d this is largest
+//     at th = 1: (0.575 + 1.683) / 0.1585 + 1/2 = 14.8;  th^3 = (th th) th: 3 * 1.25 + 1 = 4.75;  quotient 1/2:  C2 <= 20 relative
+//     (the series: x carries 3, which moves C2 by less than 1; Horner's roundings add less than 1 1/2: below 3)
+//   C1 [a]x: 8 + 1/2 on |C1 a_k| <= th / 2:                                                                           4.25 th
+//   [a]x^2 entries a_i a_j (1/2) or -(a_j^2 + a_k^2) (1): with C2 <= 1/6, (20 + 1 + 1/2) th^2 / 6:                     3.6 th^2
+//   the two sums: 1/2 (1 + th / 2) + 1/2 (1 + th / 2 + th^2 / 6)
+// together below 1 + 4.75 th + 3.7 th^2 (52.5 at th = pi).  The tests hold every entry to that count.
+struct SweepJl {
+  double C1, C2;
+};
+
+DC_HD SweepJl sweep_left_jacobian(const SweepRot& r) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  SweepJl j;
+  const double x = r.a0 * r.a0 + r.a1 * r.a1 + r.a2 * r.a2;
+  const double th = sqrt(x);
+  j.C1 = r.B;
+  if (th < 0x1p-26) {
+    j.C2 = 0.0;
+  } else if (th < 1.0) {
+    double s = 1.0 / 121645100408832000.0;                   // 1 / 19!
+    s = 1.0 / 355687428096000.0 - x * s;                     // 1 / 17!
+    s = 1.0 / 1307674368000.0 - x * s;                       // 1 / 15!
+    s = 1.0 / 6227020800.0 - x * s;                          // 1 / 13!
+    s = 1.0 / 39916800.0 - x * s;                            // 1 / 11!
+    s = 1.0 / 362880.0 - x * s;                              // 1 / 9!
+    s = 1.0 / 5040.0 - x * s;                                // 1 / 7!
+    s = 1.0 / 120.0 - x * s;                                 // 1 / 5!
+    j.C2 = 1.0 / 6.0 - x * s;
+  } else {                        // NaN comes here and stays NaN
+    j.C2 = (th - sin(th)) / ((th * th) * th);
+  }
+  return j;
+}
+
+// y = J_l(a)^T u = (u - C1 (a x u)) + C2 (a x (a x u))     ([a]x is skew, its square symmetric)
+DC_HD void sweep_jl_transposed(const SweepRot& r, const SweepJl& j, double u0, double u1, double u2, double* y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double c0 = r.a1 * u2 - r.a2 * u1, c1 = r.a2 * u0 - r.a0 * u2, c2 = r.a0 * u1 - r.a1 * u0;
+  const double e0 = r.a1 * c2 - r.a2 * c1, e1 = r.a2 * c0 - r.a0 * c2, e2 = r.a0 * c1 - r.a1 * c0;
+  y[0] = (u0 - j.C1 * c0) + j.C2 * e0;
+  y[1] = (u1 - j.C1 * c1) + j.C2 * e1;
+  y[2] = (u2 - j.C1 * c2) + j.C2 * e2;
+}
+
+// J = J_l(a), row-major 3 x 3: (I + C1 [a]x) + C2 [a]x^2 entry by entry
+DC_HD void sweep_jl_matrix(const SweepRot& r, const SweepJl& j, double* J) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double a0 = r.a0, a1 = r.a1, a2 = r.a2;
+  J[0] = 1.0 + j.C2 * -(a1 * a1 + a2 * a2);
+  J[1] = -(j.C1 * a2) + j.C2 * (a0 * a1);
+  J[2] = j.C1 * a1 + j.C2 * (a0 * a2);
+  J[3] = j.C1 * a2 + j.C2 * (a0 * a1);
+  J[4] = 1.0 + j.C2 * -(a0 * a0 + a2 * a2);
+  J[5] = -(j.C1 * a0) + j.C2 * (a1 * a2);
+  J[6] = -(j.C1 * a1) + j.C2 * (a0 * a2);
+  J[7] = j.C1 * a0 + j.C2 * (a1 * a2);
+  J[8] = 1.0 + j.C2 * -(a0 * a0 + a1 * a1);
+}
+
 }  // namespace dc

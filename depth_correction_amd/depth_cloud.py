@@ -43,7 +43,7 @@ class DepthCloud(object):
 
     def __init__(self, vps=None, dirs=None, depth=None, points=None, mean=None, cov=None, eigvals=None, eigvecs=None,
                  normals=None, inc_angles=None, trace=None, loss=None, mask=None, neighbors=None, distances=None,
-                 neighbor_points=None, weights=None, dir_neighbors=None, dir_neighbor_weights=None, dir_distances=None):
+                 neighbor_points=None, weights=None, dir_neighbors=None, dir_neighbor_weights=None, dir_distances=None, sweep_t=None):
         if vps is None:
             vps = torch.zeros((1, 3))
         assert isinstance(vps, torch.Tensor) and vps.shape[-1] == 3
@@ -56,6 +56,11 @@ class DepthCloud(object):
         self.neighbors, self.weights, self._distances, self.neighbor_points = neighbors, weights, distances, neighbor_points
         self.dir_neighbors, self.dir_neighbor_weights, self.dir_distances = dir_neighbors, dir_neighbor_weights, dir_distances
         self._feat = None           # (key, outputs) of the last fused feature evaluation
+        # optional: the sweep time of every point, float64 [N] (a moving-sweep scan on its way to the mapper, slam.mapper_input).  Not
+        # one of all_fields -- no feature, filter or file format reads it -- but a per-row field all the same: copy, clone, to and
+        # every row selection take it along; operations that merge clouds (concatenate, +) have no use for it and drop it.
+        assert sweep_t is None or (isinstance(sweep_t, torch.Tensor) and tuple(sweep_t.shape) == (dirs.shape[0],))
+        self.sweep_t = sweep_t
 
     # ---- container ---------------------------------------------------------------------------------
     @property
@@ -76,10 +81,11 @@ class DepthCloud(object):
         return {f: self._raw(f) for f in DepthCloud.all_fields if self._raw(f) is not None}
 
     def copy(self):
-        return DepthCloud(**self._present())
+        return DepthCloud(sweep_t=self.sweep_t, **self._present())
 
     def clone(self):
-        return DepthCloud(**{f: (x if x is _STALE else x.clone()) for f, x in self._present().items()})
+        return DepthCloud(sweep_t=None if self.sweep_t is None else self.sweep_t.clone(),
+                          **{f: (x if x is _STALE else x.clone()) for f, x in self._present().items()})
 
     def size(self):
         return self.dirs.shape[0]
@@ -90,6 +96,12 @@ class DepthCloud(object):
         return self.depth.device
 
     def __getitem__(self, item):
+        out = self._rows(item)
+        if self.sweep_t is not None:                 # the sweep times follow their rows (a list of field names selects no rows)
+            out.sweep_t = self.sweep_t if (isinstance(item, list) and len(item) > 0 and isinstance(item[0], str)) else self.sweep_t[item]
+        return out
+
+    def _rows(self, item):
         if isinstance(item, list) and len(item) > 0 and isinstance(item[0], str):
             return DepthCloud(**{f: getattr(self, f) for f in item})
         if isinstance(item, torch.Tensor) and item.dtype == torch.bool and item.dim() == 1 and item.is_cuda:
@@ -122,7 +134,7 @@ class DepthCloud(object):
             if (float_type and is_f) or (int_type and not is_f) or (dtype and dtype.is_floating_point == is_f):
                 t = dtype or float_type or int_type
             out[f] = x.to(device=device, dtype=t)
-        return DepthCloud(**out)
+        return DepthCloud(sweep_t=None if self.sweep_t is None else self.sweep_t.to(device=device), **out)      # (times stay float64)
 
     def cpu(self):
         return self.to(torch.device('cpu'))

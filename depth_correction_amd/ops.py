@@ -1913,6 +1913,77 @@ def icp_finish(partials, m, state, status, min_rot, min_trans, smooth, max_iters
 
 
 @on_device
+def deskew_device_twist(points, normals, tau, twist, scan_offset, points_out, normals_out):
+    """dc_deskew of one scan under a twist that lives on the device (f64 [6], the estimate of a sweep-aware registration), into
+    ``points_out`` / ``normals_out`` f64 [M,3]; ``scan_offset`` the device int64 [0, M].  Nothing is read back: the host-side check of
+    deskew (finite, |w| <= pi) is left out, dc_icp_ct_finish keeps the twist inside that bound."""
+    dev = points.device
+    need(points, (None, 3), dtype=torch.float64, name='points')
+    m = points.shape[0]
+    need(normals, (m, 3), dtype=torch.float64, name='normals', device=dev)
+    need(tau, (m,), dtype=torch.float64, name='tau', device=dev)
+    need(twist, (6,), dtype=torch.float64, name='twist', device=dev)
+    need(scan_offset, (2,), dtype=torch.int64, name='scan_offset', device=dev)
+    need(points_out, (m, 3), dtype=torch.float64, name='points_out', device=dev)
+    need(normals_out, (m, 3), dtype=torch.float64, name='normals_out', device=dev)
+    if m:
+        check(lib().dc_deskew(ptr(points), None, ptr(normals), dtype_code(points), ptr(tau), m, ptr(scan_offset), ptr(twist), 1,
+                              ptr(points_out), None, ptr(normals_out), stream_ptr()), 'dc_deskew')
+
+
+@on_device
+def icp_ct_init(twist, ct_state):
+    """ct_state f64 [DC_ICP_CT_STATE_COUNT] of a sweep-aware registration whose twist starts from, and is held to, twist f64 device [6]
+    (dc_icp_ct_init; icp_init sets the pose state and the status word)."""
+    need(twist, (6,), dtype=torch.float64, name='twist')
+    need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=twist.device)
+    check(lib().dc_icp_ct_init(ptr(twist), ptr(ct_state), stream_ptr()), 'dc_icp_ct_init')
+
+
+@on_device
+def icp_ct_accumulate(reading, q, nq, tau, map_points, map_normals, idx, dist, threshold, cos_min, state, ct_state, status, partials,
+                      kept=None):
+    """icp_accumulate for the sweep-aware iteration: the pairs of the de-skewed points ``q`` / normals ``nq`` (deskew_device_twist of
+    ``reading`` at ``tau``) -> block partials f64 [icp_blocks(M), DC_ICP_CT_PARTIALS] (dc_icp_ct_accumulate)."""
+    dev = reading.device
+    need(reading, (None, 3), dtype=torch.float64, name='reading')
+    m = reading.shape[0]
+    need(q, (m, 3), dtype=torch.float64, name='q', device=dev)
+    need(nq, (m, 3), dtype=torch.float64, name='nq', device=dev)
+    need(tau, (m,), dtype=torch.float64, name='tau', device=dev)
+    need(map_points, (None, 3), dtype=torch.float64, name='map_points', device=dev)
+    need(map_normals, tuple(map_points.shape), dtype=torch.float64, name='map_normals', device=dev)
+    need(idx, (m, None), dtype=torch.int32, name='idx', device=dev)
+    k = idx.shape[1]
+    need(dist, (m, k), dtype=torch.float64, name='dist', device=dev)
+    need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    nb = icp_blocks(m)
+    need(partials, (nb, nv.DC_ICP_CT_PARTIALS), dtype=torch.float64, name='partials', device=dev)
+    if kept is not None:
+        need(kept, (m, k), dtype=torch.uint8, name='kept', device=dev)
+    check(lib().dc_icp_ct_accumulate(ptr(reading), ptr(q), ptr(nq), ptr(tau), m, ptr(map_points), ptr(map_normals), ptr(idx), ptr(dist), k,
+                                     ptr(threshold), float(cos_min), ptr(state), ptr(ct_state), ptr(status), ptr(partials), nb, ptr(kept),
+                                     stream_ptr()), 'dc_icp_ct_accumulate')
+
+
+@on_device
+def icp_ct_finish(partials, m, state, ct_state, status, min_rot, min_trans, smooth, max_iters, max_rot, max_trans, beta_v, beta_w,
+                  max_twist_trans, max_twist_rot, min_pairs=6):
+    """Solve the 12 x 12 system with the twist prior, update pose and twist and check, in one block (dc_icp_ct_finish)."""
+    dev = partials.device
+    need(partials, (None, nv.DC_ICP_CT_PARTIALS), dtype=torch.float64, name='partials')
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    check(lib().dc_icp_ct_finish(ptr(partials), partials.shape[0], int(m), float(min_rot), float(min_trans), int(smooth), int(max_iters),
+                                 float(max_rot), float(max_trans), int(min_pairs), float(beta_v), float(beta_w), float(max_twist_trans),
+                                 float(max_twist_rot), ptr(state), ptr(ct_state), ptr(status), stream_ptr()), 'dc_icp_ct_finish')
+
+
+@on_device
 def map_select(reading, normals, depth, pose, dist1, min_dist, max_range):
     """(mask bool [M], points f64 [M,3], normals f64 [M,3]): reading points and normals moved by pose f64 device [4,4] and the mask of
     those the map takes -- nearest map point (dist1 [M]; None = empty map) beyond min_dist, depth <= max_range (dc_map_select)."""

@@ -17,12 +17,14 @@ from . import ops
 from .config import Config, SLAM
 from .utils import delta_transform, rotation_angle, translation_norm
 
-__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'dynamic_params', 'mapper_input', 'odometry_cov', 'odometry_poses',
+__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'LAUNCHES_PER_ITERATION_CT', 'dynamic_params', 'mapper_input', 'odometry_cov', 'odometry_poses',
            'path_lengths', 'run_slam', 'slam_errors']
 
 # launches of one ICP iteration: dc_knn_grid_query 3 (moved queries, the 16-lanes-per-query search, the tail search), dc_quantile 18
 # (a state memset, 8 x histogram + pick, next value, threshold), dc_icp_accumulate 1, dc_icp_finish 1
 LAUNCHES_PER_ITERATION = 23
+# the sweep-aware iteration: dc_deskew 1 more, dc_icp_ct_accumulate and dc_icp_ct_finish in the places of the two last
+LAUNCHES_PER_ITERATION_CT = 24
 FAILED = ('empty', 'too_few_pairs', 'singular', 'not_finite', 'bound')
 
 
@@ -95,11 +97,34 @@ def mapper_input(cloud, model, cfg: Config):
     from .online import correct_cloud
     from .preproc import filtered_cloud
     cloud = filtered_cloud(cloud, cfg)
+    if cfg.slam_ct and 't' in (getattr(getattr(cloud, 'dtype', None), 'names', None) or ()):
+        return _timed_input(cloud, model, cfg)           # (only the sweep-aware registration reads the times)
     if model is not None:
         return correct_cloud(cloud, model, cfg)
     if isinstance(cloud, DepthCloud):
         return cloud
     return DepthCloud.from_structured_array(cloud, dtype=np.float64, device=cfg.device)
+
+
+def _timed_input(cloud, model, cfg: Config):
+    """mapper_input for a structured cloud with sweep times (the field ``t``; the host filters above select rows of the structured
+    array, times included): the same DepthCloud with the times as its ``sweep_t`` f64 [N].  The correction is online.correct_cloud
+    itself, given the cloud it would have made from the array; its filters and the model's copy take the times along
+    (DepthCloud.sweep_t)."""
+    from .depth_cloud import DepthCloud
+    from .online import correct_cloud
+    t = torch.as_tensor(np.ascontiguousarray(cloud['t'], dtype=np.float64), device=cfg.device)
+    if model is None:
+        dc = DepthCloud.from_structured_array(cloud, dtype=np.float64, device=cfg.device)
+        dc.sweep_t = t
+        return dc
+    dc = DepthCloud.from_structured_array(cloud, dtype=cfg.numpy_float_type(), device=cfg.device)     # local_feature_cloud's own call
+    dc.sweep_t = t
+    dc = correct_cloud(dc, model, cfg)
+    if dc.sweep_t is None or dc.sweep_t.shape[0] != len(dc):
+        raise RuntimeError('the sweep times did not follow their points through the correction (%s times, %d points)'
+                           % ('no' if dc.sweep_t is None else dc.sweep_t.shape[0], len(dc)))
+    return dc
 
 
 def dynamic_params(cfg: Config):
@@ -129,10 +154,10 @@ def dynamic_params(cfg: Config):
 
 class MapperScan(object):
     """A reading as the ICP uses it: points fp64 [M,3] in the sensor frame, their normals [M,3] (k nearest neighbours inside the scan,
-    oriented toward the sensor: input_filters.yaml) and depths [M]."""
+    oriented toward the sensor: input_filters.yaml) and depths [M]; ``t`` (optional) fp64 [M], the sweep time of every point."""
 
-    def __init__(self, points, normals, depth):
-        self.points, self.normals, self.depth = points, normals, depth
+    def __init__(self, points, normals, depth, t=None):
+        self.points, self.normals, self.depth, self.t = points, normals, depth, t
 
     def __len__(self):
         return self.points.shape[0]
@@ -198,19 +223,27 @@ class IcpMapper(object):
         dc.update_all(k=min(int(self.cfg.slam_normals_k), m))
         normals = torch.nan_to_num(dc.normals.detach(), nan=0.0).to(torch.float64).contiguous()
         depth = dc.depth.detach().reshape(-1).to(torch.float64).contiguous()
-        return MapperScan(pts, normals, depth)
+        t = getattr(cloud, 'sweep_t', None)
+        if t is not None:
+            t = t.detach().to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+            if t.shape[0] != m:
+                raise ValueError('%d sweep times for %d points' % (t.shape[0], m))
+        return MapperScan(pts, normals, depth, t)
 
     # ---- registration ---------------------------------------------------------------------------------------------------------
-    def _info(self, status, iterations=0, overlap=0.0, pairs=0, sse=0.0):
+    def _info(self, status, iterations=0, overlap=0.0, pairs=0, sse=0.0, launches=LAUNCHES_PER_ITERATION):
         return dict(status=status, ok=status not in FAILED, iterations=iterations, overlap=overlap, pairs=pairs, sse=sse,
-                    host_reads=self.host_reads, launches_per_iteration=LAUNCHES_PER_ITERATION)
+                    host_reads=self.host_reads, launches_per_iteration=launches)
 
-    def register(self, scan, prior):
+    def register(self, scan, prior, twist=None):
         """Pose of ``scan`` in the map from ``prior`` (4 x 4): ICP iterations queued ``status_every`` at a time, one status read
         after each group.  An empty scan or failed registration returns the prior; an empty map returns the prior with status
-        'init' (the first scan initialises the map)."""
+        'init' (the first scan initialises the map).  With cfg.slam_ct and a scan that has sweep times the twist of the sweep is
+        estimated with the pose (register_ct), from ``twist`` [6] = (v0, w0) as start and prior (zero when None)."""
         cfg = self.cfg
         scan = self.prepare(scan)
+        if cfg.slam_ct and scan.t is not None:
+            return self.register_ct(scan, prior, twist)
         prior = np.asarray(prior, dtype=np.float64).reshape(4, 4)
         self.host_reads = 0
         m = len(scan)
@@ -260,6 +293,104 @@ class IcpMapper(object):
                            kept=kept)
         ops.icp_finish(partials, len(scan), self.state, self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans, cfg.icp_smooth_length,
                        cfg.icp_max_iters, cfg.icp_max_rotation, cfg.icp_max_translation)
+
+    # ---- sweep-aware registration (DESIGN "Sweep-aware registration") ---------------------------------------------------------------
+    def ct_params(self):
+        """(beta_v, beta_w, max_twist_trans, max_twist_rot) of cfg, checked (ValueError)."""
+        cfg = self.cfg
+        beta = [float(b) for b in cfg.slam_ct_prior]
+        mt = cfg.slam_ct_max_twist
+        mt = [float(cfg.icp_max_translation), float(cfg.icp_max_rotation)] if mt is None else [float(b) for b in mt]
+        if len(beta) != 2 or not all(b >= 0.0 and np.isfinite(b) for b in beta):
+            raise ValueError('slam_ct_prior must be [beta_v, beta_w], finite and >= 0, got %r' % (cfg.slam_ct_prior,))
+        if len(mt) != 2:
+            raise ValueError('slam_ct_max_twist must be [trans, rot], got %r' % (cfg.slam_ct_max_twist,))
+        return beta[0], beta[1], mt[0], mt[1]
+
+    def ct_buffers(self, m):
+        """The device buffers of a sweep-aware registration of an m-point scan: the twist state, the de-skewed points and normals
+        (scratch, rewritten by every iteration), the scan offsets of dc_deskew and the block partials."""
+        dev = self.device
+        return dict(ct=torch.zeros((nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, device=dev),
+                    q=torch.empty((m, 3), dtype=torch.float64, device=dev), nq=torch.empty((m, 3), dtype=torch.float64, device=dev),
+                    off=torch.tensor([0, m], dtype=torch.int64, device=dev),
+                    partials=torch.empty((ops.icp_blocks(m), nv.DC_ICP_CT_PARTIALS), dtype=torch.float64, device=dev))
+
+    def register_ct(self, scan, prior, twist=None):
+        """register() with the twist (v, w) of the sweep as six more unknowns: -> (pose at sweep time 0, info).  info['twist'] is the
+        estimated twist (the prior twist when the registration fails) and info['deskewed'] the scan de-skewed by it (points and
+        normals of a last dc_deskew, the depths as they were), which is what update / update_dynamic are to be given."""
+        cfg = self.cfg
+        prior = np.asarray(prior, dtype=np.float64).reshape(4, 4)
+        twist0 = np.zeros(6) if twist is None else np.asarray(twist, dtype=np.float64).reshape(6)
+        if not np.isfinite(twist0).all() or float(np.linalg.norm(twist0[3:])) > np.pi:
+            raise ValueError('the prior twist must be finite with a rotation of at most pi, got %r' % (twist0,))
+        prm = self.ct_params()
+        self.host_reads = 0
+        m = len(scan)
+        launches = LAUNCHES_PER_ITERATION_CT
+
+        def ended(status, **kw):
+            info = self._info(status, launches=launches, **kw)
+            info['twist'], info['deskewed'] = twist0.copy(), scan
+            return prior.copy(), info
+        if m == 0:
+            return ended('empty')
+        if self.n_map == 0:
+            # the first scan: nothing to register against, the map takes it de-skewed by the prior twist
+            x, _, nx = ops.deskew(scan.points, scan.t, [0, m], twist0[None], normals=scan.normals)
+            pose, info = ended('init')
+            info['deskewed'] = MapperScan(x, nx, scan.depth, scan.t)
+            return pose, info
+        grid, map_pts, map_nrm, _ = self.reference(m)
+        if grid is None:
+            return ended('too_few_pairs')
+        dev, k = self.device, self.knn
+        idx = torch.empty((m, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((m, k), dtype=torch.float64, device=dev)
+        thr = torch.empty((1,), dtype=torch.float64, device=dev)
+        buf = self.ct_buffers(m)
+        pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
+        cos_min = float(np.cos(cfg.icp_max_normal_angle))
+        ops.icp_init(torch.as_tensor(prior, device=dev), self.state, self.status)
+        ops.icp_ct_init(torch.as_tensor(twist0, device=dev), buf['ct'])
+        done = 0
+        code = 0
+        while done < cfg.icp_max_iters:
+            for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
+                self.iteration_ct(scan, pose_d, idx, dist, thr, buf, map_pts, map_nrm, cos_min, prm, grid=grid)
+                done += 1
+            st = self.status.cpu()
+            self.host_reads += 1
+            code = int(st[0])
+            if code != 0:
+                break
+        st = self.state.cpu().numpy()
+        iters = int(self.status[1].item())
+        info = self._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
+                          float(st[nv.DC_ICP_STATE_SSE]), launches=launches)
+        if not info['ok']:
+            info['twist'], info['deskewed'] = twist0.copy(), scan
+            return prior.copy(), info
+        tw = buf['ct'][nv.DC_ICP_CT_STATE_TWIST:nv.DC_ICP_CT_STATE_TWIST + 6]
+        ops.deskew_device_twist(scan.points, scan.normals, scan.t, tw, buf['off'], buf['q'], buf['nq'])      # by the final twist
+        info['twist'] = tw.cpu().numpy().copy()
+        info['deskewed'] = MapperScan(buf['q'], buf['nq'], scan.depth, scan.t)
+        return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+
+    def iteration_ct(self, scan, pose_d, idx, dist, thr, buf, map_pts, map_nrm, cos_min, prm, kept=None, grid=None):
+        """One sweep-aware iteration, queued on the stream: de-skew by the device's twist, match, trimmed threshold, pairs and
+        partials, the 12 x 12 solve and the update of pose and twist.  ``buf`` from ct_buffers, ``prm`` from ct_params."""
+        cfg = self.cfg
+        tw = buf['ct'][nv.DC_ICP_CT_STATE_TWIST:nv.DC_ICP_CT_STATE_TWIST + 6]
+        ops.deskew_device_twist(scan.points, scan.normals, scan.t, tw, buf['off'], buf['q'], buf['nq'])
+        ops.knn_grid_query(self.grid if grid is None else grid, buf['q'], pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx,
+                           dist=dist)
+        ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
+        ops.icp_ct_accumulate(scan.points, buf['q'], buf['nq'], scan.t, map_pts, map_nrm, idx, dist, thr, cos_min, self.state, buf['ct'],
+                              self.status, buf['partials'], kept=kept)
+        ops.icp_ct_finish(buf['partials'], len(scan), self.state, buf['ct'], self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans,
+                          cfg.icp_smooth_length, cfg.icp_max_iters, cfg.icp_max_rotation, cfg.icp_max_translation, *prm)
 
     # ---- map ------------------------------------------------------------------------------------------------------------------
     def _ensure_grid(self, m):
@@ -387,6 +518,12 @@ class IcpMapper(object):
         self._ensure_grid(m)
         return added
 
+    def clear(self):
+        """Empty the map (points, normals, probabilities, grids); the buffers and the counters of grid builds stay."""
+        self.n_map, self.n_dynamic = 0, 0
+        self.last_dyn, self._ref, self.grid = None, None, None
+        self._version += 1
+
     def map_points(self, static_only=False):
         """(points, normals) fp64 [N,3] of the map (world frame); ``static_only``: the rows with P < cfg.slam_threshold_dynamic."""
         pts, nrm = self._pts[:self.n_map], self._nrm[:self.n_map]
@@ -396,15 +533,44 @@ class IcpMapper(object):
         return pts, nrm
 
 
+def _redo_first_scan(mapper, first, pose0, scan, prior, twist, pose, info, info0, cfg, passes=2):
+    """The first scan of a sweep-aware run has no map to be registered against, so its twist cannot be estimated: it entered the map
+    de-skewed by the odometry's first step, and a map bent by that step's error bends every later estimate with it.  Once the second
+    scan is registered, the constant-velocity twist of the first is known from the registered step pose0^-1 pose instead (times
+    cfg.slam_sweep_fraction): the map, which holds nothing but the first scan, is rebuilt from the scan de-skewed by that twist and
+    the second scan registered again, ``passes`` times.  Returns the second scan's (pose, info); info0 (the first scan's) gets the
+    twist used, ``added`` and ``map_size``.  A registration that fails on the way ends it with that result."""
+    from .sweep import motion_twist
+    m = len(first)
+    for _ in range(passes):
+        tw0 = float(cfg.slam_sweep_fraction) * motion_twist(delta_transform(pose0, pose))
+        if not np.isfinite(tw0).all() or float(np.linalg.norm(tw0[3:])) > np.pi:
+            break
+        x, _, nx = ops.deskew(first.points, first.t, [0, m], tw0[None], normals=first.normals)
+        mapper.clear()
+        info0['added'] = mapper.update(MapperScan(x, nx, first.depth, first.t), pose0)
+        info0['map_size'], info0['twist'] = mapper.n_map, tw0
+        pose, info = mapper.register(scan, prior, twist=twist)
+        if not info['ok']:
+            break
+    return pose, info
+
+
 def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     """The mapper over one sequence with the perturbed odometry of cfg.odom_cov (robot_data): prior[i] = slam[i-1] odom[i-1]^-1 odom[i],
     slam[0] = odom[0] = gt[0]; a failed registration keeps its prior and leaves the map and its probabilities as they are.  Every info
     has ``dynamic`` (map points with P >= cfg.slam_threshold_dynamic) and ``dyn`` (update_dynamic's counts, None when it did not run).
     With cfg.slam_deskew a cloud that carries sweep times (the field ``t``) is de-skewed before anything else sees it, with the twist
     of slam[i-1]^-1 prior[i] times cfg.slam_sweep_fraction (preproc.deskew_cloud; the poses hold at the sweep's start).
+    With cfg.slam_ct the cloud is left as it is, that twist is the prior twist of the sweep-aware registration (IcpMapper.register_ct)
+    and the map takes the scan de-skewed by the estimated twist (info['twist']); both together are refused (ValueError).  The first
+    scan of an empty map is de-skewed by the odometry's first step and, once the second scan is registered, again by the twist of
+    the registered step (_redo_first_scan).
     Returns dict(slam, odom, gt [N,4,4], path_lengths [N], info [N dicts], ids)."""
     if cfg.slam not in SLAM:
         raise ValueError('unknown SLAM pipeline %r; available: %s' % (cfg.slam, ', '.join(SLAM)))
+    if cfg.slam_ct and cfg.slam_deskew:
+        raise ValueError('slam_ct estimates the twist of a sweep inside the ICP and slam_deskew removes it beforehand: set one of them')
     items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in dataset]
     gt = np.stack([pose for _, pose in items]) if items else np.zeros((0, 4, 4))
     odom = odometry_poses(gt, cfg.odom_cov)
@@ -412,17 +578,30 @@ def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     mapper = mapper or IcpMapper(cfg)
     slam = odom.copy()
     infos = []
+    first = None
     for i, (cloud, _) in enumerate(items):
         prior = odom[0] if i == 0 else np.matmul(slam[i - 1], delta_transform(odom[i - 1], odom[i]))
-        if cfg.slam_deskew and 't' in (getattr(getattr(cloud, 'dtype', None), 'names', None) or ()):
+        twist = None
+        if (cfg.slam_deskew or cfg.slam_ct) and 't' in (getattr(getattr(cloud, 'dtype', None), 'names', None) or ()):
             # constant velocity: the sweep's twist is that of the motion from the last estimate to this prior (scan 0: the odometry's
             # first step; a single scan: none), times the part of the period the sweep takes
             from .preproc import deskew_cloud
             from .sweep import motion_twist
             step = delta_transform(slam[i - 1], prior) if i > 0 else (delta_transform(odom[0], odom[1]) if len(items) > 1 else np.eye(4))
-            cloud = deskew_cloud(cloud, float(cfg.slam_sweep_fraction) * motion_twist(step), device=mapper.device)
+            twist = float(cfg.slam_sweep_fraction) * motion_twist(step)
+            if cfg.slam_deskew:
+                cloud = deskew_cloud(cloud, twist, device=mapper.device)
         scan = mapper.prepare(mapper_input(cloud, model, cfg))
-        pose, info = mapper.register(scan, prior)
+        if cfg.slam_ct:
+            # the twist above is only the prior twist: the registration estimates the sweep's own and returns the scan de-skewed by it
+            pose, info = mapper.register(scan, prior, twist=twist)
+            if info['status'] == 'init' and scan.t is not None and len(scan) > 0:
+                first = scan                          # entered the map de-skewed by the odometry's first step: redone below
+            elif i == 1 and first is not None and info['ok']:
+                pose, info = _redo_first_scan(mapper, first, slam[0], scan, prior, twist, pose, info, infos[0], cfg)
+            scan = info.pop('deskewed', scan)
+        else:
+            pose, info = mapper.register(scan, prior)
         mapper.last_dyn = None
         if info['ok']:
             info['added'] = mapper.update(scan, pose, overlap=info['overlap'] if info['status'] != 'init' else None)

@@ -1102,6 +1102,40 @@ int dc_icp_finish(const double* partials, int n_blocks, int64_t m, double min_ro
 int dc_map_select(const double* reading, const double* normals, const double* depth, int64_t m, const double* pose, const double* dist1,
                   double min_dist, double max_range, uint8_t* mask_out, double* points_out, double* normals_out, dcStream_t stream);
 
+/* ---- sweep-aware registration: the scan's twist estimated inside the ICP (dc_slam.hip, dc_slam_math.h, dc_sweepmath.h; DESIGN
+ * "Sweep-aware registration").  Reading point p_i was measured at the sweep time tau_i; with the pose T = [R | t] of the sweep's start
+ * and the twist (v, w) of D(tau) = [Exp(tau w) | tau v] (dc_deskew's model):
+ *   q_i = D(tau_i) p_i,   x_i = R q_i + t,   r = n_map . (x_i - y).
+ * Unknown d = (d theta, d t, d v, d w): d theta and d t left-multiplied onto T as dc_icp_finish does, v += d v, w += d w.  The row of
+ * the Jacobian, with n_s = R^T n_map, a = tau w and u = Exp(a) p = q - tau v (the rotated point, without the translation):
+ *   [x x n_map, n_map, tau n_s, tau J_l(a)^T (u x n_s)],   J_l(a) = I + C1 [a]x + C2 [a]x^2 the left Jacobian of SO(3),
+ *   C1 = (sin(th/2) / (th/2))^2 / 2,  C2 = (th - sin th) / th^3  (series below th = 1; th < 2^-26: J_l = I + [a]x / 2).
+ * Normals take Exp(tau w), then R.  The cost carries the constant-velocity prior N (beta_v |v - v0|^2 + beta_w |w - w0|^2), N the
+ * kept pairs, added by dc_icp_ct_finish.  One iteration = dc_deskew (n_scans = 1, twists = the twist of ct_state) into q / nq +
+ * dc_knn_grid_query of q + dc_quantile + dc_icp_ct_accumulate + dc_icp_ct_finish; state, status word and status codes are
+ * dc_icp_init's, and a set status word makes the last two return at once. ---- */
+#ifndef DC_ICP_CT_STATE_COUNT
+#define DC_ICP_CT_STATE_COUNT 16          /* doubles of the twist state: */
+#define DC_ICP_CT_STATE_TWIST 0           /*   [6] the estimate (v, w) */
+#define DC_ICP_CT_STATE_PRIOR_TWIST 6     /*   [6] the prior twist (v0, w0) of the cost and of the twist bound; [12..15] zero */
+#define DC_ICP_CT_PARTIALS 93             /* doubles per block partial: JtJ upper triangle row by row (78), Jtr (12), pairs, sum r^2, points used */
+#endif
+/* ct_state double [DC_ICP_CT_STATE_COUNT] <- twist (DEVICE double [6] = (v0, w0)) as estimate and prior.  dc_icp_init sets the rest. */
+int dc_icp_ct_init(const double* twist, double* ct_state, dcStream_t stream);
+/* dc_icp_accumulate's pair filters, in its order and with its arithmetic, on the de-skewed points q / normals nq [m,3] (dc_deskew of
+ * reading / its normals at tau [m] under the twist of ct_state); partials double [n_blocks = dc_icp_blocks(m), DC_ICP_CT_PARTIALS]. */
+int dc_icp_ct_accumulate(const double* reading, const double* q, const double* nq, const double* tau, int64_t m, const double* map_points,
+                         const double* map_normals, const int32_t* idx, const double* dist, int knn, const double* threshold,
+                         double cos_min, const double* state, const double* ct_state, const int32_t* status, double* partials,
+                         int n_blocks, uint8_t* kept_out, dcStream_t stream);
+/* One block: the partials summed in dc_icp_finish's order, the prior added (H_vv += N beta_v I, g_v += N beta_v (v - v0), likewise w),
+ * the 12 x 12 Cholesky solve with dc_icp_finish's pivot rule, pose and twist updated, dc_icp_finish's checks with: the history holds
+ * max(angle(d theta), |d w|) and max(|d t|, |d v|); DC_ICP_FAIL_BOUND also when |w| > pi, |v - v0| > max_twist_trans or |w - w0| >
+ * max_twist_rot.  Every failure leaves pose and twist as they were. */
+int dc_icp_ct_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
+                     double max_rot, double max_trans, int min_pairs, double beta_v, double beta_w, double max_twist_trans,
+                     double max_twist_rot, double* state, double* ct_state, int32_t* status, dcStream_t stream);
+
 /* ---- dynamic points in the map (depth_correction_amd/csrc/dc_dynamic.hip, dc_dynmath.h; the rule and its deviations in DESIGN
  * "Dynamic points in the map"): launch/slam.launch compute_prob_dynamic, after Pomerleau et al., "Long-term 3D map maintenance in
  * dynamic environments" (ICRA 2014).  All fp64, sums and products unfused and in the order written.  One update = dc_dyn_directions

@@ -3,6 +3,10 @@ pillars, run through the mapper with the slam_eval.launch odometry noise.  Per s
 reads, map-update time and map size; launches per ICP iteration; the mean errors of SLAM and odometry.  Prints one JSON line.
 
     python tools/slam_bench.py [--poses 100] [--size 64 2048] [--grid-res 0.1]
+
+With --sweep the sequence is rendered as moving sweeps (render.SweepModel) and registered twice, by the 6-dof iteration on the raw
+scans and by the sweep-aware 12-dof iteration (cfg.slam_ct, the odometry's twist as prior twist): registration time, iterations, time
+and launches per iteration and the errors of both, side by side, in one JSON line.
 """
 import argparse
 import json
@@ -29,15 +33,68 @@ def _poses(n):
     return np.stack(out)
 
 
+def _sweep_compare(args):
+    """The swept sequence through both registrations: dict(six_dof=..., sweep_aware=...) of medians and errors."""
+    from depth_correction_amd.config import Config
+    from depth_correction_amd.mesh import room_mesh
+    from depth_correction_amd.render import RenderedMeshDataset, SweepModel
+    from depth_correction_amd.slam import IcpMapper, mapper_input, odometry_poses, path_lengths, slam_errors
+    from depth_correction_amd.sweep import motion_twist
+    from depth_correction_amd.utils import delta_transform
+    dev = 'cuda:0'
+    mesh = room_mesh((8.0, 5.0, 2.0), 0.5, pillars=[((2.0, 2.5, 0.0), (0.4, 0.4, 1.5)), ((-2.5, -2.5, 0.0), (0.5, 0.3, 1.5)),
+                                                    ((0.5, -1.0, 0.0), (0.3, 0.3, 1.5))])
+    path = os.path.join(tempfile.mkdtemp(), 'bench_room.ply')
+    mesh.save_ply(path)
+    gt = _poses(args.poses)
+    ds = RenderedMeshDataset(path, poses=gt, size=tuple(args.size), fov=(45.0, 360.0), num_segments=16, device=dev, sweep=SweepModel())
+    clouds = [c for c, _ in ds]
+    lengths = path_lengths(gt)
+    out = dict(tool='slam_bench', sweep=True, poses=args.poses, size=list(args.size), grid_res=args.grid_res, status_every=args.status_every)
+    for name, ct in (('six_dof', False), ('sweep_aware', True)):
+        cfg = Config(device=dev, float_type='float64', min_depth=0.5, max_depth=25.0, grid_res=args.grid_res,
+                     odom_cov=[1e-4] * 3 + [2.5e-3] * 3, slam_ct=ct)
+        odom = odometry_poses(gt, cfg.odom_cov)
+        mapper = IcpMapper(cfg, status_every=args.status_every)
+        slam = odom.copy()
+        rows = []
+        for i, cloud in enumerate(clouds):
+            scan = mapper.prepare(mapper_input(cloud, None, cfg))
+            prior = odom[0] if i == 0 else slam[i - 1] @ delta_transform(odom[i - 1], odom[i])
+            step = delta_transform(slam[i - 1], prior) if i > 0 else (delta_transform(odom[0], odom[1]) if len(clouds) > 1 else np.eye(4))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pose, info = mapper.register(scan, prior, twist=motion_twist(step))
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if info['ok']:
+                mapper.update(info.pop('deskewed', scan), pose, overlap=info['overlap'] if info['status'] != 'init' else None)
+            slam[i] = pose
+            rows.append(dict(register_ms=(t1 - t0) * 1e3, iterations=info['iterations'], status=info['status'],
+                             launches=info['launches_per_iteration']))
+        reg = [r for r in rows[1:] if r['iterations'] > 0]
+        out[name] = dict(register_ms_median=float(np.median([r['register_ms'] for r in reg])) if reg else None,
+                         iterations_median=float(np.median([r['iterations'] for r in reg])) if reg else None,
+                         ms_per_iteration_median=float(np.median([r['register_ms'] / r['iterations'] for r in reg])) if reg else None,
+                         launches_per_iteration=reg[0]['launches'] if reg else None,
+                         failed=[i for i, r in enumerate(rows) if r['status'] in ('empty', 'too_few_pairs', 'singular', 'not_finite', 'bound')],
+                         map_size_final=mapper.n_map, slam_errors=slam_errors(slam, gt, lengths))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--poses', type=int, default=100)
     ap.add_argument('--size', type=int, nargs=2, default=(64, 2048))
     ap.add_argument('--grid-res', type=float, default=0.1)
     ap.add_argument('--status-every', type=int, default=4)
+    ap.add_argument('--sweep', action='store_true', help='render moving sweeps and time the 6-dof and the sweep-aware registration')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('slam_bench needs a GPU')
+    if args.sweep:
+        print(json.dumps(_sweep_compare(args)))
+        return
     from depth_correction_amd.config import Config
     from depth_correction_amd.mesh import room_mesh
     from depth_correction_amd.render import RenderedMeshDataset
