@@ -39,6 +39,8 @@ BEAM_WEIGHTS = {'uniform': 0, 'lambert': 1}
 DC_ALIGN_STATE_COUNT, DC_ALIGN_STATE_POSE, DC_ALIGN_STATE_PRIOR, DC_ALIGN_STATE_THRESHOLD = 64, 0, 16, 32
 DC_ALIGN_STATE_PAIRS, DC_ALIGN_STATE_RMS, DC_ALIGN_STATE_D_ROT, DC_ALIGN_STATE_D_TRANS = 33, 34, 35, 36
 DC_ALIGN_PARTIALS, DC_ALIGN_HISTORY_COLS = 17, 5
+# include/dc_hip.h: bins per pair feature and values per descriptor of the global registration (DC_GREG_*)
+DC_GREG_BINS, DC_GREG_FEAT = 11, 33
 ALIGN_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'degenerate', -3: 'not_finite'}
 ICP_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'singular', -3: 'not_finite', -4: 'bound'}
 
@@ -219,6 +221,13 @@ _SIGNATURES = {
     'dc_survey_align_workspace_bytes': (_sz, [_i64]),
     'dc_survey_align': (_i32, [_vp, _sz, _i64, _vp, _i64, _vp, _i64, _vp, _f64, _f64, _i32, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
                                _vp]),
+    # global registration (csrc/dc_globalreg.hip)
+    'dc_pair_spfh': (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    'dc_pair_fpfh': (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'dc_feature_nn': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'dc_feature_nn_tile': (_i32, []),
+    'dc_greg_fit': (_i32, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    'dc_greg_score': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp]),
 }
 
 

@@ -18,6 +18,7 @@
 #include "dc_dynmath.h"
 #include "dc_rangeimage_math.h"
 #include "dc_align_math.h"
+#include "dc_globalreg_math.h"
 #include "dc_cons_route.h"
 
 extern "C" {
@@ -729,6 +730,64 @@ int dc_host_align_finish(const double* partials, int n_blocks, const double* ori
   const int row = status[1];
   double* hist = (history && row >= 0 && row < n_history_rows) ? history + (int64_t)row * DC_ALIGN_HISTORY_COLS : nullptr;
   dc::align_finish_tail(tot, origins, prm, state, status, hist);
+  return 0;
+}
+
+// ---- global registration (dc_globalreg_math.h; dc_globalreg.hip) ----
+// The pair feature: 1 and a [3], bins [3], *L for a valid pair, 0 otherwise
+int dc_host_pair_feature(const double* xi, const double* ni, const double* xj, const double* nj, double* a, int32_t* bins, double* L) {
+  const int ok = dc::greg_pair_feature(xi, ni, xj, nj, a, L);
+  if (ok) for (int c = 0; c < 3; ++c) bins[c] = dc::greg_bin(a[c]);
+  return ok;
+}
+
+float dc_host_feature_dist(const float* fq, const float* fs) { return dc::greg_feature_dist(fq, fs); }
+
+int64_t dc_host_greg_draw(int64_t seed, int64_t h, int t, int64_t C) { return dc::greg_draw((uint64_t)seed, (uint64_t)h, t, C); }
+
+int dc_host_greg_check_fit(const double* p, const double* y, const double* o, double min_edge, double rho, double* T, double* lam) {
+  return dc::greg_check_fit(p, y, o, min_edge, rho, T, lam);
+}
+
+double dc_host_greg_residual2(const double* T, const double* p, const double* y) { return dc::greg_residual2(T, p, y); }
+
+// dc_pair_spfh + dc_pair_fpfh on the host, point by point in the kernels' order: spfh double [n, 33] (scratch of the caller), m int32
+// [n], feat float [n, 33], has int32 [n].  0, or 1 for refused arguments.
+int dc_host_pair_histograms(const double* points, const double* normals, int64_t n, const int32_t* nbr, int k, double* spfh, int32_t* m,
+                            float* feat, int32_t* has) {
+  if (n < 0 || k < 1 || k > dc::kGregMaxK || (n > 0 && (!points || !normals || !nbr || !spfh || !m || !feat || !has))) return 1;
+  for (int64_t i = 0; i < n; ++i) {
+    int cnt[dc::kGregFeat] = {0};
+    int mi = 0;
+    for (int s = 0; s < k; ++s) {
+      const int32_t j = nbr[i * k + s];
+      double a[3], L;
+      if (j < 0 || j >= n || !dc::greg_pair_feature(points + 3 * i, normals + 3 * i, points + 3 * (int64_t)j, normals + 3 * (int64_t)j, a, &L))
+        continue;
+      ++mi;
+      for (int c = 0; c < 3; ++c) ++cnt[c * dc::kGregBins + dc::greg_bin(a[c])];
+    }
+    m[i] = mi;
+    for (int b = 0; b < dc::kGregFeat; ++b) spfh[i * dc::kGregFeat + b] = mi > 0 ? (double)cnt[b] / (double)mi : 0.0;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    double acc[dc::kGregFeat] = {0.0}, F[dc::kGregFeat];
+    for (int s = 0; s < k; ++s) {
+      const int32_t j = nbr[i * k + s];
+      double a[3], L;
+      if (j < 0 || j >= n || !dc::greg_pair_feature(points + 3 * i, normals + 3 * i, points + 3 * (int64_t)j, normals + 3 * (int64_t)j, a, &L))
+        continue;
+      for (int b = 0; b < dc::kGregFeat; ++b) acc[b] = dc::greg_fpfh_term(acc[b], L, spfh[(int64_t)j * dc::kGregFeat + b]);
+    }
+    for (int b = 0; b < dc::kGregFeat; ++b) F[b] = m[i] > 0 ? dc::greg_fpfh_value(spfh[i * dc::kGregFeat + b], m[i], acc[b]) : 0.0;
+    for (int c = 0; c < 3; ++c) {
+      double sum = 0.0;
+      for (int b = 0; b < dc::kGregBins; ++b) sum += F[c * dc::kGregBins + b];
+      const double scale = dc::greg_block_scale(sum);
+      for (int b = 0; b < dc::kGregBins; ++b) feat[i * dc::kGregFeat + c * dc::kGregBins + b] = (float)(F[c * dc::kGregBins + b] * scale);
+    }
+    has[i] = m[i] > 0 ? 1 : 0;
+  }
   return 0;
 }
 

@@ -427,7 +427,8 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
     cfg.grid_res (mapping_accuracy:106; skipped when 0), and metrics.map_accuracy is taken.  With ``cfg.map_eval_register`` the
     filtered map is first registered to the dataset's survey (its own, or the one sampled from its mesh) by
     registration.register_cloud(**cfg.register_kwargs), the accuracy is that of the registered points and ``res['registration']``
-    holds the Registration.  Appends ``name n mean rms median trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and
+    holds the Registration; with ``cfg.map_eval_register_init`` 'global' it starts from the prior of registration.register_global
+    (**cfg.register_global_kwargs), which ``res['registration_coarse']`` then holds.  Appends ``name n mean rms median trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and
     returns the per-sequence dicts."""
     from .filters import filter_grid
     from .io import append
@@ -459,7 +460,16 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
         reg = None
         if cfg.map_eval_register:
             from .registration import register_cloud
-            reg = register_cloud(points, _dataset_survey(ds, name, cfg, who='eval_map with map_eval_register'), **dict(cfg.register_kwargs))
+            kw = dict(cfg.register_kwargs)
+            if cfg.map_eval_register_init is not None:
+                if cfg.map_eval_register_init != 'global':
+                    raise ValueError("map_eval_register_init must be None or 'global', got %r" % (cfg.map_eval_register_init,))
+                kw.update(init='global', global_kwargs=dict(cfg.register_global_kwargs))
+            reg = register_cloud(points, _dataset_survey(ds, name, cfg, who='eval_map with map_eval_register'), **kw)
+            if reg.coarse is not None:
+                print('Global registration of the map of %s: %s, hypothesis %d, score %d of %d matches, fitness %d of %d points.'
+                      % (name, reg.coarse.status, reg.coarse.hypothesis, reg.coarse.score, reg.coarse.n_correspondences,
+                         reg.coarse.fitness, reg.coarse.n_points))
             print('Registration of the map of %s to its survey: %s after %d iterations, %d pairs, rms %.6f m.'
                   % (name, reg.status, reg.iterations, reg.pairs, reg.rms))
             T = torch.as_tensor(reg.T, device=points.device)
@@ -469,6 +479,8 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
         res['name'] = name
         if reg is not None:
             res['registration'] = reg
+            if reg.coarse is not None:
+                res['registration_coarse'] = reg.coarse
         print('Map accuracy on %s: %d points, mean %.6f m, rms %.6f m, median %.6f m, trimmed mean %.6f m, signed mean %.6f m.'
               % ((name, int(res['n'])) + tuple(res[f] for f in MAP_EVAL_FIELDS[1:])))
         if cfg.map_eval_csv:

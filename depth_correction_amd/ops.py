@@ -19,7 +19,7 @@ __all__ = [
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace', 'cloud_loss', 'cloud_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
-    'survey_align_workspace',
+    'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -1861,6 +1861,103 @@ def survey_align(survey_dev, query, origins, prior=None, inlier_ratio=1.0, max_d
                                 ratio, md, n_iters, float(min_rot), float(min_trans), min_pairs, ptr(origins), ptr(state), ptr(status),
                                 ptr(history), ptr(ws), ws.shape[0], stream_ptr()), 'dc_survey_align')
     return state, status, history
+
+
+# ------------------------------------------------------------------------------------------------
+# global registration, the coarse stage (csrc/dc_globalreg.hip, registration.register_global)
+# ------------------------------------------------------------------------------------------------
+def feature_nn_tile():
+    """Survey rows per LDS tile of feature_nn (dc_feature_nn_tile)."""
+    return int(lib().dc_feature_nn_tile())
+
+
+@on_device
+def pair_histograms(points, normals, nbr_idx, nbr_dist=None, want_spfh=False):
+    """Folded pair-feature descriptors of points / normals f64 [N,3] over the neighbour table nbr_idx i32 [N,k] (k <= 64, -1 for a
+    missing slot; as ops.knn returns it): (feat f32 [N,33], has i32 [N]) by dc_pair_spfh + dc_pair_fpfh; with ``want_spfh`` also (spfh
+    f64 [N,33], m i32 [N]), the simplified histograms and the valid pairs per row.  ``nbr_dist`` (f64 [N,k], ops.knn's other result) is
+    checked for its shape only: a pair's length is taken from the points, by the rule of the pair feature."""
+    need(points, (None, 3), dtype=torch.float64, name='points')
+    dev = points.device
+    n = points.shape[0]
+    need(normals, (n, 3), dtype=torch.float64, name='normals', device=dev)
+    need(nbr_idx, (n, None), dtype=torch.int32, name='nbr_idx', device=dev)
+    k = nbr_idx.shape[1]
+    if not 1 <= k <= 64:
+        raise ValueError('the neighbour table must have 1..64 slots per row, got %d' % k)
+    if nbr_dist is not None:
+        need(nbr_dist, (n, k), dtype=torch.float64, name='nbr_dist', device=dev)
+    spfh = torch.empty((n, nv.DC_GREG_FEAT), dtype=torch.float64, device=dev)
+    m = torch.empty((n,), dtype=torch.int32, device=dev)
+    feat = torch.empty((n, nv.DC_GREG_FEAT), dtype=torch.float32, device=dev)
+    has = torch.empty((n,), dtype=torch.int32, device=dev)
+    check(lib().dc_pair_spfh(ptr(points), ptr(normals), n, ptr(nbr_idx), k, ptr(spfh), ptr(m), stream_ptr()), 'dc_pair_spfh')
+    check(lib().dc_pair_fpfh(ptr(points), ptr(normals), n, ptr(nbr_idx), k, ptr(spfh), ptr(feat), ptr(has), stream_ptr()), 'dc_pair_fpfh')
+    return (feat, has, spfh, m) if want_spfh else (feat, has)
+
+
+@on_device
+def feature_nn(feat_q, has_q, feat_s, has_s):
+    """(idx i32 [Nq], dist f32 [Nq]): the nearest row of feat_s f32 [Ns,33] to every row of feat_q f32 [Nq,33] by the fp32 squared
+    distance in bin order, the lower survey row among equal distances; rows with has == 0 (i32) take no part on either side, a cloud
+    row without a match gets -1 / +inf (dc_feature_nn)."""
+    need(feat_q, (None, nv.DC_GREG_FEAT), dtype=torch.float32, name='feat_q')
+    dev = feat_q.device
+    nq = feat_q.shape[0]
+    need(has_q, (nq,), dtype=torch.int32, name='has_q', device=dev)
+    need(feat_s, (None, nv.DC_GREG_FEAT), dtype=torch.float32, name='feat_s', device=dev)
+    ns = feat_s.shape[0]
+    need(has_s, (ns,), dtype=torch.int32, name='has_s', device=dev)
+    idx = torch.empty((nq,), dtype=torch.int32, device=dev)
+    dist = torch.empty((nq,), dtype=torch.float32, device=dev)
+    check(lib().dc_feature_nn(ptr(feat_q), ptr(has_q), nq, ptr(feat_s), ptr(has_s), ns, ptr(idx), ptr(dist), stream_ptr()), 'dc_feature_nn')
+    return idx, dist
+
+
+def _greg_pairs(p, y):
+    need(p, (None, 3), dtype=torch.float64, name='p')
+    need(y, (p.shape[0], 3), dtype=torch.float64, name='y', device=p.device)
+    return p.shape[0]
+
+
+@on_device
+def greg_fit(p, y, origins, n_hypotheses, seed, min_edge, edge_ratio=0.9):
+    """(valid i32 [K], T f64 [K,4,4]): hypothesis h draws three of the correspondences p / y f64 [C,3] (splitmix64(seed ^ (h << 2) ^ t)
+    mod C), checks that they are distinct and that every edge is at least ``min_edge`` long and within ``edge_ratio`` of its image,
+    and fits them in closed form about origins f64 device [6]; NaN transforms where it is not valid (dc_greg_fit)."""
+    c = _greg_pairs(p, y)
+    dev = p.device
+    need(origins, (6,), dtype=torch.float64, name='origins', device=dev)
+    k, seed, min_edge, rho = int(n_hypotheses), int(seed), float(min_edge), float(edge_ratio)
+    if k < 0 or k > 0x7fffffff:
+        raise ValueError('n_hypotheses must lie in 0..2^31-1, got %r' % (n_hypotheses,))
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError('seed must fit a signed 64-bit integer, got %d' % seed)
+    if not min_edge >= 0.0 or not 0.0 < rho <= 1.0:
+        raise ValueError('greg_fit needs min_edge >= 0 and 0 < edge_ratio <= 1, got %r and %r' % (min_edge, rho))
+    valid = torch.empty((k,), dtype=torch.int32, device=dev)
+    T = torch.empty((k, 4, 4), dtype=torch.float64, device=dev)
+    check(lib().dc_greg_fit(ptr(p), ptr(y), c, k, seed, min_edge, rho, ptr(origins), ptr(valid), ptr(T), stream_ptr()), 'dc_greg_fit')
+    return valid, T
+
+
+@on_device
+def greg_score(valid, T, p, y, eps, want_list=False):
+    """score i32 [K]: for every valid hypothesis the number of correspondences p / y f64 [C,3] with |T_h p - y|^2 <= eps^2, -1 for the
+    others (dc_greg_score over the valid hypotheses in ascending order, compacted on the device: ONE host read, of their number).
+    With ``want_list`` also that list (i32)."""
+    c = _greg_pairs(p, y)
+    dev = p.device
+    need(valid, (None,), dtype=torch.int32, name='valid', device=dev)
+    k = valid.shape[0]
+    need(T, (k, 4, 4), dtype=torch.float64, name='T', device=dev)
+    eps = float(eps)
+    if not (eps >= 0.0 and eps < float('inf')):
+        raise ValueError('eps must be finite and >= 0, got %r' % (eps,))
+    vlist = torch.nonzero(valid).reshape(-1).to(torch.int32)        # ascending; the read of its length
+    score = torch.full((k,), -1, dtype=torch.int32, device=dev)
+    check(lib().dc_greg_score(ptr(vlist), vlist.shape[0], ptr(T), k, ptr(p), ptr(y), c, eps, ptr(score), stream_ptr()), 'dc_greg_score')
+    return (score, vlist) if want_list else score
 
 
 def icp_blocks(m):

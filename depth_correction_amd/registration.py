@@ -6,16 +6,21 @@ scans' poses share one frame.  This module gets them there:
 ``absolute_orientation``  the closed-form rigid fit of paired points (utils.py:253-304 of the reference), on the host;
 ``align_paths``           the same for two paths, with the residual statistics scripts/paths_alignment prints;
 ``register_cloud``        trimmed ICP of a cloud against a survey, what scripts/map_bias_removal:167-185 icp_alignment does on the
-                          host with a cKDTree -- here one queue of device work (ops.survey_align) and ONE host read, at the end.
+                          host with a cKDTree -- here one queue of device work (ops.survey_align) and ONE host read, at the end;
+``register_global``       the coarse stage for a cloud that is an ARBITRARY rigid motion away from the survey (DESIGN "Global
+                          registration"): folded pair-feature histograms, descriptor matching and RANSAC over the matches on
+                          the device, then ``register_cloud`` from the winner.
 """
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 import torch
 
 from . import _native as nv
 
-__all__ = ['absolute_orientation', 'align_paths', 'register_cloud', 'Registration']
+__all__ = ['absolute_orientation', 'align_paths', 'register_cloud', 'Registration', 'register_global', 'GlobalRegistration']
 
 
 def absolute_orientation(x, y, fix_reflection=False):
@@ -69,7 +74,10 @@ class Registration(object):
     """Result of ``register_cloud``: ``T`` (numpy [4,4], survey frame from the cloud's frame), ``status`` ('converged',
     'max_iterations', 'too_few_pairs', 'degenerate', 'not_finite' or 'empty'), ``ok``, ``iterations``, and of the last iteration
     ``pairs`` (kept pairs), ``rms`` (rms distance of the kept pairs before its fit) and ``threshold`` (the trimming distance);
-    ``history`` [n_iters, 5] = (pairs, rms, threshold, d_rot, d_trans) per iteration, NaN in the rows never reached."""
+    ``history`` [n_iters, 5] = (pairs, rms, threshold, d_rot, d_trans) per iteration, NaN in the rows never reached.  ``coarse``: the
+    GlobalRegistration the prior came from (``init='global'``), else None."""
+
+    coarse = None
 
     def __init__(self, T, status, iterations, pairs, rms, threshold, history):
         self.T, self.status, self.iterations = T, status, int(iterations)
@@ -88,20 +96,37 @@ class Registration(object):
 
 
 def register_cloud(points, survey, init=None, inlier_ratio=1.0, max_dist=None, n_iters=100, min_rot=0.0, min_trans=0.0, min_pairs=3,
-                   mask=None, device=None):
+                   mask=None, device=None, global_kwargs=None):
     """Trimmed ICP of ``points`` [N,3] (tensor or array, frame A) against ``survey`` (survey.SurveyCloud): the T with T points ~ survey.
     Every iteration matches T_k p to its nearest survey point within ``max_dist`` (required, finite, > 0), keeps the pairs whose
     distance is at most the ``inlier_ratio`` quantile of the matched distances, and fits T_{k+1} in closed form from the ORIGINAL
     points; it stops when the rotation and the translation increments fall below ``min_rot`` (rad) and ``min_trans`` (strictly: 0
     disables the check), after ``n_iters`` iterations, or on a failure, which leaves the estimate as it was.  ``init`` [4,4]: the
-    prior (default identity).  Rows outside ``mask`` (bool [N]) are left out.  Defaults as icp_alignment of the reference.
+    prior (default identity), or 'global': the prior is ``register_global(points, survey, refine=False, **global_kwargs)``, which
+    the result carries as ``coarse``.  Rows outside ``mask`` (bool [N]) are left out.  Defaults as icp_alignment of the reference.
 
     All iterations are queued on the device by one call (ops.survey_align); the host reads the result once, at the end."""
-    from . import ops
     if max_dist is None:
         raise ValueError('register_cloud needs max_dist (finite, > 0)')
     if device is None:
         device = points.device if isinstance(points, torch.Tensor) and points.is_cuda else 'cuda'
+    coarse = None
+    if isinstance(init, str):
+        if init != 'global':
+            raise ValueError("init must be a 4 x 4 transform, None or 'global', got %r" % (init,))
+        coarse = register_global(points, survey, refine=False, mask=mask, device=device, **dict(global_kwargs or {}))
+        if coarse.status != 'ok':
+            warnings.warn('register_cloud: the global prior is not reliable (%r); the refinement starts from it all the same' % (coarse,))
+        init = coarse.T
+    elif global_kwargs is not None:
+        raise ValueError("global_kwargs goes with init='global'")
+    reg = _register_cloud(points, survey, init, inlier_ratio, max_dist, n_iters, min_rot, min_trans, min_pairs, mask, device)
+    reg.coarse = coarse
+    return reg
+
+
+def _register_cloud(points, survey, init, inlier_ratio, max_dist, n_iters, min_rot, min_trans, min_pairs, mask, device):
+    from . import ops
     sd = survey.on_device(device)
     dev = sd.device
     pts = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float64).reshape(-1, 3)
@@ -133,3 +158,156 @@ def register_cloud(points, survey, init=None, inlier_ratio=1.0, max_dist=None, n
     return Registration(st[nv.DC_ALIGN_STATE_POSE:nv.DC_ALIGN_STATE_POSE + 16].reshape(4, 4).copy(), nv.ALIGN_STATUS[int(code[0])], iters,
                         int(st[nv.DC_ALIGN_STATE_PAIRS]) if np.isfinite(st[nv.DC_ALIGN_STATE_PAIRS]) else 0,
                         float(st[nv.DC_ALIGN_STATE_RMS]), float(st[nv.DC_ALIGN_STATE_THRESHOLD]), hist.copy())
+
+
+class GlobalRegistration(object):
+    """Result of ``register_global``: ``T`` (numpy [4,4], survey frame from the cloud's frame; the refined one with ``refine``),
+    ``T_coarse`` (the winning hypothesis's), ``status`` ('ok', 'low_fitness', 'no_correspondences', 'no_hypothesis' or 'empty'), ``ok``,
+    ``hypothesis`` (the winner's number, -1 without one), its ``score`` (matches within eps) and ``fitness`` (voxel-filtered cloud
+    points with a survey point within eps), ``n_points`` (cloud points after the voxel filter), ``n_correspondences``, ``n_valid``
+    (valid hypotheses), ``candidates`` int64 [M,3] = (h, score, fitness) in the order they were tried, and with ``refine`` ``refined``,
+    the Registration of register_cloud from the coarse T."""
+
+    def __init__(self, T, status, hypothesis=-1, score=0, fitness=0, n_points=0, n_correspondences=0, n_valid=0, candidates=None):
+        self.T, self.T_coarse, self.status = T, T.copy(), status
+        self.hypothesis, self.score, self.fitness = int(hypothesis), int(score), int(fitness)
+        self.n_points, self.n_correspondences, self.n_valid = int(n_points), int(n_correspondences), int(n_valid)
+        self.candidates = np.zeros((0, 3), dtype=np.int64) if candidates is None else candidates
+        self.refined = None
+
+    @property
+    def ok(self):
+        return self.status == 'ok' and (self.refined is None or self.refined.ok)
+
+    def __repr__(self):
+        return 'GlobalRegistration(%s, hypothesis %d, score %d of %d matches, fitness %d of %d points)' % (
+            self.status, self.hypothesis, self.score, self.n_correspondences, self.fitness, self.n_points)
+
+    def as_dict(self):
+        return dict(T=self.T.tolist(), T_coarse=self.T_coarse.tolist(), status=self.status, ok=self.ok, hypothesis=self.hypothesis,
+                    score=self.score, fitness=self.fitness, n_points=self.n_points, n_correspondences=self.n_correspondences,
+                    n_valid=self.n_valid, candidates=self.candidates.tolist())
+
+
+def global_descriptors(points, normals, voxel, feature_k, feature_radius):
+    """The descriptor side of ``register_global`` for one cloud on the device (points f64 [N,3] finite, normals f64 [N,3] or None):
+    (points, normals, feat f32 [n,33], has i32 [n]) of the n survivors of ops.voxel_filter(preserve_order=True).  The neighbour table
+    is ops.knn of the filtered cloud in itself with min(feature_k + 1, 64) columns within ``feature_radius``, the point's own row
+    taken out: the feature_k nearest OTHER points (63 of them at feature_k = 64, the most ops.knn's table holds beside the point
+    itself).  ``normals=None`` estimates them on the filtered cloud with the package's feature kernels (k = 10, as
+    SurveyCloud.from_points does); a point without one has no descriptor."""
+    from . import ops
+    keep = ops.voxel_filter(points, float(voxel), preserve_order=True)
+    if keep is None:
+        raise ValueError('the cloud spans too many voxels of %g m for the voxel filter: use a larger voxel' % voxel)
+    fp = points[keep].contiguous()
+    if normals is None:
+        from .depth_cloud import DepthCloud
+        cloud = DepthCloud.from_points(fp)
+        cloud.update_all(k=10, r=None)
+        fn = cloud.normals.detach().to(torch.float64).contiguous()
+    else:
+        fn = normals[keep].contiguous()
+    n = fp.shape[0]
+    k_tab = min(int(feature_k) + 1, 64)
+    dist, idx = ops.knn(fp, k_tab, r=float(feature_radius))
+    idx = torch.where(idx == torch.arange(n, dtype=torch.int32, device=fp.device)[:, None], torch.full_like(idx, -1), idx).contiguous()
+    feat, has = ops.pair_histograms(fp, fn, idx, dist)
+    return fp, fn, feat, has
+
+
+def register_global(points, survey, normals=None, voxel=0.25, feature_k=64, feature_radius=None, n_hypotheses=2 ** 20, eps=None,
+                    edge_ratio=0.9, min_edge=None, n_candidates=16, seed=135, min_fitness=0.5, refine=True, refine_kwargs=None, mask=None,
+                    device=None):
+    """Registration of ``points`` [N,3] against ``survey`` (survey.SurveyCloud) WITHOUT a prior (DESIGN "Global registration"): both
+    clouds are voxel-filtered at ``voxel``, every point gets a 33-bin descriptor of the folded pair features of its ``feature_k``
+    nearest other points within ``feature_radius`` (default 6 voxel; ``normals`` [N,3] of any sign, estimated when None), every cloud
+    descriptor is matched to its nearest survey descriptor, ``n_hypotheses`` triples of matches are drawn (seeded: ``seed``), those
+    whose edges are at least ``min_edge`` (default 4 voxel) long and within ``edge_ratio`` of their images are fitted in closed form
+    and scored by the matches they bring within ``eps`` (default 0.6 voxel); the ``n_candidates`` best are ranked by their fitness,
+    the filtered cloud points they bring within eps of the survey.  status 'low_fitness': the winner's fitness is below
+    ``min_fitness`` x the filtered points (T is still returned).  With ``refine`` the coarse T is the prior of
+    register_cloud(points, survey, **refine_kwargs) (max_dist defaults to 2 voxel), and T is the refined one.  Rows outside ``mask``
+    and rows that are not finite are left out.  The survey's side is computed once per device and argument set.  The default
+    ``n_hypotheses`` is too few where only 1 to 2 % of the matches are right: on the test room it leaves three of five placements
+    without an all-inlier triple, and 2^22 is what all five need (DESIGN "Global registration"); a 'low_fitness' status says that the
+    pose found does not explain the cloud -- raise n_hypotheses or the voxel -- and the refinement then runs with a warning.  All of it runs on
+    the device; the host reads two counts on the way (the matches, the valid hypotheses) and the candidates once, at the end."""
+    from . import ops
+    voxel = float(voxel)
+    if not (voxel > 0.0 and voxel < float('inf')):
+        raise ValueError('voxel must be finite and > 0, got %r' % (voxel,))
+    feature_radius = 6.0 * voxel if feature_radius is None else float(feature_radius)
+    eps = 0.6 * voxel if eps is None else float(eps)
+    min_edge = 4.0 * voxel if min_edge is None else float(min_edge)
+    feature_k, n_hyp, n_cand = int(feature_k), int(n_hypotheses), int(n_candidates)
+    if not 1 <= feature_k <= 64:
+        raise ValueError('feature_k must lie in 1..64, got %r' % (feature_k,))
+    if not (feature_radius > 0.0 and eps > 0.0 and min_edge >= 0.0 and 0.0 < float(edge_ratio) <= 1.0):
+        raise ValueError('register_global needs feature_radius, eps > 0, min_edge >= 0 and 0 < edge_ratio <= 1')
+    if n_hyp < 1 or n_cand < 1:
+        raise ValueError('register_global needs n_hypotheses >= 1 and n_candidates >= 1')
+    if device is None:
+        device = points.device if isinstance(points, torch.Tensor) and points.is_cuda else 'cuda'
+    sd = survey.on_device(device)
+    dev = sd.device
+    pts = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float64).reshape(-1, 3)
+    nrm = None if normals is None else torch.as_tensor(normals).detach().to(device=dev, dtype=torch.float64).reshape(-1, 3)
+    if nrm is not None and nrm.shape[0] != pts.shape[0]:
+        raise ValueError('normals must be [%d,3]' % pts.shape[0])
+    keep = torch.isfinite(pts).all(dim=1)
+    if mask is not None:
+        m = torch.as_tensor(mask).to(device=dev).reshape(-1)
+        if m.dtype != torch.bool or m.shape[0] != pts.shape[0]:
+            raise ValueError('mask must be bool [%d]' % pts.shape[0])
+        keep = keep & m
+    pts = pts[keep].contiguous()
+    nrm = None if nrm is None else nrm[keep].contiguous()
+    if pts.shape[0] == 0:
+        return GlobalRegistration(np.eye(4), 'empty')
+    with torch.no_grad():
+        fp, _, feat, has = global_descriptors(pts, nrm, voxel, feature_k, feature_radius)
+        sp, _, sfeat, shas = survey.global_descriptors(dev, voxel, feature_k, feature_radius)
+        n = fp.shape[0]
+        midx, _ = ops.feature_nn(feat, has, sfeat, shas)
+        rows = torch.nonzero(midx >= 0).reshape(-1)                 # ascending; a host read: the number of matches
+        c = rows.shape[0]
+        if c == 0:
+            return GlobalRegistration(np.eye(4), 'no_correspondences', n_points=n)
+        p = fp[rows].contiguous()
+        y = sp[midx[rows].long()].contiguous()
+        # the two fixed origins of register_cloud: the centre of the cloud's bounding box and the centre of the survey's bounds
+        origins = torch.cat([0.5 * (pts.amin(dim=0) + pts.amax(dim=0)), sd.origin()]).contiguous()
+        valid, T = ops.greg_fit(p, y, origins, n_hyp, seed, min_edge, edge_ratio)
+        score, vlist = ops.greg_score(valid, T, p, y, eps, want_list=True)   # a host read: the number of valid hypotheses
+        n_valid = vlist.shape[0]
+        if n_valid == 0:
+            return GlobalRegistration(np.eye(4), 'no_hypothesis', n_points=n, n_correspondences=c)
+        # the candidates: the largest (score, then lower h) by one int64 key, sorted on the device
+        h_all = torch.arange(n_hyp, dtype=torch.int64, device=dev)
+        key = score.to(torch.int64) * (1 << 32) + ((1 << 32) - 1 - h_all)
+        cand = (1 << 32) - 1 - (torch.topk(key, min(n_cand, n_valid), sorted=True).values & ((1 << 32) - 1))
+        sd.reserve(n)
+        idx1 = torch.empty((n, 1), dtype=torch.int32, device=dev)
+        dist1 = torch.empty((n, 1), dtype=torch.float64, device=dev)
+        Tc = T[cand].contiguous()
+        fitness = torch.empty((cand.shape[0],), dtype=torch.int64, device=dev)
+        for q in range(cand.shape[0]):
+            ops.knn_grid_query(sd.grid, fp, Tc[q], 1, r=eps, idx=idx1, dist=dist1)
+            fitness[q] = (idx1 >= 0).sum()
+        packed = torch.cat([cand.to(torch.float64), score[cand].to(torch.float64), fitness.to(torch.float64), Tc.reshape(-1)]).cpu().numpy()
+    m_c = cand.shape[0]                                              # the one read of the result
+    table = np.stack([packed[:m_c], packed[m_c:2 * m_c], packed[2 * m_c:3 * m_c]], axis=1).astype(np.int64)
+    best = int(np.argmax(table[:, 2]))                              # the first of the largest: ties go to the earlier candidate
+    T_best = packed[3 * m_c:].reshape(m_c, 4, 4)[best].copy()
+    status = 'ok' if table[best, 2] >= float(min_fitness) * n else 'low_fitness'
+    res = GlobalRegistration(T_best, status, table[best, 0], table[best, 1], table[best, 2], n, c, n_valid, table)
+    if refine:
+        if status != 'ok':
+            warnings.warn('register_global: refining from a prior of low fitness (%d of %d points): the result is not reliable'
+                          % (res.fitness, n))
+        kw = dict(refine_kwargs or {})
+        kw.setdefault('max_dist', 2.0 * voxel)
+        res.refined = register_cloud(pts, survey, init=T_best, device=dev, **kw)
+        res.T = res.refined.T
+    return res

@@ -100,6 +100,7 @@ class SurveyCloud(object):
         self.normals = (normals / norm).contiguous()
         self._device = {}
         self._surfels = {}
+        self._descriptors = {}
 
     def __len__(self):
         return self.points.shape[0]
@@ -157,6 +158,23 @@ class SurveyCloud(object):
         """registration.register_cloud(points, self, **kw): the Registration whose ``T`` takes ``points`` into this survey's frame."""
         from .registration import register_cloud
         return register_cloud(points, self, **kw)
+
+    def register_global(self, points, **kw):
+        """registration.register_global(points, self, **kw): the GlobalRegistration of a cloud without a prior."""
+        from .registration import register_global
+        return register_global(points, self, **kw)
+
+    def global_descriptors(self, device, voxel, feature_k, feature_radius):
+        """(points f64 [m,3], normals f64 [m,3], feat f32 [m,33], has i32 [m]) of the survey's side of registration.register_global
+        on ``device`` (a GPU): the voxel-filtered survey with its descriptors, computed once per device and argument set."""
+        dev = self.on_device(device)
+        key = (dev.device, float(voxel), int(feature_k), float(feature_radius))
+        got = self._descriptors.get(key)
+        if got is None:
+            from .registration import global_descriptors
+            with torch.no_grad():
+                got = self._descriptors[key] = global_descriptors(dev.points, dev.normals, *key[1:])
+        return got
 
     def transformed(self, T):
         """A new SurveyCloud whose points are ``T`` (4 x 4 rigid) applied to these and whose normals are rotated with them; it has a

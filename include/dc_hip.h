@@ -1276,6 +1276,44 @@ int dc_survey_align(void* grid_ws, size_t grid_ws_bytes, int64_t n_query_max, co
                     int min_pairs, const double* origins, double* state, int32_t* status, double* history, void* ws, size_t ws_bytes,
                     dcStream_t stream);
 
+/* ---- global registration, the coarse stage (depth_correction_amd/csrc/dc_globalreg.hip, dc_globalreg_math.h; DESIGN "Global
+ * registration"): folded pair-feature histograms, descriptor matching and RANSAC over the matches.  None of these allocates, copies,
+ * synchronises or uses an atomic; the same inputs give the same bits.  A row count of 0 launches nothing and returns DC_OK. ---- */
+#ifndef DC_GREG_FEAT
+#define DC_GREG_BINS 11               /* bins per feature */
+#define DC_GREG_FEAT 33               /* values per descriptor: three blocks of DC_GREG_BINS */
+#endif
+/* Simplified histograms of points / normals fp64 [n,3] (normals of any sign and non-zero length) over the neighbour table nbr int32
+ * [n,k] (1 <= k <= 64; a slot outside 0 .. n-1 is missing; the point itself, a duplicate of it or a row that is not finite never
+ * forms a valid pair).  Pair (i, j): d = x_j - x_i, L = |d|, e = d / L, a1 = |n^_i.e|, a2 = |n^_j.e|, a3 = |n^_i.n^_j|, bin(a) =
+ * min(10, floor(11 a)); valid iff L and both |n| are finite and > 0 and no a is NaN.  m int32 [n] <- the valid pairs of row i, spfh
+ * double [n,33] <- the three blocks of counts divided by m (zeros when m == 0). */
+int dc_pair_spfh(const double* points, const double* normals, int64_t n, const int32_t* nbr, int k, double* spfh, int32_t* m,
+                 dcStream_t stream);
+/* Descriptors from dc_pair_spfh's rows (same points, normals and table): F_i = SPFH_i + (1 / m_i) sum_j (1 / L_ij) SPFH_j over the valid
+ * slots in ascending slot order, each block of 11 then scaled to sum 100 (its sum in ascending bin order; a sum of 0 leaves zeros),
+ * rounded once to fp32.  feat float [n,33], has int32 [n] = (m_i > 0). */
+int dc_pair_fpfh(const double* points, const double* normals, int64_t n, const int32_t* nbr, int k, const double* spfh, float* feat,
+                 int32_t* has, dcStream_t stream);
+/* Nearest survey descriptor of every cloud descriptor in fp32: s = 0; s = s + t t with t = fq[b] - fs[b], b = 0 .. 32 (the product
+ * rounded, then the sum); the smallest s, the lower survey row among equal s.  Rows with has == 0 take no part on either side: a cloud
+ * row with has_q == 0, or without a usable survey row, gets -1 / +inf.  idx_out int32 [n_q], dist_out float [n_q]. */
+int dc_feature_nn(const float* feat_q, const int32_t* has_q, int64_t n_q, const float* feat_s, const int32_t* has_s, int64_t n_s,
+                  int32_t* idx_out, float* dist_out, dcStream_t stream);
+/* Survey rows per LDS tile of dc_feature_nn (for tests that cross it). */
+int dc_feature_nn_tile(void);
+/* Hypothesis h in [0, n_hyp) over the correspondences p / y fp64 [n_corr,3] (cloud point, matched survey point): draws j_t =
+ * splitmix64(seed ^ (h << 2) ^ t) mod n_corr, t = 0, 1, 2; valid iff the draws are distinct, every one of the three point pairs has
+ * lp = |p_a - p_b| >= min_edge, lp >= edge_ratio ly and ly >= edge_ratio lp (ly = |y_a - y_b|), and dc_align_finish's closed-form fit
+ * of the three pairs about origins (DEVICE double [6]; moments summed in draw order) is not degenerate and finite.  valid int32
+ * [n_hyp], T double [n_hyp,16] <- the fit, NaN for an invalid hypothesis.  min_edge >= 0, 0 < edge_ratio <= 1 (DC_ERR_ARG). */
+int dc_greg_fit(const double* p, const double* y, int64_t n_corr, int64_t n_hyp, int64_t seed, double min_edge, double edge_ratio,
+                const double* origins, int32_t* valid, double* T, dcStream_t stream);
+/* score[h] <- the number of correspondences with |T_h p - y|^2 <= eps^2 (T_h p in dc_knn_grid_query's order) for every h of list int32
+ * [n_list] (the valid hypotheses; an entry outside 0 .. n_hyp-1 is skipped); the other rows of score int32 [n_hyp] are the caller's. */
+int dc_greg_score(const int32_t* list, int64_t n_list, const double* T, int64_t n_hyp, const double* p, const double* y, int64_t n_corr,
+                  double eps, int32_t* score, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
