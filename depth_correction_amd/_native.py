@@ -41,6 +41,8 @@ DC_ALIGN_STATE_PAIRS, DC_ALIGN_STATE_RMS, DC_ALIGN_STATE_D_ROT, DC_ALIGN_STATE_D
 DC_ALIGN_PARTIALS, DC_ALIGN_HISTORY_COLS = 17, 5
 # include/dc_hip.h: bins per pair feature and values per descriptor of the global registration (DC_GREG_*)
 DC_GREG_BINS, DC_GREG_FEAT = 11, 33
+# fewest and most planes a side of the plane registration (include/dc_hip.h: 3 and DC_PLANEREG_MAX_PLANES)
+DC_PLANEREG_MIN_PLANES, DC_PLANEREG_MAX_PLANES = 3, 64
 ALIGN_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'degenerate', -3: 'not_finite'}
 ICP_STATUS = {0: 'running', 1: 'converged', 2: 'max_iterations', -1: 'too_few_pairs', -2: 'singular', -3: 'not_finite', -4: 'bound'}
 
@@ -228,6 +230,10 @@ _SIGNATURES = {
     'dc_feature_nn_tile': (_i32, []),
     'dc_greg_fit': (_i32, [_vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     'dc_greg_score': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp]),
+    # plane registration (csrc/dc_planereg.hip)
+    'dc_planereg_blocks': (_i64, [_i64]),
+    'dc_planereg_count': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _vp, _vp]),
+    'dc_planereg_fill': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -275,9 +275,11 @@ class Config(object):
         self.register_kwargs = {'inlier_ratio': 0.8, 'max_dist': 1.0, 'n_iters': 50, 'min_rot': 1e-6, 'min_trans': 1e-6}
         # map_eval_register_init: None (the registration starts from the identity) or 'global' (from the prior of
         # registration.register_global with register_global_kwargs; DESIGN "Global registration") -- for maps that are an arbitrary
-        # rigid motion away from the survey
+        # rigid motion away from the survey -- or 'planes' (registration.register_planes with register_planes_kwargs; DESIGN "Plane
+        # registration"), for maps of rooms and corridors
         self.map_eval_register_init = None
         self.register_global_kwargs = {}
+        self.register_planes_kwargs = {}
         # depth bias against the ground-truth mesh (eval.eval_bias, DESIGN "Depth bias against the mesh"; not in the reference's
         # Config): eval_bias appends a line per sequence to bias_eval_csv and writes the per-bin table to bias_eval_curve_csv; bins of
         # the true incidence angle over [0, pi/2]; rays with |d - t| above bias_eval_max_residual (metres) are left out; back-face

@@ -19,6 +19,7 @@
 #include "dc_rangeimage_math.h"
 #include "dc_align_math.h"
 #include "dc_globalreg_math.h"
+#include "dc_planereg_math.h"
 #include "dc_cons_route.h"
 
 extern "C" {
@@ -789,6 +790,43 @@ int dc_host_pair_histograms(const double* points, const double* normals, int64_t
     has[i] = m[i] > 0 ? 1 : 0;
   }
   return 0;
+}
+
+// ---- plane registration (dc_planereg_math.h; dc_planereg.hip) ----
+// The enumeration of [h_begin, h_end) done sequentially: the valid hypotheses in ascending h; the first `cap` of them are written to
+// h_out [cap], T_out [cap, 16] and score_out [cap] (any of them may be null).  Returns their number, or -1 for refused arguments
+// (the kernels' DC_ERR_ARG cases: plane counts, tolerances, more than 41 664 triples, the range).
+int64_t dc_host_planereg_enumerate(const double* cp, const int64_t* cs, int pc, const double* sp, int ps, const int32_t* tri, int64_t n_tri,
+                                   int64_t h_begin, int64_t h_end, double min_det, double tol_dot, double cos_tol, double tol_d,
+                                   int64_t cap, int64_t* h_out, double* T_out, int64_t* score_out) {
+  const dc::PregParams prm{min_det, tol_dot, cos_tol, tol_d};
+  if (!dc::preg_args_ok(pc, ps, prm) || n_tri < 0 || n_tri > dc::kPregMaxTriples || h_begin < 0 || h_end < h_begin || h_end > n_tri * ps * ps * ps * 8) return -1;
+  int64_t n = 0;
+  for (int64_t h = h_begin; h < h_end; ++h) {
+    double T[16];
+    int64_t score = 0;
+    if (!dc::preg_hypothesis(h, cp, cs, pc, sp, ps, tri, prm, T, &score)) continue;
+    if (n < cap) {
+      if (h_out) h_out[n] = h;
+      if (score_out) score_out[n] = score;
+      if (T_out) for (int c = 0; c < 16; ++c) T_out[n * 16 + c] = T[c];
+    }
+    ++n;
+  }
+  return n;
+}
+
+// The score of one transform T [16] over the plane tables
+int64_t dc_host_planereg_score(const double* T, const double* cp, const int64_t* cs, int pc, const double* sp, int ps, double cos_tol,
+                               double tol_d) {
+  return dc::preg_score(T, cp, cs, pc, sp, ps, cos_tol, tol_d);
+}
+
+// Rules 2 to 4 and the fit of one pairing (rows of 4): 1 and T [16] when valid
+int dc_host_planereg_pair(const double* na, const double* nb, const double* nc, const double* mi, const double* mj, const double* mk, int s,
+                          double min_det, double tol_dot, double* T) {
+  if (!dc::preg_check(na, nb, nc, mi, mj, mk, s, min_det, tol_dot)) return 0;
+  return dc::preg_fit(na, nb, nc, mi, mj, mk, s, T);
 }
 
 }  // extern "C"

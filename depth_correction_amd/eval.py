@@ -428,7 +428,8 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
     filtered map is first registered to the dataset's survey (its own, or the one sampled from its mesh) by
     registration.register_cloud(**cfg.register_kwargs), the accuracy is that of the registered points and ``res['registration']``
     holds the Registration; with ``cfg.map_eval_register_init`` 'global' it starts from the prior of registration.register_global
-    (**cfg.register_global_kwargs), which ``res['registration_coarse']`` then holds.  Appends ``name n mean rms median trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and
+    (**cfg.register_global_kwargs) and with 'planes' from that of registration.register_planes (**cfg.register_planes_kwargs), which
+    ``res['registration_coarse']`` then holds.  Appends ``name n mean rms median trimmed_mean signed_mean`` to ``cfg.map_eval_csv`` when set and
     returns the per-sequence dicts."""
     from .filters import filter_grid
     from .io import append
@@ -462,11 +463,16 @@ def eval_map(cfg: Config, test_datasets=None, model=None):
             from .registration import register_cloud
             kw = dict(cfg.register_kwargs)
             if cfg.map_eval_register_init is not None:
-                if cfg.map_eval_register_init != 'global':
-                    raise ValueError("map_eval_register_init must be None or 'global', got %r" % (cfg.map_eval_register_init,))
-                kw.update(init='global', global_kwargs=dict(cfg.register_global_kwargs))
+                if cfg.map_eval_register_init not in ('global', 'planes'):
+                    raise ValueError("map_eval_register_init must be None, 'global' or 'planes', got %r" % (cfg.map_eval_register_init,))
+                kw.update(init=cfg.map_eval_register_init, global_kwargs=dict(
+                    cfg.register_global_kwargs if cfg.map_eval_register_init == 'global' else cfg.register_planes_kwargs))
             reg = register_cloud(points, _dataset_survey(ds, name, cfg, who='eval_map with map_eval_register'), **kw)
-            if reg.coarse is not None:
+            if reg.coarse is not None and reg.coarse.method == 'planes':
+                print('Plane registration of the map of %s: %s, %s planes, hypothesis %d of %d valid, score %d, fitness %d of %d points.'
+                      % (name, reg.coarse.status, reg.coarse.n_planes, reg.coarse.hypothesis, reg.coarse.n_valid, reg.coarse.score,
+                         reg.coarse.fitness, reg.coarse.n_points))
+            elif reg.coarse is not None:
                 print('Global registration of the map of %s: %s, hypothesis %d, score %d of %d matches, fitness %d of %d points.'
                       % (name, reg.coarse.status, reg.coarse.hypothesis, reg.coarse.score, reg.coarse.n_correspondences,
                          reg.coarse.fitness, reg.coarse.n_points))

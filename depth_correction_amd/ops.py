@@ -6,6 +6,7 @@ and the HIP library.  Shapes follow the reference's tensors (``[N,3]`` points, `
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -19,7 +20,8 @@ __all__ = [
     'as_index32', 'scan_ids', 'points_extent', 'gather_rows', 'cat_rows', 'bvh_build', 'raycast', 'raycast_rays', 'beam_subrays', 'raycast_beams', 'bias_accumulate', 'bias_out_count', 'mesh_closest', 'mesh_sample', 'mesh_loss', 'mesh_loss_workspace', 'cloud_loss', 'cloud_loss_workspace',
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
-    'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score',
+    'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
+    'planereg_hypotheses', 'planereg_select',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -1958,6 +1960,119 @@ def greg_score(valid, T, p, y, eps, want_list=False):
     score = torch.full((k,), -1, dtype=torch.int32, device=dev)
     check(lib().dc_greg_score(ptr(vlist), vlist.shape[0], ptr(T), k, ptr(p), ptr(y), c, eps, ptr(score), stream_ptr()), 'dc_greg_score')
     return (score, vlist) if want_list else score
+
+
+# ------------------------------------------------------------------------------------------------
+# plane registration, the coarse stage from plane correspondences (csrc/dc_planereg.hip, registration.register_planes)
+# ------------------------------------------------------------------------------------------------
+def planereg_triples(cloud_planes, min_det):
+    """int32 device [U,3]: the triples a < b < c of cloud_planes f64 device [Pc,4] with |det[n_a n_b n_c]| >= min_det in lexicographic
+    order, the determinant in the order of csrc/dc_planereg_math.h (a torch expression: at most 41 664 rows)."""
+    need(cloud_planes, (None, 4), dtype=torch.float64, name='cloud_planes')
+    pc = cloud_planes.shape[0]
+    abc = torch.combinations(torch.arange(pc, device=cloud_planes.device), 3)          # lexicographic
+    n = cloud_planes[:, :3]
+    a, b, c = n[abc[:, 0]], n[abc[:, 1]], n[abc[:, 2]]
+    m0 = b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]
+    m1 = b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2]
+    m2 = b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0]
+    det = (a[:, 0] * m0 + a[:, 1] * m1) + a[:, 2] * m2
+    return abc[det.abs() >= float(min_det)].to(torch.int32).contiguous()
+
+
+def _planereg_args(cloud_planes, support, survey_planes, triples, h_begin, h_end, min_det, tol_dot, cos_tol, tol_d, who):
+    need(cloud_planes, (None, 4), dtype=torch.float64, name='cloud_planes')
+    dev = cloud_planes.device
+    pc = cloud_planes.shape[0]
+    need(support, (pc,), dtype=torch.int64, name='support', device=dev)
+    need(survey_planes, (None, 4), dtype=torch.float64, name='survey_planes', device=dev)
+    ps = survey_planes.shape[0]
+    need(triples, (None, 3), dtype=torch.int32, name='triples', device=dev)
+    u = triples.shape[0]
+    total = u * ps ** 3 * 8
+    h_begin, h_end = int(h_begin), total if h_end is None else int(h_end)
+    tol = tuple(float(v) for v in (min_det, tol_dot, cos_tol, tol_d))
+    if not (nv.DC_PLANEREG_MIN_PLANES <= pc <= nv.DC_PLANEREG_MAX_PLANES and nv.DC_PLANEREG_MIN_PLANES <= ps <= nv.DC_PLANEREG_MAX_PLANES):
+        raise ValueError('%s needs 3..64 planes a side, got %d and %d' % (who, pc, ps))
+    if not 0 <= h_begin <= h_end <= total:
+        raise ValueError('%s: the range %d..%d lies outside the %d hypotheses' % (who, h_begin, h_end, total))
+    if not all(math.isfinite(v) for v in tol) or tol[0] < 0.0 or tol[1] < 0.0 or tol[3] < 0.0:
+        raise ValueError('%s needs finite tolerances, min_det, tol_dot and tol_d >= 0, got %r' % (who, tol))
+    return dev, pc, ps, u, h_begin, h_end, tol
+
+
+@on_device
+def planereg_count(cloud_planes, support, survey_planes, triples, min_det, tol_dot, cos_tol, tol_d, h_begin=0, h_end=None):
+    """counts i32 [blocks]: the valid hypotheses of every block's range of h_begin <= h < h_end (default: the whole enumeration,
+    U Ps^3 8) over the plane tables cloud_planes f64 [Pc,4] / support i64 [Pc] / survey_planes f64 [Ps,4] and the cloud triples i32
+    [U,3] of planereg_triples (dc_planereg_count; the rules: csrc/dc_planereg_math.h)."""
+    dev, pc, ps, u, h0, h1, tol = _planereg_args(cloud_planes, support, survey_planes, triples, h_begin, h_end, min_det, tol_dot, cos_tol,
+                                                 tol_d, 'planereg_count')
+    counts = torch.empty((int(lib().dc_planereg_blocks(h1 - h0)),), dtype=torch.int32, device=dev)
+    check(lib().dc_planereg_count(ptr(cloud_planes), ptr(support), pc, ptr(survey_planes), ps, ptr(triples), u, h0, h1, *tol, ptr(counts),
+                                  stream_ptr()), 'dc_planereg_count')
+    return counts
+
+
+@on_device
+def planereg_fill(cloud_planes, support, survey_planes, triples, min_det, tol_dot, cos_tol, tol_d, offsets, n_valid, h_begin=0, h_end=None):
+    """(h i64 [n_valid] ascending, T f64 [n_valid,4,4], score i64 [n_valid]) of the valid hypotheses, written at offsets i64 [blocks],
+    the exclusive scan of planereg_count's counts for the same arguments (dc_planereg_fill)."""
+    dev, pc, ps, u, h0, h1, tol = _planereg_args(cloud_planes, support, survey_planes, triples, h_begin, h_end, min_det, tol_dot, cos_tol,
+                                                 tol_d, 'planereg_fill')
+    need(offsets, (int(lib().dc_planereg_blocks(h1 - h0)),), dtype=torch.int64, name='offsets', device=dev)
+    n_valid = int(n_valid)
+    h = torch.empty((n_valid,), dtype=torch.int64, device=dev)
+    T = torch.empty((n_valid, 4, 4), dtype=torch.float64, device=dev)
+    score = torch.empty((n_valid,), dtype=torch.int64, device=dev)
+    check(lib().dc_planereg_fill(ptr(cloud_planes), ptr(support), pc, ptr(survey_planes), ps, ptr(triples), u, h0, h1, *tol, ptr(offsets),
+                                 n_valid, ptr(h), ptr(T), ptr(score), stream_ptr()), 'dc_planereg_fill')
+    return h, T, score
+
+
+def planereg_hypotheses(cloud_planes, support, survey_planes, triples, min_det, tol_dot, cos_tol, tol_d, h_begin=0, h_end=None):
+    """(h, T, score) of planereg_fill after planereg_count and the exclusive scan of its counts; ONE host read, of the total, which
+    sizes the results."""
+    args = (cloud_planes, support, survey_planes, triples, min_det, tol_dot, cos_tol, tol_d)
+    counts = planereg_count(*args, h_begin=h_begin, h_end=h_end)
+    ends = torch.cumsum(counts, dim=0, dtype=torch.int64)
+    n_valid = int(ends[-1]) if ends.shape[0] else 0
+    return planereg_fill(*args, (ends - counts).contiguous(), n_valid, h_begin=h_begin, h_end=h_end)
+
+
+def planereg_select(score, T, centre, n_candidates, dedupe_rot, dedupe_trans):
+    """rows i64 device [n_candidates] into the valid list (ascending h), -1 where none remained: the greedy suppression of DESIGN "Plane
+    registration".  Every round keeps the best remaining hypothesis by (score descending, row ascending) and drops every remaining one
+    whose rotation lies within ``dedupe_rot`` of it (the angle of csrc/dc_align_math.h's rotation_angle_between) AND whose image of
+    ``centre`` f64 device [3] lies within ``dedupe_trans`` of its image.  score i64 [V], T f64 [V,4,4].  Elementwise torch operations
+    and device-side reductions only: nothing is read back."""
+    need(score, (None,), dtype=torch.int64, name='score')
+    dev = score.device
+    v = score.shape[0]
+    need(T, (v, 4, 4), dtype=torch.float64, name='T', device=dev)
+    need(centre, (3,), dtype=torch.float64, name='centre', device=dev)
+    m = int(n_candidates)
+    if v == 0 or m == 0:
+        return torch.full((m,), -1, dtype=torch.int64, device=dev)
+    R = T[:, :3, :3].contiguous()
+    img = R @ centre + T[:, :3, 3]
+    pos = torch.arange(v, dtype=torch.int64, device=dev)
+    alive = torch.ones((v,), dtype=torch.bool, device=dev)
+    none = torch.full((), -1, dtype=torch.int64, device=dev)
+    last = torch.full((), v, dtype=torch.int64, device=dev)
+    rows = []
+    for c in range(m):
+        masked = torch.where(alive, score, none)
+        smax = masked.max()
+        best = torch.where(masked == smax, pos, last).amin().reshape(1)         # the first of the largest score
+        rows.append(torch.where(alive.any(), best, none))
+        # the kept row by index_select: indexing with a device scalar (R[best]) would read it back, a host sync per round
+        D = R @ R.index_select(0, best)[0].t()
+        ax = 0.5 * torch.stack([D[:, 2, 1] - D[:, 1, 2], D[:, 0, 2] - D[:, 2, 0], D[:, 1, 0] - D[:, 0, 1]], dim=1)
+        ang = torch.atan2(torch.linalg.norm(ax, dim=1), 0.5 * (D[:, 0, 0] + D[:, 1, 1] + D[:, 2, 2] - 1.0))
+        dist = torch.linalg.norm(img - img.index_select(0, best), dim=1)
+        alive = alive & ~((ang <= float(dedupe_rot)) & (dist <= float(dedupe_trans))) & (pos != best)
+    return torch.cat(rows)
 
 
 def icp_blocks(m):

@@ -10,9 +10,13 @@ scans' poses share one frame.  This module gets them there:
 ``register_global``       the coarse stage for a cloud that is an ARBITRARY rigid motion away from the survey (DESIGN "Global
                           registration"): folded pair-feature histograms, descriptor matching and RANSAC over the matches on
                           the device, then ``register_cloud`` from the winner.
+``register_planes``       the coarse stage for maps of rooms and corridors (DESIGN "Plane registration"): planes on both sides, every
+                          pairing of a triple of cloud planes with a triple of survey planes fitted in closed form on the device,
+                          ranked by plane agreement and then by point fitness.
 """
 from __future__ import annotations
 
+import math
 import warnings
 
 import numpy as np
@@ -20,7 +24,8 @@ import torch
 
 from . import _native as nv
 
-__all__ = ['absolute_orientation', 'align_paths', 'register_cloud', 'Registration', 'register_global', 'GlobalRegistration']
+__all__ = ['absolute_orientation', 'align_paths', 'register_cloud', 'Registration', 'register_global', 'GlobalRegistration',
+           'register_planes']
 
 
 def absolute_orientation(x, y, fix_reflection=False):
@@ -102,8 +107,8 @@ def register_cloud(points, survey, init=None, inlier_ratio=1.0, max_dist=None, n
     distance is at most the ``inlier_ratio`` quantile of the matched distances, and fits T_{k+1} in closed form from the ORIGINAL
     points; it stops when the rotation and the translation increments fall below ``min_rot`` (rad) and ``min_trans`` (strictly: 0
     disables the check), after ``n_iters`` iterations, or on a failure, which leaves the estimate as it was.  ``init`` [4,4]: the
-    prior (default identity), or 'global': the prior is ``register_global(points, survey, refine=False, **global_kwargs)``, which
-    the result carries as ``coarse``.  Rows outside ``mask`` (bool [N]) are left out.  Defaults as icp_alignment of the reference.
+    prior (default identity), or 'global' / 'planes': the prior is ``register_global`` / ``register_planes(points, survey,
+    refine=False, **global_kwargs)``, which the result carries as ``coarse``.  Rows outside ``mask`` (bool [N]) are left out.  Defaults as icp_alignment of the reference.
 
     All iterations are queued on the device by one call (ops.survey_align); the host reads the result once, at the end."""
     if max_dist is None:
@@ -112,14 +117,15 @@ def register_cloud(points, survey, init=None, inlier_ratio=1.0, max_dist=None, n
         device = points.device if isinstance(points, torch.Tensor) and points.is_cuda else 'cuda'
     coarse = None
     if isinstance(init, str):
-        if init != 'global':
-            raise ValueError("init must be a 4 x 4 transform, None or 'global', got %r" % (init,))
-        coarse = register_global(points, survey, refine=False, mask=mask, device=device, **dict(global_kwargs or {}))
+        if init not in ('global', 'planes'):
+            raise ValueError("init must be a 4 x 4 transform, None, 'global' or 'planes', got %r" % (init,))
+        coarse = (register_global if init == 'global' else register_planes)(points, survey, refine=False, mask=mask, device=device,
+                                                                            **dict(global_kwargs or {}))
         if coarse.status != 'ok':
             warnings.warn('register_cloud: the global prior is not reliable (%r); the refinement starts from it all the same' % (coarse,))
         init = coarse.T
     elif global_kwargs is not None:
-        raise ValueError("global_kwargs goes with init='global'")
+        raise ValueError("global_kwargs goes with init='global' or init='planes'")
     reg = _register_cloud(points, survey, init, inlier_ratio, max_dist, n_iters, min_rot, min_trans, min_pairs, mask, device)
     reg.coarse = coarse
     return reg
@@ -166,7 +172,19 @@ class GlobalRegistration(object):
     ``hypothesis`` (the winner's number, -1 without one), its ``score`` (matches within eps) and ``fitness`` (voxel-filtered cloud
     points with a survey point within eps), ``n_points`` (cloud points after the voxel filter), ``n_correspondences``, ``n_valid``
     (valid hypotheses), ``candidates`` int64 [M,3] = (h, score, fitness) in the order they were tried, and with ``refine`` ``refined``,
-    the Registration of register_cloud from the coarse T."""
+    the Registration of register_cloud from the coarse T.
+
+    ``register_planes`` returns the same class with ``method`` 'planes' (else 'descriptors'): ``status`` may also be 'too_few_planes',
+    ``score`` is the summed support of the agreeing cloud planes, ``n_planes`` = (Pc, Ps), ``n_triples`` the independent cloud
+    triples, ``n_enumerated`` the hypotheses walked, ``hypothesis`` and the first column of ``candidates`` are 64-bit hypothesis
+    numbers, and ``runner_up`` is the best fitness among the OTHER candidates (an ambiguous room shows there); ``n_correspondences``
+    stays 0."""
+
+    method = 'descriptors'
+    n_planes = None
+    n_triples = 0
+    n_enumerated = 0
+    runner_up = None
 
     def __init__(self, T, status, hypothesis=-1, score=0, fitness=0, n_points=0, n_correspondences=0, n_valid=0, candidates=None):
         self.T, self.T_coarse, self.status = T, T.copy(), status
@@ -180,13 +198,20 @@ class GlobalRegistration(object):
         return self.status == 'ok' and (self.refined is None or self.refined.ok)
 
     def __repr__(self):
+        if self.method == 'planes':
+            return 'GlobalRegistration(planes: %s, %s planes, hypothesis %d of %d valid, score %d, fitness %d of %d points, runner-up %s)' % (
+                self.status, self.n_planes, self.hypothesis, self.n_valid, self.score, self.fitness, self.n_points, self.runner_up)
         return 'GlobalRegistration(%s, hypothesis %d, score %d of %d matches, fitness %d of %d points)' % (
             self.status, self.hypothesis, self.score, self.n_correspondences, self.fitness, self.n_points)
 
     def as_dict(self):
-        return dict(T=self.T.tolist(), T_coarse=self.T_coarse.tolist(), status=self.status, ok=self.ok, hypothesis=self.hypothesis,
-                    score=self.score, fitness=self.fitness, n_points=self.n_points, n_correspondences=self.n_correspondences,
-                    n_valid=self.n_valid, candidates=self.candidates.tolist())
+        out = dict(T=self.T.tolist(), T_coarse=self.T_coarse.tolist(), status=self.status, ok=self.ok, hypothesis=self.hypothesis,
+                   score=self.score, fitness=self.fitness, n_points=self.n_points, n_correspondences=self.n_correspondences,
+                   n_valid=self.n_valid, candidates=self.candidates.tolist())
+        if self.method == 'planes':
+            out.update(method=self.method, n_planes=self.n_planes, n_triples=self.n_triples, n_enumerated=self.n_enumerated,
+                       runner_up=self.runner_up)
+        return out
 
 
 def global_descriptors(points, normals, voxel, feature_k, feature_radius):
@@ -309,5 +334,126 @@ def register_global(points, survey, normals=None, voxel=0.25, feature_k=64, feat
         kw = dict(refine_kwargs or {})
         kw.setdefault('max_dist', 2.0 * voxel)
         res.refined = register_cloud(pts, survey, init=T_best, device=dev, **kw)
+        res.T = res.refined.T
+    return res
+
+
+def _planes_result(status, n_planes=None, **kw):
+    res = GlobalRegistration(np.eye(4), status, **kw)
+    res.method, res.n_planes = 'planes', n_planes
+    return res
+
+
+def cloud_planes(points, plane_voxel, distance_threshold, min_support, ransac_iters, cluster_eps, max_planes, seed):
+    """(params f64 device [P,4], support i64 device [P]) of one side of ``register_planes``: segmentation.fit_planes on the rows
+    ops.voxel_filter(preserve_order=True) keeps at ``plane_voxel`` (all rows when None); a plane's support is its point count."""
+    from . import ops
+    from .segmentation import fit_planes
+    x = points
+    if plane_voxel is not None:
+        keep = ops.voxel_filter(points, float(plane_voxel), preserve_order=True)
+        if keep is None:
+            raise ValueError('the cloud spans too many voxels of %g m for the voxel filter: use a larger plane_voxel' % plane_voxel)
+        x = points[keep].contiguous()
+    planes = fit_planes(x, float(distance_threshold), min_support=int(min_support), max_iterations=int(ransac_iters),
+                        max_models=int(max_planes), eps=cluster_eps, seed=int(seed))
+    params = planes.params.to(device=points.device, dtype=torch.float64).reshape(-1, 4).contiguous()
+    support = torch.tensor([int(i.shape[0]) for i in planes.indices], dtype=torch.int64, device=points.device)
+    return params, support
+
+
+def register_planes(points, survey, plane_voxel=0.1, distance_threshold=0.03, min_support=40, survey_min_support=100, ransac_iters=500,
+                    cluster_eps=0.4, max_planes=32, min_det=0.5, tol_dot=0.05, angle_tol=math.radians(3.0), offset_tol=0.05, voxel=0.25,
+                    eps=None, n_candidates=64, dedupe_rot=math.radians(5.0), dedupe_trans=0.25, seed=0, min_fitness=0.5, refine=True,
+                    refine_kwargs=None, mask=None, device=None):
+    """Registration of ``points`` [N,3] against ``survey`` (survey.SurveyCloud) WITHOUT a prior, from plane correspondences (DESIGN
+    "Plane registration"): for maps of rooms and corridors, where ``register_global``'s descriptors are those of a plane almost
+    everywhere.  Planes are fitted on both sides (segmentation.fit_planes on the rows the voxel filter keeps at ``plane_voxel``, all
+    rows when None; threshold ``distance_threshold``, ``ransac_iters`` hypotheses a round, clusters of ``cluster_eps``, at most
+    ``max_planes`` <= 64 planes of at least ``min_support`` / ``survey_min_support`` points; the survey's once per device and argument
+    set).  Every pairing of an independent triple of cloud planes (|det| >= ``min_det``) with three survey planes under the eight sign
+    patterns is enumerated on the device: those whose normals' dot products agree within ``tol_dot`` and whose handedness agrees are
+    fitted in closed form and scored by the summed support of the cloud planes that land on a survey plane within ``angle_tol``
+    (radians) and ``offset_tol``.  The best by (score, then lower number) are walked with suppression of poses within ``dedupe_rot``
+    AND ``dedupe_trans`` (at the cloud's bounding-box centre) of one already kept, until ``n_candidates`` distinct poses are kept;
+    they are ranked by fitness exactly as in ``register_global`` (the cloud voxel-filtered at ``voxel``, a survey point within
+    ``eps``, default 0.6 voxel).  The infinite planes of a box room agree under many wrong poses, and only the fitness tells them
+    apart: the true pose must be AMONG the candidates, which is why there are 64 of them and why they are distinct.
+    status 'too_few_planes': fewer than 3 planes on a side, or no independent triple (``register_global`` remains the fallback);
+    'no_hypothesis', 'low_fitness', 'empty' and ``refine`` / ``refine_kwargs`` / ``mask`` as in register_global.  The host reads the
+    per-round results of the plane fits, the number of valid hypotheses, the kept rows and the candidates, once each."""
+    from . import ops
+    voxel = float(voxel)
+    if not (voxel > 0.0 and voxel < float('inf')):
+        raise ValueError('voxel must be finite and > 0, got %r' % (voxel,))
+    eps = 0.6 * voxel if eps is None else float(eps)
+    n_cand, max_planes = int(n_candidates), int(max_planes)
+    if not (eps > 0.0 and n_cand >= 1 and 3 <= max_planes <= nv.DC_PLANEREG_MAX_PLANES):
+        raise ValueError('register_planes needs eps > 0, n_candidates >= 1 and 3 <= max_planes <= %d' % nv.DC_PLANEREG_MAX_PLANES)
+    tol = (float(min_det), float(tol_dot), math.cos(float(angle_tol)), float(offset_tol))
+    if not all(math.isfinite(v) for v in tol + (float(dedupe_rot), float(dedupe_trans))) or min(tol[0], tol[1], tol[3]) < 0.0:
+        raise ValueError('register_planes needs finite tolerances, min_det, tol_dot and offset_tol >= 0')
+    if device is None:
+        device = points.device if isinstance(points, torch.Tensor) and points.is_cuda else 'cuda'
+    sd = survey.on_device(device)
+    dev = sd.device
+    pts = torch.as_tensor(points).detach().to(device=dev, dtype=torch.float64).reshape(-1, 3)
+    keep = torch.isfinite(pts).all(dim=1)
+    if mask is not None:
+        m = torch.as_tensor(mask).to(device=dev).reshape(-1)
+        if m.dtype != torch.bool or m.shape[0] != pts.shape[0]:
+            raise ValueError('mask must be bool [%d]' % pts.shape[0])
+        keep = keep & m
+    pts = pts[keep].contiguous()
+    if pts.shape[0] == 0:
+        return _planes_result('empty')
+    with torch.no_grad():
+        cp, cs = cloud_planes(pts, plane_voxel, distance_threshold, min_support, ransac_iters, cluster_eps, max_planes, seed)
+        sp, _ = survey.planes(dev, plane_voxel, distance_threshold, survey_min_support, ransac_iters, cluster_eps, max_planes, seed)
+        n_planes = (int(cp.shape[0]), int(sp.shape[0]))
+        fkeep = ops.voxel_filter(pts, voxel, preserve_order=True)
+        if fkeep is None:
+            raise ValueError('the cloud spans too many voxels of %g m for the voxel filter: use a larger voxel' % voxel)
+        fp = pts[fkeep].contiguous()
+        n = fp.shape[0]
+        if min(n_planes) < nv.DC_PLANEREG_MIN_PLANES:
+            return _planes_result('too_few_planes', n_planes, n_points=n)
+        tri = ops.planereg_triples(cp, tol[0])
+        n_tri = tri.shape[0]
+        if n_tri == 0:
+            return _planes_result('too_few_planes', n_planes, n_points=n)
+        n_enum = n_tri * n_planes[1] ** 3 * 8
+        h, T, score = ops.planereg_hypotheses(cp, cs, sp, tri, *tol)          # a host read: the number of valid hypotheses
+        n_valid = h.shape[0]
+        if n_valid == 0:
+            res = _planes_result('no_hypothesis', n_planes, n_points=n)
+            res.n_triples, res.n_enumerated = n_tri, n_enum
+            return res
+        centre = 0.5 * (pts.amin(dim=0) + pts.amax(dim=0))
+        rows = ops.planereg_select(score, T, centre, n_cand, float(dedupe_rot), float(dedupe_trans))
+        rows = rows[rows >= 0]                                              # a host read: the distinct poses kept
+        sd.reserve(n)
+        idx1 = torch.empty((n, 1), dtype=torch.int32, device=dev)
+        dist1 = torch.empty((n, 1), dtype=torch.float64, device=dev)
+        Tc = T[rows].contiguous()
+        fitness = torch.empty((rows.shape[0],), dtype=torch.int64, device=dev)
+        for q in range(rows.shape[0]):
+            ops.knn_grid_query(sd.grid, fp, Tc[q], 1, r=eps, idx=idx1, dist=dist1)
+            fitness[q] = (idx1 >= 0).sum()
+        table = torch.stack([h[rows], score[rows], fitness], dim=1).cpu().numpy()      # the read of the result (int64: h passes 2^53)
+        Tc = Tc.cpu().numpy()
+    best = int(np.argmax(table[:, 2]))                              # the first of the largest: ties go to the earlier candidate
+    others = np.delete(table[:, 2], best)
+    status = 'ok' if table[best, 2] >= float(min_fitness) * n else 'low_fitness'
+    res = GlobalRegistration(Tc[best].copy(), status, table[best, 0], table[best, 1], table[best, 2], n, 0, n_valid, table)
+    res.method, res.n_planes, res.n_triples, res.n_enumerated = 'planes', n_planes, n_tri, n_enum
+    res.runner_up = int(others.max()) if len(others) else 0
+    if refine:
+        if status != 'ok':
+            warnings.warn('register_planes: refining from a prior of low fitness (%d of %d points): the result is not reliable'
+                          % (res.fitness, n))
+        kw = dict(refine_kwargs or {})
+        kw.setdefault('max_dist', 2.0 * voxel)
+        res.refined = register_cloud(pts, survey, init=Tc[best], device=dev, **kw)
         res.T = res.refined.T
     return res

@@ -101,6 +101,7 @@ class SurveyCloud(object):
         self._device = {}
         self._surfels = {}
         self._descriptors = {}
+        self._planes = {}
 
     def __len__(self):
         return self.points.shape[0]
@@ -174,6 +175,25 @@ class SurveyCloud(object):
             from .registration import global_descriptors
             with torch.no_grad():
                 got = self._descriptors[key] = global_descriptors(dev.points, dev.normals, *key[1:])
+        return got
+
+    def register_planes(self, points, **kw):
+        """registration.register_planes(points, self, **kw): the GlobalRegistration of a map of rooms or corridors without a prior."""
+        from .registration import register_planes
+        return register_planes(points, self, **kw)
+
+    def planes(self, device, plane_voxel=0.1, distance_threshold=0.03, min_support=100, ransac_iters=500, cluster_eps=0.4, max_planes=32,
+               seed=0):
+        """(params f64 [P,4], support i64 [P]) of the survey's side of registration.register_planes on ``device`` (a GPU): its planes
+        by registration.cloud_planes, computed once per device and argument set."""
+        dev = self.on_device(device)
+        key = (dev.device, None if plane_voxel is None else float(plane_voxel), float(distance_threshold), int(min_support),
+               int(ransac_iters), None if cluster_eps is None else float(cluster_eps), int(max_planes), int(seed))
+        got = self._planes.get(key)
+        if got is None:
+            from .registration import cloud_planes
+            with torch.no_grad():
+                got = self._planes[key] = cloud_planes(dev.points, *key[1:])
         return got
 
     def transformed(self, T):

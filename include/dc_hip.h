@@ -1314,6 +1314,31 @@ int dc_greg_fit(const double* p, const double* y, int64_t n_corr, int64_t n_hyp,
 int dc_greg_score(const int32_t* list, int64_t n_list, const double* T, int64_t n_hyp, const double* p, const double* y, int64_t n_corr,
                   double eps, int32_t* score, dcStream_t stream);
 
+/* ---- plane registration, the coarse stage from plane correspondences (depth_correction_amd/csrc/dc_planereg.hip, dc_planereg_math.h;
+ * DESIGN "Plane registration").  cloud_planes double [n_cloud,4] and survey_planes double [n_survey,4] are rows (n, d) with
+ * n.x + d = 0, support int64 [n_cloud] the cloud planes' point counts, triples int32 [n_triples,3] the cloud triples a < b < c in
+ * lexicographic order (all DEVICE).  Hypothesis h = (((u n_survey + i) n_survey + j) n_survey + k) 8 + s pairs triple u with the survey
+ * planes (i, j, k) under the signs s; the calls walk h_begin <= h < h_end <= n_triples n_survey^3 8.  Plane counts outside 3 .. 64, more
+ * than 41 664 triples, a range outside the enumeration and tolerances that are negative or not finite return DC_ERR_ARG; an empty range
+ * launches nothing.  Neither call allocates, copies, synchronises or uses an atomic; the same inputs give the same bits. ---- */
+#ifndef DC_PLANEREG_MAX_PLANES
+#define DC_PLANEREG_MAX_PLANES 64
+#endif
+/* Blocks (rows of counts / offsets) of a range of n_hyp hypotheses: every block owns 16 384 consecutive numbers. */
+int64_t dc_planereg_blocks(int64_t n_hyp);
+/* counts int32 [blocks] <- the valid hypotheses (rules 1 to 5 of dc_planereg_math.h) of every block's range. */
+int dc_planereg_count(const double* cloud_planes, const int64_t* support, int n_cloud, const double* survey_planes, int n_survey,
+                      const int32_t* triples, int64_t n_triples, int64_t h_begin, int64_t h_end, double min_det, double tol_dot,
+                      double cos_tol, double tol_d, int32_t* counts, dcStream_t stream);
+/* The valid hypotheses in ascending h: h_out int64 [n_valid], T_out double [n_valid,16] (survey frame from cloud frame), score_out int64
+ * [n_valid] (the summed support of the cloud planes that agree with a survey plane within cos_tol and tol_d), written at offsets int64
+ * [blocks], the exclusive scan of dc_planereg_count's counts for the same arguments, whose total is n_valid.  A row that would fall
+ * outside 0 .. n_valid-1 is not written. */
+int dc_planereg_fill(const double* cloud_planes, const int64_t* support, int n_cloud, const double* survey_planes, int n_survey,
+                     const int32_t* triples, int64_t n_triples, int64_t h_begin, int64_t h_end, double min_det, double tol_dot,
+                     double cos_tol, double tol_d, const int64_t* offsets, int64_t n_valid, int64_t* h_out, double* T_out,
+                     int64_t* score_out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
