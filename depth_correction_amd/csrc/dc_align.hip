@@ -8,7 +8,7 @@
 //   3. align_accumulate_kernel: a point is kept when idx >= 0 and d <= threshold; the 17 moments of the kept pairs about the two fixed
 //      origins, summed per wavefront by a shuffle tree, per block through LDS, one row of partials per block; the grid is capped at
 //      kAlignBlocksMax blocks and strides over the rest.
-//   4. align_finish_kernel, one block: the partials in a fixed order (align_lane_sum), the closed-form fit (dc_align_math.h), the
+//   4. align_finish_kernel, one block: the partials in a fixed order (dc_rowsum.h), the closed-form fit (dc_align_math.h), the
 //      estimate, the history row and the status word.
 //
 // The status word is the `stop` word of 1 and 2 and is tested by 3 and 4: once it is set every later launch returns at once, so
@@ -18,6 +18,7 @@
 #include "../../include/dc_hip.h"
 #include "dc_device.h"
 #include "dc_hostutil.h"
+#include "dc_rowsum.h"
 #include "dc_align_math.h"
 
 namespace dc {
@@ -85,25 +86,17 @@ __global__ __launch_bounds__(kBlock) void align_accumulate_kernel(const double* 
   }
 }
 
-// One block: threads 8 q .. 8 q + 7 sum value q over the blocks b = l, l + 8, ... in order (align_lane_sum), thread q adds the eight
-// sums of value q in order; thread 0 then solves and updates (align_finish_tail).
+// One block: threads 8 q .. 8 q + 7 sum value q over the blocks b = l, l + 8, ... in order, thread q adds the eight sums of value
+// q in order (rows_block_totals); thread 0 then solves and updates (align_finish_tail).
 __global__ __launch_bounds__(kBlock) void align_finish_kernel(const double* __restrict__ partials, int n_blocks,
                                                               const double* __restrict__ origins, AlignParams prm,
                                                               double* __restrict__ state, int32_t* __restrict__ status,
                                                               double* __restrict__ history, int n_hist_rows) {
-  __shared__ double s_part[DC_ALIGN_PARTIALS * kAlignSumLanes];
+  __shared__ double s_part[DC_ALIGN_PARTIALS * kRowSumLanes];
   __shared__ double s_tot[DC_ALIGN_PARTIALS];
   if (status[0] != 0) return;
-  const int t = threadIdx.x;
-  if (t < DC_ALIGN_PARTIALS * kAlignSumLanes) s_part[t] = align_lane_sum(partials, n_blocks, t / kAlignSumLanes, t % kAlignSumLanes);
-  __syncthreads();
-  if (t < DC_ALIGN_PARTIALS) {
-    double s = 0.0;
-    for (int l = 0; l < kAlignSumLanes; ++l) s += s_part[t * kAlignSumLanes + l];
-    s_tot[t] = s;
-  }
-  __syncthreads();
-  if (t != 0) return;
+  rows_block_totals<DC_ALIGN_PARTIALS, kRowSumLanes>(partials, n_blocks, s_part, s_tot);
+  if (threadIdx.x != 0) return;
   double o[6];
   for (int q = 0; q < 6; ++q) o[q] = origins[q];
   const int row = status[1];                        // iterations done so far = the row this one writes
@@ -111,21 +104,17 @@ __global__ __launch_bounds__(kBlock) void align_finish_kernel(const double* __re
   align_finish_tail(s_tot, o, prm, state, status, hist);
 }
 
-inline size_t align_up256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct AlignWs {
   void* qws; double* dist; int32_t* idx; double* partials; size_t total;
 };
 static AlignWs align_carve(void* ws, int64_t n) {
-  char* base = (char*)ws;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up256(bytes); return (void*)p; };
+  Carver cv(ws);
   AlignWs c;
-  c.qws = take(dc_quantile_workspace_bytes());
-  c.dist = (double*)take((size_t)n * sizeof(double));
-  c.idx = (int32_t*)take((size_t)n * sizeof(int32_t));
-  c.partials = (double*)take((size_t)kAlignBlocksMax * DC_ALIGN_PARTIALS * sizeof(double));
-  c.total = off;
+  c.qws = cv.take<char>(dc_quantile_workspace_bytes());
+  c.dist = cv.take<double>((size_t)n);
+  c.idx = cv.take<int32_t>((size_t)n);
+  c.partials = cv.take<double>((size_t)kAlignBlocksMax * DC_ALIGN_PARTIALS);
+  c.total = cv.off;
   return c;
 }
 

@@ -16,31 +16,8 @@ struct AlignParams {
 };
 
 constexpr int kAlignBlocksMax = 1024;   // most blocks (rows of partials) of dc_align_accumulate
-constexpr int kAlignSumLanes = 8;       // lanes that share the sum of one value over the blocks (dc_icp_finish's order)
 constexpr double kAlignRelEps = 1e-12;  // icp_solve6's rel_eps: the relative eigenvalue gap below which the fit is not unique
 constexpr int kAlignSweeps = 16;        // cyclic Jacobi sweeps at most (a 4 x 4 matrix converges in 4 - 6)
-
-// The order dc_align_finish adds the block partials [n_blocks, DC_ALIGN_PARTIALS] of value q in: icp_lane_sum / icp_block_sum of
-// dc_slam_math.h with this row length.
-DC_HD double align_lane_sum(const double* partials, int n_blocks, int q, int l) {
-  double s = 0.0;
-  int b = l;
-  // eight rows at a time: the loads are issued together, the additions keep their order (one load per addition would wait a
-  // memory round trip each)
-  for (; b + 7 * kAlignSumLanes < n_blocks; b += 8 * kAlignSumLanes) {
-    double v[8];
-    for (int u = 0; u < 8; ++u) v[u] = partials[(int64_t)(b + u * kAlignSumLanes) * DC_ALIGN_PARTIALS + q];
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; b < n_blocks; b += kAlignSumLanes) s += partials[(int64_t)b * DC_ALIGN_PARTIALS + q];
-  return s;
-}
-
-DC_HD double align_block_sum(const double* partials, int n_blocks, int q) {
-  double tot = 0.0;
-  for (int l = 0; l < kAlignSumLanes; ++l) tot += align_lane_sum(partials, n_blocks, q, l);
-  return tot;
-}
 
 // Horn's matrix N (row-major 4 x 4, symmetric) of C (row-major 3 x 3, C_ij = sum p_i y_j): q^T N q = trace(R(q)^T ... ) is largest
 // for the unit quaternion q = (q0, qx, qy, qz) of the rotation that takes p to y.

@@ -8,11 +8,10 @@
 //   2. dc_knn_grid_query (k = 1, r = max_dist) of those rows in the survey's persistent grid: the kernels of dc_knn_build, so the
 //      index and the distance are its bits (smallest d^2, a tie to the lower index, d^2 < max_dist^2).
 //   3. with inlier_ratio < 1, dc_quantile of the distances (+inf rows, the unmatched ones, do not count) -> threshold.
-//   4. cloud_loss_kernel, one lane per point, 128 lanes per block, the blocks laid out per scan from scan_ptr (scan s owns
-//      ceil(n_s / 128) consecutive blocks), so a block's pose sums are the sums of its one scan.  A lane classifies its point
-//      (invalid / gated / trimmed / used), forms the term and dl/dx (dc_cloudloss_math.h) and runs the point epilogue of
-//      dc_points_bwd (points_bwd_point).  The block's partial row [sum l, used, gated, trimmed, invalid, dw[P], de[P], d[R|t][12]]
-//      is summed in a fixed order: a shuffle tree within the wavefront, then wavefront 0 + wavefront 1 through LDS.
+//   4. cloud_loss_kernel, one lane per point, 128 lanes per block, the blocks laid out per scan from scan_ptr (dc_scanloss.h: the
+//      layout, the block's setup and partial row, the finishing).  A lane classifies its point (invalid / gated / trimmed / used),
+//      forms the term and dl/dx (dc_cloudloss_math.h) and runs the point epilogue of dc_points_bwd (points_bwd_point).  The block's
+//      partial row is [sum l, used, gated, trimmed, invalid, dw[P], de[P], d[R|t][12]].
 //   5. cloud_loss_finish_kernel, one block: per scan, in scan order, four interleaved chains add the scan's block rows in block
 //      order, the four sums are added in chain order; the scalar columns are then added over the scans in scan order.
 //
@@ -24,50 +23,17 @@
 #include "dc_pointmath.h"
 #include "dc_points_dev.h"
 #include "dc_cloudloss_math.h"
+#include "dc_scanloss.h"
 #include "../../include/dc_hip.h"
 
 namespace {
 
 using namespace dc;
 
-constexpr int kLossBlock = 128;
-constexpr int kLossWaves = kLossBlock / kWave;
 constexpr int kFixedCols = 5;                                 // sum l, used, gated, trimmed, invalid
 constexpr int kMaxCols = kFixedCols + 2 * DC_MAX_MODEL_TERMS + 12;
-constexpr int kFinishBlock = 256;
-constexpr int kFinishCols = 64;                               // >= kMaxCols
-constexpr int kChains = kFinishBlock / kFinishCols;
+constexpr int kFinishCols = 64;                               // one finishing lane per column, four chains
 constexpr int kHeadDoubles = 32;                              // [0,16) the identity pose, [16] the threshold
-static_assert(kMaxCols <= kFinishCols, "one finishing lane per column");
-
-// points [a, b) of scan s (scan_ptr == NULL: one scan holding every point), clipped to [0, n]
-__device__ __forceinline__ void scan_range(const int64_t* __restrict__ scan_ptr, int s, int64_t n, int64_t* a, int64_t* b) {
-  int64_t lo = scan_ptr ? scan_ptr[s] : 0, hi = scan_ptr ? scan_ptr[s + 1] : n;
-  lo = lo < 0 ? 0 : (lo > n ? n : lo);
-  hi = hi < lo ? lo : (hi > n ? n : hi);
-  *a = lo;
-  *b = hi;
-}
-__device__ __forceinline__ int64_t blocks_of(int64_t count) { return (count + kLossBlock - 1) / kLossBlock; }
-
-// the scan of block `blk` and its points [first, last) (block-uniform); false for a block past the last scan
-__device__ __forceinline__ bool block_scan(const int64_t* __restrict__ scan_ptr, int n_scans, int64_t n, int64_t blk, int* scan,
-                                           int64_t* first, int64_t* last) {
-  int64_t cum = 0;
-  for (int s = 0; s < n_scans; ++s) {
-    int64_t a, b;
-    scan_range(scan_ptr, s, n, &a, &b);
-    const int64_t nb = blocks_of(b - a);
-    if (blk < cum + nb) {
-      *scan = s;
-      *first = a + (blk - cum) * kLossBlock;
-      *last = b;
-      return true;
-    }
-    cum += nb;
-  }
-  return false;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(kLossBlock) cloud_points_kernel(PointInputs in, const uint8_t* __restrict__ mask,
@@ -114,26 +80,19 @@ __global__ void __launch_bounds__(kLossBlock) cloud_loss_kernel(PointInputs in, 
                                                                 double* __restrict__ resid_out, double* __restrict__ partials) {
   __shared__ double s_pose[12];
   __shared__ double s_red[kLossWaves][kMaxCols];
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   int scan = -1;
   int64_t first = 0, last = 0;
   if (!block_scan(scan_ptr, in.n_scans, n, (int64_t)blockIdx.x, &scan, &first, &last)) return;   // the grid is an upper bound
-  if (in.poses && tid < 12) s_pose[tid] = in.poses[(int64_t)scan * 12 + tid];
-  __syncthreads();
-  PointInputs one = in;
-  one.scan_id = nullptr;
-  one.n_scans = 1;
-  const PoseTile tile{in.poses ? s_pose : nullptr};
+  PointInputs one;
   ModelParams mp;
-  load_model(in, mp);
-  const int nt = in.model_kind == DC_MODEL_NONE ? 0 : in.n_terms;
+  int nt;
+  scan_block_setup(in, scan, s_pose, one, mp, nt);
+  const PoseTile tile{in.poses ? s_pose : nullptr};
   const double thr = *threshold;
 
   double acc[kFixedCols] = {0.0, 0.0, 0.0, 0.0, 0.0}, gw[DC_MAX_MODEL_TERMS], ge[DC_MAX_MODEL_TERMS], gT[6];
-#pragma unroll
-  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) gw[k] = ge[k] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) gT[k] = 0.0;
+  zero_grads(gw, ge, gT);
   const int64_t g = first + tid;
   if (g < last) {
     int32_t hit = -1;
@@ -165,104 +124,32 @@ __global__ void __launch_bounds__(kLossBlock) cloud_loss_kernel(PointInputs in, 
     if (dist_out) dist_out[g] = dist;
     if (resid_out) resid_out[g] = resid;
   }
-  // block sums, column by column: a fixed shuffle tree per wavefront, then the wavefronts in order
-#pragma unroll
-  for (int q = 0; q < kFixedCols; ++q) {
-    const double s = wave_sum(acc[q]);
-    if (lane == 0) s_red[wave][q] = s;
-  }
-#pragma unroll
-  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) {
-    if (k < nt) {
-      const double sw = wave_sum(gw[k]), se = wave_sum(ge[k]);
-      if (lane == 0) {
-        s_red[wave][kFixedCols + k] = sw;
-        s_red[wave][kFixedCols + nt + k] = se;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 12; ++q) {
-    // dL/d[R|t]_{a,b} = g_a [xl, 1]_b, the product rounded before it is added (no contraction into the sum)
-    const double v = (q & 3) == 3 ? gT[q >> 2] : __dmul_rn(gT[q >> 2], gT[3 + (q & 3)]);
-    const double s = wave_sum(v);
-    if (lane == 0) s_red[wave][kFixedCols + 2 * nt + q] = s;
-  }
-  __syncthreads();
-  const int ncols = kFixedCols + 2 * nt + 12;
-  if (tid < ncols) {
-    double t = s_red[0][tid];
-#pragma unroll
-    for (int wv = 1; wv < kLossWaves; ++wv) t += s_red[wv][tid];
-    partials[(int64_t)blockIdx.x * ncols + tid] = t;
-  }
+  scan_block_store<kFixedCols>(acc, gw, ge, gT, nt, s_red, partials);
 }
 
 // out = [mean loss, used, gated, trimmed, invalid, threshold, dL/dw[P], dL/de[P], dL/d[R|t][12 S]], the gradients divided by M = used
-__global__ void __launch_bounds__(kFinishBlock) cloud_loss_finish_kernel(const double* __restrict__ partials, int nt,
-                                                                        const int64_t* __restrict__ scan_ptr, int64_t n, int n_scans,
-                                                                        int64_t n_rows, const double* __restrict__ threshold,
-                                                                        double* __restrict__ out) {
-  __shared__ double s_red[kChains][kFinishCols];
-  __shared__ double s_count;
-  const int tid = threadIdx.x, col = tid & (kFinishCols - 1), chain = tid / kFinishCols;
-  const int ncols = kFixedCols + 2 * nt + 12, n_scalar = kFixedCols + 2 * nt;
-  const int o_grad = 6 + 2 * nt;                              // first pose gradient in `out`
-  double total = 0.0;                                         // chain 0, scalar columns: the sum over the scans so far
-  int64_t blk0 = 0;
-  for (int s = 0; s < n_scans; ++s) {
-    int64_t a, b;
-    scan_range(scan_ptr, s, n, &a, &b);
-    int64_t nb = blocks_of(b - a);
-    if (blk0 + nb > n_rows) nb = n_rows - blk0;               // never past the rows the loss kernel had blocks for
-    double sum = 0.0;
-    if (col < ncols)
-      for (int64_t r = chain; r < nb; r += kChains) sum += partials[(blk0 + r) * ncols + col];
-    s_red[chain][col] = sum;
-    __syncthreads();
-    if (chain == 0 && col < ncols) {
-      double t = s_red[0][col];
-#pragma unroll
-      for (int ch = 1; ch < kChains; ++ch) t += s_red[ch][col];
-      if (col < n_scalar) total += t;
-      else out[o_grad + (int64_t)s * 12 + (col - n_scalar)] = t;
-    }
-    __syncthreads();
-    blk0 += nb;
-  }
-  if (tid == 1) s_count = total;                              // M = used
-  __syncthreads();
-  const double M = s_count;
-  if (chain == 0 && col < n_scalar) {
-    if (col == 0) out[0] = M > 0.0 ? total / M : __longlong_as_double(0x7ff8000000000000ll);
-    else if (col < kFixedCols) out[col] = total;
-    else out[col + 1] = M > 0.0 ? total / M : 0.0;            // (out[5] is the threshold)
-  }
-  if (tid == kFinishCols) out[5] = threshold ? *threshold : INFINITY;
-  for (int64_t i = tid; i < 12 * (int64_t)n_scans; i += kFinishBlock) {
-    const double v = out[o_grad + i];                         // written by this block before the barriers above
-    out[o_grad + i] = M > 0.0 ? v / M : 0.0;
-  }
+__global__ void __launch_bounds__(kLossFinishBlock) cloud_loss_finish_kernel(const double* __restrict__ partials, int nt,
+                                                                            const int64_t* __restrict__ scan_ptr, int64_t n,
+                                                                            int n_scans, int64_t n_rows,
+                                                                            const double* __restrict__ threshold,
+                                                                            double* __restrict__ out) {
+  scan_loss_finish<kFixedCols, kLossFinishBlock / kFinishCols, kFinishCols>(partials, nt, scan_ptr, n, n_scans, n_rows, 6, out);
+  if (threadIdx.x == kFinishCols) out[5] = threshold ? *threshold : INFINITY;
 }
-
-inline int64_t max_blocks(int64_t n, int n_scans) { return n / kLossBlock + n_scans; }      // >= sum_s ceil(n_s / 128)
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 struct CloudWs {
   double* head; void* qws; double* x; double* dist; int32_t* idx; double* partials; size_t total;
 };
 CloudWs carve(void* ws, int64_t n, int n_scans, int n_terms) {
-  char* base = (char*)ws;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += up256(bytes); return (void*)p; };
+  Carver cv(ws);
   CloudWs c;
-  c.head = (double*)take(kHeadDoubles * sizeof(double));
-  c.qws = take(dc_quantile_workspace_bytes());
-  c.x = (double*)take((size_t)n * 3 * sizeof(double));
-  c.dist = (double*)take((size_t)n * sizeof(double));
-  c.idx = (int32_t*)take((size_t)n * sizeof(int32_t));
-  c.partials = (double*)take((size_t)(max_blocks(n, n_scans) + 1) * (size_t)(kFixedCols + 2 * n_terms + 12) * sizeof(double));
-  c.total = off;
+  c.head = cv.take<double>(kHeadDoubles);
+  c.qws = cv.take<char>(dc_quantile_workspace_bytes());
+  c.x = cv.take<double>((size_t)n * 3);
+  c.dist = cv.take<double>((size_t)n);
+  c.idx = cv.take<int32_t>((size_t)n);
+  c.partials = cv.take<double>((size_t)(max_blocks(n, n_scans) + 1) * (size_t)(kFixedCols + 2 * n_terms + 12));
+  c.total = cv.off;
   return c;
 }
 
@@ -282,30 +169,18 @@ int dc_cloud_loss(void* grid_ws, size_t grid_ws_bytes, int64_t n_query_max, cons
                   double inlier_ratio, int32_t* idx_out, double* dist_out, double* resid_out, double* out, void* ws, size_t ws_bytes,
                   dcStream_t stream) {
   if (n_map < 1 || n < 0 || n_scans < 0 || !grid_ws || !map_points || (plane && !map_normals) || !out) return DC_ERR_ARG;
-  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
-  if (!(max_dist > 0.0) || !(max_dist < INFINITY)) return DC_ERR_ARG;
-  if (!(inlier_ratio >= 0.0 && inlier_ratio <= 1.0)) return DC_ERR_ARG;
-  if (model_kind < DC_MODEL_NONE || model_kind > DC_MODEL_LAST) return DC_ERR_ARG;
-  if (model_kind != DC_MODEL_NONE) {
-    if (n_terms < 1 || n_terms > DC_MAX_MODEL_TERMS || !w || !e || (n > 0 && !inc)) return DC_ERR_ARG;
-    if (model_kind == DC_MODEL_LINEAR && n_terms != 3) return DC_ERR_ARG;
-    if ((model_kind == DC_MODEL_INVCOS || model_kind == DC_MODEL_SCALED_INVCOS) && n_terms != 1) return DC_ERR_ARG;
-  } else {
-    n_terms = 0;
-  }
-  if (n > 0 && (n_scans < 1 || !dirs || !depth)) return DC_ERR_ARG;
-  if (n_scans > 1 && !scan_ptr) return DC_ERR_ARG;
-  if (n > n_query_max) return DC_ERR_ARG;                     // the grid's query buffer holds n_query_max rows
-  const int64_t rows = max_blocks(n, n_scans);
-  if (rows > 0x7fffffff) return DC_ERR_UNSUPPORTED;
+  PointInputs in;
+  int64_t rows;
+  const bool own_ok = max_dist > 0.0 && max_dist < INFINITY && inlier_ratio >= 0.0 && inlier_ratio <= 1.0 &&
+                      n <= n_query_max;                       // the grid's query buffer holds n_query_max rows
+  const int rc0 = scan_loss_args(vps, dirs, depth, inc, lmask, dtype, n, scan_ptr, poses, n_scans, model_kind, &n_terms, w, e, own_ok,
+                                 &in, &rows);
+  if (rc0 != DC_OK) return rc0;
   if (n > 0 && (!ws || ws_bytes < dc_cloud_loss_workspace_bytes(n, n_scans, n_terms))) return DC_ERR_WORKSPACE;
   const CloudWs c = carve(ws, n, n_scans, n_terms);
   const hipStream_t st = (hipStream_t)stream;
   const bool trim = inlier_ratio < 1.0;
   if (n > 0) {
-    PointInputs in;
-    in.vps = vps; in.dirs = dirs; in.depth = depth; in.inc = inc; in.lmask = lmask; in.scan_id = nullptr;
-    in.poses = poses; in.w = w; in.e = e; in.model_kind = model_kind; in.n_terms = n_terms; in.n_scans = n_scans;
     const dim3 grid((unsigned)rows), block(kLossBlock);
     // rows of x no scan covers (a scan_ptr that does not span [0, n]) must not reach the search or the quantile as stale memory
     DC_HIP(hipMemsetAsync(c.x, 0xff, (size_t)n * 3 * sizeof(double), st));
@@ -328,8 +203,8 @@ int dc_cloud_loss(void* grid_ws, size_t grid_ws_bytes, int64_t n_query_max, cons
                                                         c.partials);
     DC_HIP(hipGetLastError());
   }
-  cloud_loss_finish_kernel<<<1, kFinishBlock, 0, st>>>(c.partials, n_terms, scan_ptr, n, n_scans, rows,
-                                                       (n > 0 && trim) ? c.head + 16 : nullptr, out);
+  cloud_loss_finish_kernel<<<1, kLossFinishBlock, 0, st>>>(c.partials, n_terms, scan_ptr, n, n_scans, rows,
+                                                           (n > 0 && trim) ? c.head + 16 : nullptr, out);
   DC_HIP(hipGetLastError());
   return DC_OK;
 }

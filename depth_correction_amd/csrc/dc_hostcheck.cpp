@@ -5,6 +5,7 @@
 #include "dc_bvh.h"
 #include "dc_eig3.h"
 #include "dc_pointmath.h"
+#include "dc_rowsum.h"
 #include "dc_slam_math.h"
 #include "dc_trimath.h"
 #include "dc_meshloss_math.h"
@@ -139,6 +140,14 @@ int dc_host_icp_solve(const double* a21, const double* b6, double* x6) { return 
 // out = [R(x[0:3]) x[3:6]; 0 1] T (row-major 4 x 4): the finish kernel's pose update
 void dc_host_icp_step(const double* x6, const double* T, double* out) { dc::icp_apply_step(x6, T, out); }
 
+// The fixed-order row sum every finish kernel shares (dc_rowsum.h): value q of rows [n_rows, stride] on `lanes` = 4 or 8 lanes
+// (the chains of dc_cloud_loss's finishing; everything else); NaN for another lane count.
+double dc_host_rows_sum(const double* rows, int64_t n_rows, int stride, int q, int lanes) {
+  if (lanes == 4) return dc::rows_sum<4>(rows, n_rows, stride, q);
+  if (lanes == 8) return dc::rows_sum<8>(rows, n_rows, stride, q);
+  return NAN;
+}
+
 // dc_icp_finish on the host: the same argument checks, the partials summed in the kernel's order, the same tail; state [DC_ICP_STATE_COUNT]
 // and status [4] are host arrays.  0, or 1 for arguments dc_icp_finish refuses.
 int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
@@ -147,7 +156,7 @@ int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double m
   if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1) return 1;
   if (status[0] != 0) return 0;
   double tot[DC_ICP_PARTIALS];
-  for (int q = 0; q < DC_ICP_PARTIALS; ++q) tot[q] = dc::icp_block_sum(partials, n_blocks, q);
+  for (int q = 0; q < DC_ICP_PARTIALS; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, DC_ICP_PARTIALS, q);
   const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
   dc::icp_finish_tail(tot, m, prm, state, status);
   return 0;
@@ -162,7 +171,7 @@ int dc_host_icp_ct_finish(const double* partials, int n_blocks, int64_t m, doubl
   if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1 || !(beta_v >= 0.0) || !(beta_w >= 0.0)) return 1;
   if (status[0] != 0) return 0;
   double tot[DC_ICP_CT_PARTIALS], work[dc::kIcpCtWork];
-  for (int q = 0; q < DC_ICP_CT_PARTIALS; ++q) tot[q] = dc::icp_ct_block_sum(partials, n_blocks, q);
+  for (int q = 0; q < DC_ICP_CT_PARTIALS; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, DC_ICP_CT_PARTIALS, q);
   const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
   const dc::IcpCtParams cp{beta_v, beta_w, max_twist_trans, max_twist_rot};
   dc::icp_ct_finish_tail(tot, m, prm, cp, state, ct_state, status, work);
@@ -726,7 +735,7 @@ int dc_host_align_finish(const double* partials, int n_blocks, const double* ori
   if (!(min_rot >= 0.0) || !(min_trans >= 0.0) || min_pairs < 3 || max_iters < 1 || n_history_rows < 0) return 1;
   if (status[0] != 0) return 0;
   double tot[DC_ALIGN_PARTIALS];
-  for (int q = 0; q < DC_ALIGN_PARTIALS; ++q) tot[q] = dc::align_block_sum(partials, n_blocks, q);
+  for (int q = 0; q < DC_ALIGN_PARTIALS; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, DC_ALIGN_PARTIALS, q);
   const dc::AlignParams prm{min_rot, min_trans, min_pairs, max_iters};
   const int row = status[1];
   double* hist = (history && row >= 0 && row < n_history_rows) ? history + (int64_t)row * DC_ALIGN_HISTORY_COLS : nullptr;

@@ -19,6 +19,7 @@
 #include "../../include/dc_hip.h"
 #include "dc_device.h"
 #include "dc_hostutil.h"
+#include "dc_rowsum.h"
 #include "dc_slam_math.h"
 #include "dc_sweepmath.h"
 
@@ -105,23 +106,15 @@ __global__ __launch_bounds__(kBlock) void icp_accumulate_kernel(const double* __
   }
 }
 
-// One block: threads 8 q .. 8 q + 7 sum value q over the blocks b = l, l + 8, ... in order (icp_lane_sum), thread q adds the eight
-// sums of value q in order; thread 0 then solves and updates (icp_finish_tail).
+// One block: threads 8 q .. 8 q + 7 sum value q over the blocks b = l, l + 8, ... in order, thread q adds the eight sums of value
+// q in order (rows_block_totals); thread 0 then solves and updates (icp_finish_tail).
 __global__ __launch_bounds__(kBlock) void icp_finish_kernel(const double* __restrict__ partials, int n_blocks, int64_t m, IcpParams prm,
                                                             double* __restrict__ state, int32_t* __restrict__ status) {
-  __shared__ double s_part[DC_ICP_PARTIALS * kIcpSumLanes];
+  __shared__ double s_part[DC_ICP_PARTIALS * kRowSumLanes];
   __shared__ double s_tot[DC_ICP_PARTIALS];
   if (status[0] != 0) return;
-  const int t = threadIdx.x;
-  if (t < DC_ICP_PARTIALS * kIcpSumLanes) s_part[t] = icp_lane_sum(partials, n_blocks, t / kIcpSumLanes, t % kIcpSumLanes);
-  __syncthreads();
-  if (t < DC_ICP_PARTIALS) {
-    double s = 0.0;
-    for (int l = 0; l < kIcpSumLanes; ++l) s += s_part[t * kIcpSumLanes + l];
-    s_tot[t] = s;
-  }
-  __syncthreads();
-  if (t != 0) return;
+  rows_block_totals<DC_ICP_PARTIALS, kRowSumLanes>(partials, n_blocks, s_part, s_tot);
+  if (threadIdx.x != 0) return;
   icp_finish_tail(s_tot, m, prm, state, status);
 }
 
@@ -215,21 +208,12 @@ __global__ __launch_bounds__(kBlock) void icp_ct_accumulate_kernel(const double*
 __global__ __launch_bounds__(kBlock) void icp_ct_finish_kernel(const double* __restrict__ partials, int n_blocks, int64_t m, IcpParams prm,
                                                                IcpCtParams cp, double* __restrict__ state, double* __restrict__ ct,
                                                                int32_t* __restrict__ status) {
-  __shared__ double s_part[DC_ICP_CT_PARTIALS * kIcpSumLanes];
+  __shared__ double s_part[DC_ICP_CT_PARTIALS * kRowSumLanes];
   __shared__ double s_tot[DC_ICP_CT_PARTIALS];
   __shared__ double s_work[kIcpCtWork];
   if (status[0] != 0) return;
-  const int t = threadIdx.x;
-  for (int e = t; e < DC_ICP_CT_PARTIALS * kIcpSumLanes; e += kBlock)
-    s_part[e] = icp_ct_lane_sum(partials, n_blocks, e / kIcpSumLanes, e % kIcpSumLanes);
-  __syncthreads();
-  if (t < DC_ICP_CT_PARTIALS) {
-    double s = 0.0;
-    for (int l = 0; l < kIcpSumLanes; ++l) s += s_part[t * kIcpSumLanes + l];
-    s_tot[t] = s;
-  }
-  __syncthreads();
-  if (t != 0) return;
+  rows_block_totals<DC_ICP_CT_PARTIALS, kRowSumLanes>(partials, n_blocks, s_part, s_tot);
+  if (threadIdx.x != 0) return;
   icp_ct_finish_tail(s_tot, m, prm, cp, state, ct, status, s_work);
 }
 

@@ -100,24 +100,9 @@ struct IcpParams {
 };
 
 constexpr int kIcpBlocksMax = 512;      // most blocks (rows of partials) of dc_icp_accumulate
-constexpr int kIcpSumLanes = 8;         // lanes that share the sum of one value over the blocks
 
-// The order dc_icp_finish adds the block partials [n_blocks, DC_ICP_PARTIALS] of value q in: lane l of eight takes the blocks l,
-// l + 8, ... in order (icp_lane_sum: one thread of the finish kernel each), then the eight sums are added in order (the kernel's
-// second stage; icp_block_sum is the same additions run one after the other, for the host build).
-DC_HD double icp_lane_sum(const double* partials, int n_blocks, int q, int l) {
-  double s = 0.0;
-  for (int b = l; b < n_blocks; b += kIcpSumLanes) s += partials[(int64_t)b * DC_ICP_PARTIALS + q];
-  return s;
-}
-
-DC_HD double icp_block_sum(const double* partials, int n_blocks, int q) {
-  double tot = 0.0;
-  for (int l = 0; l < kIcpSumLanes; ++l) tot += icp_lane_sum(partials, n_blocks, q, l);
-  return tot;
-}
-
-// The single-thread tail of dc_icp_finish once the DC_ICP_PARTIALS totals of an iteration are complete: counts the iteration,
+// The single-thread tail of dc_icp_finish once the DC_ICP_PARTIALS totals of an iteration are complete (the block partials
+// [n_blocks, DC_ICP_PARTIALS] added in the order of dc_rowsum.h, eight lanes): counts the iteration,
 // records pairs / SSE / overlap, solves, and then in this order: DC_ICP_FAIL_PAIRS, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE,
 // DC_ICP_FAIL_BOUND (each leaves the estimate as it was), the estimate and the increment history updated, DC_ICP_CONVERGED,
 // DC_ICP_MAX_ITERS.  A status word that is already set is the caller's to test: this function is not called then.
@@ -271,19 +256,6 @@ DC_HD void icp_ct_finish_tail(const double* tot, int64_t m, const IcpParams& prm
     if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
   }
   if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;
-}
-
-// icp_lane_sum / icp_block_sum for rows of DC_ICP_CT_PARTIALS values: the same order.
-DC_HD double icp_ct_lane_sum(const double* partials, int n_blocks, int q, int l) {
-  double s = 0.0;
-  for (int b = l; b < n_blocks; b += kIcpSumLanes) s += partials[(int64_t)b * DC_ICP_CT_PARTIALS + q];
-  return s;
-}
-
-DC_HD double icp_ct_block_sum(const double* partials, int n_blocks, int q) {
-  double tot = 0.0;
-  for (int l = 0; l < kIcpSumLanes; ++l) tot += icp_ct_lane_sum(partials, n_blocks, q, l);
-  return tot;
 }
 
 }  // namespace dc

@@ -344,51 +344,46 @@ def icp_loss(clouds, poses=None, model=None, masks=None, **kwargs):
     return loss / len(clouds), loss_cloud
 
 
-# ---- supervised loss against a ground-truth mesh -------------------------------------------------------------------
-class _MeshLossSequence(torch.autograd.Function):
-    """mesh_loss of one sequence through dc_mesh_loss: forward and backward come out of the same host call."""
+# ---- supervised losses against a ground-truth mesh and against a surveyed point cloud ------------------------------------------
+class _ScanLossSequence(torch.autograd.Function):
+    """mesh_loss / cloud_loss of one sequence through dc_mesh_loss / dc_cloud_loss: forward and backward come out of the same host
+    call.  ``opts``: the plan's options as sorted (name, value) pairs."""
 
     @staticmethod
-    def forward(ctx, w, exponent, poses, plan, kind, squared, max_dist):
+    def forward(ctx, w, exponent, poses, plan, kind, opts):
         P12 = poses.detach().to(torch.float64)[:, :3, :].reshape(-1, 12).contiguous()
         wv = None if w is None else w.detach().reshape(-1).to(torch.float64).contiguous()
         ev = None if exponent is None else exponent.detach().reshape(-1).to(torch.float64).contiguous()
         want_e = isinstance(exponent, torch.Tensor) and bool(ctx.needs_input_grad[1])
-        out = plan.eval(P12, kind, wv, ev, squared=squared, max_dist=max_dist, want_exponent=want_e)
+        out = plan.eval(P12, kind, wv, ev, want_exponent=want_e, **dict(opts))
         ctx.save_for_backward(out)
         ctx.meta = (None if w is None else (w.shape, w.dtype), poses.dtype, poses.shape[0],
-                    exponent.shape if isinstance(exponent, torch.Tensor) else None)
+                    exponent.shape if isinstance(exponent, torch.Tensor) else None, plan.header)
         return out[0].clone()
 
     @staticmethod
     def backward(ctx, g):
         out, = ctx.saved_tensors
-        wmeta, pdt, ns, eshape = ctx.meta
-        nt = (out.numel() - 4 - 12 * ns) // 2
+        wmeta, pdt, ns, eshape, h = ctx.meta
+        nt = (out.numel() - h - 12 * ns) // 2
         gw = ge = gT = None
         if wmeta is not None and ctx.needs_input_grad[0]:
-            gw = (g * out[4:4 + nt]).reshape(wmeta[0]).to(wmeta[1])
+            gw = (g * out[h:h + nt]).reshape(wmeta[0]).to(wmeta[1])
         if eshape is not None and ctx.needs_input_grad[1]:
-            ge = (g * out[4 + nt:4 + 2 * nt]).reshape(eshape)
+            ge = (g * out[h + nt:h + 2 * nt]).reshape(eshape)
         if ctx.needs_input_grad[2]:
             gT = torch.zeros((ns, 4, 4), dtype=torch.float64, device=out.device)
-            gT[:, :3, :] = (g * out[4 + 2 * nt:]).reshape(ns, 3, 4)
+            gT[:, :3, :] = (g * out[h + 2 * nt:]).reshape(ns, 3, 4)
             gT = gT.to(pdt)
-        return gw, ge, gT, None, None, None, None
+        return gw, ge, gT, None, None, None
 
 
-class _MeshLossPlan(object):
-    """What is constant over the optimisation of one sequence against its mesh: the scans' fields concatenated scan-major, the
-    scan offsets, the mesh's tree, the loss mask, the workspace -- and the leaf hint, which starts at -1 and is carried from one
-    evaluation to the next (a point's nearest face changes little between two optimiser steps)."""
+class _ScanLossPlan(object):
+    """What is constant over the optimisation of one sequence against its target: the scans' fields concatenated scan-major, the
+    scan offsets, the loss mask, the workspace per term count.  A subclass adds the target, ``header`` (the entries of ``out`` in
+    front of the gradients), ``_workspace`` and ``_call``, its one ops call."""
 
-    def __init__(self, seq_clouds, mesh, point_mask, with_model):
-        self._fields(seq_clouds, point_mask, with_model)
-        self.mesh = mesh
-        self.bvh = mesh.on_device(self.device)[3]
-        self.leaf_hint = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
-
-    def _fields(self, seq_clouds, point_mask, with_model):
+    def __init__(self, seq_clouds, point_mask, with_model):
         dev = seq_clouds[0].dirs.device
         sizes = [len(c) for c in seq_clouds]
 
@@ -413,142 +408,49 @@ class _MeshLossPlan(object):
         self.mask = None if point_mask is None else torch.as_tensor(point_mask, device=dev).to(torch.bool).contiguous()
         self._ws = {}
 
-    def eval(self, poses12, kind=None, w=None, e=None, squared=False, max_dist=None, want_exponent=False, want_points=False):
+    def eval(self, poses12, kind=None, w=None, e=None, **opts):
         nt = 0 if not kind else w.numel()
         ws = self._ws.get(nt)
         if ws is None:
-            ws = self._ws[nt] = ops.mesh_loss_workspace(self.n, self.n_scans, nt, self.device)
-        return ops.mesh_loss(self.bvh, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, squared=squared, max_dist=max_dist,
-                             leaf_hint=self.leaf_hint, want_points=want_points, want_exponent=want_exponent, ws=ws)
+            ws = self._ws[nt] = self._workspace(self.n, self.n_scans, nt, self.device)
+        return self._call(poses12, kind, w, e, ws=ws, **opts)
 
 
-_mesh_plans = PlanRegistry()
+class _MeshLossPlan(_ScanLossPlan):
+    """The mesh's tree, and the leaf hint, which starts at -1 and is carried from one evaluation to the next (a point's nearest face
+    changes little between two optimiser steps)."""
+    header, _workspace = 4, staticmethod(ops.mesh_loss_workspace)
+
+    def __init__(self, seq_clouds, mesh, point_mask, with_model):
+        super().__init__(seq_clouds, point_mask, with_model)
+        self.mesh = mesh
+        self.bvh = mesh.on_device(self.device)[3]
+        self.leaf_hint = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+
+    def _call(self, poses12, kind, w, e, **opts):
+        return ops.mesh_loss(self.bvh, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, leaf_hint=self.leaf_hint, **opts)
 
 
-def _mesh_sequence_plan(seq_clouds, mesh, point_mask, with_model):
-    fields = [t for c in seq_clouds for t in (c.vps, c.dirs, c.depth, c.inc_angles, c.mask)] + [point_mask, mesh]
-    return _mesh_plans.get(fields, (bool(with_model),), lambda: _MeshLossPlan(seq_clouds, mesh, point_mask, with_model))
-
-
-def _unfused_mesh_sequence(seq_clouds, seq_poses, model, mesh, point_mask, squared, max_dist):
-    """The same loss from tensor operations: x in fp64 through the model and the poses, the closest points (detached) from
-    ops.mesh_closest, l = |x - c|, torch autograd.  For models without a kernel kind, and what the fused form is tested against."""
-    dev = seq_clouds[0].dirs.device
-    parts = []
-    for i, c in enumerate(seq_clouds):
-        c64 = DepthCloud(vps=c.vps.double(), dirs=c.dirs.double(), depth=c.depth.double(),
-                         inc_angles=None if c.inc_angles is None else c.inc_angles.double(), mask=c.mask)
-        if model is not None:
-            c64 = model(c64)
-        if seq_poses is not None:
-            c64 = c64.transform(seq_poses[i].double())
-        parts.append(c64.vps + c64.depth * c64.dirs)
-    x = torch.cat(parts)
-    bvh = mesh.on_device(dev)[3]
-    face, _, closest = ops.mesh_closest(bvh, x.detach().contiguous(), max_dist=max_dist)
-    used = face >= 0
-    if point_mask is not None:
-        used = used & torch.as_tensor(point_mask, device=dev).to(torch.bool)
-    d = x[used] - closest[used]
-    sq = (d * d).sum(dim=-1)
-    if squared:
-        return sq.mean()
-    # r = 0 has no direction: zero gradient there (sqrt'(0) is infinite), as in the kernel
-    pos = sq > 0
-    return (torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))) * pos).mean()
-
-
-def mesh_loss(clouds, poses=None, model=None, masks=None, **kwargs):
-    """Supervised loss against ground-truth meshes over lists of sequences of scans: the mean distance of the corrected, posed
-    points of a sequence to its mesh (``mesh_squared``: the mean squared distance; ``mesh_max_dist``: points farther away are left
-    out), averaged over the sequences like icp_loss.  ``masks[i]`` = (mesh.TriangleMesh, bool point mask [N_i] or None) of sequence
-    ``i``.  Differentiable to the model's weights and exponents and to the poses; GPU clouds with a kernel model (or none) and
-    poses take one dc_mesh_loss call per sequence (``fused=False`` forces the tensor form)."""
-    if not clouds or not clouds[0]:
-        raise ValueError('mesh_loss needs at least one sequence with one scan')
-    if not clouds[0][0].dirs.is_cuda:
-        raise RuntimeError('mesh_loss: the clouds must live on the GPU (depth_correction_amd has no CPU path)')
-    if masks is None or len(masks) != len(clouds):
-        raise ValueError('mesh_loss needs masks[i] = (mesh, point mask or None) for every sequence')
-    squared, max_dist = bool(kwargs.get('mesh_squared', False)), kwargs.get('mesh_max_dist')
-    kind = getattr(model, 'kernel_kind', None) if model is not None else None
-    fused = kwargs.get('fused', True) and poses is not None and (model is None or kind)
-    loss, loss_cloud = 0., []
-    for i, seq in enumerate(clouds):
-        mesh, point_mask = masks[i] if isinstance(masks[i], (tuple, list)) else (masks[i], None)
-        if mesh is None or not hasattr(mesh, 'on_device'):
-            raise ValueError('mesh_loss: sequence %d has no ground-truth mesh (masks[%d] = (mesh, point mask))' % (i, i))
-        if fused:
-            w, e = model.kernel_params() if kind else (None, None)
-            plan = _mesh_sequence_plan(seq, mesh, point_mask, bool(kind))
-            seq_poses = poses[i] if isinstance(poses[i], torch.Tensor) else torch.stack(list(poses[i]))
-            loss_seq = _MeshLossSequence.apply(w, e, seq_poses, plan, kind, squared, max_dist)
-        else:
-            loss_seq = _unfused_mesh_sequence(seq, None if poses is None else poses[i], model, mesh, point_mask, squared, max_dist)
-        loss = loss + loss_seq
-        loss_cloud.append(_MovedClouds(seq, None if poses is None else poses[i], model, loss))
-    return loss / len(clouds), loss_cloud
-
-
-# ---- supervised loss against a surveyed point cloud ----------------------------------------------------------------
-class _CloudLossSequence(torch.autograd.Function):
-    """cloud_loss of one sequence through dc_cloud_loss: forward and backward come out of the same host call."""
-
-    @staticmethod
-    def forward(ctx, w, exponent, poses, plan, kind, opts):
-        P12 = poses.detach().to(torch.float64)[:, :3, :].reshape(-1, 12).contiguous()
-        wv = None if w is None else w.detach().reshape(-1).to(torch.float64).contiguous()
-        ev = None if exponent is None else exponent.detach().reshape(-1).to(torch.float64).contiguous()
-        want_e = isinstance(exponent, torch.Tensor) and bool(ctx.needs_input_grad[1])
-        out = plan.eval(P12, kind, wv, ev, want_exponent=want_e, **dict(opts))
-        ctx.save_for_backward(out)
-        ctx.meta = (None if w is None else (w.shape, w.dtype), poses.dtype, poses.shape[0],
-                    exponent.shape if isinstance(exponent, torch.Tensor) else None)
-        return out[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        out, = ctx.saved_tensors
-        wmeta, pdt, ns, eshape = ctx.meta
-        nt = (out.numel() - 6 - 12 * ns) // 2
-        gw = ge = gT = None
-        if wmeta is not None and ctx.needs_input_grad[0]:
-            gw = (g * out[6:6 + nt]).reshape(wmeta[0]).to(wmeta[1])
-        if eshape is not None and ctx.needs_input_grad[1]:
-            ge = (g * out[6 + nt:6 + 2 * nt]).reshape(eshape)
-        if ctx.needs_input_grad[2]:
-            gT = torch.zeros((ns, 4, 4), dtype=torch.float64, device=out.device)
-            gT[:, :3, :] = (g * out[6 + 2 * nt:]).reshape(ns, 3, 4)
-            gT = gT.to(pdt)
-        return gw, ge, gT, None, None, None
-
-
-class _CloudLossPlan(_MeshLossPlan):
-    """What is constant over the optimisation of one sequence against its survey: the scans' fields concatenated scan-major, the
-    scan offsets, the survey's device copies with their grid (built once, its query buffer sized here), the loss mask, the
-    workspace."""
+class _CloudLossPlan(_ScanLossPlan):
+    """The survey's device copies with their grid (built once, its query buffer sized here)."""
+    header, _workspace = 6, staticmethod(ops.cloud_loss_workspace)
 
     def __init__(self, seq_clouds, survey, point_mask, with_model):
-        self._fields(seq_clouds, point_mask, with_model)
+        super().__init__(seq_clouds, point_mask, with_model)
         self.survey = survey
         self.survey_dev = survey.on_device(self.device).reserve(self.n)
 
-    def eval(self, poses12, kind=None, w=None, e=None, plane=True, squared=False, max_dist=None, inlier_ratio=1.0, want_exponent=False,
-             want_points=False):
-        nt = 0 if not kind else w.numel()
-        ws = self._ws.get(nt)
-        if ws is None:
-            ws = self._ws[nt] = ops.cloud_loss_workspace(self.n, self.n_scans, nt, self.device)
-        return ops.cloud_loss(self.survey_dev, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, plane=plane, squared=squared,
-                              max_dist=max_dist, inlier_ratio=inlier_ratio, want_points=want_points, want_exponent=want_exponent, ws=ws)
+    def _call(self, poses12, kind, w, e, **opts):
+        return ops.cloud_loss(self.survey_dev, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, **opts)
 
 
+_mesh_plans = PlanRegistry()
 _cloud_plans = PlanRegistry()
 
 
-def _cloud_sequence_plan(seq_clouds, survey, point_mask, with_model):
-    fields = [t for c in seq_clouds for t in (c.vps, c.dirs, c.depth, c.inc_angles, c.mask)] + [point_mask, survey]
-    return _cloud_plans.get(fields, (bool(with_model),), lambda: _CloudLossPlan(seq_clouds, survey, point_mask, with_model))
+def _scan_loss_plan(registry, plan_type, seq_clouds, target, point_mask, with_model):
+    fields = [t for c in seq_clouds for t in (c.vps, c.dirs, c.depth, c.inc_angles, c.mask)] + [point_mask, target]
+    return registry.get(fields, (bool(with_model),), lambda: plan_type(seq_clouds, target, point_mask, with_model))
 
 
 def _posed_points64(seq_clouds, seq_poses, model, keep=None):
@@ -568,6 +470,25 @@ def _posed_points64(seq_clouds, seq_poses, model, keep=None):
             c64 = c64.transform(seq_poses[i].double())
         parts.append(c64.vps + c64.depth * c64.dirs)
     return torch.cat(parts)
+
+
+def _unfused_mesh_sequence(seq_clouds, seq_poses, model, mesh, point_mask, squared, max_dist):
+    """The same loss from tensor operations: x in fp64 through the model and the poses, the closest points (detached) from
+    ops.mesh_closest, l = |x - c|, torch autograd.  For models without a kernel kind, and what the fused form is tested against."""
+    dev = seq_clouds[0].dirs.device
+    x = _posed_points64(seq_clouds, seq_poses, model)
+    bvh = mesh.on_device(dev)[3]
+    face, _, closest = ops.mesh_closest(bvh, x.detach().contiguous(), max_dist=max_dist)
+    used = face >= 0
+    if point_mask is not None:
+        used = used & torch.as_tensor(point_mask, device=dev).to(torch.bool)
+    d = x[used] - closest[used]
+    sq = (d * d).sum(dim=-1)
+    if squared:
+        return sq.mean()
+    # r = 0 has no direction: zero gradient there (sqrt'(0) is infinite), as in the kernel
+    pos = sq > 0
+    return (torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))) * pos).mean()
 
 
 def _unfused_cloud_sequence(seq_clouds, seq_poses, model, survey, point_mask, plane, squared, max_dist, inlier_ratio):
@@ -600,6 +521,55 @@ def _unfused_cloud_sequence(seq_clouds, seq_poses, model, survey, point_mask, pl
     return (torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))) * pos).mean()
 
 
+def _scan_loss(name, target, registry, plan_type, unfused, options, clouds, poses, model, masks, kwargs):
+    """The driver of mesh_loss and cloud_loss.  ``target`` = (its name in masks[i], what it is, the attributes it must have);
+    ``options(kwargs)`` -> the options of the plan's ops call and of ``unfused``, read once the operands have been checked."""
+    short, long, attrs = target
+    if not clouds or not clouds[0]:
+        raise ValueError('%s needs at least one sequence with one scan' % name)
+    if not clouds[0][0].dirs.is_cuda:
+        raise RuntimeError('%s: the clouds must live on the GPU (depth_correction_amd has no CPU path)' % name)
+    if masks is None or len(masks) != len(clouds):
+        raise ValueError('%s needs masks[i] = (%s, point mask or None) for every sequence' % (name, short))
+    opts = options(kwargs)
+    kind = getattr(model, 'kernel_kind', None) if model is not None else None
+    fused = kwargs.get('fused', True) and poses is not None and (model is None or kind)
+    loss, loss_cloud = 0., []
+    for i, seq in enumerate(clouds):
+        tgt, point_mask = masks[i] if isinstance(masks[i], (tuple, list)) else (masks[i], None)
+        if tgt is None or not all(hasattr(tgt, a) for a in attrs):
+            raise ValueError('%s: sequence %d has no %s (masks[%d] = (%s, point mask))' % (name, i, long, i, short))
+        if fused:
+            w, e = model.kernel_params() if kind else (None, None)
+            plan = _scan_loss_plan(registry, plan_type, seq, tgt, point_mask, bool(kind))
+            seq_poses = poses[i] if isinstance(poses[i], torch.Tensor) else torch.stack(list(poses[i]))
+            loss_seq = _ScanLossSequence.apply(w, e, seq_poses, plan, kind, tuple(sorted(opts.items())))
+        else:
+            loss_seq = unfused(seq, None if poses is None else poses[i], model, tgt, point_mask, **opts)
+        loss = loss + loss_seq
+        loss_cloud.append(_MovedClouds(seq, None if poses is None else poses[i], model, loss))
+    return loss / len(clouds), loss_cloud
+
+
+def mesh_loss(clouds, poses=None, model=None, masks=None, **kwargs):
+    """Supervised loss against ground-truth meshes over lists of sequences of scans: the mean distance of the corrected, posed
+    points of a sequence to its mesh (``mesh_squared``: the mean squared distance; ``mesh_max_dist``: points farther away are left
+    out), averaged over the sequences like icp_loss.  ``masks[i]`` = (mesh.TriangleMesh, bool point mask [N_i] or None) of sequence
+    ``i``.  Differentiable to the model's weights and exponents and to the poses; GPU clouds with a kernel model (or none) and
+    poses take one dc_mesh_loss call per sequence (``fused=False`` forces the tensor form)."""
+    options = lambda kw: dict(squared=bool(kw.get('mesh_squared', False)), max_dist=kw.get('mesh_max_dist'))
+    return _scan_loss('mesh_loss', ('mesh', 'ground-truth mesh', ('on_device',)), _mesh_plans, _MeshLossPlan, _unfused_mesh_sequence,
+                      options, clouds, poses, model, masks, kwargs)
+
+
+def _cloud_options(kwargs):
+    max_dist = kwargs.get('cloud_max_dist')
+    if max_dist is None:
+        raise ValueError("cloud_loss needs loss_kwargs['cloud_max_dist'] (metres, finite, > 0)")
+    return dict(plane=bool(kwargs.get('cloud_point_to_plane', True)), squared=bool(kwargs.get('cloud_squared', False)),
+                max_dist=float(max_dist), inlier_ratio=float(kwargs.get('cloud_inlier_ratio', 1.0)))
+
+
 def cloud_loss(clouds, poses=None, model=None, masks=None, **kwargs):
     """Supervised loss against surveyed clouds over lists of sequences of scans: the mean distance of the corrected, posed points of
     a sequence to their nearest survey points -- to the planes through them (``cloud_point_to_plane``, default True) or to the points
@@ -609,34 +579,8 @@ def cloud_loss(clouds, poses=None, model=None, masks=None, **kwargs):
     ``masks[i]`` = (survey.SurveyCloud, bool point mask [N_i] or None) of sequence ``i``.  Differentiable to the model's weights and
     exponents and to the poses, the correspondences held constant; GPU clouds with a kernel model (or none) and poses take one
     dc_cloud_loss call per sequence (``fused=False`` forces the tensor form)."""
-    if not clouds or not clouds[0]:
-        raise ValueError('cloud_loss needs at least one sequence with one scan')
-    if not clouds[0][0].dirs.is_cuda:
-        raise RuntimeError('cloud_loss: the clouds must live on the GPU (depth_correction_amd has no CPU path)')
-    if masks is None or len(masks) != len(clouds):
-        raise ValueError('cloud_loss needs masks[i] = (survey, point mask or None) for every sequence')
-    max_dist = kwargs.get('cloud_max_dist')
-    if max_dist is None:
-        raise ValueError("cloud_loss needs loss_kwargs['cloud_max_dist'] (metres, finite, > 0)")
-    opts = dict(plane=bool(kwargs.get('cloud_point_to_plane', True)), squared=bool(kwargs.get('cloud_squared', False)),
-                max_dist=float(max_dist), inlier_ratio=float(kwargs.get('cloud_inlier_ratio', 1.0)))
-    kind = getattr(model, 'kernel_kind', None) if model is not None else None
-    fused = kwargs.get('fused', True) and poses is not None and (model is None or kind)
-    loss, loss_cloud = 0., []
-    for i, seq in enumerate(clouds):
-        survey, point_mask = masks[i] if isinstance(masks[i], (tuple, list)) else (masks[i], None)
-        if survey is None or not hasattr(survey, 'on_device') or not hasattr(survey, 'normals'):
-            raise ValueError('cloud_loss: sequence %d has no surveyed cloud (masks[%d] = (survey, point mask))' % (i, i))
-        if fused:
-            w, e = model.kernel_params() if kind else (None, None)
-            plan = _cloud_sequence_plan(seq, survey, point_mask, bool(kind))
-            seq_poses = poses[i] if isinstance(poses[i], torch.Tensor) else torch.stack(list(poses[i]))
-            loss_seq = _CloudLossSequence.apply(w, e, seq_poses, plan, kind, tuple(sorted(opts.items())))
-        else:
-            loss_seq = _unfused_cloud_sequence(seq, None if poses is None else poses[i], model, survey, point_mask, **opts)
-        loss = loss + loss_seq
-        loss_cloud.append(_MovedClouds(seq, None if poses is None else poses[i], model, loss))
-    return loss / len(clouds), loss_cloud
+    return _scan_loss('cloud_loss', ('survey', 'surveyed cloud', ('on_device', 'normals')), _cloud_plans, _CloudLossPlan,
+                      _unfused_cloud_sequence, _cloud_options, clouds, poses, model, masks, kwargs)
 
 
 def loss_by_name(name):

@@ -30,6 +30,23 @@ def _ws(nbytes, device):
     return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
 
 
+def _out_arg(out, count, device):
+    """``out`` f64 [count]: the caller's, checked, or a new one."""
+    if out is None:
+        return torch.empty((count,), dtype=torch.float64, device=device)
+    return need(out, (count,), dtype=torch.float64, name='out', device=device)
+
+
+def _ws_arg(ws, nbytes, device):
+    """``ws`` uint8 of at least nbytes: the caller's, checked, or a new one."""
+    if ws is None:
+        return _ws(nbytes, device)
+    need(ws, (None,), dtype=torch.uint8, name='ws', device=device)
+    if ws.shape[0] < nbytes:
+        raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    return ws
+
+
 def as_index32(neighbors):
     """Reference neighbour tensors are int64 (nearest_neighbors.py:78); the kernels take int32."""
     if neighbors.dtype == torch.int32:
@@ -1042,10 +1059,7 @@ class IcpSequence:
             raise ValueError('sequence was built without incidence angles')
         need(poses12, (self.n_scans, 12), dtype=torch.float64, name='poses[S,12]', device=self.device)
         n_out = 1 + 2 * nt + 12 * self.n_scans
-        if out is None:
-            out = torch.empty((n_out,), dtype=torch.float64, device=self.device)
-        else:
-            need(out, (n_out,), dtype=torch.float64, name='out', device=self.device)
+        out = _out_arg(out, n_out, self.device)
         fn = lib().dc_p2plane_sequence if self.plane else lib().dc_p2point_sequence
         check(fn(ctypes.cast(self.scan_desc, ctypes.c_void_p), self.n_scans, ctypes.cast(self.pair_desc, ctypes.c_void_p),
                  self.n_pairs, 0 if self.dtype == torch.float32 else 1, ptr(poses12), kind, nt, ptr(w), ptr(e),
@@ -1484,9 +1498,7 @@ def bias_accumulate(depth, inc_est, mask, face, t_true, inc_true, model_kind, ex
     if not 1 <= p <= nv.DC_BIAS_MAX_TERMS or not 1 <= b <= nv.DC_BIAS_MAX_BINS:
         raise ValueError('bias_accumulate takes 1..%d terms and 1..%d bins, got %d and %d' % (nv.DC_BIAS_MAX_TERMS, nv.DC_BIAS_MAX_BINS, p, b))
     count = bias_out_count(b, p)
-    if out is None:
-        out = torch.empty((count,), dtype=torch.float64, device=dev)
-    need(out, (count,), dtype=torch.float64, name='out', device=dev)
+    out = _out_arg(out, count, dev)
     nbytes = lib().dc_bias_workspace_bytes(b, p)
     if ws is None:
         ws = _ws(nbytes, dev)
@@ -1549,6 +1561,16 @@ def _check_scan_ptr(ps, scan_ptr):
     return scan_ptr.shape[0] - 1
 
 
+def _scan_loss_args(ps, scan_ptr, poses12, model_kind, w, e, mask, dev):
+    """The operand checks mesh_loss and cloud_loss share -> (kind, n_terms, w, e, n_scans)."""
+    kind, nt, w, e = _model_args(model_kind, w, e, ps)
+    ns = _check_scan_ptr(ps, scan_ptr)
+    need(poses12, (ns, 12), dtype=torch.float64, name='poses[S,12]', device=dev)
+    if mask is not None:
+        need(mask, (ps.n,), dtype=torch.bool, name='mask', device=dev)
+    return kind, nt, w, e, ns
+
+
 @on_device
 def mesh_loss(bvh, ps, scan_ptr, poses12, model_kind=None, w=None, e=None, mask=None, squared=False, max_dist=None, leaf_hint=None,
               want_points=False, want_exponent=False, out=None, ws=None):
@@ -1563,28 +1585,15 @@ def mesh_loss(bvh, ps, scan_ptr, poses12, model_kind=None, w=None, e=None, mask=
     dev = bvh.leaf_face.device
     if ps.device != dev:
         raise RuntimeError('points are on %s, the mesh on %s' % (ps.device, dev))
-    kind, nt, w, e = _model_args(model_kind, w, e, ps)
-    ns = _check_scan_ptr(ps, scan_ptr)
-    need(poses12, (ns, 12), dtype=torch.float64, name='poses[S,12]', device=dev)
-    if mask is not None:
-        need(mask, (ps.n,), dtype=torch.bool, name='mask', device=dev)
+    kind, nt, w, e, ns = _scan_loss_args(ps, scan_ptr, poses12, model_kind, w, e, mask, dev)
     if leaf_hint is not None:
         need(leaf_hint, (ps.n,), dtype=torch.int32, name='leaf_hint', device=dev)
     md = 0.0 if max_dist is None else float(max_dist)
     if md != md:
         raise ValueError('max_dist must not be NaN')
     n_out = 4 + 2 * nt + 12 * ns
-    if out is None:
-        out = torch.empty((n_out,), dtype=torch.float64, device=dev)
-    else:
-        need(out, (n_out,), dtype=torch.float64, name='out', device=dev)
-    nbytes = lib().dc_mesh_loss_workspace_bytes(ps.n, ns, nt)
-    if ws is None:
-        ws = _ws(nbytes, dev)
-    else:
-        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
-        if ws.shape[0] < nbytes:
-            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    out = _out_arg(out, n_out, dev)
+    ws = _ws_arg(ws, lib().dc_mesh_loss_workspace_bytes(ps.n, ns, nt), dev)
     face = dist = closest = None
     if want_points:
         face = torch.empty((ps.n,), dtype=torch.int32, device=dev)
@@ -1698,11 +1707,7 @@ def cloud_loss(survey_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=Non
     dev = survey_dev.device
     if ps.device != dev:
         raise RuntimeError('points are on %s, the survey on %s' % (ps.device, dev))
-    kind, nt, w, e = _model_args(model_kind, w, e, ps)
-    ns = _check_scan_ptr(ps, scan_ptr)
-    need(poses12, (ns, 12), dtype=torch.float64, name='poses[S,12]', device=dev)
-    if mask is not None:
-        need(mask, (ps.n,), dtype=torch.bool, name='mask', device=dev)
+    kind, nt, w, e, ns = _scan_loss_args(ps, scan_ptr, poses12, model_kind, w, e, mask, dev)
     if max_dist is None:
         raise ValueError('cloud_loss needs max_dist (finite, > 0)')
     md, ratio = float(max_dist), float(inlier_ratio)
@@ -1715,17 +1720,8 @@ def cloud_loss(survey_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=Non
     survey_dev.reserve(ps.n)
     grid = survey_dev.grid
     n_out = 6 + 2 * nt + 12 * ns
-    if out is None:
-        out = torch.empty((n_out,), dtype=torch.float64, device=dev)
-    else:
-        need(out, (n_out,), dtype=torch.float64, name='out', device=dev)
-    nbytes = lib().dc_cloud_loss_workspace_bytes(ps.n, ns, nt)
-    if ws is None:
-        ws = _ws(nbytes, dev)
-    else:
-        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
-        if ws.shape[0] < nbytes:
-            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    out = _out_arg(out, n_out, dev)
+    ws = _ws_arg(ws, lib().dc_cloud_loss_workspace_bytes(ps.n, ns, nt), dev)
     idx = dist = resid = None
     if want_points:
         idx = torch.empty((ps.n,), dtype=torch.int32, device=dev)
@@ -1852,13 +1848,7 @@ def survey_align(survey_dev, query, origins, prior=None, inlier_ratio=1.0, max_d
         history = torch.empty((n_iters, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, device=dev)
     else:
         need(history, (n_iters, nv.DC_ALIGN_HISTORY_COLS), dtype=torch.float64, name='history', device=dev)
-    nbytes = lib().dc_survey_align_workspace_bytes(n)
-    if ws is None:
-        ws = _ws(nbytes, dev)
-    else:
-        need(ws, (None,), dtype=torch.uint8, name='ws', device=dev)
-        if ws.shape[0] < nbytes:
-            raise ValueError('workspace of %d bytes, %d needed' % (ws.shape[0], nbytes))
+    ws = _ws_arg(ws, lib().dc_survey_align_workspace_bytes(n), dev)
     check(lib().dc_survey_align(ptr(grid.ws), grid.ws.numel(), grid.n_query_max, ptr(survey_dev.points), grid.n, ptr(query), n, ptr(prior),
                                 ratio, md, n_iters, float(min_rot), float(min_trans), min_pairs, ptr(origins), ptr(state), ptr(status),
                                 ptr(history), ptr(ws), ws.shape[0], stream_ptr()), 'dc_survey_align')

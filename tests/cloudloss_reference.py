@@ -57,9 +57,10 @@ def survey(seed=3):
     return np.concatenate([HAND_SURVEY, pts[keep]]), np.concatenate([up, nrm[keep]])
 
 
-def scene(dtype=np.float64, seed=11):
-    """(mesh, scans, poses, loss_mask): meshloss_reference.scene with the last scan re-posed and the hand-made points in place."""
-    mesh, scans, poses = M.scene(seed=seed, dtype=np.float64)
+def scene(dtype=np.float64, seed=11, sizes=SIZES):
+    """(mesh, scans, poses, loss_mask): meshloss_reference.scene with the last scan re-posed and the hand-made points in place (a last
+    scan of fewer points than there are hand-made ones is only re-posed)."""
+    mesh, scans, poses = M.scene(sizes=sizes, seed=seed, dtype=np.float64)
     last = len(scans) - 1
     c, T = scans[last], poses[last]
     world = (c['vps'] + c['depth'][:, None] * c['dirs']) @ T[:3, :3].T + T[:3, 3]        # where the scan's points lie
@@ -71,7 +72,7 @@ def scene(dtype=np.float64, seed=11):
     dirs = ray / depth[:, None]
     lmask = np.ones(len(depth), bool)
     k0 = len(depth) - len(HAND_ORDER)
-    for k, name in enumerate(HAND_ORDER):
+    for k, name in enumerate(HAND_ORDER if k0 >= 0 else ()):
         vps[k0 + k] = np.array(HAND_QUERY[name]) - T_LAST
         dirs[k0 + k] = [0.0, 0.0, 1.0]
         depth[k0 + k] = 0.0
@@ -80,7 +81,7 @@ def scene(dtype=np.float64, seed=11):
     poses = poses.copy()
     poses[last] = Tn
     scans = [{k: (v if k == 'lmask' else v.astype(dtype)) for k, v in s.items()} for s in scans]
-    loss_mask = np.ones(N_ALL, bool)
+    loss_mask = np.ones(sum(sizes), bool)
     loss_mask[MASKED] = False
     return mesh, scans, poses, loss_mask
 

@@ -40,10 +40,10 @@ def _t(a, dtype=None):
 class Scene(object):
     """The reference scene on the device in one cloud dtype: PointSet, scan_ptr, poses12, the loss mask, the survey and its grid."""
 
-    def __init__(self, dtype, lmask=None, seed=11):
+    def __init__(self, dtype, lmask=None, seed=11, sizes=C.SIZES):
         from depth_correction_amd import ops
         from depth_correction_amd.survey import SurveyCloud
-        self.mesh, self.scans, self.poses, self.loss_mask = C.scene(dtype=NP_DTYPES[dtype], seed=seed)
+        self.mesh, self.scans, self.poses, self.loss_mask = C.scene(dtype=NP_DTYPES[dtype], seed=seed, sizes=sizes)
         if lmask is not None:
             off = 0
             for c in self.scans:
@@ -86,10 +86,10 @@ class Scene(object):
         return ops.points_fwd(ps64, self.poses12, kind, w, e)
 
 
-def _scene(dtype):
-    if dtype not in _cache:
-        _cache[dtype] = Scene(dtype)
-    return _cache[dtype]
+def _scene(dtype, sizes=C.SIZES):
+    if (dtype, sizes) not in _cache:
+        _cache[dtype, sizes] = Scene(dtype, sizes=sizes)
+    return _cache[dtype, sizes]
 
 
 def _split(out, nt, ns):
@@ -198,26 +198,30 @@ CASES = {
     'invcos_plane_trim': dict(kind='InvCos', inlier_ratio=0.8),
     'invcos_point_squared': dict(kind='InvCos', plane=False, squared=True),
     'local_mask_plane': dict(kind='ScaledPolynomial', local_mask=True),
+    # 513 points in scan 0: five blocks on the finishing kernel's four chains, so chain 0 adds two rows (float64 only)
+    'five_blocks': dict(kind='ScaledPolynomial', sizes=(513, 0, 1)),
 }
 
 
-@pytest.mark.parametrize('dtype', ['float32', 'float64'])
-@pytest.mark.parametrize('case', sorted(CASES))
+@pytest.mark.parametrize('case,dtype', [(c, d) for d in ('float32', 'float64') for c in sorted(CASES) if 'sizes' not in CASES[c]]
+                         + [('five_blocks', 'float64')])
 def test_loss_and_gradients(dtype, case):
     """out against the closed form: loss, the four counts, dL/dw, dL/de, dL/d[R|t] of every scan (the empty scan's is zero).  The
     closed form's correspondences are the brute force's, asserted equal to the device's first."""
     cfg = dict(CASES[case])
     rng = np.random.default_rng(5)
-    sc = Scene(dtype, lmask=rng.random(C.N_ALL) < 0.7) if cfg.pop('local_mask', False) else _scene(dtype)
+    sizes = cfg.pop('sizes', C.SIZES)
+    sc = Scene(dtype, lmask=rng.random(C.N_ALL) < 0.7) if cfg.pop('local_mask', False) else _scene(dtype, sizes)
     kind, w, e = sc.model(cfg.pop('kind'))
     plane, squared, want_e = cfg.get('plane', True), cfg.get('squared', False), cfg.get('want_exponent', False)
     out, idx, dist, resid = sc.run(kind, w, e, want_points=True, **cfg)
     ref = sc.reference(kind, plane=plane, squared=squared, ratio=cfg.get('inlier_ratio', 1.0))
+    assert ref['mask'][:sizes[0]].any() and ref['mask'][-sizes[-1]:].any()       # the first and the last scan have used points
     assert np.array_equal(idx.cpu().numpy(), ref['idx'])
     nt = 0 if kind is None else len(W_MODEL[kind][0])
     got = _split(out, nt, len(sc.sizes))
     _check_gradients(got, ref, plane, squared, '%s %s' % (dtype, case), want_e)
-    assert not got['gT'][2].any()                                      # the empty scan
+    assert not got['gT'][sizes.index(0)].any()                         # the empty scan
     if case == 'local_mask_plane':                                     # uncorrected points: no weight gradient of theirs
         lm = np.concatenate([c['lmask'] for c in sc.scans])
         assert not ref['terms']['gw'][~lm].any() and ref['terms']['gw'][lm].any()

@@ -37,9 +37,9 @@ def _t(a, dtype=None):
 class Scene(object):
     """The reference scene on the device in one cloud dtype: PointSet, scan_ptr, poses12, the mesh's tree."""
 
-    def __init__(self, dtype, lmask=None, seed=11):
+    def __init__(self, dtype, lmask=None, seed=11, sizes=M.SIZES):
         from depth_correction_amd import ops
-        self.mesh, self.scans, self.poses = M.scene(dtype=NP_DTYPES[dtype], seed=seed)
+        self.mesh, self.scans, self.poses = M.scene(sizes=sizes, dtype=NP_DTYPES[dtype], seed=seed)
         if lmask is not None:
             off = 0
             for c in self.scans:
@@ -64,10 +64,10 @@ class Scene(object):
         return out
 
 
-def _scene(dtype):
-    if dtype not in _cache:
-        _cache[dtype] = Scene(dtype)
-    return _cache[dtype]
+def _scene(dtype, sizes=M.SIZES):
+    if (dtype, sizes) not in _cache:
+        _cache[dtype, sizes] = Scene(dtype, sizes=sizes)
+    return _cache[dtype, sizes]
 
 
 def _split(out, nt, ns):
@@ -134,18 +134,21 @@ CASES = {
     'exponent_grad_squared': dict(kind='Polynomial', want_exponent=True, squared=True),
     'local_mask': dict(kind='ScaledPolynomial', local_mask=True),
     'loss_mask': dict(kind='ScaledPolynomial', loss_mask=True),
+    # 1025 points in scan 0: nine blocks on the finishing kernel's eight chains, so chain 0 adds two rows (float64 only)
+    'nine_blocks': dict(kind='ScaledPolynomial', sizes=(1025, 0, 1)),
 }
 
 
-@pytest.mark.parametrize('dtype', ['float32', 'float64'])
-@pytest.mark.parametrize('case', sorted(CASES))
+@pytest.mark.parametrize('case,dtype', [(c, d) for d in ('float32', 'float64') for c in sorted(CASES) if 'sizes' not in CASES[c]]
+                         + [('nine_blocks', 'float64')])
 def test_loss_and_gradients(dtype, case):
     """out against the closed form at the device's own faces: loss, the three counts, dL/dw, dL/de, dL/d[R|t] of every scan (the
     empty scan's is zero)."""
     cfg = dict(CASES[case])
     rng = np.random.default_rng(5)
-    n = sum(M.SIZES)
-    sc = Scene(dtype, lmask=rng.random(n) < 0.7) if cfg.pop('local_mask', False) else _scene(dtype)
+    sizes = cfg.pop('sizes', M.SIZES)
+    n = sum(sizes)
+    sc = Scene(dtype, lmask=rng.random(n) < 0.7) if cfg.pop('local_mask', False) else _scene(dtype, sizes)
     loss_mask = rng.random(n) < 0.6 if cfg.pop('loss_mask', False) else None
     kind, w, e = sc.model(cfg.pop('kind'))
     squared, want_e = cfg.get('squared', False), cfg.get('want_exponent', False)
@@ -154,13 +157,14 @@ def test_loss_and_gradients(dtype, case):
     # the per-point outputs hold first (test 1's bars), then the closed form at these faces
     bf = M.mesh_loss(sc.mesh, sc.scans, sc.poses, kind, wv, ev, loss_mask=loss_mask, squared=squared)
     used = bf['mask']
+    assert used[:sizes[0]].any() and used[-sizes[-1]:].any()           # the first and the last scan have used points
     assert np.abs(dist.cpu().numpy()[used] - bf['r'][used]).max() <= M.BAR
     assert (face.cpu().numpy()[~used] == -1).all()
     ref = M.mesh_loss(sc.mesh, sc.scans, sc.poses, kind, wv, ev, face=face.cpu().numpy(), loss_mask=loss_mask, squared=squared)
     nt = 0 if kind is None else len(wv)
     got = _split(out, nt, len(sc.sizes))
     _check_gradients(got, ref, squared, '%s %s' % (dtype, case), want_e)
-    assert not got['gT'][2].any()                                      # the empty scan
+    assert not got['gT'][sizes.index(0)].any()                         # the empty scan
     if case == 'local_mask':                                           # uncorrected points: no weight gradient of theirs
         lm = np.concatenate([c['lmask'] for c in sc.scans])
         assert not ref['terms']['gw'][~lm].any() and ref['terms']['gw'][lm].any()

@@ -256,7 +256,7 @@ def test_icp_finish_block_sum_order_is_bit_exact(host, n_blocks):
     """The documented order of the block sum (lane l of eight: blocks l, l + 8, ...; then the eight sums in order) emulated in numpy
     fp64: pairs / SSE / overlap and the pose after a step with JtJ = 2^4 I are bit-equal.  An IEEE statement, not a tolerance: the
     step rotates about z by an angle below 1e-9 from the identity, where every product of the update is exact.  The host build
-    shares the per-lane loop (icp_lane_sum) with the finish kernel but adds the eight lane sums in a loop of its own: the kernel's
+    shares the per-lane loop (rows_lane_sum of dc_rowsum.h) with the finish kernel but adds the eight lane sums in a loop of its own: the kernel's
     second stage is pinned by the same case on the device (tests/test_gpu_slam_parity.py)."""
     import slam_reference as R
     partials, want_state = _block_sum_case(n_blocks)
