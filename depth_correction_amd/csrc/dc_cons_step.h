@@ -149,14 +149,17 @@ constexpr int kStepVar = kVarF32Sweep | kVarSlimTail | kVarDppSums;     // what 
 
 // Covariance, smallest eigenpair, loss and the coefficients c1, c2 of a centre from its moments about the centre point.
 // The covariance is only ever needed divided by its trace (eig3_smallest_unit), so the Bessel / unit factor f = unit^2 / D
-// multiplies the trace alone; `full` (wave-uniform): every lane of the wavefront has all NS neighbours, W and D are constants.
+// multiplies the trace alone; `full` (wave-uniform): every lane of the wavefront has all `ns` neighbours, W and D are constants (ns: the
+// slot count, NS unless the kernel learns it at run time; 1 / ns and 1 / (ns - 1) are correctly rounded divisions either way, so a
+// run-time count gives the bits of the compile-time one).
 template <typename PT, int NS>
 __device__ __forceinline__ void step_point2(const CovAcc& acc, int n_have, bool full, bool m, const LossParams& lp, const QParams& qp,
-                                            double* acc2, double* cm, double* v0, double* c1, double* c2, double* sum_e2 = nullptr) {
+                                            double* acc2, double* cm, double* v0, double* c1, double* c2, double* sum_e2 = nullptr,
+                                            int ns = NS) {
   const double u = Pt<PT>::unit(qp);
   double invW, D, invD;
   if (full) {
-    invW = 1.0 / NS; D = NS - 1.0; invD = 1.0 / (NS - 1.0);
+    invW = 1.0 / ns; D = ns - 1.0; invD = 1.0 / (ns - 1.0);
   } else {
     const double W = (double)n_have;
     invW = recip1_(W);                                  // W = 0: inf * 0 -> NaN mean, like the reference's 0 / 0
@@ -303,8 +306,22 @@ constexpr int kDppRor4 = 0x124;     // row_ror:4
 constexpr int kDppRor8 = 0x128;     // row_ror:8
 constexpr int kDppShl4 = 0x104;     // row_shl:4 (lane l reads lane l + 4 of its row)
 constexpr int kDppQuad3 = 0xFF;     // quad_perm:[3,3,3,3]
+// Lane l < W of every 2 W lanes: the value of lane l + W (W = 16: the next row, W = 32: the other half), through gfx950's row / half
+// swaps -- VALU moves, where a shuffle is an LDS round trip.  (The other lanes get nothing they can use.)
+template <int W>
+__device__ __forceinline__ double upper_lanes_f64(double v) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  // {vdst, vsrc} after the swap of vdst's odd rows (upper half) with vsrc's even rows (lower half): vsrc's lower lanes hold vdst's upper
+  if constexpr (W == 16)
+    return __hiloint2double((int)__builtin_amdgcn_permlane16_swap(hi, hi, false, false)[1], (int)__builtin_amdgcn_permlane16_swap(lo, lo, false, false)[1]);
+  else
+    return __hiloint2double((int)__builtin_amdgcn_permlane32_swap(hi, hi, false, false)[1], (int)__builtin_amdgcn_permlane32_swap(lo, lo, false, false)[1]);
+}
 // Four values per lane -> lane l < 4 of the wavefront holds the total of value bitrev2(l) (as wave_sum_packed<4>): two quad
-// steps that also halve what a lane carries, two rotations inside the rows, two cross-row exchanges.
+// steps that also halve what a lane carries, two rotations inside the rows, two cross-row exchanges.  SWAP: the cross-row exchanges as
+// swaps, which serve lanes < 16 only (the same additions in the same order there: step_block_row, whose wavefront 0 alone stands
+// between the block and its end).
+template <bool SWAP = false>
 __device__ __forceinline__ double wave_sum4_dpp(double* v) {
   const int lane = threadIdx.x & (kWave - 1);
   const bool up1 = (lane & 1) != 0, up2 = (lane & 2) != 0;
@@ -318,8 +335,13 @@ __device__ __forceinline__ double wave_sum4_dpp(double* v) {
   double r = kk + dpp_f64<kDppXor2>(gg);
   r += dpp_f64<kDppRor4>(r);
   r += dpp_f64<kDppRor8>(r);
-  r += __shfl_xor(r, 16, kWave);
-  r += __shfl_xor(r, 32, kWave);
+  if constexpr (SWAP) {
+    r += upper_lanes_f64<16>(r);
+    r += upper_lanes_f64<32>(r);
+  } else {
+    r += __shfl_xor(r, 16, kWave);
+    r += __shfl_xor(r, 32, kWave);
+  }
   return r;
 }
 
@@ -347,7 +369,8 @@ __device__ __forceinline__ double wave_sum8_regs(const double* v) {
 }
 
 // {sum loss, count} -> p_fwd columns, dL/dw -> p_bwd columns (same row stride: one row per wavefront), through one packed
-// wavefront reduction of the 2 + P values
+// wavefront reduction of the 2 + P values: the ordinary (unchained) form of the step kernels.  (per_block: the pose kernel's one row
+// per block; the chained step kernels have step_block_row below.)
 template <int P, bool DPP = false>
 __device__ __forceinline__ void step_partials(const double* acc2, const double* gw, double* __restrict__ p_fwd, double* __restrict__ p_bwd,
                                               bool per_block = false, int n_front = 0) {
@@ -375,6 +398,83 @@ __device__ __forceinline__ void step_partials(const double* acc2, const double* 
     const int q = packed_value_of_lane<NP2>(lane);
     if (q < 2) p_fwd[q * rs + row] = tot;
     else if (q < NV) p_bwd[(q - 2) * rs + row] = tot;
+  }
+}
+
+// ---- a chained launch's row of partials {sum loss, count, dL/dw_0..P-1}: ONE row per block, summed ONCE -----------------------
+// Every one-pass step kernel ends its chained form here, so that the same lane values give the same row whichever kernel formed
+// them (the tests compare the kernels' chained sums byte for byte).  The order of the additions is fixed:
+//  (a) every lane holds its fp64 values: the loss and dL/dw_k, already converted and scaled (1 + P values; an idle lane's are +0.0);
+//  (b) wavefronts 1..3 hand their lanes' values to wavefront 0 through LDS -- `hand`, laid out [value][wavefront - 1][lane] -- and
+//      lane l of wavefront 0 forms (v0 + v1) + (v2 + v3) per value, v_w being lane l's value in wavefront w;
+//  (c) wavefront 0 runs the packed wavefront reduction once over {loss, 0, dL/dw..}: wave_sum4_dpp for 2 + P <= 4 (its cross-row
+//      exchanges as swaps: the same additions), wave_sum8_regs for three weights (DPP = false, the A-B baseline: wave_sum_packed, the
+//      same selects, exchanges and additions through shuffles);
+//  (d) the count is the number of lanes that count, wavefront by wavefront (popcount of the ballot), added as (c0 + c1) + (c2 + c3):
+//      small integers, so the same double as the sum of the lanes' 0 / 1 in any order; it takes the place of column 1's total;
+//  (e) lanes < NP2 of wavefront 0 store the row: row blockIdx.x - n_front of gridDim.x - n_front, columns {loss, count} at p_fwd and
+//      dL/dw at p_bwd.
+// `bad` (a slot count the kernel is not built for, a wait for the weights that ran out) poisons loss and count with NaN; `nothing` (a
+// padding block, a block none of whose centres is inside the mask) stores +0.0 in every column -- what the sums of its zeros were --
+// without a barrier.  Both are the same for the whole block, and every thread of the block makes the call.
+// `hand` is the block's tile: it is dead once every wavefront has left its second sweep, which the first barrier below waits for (no LDS
+// of its own: the q32 kernel's seven or six tiles per CU stay what they were).  The launch gives the tile at least step_hand_bytes<P>().
+// The row's address is the same for the whole block but for the lane's column: the bases stay in scalar registers and a lane adds a
+// 32-bit byte offset ((2 + P) * 8 * rows < 2^32: a hundred million blocks).
+template <int P> constexpr size_t step_hand_bytes() { return (size_t)((kWavesPerBlock - 1) * kWave * (1 + P) + kWavesPerBlock) * sizeof(double); }
+template <int P, bool DPP = true>
+__device__ __forceinline__ void step_block_row(double loss, bool cnt_lane, const double* gw, bool bad, bool nothing, double* hand,
+                                               double* __restrict__ p_fwd, double* __restrict__ p_bwd, int n_front) {
+  constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8, NL = 1 + P, kOthers = kWavesPerBlock - 1;
+  static_assert(kWavesPerBlock == 4, "(v0 + v1) + (v2 + v3)");
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+  const uint32_t rs = gridDim.x - (uint32_t)n_front, row = blockIdx.x - (uint32_t)n_front;
+  const int q = packed_value_of_lane<NP2>((int)(lane & (NP2 - 1)));
+  char* const fwd = reinterpret_cast<char*>(p_fwd);
+  char* const bwd = reinterpret_cast<char*>(p_bwd);
+  const uint32_t off_f = ((uint32_t)q * rs + row) * 8u, off_b = ((uint32_t)(q - 2) * rs + row) * 8u;
+  if (nothing && !bad) {
+    if (wave == 0 && lane < NP2) {
+      if (q < 2) *reinterpret_cast<double*>(fwd + off_f) = 0.0;
+      else if (q < NV) *reinterpret_cast<double*>(bwd + off_b) = 0.0;
+    }
+    return;
+  }
+  const double nan_ = __longlong_as_double(0x7ff8000000000000ll);
+  double cnt = bad ? nan_ : (double)(int)__popcll(__ballot((int)cnt_lane));
+  double v[NP2];
+  v[0] = bad ? nan_ : loss; v[1] = 0.0;
+#pragma unroll
+  for (int k = 0; k < NP2 - 2; ++k) v[2 + k] = k < P ? gw[k] : 0.0;
+  __syncthreads();                                      // every wavefront has read the last of its staged rows
+  if (wave != 0) {
+    double* h = hand + (wave - 1) * kWave + lane;
+    h[0] = v[0];
+#pragma unroll
+    for (int k = 0; k < P; ++k) h[(1 + k) * kOthers * kWave] = v[2 + k];
+    if (lane == 0) hand[NL * kOthers * kWave + wave] = cnt;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  {
+    const double* h = hand + lane;
+    v[0] = (v[0] + h[0]) + (h[kWave] + h[2 * kWave]);
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      const double* hk = h + (1 + k) * kOthers * kWave;
+      v[2 + k] = (v[2 + k] + hk[0]) + (hk[kWave] + hk[2 * kWave]);
+    }
+    const double* hc = hand + NL * kOthers * kWave;
+    cnt = (cnt + hc[1]) + (hc[2] + hc[3]);
+  }
+  double tot;
+  if constexpr (NP2 == 4) tot = DPP ? wave_sum4_dpp<true>(v) : wave_sum_packed<4>(v);
+  else tot = DPP ? wave_sum8_regs(v) : wave_sum_packed<8>(v);
+  if (q == 1) tot = cnt;
+  if (lane < NP2) {
+    if (q < 2) *reinterpret_cast<double*>(fwd + off_f) = tot;
+    else if (q < NV) *reinterpret_cast<double*>(bwd + off_b) = tot;
   }
 }
 
@@ -492,8 +592,12 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_kernel(
       }
     }
   }
+  if (chained) {                                         // one row per block (step_block_row)
+    step_block_row<P, (VAR & kVarDppSums) != 0>(acc2[0], acc2[1] != 0.0, gw, bad, blk < 0, reinterpret_cast<double*>(tile), p_fwd, p_bwd, ch.n_front);
+    return;
+  }
   if (bad) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, (VAR & kVarDppSums) != 0>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
+  step_partials<P, (VAR & kVarDppSums) != 0>(acc2, gw, p_fwd, p_bwd);
 }
 
 // ---- the one-pass kernel for q32 points and a fixed slot count: what a C2 step runs ----------------------------------------
@@ -622,7 +726,6 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
   __shared__ int4 tile[StepRow<q32, P>::kPieces * CAP];
   __shared__ double s_w[DC_MAX_MODEL_TERMS];
   __shared__ double s_front[kWavesPerBlock];
-  __shared__ double s_comb[kWavesPerBlock * NP2];
   __shared__ int s_ok[2];
   DC_TRACE_BEGIN();
   const bool chained = ch.ready != nullptr;
@@ -732,9 +835,16 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
       for (int k = 0; k < P; ++k) gw[k] = (double)gwf[k] * u;          // differences were in grid steps
     }
   }
+  if (chained) {
+    // one row per block, summed once (step_block_row); the tile is the hand-over
+    static_assert(sizeof(tile) >= step_hand_bytes<P>(), "the hand-over of step_block_row lives in the tile");
+    step_block_row<P>(loss, cnt_lane, gw, bad, skip, reinterpret_cast<double*>(tile), p_fwd, p_bwd, ch.n_front);
+    DC_TRACE_END();
+    return;
+  }
   const double nan_ = __longlong_as_double(0x7ff8000000000000ll);
   if (bad) loss = nan_;
-  // ---- {sum loss, count, dL/dw} of the wavefront (one row per wavefront; chained: per block), as step_partials; the count's
+  // ---- {sum loss, count, dL/dw} of the wavefront (one row per wavefront), as step_partials; the count's
   // column of the packed reduction carries zeros and its lane takes the number of counting lanes instead (NaN when `bad`,
   // as the sum of the lanes' NaNs was)
   const double cnt = bad ? nan_ : (double)__popcll(__ballot((int)cnt_lane));
@@ -747,15 +857,7 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
   else tot = wave_sum8_regs(v);
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if (packed_value_of_lane<NP2>(lane & (NP2 - 1)) == 1) tot = cnt;
-  int64_t rs = (int64_t)gridDim.x * kWavesPerBlock, row = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (chained) {
-    if (lane < NP2) s_comb[wave * NP2 + lane] = tot;
-    __syncthreads();
-    if (wave != 0) return;
-    if (lane < NP2) tot = (s_comb[lane] + s_comb[NP2 + lane]) + (s_comb[2 * NP2 + lane] + s_comb[3 * NP2 + lane]);
-    rs = (int64_t)gridDim.x - ch.n_front;
-    row = (int64_t)blockIdx.x - ch.n_front;
-  }
+  const int64_t rs = (int64_t)gridDim.x * kWavesPerBlock, row = (int64_t)blockIdx.x * kWavesPerBlock + wave;
   if (lane < NP2) {
     const int q = packed_value_of_lane<NP2>(lane);
     if (q < 2) p_fwd[q * rs + row] = tot;
@@ -835,7 +937,10 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_slots_kernel(
     if (nslots > kPreSlots) n_have += gather_tail<PT>(tile, cap, ci, lrow, nslots, packed != 0, acc);
     acc.W = (double)n_have;
     double cm[3], v0[3], c1, c2;
-    step_point2<PT, 2>(acc, n_have, false, mask ? mask[i] != 0 : true, lp, qp, acc2, cm, v0, &c1, &c2);
+    // a wavefront all of whose lanes have every slot takes W and D as the fixed-K kernels' full wavefronts do (step_point2): on a
+    // table with a fixed slot count this kernel then returns their sums bit for bit
+    const bool full = nslots >= 2 && !__any((int)(n_have != nslots));
+    step_point2<PT, 2>(acc, n_have, full, mask ? mask[i] != 0 : true, lp, qp, acc2, cm, v0, &c1, &c2, nullptr, nslots);
     const double u = Pt<PT>::unit(qp);
     if constexpr (std::is_same<PT, q32>::value) {
       float cmf[3], vs[3], vu[3], gwf[P];
@@ -863,8 +968,11 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_slots_kernel(
       for (int k = 0; k < P; ++k) gw[k] *= u;
     }
   }
-  if (timed_out) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, true>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
+  if (chained) {                                         // one row per block (step_block_row)
+    step_block_row<P>(acc2[0], acc2[1] != 0.0, gw, timed_out, blk < 0, reinterpret_cast<double*>(tile), p_fwd, p_bwd, ch.n_front);
+    return;
+  }
+  step_partials<P, true>(acc2, gw, p_fwd, p_bwd);
 }
 
 // ---- the one-pass kernel for ball neighbourhoods on float32 clouds (round 4) ------------------------------------------------
@@ -1036,8 +1144,8 @@ __global__ __launch_bounds__(kBlock, (CAP <= 1024 ? 5 : 4)) void consistency_ste
 #pragma unroll
     for (int k = 0; k < P; ++k) gw[k] *= u;
   }
-  if (timed_out) acc2[0] = acc2[1] = __longlong_as_double(0x7ff8000000000000ll);
-  step_partials<P, true>(acc2, gw, p_fwd, p_bwd, chained, chained ? ch.n_front : 0);
+  if (chained) step_block_row<P>(acc2[0], acc2[1] != 0.0, gw, timed_out, blk < 0, reinterpret_cast<double*>(tile), p_fwd, p_bwd, ch.n_front);
+  else step_partials<P, true>(acc2, gw, p_fwd, p_bwd);
   DC_TRACE_END();
 }
 

@@ -1192,6 +1192,7 @@ static int ragged_launch(dim3 grid, hipStream_t stream, hipEvent_t ev0, hipEvent
                          const dcBlockTable* t, int64_t n_rows, const uint8_t* mask, const LossParams& lp, const QParams& qp, double* p_fwd,
                          double* p_bwd, const StepChain& ch) {
   constexpr size_t bytes = (size_t)StepRow<q32, P>::kPieces * CAP * 16;
+  static_assert(bytes >= step_hand_bytes<P>(), "the hand-over of step_block_row lives in the tile");
   // function attributes are per device: one bit per device of the process (a second GPU of the same process sets its own)
   static std::atomic<uint64_t> attr_set{0};
   if (bytes > 60 * 1024) {
@@ -1760,13 +1761,17 @@ static int launch_step_q32(const SeqRoute& r, const StepLaunch& a) {
 
 // any [rows, K] table (float64 clouds; float32 ones without headers, with longer lists or under dc_set_option(6, ..)): the tables themselves
 #define STEP_TAIL a.pb, a.tab, r.table->own_base, r.rows_fwd, a.d->centre_idx, r.n_rows, a.d->mask, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
+// the dynamic LDS of a launch: the tile, which in a chain also carries the hand-over of step_block_row (a tile of a few rows is smaller)
+static size_t step_lds(const SeqRoute& r, const StepLaunch& a, size_t hand_bytes) {
+  return a.ch.ready && r.lds_fwd < hand_bytes ? hand_bytes : r.lds_fwd;
+}
 static int launch_step_basis(const SeqRoute& r, const StepLaunch& a) {
   ProfScope prof(1);
   const dim3 block(kBlock);
-#define STEPB(P, NS, PT) DC_TIMED_LAUNCH((consistency_step_basis_kernel<PT, NS, P, kStepVar>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL)
+#define STEPB(P, NS, PT) DC_TIMED_LAUNCH((consistency_step_basis_kernel<PT, NS, P, kStepVar>), a.grid, block, step_lds(r, a, step_hand_bytes<P>()), a.stream, STEP_TAIL)
 #define STEPB_P(NS, PT) DC_SWITCH_P(r.P, STEPB(3, NS, PT), STEPB, NS, PT)
-  if (r.round2 && r.f64) DC_TIMED_LAUNCH((consistency_step_basis_kernel<double, 10, 2, 0>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL);
-  else if (r.round2) DC_TIMED_LAUNCH((consistency_step_basis_kernel<q32, 10, 2, 0>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL);
+  if (r.round2 && r.f64) DC_TIMED_LAUNCH((consistency_step_basis_kernel<double, 10, 2, 0>), a.grid, block, step_lds(r, a, step_hand_bytes<2>()), a.stream, STEP_TAIL);
+  else if (r.round2) DC_TIMED_LAUNCH((consistency_step_basis_kernel<q32, 10, 2, 0>), a.grid, block, step_lds(r, a, step_hand_bytes<2>()), a.stream, STEP_TAIL);
   else if (r.f64) DC_SWITCH_K(r.k, , STEPB_P, double);
   else DC_SWITCH_K(r.k, , STEPB_P, q32);
 #undef STEPB_P
@@ -1778,7 +1783,7 @@ static int launch_step_basis(const SeqRoute& r, const StepLaunch& a) {
 static int launch_step_slots(const SeqRoute& r, const StepLaunch& a) {
   ProfScope prof(1);
   const dim3 block(kBlock);
-#define STEPS(P, PT, X) DC_TIMED_LAUNCH((consistency_step_basis_slots_kernel<PT, P>), a.grid, block, r.lds_fwd, a.stream, STEP_TAIL, r.table->packed)
+#define STEPS(P, PT, X) DC_TIMED_LAUNCH((consistency_step_basis_slots_kernel<PT, P>), a.grid, block, step_lds(r, a, step_hand_bytes<P>()), a.stream, STEP_TAIL, r.table->packed)
   if (r.f64) DC_SWITCH_P(r.P, STEPS(3, double, 0), STEPS, double, 0);
   else DC_SWITCH_P(r.P, STEPS(3, q32, 0), STEPS, q32, 0);
 #undef STEPS
