@@ -5,6 +5,9 @@ dc_features_fwd (gather + mean + covariance + eigh + normals + incidence angles,
 backward = dc_features_bwd (hand-derived, over the transposed neighbour list).  Gradients flow from
 ``mean``, ``cov`` and ``eigvals`` to ``points`` -- the only paths the reference's losses use (SURVEY 3C);
 eigenvectors / normals / incidence angles are returned detached, as constants of the graph.
+The backward of ``mean`` is the one of the validity-weighted mean: with explicit ``mean_weights`` (which enter
+the mean only) a gradient through ``mean`` is refused, like any gradient with ``scale``; ``cov`` and ``eigvals``
+do not depend on the mean weights and stay differentiable.
 """
 from __future__ import annotations
 
@@ -48,7 +51,8 @@ class _Features(torch.autograd.Function):
                              mean_weights=None if mean_weights is None else mean_weights.detach().contiguous(),
                              scale=scale, want_saved=True, want_weights=True,
                              want=('mean', 'cov', 'eigvals', 'eigvecs') + (('normals', 'inc_angles') if dirs is not None else ()))
-        ctx.graph, ctx.scale = graph, scale
+        ctx.graph, ctx.scale, ctx.weighted_mean = graph, scale, mean_weights is not None
+        ctx.set_materialize_grads(False)         # an output the loss never touches arrives as None, not as zeros
         ctx.save_for_backward(x, f['cmean'], f['invd'], f['nvalid'], f['eigvecs'])
         k = graph.nbr.shape[1]
         outs = (f['mean'], f['cov'], f['eigvals'], f['eigvecs'], f['normals'], f['inc_angles'],
@@ -60,6 +64,9 @@ class _Features(torch.autograd.Function):
     def backward(ctx, g_mean, g_cov, g_eig, *unused):
         if ctx.scale:
             raise NotImplementedError('backward through distance-scaled neighbour weights (nn_scale) is not implemented')
+        if ctx.weighted_mean and g_mean is not None:
+            # dc_features_bwd spreads g_mean / W over a row's edges: the derivative of the validity-weighted mean only
+            raise NotImplementedError('backward through a mean taken with explicit neighbour weights is not implemented')
         x, cmean, invd, nvalid, eigvecs = ctx.saved_tensors
         cont = lambda t: None if t is None else t.contiguous()
         csr_ptr, csr_src = ctx.graph.csr
