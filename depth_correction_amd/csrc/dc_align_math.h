@@ -16,7 +16,7 @@ struct AlignParams {
 };
 
 constexpr int kAlignBlocksMax = 1024;   // most blocks (rows of partials) of dc_align_accumulate
-constexpr double kAlignRelEps = 1e-12;  // icp_solve6's rel_eps: the relative eigenvalue gap below which the fit is not unique
+constexpr double kAlignRelEps = 1e-12;  // icp_solve's rel_eps: the relative eigenvalue gap below which the fit is not unique
 constexpr int kAlignSweeps = 16;        // cyclic Jacobi sweeps at most (a 4 x 4 matrix converges in 4 - 6)
 
 // Horn's matrix N (row-major 4 x 4, symmetric) of C (row-major 3 x 3, C_ij = sum p_i y_j): q^T N q = trace(R(q)^T ... ) is largest

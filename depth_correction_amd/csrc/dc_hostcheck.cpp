@@ -23,6 +23,15 @@
 #include "dc_planereg_math.h"
 #include "dc_cons_route.h"
 
+// The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
+// summed in the kernel's order.
+template <int NV>
+static bool host_icp_totals(const double* partials, int n_blocks, const int32_t* status, double* tot) {
+  if (status[0] != 0) return false;
+  for (int q = 0; q < NV; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, NV, q);
+  return true;
+}
+
 extern "C" {
 
 // the kernel route of a sequence evaluation (dc_cons_route.h: what sequence_eval_impl runs before it launches anything); nothing behind
@@ -135,7 +144,12 @@ void dc_host_normal_inc(const double* dir, const double* v0, double* normal, dou
 }
 
 // ICP normal equations (dc_slam.hip's finish kernel): a21 = JtJ upper triangle row by row, b6 = Jtr -> x = -(JtJ)^-1 Jtr; 1 = singular
-int dc_host_icp_solve(const double* a21, const double* b6, double* x6) { return dc::icp_solve6(a21, b6, x6); }
+int dc_host_icp_solve(const double* a21, const double* b6, double* x6) {
+  double A[36], L[36], y[6];
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) A[r * 6 + c] = a21[dc::sym_index<6>(r, c)];
+  return dc::icp_solve<6>(A, b6, x6, L, y);
+}
 
 // out = [R(x[0:3]) x[3:6]; 0 1] T (row-major 4 x 4): the finish kernel's pose update
 void dc_host_icp_step(const double* x6, const double* T, double* out) { dc::icp_apply_step(x6, T, out); }
@@ -152,13 +166,10 @@ double dc_host_rows_sum(const double* rows, int64_t n_rows, int stride, int q, i
 // and status [4] are host arrays.  0, or 1 for arguments dc_icp_finish refuses.
 int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
                        double max_rot, double max_trans, int min_pairs, double* state, int32_t* status) {
-  if (!partials || !state || !status || n_blocks < 1 || n_blocks > dc::kIcpBlocksMax || m < 0) return 1;
-  if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1) return 1;
-  if (status[0] != 0) return 0;
+  if (!dc::icp_finish_args_ok(partials, n_blocks, m, smooth, max_iters, state, status)) return 1;
   double tot[DC_ICP_PARTIALS];
-  for (int q = 0; q < DC_ICP_PARTIALS; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, DC_ICP_PARTIALS, q);
   const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
-  dc::icp_finish_tail(tot, m, prm, state, status);
+  if (host_icp_totals<DC_ICP_PARTIALS>(partials, n_blocks, status, tot)) dc::icp_finish_tail(tot, m, prm, state, status);
   return 0;
 }
 
@@ -167,14 +178,12 @@ int dc_host_icp_finish(const double* partials, int n_blocks, int64_t m, double m
 int dc_host_icp_ct_finish(const double* partials, int n_blocks, int64_t m, double min_rot, double min_trans, int smooth, int max_iters,
                           double max_rot, double max_trans, int min_pairs, double beta_v, double beta_w, double max_twist_trans,
                           double max_twist_rot, double* state, double* ct_state, int32_t* status) {
-  if (!partials || !state || !ct_state || !status || n_blocks < 1 || n_blocks > dc::kIcpBlocksMax || m < 0) return 1;
-  if (smooth < 1 || smooth > DC_ICP_MAX_SMOOTH || max_iters < 1 || !(beta_v >= 0.0) || !(beta_w >= 0.0)) return 1;
-  if (status[0] != 0) return 0;
+  if (!dc::icp_finish_args_ok(partials, n_blocks, m, smooth, max_iters, state, status) || !ct_state || !(beta_v >= 0.0) || !(beta_w >= 0.0))
+    return 1;
   double tot[DC_ICP_CT_PARTIALS], work[dc::kIcpCtWork];
-  for (int q = 0; q < DC_ICP_CT_PARTIALS; ++q) tot[q] = dc::rows_sum<dc::kRowSumLanes>(partials, n_blocks, DC_ICP_CT_PARTIALS, q);
   const dc::IcpParams prm{min_rot, min_trans, max_rot, max_trans, smooth, max_iters, min_pairs};
   const dc::IcpCtParams cp{beta_v, beta_w, max_twist_trans, max_twist_rot};
-  dc::icp_ct_finish_tail(tot, m, prm, cp, state, ct_state, status, work);
+  if (host_icp_totals<DC_ICP_CT_PARTIALS>(partials, n_blocks, status, tot)) dc::icp_ct_finish_tail(tot, m, prm, cp, state, ct_state, status, work);
   return 0;
 }
 

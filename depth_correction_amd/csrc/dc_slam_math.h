@@ -1,6 +1,6 @@
-// The per-iteration algebra of the scan-to-map point-to-plane ICP (dc_slam.hip), shared by the finish kernel and the
-// test-only host build (dc_hostcheck.cpp): the 6 x 6 fp64 normal equations, the pose update and the checks that end a
-// registration.  Reference configuration: config/slam/icp.yaml (PointToPlaneErrorMinimizer, transformationCheckers); DESIGN
+// The per-iteration algebra of the scan-to-map point-to-plane ICP (dc_slam.hip), shared by the finish kernels and the
+// test-only host build (dc_hostcheck.cpp): the fp64 normal equations of 6 unknowns (the pose) or 12 (pose and sweep twist), the
+// pose update and the checks that end a registration.  Reference configuration: config/slam/icp.yaml (PointToPlaneErrorMinimizer, transformationCheckers); DESIGN
 // "SLAM evaluation" states the algorithm.
 #pragma once
 #include <math.h>
@@ -9,41 +9,61 @@
 
 namespace dc {
 
-// JtJ packed as its upper triangle row by row: (0,0) (0,1) .. (0,5) (1,1) .. (5,5) -- 21 entries.
-DC_HD int sym6_index(int r, int c) {
+// JtJ of N unknowns packed as its upper triangle row by row: (0,0) (0,1) .. (0,N-1) (1,1) .. (N-1,N-1) -- N (N + 1) / 2 entries.
+template <int N>
+DC_HD int sym_index(int r, int c) {
   if (r > c) { const int t = r; r = c; c = t; }
-  return r * 6 - (r * (r - 1)) / 2 + (c - r);
+  return r * N - (r * (r - 1)) / 2 + (c - r);
 }
 
-// x = -(JtJ)^-1 Jtr by a Cholesky factorisation in fp64.  Returns 0, or 1 when a pivot is not above rel_eps times the largest
-// diagonal entry (the system is singular: the pairs do not constrain all six degrees of freedom) or is not finite.
-DC_HD int icp_solve6(const double* a21, const double* b6, double* x6, double rel_eps = 1e-12) {
-  double L[6][6];
+// The row of partials and totals of a registration with NU unknowns: the packed JtJ, Jtr, then pairs, sum r^2 and points with a
+// kept pair (DC_ICP_PARTIALS for 6 unknowns, DC_ICP_CT_PARTIALS for 12).
+template <int NU>
+struct IcpRow {
+  static constexpr int kJtr = NU * (NU + 1) / 2, kPairs = kJtr + NU, kSse = kPairs + 1, kUsed = kPairs + 2, kWidth = kPairs + 3;
+};
+static_assert(IcpRow<6>::kWidth == DC_ICP_PARTIALS && IcpRow<12>::kWidth == DC_ICP_CT_PARTIALS, "row layouts of include/dc_hip.h");
+
+// A (N x N row-major, both triangles) and b from a row of totals.
+template <int N>
+DC_HD void icp_unpack(const double* tot, double* A, double* b) {
+  for (int r = 0; r < N; ++r) {
+    for (int c = 0; c < N; ++c) A[r * N + c] = tot[sym_index<N>(r, c)];
+    b[r] = tot[IcpRow<N>::kJtr + r];
+  }
+}
+
+// x = -A^-1 b by a Cholesky factorisation in fp64 (A row-major N x N, its lower triangle is read).  Returns 0, or 1 when a pivot is
+// not above rel_eps times the largest diagonal entry (the system is singular: the pairs do not constrain every unknown) or is not
+// finite.  Lw [N * N] and y [N] are the caller's: local arrays for N = 6; for N = 12 the finish kernel keeps them in LDS, where a
+// runtime index costs no private segment.
+template <int N>
+DC_HD int icp_solve(const double* A, const double* b, double* x, double* Lw, double* y, double rel_eps = 1e-12) {
+  double (*L)[N] = (double (*)[N])Lw;
   double dmax = 0.0;
-  for (int i = 0; i < 6; ++i) dmax = fmax(dmax, fabs(a21[sym6_index(i, i)]));
+  for (int i = 0; i < N; ++i) dmax = fmax(dmax, fabs(A[i * N + i]));
   if (!(dmax > 0.0) || !isfinite(dmax)) return 1;
-  for (int j = 0; j < 6; ++j) {
-    double s = a21[sym6_index(j, j)];
+  for (int j = 0; j < N; ++j) {
+    double s = A[j * N + j];
     for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
     if (!(s > rel_eps * dmax) || !isfinite(s)) return 1;
     const double d = sqrt(s);
     L[j][j] = d;
-    for (int i = j + 1; i < 6; ++i) {
-      double t = a21[sym6_index(i, j)];
+    for (int i = j + 1; i < N; ++i) {
+      double t = A[i * N + j];
       for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
       L[i][j] = t / d;
     }
   }
-  double y[6];
-  for (int i = 0; i < 6; ++i) {                  // L y = -b
-    double t = -b6[i];
+  for (int i = 0; i < N; ++i) {                  // L y = -b
+    double t = -b[i];
     for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
     y[i] = t / L[i][i];
   }
-  for (int i = 5; i >= 0; --i) {                 // L^T x = y
+  for (int i = N - 1; i >= 0; --i) {             // L^T x = y
     double t = y[i];
-    for (int k = i + 1; k < 6; ++k) t -= L[k][i] * x6[k];
-    x6[i] = t / L[i][i];
+    for (int k = i + 1; k < N; ++k) t -= L[k][i] * x[k];
+    x[i] = t / L[i][i];
   }
   return 0;
 }
@@ -101,149 +121,55 @@ struct IcpParams {
 
 constexpr int kIcpBlocksMax = 512;      // most blocks (rows of partials) of dc_icp_accumulate
 
-// The single-thread tail of dc_icp_finish once the DC_ICP_PARTIALS totals of an iteration are complete (the block partials
-// [n_blocks, DC_ICP_PARTIALS] added in the order of dc_rowsum.h, eight lanes): counts the iteration,
-// records pairs / SSE / overlap, solves, and then in this order: DC_ICP_FAIL_PAIRS, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE,
-// DC_ICP_FAIL_BOUND (each leaves the estimate as it was), the estimate and the increment history updated, DC_ICP_CONVERGED,
-// DC_ICP_MAX_ITERS.  A status word that is already set is the caller's to test: this function is not called then.
-DC_HD void icp_finish_tail(const double* tot, int64_t m, const IcpParams& prm, double* st, int32_t* status) {
-  const int iter = status[1] + 1;
-  status[1] = iter;
-  st[DC_ICP_STATE_PAIRS] = tot[27];
-  st[DC_ICP_STATE_SSE] = tot[28];
-  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[29] / (double)m : 0.0;
-  if (tot[27] < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
-  double x[6];
-  if (icp_solve6(tot, tot + 21, x)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
-  double Tn[16];
-  icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
-  bool finite = true;
-  for (int q = 0; q < 6; ++q) finite = finite && isfinite(x[q]);
-  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
-  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
-  double C[16];
-  rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);            // the total correction relative to the prior (BoundTransformationChecker)
-  const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
-  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
-  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
-  // DifferentialTransformationChecker: the mean rotation / translation of the last `smooth` increments
-  const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
-  st[DC_ICP_STATE_HIST_ROT + slot] = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  st[DC_ICP_STATE_HIST_TRANS + slot] = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-  if (iter >= prm.smooth) {
-    double mr = 0.0, mt = 0.0;
-    for (int h = 0; h < prm.smooth; ++h) {
-      const int s = (iter - 1 - h) % DC_ICP_MAX_SMOOTH;
-      mr += st[DC_ICP_STATE_HIST_ROT + s];
-      mt += st[DC_ICP_STATE_HIST_TRANS + s];
-    }
-    mr /= (double)prm.smooth;
-    mt /= (double)prm.smooth;
-    if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
-  }
-  if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;      // CounterTransformationChecker: stop, keep the estimate
+// The arguments dc_icp_finish and dc_icp_ct_finish, on the device and in the host build, both refuse.
+inline bool icp_finish_args_ok(const double* partials, int n_blocks, int64_t m, int smooth, int max_iters, const double* state,
+                               const int32_t* status) {
+  return partials && state && status && n_blocks >= 1 && n_blocks <= kIcpBlocksMax && m >= 0 && smooth >= 1 && smooth <= DC_ICP_MAX_SMOOTH &&
+         max_iters >= 1;
 }
-
-// ---- the sweep-aware (12-dof) iteration: pose at the sweep's start and the twist (v, w) of the sweep; DESIGN "Sweep-aware
-// registration", include/dc_hip.h.  Unknowns in the order (d theta, d t, d v, d w). ----
-
-// JtJ packed as its upper triangle row by row: 78 entries.
-DC_HD int sym12_index(int r, int c) {
-  if (r > c) { const int t = r; r = c; c = t; }
-  return r * 12 - (r * (r - 1)) / 2 + (c - r);
-}
-
-// icp_solve6's factorisation and pivot rule for the 12 x 12 system (A row-major, full): x = -A^-1 b, 1 = singular.  L [144] and
-// y [12] are the caller's: the finish kernel keeps them in LDS, where a runtime index costs no private segment.
-DC_HD int icp_solve12(const double* A, const double* b12, double* x12, double* Lw, double* y, double rel_eps = 1e-12) {
-  double (*L)[12] = (double (*)[12])Lw;
-  double dmax = 0.0;
-  for (int i = 0; i < 12; ++i) dmax = fmax(dmax, fabs(A[i * 12 + i]));
-  if (!(dmax > 0.0) || !isfinite(dmax)) return 1;
-  for (int j = 0; j < 12; ++j) {
-    double s = A[j * 12 + j];
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    if (!(s > rel_eps * dmax) || !isfinite(s)) return 1;
-    const double d = sqrt(s);
-    L[j][j] = d;
-    for (int i = j + 1; i < 12; ++i) {
-      double t = A[i * 12 + j];
-      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
-      L[i][j] = t / d;
-    }
-  }
-  for (int i = 0; i < 12; ++i) {                 // L y = -b
-    double t = -b12[i];
-    for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
-    y[i] = t / L[i][i];
-  }
-  for (int i = 11; i >= 0; --i) {                // L^T x = y
-    double t = y[i];
-    for (int k = i + 1; k < 12; ++k) t -= L[k][i] * x12[k];
-    x12[i] = t / L[i][i];
-  }
-  return 0;
-}
-
-struct IcpCtParams {
-  double beta_v, beta_w;                  // the constant-velocity prior's weights (dimensionless, per kept pair)
-  double max_twist_trans, max_twist_rot;  // largest |v - v0| and |w - w0|
-};
 
 DC_HD double icp_norm3(const double* a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 
-// The single-thread tail of dc_icp_ct_finish once the DC_ICP_CT_PARTIALS totals are complete; st is the 6-dof state
-// [DC_ICP_STATE_COUNT] (pose, prior, history, pairs / SSE / overlap as icp_finish_tail keeps them), ct the twist state
-// [DC_ICP_CT_STATE_COUNT].  The order of icp_finish_tail: count, record, DC_ICP_FAIL_PAIRS, the prior N beta (twist - prior twist)
-// added to the system, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE, DC_ICP_FAIL_BOUND (the pose bound, |w| > pi, the twist bound;
-// every failure leaves pose and twist as they were), pose, twist and history updated, DC_ICP_CONVERGED, DC_ICP_MAX_ITERS.
-constexpr int kIcpCtWork = 144 + 144 + 3 * 12;      // doubles of icp_ct_finish_tail's workspace: A, L, b, x, y
+// ---- the steps both single-thread tails take, in the order they take them ----
 
-DC_HD void icp_ct_finish_tail(const double* tot, int64_t m, const IcpParams& prm, const IcpCtParams& cp, double* st, double* ct,
-                              int32_t* status, double* work) {
+// Counts the iteration and records pairs / SSE / overlap from the three counters at the end of a row of totals.  Returns the
+// iteration's number (from 1), or 0 with DC_ICP_FAIL_PAIRS set.
+DC_HD int icp_begin_iteration(const double* counters, int64_t m, const IcpParams& prm, double* st, int32_t* status) {
   const int iter = status[1] + 1;
   status[1] = iter;
-  const double pairs = tot[90];
-  st[DC_ICP_STATE_PAIRS] = pairs;
-  st[DC_ICP_STATE_SSE] = tot[91];
-  st[DC_ICP_STATE_OVERLAP] = m > 0 ? tot[92] / (double)m : 0.0;
-  if (pairs < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return; }
-  double *A = work, *L = work + 144, *b = work + 288, *x = work + 300, *y = work + 312;
-  for (int r = 0; r < 12; ++r) {
-    for (int c = 0; c < 12; ++c) A[r * 12 + c] = tot[sym12_index(r, c)];
-    b[r] = tot[78 + r];
-  }
-  const double* tw = ct + DC_ICP_CT_STATE_TWIST;
-  const double* tw0 = ct + DC_ICP_CT_STATE_PRIOR_TWIST;
-  for (int q = 0; q < 6; ++q) {
-    const double wgt = pairs * (q < 3 ? cp.beta_v : cp.beta_w);
-    A[(6 + q) * 12 + 6 + q] += wgt;
-    b[6 + q] += wgt * (tw[q] - tw0[q]);
-  }
-  if (icp_solve12(A, b, x, L, y)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
-  double Tn[16], twn[6];
+  st[DC_ICP_STATE_PAIRS] = counters[0];
+  st[DC_ICP_STATE_SSE] = counters[1];
+  st[DC_ICP_STATE_OVERLAP] = m > 0 ? counters[2] / (double)m : 0.0;
+  if (counters[0] < (double)prm.min_pairs) { status[0] = DC_ICP_FAIL_PAIRS; return 0; }
+  return iter;
+}
+
+// The candidate pose Tn = D(x[0:6]) T of the step x [nx]; false when an entry of x or of Tn is not finite.  The tests are joined
+// with & so that no branch splits the block that holds the rotation's products and their sums: the device compiler contracts
+// within a basic block only, and a split there changes which products of icp_apply_step become fma.
+DC_HD bool icp_candidate_pose(const double* x, int nx, const double* st, double* Tn) {
   icp_apply_step(x, st + DC_ICP_STATE_POSE, Tn);
-  for (int q = 0; q < 6; ++q) twn[q] = tw[q] + x[6 + q];
   bool finite = true;
-  for (int q = 0; q < 12; ++q) finite = finite && isfinite(x[q]);
-  for (int q = 0; q < 16; ++q) finite = finite && isfinite(Tn[q]);
-  for (int q = 0; q < 6; ++q) finite = finite && isfinite(twn[q]);
-  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  for (int q = 0; q < nx; ++q) finite &= isfinite(x[q]);
+  for (int q = 0; q < 16; ++q) finite &= isfinite(Tn[q]);
+  return finite;
+}
+
+// BoundTransformationChecker: the total correction of the candidate relative to the prior inside max_rot / max_trans.
+DC_HD bool icp_pose_in_bound(const double* Tn, const double* st, const IcpParams& prm) {
   double C[16];
   rigid_div(Tn, st + DC_ICP_STATE_PRIOR, C);
   const double c_rot = rotation_angle4(C), c_trans = sqrt(C[3] * C[3] + C[7] * C[7] + C[11] * C[11]);
-  if (!(c_rot <= prm.max_rot) || !(c_trans <= prm.max_trans)) { status[0] = DC_ICP_FAIL_BOUND; return; }
-  double dtw[6];
-  for (int q = 0; q < 6; ++q) dtw[q] = twn[q] - tw0[q];
-  if (!(icp_norm3(twn + 3) <= 3.14159265358979323846) || !(icp_norm3(dtw) <= cp.max_twist_trans) || !(icp_norm3(dtw + 3) <= cp.max_twist_rot)) {
-    status[0] = DC_ICP_FAIL_BOUND;
-    return;
-  }
-  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
-  for (int q = 0; q < 6; ++q) ct[DC_ICP_CT_STATE_TWIST + q] = twn[q];
+  return c_rot <= prm.max_rot && c_trans <= prm.max_trans;
+}
+
+// DifferentialTransformationChecker on the history ring: records the rotation / translation sizes of iteration iter's increment,
+// then DC_ICP_CONVERGED when the means of the last `smooth` are below min_rot / min_trans, else DC_ICP_MAX_ITERS at the counter
+// (CounterTransformationChecker: stop, keep the estimate).
+DC_HD void icp_record_increment(int iter, double d_rot, double d_trans, const IcpParams& prm, double* st, int32_t* status) {
   const int slot = (iter - 1) % DC_ICP_MAX_SMOOTH;
-  st[DC_ICP_STATE_HIST_ROT + slot] = fmax(icp_norm3(x), icp_norm3(x + 9));
-  st[DC_ICP_STATE_HIST_TRANS + slot] = fmax(icp_norm3(x + 3), icp_norm3(x + 6));
+  st[DC_ICP_STATE_HIST_ROT + slot] = d_rot;
+  st[DC_ICP_STATE_HIST_TRANS + slot] = d_trans;
   if (iter >= prm.smooth) {
     double mr = 0.0, mt = 0.0;
     for (int h = 0; h < prm.smooth; ++h) {
@@ -256,6 +182,72 @@ DC_HD void icp_ct_finish_tail(const double* tot, int64_t m, const IcpParams& prm
     if (mr < prm.min_rot && mt < prm.min_trans) { status[0] = DC_ICP_CONVERGED; return; }
   }
   if (iter >= prm.max_iters) status[0] = DC_ICP_MAX_ITERS;
+}
+
+// The single-thread tail of dc_icp_finish once the DC_ICP_PARTIALS totals of an iteration are complete (the block partials
+// [n_blocks, DC_ICP_PARTIALS] added in the order of dc_rowsum.h, eight lanes): counts the iteration,
+// records pairs / SSE / overlap, solves, and then in this order: DC_ICP_FAIL_PAIRS, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE,
+// DC_ICP_FAIL_BOUND (each leaves the estimate as it was), the estimate and the increment history updated, DC_ICP_CONVERGED,
+// DC_ICP_MAX_ITERS.  A status word that is already set is the caller's to test: this function is not called then.
+DC_HD void icp_finish_tail(const double* tot, int64_t m, const IcpParams& prm, double* st, int32_t* status) {
+  const int iter = icp_begin_iteration(tot + IcpRow<6>::kPairs, m, prm, st, status);
+  if (!iter) return;
+  double A[36], L[36], b[6], x[6], y[6];
+  icp_unpack<6>(tot, A, b);
+  if (icp_solve<6>(A, b, x, L, y)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
+  double Tn[16];
+  if (!icp_candidate_pose(x, 6, st, Tn)) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  if (!icp_pose_in_bound(Tn, st, prm)) { status[0] = DC_ICP_FAIL_BOUND; return; }
+  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
+  icp_record_increment(iter, icp_norm3(x), icp_norm3(x + 3), prm, st, status);
+}
+
+// ---- the sweep-aware (12-dof) iteration: pose at the sweep's start and the twist (v, w) of the sweep; DESIGN "Sweep-aware
+// registration", include/dc_hip.h.  Unknowns in the order (d theta, d t, d v, d w). ----
+
+struct IcpCtParams {
+  double beta_v, beta_w;                  // the constant-velocity prior's weights (dimensionless, per kept pair)
+  double max_twist_trans, max_twist_rot;  // largest |v - v0| and |w - w0|
+};
+
+constexpr int kIcpCtWork = 144 + 144 + 3 * 12;      // doubles of icp_ct_finish_tail's workspace: A, L, b, x, y
+
+// The single-thread tail of dc_icp_ct_finish once the DC_ICP_CT_PARTIALS totals are complete; st is the 6-dof state
+// [DC_ICP_STATE_COUNT] (pose, prior, history, pairs / SSE / overlap as icp_finish_tail keeps them), ct the twist state
+// [DC_ICP_CT_STATE_COUNT].  icp_finish_tail's steps with the twist's between them: count, record, DC_ICP_FAIL_PAIRS, the prior
+// N beta (twist - prior twist) added to the system, DC_ICP_FAIL_SINGULAR, DC_ICP_FAIL_NONFINITE, DC_ICP_FAIL_BOUND (the pose bound,
+// |w| > pi, the twist bound; every failure leaves pose and twist as they were), pose, twist and history updated (the history
+// holds the larger of the pose's and the twist's increment), DC_ICP_CONVERGED, DC_ICP_MAX_ITERS.
+DC_HD void icp_ct_finish_tail(const double* tot, int64_t m, const IcpParams& prm, const IcpCtParams& cp, double* st, double* ct,
+                              int32_t* status, double* work) {
+  const int iter = icp_begin_iteration(tot + IcpRow<12>::kPairs, m, prm, st, status);
+  if (!iter) return;
+  double *A = work, *L = work + 144, *b = work + 288, *x = work + 300, *y = work + 312;
+  icp_unpack<12>(tot, A, b);
+  const double pairs = tot[IcpRow<12>::kPairs];
+  const double* tw = ct + DC_ICP_CT_STATE_TWIST;
+  const double* tw0 = ct + DC_ICP_CT_STATE_PRIOR_TWIST;
+  for (int q = 0; q < 6; ++q) {
+    const double wgt = pairs * (q < 3 ? cp.beta_v : cp.beta_w);
+    A[(6 + q) * 12 + 6 + q] += wgt;
+    b[6 + q] += wgt * (tw[q] - tw0[q]);
+  }
+  if (icp_solve<12>(A, b, x, L, y)) { status[0] = DC_ICP_FAIL_SINGULAR; return; }
+  double Tn[16], twn[6];
+  bool finite = icp_candidate_pose(x, 12, st, Tn);
+  for (int q = 0; q < 6; ++q) twn[q] = tw[q] + x[6 + q];
+  for (int q = 0; q < 6; ++q) finite = finite && isfinite(twn[q]);
+  if (!finite) { status[0] = DC_ICP_FAIL_NONFINITE; return; }
+  if (!icp_pose_in_bound(Tn, st, prm)) { status[0] = DC_ICP_FAIL_BOUND; return; }
+  double dtw[6];
+  for (int q = 0; q < 6; ++q) dtw[q] = twn[q] - tw0[q];
+  if (!(icp_norm3(twn + 3) <= 3.14159265358979323846) || !(icp_norm3(dtw) <= cp.max_twist_trans) || !(icp_norm3(dtw + 3) <= cp.max_twist_rot)) {
+    status[0] = DC_ICP_FAIL_BOUND;
+    return;
+  }
+  for (int q = 0; q < 16; ++q) st[DC_ICP_STATE_POSE + q] = Tn[q];
+  for (int q = 0; q < 6; ++q) ct[DC_ICP_CT_STATE_TWIST + q] = twn[q];
+  icp_record_increment(iter, fmax(icp_norm3(x), icp_norm3(x + 9)), fmax(icp_norm3(x + 3), icp_norm3(x + 6)), prm, st, status);
 }
 
 }  // namespace dc

@@ -2079,26 +2079,43 @@ def icp_init(prior, state, status):
     check(lib().dc_icp_init(ptr(prior), ptr(state), ptr(status), stream_ptr()), 'dc_icp_init')
 
 
-@on_device
-def icp_accumulate(reading, normals, map_points, map_normals, idx, dist, threshold, cos_min, state, status, partials, kept=None):
-    """Filtered point-to-plane pairs of one ICP iteration -> block partials f64 [icp_blocks(M), DC_ICP_PARTIALS] (dc_icp_accumulate);
-    ``kept`` (uint8 [M,k], optional) receives the kept flags."""
+def _icp_accumulate_args(reading, per_point, map_points, map_normals, idx, dist, threshold, state, status, partials, width, kept,
+                         ct_state=None):
+    """The checks icp_accumulate and icp_ct_accumulate share (``per_point``: (name, tensor, trailing shape) of the caller's own
+    per-point inputs; ``width`` of a row of partials) -> (M, k, blocks)."""
     dev = reading.device
     need(reading, (None, 3), dtype=torch.float64, name='reading')
     m = reading.shape[0]
-    need(normals, (m, 3), dtype=torch.float64, name='normals', device=dev)
+    for name, t, tail in per_point:
+        need(t, (m,) + tail, dtype=torch.float64, name=name, device=dev)
     need(map_points, (None, 3), dtype=torch.float64, name='map_points', device=dev)
     need(map_normals, tuple(map_points.shape), dtype=torch.float64, name='map_normals', device=dev)
     need(idx, (m, None), dtype=torch.int32, name='idx', device=dev)
     k = idx.shape[1]
     need(dist, (m, k), dtype=torch.float64, name='dist', device=dev)
     need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
-    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
-    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    _icp_state_args(state, status, dev, ct_state)
     nb = icp_blocks(m)
-    need(partials, (nb, nv.DC_ICP_PARTIALS), dtype=torch.float64, name='partials', device=dev)
+    need(partials, (nb, width), dtype=torch.float64, name='partials', device=dev)
     if kept is not None:
         need(kept, (m, k), dtype=torch.uint8, name='kept', device=dev)
+    return m, k, nb
+
+
+def _icp_state_args(state, status, dev, ct_state=None):
+    """The state / status (and twist state) checks of the ICP calls."""
+    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
+    if ct_state is not None:
+        need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=dev)
+    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+
+
+@on_device
+def icp_accumulate(reading, normals, map_points, map_normals, idx, dist, threshold, cos_min, state, status, partials, kept=None):
+    """Filtered point-to-plane pairs of one ICP iteration -> block partials f64 [icp_blocks(M), DC_ICP_PARTIALS] (dc_icp_accumulate);
+    ``kept`` (uint8 [M,k], optional) receives the kept flags."""
+    m, k, nb = _icp_accumulate_args(reading, [('normals', normals, (3,))], map_points, map_normals, idx, dist, threshold, state, status,
+                                    partials, nv.DC_ICP_PARTIALS, kept)
     check(lib().dc_icp_accumulate(ptr(reading), ptr(normals), m, ptr(map_points), ptr(map_normals), ptr(idx), ptr(dist), k, ptr(threshold),
                                   float(cos_min), ptr(state), ptr(status), ptr(partials), nb, ptr(kept), stream_ptr()), 'dc_icp_accumulate')
 
@@ -2106,10 +2123,8 @@ def icp_accumulate(reading, normals, map_points, map_normals, idx, dist, thresho
 @on_device
 def icp_finish(partials, m, state, status, min_rot, min_trans, smooth, max_iters, max_rot, max_trans, min_pairs=6):
     """Solve, update and check one ICP iteration in one block (dc_icp_finish)."""
-    dev = partials.device
     need(partials, (None, nv.DC_ICP_PARTIALS), dtype=torch.float64, name='partials')
-    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
-    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    _icp_state_args(state, status, partials.device)
     check(lib().dc_icp_finish(ptr(partials), partials.shape[0], int(m), float(min_rot), float(min_trans), int(smooth), int(max_iters),
                               float(max_rot), float(max_trans), int(min_pairs), ptr(state), ptr(status), stream_ptr()), 'dc_icp_finish')
 
@@ -2147,25 +2162,8 @@ def icp_ct_accumulate(reading, q, nq, tau, map_points, map_normals, idx, dist, t
                       kept=None):
     """icp_accumulate for the sweep-aware iteration: the pairs of the de-skewed points ``q`` / normals ``nq`` (deskew_device_twist of
     ``reading`` at ``tau``) -> block partials f64 [icp_blocks(M), DC_ICP_CT_PARTIALS] (dc_icp_ct_accumulate)."""
-    dev = reading.device
-    need(reading, (None, 3), dtype=torch.float64, name='reading')
-    m = reading.shape[0]
-    need(q, (m, 3), dtype=torch.float64, name='q', device=dev)
-    need(nq, (m, 3), dtype=torch.float64, name='nq', device=dev)
-    need(tau, (m,), dtype=torch.float64, name='tau', device=dev)
-    need(map_points, (None, 3), dtype=torch.float64, name='map_points', device=dev)
-    need(map_normals, tuple(map_points.shape), dtype=torch.float64, name='map_normals', device=dev)
-    need(idx, (m, None), dtype=torch.int32, name='idx', device=dev)
-    k = idx.shape[1]
-    need(dist, (m, k), dtype=torch.float64, name='dist', device=dev)
-    need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
-    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
-    need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=dev)
-    need(status, (4,), dtype=torch.int32, name='status', device=dev)
-    nb = icp_blocks(m)
-    need(partials, (nb, nv.DC_ICP_CT_PARTIALS), dtype=torch.float64, name='partials', device=dev)
-    if kept is not None:
-        need(kept, (m, k), dtype=torch.uint8, name='kept', device=dev)
+    m, k, nb = _icp_accumulate_args(reading, [('q', q, (3,)), ('nq', nq, (3,)), ('tau', tau, ())], map_points, map_normals, idx, dist,
+                                    threshold, state, status, partials, nv.DC_ICP_CT_PARTIALS, kept, ct_state)
     check(lib().dc_icp_ct_accumulate(ptr(reading), ptr(q), ptr(nq), ptr(tau), m, ptr(map_points), ptr(map_normals), ptr(idx), ptr(dist), k,
                                      ptr(threshold), float(cos_min), ptr(state), ptr(ct_state), ptr(status), ptr(partials), nb, ptr(kept),
                                      stream_ptr()), 'dc_icp_ct_accumulate')
@@ -2175,11 +2173,8 @@ def icp_ct_accumulate(reading, q, nq, tau, map_points, map_normals, idx, dist, t
 def icp_ct_finish(partials, m, state, ct_state, status, min_rot, min_trans, smooth, max_iters, max_rot, max_trans, beta_v, beta_w,
                   max_twist_trans, max_twist_rot, min_pairs=6):
     """Solve the 12 x 12 system with the twist prior, update pose and twist and check, in one block (dc_icp_ct_finish)."""
-    dev = partials.device
     need(partials, (None, nv.DC_ICP_CT_PARTIALS), dtype=torch.float64, name='partials')
-    need(state, (nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, name='state', device=dev)
-    need(ct_state, (nv.DC_ICP_CT_STATE_COUNT,), dtype=torch.float64, name='ct_state', device=dev)
-    need(status, (4,), dtype=torch.int32, name='status', device=dev)
+    _icp_state_args(state, status, partials.device, ct_state)
     check(lib().dc_icp_ct_finish(ptr(partials), partials.shape[0], int(m), float(min_rot), float(min_trans), int(smooth), int(max_iters),
                                  float(max_rot), float(max_trans), int(min_pairs), float(beta_v), float(beta_w), float(max_twist_trans),
                                  float(max_twist_rot), ptr(state), ptr(ct_state), ptr(status), stream_ptr()), 'dc_icp_ct_finish')

@@ -254,20 +254,28 @@ class IcpMapper(object):
         grid, map_pts, map_nrm, _ = self.reference(m)
         if grid is None:
             return prior.copy(), self._info('too_few_pairs')
+        partials = torch.empty((ops.icp_blocks(m), nv.DC_ICP_PARTIALS), dtype=torch.float64, device=self.device)
+        return self._run_registration(m, prior, LAUNCHES_PER_ITERATION, lambda pose_d, idx, dist, thr, cos_min: self.iteration(
+            scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, grid=grid))
+
+    def _run_registration(self, m, prior, launches, iterate):
+        """What register and register_ct share once there is something to match against: the match / distance / threshold buffers
+        of an m-point scan, icp_init from ``prior``, ``iterate(pose_d, idx, dist, thr, cos_min)`` (one iteration of ``launches``
+        launches, queued) ``status_every`` at a time with one status read per group, and the read-back.  -> (pose, info), the
+        prior's copy when the registration failed."""
+        cfg = self.cfg
         dev, k = self.device, self.knn
-        prior_d = torch.as_tensor(prior, device=dev)
         idx = torch.empty((m, k), dtype=torch.int32, device=dev)
         dist = torch.empty((m, k), dtype=torch.float64, device=dev)
         thr = torch.empty((1,), dtype=torch.float64, device=dev)
-        partials = torch.empty((ops.icp_blocks(m), nv.DC_ICP_PARTIALS), dtype=torch.float64, device=dev)
         pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
         cos_min = float(np.cos(cfg.icp_max_normal_angle))
-        ops.icp_init(prior_d, self.state, self.status)
+        ops.icp_init(torch.as_tensor(prior, device=dev), self.state, self.status)
         done = 0
         code = 0
         while done < cfg.icp_max_iters:
             for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
-                self.iteration(scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, grid=grid)
+                iterate(pose_d, idx, dist, thr, cos_min)
                 done += 1
             st = self.status.cpu()
             self.host_reads += 1
@@ -277,18 +285,23 @@ class IcpMapper(object):
         st = self.state.cpu().numpy()
         iters = int(self.status[1].item())
         info = self._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
-                          float(st[nv.DC_ICP_STATE_SSE]))
+                          float(st[nv.DC_ICP_STATE_SSE]), launches=launches)
         if not info['ok']:
             return prior.copy(), info
         return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+
+    def _match(self, points, pose_d, idx, dist, thr, grid):
+        """The two launches every iteration starts with: the k-NN of ``points`` moved by the device-side pose, the trimmed threshold."""
+        cfg = self.cfg
+        ops.knn_grid_query(self.grid if grid is None else grid, points, pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx,
+                           dist=dist)
+        ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
 
     def iteration(self, scan, pose_d, idx, dist, thr, partials, map_pts, map_nrm, cos_min, kept=None, grid=None):
         """One ICP iteration, queued on the stream: match, trimmed threshold, pairs and partials, solve and update.  ``grid`` is the
         grid of ``map_pts`` (the whole map's unless given: reference())."""
         cfg = self.cfg
-        ops.knn_grid_query(self.grid if grid is None else grid, scan.points, pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx,
-                           dist=dist)
-        ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
+        self._match(scan.points, pose_d, idx, dist, thr, grid)
         ops.icp_accumulate(scan.points, scan.normals, map_pts, map_nrm, idx, dist, thr, cos_min, self.state, self.status, partials,
                            kept=kept)
         ops.icp_finish(partials, len(scan), self.state, self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans, cfg.icp_smooth_length,
@@ -320,7 +333,6 @@ class IcpMapper(object):
         """register() with the twist (v, w) of the sweep as six more unknowns: -> (pose at sweep time 0, info).  info['twist'] is the
         estimated twist (the prior twist when the registration fails) and info['deskewed'] the scan de-skewed by it (points and
         normals of a last dc_deskew, the depths as they were), which is what update / update_dynamic are to be given."""
-        cfg = self.cfg
         prior = np.asarray(prior, dtype=np.float64).reshape(4, 4)
         twist0 = np.zeros(6) if twist is None else np.asarray(twist, dtype=np.float64).reshape(6)
         if not np.isfinite(twist0).all() or float(np.linalg.norm(twist0[3:])) > np.pi:
@@ -345,38 +357,18 @@ class IcpMapper(object):
         grid, map_pts, map_nrm, _ = self.reference(m)
         if grid is None:
             return ended('too_few_pairs')
-        dev, k = self.device, self.knn
-        idx = torch.empty((m, k), dtype=torch.int32, device=dev)
-        dist = torch.empty((m, k), dtype=torch.float64, device=dev)
-        thr = torch.empty((1,), dtype=torch.float64, device=dev)
         buf = self.ct_buffers(m)
-        pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
-        cos_min = float(np.cos(cfg.icp_max_normal_angle))
-        ops.icp_init(torch.as_tensor(prior, device=dev), self.state, self.status)
-        ops.icp_ct_init(torch.as_tensor(twist0, device=dev), buf['ct'])
-        done = 0
-        code = 0
-        while done < cfg.icp_max_iters:
-            for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
-                self.iteration_ct(scan, pose_d, idx, dist, thr, buf, map_pts, map_nrm, cos_min, prm, grid=grid)
-                done += 1
-            st = self.status.cpu()
-            self.host_reads += 1
-            code = int(st[0])
-            if code != 0:
-                break
-        st = self.state.cpu().numpy()
-        iters = int(self.status[1].item())
-        info = self._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
-                          float(st[nv.DC_ICP_STATE_SSE]), launches=launches)
+        ops.icp_ct_init(torch.as_tensor(twist0, device=self.device), buf['ct'])
+        pose, info = self._run_registration(m, prior, launches, lambda pose_d, idx, dist, thr, cos_min: self.iteration_ct(
+            scan, pose_d, idx, dist, thr, buf, map_pts, map_nrm, cos_min, prm, grid=grid))
         if not info['ok']:
             info['twist'], info['deskewed'] = twist0.copy(), scan
-            return prior.copy(), info
+            return pose, info
         tw = buf['ct'][nv.DC_ICP_CT_STATE_TWIST:nv.DC_ICP_CT_STATE_TWIST + 6]
         ops.deskew_device_twist(scan.points, scan.normals, scan.t, tw, buf['off'], buf['q'], buf['nq'])      # by the final twist
         info['twist'] = tw.cpu().numpy().copy()
         info['deskewed'] = MapperScan(buf['q'], buf['nq'], scan.depth, scan.t)
-        return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+        return pose, info
 
     def iteration_ct(self, scan, pose_d, idx, dist, thr, buf, map_pts, map_nrm, cos_min, prm, kept=None, grid=None):
         """One sweep-aware iteration, queued on the stream: de-skew by the device's twist, match, trimmed threshold, pairs and
@@ -384,9 +376,7 @@ class IcpMapper(object):
         cfg = self.cfg
         tw = buf['ct'][nv.DC_ICP_CT_STATE_TWIST:nv.DC_ICP_CT_STATE_TWIST + 6]
         ops.deskew_device_twist(scan.points, scan.normals, scan.t, tw, buf['off'], buf['q'], buf['nq'])
-        ops.knn_grid_query(self.grid if grid is None else grid, buf['q'], pose_d, self.knn, r=cfg.icp_max_dist, stop=self.status, idx=idx,
-                           dist=dist)
-        ops.quantile(dist, cfg.icp_trim_ratio, stop=self.status, out=thr, ws=self.quantile_ws)
+        self._match(buf['q'], pose_d, idx, dist, thr, grid)
         ops.icp_ct_accumulate(scan.points, buf['q'], buf['nq'], scan.t, map_pts, map_nrm, idx, dist, thr, cos_min, self.state, buf['ct'],
                               self.status, buf['partials'], kept=kept)
         ops.icp_ct_finish(buf['partials'], len(scan), self.state, buf['ct'], self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans,

@@ -1,7 +1,8 @@
 """Sweep-aware registration on the device against tests/slam_ct_reference.py (numpy + cKDTree, fp64, sums in extended precision):
-dc_icp_ct_accumulate on hand-written tables at the sizes where it can go wrong, zero motion against the 6-dof path, a whole
-registration of a swept scan iteration by iteration, the sweep times through mapper_input and prepare, and run_slam on the six-pose
-arc of tests/test_gpu_sweep.py raw, de-skewed by the odometry and sweep-aware.
+dc_icp_ct_accumulate on hand-written tables at the sizes where it can go wrong, dc_icp_ct_finish's state machine on scripted
+registrations, zero motion against the 6-dof path, a whole registration of a swept scan iteration by iteration, the sweep times
+through mapper_input and prepare, and run_slam on the six-pose arc of tests/test_gpu_sweep.py raw, de-skewed by the odometry and
+sweep-aware.
 
 The bars.  Totals: (n + 16) 2^-53 sum|term|, what dc_icp_accumulate is held to.  Pose and twist entries per iteration: 2 000 x the
 largest change of the reference's own result on the parity scene when the order of its sums is permuted (DESIGN "SLAM evaluation"
@@ -19,6 +20,7 @@ import slam_ct_reference as C
 import slam_reference as R
 import sweep_reference as S
 from helpers import slam_pose
+from test_slam_ct_host import host, host_ct_finish          # noqa: F401 (host is a fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -156,6 +158,65 @@ def test_ct_accumulate_edges():
     # a status word that is set: partials and kept flags keep their bytes
     part, kept = _run(c, q, nq, status_code=1, fill=3.25)
     assert (part == 3.25).all() and (kept == 7).all()
+
+
+# ---- 1b. dc_icp_ct_finish as a state machine on the device -------------------------------------------------------------------------
+def _dev_ct_finish(partials, m, prm, state, ct, status):
+    from depth_correction_amd import ops
+    ops.icp_ct_finish(partials, m, state, ct, status, prm.icp_min_diff_rot, prm.icp_min_diff_trans, int(prm.icp_smooth_length),
+                      int(prm.icp_max_iters), prm.icp_max_rotation, prm.icp_max_translation, prm.slam_ct_prior[0], prm.slam_ct_prior[1],
+                      prm.slam_ct_max_twist[0], prm.slam_ct_max_twist[1], min_pairs=int(prm.min_pairs))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('case', C.finish_cases(), ids=lambda c: c[0])
+def test_ct_finish_scripted_registrations_on_device(host, case):
+    """The table of tests/test_slam_ct_host.py through ops.icp_ct_finish with hand-made [1, 93] partials, what
+    tests/test_gpu_slam_parity.py does for the 6-unknown finish.  Against the numpy restatement: status, iterations, pairs / SSE /
+    overlap, history and prior twist bit-equal, pose and twist 1e-14.  Against the host build of the same header, which takes every
+    step from the state the device took it from: the same words equal, pose and twist within 4 ulp (libm against the device's sin /
+    cos / sqrt), the ulp being that of the entry's terms: sum_k |D_rk| |T_kc| for the pose update D T, |twist| + |step| for the
+    twist.  A failure leaves pose and twist byte for byte; a launch after the end changes nothing."""
+    name, over, steps, expect = case
+    prm = C.script_params(over)
+    ref = C.new_state(R.SCRIPT_PRIOR, C.SCRIPT_TWIST)
+    state, ct = (_t(a) for a in C.state_vectors(ref))
+    status = torch.zeros((4,), dtype=torch.int32, device=DEV)
+    codes = []
+    for step in steps:
+        if codes and codes[-1] != 0:
+            break
+        tot, m = C.script_totals(step)
+        before, ct_before = _np(state).copy(), _np(ct).copy()
+        h_state, h_ct, h_status = before.copy(), ct_before.copy(), _np(status).copy()
+        _dev_ct_finish(_t(tot.reshape(1, C.N_TOT)), m, prm, state, ct, status)
+        host_ct_finish(host, tot, m, prm, h_state, h_ct, h_status)
+        x_step, _ = C.finish(tot, m, prm, ref)
+        got, got_ct, word = _np(state), _np(ct), _np(status)
+        want, want_ct = C.state_vectors(ref)
+        codes.append(int(word[0]))
+        assert word[0] == ref.code == h_status[0] and word[1] == ref.iters == h_status[1] == len(codes), (name, codes)
+        assert got[16:].tobytes() == want[16:].tobytes() == h_state[16:].tobytes(), (name, len(codes), got[32:51], want[32:51])
+        assert got_ct[6:].tobytes() == want_ct[6:].tobytes() == h_ct[6:].tobytes(), (name, len(codes))
+        assert np.abs(got[:16] - want[:16]).max() <= 1e-14 and np.abs(got_ct[:6] - want_ct[:6]).max() <= 1e-14, (name, len(codes))
+        if word[0] < 0:                                    # a failure: the estimate it was given, byte for byte
+            assert got[:16].tobytes() == before[:16].tobytes() == h_state[:16].tobytes(), name
+            assert got_ct.tobytes() == ct_before.tobytes() == h_ct.tobytes(), name
+        else:
+            D = np.eye(4)
+            D[:3, :3], D[:3, 3] = R.rotation(x_step[:3]), x_step[3:6]
+            terms = (np.abs(D) @ np.abs(before[:16].reshape(4, 4))).reshape(-1)
+            unit = np.spacing(np.maximum(terms, np.abs(h_state[:16])))
+            big = np.abs(h_state[:16]) >= 0.5
+            assert (unit[big] <= 2 * np.spacing(np.abs(h_state[:16]))[big]).all()        # no cancellation there: the entry's own ulp
+            assert (np.abs(got[:16] - h_state[:16]) <= 4 * unit).all(), (name, got[:16] - h_state[:16])
+            unit_tw = np.spacing(np.maximum(np.abs(ct_before[:6]) + np.abs(x_step[6:]), np.abs(h_ct[:6])))
+            assert (np.abs(got_ct[:6] - h_ct[:6]) <= 4 * unit_tw).all(), (name, got_ct[:6] - h_ct[:6])
+            assert got[:16].tobytes() != before[:16].tobytes() or got_ct[:6].tobytes() != ct_before[:6].tobytes(), name
+    assert codes == expect, (name, codes)
+    frozen = (_np(state).tobytes(), _np(ct).tobytes(), _np(status).tobytes())
+    _dev_ct_finish(_t(C.script_totals(steps[0])[0].reshape(1, C.N_TOT)), 50, prm, state, ct, status)
+    assert (_np(state).tobytes(), _np(ct).tobytes(), _np(status).tobytes()) == frozen, name
 
 
 # ---- 2. the pillared room -------------------------------------------------------------------------------------------------------------

@@ -270,8 +270,9 @@ def test_ct_finish_block_sum_order(host, n_blocks):
 
 # ---- 4. the code object ---------------------------------------------------------------------------------------------------------------
 def test_ct_kernels_have_no_private_segment():
-    """icp_ct_accumulate_kernel keeps its 93 fp64 sums in registers: no private segment in any of the new kernels, at most 512
-    registers per lane (one wavefront per SIMD).  Metadata notes of the built library only."""
+    """icp_ct_accumulate_kernel keeps its 93 fp64 sums in registers: no private segment in the pair and finish kernels of either
+    registration nor in icp_ct_init_kernel, at most 512 registers per lane (one wavefront per SIMD); the pair kernels' LDS is the
+    block sum's one row per wavefront (4 x 30 and 4 x 93 doubles).  Metadata notes of the built library only."""
     from test_step_kernel_resources import _code_objects, _kernels
     import __graft_entry__ as ge
     ge.build()
@@ -280,15 +281,18 @@ def test_ct_kernels_have_no_private_segment():
     found = {}
     for elf in _code_objects(blob):
         for k in _kernels(elf):
-            m = re.search(r'\d+(icp_ct_init_kernel|icp_ct_accumulate_kernel|icp_ct_finish_kernel)E', k['.name'])
+            m = re.search(r'\d+(icp_accumulate_kernel|icp_finish_kernel|icp_ct_init_kernel|icp_ct_accumulate_kernel|icp_ct_finish_kernel)E',
+                          k['.name'])
             if m:
                 found[m.group(1)] = k
-    assert len(found) == 3, sorted(found)
+    assert len(found) == 5, sorted(found)
     for name, k in sorted(found.items()):
         print('%s: vgpr %d sgpr %d scratch %d lds %d' % (name, k['.vgpr_count'], k['.sgpr_count'], k['.private_segment_fixed_size'],
                                                          k['.group_segment_fixed_size']))
         assert k['.private_segment_fixed_size'] == 0, name
         assert k['.vgpr_count'] <= 512, name
+    assert found['icp_accumulate_kernel']['.group_segment_fixed_size'] == 4 * 30 * 8
+    assert found['icp_ct_accumulate_kernel']['.group_segment_fixed_size'] == 4 * 93 * 8
 
 
 # ---- 5. configuration and refusals ----------------------------------------------------------------------------------------------------
