@@ -234,6 +234,12 @@ _SIGNATURES = {
     'dc_planereg_blocks': (_i64, [_i64]),
     'dc_planereg_count': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _vp, _vp]),
     'dc_planereg_fill': (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    # surface reconstruction (csrc/dc_tsdf.hip)
+    'dc_tsdf_integrate': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _i32, _i32, _f64, _i32, _f64, _f64, _f64,
+                                 _vp, _vp, _vp, _vp]),
+    'dc_tsdf_extract_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'dc_tsdf_extract_count': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'dc_tsdf_extract_fill': (_i32, [_vp, _vp, _f64, _f64, _f64, _f64, _i32, _i32, _i32, _i32, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
 }
 
 

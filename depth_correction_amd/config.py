@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['bias_eval_csv', 'CLOUD_LOSS_DEFAULTS', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'SLAM', 'nonempty',
+__all__ = ['bias_eval_csv', 'CLOUD_LOSS_DEFAULTS', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'recon_eval_csv', 'SLAM', 'nonempty',
            'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
@@ -103,6 +103,14 @@ def bias_eval_csv(log_dir: str, subset: str = None):
 def map_eval_csv(log_dir: str, subset: str = None):
     """CSV file eval_map_all appends to for one subset (named as slam_eval_csv names its files; not in the reference)."""
     path = 'map_eval_{subset}.csv'.format(subset=subset) if subset else 'map_eval.csv'
+    if log_dir:
+        path = os.path.join(log_dir, path)
+    return path
+
+
+def recon_eval_csv(log_dir: str, subset: str = None):
+    """CSV file eval_recon_all appends to for one subset (named as map_eval_csv names its files; not in the reference)."""
+    path = 'recon_eval_{subset}.csv'.format(subset=subset) if subset else 'recon_eval.csv'
     if log_dir:
         path = os.path.join(log_dir, path)
     return path
@@ -280,6 +288,23 @@ class Config(object):
         self.map_eval_register_init = None
         self.register_global_kwargs = {}
         self.register_planes_kwargs = {}
+        # surface reconstruction (eval.eval_recon, DESIGN "Surface reconstruction"; not in the reference's Config): the scans are fused
+        # into a TSDF volume of recon_voxel_size metres truncated at recon_trunc (None: 3 voxels) inside recon_bounds ((lo, hi), None:
+        # the box of the posed points); rays beyond recon_max_range are left out; recon_carve_from >= 0 also records the free space
+        # from that range on; a voxel seen fewer than recon_min_count times is unobserved.  recon_poses 'dataset' or 'slam' as
+        # map_eval_poses.  eval_recon appends to recon_eval_csv and writes the mesh to recon_mesh_ply when set; the accuracy is taken
+        # on recon_eval_samples samples of either mesh, the coverage within recon_eval_max_dist (None: not computed)
+        self.recon_voxel_size = 0.1
+        self.recon_trunc = None
+        self.recon_min_count = 1
+        self.recon_max_range = None
+        self.recon_carve_from = None
+        self.recon_bounds = None
+        self.recon_poses = 'dataset'
+        self.recon_eval_csv = None
+        self.recon_mesh_ply = None
+        self.recon_eval_samples = 100000
+        self.recon_eval_max_dist = None
         # depth bias against the ground-truth mesh (eval.eval_bias, DESIGN "Depth bias against the mesh"; not in the reference's
         # Config): eval_bias appends a line per sequence to bias_eval_csv and writes the per-bin table to bias_eval_curve_csv; bins of
         # the true incidence angle over [0, pi/2]; rays with |d - t| above bias_eval_max_residual (metres) are left out; back-face

@@ -1,6 +1,7 @@
 // TEST-ONLY host build of the per-point math the kernels use (dc_eig3.h, dc_pointmath.h).
 // Lets the CPU test-suite pin the eigen-solver and the covariance / loss / backward-coefficient
 // arithmetic against LAPACK and the oracle without a GPU.  Never loaded by depth_correction_amd.
+#include <vector>
 #include "dc_common.h"
 #include "dc_bvh.h"
 #include "dc_eig3.h"
@@ -21,6 +22,7 @@
 #include "dc_align_math.h"
 #include "dc_globalreg_math.h"
 #include "dc_planereg_math.h"
+#include "dc_tsdf_math.h"
 #include "dc_cons_route.h"
 
 // The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
@@ -845,6 +847,69 @@ int dc_host_planereg_pair(const double* na, const double* nb, const double* nc, 
                           double min_det, double tol_dot, double* T) {
   if (!dc::preg_check(na, nb, nc, mi, mj, mk, s, min_det, tol_dot)) return 0;
   return dc::preg_fit(na, nb, nc, mi, mj, mk, s, T);
+}
+
+// ---- surface reconstruction (dc_tsdf_math.h; dc_tsdf.hip) ----
+// dc_tsdf_integrate over a list of rays into host arrays, ray after ray: vps / dirs [n,3], depth [n] of `dtype`, mask uint8 [n] or null,
+// pose [16] or null, og [3]; sum int64 [V], count int32 [V] and stats int64 [4] are added to.  Returns the kernels' status.
+int dc_host_tsdf_integrate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask, const double* pose,
+                           const double* og, double voxel, int nx, int ny, int nz, double trunc, int k_steps, double min_depth,
+                           double max_range, double carve_from, int64_t* sum, int32_t* count, int64_t* stats) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {nx, ny, nz}};
+  const dc::TsdfRule r{trunc, voxel / 2.0, min_depth, max_range, carve_from, k_steps};
+  if (!dc::tsdf_grid_ok(g) || !dc::tsdf_rule_ok(r) || n < 0) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  dc::TsdfTally t{0, 0, 0, 0};
+  for (int64_t i = 0; i < n; ++i) {
+    double vp[3], dir[3], d;
+    for (int a = 0; a < 3; ++a) {
+      vp[a] = dtype == DC_F32 ? (double)((const float*)vps)[3 * i + a] : ((const double*)vps)[3 * i + a];
+      dir[a] = dtype == DC_F32 ? (double)((const float*)dirs)[3 * i + a] : ((const double*)dirs)[3 * i + a];
+    }
+    d = dtype == DC_F32 ? (double)((const float*)depth)[i] : ((const double*)depth)[i];
+    dc::tsdf_ray(vp, dir, d, mask ? mask[i] != 0 : true, pose, g, r, &t, [&](int64_t v, int64_t q) { sum[v] += q; count[v] += 1; });
+  }
+  stats[0] += t.used; stats[1] += t.skipped; stats[2] += t.outside; stats[3] += t.visits;
+  return DC_OK;
+}
+
+// dc_tsdf_extract_count + _fill on host arrays, done sequentially: totals [2] <- {vertices, faces}; the first cap_v vertices go to
+// vertices [cap_v,3] and the first cap_f faces to faces [cap_f,3] (either may be null).  Returns the kernels' status.
+int dc_host_tsdf_extract(const int64_t* sum, const int32_t* count, const double* og, double voxel, int nx, int ny, int nz, int min_count,
+                         int64_t cap_v, int64_t cap_f, double* vertices, int32_t* faces, int64_t* totals) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {nx, ny, nz}};
+  if (!dc::tsdf_grid_ok(g) || min_count < 1) return DC_ERR_ARG;
+  const int64_t n_cells = dc::tsdf_cell_count(nx, ny, nz);
+  std::vector<int32_t> id((size_t)n_cells, -1);
+  int64_t nv = 0, nf = 0;
+  for (int x = 0; x < nx - 1; ++x)
+    for (int y = 0; y < ny - 1; ++y)
+      for (int z = 0; z < nz - 1; ++z) {
+        int64_t corner[8];
+        int bits;
+        if (!dc::tsdf_cell_active(sum, count, g, min_count, x, y, z, corner, &bits)) continue;
+        if (vertices && nv < cap_v) dc::tsdf_cell_vertex(sum, count, g, x, y, z, corner, bits, vertices + 3 * nv);
+        id[(size_t)dc::tsdf_cell_index(g, x, y, z)] = (int32_t)nv++;
+      }
+  for (int x = 0; x < nx; ++x)
+    for (int y = 0; y < ny; ++y)
+      for (int z = 0; z < nz; ++z)
+        for (int e = 0; e < 3; ++e) {
+          bool in;
+          int64_t cells[4];
+          if (!dc::tsdf_edge_crosses(sum, count, g, min_count, x, y, z, e, &in) || !dc::tsdf_edge_cells(g, x, y, z, e, cells)) continue;
+          const int32_t q[4] = {id[(size_t)cells[in ? 0 : 3]], id[(size_t)cells[in ? 1 : 2]], id[(size_t)cells[in ? 2 : 1]], id[(size_t)cells[in ? 3 : 0]]};
+          if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) continue;
+          if (faces && nf + 1 < cap_f) {
+            int32_t* o = faces + 3 * nf;
+            o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+            o[3] = q[0]; o[4] = q[2]; o[5] = q[3];
+          }
+          nf += 2;
+        }
+  totals[0] = nv;
+  totals[1] = nf;
+  return DC_OK;
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ offsets / distance weights, any of the reference's models or none) every sequenc
 localization-accuracy evaluation (eval.py:214-290) with this package's ICP mapper instead of ROS (slam.py); ``eval_map`` /
 ``eval_map_all`` the accuracy of the map against the ground-truth mesh (scripts/mapping_accuracy:82-118); ``eval_bias`` /
 ``eval_bias_all`` the depth error of every ray against the mesh over the true incidence angle and the supervised fit
-(scripts/bias_estimation, depth_bias.py).  ``landscape_clouds`` evaluates
+(scripts/bias_estimation, depth_bias.py); ``eval_recon`` / ``eval_recon_all`` the surface fused from the corrected scans against
+the ground-truth mesh (what scripts/reconstruction_eval is named after).  ``landscape_clouds`` evaluates
 the loss for many candidate weights of the model at once: every model with a basis form is affine in its weights, so a
 neighbourhood's covariance is a quadratic form in w and one pass over the neighbours (dc_sequence_landscape) serves every
 row; configurations outside that path loop over ``eval_loss_clouds`` ("Loss landscape").
@@ -23,14 +24,14 @@ from collections import Counter
 import numpy as np
 import torch
 
-from .config import SLAM, Config, NeighborhoodType, PoseCorrection, bias_eval_csv, loss_eval_csv, map_eval_csv, nonempty, slam_eval_csv
+from .config import SLAM, Config, NeighborhoodType, PoseCorrection, bias_eval_csv, loss_eval_csv, map_eval_csv, nonempty, recon_eval_csv, slam_eval_csv
 from .depth_cloud import DepthCloud
 from .plan import PlanRegistry, SequencePlan, consistency_loss
 from .preproc import (compute_neighborhood_features, global_cloud, global_cloud_mask, local_feature_cloud,
                       offset_cloud)
 from .transform import corrected_poses, xyz_axis_angle_to_matrix
 
-__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_bias', 'eval_bias_all', 'eval_loss_landscape', 'eval_map', 'eval_map_all', 'eval_slam', 'eval_slam_all',
+__all__ = ['create_corrected_poses', 'eval_loss', 'eval_loss_all', 'eval_loss_clouds', 'eval_bias', 'eval_bias_all', 'eval_loss_landscape', 'eval_map', 'eval_map_all', 'eval_recon', 'eval_recon_all', 'eval_slam', 'eval_slam_all',
            'initialize_pose_corrections', 'fused_supported', 'landscape_clouds', 'landscape_paths', 'PlanCloud', 'LazyFeatureCloud']
 
 
@@ -509,6 +510,69 @@ def eval_map_all(cfg: Config):
         eval_cfg.test_poses_path = []
         eval_cfg.map_eval_csv = map_eval_csv(cfg.log_dir, suffix)
         out[suffix] = eval_map(cfg=eval_cfg)
+    return out
+
+
+# ---- surface reconstruction against the ground-truth mesh --------------------------------------------------------------------------
+RECON_EVAL_FIELDS = ('mean', 'rms', 'median', 'trimmed_mean')
+
+
+def eval_recon(cfg: Config, test_datasets=None, model=None):
+    """The surface fused from every test sequence against its dataset's mesh: each scan goes through the depth filter and the
+    correction by ``model`` (from the configuration unless given) -- slam.mapper_input without the grid filter, a fusion wants all rays
+    -- and is moved by its pose (``cfg.recon_poses`` 'dataset' or 'slam', as eval_map's); reconstruction.reconstruct fuses them at
+    cfg.recon_voxel_size and extracts the mesh; metrics.reconstruction_accuracy holds it against get_mesh().  Appends ``name vertices
+    faces accuracy(mean rms median trimmed_mean) completeness(mean rms median trimmed_mean) coverage`` to ``cfg.recon_eval_csv`` and
+    writes the mesh to ``cfg.recon_mesh_ply`` when set; returns the per-sequence dicts (with 'mesh' and 'volume')."""
+    from .io import append
+    from .metrics import reconstruction_accuracy
+    from .reconstruction import reconstruct
+    from .slam import mapper_input, run_slam
+    if cfg.recon_poses not in ('dataset', 'slam'):
+        raise ValueError("recon_poses must be 'dataset' or 'slam', got %r" % (cfg.recon_poses,))
+    test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
+    all_rays = cfg.copy()
+    all_rays.grid_res = 0.0
+    results = []
+    for name, ds in zip(test_names, test_datasets):
+        gt = _dataset_mesh(ds, name, who='eval_recon')
+        items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in ds]
+        poses = run_slam(ds, model, cfg)['slam'] if cfg.recon_poses == 'slam' else [pose for _, pose in items]
+        scans = [mapper_input(cloud, model, all_rays) for cloud, _ in items]
+        mesh, volume = reconstruct(scans, poses, cfg.recon_voxel_size, trunc=cfg.recon_trunc, bounds=cfg.recon_bounds,
+                                   min_count=cfg.recon_min_count, max_range=cfg.recon_max_range, carve_from=cfg.recon_carve_from,
+                                   device=cfg.device)
+        res = reconstruction_accuracy(mesh, gt, n_samples=cfg.recon_eval_samples, seed=cfg.random_seed,
+                                      inlier_ratio=cfg.map_eval_inlier_ratio, max_dist=cfg.recon_eval_max_dist)
+        res.update(name=name, mesh=mesh, volume=volume, stats=volume.stats())
+        acc, com = res['accuracy'], res['completeness']
+        print('Reconstruction of %s: %d vertices, %d faces; accuracy mean %.6f m, rms %.6f m; completeness mean %.6f m, rms %.6f m; '
+              'coverage %.4f.' % (name, mesh.vertices.shape[0], len(mesh), acc['mean'], acc['rms'], com['mean'], com['rms'], res['coverage']))
+        if cfg.recon_mesh_ply:
+            mesh.save_ply(cfg.recon_mesh_ply)
+        if cfg.recon_eval_csv:
+            append(cfg.recon_eval_csv, '%s %d %d %s %s %.9f\n' % (name, mesh.vertices.shape[0], len(mesh),
+                                                                 ' '.join('%.9f' % acc[f] for f in RECON_EVAL_FIELDS),
+                                                                 ' '.join('%.9f' % com[f] for f in RECON_EVAL_FIELDS), res['coverage']))
+        results.append(res)
+    return results
+
+
+def eval_recon_all(cfg: Config):
+    """eval_recon on the train, val and test subsets with the poses the datasets yield, one CSV file per subset (the shape of
+    eval_map_all)."""
+    out = {}
+    for names, suffix in zip([cfg.train_names, cfg.val_names, cfg.test_names], ['train', 'val', 'test']):
+        if not names:
+            continue
+        eval_cfg = cfg.copy()
+        eval_cfg.test_names = names
+        eval_cfg.train_poses_path = []
+        eval_cfg.val_poses_path = []
+        eval_cfg.test_poses_path = []
+        eval_cfg.recon_eval_csv = recon_eval_csv(cfg.log_dir, suffix)
+        eval_cfg.recon_mesh_ply = None
+        out[suffix] = eval_recon(cfg=eval_cfg)
     return out
 
 

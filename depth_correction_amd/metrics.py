@@ -23,7 +23,7 @@ import torch
 from . import ops
 
 __all__ = ['bias_statistics', 'chamfer_distance', 'depth_bias', 'fit_bias', 'fitted_model', 'map_accuracy', 'map_statistics',
-           'point_to_cloud_distance', 'point_to_mesh_distance']
+           'point_to_cloud_distance', 'point_to_mesh_distance', 'reconstruction_accuracy']
 
 BIAS_TOTALS, BIAS_BIN_COLS = 5, 9                    # include/dc_hip.h: DC_BIAS_TOTALS, DC_BIAS_BIN_COLS
 BIAS_TOTAL_NAMES = ('rays', 'masked', 'hits', 'used', 'beyond_gate')
@@ -153,6 +153,24 @@ def map_accuracy(points, mesh, inlier_ratio=0.8, n_samples=None, seed=135):
 
 
 # ---- depth bias against the mesh -------------------------------------------------------------------------------------------------
+def reconstruction_accuracy(mesh, gt_mesh, n_samples=100000, seed=135, inlier_ratio=0.8, max_dist=None):
+    """Quality of a reconstructed ``mesh`` against the ground-truth ``gt_mesh`` (both mesh.TriangleMesh; what the reference's
+    scripts/reconstruction_eval is named after): dict(accuracy=map_statistics of the distances from mesh.sample(n_samples, seed) to
+    gt_mesh -- how far the reconstruction is from the truth --, completeness=map_statistics of the distances from
+    gt_mesh.sample(n_samples, seed) to mesh -- how far the truth is from the reconstruction --, coverage=the share of the
+    ground-truth samples within ``max_dist`` of the reconstruction (None: NaN)).  Every distance is point_to_mesh_distance's, without
+    a cut-off, so that a far sample weighs on the mean instead of leaving it."""
+    quantile = lambda v, r: ops.quantile(v.contiguous(), r)
+    ours = mesh.sample(int(n_samples), seed=seed)[0]                 # (on the current GPU; without one: "no CPU path")
+    truth = gt_mesh.sample(int(n_samples), seed=seed)[0]
+    to_truth = point_to_mesh_distance(ours, gt_mesh)
+    to_ours = point_to_mesh_distance(truth, mesh)
+    out = dict(accuracy=map_statistics(to_truth, None, inlier_ratio, quantile=quantile),
+               completeness=map_statistics(to_ours, None, inlier_ratio, quantile=quantile))
+    out['coverage'] = float((to_ours <= float(max_dist)).to(torch.float64).mean()) if max_dist is not None else float('nan')
+    return out
+
+
 def _bias_system_len(p):
     return 2 + p + p * (p + 1) // 2
 

@@ -21,7 +21,7 @@ __all__ = [
     'KnnGrid', 'knn_grid_build', 'knn_grid_query', 'quantile', 'icp_blocks', 'icp_init', 'icp_accumulate', 'icp_finish', 'map_select',
     'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
     'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
-    'planereg_hypotheses', 'planereg_select',
+    'planereg_hypotheses', 'planereg_select', 'tsdf_k_steps', 'tsdf_integrate', 'tsdf_extract',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -2406,3 +2406,89 @@ def image_shadow_mask(points, vps, dirs, pixel, index_image, grid, window, r, lo
                                      ptr(count), rows, cols, wrap, int(window[0]), int(window[1]), float(r), float(lo), float(hi), ptr(mask),
                                      stream_ptr()), 'dc_image_shadow_mask')
     return mask
+
+
+# ------------------------------------------------------------------------------------------------
+# surface reconstruction: TSDF fusion and surface-nets extraction (csrc/dc_tsdf.hip, reconstruction.TsdfVolume)
+# ------------------------------------------------------------------------------------------------
+def tsdf_k_steps(trunc, voxel):
+    """K = ceil(trunc / h) with h = voxel / 2: the samples a ray takes on either side of its end point."""
+    return int(math.ceil(float(trunc) / (float(voxel) / 2.0)))
+
+
+def _tsdf_volume_args(sum_, count, origin, voxel, who):
+    need(sum_, (None, None, None), dtype=torch.int64, name='sum')
+    dev, dims = sum_.device, tuple(sum_.shape)
+    need(count, dims, dtype=torch.int32, name='count', device=dev)
+    origin = tuple(float(v) for v in origin)
+    voxel = float(voxel)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+        raise ValueError('%s needs a finite origin of 3 values, got %r' % (who, origin))
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('%s needs a voxel size > 0, got %r' % (who, voxel))
+    if min(dims) < 2 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError('%s needs dims >= 2 with fewer than 2^31 voxels, got %r' % (who, dims))
+    return dev, dims, origin, voxel
+
+
+@on_device
+def tsdf_integrate(sum_, count, stats, origin, voxel, trunc, vps, dirs, depth, pose=None, mask=None, min_depth=0., max_range=None,
+                   carve_from=None):
+    """Adds the rays (vps [n,3] or [1,3], dirs [n,3], depth [n] or [n,1]; f32 or f64, sensor frame) of one scan to the volume sum i64 /
+    count i32 [nx,ny,nz] with the minimum corner ``origin`` and the voxel size ``voxel``, truncated at ``trunc`` (dc_tsdf_integrate; the
+    rule: csrc/dc_tsdf_math.h).  pose f64 device [4,4] (world from sensor) or None; mask bool / uint8 [n] or None; rays at or below
+    ``min_depth`` or beyond ``max_range`` are skipped; ``carve_from`` >= 0 also samples the free space from that range on.  stats i64
+    device [4] += {rays used, rays skipped, samples outside the grid, visits}.  In place; nothing is read back."""
+    dev, dims, origin, voxel = _tsdf_volume_args(sum_, count, origin, voxel, 'tsdf_integrate')
+    need(stats, (4,), dtype=torch.int64, name='stats', device=dev)
+    trunc = float(trunc)
+    if not (trunc > 0.0 and math.isfinite(trunc)):
+        raise ValueError('tsdf_integrate needs a truncation > 0, got %r' % trunc)
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n, dt = dirs.shape[0], dirs.dtype
+    code = dtype_code(dirs)
+    vps = vps.reshape(-1, 3)
+    if vps.shape[0] == 1 and n != 1:
+        vps = vps.expand(n, 3).contiguous()
+    need(vps, (n, 3), dtype=dt, name='vps', device=dev)
+    depth = depth.reshape(-1)
+    need(depth, (n,), dtype=dt, name='depth', device=dev)
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
+        need(mask, (n,), name='mask', device=dev)
+    if pose is not None:
+        need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    min_depth = float(min_depth)
+    max_range = math.inf if max_range is None else float(max_range)
+    carve_from = -1.0 if carve_from is None else float(carve_from)
+    if math.isnan(min_depth) or math.isnan(max_range) or math.isnan(carve_from) or (carve_from < 0.0 and carve_from != -1.0):
+        raise ValueError('tsdf_integrate needs min_depth and max_range that are numbers and carve_from >= 0 or None')
+    check(lib().dc_tsdf_integrate(ptr(vps), ptr(dirs), ptr(depth), code, n, ptr(mask), ptr(pose), *origin, voxel, *dims, trunc,
+                                  tsdf_k_steps(trunc, voxel), min_depth, max_range, carve_from, ptr(sum_), ptr(count), ptr(stats), stream_ptr()),
+          'dc_tsdf_integrate')
+
+
+@on_device
+def tsdf_extract(sum_, count, origin, voxel, min_count=1, ws=None):
+    """(vertices f64 [Nv,3], faces i32 [Nf,3]): the surface nets of the volume sum i64 / count i32 [nx,ny,nz] on the lattice of voxel
+    centres, vertices in ascending cell index and faces in ascending (lattice point, axis), normals to the free side
+    (dc_tsdf_extract_count, the library's scans, dc_tsdf_extract_fill).  ONE host read: the two totals, which size the outputs."""
+    dev, dims, origin, voxel = _tsdf_volume_args(sum_, count, origin, voxel, 'tsdf_extract')
+    min_count = int(min_count)
+    if min_count < 1:
+        raise ValueError('tsdf_extract needs min_count >= 1, got %d' % min_count)
+    nbytes = int(lib().dc_tsdf_extract_workspace_bytes(*dims))
+    if nbytes == 0:
+        raise ValueError('tsdf_extract takes volumes of fewer than 2^31 / 3 voxels, got %r' % (dims,))
+    ws = _ws_arg(ws, nbytes, dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    check(lib().dc_tsdf_extract_count(ptr(sum_), ptr(count), *dims, min_count, ptr(totals), ptr(ws), ws.shape[0], stream_ptr()),
+          'dc_tsdf_extract_count')
+    n_vertices, n_faces = totals.tolist()
+    vertices = torch.empty((n_vertices, 3), dtype=torch.float64, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    check(lib().dc_tsdf_extract_fill(ptr(sum_), ptr(count), *origin, voxel, *dims, min_count, ptr(ws), ws.shape[0], n_vertices, n_faces,
+                                     ptr(vertices), ptr(faces), stream_ptr()), 'dc_tsdf_extract_fill')
+    return vertices, faces

@@ -1339,6 +1339,42 @@ int dc_planereg_fill(const double* cloud_planes, const int64_t* support, int n_c
                      double cos_tol, double tol_d, const int64_t* offsets, int64_t n_valid, int64_t* h_out, double* T_out,
                      int64_t* score_out, dcStream_t stream);
 
+/* ---- surface reconstruction: TSDF fusion of scans and surface-nets extraction (depth_correction_amd/csrc/dc_tsdf.hip, dc_tsdf_math.h;
+ * DESIGN "Surface reconstruction").  The volume has the minimum corner (ox, oy, oz), the voxel size `voxel` > 0 and the dims (nx, ny, nz),
+ * each >= 2 with nx ny nz < 2^31 (DC_ERR_ARG otherwise); voxel (ix, iy, iz) has the linear index (ix ny + iy) nz + iz and the centre
+ * origin + (i + 0.5) voxel.  sum int64 [V] and count int32 [V] (DEVICE) are its accumulators: a voxel's value is sum / (count 2^20), it is
+ * observed iff count >= min_count and inside iff sum < 0.  All arithmetic is fp64 without fused multiply-adds, the sums are integers:
+ * the same inputs give the same bits in any ray order, and the host build of dc_tsdf_math.h gives the same bits again. ---- */
+/* Adds n rays of one scan.  vps, dirs [n,3] and depth [n] (`dtype` DC_F32 / DC_F64, widened exactly) are in the sensor frame; pose (DEVICE
+ * double [16], row-major, world from sensor, or NULL) gives o = R vp + t and u = R dir, the row sums left to right.  mask uint8 [n] or
+ * NULL.  A ray is skipped (stats[1]) when its mask is 0, when any of o, u, depth is not finite, when depth <= min_depth or depth >
+ * max_range (+inf: no limit); else it is used (stats[0]).  With h = voxel / 2 it is sampled at t = depth + k h for k = -k_steps ..
+ * k_steps (k_steps = ceil(trunc / h), formed by the caller), or, with carve_from >= 0, from k = -max(k_steps, floor((depth - carve_from)
+ * / h)); samples with t <= 0 are dropped, samples outside the grid counted in stats[2], and a sample in the voxel of the ray's last
+ * in-grid sample dropped.  With the voxel's centre c, s = depth - u.(c - o): s < -trunc adds nothing, else sum += llrint(min(s, trunc) /
+ * trunc 2^20) (ties to even), count += 1, stats[3] += 1.  stats int64 [4] (DEVICE) is added to, not cleared.  Two integer atomics per
+ * visit, no floating-point atomic; no allocation, copy or synchronisation. */
+int dc_tsdf_integrate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask, const double* pose,
+                      double ox, double oy, double oz, double voxel, int nx, int ny, int nz, double trunc, int k_steps, double min_depth,
+                      double max_range, double carve_from, int64_t* sum, int32_t* count, int64_t* stats, dcStream_t stream);
+/* Surface nets on the lattice of voxel centres.  Cell (x, y, z), 0 <= x < nx - 1 and so on, linear index (x (ny - 1) + y) (nz - 1) + z, has
+ * the corners c = bx + 2 by + 4 bz; it is active iff all eight are observed and their inside flags are not all equal.  Its vertex is origin
+ * + ((x, y, z) + 0.5 + the mean of its edge crossings) voxel, the crossings r = f_a / (f_a - f_b) taken over the edges (0,1) (0,2) (0,4)
+ * (1,3) (1,5) (2,3) (2,6) (3,7) (4,5) (4,6) (5,7) (6,7) in this order; vertices come in ascending cell index.  Every lattice edge q -> q + e
+ * (ascending (index of q, e)) that is in range, has two observed ends with different flags and four active cells around it (q offset by
+ * (-1,-1), (0,-1), (0,0), (-1,0) along the axes (e+1) % 3, (e+2) % 3) emits the quad of their vertices, in this order if q is inside and
+ * reversed otherwise, as the faces (q0, q1, q2) and (q0, q2, q3): normals point to the free side.
+ * dc_tsdf_extract_count fills the workspace (dc_tsdf_extract_workspace_bytes; 0 for dims it refuses) and totals (DEVICE int64 [2]) <-
+ * {vertices, faces}: the caller's one host read.  dc_tsdf_extract_fill then writes vertices double [n_vertices,3] and faces int32
+ * [n_faces,3] from the same volume and workspace; a row that would fall outside them is not written.  Volumes of 2^31 / 3 voxels or more
+ * return DC_ERR_UNSUPPORTED (the 32-bit scans). */
+size_t dc_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int dc_tsdf_extract_count(const int64_t* sum, const int32_t* count, int nx, int ny, int nz, int min_count, int64_t* totals, void* ws,
+                          size_t ws_bytes, dcStream_t stream);
+int dc_tsdf_extract_fill(const int64_t* sum, const int32_t* count, double ox, double oy, double oz, double voxel, int nx, int ny, int nz,
+                         int min_count, const void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_faces, double* vertices, int32_t* faces,
+                         dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
