@@ -364,7 +364,7 @@ static int icp_pair_impl(bool plane, const void* vpsA, const void* dirsA, const 
   (void)want_exponent_grad; (void)want_pose_grad;      // always produced: the kernel is tiny next to the k-NN set-up
   if (!dirsA || !depthA || !dirsB || !depthB || (plane && (!normalsA || !normalsB))) return DC_ERR_ARG;
   if (!plane) normalsA = normalsB = nullptr;
-  if (!poseA || !poseB || !idxA || !idxB || m < 0 || !partials_ws || !out) return DC_ERR_ARG;
+  if (!poseA || !poseB || m < 0 || (m > 0 && (!idxA || !idxB)) || !partials_ws || !out) return DC_ERR_ARG;      // (no correspondence: no index arrays)
   if (model_kind < DC_MODEL_NONE || model_kind > DC_MODEL_LAST) return DC_ERR_ARG;
   if (model_kind != DC_MODEL_NONE && (n_terms < 1 || n_terms > DC_MAX_MODEL_TERMS || !incA || !incB || !w || !e)) return DC_ERR_ARG;
   if (model_kind == DC_MODEL_NONE) n_terms = 0;

@@ -421,7 +421,7 @@ int dc_correct_depth(const void* depth, const void* gamma, const uint8_t* mask, 
  * the distances are formed (loss.py:436-437).  Forward and backward are one kernel:
  *   out fp64 [2 + 2 P + 24] = { sum |nA.(xB-xA)| |nA|, sum |nB.(xA-xB)| |nB|,
  *                               d(sum12+sum21)/dw [P], /dexponent [P], /d[R|t]_A [12], /d[R|t]_B [12] }.
- * partials_ws: fp64 [dc_p2plane_partial_count(m)]. */
+ * partials_ws: fp64 [dc_p2plane_partial_count(m)].  m == 0: out is all zeros, idxA / idxB may be NULL. */
 int64_t dc_p2plane_partial_count(int64_t m);
 int dc_p2plane_pair(const void* vpsA, const void* dirsA, const void* depthA, const void* incA, const uint8_t* lmaskA,
                     const void* normalsA, const void* vpsB, const void* dirsB, const void* depthB, const void* incB,
