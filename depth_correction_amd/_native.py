@@ -240,6 +240,15 @@ _SIGNATURES = {
     'dc_tsdf_extract_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'dc_tsdf_extract_count': (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     'dc_tsdf_extract_fill': (_i32, [_vp, _vp, _f64, _f64, _f64, _f64, _i32, _i32, _i32, _i32, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
+    # sparse TSDF volumes (csrc/dc_tsdf_sparse.hip)
+    'dc_tsdf_sparse_workspace_bytes': (_sz, [_i64, _i32, _i64]),
+    'dc_tsdf_sparse_allocate': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _f64, _f64, _i64, _vp, _vp, _vp,
+                                       _vp, _vp, _sz, _vp]),
+    'dc_tsdf_sparse_integrate': (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _f64, _f64, _i64, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp]),
+    'dc_tsdf_sparse_extract_workspace_bytes': (_sz, [_i64]),
+    'dc_tsdf_sparse_extract_count': (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    'dc_tsdf_sparse_extract_fill': (_i32, [_vp, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
 }
 
 

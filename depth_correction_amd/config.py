@@ -300,6 +300,7 @@ class Config(object):
         self.recon_max_range = None
         self.recon_carve_from = None
         self.recon_bounds = None
+        self.recon_sparse = False                # a block-allocated SparseTsdfVolume instead of the dense box (no bounds, no carving)
         self.recon_poses = 'dataset'
         self.recon_eval_csv = None
         self.recon_mesh_ply = None

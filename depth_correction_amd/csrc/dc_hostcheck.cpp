@@ -1,6 +1,7 @@
 // TEST-ONLY host build of the per-point math the kernels use (dc_eig3.h, dc_pointmath.h).
 // Lets the CPU test-suite pin the eigen-solver and the covariance / loss / backward-coefficient
 // arithmetic against LAPACK and the oracle without a GPU.  Never loaded by depth_correction_amd.
+#include <algorithm>
 #include <vector>
 #include "dc_common.h"
 #include "dc_bvh.h"
@@ -23,6 +24,7 @@
 #include "dc_globalreg_math.h"
 #include "dc_planereg_math.h"
 #include "dc_tsdf_math.h"
+#include "dc_tsdf_sparse_math.h"
 #include "dc_cons_route.h"
 
 // The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
@@ -907,6 +909,151 @@ int dc_host_tsdf_extract(const int64_t* sum, const int32_t* count, const double*
           }
           nf += 2;
         }
+  totals[0] = nv;
+  totals[1] = nf;
+  return DC_OK;
+}
+
+// ---- sparse TSDF volumes (dc_tsdf_sparse_math.h; dc_tsdf_sparse.hip) ----
+namespace {
+struct HostRays {
+  const void *vps, *dirs, *depth;
+  int dtype;
+  const uint8_t* mask;
+  void load(int64_t i, double* vp, double* dir, double* d, bool* in) const {
+    for (int a = 0; a < 3; ++a) {
+      vp[a] = dtype == DC_F32 ? (double)((const float*)vps)[3 * i + a] : ((const double*)vps)[3 * i + a];
+      dir[a] = dtype == DC_F32 ? (double)((const float*)dirs)[3 * i + a] : ((const double*)dirs)[3 * i + a];
+    }
+    *d = dtype == DC_F32 ? (double)((const float*)depth)[i] : ((const double*)depth)[i];
+    *in = mask ? mask[i] != 0 : true;
+  }
+};
+bool host_sparse_rule(const double* og, double voxel, double trunc, int k_steps, double min_depth, double max_range, int64_t capacity,
+                      dc::TsdfGrid* g, dc::TsdfRule* r) {
+  *g = dc::TsdfGrid{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  *r = dc::TsdfRule{trunc, voxel / 2.0, min_depth, max_range, -1.0, k_steps};
+  return dc::tsdf_lattice_ok(*g) && dc::tsdf_rule_ok(*r) && capacity >= 1 && capacity < ((int64_t)1 << 22);
+}
+}  // namespace
+
+// dc_tsdf_sparse_allocate on host arrays, ray after ray: keys uint64 [capacity], slots int32 [capacity], n_blocks int64 [1], info int64 [2].
+// max_ray_blocks (or null) <- the most distinct wanted blocks any one ray met, table or not: what the candidate buffer's share must hold.
+int dc_host_tsdf_sparse_allocate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask,
+                                 const double* pose, const double* og, double voxel, double trunc, int k_steps, double min_depth,
+                                 double max_range, int64_t capacity, uint64_t* keys, int32_t* slots, int64_t* n_blocks, int64_t* info,
+                                 int64_t* max_ray_blocks) {
+  dc::TsdfGrid g;
+  dc::TsdfRule r;
+  if (!host_sparse_rule(og, voxel, trunc, k_steps, min_depth, max_range, capacity, &g, &r) || n < 0) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  const int64_t nb = *n_blocks < 0 ? 0 : (*n_blocks > capacity ? capacity : *n_blocks);
+  const HostRays rays{vps, dirs, depth, dtype, mask};
+  std::vector<uint64_t> cand;
+  int64_t most = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    double vp[3], dir[3], d;
+    bool in;
+    rays.load(i, vp, dir, &d, &in);
+    dc::TsdfTally t{0, 0, 0, 0};
+    std::vector<uint64_t> mine;
+    dc::tsdf_ray_walk(vp, dir, d, in, pose, dc::TsdfSparseAddress{g}, r, &t, [&](const dc::TsdfSparseAddress::Voxel& x, int64_t) {
+      const uint64_t key = dc::tsdf_voxel_key(x.i);
+      if (std::find(mine.begin(), mine.end(), key) == mine.end()) mine.push_back(key);
+      if (dc::tsdf_table_find(keys, nb, key) < 0) cand.push_back(key);
+    });
+    most = std::max<int64_t>(most, (int64_t)mine.size());
+  }
+  std::sort(cand.begin(), cand.end());
+  cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+  const int64_t wanted = (int64_t)cand.size(), admitted = std::min<int64_t>(wanted, capacity - nb);
+  std::vector<std::pair<uint64_t, int32_t>> table;
+  for (int64_t t = 0; t < nb; ++t) table.emplace_back(keys[t], slots[t]);
+  for (int64_t t = 0; t < admitted; ++t) table.emplace_back(cand[(size_t)t], (int32_t)(nb + t));
+  std::sort(table.begin(), table.end());
+  for (size_t t = 0; t < table.size(); ++t) { keys[t] = table[t].first; slots[t] = table[t].second; }
+  *n_blocks = nb + admitted;
+  info[0] = nb + admitted;
+  info[1] = wanted - admitted;
+  if (max_ray_blocks) *max_ray_blocks = most;
+  return DC_OK;
+}
+
+// dc_tsdf_sparse_integrate on host arrays: sum int64 [capacity,512], count int32 [capacity,512] and stats int64 [5] are added to.
+int dc_host_tsdf_sparse_integrate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask,
+                                  const double* pose, const double* og, double voxel, double trunc, int k_steps, double min_depth,
+                                  double max_range, int64_t capacity, const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks,
+                                  int64_t* sum, int32_t* count, int64_t* stats) {
+  dc::TsdfGrid g;
+  dc::TsdfRule r;
+  if (!host_sparse_rule(og, voxel, trunc, k_steps, min_depth, max_range, capacity, &g, &r) || n < 0) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  const int64_t nb = *n_blocks < 0 ? 0 : (*n_blocks > capacity ? capacity : *n_blocks);
+  const HostRays rays{vps, dirs, depth, dtype, mask};
+  dc::TsdfTally t{0, 0, 0, 0};
+  int64_t dropped = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    double vp[3], dir[3], d;
+    bool in;
+    rays.load(i, vp, dir, &d, &in);
+    dc::TsdfBlockCache cache{dc::kTsdfNoKey, -1};
+    dc::tsdf_ray_walk(vp, dir, d, in, pose, dc::TsdfSparseAddress{g}, r, &t, [&](const dc::TsdfSparseAddress::Voxel& x, int64_t q) {
+      const int64_t pos = dc::tsdf_cached_find(keys, nb, dc::tsdf_voxel_key(x.i), &cache);
+      const int64_t slot = pos < 0 ? -1 : (int64_t)slots[pos];
+      if (slot < 0 || slot >= capacity) { ++dropped; return; }
+      const int64_t v = slot * dc::kTsdfBlockVoxels + dc::tsdf_voxel_local(x.i);
+      sum[v] += q;
+      count[v] += 1;
+    });
+  }
+  stats[0] += t.used; stats[1] += t.skipped; stats[2] += t.outside; stats[3] += t.visits; stats[4] += dropped;
+  return DC_OK;
+}
+
+// dc_tsdf_sparse_extract_count + _fill on host arrays, block after block in key order; outputs as dc_host_tsdf_extract.
+int dc_host_tsdf_sparse_extract(const uint64_t* keys, const int32_t* slots, int64_t n_blocks, const int64_t* sum, const int32_t* count,
+                                const double* og, double voxel, int min_count, int64_t cap_v, int64_t cap_f, double* vertices, int32_t* faces,
+                                int64_t* totals) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  if (!dc::tsdf_lattice_ok(g) || min_count < 1 || n_blocks < 0) return DC_ERR_ARG;
+  if (n_blocks * dc::kTsdfBlockVoxels * 3 >= ((int64_t)1 << 31)) return DC_ERR_UNSUPPORTED;
+  std::vector<int32_t> nbr((size_t)n_blocks * 27), id((size_t)n_blocks * dc::kTsdfBlockVoxels, -1);
+  for (int64_t t = 0; t < n_blocks * 27; ++t) nbr[(size_t)t] = dc::tsdf_block_neighbour(keys, n_blocks, t / 27, (int)(t % 27));
+  int64_t nv = 0, nf = 0;
+  for (int64_t p = 0; p < n_blocks; ++p) {
+    int b[3];
+    dc::tsdf_block_of_key(keys[p], b);
+    for (int lx = 0; lx < 8; ++lx)
+      for (int ly = 0; ly < 8; ++ly)
+        for (int lz = 0; lz < 8; ++lz) {
+          int64_t corner[8];
+          int bits;
+          if (!dc::tsdf_sparse_cell_active(sum, count, nbr.data() + 27 * p, slots, min_count, lx, ly, lz, corner, &bits)) continue;
+          if (vertices && nv < cap_v)
+            dc::tsdf_cell_vertex(sum, count, g, 8 * b[0] + lx, 8 * b[1] + ly, 8 * b[2] + lz, corner, bits, vertices + 3 * nv);
+          id[(size_t)(p * dc::kTsdfBlockVoxels + (lx * 8 + ly) * 8 + lz)] = (int32_t)nv++;
+        }
+  }
+  for (int64_t p = 0; p < n_blocks; ++p)
+    for (int lx = 0; lx < 8; ++lx)
+      for (int ly = 0; ly < 8; ++ly)
+        for (int lz = 0; lz < 8; ++lz)
+          for (int e = 0; e < 3; ++e) {
+            bool in;
+            int64_t cells[4];
+            const int32_t* nb27 = nbr.data() + 27 * p;
+            if (!dc::tsdf_sparse_edge_crosses(sum, count, nb27, slots, min_count, lx, ly, lz, e, &in) ||
+                !dc::tsdf_sparse_edge_cells(nb27, lx, ly, lz, e, cells))
+              continue;
+            const int32_t q[4] = {id[(size_t)cells[in ? 0 : 3]], id[(size_t)cells[in ? 1 : 2]], id[(size_t)cells[in ? 2 : 1]], id[(size_t)cells[in ? 3 : 0]]};
+            if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) continue;
+            if (faces && nf + 1 < cap_f) {
+              int32_t* o = faces + 3 * nf;
+              o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+              o[3] = q[0]; o[4] = q[2]; o[5] = q[3];
+            }
+            nf += 2;
+          }
   totals[0] = nv;
   totals[1] = nf;
   return DC_OK;

@@ -17,6 +17,11 @@ hipError_t sort_pairs_u64(void* tmp, size_t tmp_bytes, const uint64_t* keys_in, 
 hipError_t sort_pairs_u32(void* tmp, size_t tmp_bytes, const void* keys_in, void* keys_out, const void* vals_in, void* vals_out,
                           size_t n, unsigned bit0, unsigned bit1, hipStream_t stream);
 
+// keys alone, 64 bits wide: bytes of temporary storage for n keys, and the sort by the key bits [bit0, bit1)
+size_t sort_keys_bytes(size_t n);
+hipError_t sort_keys_u64(void* tmp, size_t tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, size_t n, unsigned bit0, unsigned bit1,
+                         hipStream_t stream);
+
 // bytes of temporary storage of the prefix sums over n 32-bit items
 size_t scan_bytes(size_t n);
 // out[i] = in[0] + ... + in[i]  (32-bit integers; wrap-around like the unsigned sum)

@@ -29,6 +29,17 @@ hipError_t sort_pairs_u32(void* tmp, size_t tmp_bytes, const void* keys_in, void
                                    (uint32_t*)vals_out, n, bit0, bit1, stream);
 }
 
+size_t sort_keys_bytes(size_t n) {
+  size_t b = 0;
+  (void)rocprim::radix_sort_keys(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, n > 0 ? n : 1, 0, 64, (hipStream_t)0);
+  return b;
+}
+
+hipError_t sort_keys_u64(void* tmp, size_t tmp_bytes, const uint64_t* keys_in, uint64_t* keys_out, size_t n, unsigned bit0, unsigned bit1,
+                         hipStream_t stream) {
+  return rocprim::radix_sort_keys(tmp, tmp_bytes, keys_in, keys_out, n, bit0, bit1, stream);
+}
+
 size_t scan_bytes(size_t n) {
   size_t a = 0, b = 0;
   const size_t ne = n > 0 ? n : 1;

@@ -55,10 +55,33 @@ DC_HD bool tsdf_rule_ok(const TsdfRule& r) {
 DC_HD int64_t tsdf_index(const TsdfGrid& g, int ix, int iy, int iz) { return ((int64_t)ix * g.n[1] + iy) * g.n[2] + iz; }
 DC_HD double tsdf_centre(const TsdfGrid& g, int axis, int i) { return g.og[axis] + ((double)i + 0.5) * g.a; }
 
-// One ray.  vp, dir [3] and d are the widened inputs, pose a row-major [16] or null; add(v, q) receives every visit.
-template <typename Add>
-DC_HD void tsdf_ray(const double* vp, const double* dir, double d, bool masked_in, const double* pose, const TsdfGrid& g,
-                    const TsdfRule& r, TsdfTally* tally, Add add) {
+// The address policy of the dense volume: what the sample loop (tsdf_ray_walk) asks of a volume.  locate() is the in-range test on the
+// floored doubles and gives the voxel; same() is the identity of the "voxel of the last in-grid sample" rule; centre() the voxel's centre.
+// The sparse volume (dc_tsdf_sparse_math.h) supplies another policy; the loop itself exists once.
+struct TsdfDenseAddress {
+  const TsdfGrid& g;
+  struct Voxel {
+    int i[3];
+    int64_t v;
+  };
+  DC_HD static Voxel none() { return Voxel{{0, 0, 0}, -1}; }
+  DC_HD bool locate(const double* gx, Voxel* out) const {
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) in = in && gx[a] >= 0.0 && gx[a] < (double)g.n[a];
+    if (!in) return false;
+    out->i[0] = (int)gx[0]; out->i[1] = (int)gx[1]; out->i[2] = (int)gx[2];
+    out->v = tsdf_index(g, out->i[0], out->i[1], out->i[2]);
+    return true;
+  }
+  DC_HD static bool same(const Voxel& a, const Voxel& b) { return a.v == b.v; }
+  DC_HD double centre(int axis, const Voxel& x) const { return tsdf_centre(g, axis, x.i[axis]); }
+};
+
+// One ray.  vp, dir [3] and d are the widened inputs, pose a row-major [16] or null; add(voxel, q) receives every visit that adds.
+template <typename Address, typename Add>
+DC_HD void tsdf_ray_walk(const double* vp, const double* dir, double d, bool masked_in, const double* pose, const Address& ad,
+                         const TsdfRule& r, TsdfTally* tally, Add add) {
   double o[3], u[3];
   if (pose) {
 #pragma unroll
@@ -84,33 +107,42 @@ DC_HD void tsdf_ray(const double* vp, const double* dir, double d, bool masked_i
     const int ci = c > 0.0 ? (int)c : 0;
     k_lo = -(r.K > ci ? r.K : ci);
   }
-  int64_t last = -1;
+  typename Address::Voxel last = Address::none();
   for (int k = k_lo; k <= r.K; ++k) {
     const double t = d + (double)k * r.h;
     if (!(t > 0.0)) continue;
     double gx[3];
-    bool in = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const double p = o[a] + t * u[a];
-      gx[a] = floor((p - g.og[a]) / g.a);
-      in = in && gx[a] >= 0.0 && gx[a] < (double)g.n[a];
+      gx[a] = floor((p - ad.g.og[a]) / ad.g.a);
     }
-    if (!in) {
+    typename Address::Voxel x;
+    if (!ad.locate(gx, &x)) {
       tally->outside += 1;
       continue;
     }
-    const int ix = (int)gx[0], iy = (int)gx[1], iz = (int)gx[2];
-    const int64_t v = tsdf_index(g, ix, iy, iz);
-    if (v == last) continue;
-    last = v;
-    const double c0 = tsdf_centre(g, 0, ix), c1 = tsdf_centre(g, 1, iy), c2 = tsdf_centre(g, 2, iz);
+    if (Address::same(x, last)) continue;
+    last = x;
+    const double c0 = ad.centre(0, x), c1 = ad.centre(1, x), c2 = ad.centre(2, x);
     const double s = d - ((u[0] * (c0 - o[0]) + u[1] * (c1 - o[1])) + u[2] * (c2 - o[2]));
     if (!(s >= -r.tau)) continue;
     const double m = s < r.tau ? s : r.tau;
-    add(v, (int64_t)llrint(m / r.tau * kTsdfOne));
+    add(x, (int64_t)llrint(m / r.tau * kTsdfOne));
     tally->visits += 1;
   }
+}
+
+// The dense volume's ray: add(v, q) receives the linear index of every visit that adds.
+template <typename Add>
+struct TsdfDenseAdd {
+  Add add;
+  DC_HD void operator()(const TsdfDenseAddress::Voxel& x, int64_t q) { add(x.v, q); }
+};
+template <typename Add>
+DC_HD void tsdf_ray(const double* vp, const double* dir, double d, bool masked_in, const double* pose, const TsdfGrid& g,
+                    const TsdfRule& r, TsdfTally* tally, Add add) {
+  tsdf_ray_walk(vp, dir, d, masked_in, pose, TsdfDenseAddress{g}, r, tally, TsdfDenseAdd<Add>{add});
 }
 
 // ---- extraction ------------------------------------------------------------------------------------------------------------------

@@ -541,7 +541,7 @@ def eval_recon(cfg: Config, test_datasets=None, model=None):
         scans = [mapper_input(cloud, model, all_rays) for cloud, _ in items]
         mesh, volume = reconstruct(scans, poses, cfg.recon_voxel_size, trunc=cfg.recon_trunc, bounds=cfg.recon_bounds,
                                    min_count=cfg.recon_min_count, max_range=cfg.recon_max_range, carve_from=cfg.recon_carve_from,
-                                   device=cfg.device)
+                                   device=cfg.device, sparse=cfg.recon_sparse)
         res = reconstruction_accuracy(mesh, gt, n_samples=cfg.recon_eval_samples, seed=cfg.random_seed,
                                       inlier_ratio=cfg.map_eval_inlier_ratio, max_dist=cfg.recon_eval_max_dist)
         res.update(name=name, mesh=mesh, volume=volume, stats=volume.stats())

@@ -22,6 +22,7 @@ __all__ = [
     'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
     'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
     'planereg_hypotheses', 'planereg_select', 'tsdf_k_steps', 'tsdf_integrate', 'tsdf_extract',
+    'tsdf_sparse_allocate', 'tsdf_sparse_integrate', 'tsdf_sparse_extract',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -2491,4 +2492,125 @@ def tsdf_extract(sum_, count, origin, voxel, min_count=1, ws=None):
     faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
     check(lib().dc_tsdf_extract_fill(ptr(sum_), ptr(count), *origin, voxel, *dims, min_count, ptr(ws), ws.shape[0], n_vertices, n_faces,
                                      ptr(vertices), ptr(faces), stream_ptr()), 'dc_tsdf_extract_fill')
+    return vertices, faces
+
+
+# ------------------------------------------------------------------------------------------------
+# sparse TSDF volumes: block-allocated fusion and extraction (csrc/dc_tsdf_sparse.hip, reconstruction.SparseTsdfVolume)
+# ------------------------------------------------------------------------------------------------
+TSDF_BLOCK_VOXELS = 512
+TSDF_MAX_BLOCKS = 2 ** 22 - 1
+
+
+def _tsdf_sparse_table(keys, slots, n_blocks, who):
+    """The device and capacity of the table keys i64 [capacity] (the 63-bit keys, never negative), slots i32 [capacity], n_blocks i64 [1]."""
+    need(keys, (None,), dtype=torch.int64, name='keys')
+    dev, capacity = keys.device, keys.shape[0]
+    if not 1 <= capacity <= TSDF_MAX_BLOCKS:
+        raise ValueError('%s needs a table of 1 .. 2^22 - 1 blocks, got %d' % (who, capacity))
+    need(slots, (capacity,), dtype=torch.int32, name='slots', device=dev)
+    if n_blocks is not None:
+        need(n_blocks, (1,), dtype=torch.int64, name='n_blocks', device=dev)
+    return dev, capacity
+
+
+def _tsdf_sparse_rays(who, dev, origin, voxel, trunc, vps, dirs, depth, pose, mask, min_depth, max_range):
+    """The checked ray and rule arguments of dc_tsdf_sparse_allocate / _integrate, in the order of the C calls up to max_range."""
+    origin = tuple(float(v) for v in origin)
+    voxel, trunc = float(voxel), float(trunc)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+        raise ValueError('%s needs a finite origin of 3 values, got %r' % (who, origin))
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('%s needs a voxel size > 0, got %r' % (who, voxel))
+    if not (trunc > 0.0 and math.isfinite(trunc)):
+        raise ValueError('%s needs a truncation > 0, got %r' % (who, trunc))
+    need(dirs, (None, 3), name='dirs', device=dev)
+    n, dt = dirs.shape[0], dirs.dtype
+    code = dtype_code(dirs)
+    vps = vps.reshape(-1, 3)
+    if vps.shape[0] == 1 and n != 1:
+        vps = vps.expand(n, 3).contiguous()
+    need(vps, (n, 3), dtype=dt, name='vps', device=dev)
+    depth = depth.reshape(-1)
+    need(depth, (n,), dtype=dt, name='depth', device=dev)
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
+        need(mask, (n,), name='mask', device=dev)
+    if pose is not None:
+        need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    min_depth = float(min_depth)
+    max_range = math.inf if max_range is None else float(max_range)
+    if math.isnan(min_depth) or math.isnan(max_range):
+        raise ValueError('%s needs min_depth and max_range that are numbers' % who)
+    k = tsdf_k_steps(trunc, voxel)
+    if not 1 <= k <= 2 ** 20:
+        raise ValueError('%s: a truncation of %g at a voxel size of %g takes %d steps, 1 .. 2^20 are supported' % (who, trunc, voxel, k))
+    keep = (vps, dirs, depth, mask, pose)
+    return n, k, keep, (ptr(vps), ptr(dirs), ptr(depth), code, n, ptr(mask), ptr(pose)) + origin + (voxel, trunc, k, min_depth, max_range)
+
+
+@on_device
+def tsdf_sparse_allocate(keys, slots, n_blocks, info, origin, voxel, trunc, vps, dirs, depth, pose=None, mask=None, min_depth=0., max_range=None,
+                         ws=None):
+    """Admits the blocks the rays will add to into the table keys i64 [capacity] / slots i32 [capacity] / n_blocks i64 [1]
+    (dc_tsdf_sparse_allocate; the rule: csrc/dc_tsdf_sparse_math.h): the wanted keys the table lacks, ascending, get the next slots until
+    the capacity; info i64 device [2] <- {n_blocks after the call, blocks wanted but not admitted}.  In place; nothing is read back."""
+    dev, capacity = _tsdf_sparse_table(keys, slots, n_blocks, 'tsdf_sparse_allocate')
+    need(info, (2,), dtype=torch.int64, name='info', device=dev)
+    n, k, keep, args = _tsdf_sparse_rays('tsdf_sparse_allocate', dev, origin, voxel, trunc, vps, dirs, depth, pose, mask, min_depth, max_range)
+    nbytes = int(lib().dc_tsdf_sparse_workspace_bytes(n, k, capacity))
+    if nbytes == 0:
+        raise ValueError('tsdf_sparse_allocate takes fewer than 2^31 / (2 K + 1) rays a call, got %d rays at K = %d' % (n, k))
+    ws = _ws_arg(ws, nbytes, dev)
+    check(lib().dc_tsdf_sparse_allocate(*args, capacity, ptr(keys), ptr(slots), ptr(n_blocks), ptr(info), ptr(ws), ws.shape[0], stream_ptr()),
+          'dc_tsdf_sparse_allocate')
+
+
+@on_device
+def tsdf_sparse_integrate(keys, slots, n_blocks, sum_, count, stats, origin, voxel, trunc, vps, dirs, depth, pose=None, mask=None, min_depth=0.,
+                          max_range=None):
+    """Adds the rays to the pool sum i64 / count i32 [capacity, 512] at the slots of the table (dc_tsdf_sparse_integrate); a visit whose
+    block the table lacks is dropped.  stats i64 device [5] += {rays used, rays skipped, samples outside, visits, visits dropped}.  In
+    place; nothing is read back."""
+    dev, capacity = _tsdf_sparse_table(keys, slots, n_blocks, 'tsdf_sparse_integrate')
+    need(sum_, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='sum', device=dev)
+    need(count, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='count', device=dev)
+    need(stats, (5,), dtype=torch.int64, name='stats', device=dev)
+    _, _, keep, args = _tsdf_sparse_rays('tsdf_sparse_integrate', dev, origin, voxel, trunc, vps, dirs, depth, pose, mask, min_depth, max_range)
+    check(lib().dc_tsdf_sparse_integrate(*args, capacity, ptr(keys), ptr(slots), ptr(n_blocks), ptr(sum_), ptr(count), ptr(stats), stream_ptr()),
+          'dc_tsdf_sparse_integrate')
+
+
+@on_device
+def tsdf_sparse_extract(keys, slots, n_blocks, sum_, count, origin, voxel, min_count=1, ws=None):
+    """(vertices f64 [Nv,3], faces i32 [Nf,3]): the surface nets of the sparse volume, vertices in ascending (block key, local cell) and
+    faces in ascending (block key, local point, axis), normals to the free side (dc_tsdf_sparse_extract_count, the library's scans,
+    dc_tsdf_sparse_extract_fill).  ``n_blocks`` is the host's int.  ONE host read: the two totals, which size the outputs."""
+    dev, capacity = _tsdf_sparse_table(keys, slots, None, 'tsdf_sparse_extract')
+    need(sum_, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='sum', device=dev)
+    need(count, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='count', device=dev)
+    n_blocks, min_count = int(n_blocks), int(min_count)
+    origin = tuple(float(v) for v in origin)
+    voxel = float(voxel)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin) or not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('tsdf_sparse_extract needs a finite origin of 3 values and a voxel size > 0, got %r and %r' % (origin, voxel))
+    if not 0 <= n_blocks <= capacity:
+        raise ValueError('tsdf_sparse_extract needs 0 <= n_blocks <= the capacity %d, got %d' % (capacity, n_blocks))
+    if min_count < 1:
+        raise ValueError('tsdf_sparse_extract needs min_count >= 1, got %d' % min_count)
+    nbytes = int(lib().dc_tsdf_sparse_extract_workspace_bytes(n_blocks))
+    if nbytes == 0:
+        raise ValueError('tsdf_sparse_extract takes fewer than 2^31 / 1536 blocks, got %d' % n_blocks)
+    ws = _ws_arg(ws, nbytes, dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    check(lib().dc_tsdf_sparse_extract_count(ptr(keys), ptr(slots), n_blocks, ptr(sum_), ptr(count), min_count, ptr(totals), ptr(ws), ws.shape[0],
+                                             stream_ptr()), 'dc_tsdf_sparse_extract_count')
+    n_vertices, n_faces = totals.tolist()
+    vertices = torch.empty((n_vertices, 3), dtype=torch.float64, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    check(lib().dc_tsdf_sparse_extract_fill(ptr(keys), ptr(slots), n_blocks, ptr(sum_), ptr(count), *origin, voxel, min_count, ptr(ws),
+                                            ws.shape[0], n_vertices, n_faces, ptr(vertices), ptr(faces), stream_ptr()),
+          'dc_tsdf_sparse_extract_fill')
     return vertices, faces

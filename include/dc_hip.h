@@ -1375,6 +1375,47 @@ int dc_tsdf_extract_fill(const int64_t* sum, const int32_t* count, double ox, do
                          int min_count, const void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_faces, double* vertices, int32_t* faces,
                          dcStream_t stream);
 
+/* ---- sparse TSDF volumes: block-allocated fusion and extraction (depth_correction_amd/csrc/dc_tsdf_sparse.hip, dc_tsdf_sparse_math.h;
+ * DESIGN "Sparse TSDF volumes").  The lattice has the origin (ox, oy, oz) and the voxel size `voxel` and no bounds: a sample at p lies in
+ * voxel i = floor((p - origin) / voxel), any integer, whose centre is origin + (i + 0.5) voxel.  Voxel i lies in the 8 x 8 x 8 block b = i
+ * >> 3 at the local index ((lx 8) + ly) 8 + lz, l = i - 8 b; blocks are valid in [-2^20, 2^20) per axis and have the key ((bx + 2^20) <<
+ * 42) | ((by + 2^20) << 21) | (bz + 2^20).  The table (all DEVICE): keys uint64 [capacity], the first *n_blocks ascending; slots int32
+ * [capacity], the pool slot of each key; n_blocks int64 [1]; the pool sum int64 [capacity, 512] and count int32 [capacity, 512].
+ * 1 <= capacity < 2^22.  The rays, the skipping of rays, the samples, s and the fixed point are those of dc_tsdf_integrate without carving
+ * (one sample loop serves both); a sample whose block is out of range counts as outside the grid.  On any window of the lattice the pool
+ * holds the bits a dense volume with the same origin holds. ---- */
+/* Bytes of workspace dc_tsdf_sparse_allocate needs (n_rays (2 k_steps + 1) candidate keys, their sort and scan, a second table); 0 for
+ * sizes it refuses. */
+size_t dc_tsdf_sparse_workspace_bytes(int64_t n_rays, int k_steps, int64_t capacity);
+/* Admits the blocks the rays will add to.  Every visit that adds (s >= -trunc) wants its block; the wanted keys that the table does not
+ * hold, unique and ascending, get the slots *n_blocks, *n_blocks + 1, ... until `capacity`; the table stays sorted by key and *n_blocks
+ * grows.  info (DEVICE int64 [2]) <- {n_blocks after the call, blocks wanted but not admitted}.  Idempotent: again on the same rays it
+ * changes nothing, again with a larger capacity it admits exactly the rest.  All queued on `stream`, nothing is read by the host.  n *
+ * (2 k_steps + 1) >= 2^31 returns DC_ERR_UNSUPPORTED. */
+int dc_tsdf_sparse_allocate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask, const double* pose,
+                            double ox, double oy, double oz, double voxel, double trunc, int k_steps, double min_depth, double max_range,
+                            int64_t capacity, uint64_t* keys, int32_t* slots, int64_t* n_blocks, int64_t* info, void* ws, size_t ws_bytes,
+                            dcStream_t stream);
+/* Adds n rays as dc_tsdf_integrate does, at slot 512 + local of each visit's block (binary search, once per block change of a lane).  A
+ * visit whose block is not in the table adds nothing.  stats int64 [5] (DEVICE) += {rays used, rays skipped, samples outside, visits,
+ * visits dropped}; visits counts the dropped ones too.  Two integer atomics per visit that lands, no floating-point atomic. */
+int dc_tsdf_sparse_integrate(const void* vps, const void* dirs, const void* depth, int dtype, int64_t n, const uint8_t* mask, const double* pose,
+                             double ox, double oy, double oz, double voxel, double trunc, int k_steps, double min_depth, double max_range,
+                             int64_t capacity, const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t* sum, int32_t* count,
+                             int64_t* stats, dcStream_t stream);
+/* Surface nets as dc_tsdf_extract_* on the unbounded lattice: every cell exists, a voxel of a block that is not in the table is
+ * unobserved, a cell belongs to the block of its corner 0 and has the vertex arithmetic of the dense cell with its global integer
+ * coordinates.  Vertices come in ascending (block key, local cell index), faces in ascending (block key of q, local index of q, e).
+ * n_blocks is the HOST's copy of the table size.  _count fills the workspace (the 27 neighbour positions of every block, flags, offsets)
+ * and totals (DEVICE int64 [2]) <- {vertices, faces}: the one host read; _fill writes vertices double [n_vertices,3] and faces int32
+ * [n_faces,3], a row that would fall outside them is not written.  n_blocks 512 3 >= 2^31 returns DC_ERR_UNSUPPORTED (workspace bytes 0). */
+size_t dc_tsdf_sparse_extract_workspace_bytes(int64_t n_blocks);
+int dc_tsdf_sparse_extract_count(const uint64_t* keys, const int32_t* slots, int64_t n_blocks, const int64_t* sum, const int32_t* count,
+                                 int min_count, int64_t* totals, void* ws, size_t ws_bytes, dcStream_t stream);
+int dc_tsdf_sparse_extract_fill(const uint64_t* keys, const int32_t* slots, int64_t n_blocks, const int64_t* sum, const int32_t* count, double ox,
+                                double oy, double oz, double voxel, int min_count, const void* ws, size_t ws_bytes, int64_t n_vertices,
+                                int64_t n_faces, double* vertices, int32_t* faces, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,12 @@ events, medians of --reps runs in a warm process.  The yardstick is a torch rest
 the ray, elementwise fp64 operations and index_add_ on the int64 sums -- whose volume must EQUAL the kernel's (asserted).  Also the
 accuracy and completeness of the mesh against the room.  Prints one JSON line.
 
-    python tools/recon_bench.py [--poses 10] [--size 64 2048] [--voxel 0.05] [--reps 10]
+--sparse adds the block-allocated volume (csrc/dc_tsdf_sparse.hip) on the same scene and the same lattice: dc_tsdf_sparse_allocate and
+dc_tsdf_sparse_integrate timed per scan, each on its own, into a pool of the size the scene needs; blocks and pool bytes beside the
+dense volume's; the extraction; the pool must EQUAL the dense volume on the dense box (asserted).  Then one scene the dense volume
+refuses (asserted): scans of the 1 M-triangle terrain at --reach-voxel, fused with a growing pool.
+
+    python tools/recon_bench.py [--poses 10] [--size 64 2048] [--voxel 0.05] [--reps 10] [--sparse]
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/recon_bench.py --reps 3      # kernel times
 """
 import argparse
@@ -81,6 +86,99 @@ def torch_integrate(sum_, count, origin, voxel, trunc, dirs, depth, pose):
     return visits
 
 
+def _cloud(vps, dirs, depth):
+    from depth_correction_amd.depth_cloud import DepthCloud
+    return DepthCloud(vps.expand(dirs.shape[0], 3).contiguous(), dirs, depth.reshape(-1, 1).contiguous())
+
+
+def sparse_room(args, vol, vps, dirs, depth, poses):
+    """The room's scans into a sparse volume on the dense volume's lattice: figures beside the dense ones."""
+    from depth_correction_amd import ops
+    from depth_correction_amd.reconstruction import SparseTsdfVolume
+    dev = dirs.device
+    grown = SparseTsdfVolume(vol.voxel_size, trunc=vol.trunc, origin=vol.origin, device=dev)
+    for p in range(args.poses):
+        grown.integrate(_cloud(vps, dirs, depth[p]), pose=poses[p])
+    blocks = grown.n_blocks
+    del grown
+    sv = SparseTsdfVolume(vol.voxel_size, trunc=vol.trunc, origin=vol.origin, max_blocks=blocks, device=dev)
+    k = ops.tsdf_k_steps(vol.trunc, vol.voxel_size)
+    ws = torch.empty((int(ops.lib().dc_tsdf_sparse_workspace_bytes(dirs.shape[0], k, blocks)),), dtype=torch.uint8, device=dev)
+    rule = (sv.origin, sv.voxel_size, sv.trunc, vps, dirs)
+    alloc, integ = [[] for _ in range(args.poses)], [[] for _ in range(args.poses)]
+    for r in range(args.reps + 1):
+        sv.reset()
+        marks = []
+        for p in range(args.poses):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            ops.tsdf_sparse_allocate(sv._keys, sv._slots, sv._n_blocks, sv._info, *rule, depth[p], pose=poses[p], ws=ws)
+            ev[1].record()
+            ops.tsdf_sparse_integrate(sv._keys, sv._slots, sv._n_blocks, sv._sum, sv._count, sv._stats, *rule, depth[p], pose=poses[p])
+            ev[2].record()
+            marks.append(ev)
+        torch.cuda.synchronize()
+        if r:
+            for p, ev in enumerate(marks):
+                alloc[p].append(ev[0].elapsed_time(ev[1]))
+                integ[p].append(ev[1].elapsed_time(ev[2]))
+    sv._n_host = None
+    stats = sv.stats()
+    assert stats['blocks'] == blocks and stats['visits_dropped'] == 0
+    s, c = sv.window((0, 0, 0), vol.dims)
+    assert torch.equal(s, vol.sums()) and torch.equal(c, vol.counts()), 'the sparse pool and the dense volume differ on the dense box'
+    ews = torch.empty((int(ops.lib().dc_tsdf_sparse_extract_workspace_bytes(blocks)),), dtype=torch.uint8, device=dev)
+    extract = lambda: ops.tsdf_sparse_extract(sv._keys, sv._slots, blocks, sv._sum, sv._count, sv.origin, sv.voxel_size, ws=ews)
+    e_ms, e_min = _event_ms(extract, args.reps)
+    vertices, faces = extract()
+    return dict(blocks=blocks, pool_bytes=sv.nbytes, dense_bytes=12 * int(np.prod(vol.dims)), allocate_ws_bytes=int(ws.shape[0]),
+                extract_ws_bytes=int(ews.shape[0]), allocate_scan_ms=float(np.median([np.median(a) for a in alloc])),
+                allocate_scan_min_ms=float(np.min([np.min(a) for a in alloc])), integrate_scan_ms=float(np.median([np.median(a) for a in integ])),
+                integrate_scan_min_ms=float(np.min([np.min(a) for a in integ])), extract_ms=e_ms, extract_min_ms=e_min,
+                vertices=int(vertices.shape[0]), faces=int(faces.shape[0]), visits=stats['visits'], samples_outside=stats['samples_outside'],
+                equal_on_dense_box=True)
+
+
+def sparse_reach(args, vps, dirs, tmin):
+    """Scans of the 1 M-triangle terrain (200 x 200 m) at a voxel size whose box the dense volume refuses, into a growing pool."""
+    from depth_correction_amd import ops
+    from depth_correction_amd.mesh import grid_terrain_mesh
+    from depth_correction_amd.reconstruction import SparseTsdfVolume, TsdfVolume
+    dev = dirs.device
+    terrain = grid_terrain_mesh(710)
+    lo, hi = terrain.bounds
+    refused = False
+    try:
+        TsdfVolume.from_bounds(lo, hi, args.reach_voxel, device=dev)
+    except ValueError:
+        refused = True
+    assert refused, 'the dense volume takes the terrain at %g m: choose a smaller --reach-voxel' % args.reach_voxel
+    poses = _poses(args.poses, 60.0)
+    poses[:, 2, 3] += 8.0
+    poses = torch.as_tensor(poses, device=dev)
+    face, depth, _ = ops.raycast(terrain.on_device(dev)[3], dirs, poses, tmin)
+    depth = torch.where(face >= 0, depth, torch.full_like(depth, float('inf'))).contiguous()
+    sv = SparseTsdfVolume(args.reach_voxel, device=dev)
+    times = []
+    for p in range(args.poses):
+        cloud = _cloud(vps, dirs, depth[p])
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        sv.integrate(cloud, pose=poses[p], max_range=args.reach_range)
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    stats = sv.stats()
+    e_ms, e_min = _event_ms(sv.extract, max(2, args.reps // 3))
+    vertices, faces = sv.extract()
+    box = np.ceil((hi - lo + 6.0 * args.reach_voxel) / args.reach_voxel)
+    return dict(scene='terrain', faces_in=len(terrain), voxel=args.reach_voxel, max_range=args.reach_range, dense_refused=True,
+                dense_voxels=float(np.prod(box)), dense_bytes=12.0 * float(np.prod(box)), blocks=stats['blocks'], capacity=sv.capacity,
+                used_bytes=stats['blocks'] * (12 + 512 * 12), pool_bytes=sv.nbytes, scan_ms_with_growth=times,
+                scan_ms_median=float(np.median(times)), extract_ms=e_ms, extract_min_ms=e_min, vertices=int(vertices.shape[0]),
+                faces=int(faces.shape[0]), stats=stats)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--poses', type=int, default=10)
@@ -89,6 +187,9 @@ def main():
     ap.add_argument('--voxel', type=float, default=0.05)
     ap.add_argument('--samples', type=int, default=1_000_000)
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--sparse', action='store_true', help='also the block-allocated volume on the same scene, and the terrain the dense one refuses')
+    ap.add_argument('--reach-voxel', type=float, default=0.04)
+    ap.add_argument('--reach-range', type=float, default=30.0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('recon_bench needs a GPU')
@@ -134,6 +235,8 @@ def main():
     assert torch.equal(ref_s, vol.sums()) and torch.equal(ref_c, vol.counts()), 'the torch restatement and the kernel differ'
     out.update(torch_all_ms=t_ms, torch_over_kernel=t_ms / ms, equal=True)
     del ref_s, ref_c
+    if args.sparse:
+        out['sparse'] = sparse_room(args, vol, vps, dirs, depth, poses)
     # extraction (with its one host read)
     ws = torch.empty((int(ops.lib().dc_tsdf_extract_workspace_bytes(*vol.dims)),), dtype=torch.uint8, device=dev)
     e_ms, e_min = _event_ms(lambda: ops.tsdf_extract(vol.sums(), vol.counts(), vol.origin, vol.voxel_size, ws=ws), args.reps)
@@ -143,6 +246,9 @@ def main():
     acc = reconstruction_accuracy(mesh, room, n_samples=args.samples, max_dist=2.0 * args.voxel)
     out.update(accuracy_mean=acc['accuracy']['mean'], accuracy_rms=acc['accuracy']['rms'], accuracy_max=acc['accuracy']['max'],
                completeness_mean=acc['completeness']['mean'], completeness_rms=acc['completeness']['rms'], coverage=acc['coverage'])
+    if args.sparse:
+        del vol, ws
+        out['reach'] = sparse_reach(args, vps, dirs, tmin)
     print(json.dumps(out))
 
 
