@@ -249,6 +249,10 @@ _SIGNATURES = {
     'dc_tsdf_sparse_extract_workspace_bytes': (_sz, [_i64]),
     'dc_tsdf_sparse_extract_count': (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     'dc_tsdf_sparse_extract_fill': (_i32, [_vp, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
+    # scan-to-TSDF registration (csrc/dc_tsdf_track.hip)
+    'dc_tsdf_sparse_sample': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    'dc_tsdf_icp_accumulate': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
 }
 
 

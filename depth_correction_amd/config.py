@@ -269,6 +269,14 @@ class Config(object):
         self.slam_epsilon_d = 0.01              # epsilon_d
         self.slam_alpha = 0.8                   # alpha
         self.slam_beta = 0.99                   # beta
+        # the map of the icp_mapper pipeline (DESIGN "Scan-to-TSDF registration"; not in the reference's Config): 'points' is the point
+        # map above; 'tsdf' registers every scan against a sparse TSDF volume that fuses the registered scans (slam.TsdfMapper)
+        self.slam_map = 'points'
+        self.slam_tsdf_voxel_size = 0.1         # voxel size of that volume [m]
+        self.slam_tsdf_trunc = None             # its truncation [m]; None: 3 voxels
+        self.slam_tsdf_min_count = 1            # a voxel is observed from this many visits on
+        self.slam_tsdf_max_blocks = None        # a fixed pool of blocks; None: the pool grows
+        self.slam_tsdf_max_residual = None      # |distance| from which a sample is no pair [m]; None: the truncation
         # map accuracy against the ground-truth mesh (eval.eval_map, DESIGN "Map accuracy"; not in the reference's Config):
         # eval_map appends to map_eval_csv; map_eval_poses 'dataset' (the poses the dataset yields) or 'slam' (the poses run_slam
         # estimates); the quantile of trimmed_mean; samples of the mesh for completeness_mean (0 = not computed)

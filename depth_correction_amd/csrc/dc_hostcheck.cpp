@@ -25,6 +25,7 @@
 #include "dc_planereg_math.h"
 #include "dc_tsdf_math.h"
 #include "dc_tsdf_sparse_math.h"
+#include "dc_tsdf_track_math.h"
 #include "dc_cons_route.h"
 
 // The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
@@ -1056,6 +1057,46 @@ int dc_host_tsdf_sparse_extract(const uint64_t* keys, const int32_t* slots, int6
           }
   totals[0] = nv;
   totals[1] = nf;
+  return DC_OK;
+}
+
+// ---- scan-to-TSDF registration (dc_tsdf_track_math.h; dc_tsdf_track.hip) ----
+// dc_tsdf_sparse_sample on host arrays, point after point; stop (or null) as the kernel reads it.
+int dc_host_tsdf_sparse_sample(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                               const int32_t* count, const double* og, double voxel, double trunc, int min_count, const double* points, int64_t m,
+                               const double* pose, const int32_t* stop, double* x_out, double* value_out, double* grad_out, double* dist_out,
+                               uint8_t* flag_out) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  if (!dc::tsdf_lattice_ok(g) || !(trunc > 0.0) || !std::isfinite(trunc) || min_count < 1 || m < 0 || capacity < 1 ||
+      capacity >= ((int64_t)1 << 22))
+    return DC_ERR_ARG;
+  if (stop && *stop != 0) return DC_OK;
+  const int64_t nb = *n_blocks < 0 ? 0 : (*n_blocks > capacity ? capacity : *n_blocks);
+  for (int64_t i = 0; i < m; ++i) {
+    double x[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+    if (pose) dc::move_point(pose, points + 3 * i, x);
+    const dc::TsdfSample s = dc::tsdf_sample_point(x, g, trunc, min_count, keys, slots, nb, capacity, sum, count);
+    for (int a = 0; a < 3; ++a) { x_out[3 * i + a] = x[a]; grad_out[3 * i + a] = s.grad[a]; }
+    value_out[i] = s.phi;
+    dist_out[i] = s.dist;
+    flag_out[i] = (uint8_t)s.flag;
+  }
+  return DC_OK;
+}
+
+// dc_tsdf_icp_accumulate on host arrays: the pair rule and the 30 sums, added point after point into ONE row (row [DC_ICP_PARTIALS]).
+int dc_host_tsdf_icp_accumulate(const double* x, const double* value, const double* grad, const double* dist, const uint8_t* flag, int64_t m,
+                                const double* threshold, double max_residual, const int32_t* status, double* row, uint8_t* kept_out) {
+  if (m < 0 || !threshold || !status || !row || std::isnan(max_residual)) return DC_ERR_ARG;
+  if (status[0] != 0) return DC_OK;
+  for (int q = 0; q < DC_ICP_PARTIALS; ++q) row[q] = 0.0;
+  for (int64_t i = 0; i < m; ++i) {
+    const bool keep = dc::tsdf_track_keep(flag[i], dist[i], *threshold, max_residual);
+    if (kept_out) kept_out[i] = keep ? 1 : 0;
+    if (!keep) continue;
+    dc::tsdf_track_add(x + 3 * i, value[i], grad + 3 * i, row);
+    row[dc::IcpRow<6>::kUsed] += 1.0;
+  }
   return DC_OK;
 }
 

@@ -31,15 +31,6 @@ static int icp_blocks(int64_t m) {
   return (int)(b < 1 ? 1 : (b > kIcpBlocksMax ? kIcpBlocksMax : b));
 }
 
-// x = R p + t with the products and sums rounded in this order (dc_knn_grid_query moves the queries with the same arithmetic,
-// so the point a pair is formed with is the point that was matched).  Plain operators with contraction switched off for this
-// function: __dmul_rn / __dadd_rn are inline functions of plain operators, which the compiler fuses into fma where it inlines them.
-__device__ __forceinline__ void move_point(const double* T, const double* p, double* x) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int r = 0; r < 3; ++r) x[r] = ((T[r * 4] * p[0] + T[r * 4 + 1] * p[1]) + T[r * 4 + 2] * p[2]) + T[r * 4 + 3];
-}
-
 __global__ void icp_init_kernel(const double* __restrict__ prior, double* __restrict__ state, int32_t* __restrict__ status) {
   const int t = threadIdx.x;
   if (t < 16) { state[DC_ICP_STATE_POSE + t] = prior[t]; state[DC_ICP_STATE_PRIOR + t] = prior[t]; }

@@ -9,6 +9,16 @@
 
 namespace dc {
 
+// x = R p + t with the products and sums rounded in this order (dc_knn_grid_query moves the queries with the same arithmetic,
+// so the point a pair is formed with is the point that was matched; dc_tsdf_sparse_sample samples the volume at this point).  Plain
+// operators with contraction switched off for this function: __dmul_rn / __dadd_rn are inline functions of plain operators, which
+// the compiler fuses into fma where it inlines them.
+DC_HD void move_point(const double* T, const double* p, double* x) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int r = 0; r < 3; ++r) x[r] = ((T[r * 4] * p[0] + T[r * 4 + 1] * p[1]) + T[r * 4 + 2] * p[2]) + T[r * 4 + 3];
+}
+
 // JtJ of N unknowns packed as its upper triangle row by row: (0,0) (0,1) .. (0,N-1) (1,1) .. (N-1,N-1) -- N (N + 1) / 2 entries.
 template <int N>
 DC_HD int sym_index(int r, int c) {

@@ -22,7 +22,7 @@ __all__ = [
     'dyn_directions', 'dyn_update', 'align_blocks', 'align_init', 'align_accumulate', 'align_finish', 'survey_align',
     'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
     'planereg_hypotheses', 'planereg_select', 'tsdf_k_steps', 'tsdf_integrate', 'tsdf_extract',
-    'tsdf_sparse_allocate', 'tsdf_sparse_integrate', 'tsdf_sparse_extract',
+    'tsdf_sparse_allocate', 'tsdf_sparse_integrate', 'tsdf_sparse_extract', 'tsdf_sparse_sample', 'tsdf_icp_accumulate',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -2614,3 +2614,74 @@ def tsdf_sparse_extract(keys, slots, n_blocks, sum_, count, origin, voxel, min_c
                                             ws.shape[0], n_vertices, n_faces, ptr(vertices), ptr(faces), stream_ptr()),
           'dc_tsdf_sparse_extract_fill')
     return vertices, faces
+
+
+# ------------------------------------------------------------------------------------------------
+# scan-to-TSDF registration: sampling the sparse volume and the point-to-surface row (csrc/dc_tsdf_track.hip, slam.TsdfMapper)
+# ------------------------------------------------------------------------------------------------
+TSDF_SAMPLE_RANGE, TSDF_SAMPLE_UNOBSERVED = 1, 2
+
+
+@on_device
+def tsdf_sparse_sample(keys, slots, n_blocks, sum_, count, origin, voxel, trunc, points, pose=None, min_count=1, stop=None, out=None):
+    """Samples the sparse volume at ``points`` f64 [M,3] moved by ``pose`` (device f64 [4,4], None: as they are) -> dict(x [M,3] the
+    moved points, value [M] the trilinear distance in metres, grad [M,3] its analytic gradient, dist [M] = |value|, flag u8 [M]: 0,
+    TSDF_SAMPLE_RANGE or TSDF_SAMPLE_UNOBSERVED); an invalid point has value NaN, grad 0 and dist +inf (dc_tsdf_sparse_sample; the rule:
+    csrc/dc_tsdf_track_math.h).  ``out``: such a dict to write into; ``stop`` (device i32): nonzero leaves ``out`` as it is.  Nothing is
+    read back."""
+    dev, capacity = _tsdf_sparse_table(keys, slots, n_blocks, 'tsdf_sparse_sample')
+    need(sum_, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='sum', device=dev)
+    need(count, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='count', device=dev)
+    origin = tuple(float(v) for v in origin)
+    voxel, trunc, min_count = float(voxel), float(trunc), int(min_count)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin) or not (voxel > 0.0 and math.isfinite(voxel)) or \
+            not (trunc > 0.0 and math.isfinite(trunc)):
+        raise ValueError('tsdf_sparse_sample needs a finite origin of 3 values, a voxel size and a truncation > 0, got %r, %r and %r'
+                         % (origin, voxel, trunc))
+    if min_count < 1:
+        raise ValueError('tsdf_sparse_sample needs min_count >= 1, got %d' % min_count)
+    need(points, (None, 3), dtype=torch.float64, name='points', device=dev)
+    m = points.shape[0]
+    if pose is not None:
+        need(pose, (4, 4), dtype=torch.float64, name='pose', device=dev)
+    if stop is not None:
+        need(stop, None, dtype=torch.int32, name='stop', device=dev)
+    if out is None:
+        out = dict(x=torch.empty((m, 3), dtype=torch.float64, device=dev), value=torch.empty((m,), dtype=torch.float64, device=dev),
+                   grad=torch.empty((m, 3), dtype=torch.float64, device=dev), dist=torch.empty((m,), dtype=torch.float64, device=dev),
+                   flag=torch.empty((m,), dtype=torch.uint8, device=dev))
+    else:
+        for name, shape, dt in (('x', (m, 3), torch.float64), ('value', (m,), torch.float64), ('grad', (m, 3), torch.float64),
+                                ('dist', (m,), torch.float64), ('flag', (m,), torch.uint8)):
+            need(out[name], shape, dtype=dt, name=name, device=dev)
+    check(lib().dc_tsdf_sparse_sample(ptr(keys), ptr(slots), ptr(n_blocks), capacity, ptr(sum_), ptr(count), *origin, voxel, trunc, min_count,
+                                      ptr(points), m, ptr(pose), ptr(stop), ptr(out['x']), ptr(out['value']), ptr(out['grad']),
+                                      ptr(out['dist']), ptr(out['flag']), stream_ptr()), 'dc_tsdf_sparse_sample')
+    return out
+
+
+@on_device
+def tsdf_icp_accumulate(sample, threshold, max_residual, state, status, partials, kept=None):
+    """The pairs of one scan-to-TSDF iteration from ``sample`` (tsdf_sparse_sample's dict) -> block partials f64 [icp_blocks(M),
+    DC_ICP_PARTIALS] for icp_finish (dc_tsdf_icp_accumulate): point i is a pair iff flag == 0, dist <= threshold (device f64 [1]) and
+    dist < max_residual; ``kept`` (uint8 [M], optional) receives the flags."""
+    x = sample['x']
+    dev = x.device
+    need(x, (None, 3), dtype=torch.float64, name='x')
+    m = x.shape[0]
+    need(sample['value'], (m,), dtype=torch.float64, name='value', device=dev)
+    need(sample['grad'], (m, 3), dtype=torch.float64, name='grad', device=dev)
+    need(sample['dist'], (m,), dtype=torch.float64, name='dist', device=dev)
+    need(sample['flag'], (m,), dtype=torch.uint8, name='flag', device=dev)
+    need(threshold, (1,), dtype=torch.float64, name='threshold', device=dev)
+    _icp_state_args(state, status, dev)
+    nb = icp_blocks(m)
+    need(partials, (nb, nv.DC_ICP_PARTIALS), dtype=torch.float64, name='partials', device=dev)
+    if kept is not None:
+        need(kept, (m,), dtype=torch.uint8, name='kept', device=dev)
+    max_residual = float(max_residual)
+    if math.isnan(max_residual):
+        raise ValueError('tsdf_icp_accumulate needs a max_residual that is a number')
+    check(lib().dc_tsdf_icp_accumulate(ptr(x), ptr(sample['value']), ptr(sample['grad']), ptr(sample['dist']), ptr(sample['flag']), m,
+                                       ptr(threshold), max_residual, ptr(state), ptr(status), ptr(partials), nb, ptr(kept), stream_ptr()),
+          'dc_tsdf_icp_accumulate')

@@ -265,6 +265,20 @@ class SparseTsdfVolume(object):
             count[have] = self._count.reshape(-1)[at[have]]
         return sum_, count
 
+    def sample(self, points, pose=None, min_count=1, stop=None, out=None):
+        """The fused signed distance at ``points`` [M,3] (moved by ``pose`` 4 x 4 when given): dict(x f64 [M,3] the moved points, value
+        [M] metres (trilinear over the eight voxels around a point), grad [M,3] its gradient, dist [M] = |value|, flag u8 [M]: 0, 1 out of
+        range / not finite, 2 one of the eight voxels unobserved), all on the device.  An invalid point has value NaN, grad 0, dist +inf.
+        The distance of any cloud to the fused surface without extracting a mesh; slam.TsdfMapper registers scans with it."""
+        points = torch.as_tensor(points, device=self.device).to(torch.float64).reshape(-1, 3).contiguous()
+        if pose is not None and not (isinstance(pose, torch.Tensor) and pose.is_cuda):
+            pose = torch.as_tensor(np.asarray(pose, dtype=np.float64), device=self.device)
+        if pose is not None:
+            pose = pose.to(torch.float64).reshape(4, 4).contiguous()
+        with torch.no_grad():
+            return ops.tsdf_sparse_sample(self._keys, self._slots, self._n_blocks, self._sum, self._count, self.origin, self.voxel_size,
+                                          self.trunc, points, pose=pose, min_count=min_count, stop=stop, out=out)
+
     def extract(self, min_count=1):
         """(vertices f64 [Nv,3], faces i32 [Nf,3]) on the device; both empty when the volume holds no surface."""
         return ops.tsdf_sparse_extract(self._keys, self._slots, self.n_blocks, self._sum, self._count, self.origin, self.voxel_size,

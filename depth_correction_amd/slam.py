@@ -6,6 +6,10 @@ deviations.  Its device state is the map (points and the normals of the scans th
 registration's state; an ICP iteration runs on the device without the host (csrc/dc_slam.hip), which reads one status word every
 ``status_every`` iterations.  With cfg.slam_compute_prob_dynamic every map point also carries the probability that it belongs to
 something that moved (csrc/dc_dynamic.hip, DESIGN "Dynamic points in the map").
+
+With cfg.slam_map = 'tsdf' the map is a sparse TSDF volume instead (TsdfMapper, csrc/dc_tsdf_track.hip, DESIGN "Scan-to-TSDF
+registration"): a scan is registered against the fused volume by the same loop and the same finish kernel, without a nearest-neighbour
+search, and every registered scan is fused into it.  make_mapper(cfg) picks the class.
 """
 from __future__ import annotations
 
@@ -17,7 +21,8 @@ from . import ops
 from .config import Config, SLAM
 from .utils import delta_transform, rotation_angle, translation_norm
 
-__all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'LAUNCHES_PER_ITERATION_CT', 'dynamic_params', 'mapper_input', 'odometry_cov', 'odometry_poses',
+__all__ = ['IcpMapper', 'MapperScan', 'TsdfMapper', 'TsdfScan', 'make_mapper', 'LAUNCHES_PER_ITERATION', 'LAUNCHES_PER_ITERATION_CT',
+           'LAUNCHES_PER_ITERATION_TSDF', 'dynamic_params', 'mapper_input', 'odometry_cov', 'odometry_poses',
            'path_lengths', 'run_slam', 'slam_errors']
 
 # launches of one ICP iteration: dc_knn_grid_query 3 (moved queries, the 16-lanes-per-query search, the tail search), dc_quantile 18
@@ -25,6 +30,8 @@ __all__ = ['IcpMapper', 'MapperScan', 'LAUNCHES_PER_ITERATION', 'LAUNCHES_PER_IT
 LAUNCHES_PER_ITERATION = 23
 # the sweep-aware iteration: dc_deskew 1 more, dc_icp_ct_accumulate and dc_icp_ct_finish in the places of the two last
 LAUNCHES_PER_ITERATION_CT = 24
+# the scan-to-TSDF iteration: dc_tsdf_sparse_sample 1, dc_quantile 18, dc_tsdf_icp_accumulate 1, dc_icp_finish 1 -- no search
+LAUNCHES_PER_ITERATION_TSDF = 21
 FAILED = ('empty', 'too_few_pairs', 'singular', 'not_finite', 'bound')
 
 
@@ -163,6 +170,33 @@ class MapperScan(object):
         return self.points.shape[0]
 
 
+def _registration_loop(mapper, prior, launches, iterate):
+    """The loop every mapper's registration runs (IcpMapper's two, TsdfMapper's): icp_init from ``prior`` into the mapper's state and
+    status, ``iterate(pose_d)`` (one iteration of ``launches`` launches, queued; pose_d the device-side estimate) ``status_every`` at a
+    time with one status read per group, and the read-back.  -> (pose, info), the prior's copy when the registration failed."""
+    cfg = mapper.cfg
+    pose_d = mapper.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
+    ops.icp_init(torch.as_tensor(prior, device=mapper.device), mapper.state, mapper.status)
+    done = 0
+    code = 0
+    while done < cfg.icp_max_iters:
+        for _ in range(min(mapper.status_every, cfg.icp_max_iters - done)):
+            iterate(pose_d)
+            done += 1
+        st = mapper.status.cpu()
+        mapper.host_reads += 1
+        code = int(st[0])
+        if code != 0:
+            break
+    st = mapper.state.cpu().numpy()
+    iters = int(mapper.status[1].item())
+    info = mapper._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
+                        float(st[nv.DC_ICP_STATE_SSE]), launches=launches)
+    if not info['ok']:
+        return prior.copy(), info
+    return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+
+
 class IcpMapper(object):
     """Scan-to-map point-to-plane ICP and map of the reference's mapper configuration (see DESIGN "SLAM evaluation").
 
@@ -268,27 +302,8 @@ class IcpMapper(object):
         idx = torch.empty((m, k), dtype=torch.int32, device=dev)
         dist = torch.empty((m, k), dtype=torch.float64, device=dev)
         thr = torch.empty((1,), dtype=torch.float64, device=dev)
-        pose_d = self.state[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].view(4, 4)
         cos_min = float(np.cos(cfg.icp_max_normal_angle))
-        ops.icp_init(torch.as_tensor(prior, device=dev), self.state, self.status)
-        done = 0
-        code = 0
-        while done < cfg.icp_max_iters:
-            for _ in range(min(self.status_every, cfg.icp_max_iters - done)):
-                iterate(pose_d, idx, dist, thr, cos_min)
-                done += 1
-            st = self.status.cpu()
-            self.host_reads += 1
-            code = int(st[0])
-            if code != 0:
-                break
-        st = self.state.cpu().numpy()
-        iters = int(self.status[1].item())
-        info = self._info(nv.ICP_STATUS[code], iters, float(st[nv.DC_ICP_STATE_OVERLAP]), int(st[nv.DC_ICP_STATE_PAIRS]),
-                          float(st[nv.DC_ICP_STATE_SSE]), launches=launches)
-        if not info['ok']:
-            return prior.copy(), info
-        return st[nv.DC_ICP_STATE_POSE:nv.DC_ICP_STATE_POSE + 16].reshape(4, 4).copy(), info
+        return _registration_loop(self, prior, launches, lambda pose_d: iterate(pose_d, idx, dist, thr, cos_min))
 
     def _match(self, points, pose_d, idx, dist, thr, grid):
         """The two launches every iteration starts with: the k-NN of ``points`` moved by the device-side pose, the trimmed threshold."""
@@ -523,6 +538,159 @@ class IcpMapper(object):
         return pts, nrm
 
 
+class TsdfScan(object):
+    """A reading as the TSDF mapper uses it: points fp64 [M,3] in the sensor frame for the registration, and the rays they came from
+    (vps, dirs fp64 [M,3], depth fp64 [M,1]) for the fusion; no normals.  ``t`` is None (the sweep-aware registration has a point map)."""
+    t = None
+
+    def __init__(self, points, vps, dirs, depth):
+        self.points, self.vps, self.dirs, self.depth = points, vps, dirs, depth
+
+    def __len__(self):
+        return self.points.shape[0]
+
+    def cloud(self):
+        from .depth_cloud import DepthCloud
+        return DepthCloud(vps=self.vps, dirs=self.dirs, depth=self.depth)
+
+
+def _tsdf_map_refusals(cfg: Config):
+    """The switches that are rules of the point map and mean nothing for a TSDF map: ValueError."""
+    for name in ('slam_ct', 'slam_compute_prob_dynamic', 'slam_cut_dynamic'):
+        if getattr(cfg, name):
+            raise ValueError("%s is a rule of the point map: not with slam_map='tsdf'" % name)
+
+
+class TsdfMapper(object):
+    """Frame-to-model tracking: every scan is registered against a sparse TSDF volume (reconstruction.SparseTsdfVolume) that fuses the
+    registered scans (DESIGN "Scan-to-TSDF registration").  The surface of IcpMapper: ``register(scan, prior)`` -> (pose, info),
+    ``update(scan, pose, overlap=None)`` fuses the scan's rays at the pose (every registered scan, whatever its overlap) and returns the
+    rays used, ``map_points()``, ``clear()``, ``n_map`` (the volume's blocks); and ``volume`` / ``extract_mesh()``: the map the SLAM
+    ends with is the reconstruction.  An iteration samples the volume at the moved points, takes the trimmed threshold of |distance|,
+    builds the point-to-surface row and runs IcpMapper's finish; it has no nearest-neighbour search, and the map side has no normals
+    and no minimum distance between points.  The prior must lie within about the truncation of the truth (the capture range)."""
+
+    def __init__(self, cfg: Config, device=None, status_every=4):
+        from .reconstruction import SparseTsdfVolume
+        if not (1 <= int(cfg.icp_smooth_length) <= nv.DC_ICP_MAX_SMOOTH):
+            raise ValueError('icp_smooth_length must be in 1..%d' % nv.DC_ICP_MAX_SMOOTH)
+        _tsdf_map_refusals(cfg)
+        self.cfg = cfg
+        self.device = torch.device(device or cfg.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('TsdfMapper runs on the GPU (depth_correction_amd has no CPU path)')
+        self.status_every = max(1, int(status_every))
+        self.min_count = int(cfg.slam_tsdf_min_count)
+        if self.min_count < 1:
+            raise ValueError('slam_tsdf_min_count must be >= 1, got %r' % (cfg.slam_tsdf_min_count,))
+        self.volume = SparseTsdfVolume(cfg.slam_tsdf_voxel_size, trunc=cfg.slam_tsdf_trunc, max_blocks=cfg.slam_tsdf_max_blocks,
+                                       device=self.device)
+        self.max_residual = self.volume.trunc if cfg.slam_tsdf_max_residual is None else float(cfg.slam_tsdf_max_residual)
+        if not self.max_residual > 0.0:
+            raise ValueError('slam_tsdf_max_residual must be > 0, got %r' % (cfg.slam_tsdf_max_residual,))
+        self.n_dynamic, self.last_dyn = 0, None          # (run_slam reports them; a TSDF map has no dynamic-point rule)
+        self.state = torch.zeros((nv.DC_ICP_STATE_COUNT,), dtype=torch.float64, device=self.device)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=self.device)
+        self.host_reads = 0
+        self.quantile_ws = torch.empty((max(int(nv.lib().dc_quantile_workspace_bytes()), 1),), dtype=torch.uint8, device=self.device)
+
+    @property
+    def n_map(self):
+        return self.volume.n_blocks
+
+    def prepare(self, cloud):
+        """TsdfScan of a DepthCloud / structured array / points (sensor frame; points alone are rays from the origin): the fp64 points
+        and the rays next to them.  No normals are computed."""
+        from .depth_cloud import DepthCloud
+        if isinstance(cloud, TsdfScan):
+            return cloud
+        if not isinstance(cloud, DepthCloud):
+            if getattr(getattr(cloud, 'dtype', None), 'names', None):
+                cloud = DepthCloud.from_structured_array(cloud, dtype=np.float64, device=self.device)
+            else:
+                pts = torch.as_tensor(cloud, dtype=torch.float64, device=self.device).reshape(-1, 3).contiguous()
+                if pts.shape[0] == 0:
+                    return TsdfScan(pts, pts.clone(), pts.clone(), torch.empty((0, 1), dtype=torch.float64, device=self.device))
+                cloud = DepthCloud.from_points(pts, vps=torch.zeros_like(pts), dtype=torch.float64, device=self.device)
+        kw = dict(device=self.device, dtype=torch.float64)
+        dirs = cloud.dirs.detach().to(**kw).contiguous()
+        vps = cloud.vps.detach().to(**kw).expand_as(dirs).contiguous()
+        depth = cloud.depth.detach().to(**kw).reshape(-1, 1).contiguous()
+        pts = cloud.get_points().detach().to(**kw).contiguous()
+        return TsdfScan(pts, vps, dirs, depth)
+
+    def _info(self, status, iterations=0, overlap=0.0, pairs=0, sse=0.0, launches=LAUNCHES_PER_ITERATION_TSDF):
+        return dict(status=status, ok=status not in FAILED, iterations=iterations, overlap=overlap, pairs=pairs, sse=sse,
+                    host_reads=self.host_reads, launches_per_iteration=launches)
+
+    def buffers(self, m):
+        """The device buffers of a registration of an m-point scan: the sample (x, value, grad, dist, flag), the threshold, the block
+        partials."""
+        dev = self.device
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        return dict(x=f64(m, 3), value=f64(m), grad=f64(m, 3), dist=f64(m), flag=torch.empty((m,), dtype=torch.uint8, device=dev),
+                    thr=f64(1), partials=f64(ops.icp_blocks(m), nv.DC_ICP_PARTIALS))
+
+    def register(self, scan, prior):
+        """Pose of ``scan`` in the volume from ``prior`` (4 x 4), by IcpMapper's loop.  An empty scan ('empty') or a failed registration
+        returns the prior; an empty volume returns the prior with status 'init' (the first scan initialises the map)."""
+        scan = self.prepare(scan)
+        prior = np.asarray(prior, dtype=np.float64).reshape(4, 4)
+        self.host_reads = 0
+        m = len(scan)
+        if m == 0:
+            return prior.copy(), self._info('empty')
+        if self.n_map == 0:
+            return prior.copy(), self._info('init')
+        buf = self.buffers(m)
+        return _registration_loop(self, prior, LAUNCHES_PER_ITERATION_TSDF, lambda pose_d: self.iteration(scan, pose_d, buf))
+
+    def iteration(self, scan, pose_d, buf, kept=None):
+        """One iteration, queued on the stream: sample at the moved points, trimmed threshold, pairs and partials, solve and update."""
+        cfg, vol = self.cfg, self.volume
+        ops.tsdf_sparse_sample(vol._keys, vol._slots, vol._n_blocks, vol._sum, vol._count, vol.origin, vol.voxel_size, vol.trunc, scan.points,
+                               pose=pose_d, min_count=self.min_count, stop=self.status, out=buf)
+        ops.quantile(buf['dist'], cfg.icp_trim_ratio, stop=self.status, out=buf['thr'], ws=self.quantile_ws)
+        ops.tsdf_icp_accumulate(buf, buf['thr'], self.max_residual, self.state, self.status, buf['partials'], kept=kept)
+        ops.icp_finish(buf['partials'], len(scan), self.state, self.status, cfg.icp_min_diff_rot, cfg.icp_min_diff_trans, cfg.icp_smooth_length,
+                       cfg.icp_max_iters, cfg.icp_max_rotation, cfg.icp_max_translation)
+
+    def update(self, scan, pose, overlap=None):
+        """Fuse the rays of ``scan`` at ``pose`` into the volume (depths up to cfg.slam_sensor_max_range); ``overlap`` is accepted and
+        not used: a fused volume gains from every scan.  Returns the rays used."""
+        scan = self.prepare(scan)
+        if len(scan) == 0:
+            return 0
+        stats = self.volume.integrate(scan.cloud(), pose=np.asarray(pose, dtype=np.float64).reshape(4, 4),
+                                      max_range=self.cfg.slam_sensor_max_range)
+        return int(stats['rays_used'])
+
+    def clear(self):
+        self.volume.reset()
+
+    def extract_mesh(self, min_count=None):
+        return self.volume.extract_mesh(self.min_count if min_count is None else min_count)
+
+    def map_points(self):
+        """(points, normals) fp64 [N,3]: the surface-net vertices of the volume and the unit sampled gradient there (zero where the
+        sample is invalid)."""
+        pts, _ = self.volume.extract(self.min_count)
+        if pts.shape[0] == 0:
+            return pts, pts.clone()
+        g = self.volume.sample(pts, min_count=self.min_count)['grad']
+        norm = torch.linalg.norm(g, dim=1, keepdim=True)
+        return pts, torch.where(norm > 0.0, g / norm.clamp(min=1e-300), g)
+
+
+def make_mapper(cfg: Config, device=None, status_every=4):
+    """The mapper of cfg.slam_map: 'points' -> IcpMapper, 'tsdf' -> TsdfMapper (which refuses the point map's switches)."""
+    if cfg.slam_map == 'points':
+        return IcpMapper(cfg, device=device, status_every=status_every)
+    if cfg.slam_map == 'tsdf':
+        return TsdfMapper(cfg, device=device, status_every=status_every)
+    raise ValueError("unknown slam_map %r; available: 'points', 'tsdf'" % (cfg.slam_map,))
+
+
 def _redo_first_scan(mapper, first, pose0, scan, prior, twist, pose, info, info0, cfg, passes=2):
     """The first scan of a sweep-aware run has no map to be registered against, so its twist cannot be estimated: it entered the map
     de-skewed by the odometry's first step, and a map bent by that step's error bends every later estimate with it.  Once the second
@@ -556,16 +724,20 @@ def run_slam(dataset, model, cfg: Config, mapper=None, verbose=False):
     and the map takes the scan de-skewed by the estimated twist (info['twist']); both together are refused (ValueError).  The first
     scan of an empty map is de-skewed by the odometry's first step and, once the second scan is registered, again by the twist of
     the registered step (_redo_first_scan).
+    The map is cfg.slam_map's (make_mapper): 'tsdf' registers against a fused sparse TSDF volume (TsdfMapper; ``added`` is then the rays
+    fused and ``map_size`` the volume's blocks) and refuses slam_ct and the dynamic-point switches (ValueError); slam_deskew works.
     Returns dict(slam, odom, gt [N,4,4], path_lengths [N], info [N dicts], ids)."""
     if cfg.slam not in SLAM:
         raise ValueError('unknown SLAM pipeline %r; available: %s' % (cfg.slam, ', '.join(SLAM)))
     if cfg.slam_ct and cfg.slam_deskew:
         raise ValueError('slam_ct estimates the twist of a sweep inside the ICP and slam_deskew removes it beforehand: set one of them')
+    if cfg.slam_map == 'tsdf':
+        _tsdf_map_refusals(cfg)
     items = [(cloud, np.asarray(pose, dtype=np.float64)) for cloud, pose in dataset]
     gt = np.stack([pose for _, pose in items]) if items else np.zeros((0, 4, 4))
     odom = odometry_poses(gt, cfg.odom_cov)
     lengths = path_lengths(gt)
-    mapper = mapper or IcpMapper(cfg)
+    mapper = mapper or make_mapper(cfg)
     slam = odom.copy()
     infos = []
     first = None

@@ -1416,6 +1416,33 @@ int dc_tsdf_sparse_extract_fill(const uint64_t* keys, const int32_t* slots, int6
                                 double oy, double oz, double voxel, int min_count, const void* ws, size_t ws_bytes, int64_t n_vertices,
                                 int64_t n_faces, double* vertices, int32_t* faces, dcStream_t stream);
 
+/* ---- scan-to-TSDF registration: a scan registered against the sparse volume itself (depth_correction_amd/csrc/dc_tsdf_track.hip,
+ * dc_tsdf_track_math.h; DESIGN "Scan-to-TSDF registration").  One iteration = dc_tsdf_sparse_sample + dc_quantile (over dist_out) +
+ * dc_tsdf_icp_accumulate + dc_icp_finish: no nearest-neighbour search.  dc_icp_init, the state vector, the status word and its codes and
+ * dc_icp_finish are those of the scan-to-map ICP above, unchanged.  Nothing here uses an atomic, allocates or synchronises. ---- */
+#define DC_TSDF_SAMPLE_RANGE 1      /* flag: the point is not finite or lies outside the lattice's voxel range */
+#define DC_TSDF_SAMPLE_UNOBSERVED 2 /* flag: one of the eight voxels around the point has no block or count < min_count */
+/* Samples the volume (table and pool as above; n_blocks DEVICE int64 [1]) at m points (double [m,3]), one lane per point.  x = T p for
+ * pose (DEVICE double [16] row-major, or NULL: x = p) with the rounding order of dc_icp_accumulate's moved points.  q = (x - origin) /
+ * voxel - 0.5 per axis; flag DC_TSDF_SAMPLE_RANGE unless x is finite and -2^23 <= q < 2^23 - 1; i0 = floor(q), f = q - i0; corner c = bx +
+ * 2 by + 4 bz is voxel i0 + (bx, by, bz), observed iff its block is in the table and count >= min_count (>= 1), with the value sum / (count
+ * 2^20); flag DC_TSDF_SAMPLE_UNOBSERVED unless all eight are observed.  Otherwise flag 0, value_out = trunc x the trilinear interpolant
+ * (metres), grad_out = (trunc / voxel) x its analytic gradient, dist_out = |value_out|; the order of every product and sum is that of
+ * dc_tsdf_track_math.h.  An invalid point has value NaN, grad 0, dist +inf.  x_out [m,3] always receives the moved point.  stop (DEVICE
+ * int32, or NULL): *stop != 0 returns at once and leaves the outputs as they are. */
+int dc_tsdf_sparse_sample(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                          const int32_t* count, double ox, double oy, double oz, double voxel, double trunc, int min_count,
+                          const double* points, int64_t m, const double* pose, const int32_t* stop, double* x_out, double* value_out,
+                          double* grad_out, double* dist_out, uint8_t* flag_out, dcStream_t stream);
+/* The pairs of one iteration from dc_tsdf_sparse_sample's outputs: point i is kept iff flag == 0, dist <= *threshold (DEVICE; NaN keeps
+ * nothing) and dist < max_residual (strict: a fully clamped sample, |value| == trunc with zero gradient, is no pair at max_residual =
+ * trunc).  r = value, J = [x cross grad, grad]; partials double [n_blocks = dc_icp_blocks(m), DC_ICP_PARTIALS] in dc_icp_accumulate's
+ * layout (points with a kept pair = pairs), for dc_icp_finish.  kept_out uint8 [m] (optional).  Returns at once when status[0] != 0.
+ * m = 0 writes one row of zeros (dc_icp_finish then ends with DC_ICP_FAIL_PAIRS). */
+int dc_tsdf_icp_accumulate(const double* x, const double* value, const double* grad, const double* dist, const uint8_t* flag, int64_t m,
+                           const double* threshold, double max_residual, const double* state, const int32_t* status, double* partials,
+                           int n_blocks, uint8_t* kept_out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,11 @@
 pillars, run through the mapper with the slam_eval.launch odometry noise.  Per scan: registration time, ICP iterations, host status
 reads, map-update time and map size; launches per ICP iteration; the mean errors of SLAM and odometry.  Prints one JSON line.
 
-    python tools/slam_bench.py [--poses 100] [--size 64 2048] [--grid-res 0.1]
+    python tools/slam_bench.py [--poses 100] [--size 64 2048] [--grid-res 0.1] [--map points|tsdf]
+
+With --map tsdf the same scene and odometry go through slam.TsdfMapper (cfg.slam_map = 'tsdf': every scan is registered against the fused
+sparse TSDF volume, DESIGN "Scan-to-TSDF registration"); the JSON has the same keys, map_size_final counting blocks, added the rays fused
+and grid_builds 0.
 
 With --sweep the sequence is rendered as moving sweeps (render.SweepModel) and registered twice, by the 6-dof iteration on the raw
 scans and by the sweep-aware 12-dof iteration (cfg.slam_ct, the odometry's twist as prior twist): registration time, iterations, time
@@ -88,6 +92,8 @@ def main():
     ap.add_argument('--size', type=int, nargs=2, default=(64, 2048))
     ap.add_argument('--grid-res', type=float, default=0.1)
     ap.add_argument('--status-every', type=int, default=4)
+    ap.add_argument('--map', choices=('points', 'tsdf'), default='points', help="the mapper's map (cfg.slam_map)")
+    ap.add_argument('--tsdf-voxel', type=float, default=0.1, help='voxel size of the TSDF map (cfg.slam_tsdf_voxel_size)')
     ap.add_argument('--sweep', action='store_true', help='render moving sweeps and time the 6-dof and the sweep-aware registration')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -98,7 +104,7 @@ def main():
     from depth_correction_amd.config import Config
     from depth_correction_amd.mesh import room_mesh
     from depth_correction_amd.render import RenderedMeshDataset
-    from depth_correction_amd.slam import LAUNCHES_PER_ITERATION, IcpMapper, mapper_input, odometry_poses, path_lengths, slam_errors
+    from depth_correction_amd.slam import make_mapper, mapper_input, odometry_poses, path_lengths, slam_errors
     from depth_correction_amd.utils import delta_transform
     dev = 'cuda:0'
     mesh = room_mesh((8.0, 5.0, 2.0), 0.5, pillars=[((2.0, 2.5, 0.0), (0.4, 0.4, 1.5)), ((-2.5, -2.5, 0.0), (0.5, 0.3, 1.5)),
@@ -108,10 +114,11 @@ def main():
     gt = _poses(args.poses)
     ds = RenderedMeshDataset(path, poses=gt, size=tuple(args.size), fov=(45.0, 360.0), num_segments=16, device=dev)
     cfg = Config(device=dev, float_type='float64', min_depth=0.5, max_depth=25.0, grid_res=args.grid_res,
-                 odom_cov=[1e-4] * 3 + [2.5e-3] * 3)
+                 odom_cov=[1e-4] * 3 + [2.5e-3] * 3, slam_map=args.map, slam_tsdf_voxel_size=args.tsdf_voxel)
     clouds = [c for c, _ in ds]
     odom = odometry_poses(gt, cfg.odom_cov)
-    mapper = IcpMapper(cfg, status_every=args.status_every)
+    mapper = make_mapper(cfg, status_every=args.status_every)
+    launches = None
     slam = odom.copy()
     rows = []
     for i, cloud in enumerate(clouds):
@@ -128,6 +135,7 @@ def main():
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         slam[i] = pose
+        launches = info['launches_per_iteration']
         rows.append(dict(points=len(scan), prepare_ms=(t1 - t0) * 1e3, register_ms=(t2 - t1) * 1e3, update_ms=(t3 - t2) * 1e3,
                          iterations=info['iterations'], host_reads=info['host_reads'], status=info['status'], added=added,
                          map_size=mapper.n_map))
@@ -135,14 +143,14 @@ def main():
     reg = [r for r in rows[1:] if r['iterations'] > 0]
     med = lambda k, rs=reg: float(np.median([r[k] for r in rs])) if rs else float('nan')
     iters = np.array([r['iterations'] for r in reg])
-    out = dict(tool='slam_bench', poses=args.poses, size=list(args.size), grid_res=args.grid_res, points_per_scan=med('points', rows),
-               launches_per_iteration=LAUNCHES_PER_ITERATION, status_every=args.status_every,
+    out = dict(tool='slam_bench', map=args.map, poses=args.poses, size=list(args.size), grid_res=args.grid_res, points_per_scan=med('points', rows),
+               launches_per_iteration=launches, status_every=args.status_every,
                register_ms_median=med('register_ms'), register_ms_max=float(max(r['register_ms'] for r in reg)) if reg else None,
                iterations_median=float(np.median(iters)) if len(iters) else None, iterations_max=int(iters.max()) if len(iters) else None,
                ms_per_iteration_median=float(np.median([r['register_ms'] / r['iterations'] for r in reg])) if reg else None,
                host_reads_per_iteration=float(sum(r['host_reads'] for r in reg) / max(1, iters.sum())),
                prepare_ms_median=med('prepare_ms', rows), update_ms_median=med('update_ms', rows[1:]),
-               map_size_final=mapper.n_map, grid_builds=mapper.grid_builds,
+               map_size_final=mapper.n_map, grid_builds=getattr(mapper, 'grid_builds', 0),
                failed=[i for i, r in enumerate(rows) if r['status'] in ('empty', 'too_few_pairs', 'singular', 'not_finite', 'bound')],
                slam_errors=slam_errors(slam, gt, lengths), odom_errors=slam_errors(odom, gt, lengths))
     print(json.dumps(out))
