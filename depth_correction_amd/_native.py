@@ -253,6 +253,11 @@ _SIGNATURES = {
     'dc_tsdf_sparse_sample': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
     'dc_tsdf_icp_accumulate': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    # self-supervised training against the fused volume (csrc/dc_tsdf_loss.hip)
+    'dc_tsdf_loss_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'dc_tsdf_loss': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp,
+                            _sz, _vp]),
 }
 
 

@@ -12,7 +12,7 @@ import tempfile
 
 import yaml
 
-__all__ = ['bias_eval_csv', 'CLOUD_LOSS_DEFAULTS', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'recon_eval_csv', 'SLAM', 'nonempty',
+__all__ = ['bias_eval_csv', 'CLOUD_LOSS_DEFAULTS', 'TSDF_LOSS_DEFAULTS', 'Config', 'Loss', 'loss_eval_csv', 'map_eval_csv', 'Model', 'NeighborhoodType', 'PoseCorrection', 'PoseProvider', 'recon_eval_csv', 'SLAM', 'nonempty',
            'slam_eval_bag', 'slam_eval_csv', 'slam_poses_csv']
 
 
@@ -37,7 +37,9 @@ class Loss(metaclass=_Names):
     icp_loss = 'icp_loss'
     mesh_loss = 'mesh_loss'          # supervised: distance to the dataset's ground-truth mesh (loss.mesh_loss)
     cloud_loss = 'cloud_loss'        # supervised: distance to the dataset's surveyed cloud (loss.cloud_loss)
-    _unlisted = ('mesh_loss', 'cloud_loss')   # need a dataset with a mesh / a survey: not part of the default eval_losses sweep
+    tsdf_loss = 'tsdf_loss'          # self-supervised: distance to the volume the sequence's own scans fuse into (loss.tsdf_loss)
+    # need a dataset with a mesh / a survey, or a target that is re-fused as training goes: not part of the default eval_losses sweep
+    _unlisted = ('mesh_loss', 'cloud_loss', 'tsdf_loss')
 
 
 class Model(metaclass=_Names):
@@ -137,6 +139,11 @@ def slam_poses_csv(log_dir: str, name: str, slam: str):
 
 # the keys loss.cloud_loss reads from Config.loss_kwargs and their defaults (None: required)
 CLOUD_LOSS_DEFAULTS = {'cloud_point_to_plane': True, 'cloud_squared': False, 'cloud_max_dist': None, 'cloud_inlier_ratio': 1.0}
+
+# the keys loss.tsdf_loss and eval.tsdf_masks read from Config.loss_kwargs and their defaults (tsdf_trunc None: three voxels;
+# tsdf_max_residual None: the truncation)
+TSDF_LOSS_DEFAULTS = {'tsdf_voxel_size': 0.1, 'tsdf_trunc': None, 'tsdf_leave_one_out': True, 'tsdf_refresh_every': 10,
+                      'tsdf_squared': True, 'tsdf_max_residual': None}
 
 
 class Config(object):

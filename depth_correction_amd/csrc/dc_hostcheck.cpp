@@ -26,6 +26,7 @@
 #include "dc_tsdf_math.h"
 #include "dc_tsdf_sparse_math.h"
 #include "dc_tsdf_track_math.h"
+#include "dc_tsdf_loss_math.h"
 #include "dc_cons_route.h"
 
 // The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
@@ -1097,6 +1098,120 @@ int dc_host_tsdf_icp_accumulate(const double* x, const double* value, const doub
     dc::tsdf_track_add(x + 3 * i, value[i], grad + 3 * i, row);
     row[dc::IcpRow<6>::kUsed] += 1.0;
   }
+  return DC_OK;
+}
+
+// ---- self-supervised training against the fused volume (dc_tsdf_loss_math.h; dc_tsdf_loss.hip) ----
+// The sample with exclusion and the term at one world point x [3]: own_keys (or null) is ONE scan's segment of own_nb keys.  Returns the
+// class (0 used, 1 invalid, 2 unobserved, 3 gated); *phi, grad [3] the sample, *l and dl_dx [3] the term (0 unless used).
+int dc_host_tsdf_loss_point(const uint64_t* keys, const int32_t* slots, int64_t nb, int64_t capacity, const int64_t* sum, const int32_t* count,
+                            const uint64_t* own_keys, const int32_t* own_slots, int64_t own_nb, int64_t own_capacity, const int64_t* own_sum,
+                            const int32_t* own_count, const double* og, double voxel, double trunc, int min_count, const double* x, int squared,
+                            double max_residual, double* phi, double* grad, double* l, double* dl_dx) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  const dc::TsdfTable total{keys, slots, nb < 0 ? 0 : (nb > capacity ? capacity : nb), capacity, sum, count};
+  const dc::TsdfTable own{own_keys, own_slots, own_nb, own_capacity, own_sum, own_count};
+  const dc::TsdfSample s = dc::tsdf_sample_point_minus(x, g, trunc, min_count, total, own);
+  const int cls = dc::tsdf_loss_class(s, max_residual);
+  *phi = s.phi;
+  for (int a = 0; a < 3; ++a) { grad[a] = s.grad[a]; dl_dx[a] = 0.0; }
+  *l = 0.0;
+  if (cls == dc::kTsdfLossUsed) *l = dc::tsdf_loss_term(s.phi, s.grad, squared != 0, dl_dx);
+  return cls;
+}
+
+// dc_tsdf_loss on host arrays with plain loops, point after point in index order (NOT the kernel's summation order: the tests compare
+// it with the extended-precision oracle within the derived bound).  The arguments and the outputs are those of dc_tsdf_loss.
+int dc_host_tsdf_loss(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                      const int32_t* count, const uint64_t* own_keys, const int32_t* own_slots, const int64_t* own_ptr, int64_t n_own_keys,
+                      int64_t own_capacity, const int64_t* own_sum, const int32_t* own_count, const double* og, double voxel, double trunc,
+                      int min_count, const void* vps, const void* dirs, const void* depth, const void* inc, const uint8_t* lmask,
+                      const uint8_t* mask, int dtype, int64_t n, const int64_t* scan_ptr, const double* poses, int n_scans, int model_kind,
+                      int n_terms, const double* w, const double* e, int want_exponent, int squared, double max_residual, double* value_out,
+                      uint8_t* flag_out, double* x_out, double* out) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  if (n < 0 || n_scans < 0 || !out || !keys || !slots || !n_blocks || !sum || !count) return DC_ERR_ARG;
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (!dc::tsdf_lattice_ok(g) || !(trunc > 0.0) || !std::isfinite(trunc) || min_count < 1 || capacity < 1 || capacity >= ((int64_t)1 << 22) ||
+      std::isnan(max_residual))
+    return DC_ERR_ARG;
+  if (own_keys && (!own_slots || !own_ptr || !own_sum || !own_count || n_own_keys < 0 || own_capacity < 1)) return DC_ERR_ARG;
+  if (model_kind < DC_MODEL_NONE || model_kind > DC_MODEL_LAST) return DC_ERR_ARG;
+  if (model_kind == DC_MODEL_NONE) n_terms = 0;
+  else if (n_terms < 1 || n_terms > DC_MAX_MODEL_TERMS || !w || !e || (n > 0 && !inc)) return DC_ERR_ARG;
+  if (n > 0 && (n_scans < 1 || !dirs || !depth)) return DC_ERR_ARG;
+  if (n_scans > 1 && !scan_ptr) return DC_ERR_ARG;
+  dc::ModelParams mp;
+  mp.kind = model_kind;
+  mp.n_terms = n_terms;
+  for (int k = 0; k < DC_MAX_MODEL_TERMS; ++k) { mp.w[k] = k < n_terms ? w[k] : 0.0; mp.e[k] = k < n_terms ? e[k] : 0.0; }
+  const int nt = n_terms, o_grad = 5 + 2 * nt;
+  for (int q = 0; q < o_grad + 12 * n_scans; ++q) out[q] = 0.0;
+  const int64_t nb = *n_blocks < 0 ? 0 : (*n_blocks > capacity ? capacity : *n_blocks);
+  const dc::TsdfTable total{keys, slots, nb, capacity, sum, count};
+  const double nan = std::nan("");
+  for (int s = 0; s < n_scans; ++s) {
+    int64_t a = scan_ptr ? scan_ptr[s] : 0, b = scan_ptr ? scan_ptr[s + 1] : n;
+    a = a < 0 ? 0 : (a > n ? n : a);
+    b = b < a ? a : (b > n ? n : b);
+    dc::TsdfTable own{nullptr, nullptr, 0, own_capacity, own_sum, own_count};
+    if (own_keys) {
+      int64_t oa = own_ptr[s], ob = own_ptr[s + 1];
+      oa = oa < 0 ? 0 : (oa > n_own_keys ? n_own_keys : oa);
+      ob = ob < oa ? oa : (ob > n_own_keys ? n_own_keys : ob);
+      own.keys = own_keys + oa; own.slots = own_slots + oa; own.nb = ob - oa;
+    }
+    double T12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    if (poses) for (int q = 0; q < 12; ++q) T12[q] = poses[(int64_t)s * 12 + q];
+    double* gT = out + o_grad + (int64_t)s * 12;
+    for (int64_t j = a; j < b; ++j) {
+      double x[3] = {nan, nan, nan}, value = nan;
+      int cls = dc::kTsdfLossMasked;
+      if (mask ? mask[j] != 0 : true) {
+        double vp[3] = {0.0, 0.0, 0.0}, dr[3], vr[3], drr[3];
+        if (vps) host_load3(vps, dtype, j, vp);
+        host_load3(dirs, dtype, j, dr);
+        const double d = host_load1(depth, dtype, j);
+        const bool lm = lmask ? lmask[j] != 0 : true;
+        const double ia = model_kind != DC_MODEL_NONE ? host_load1(inc, dtype, j) : 0.0;
+        const double dcorr = dc::model_depth(mp, d, lm ? ia : 0.0, lm);
+        dc::rot3(T12, vp, vr);
+        dc::rot3(T12, dr, drr);
+        for (int c = 0; c < 3; ++c) x[c] = (vr[c] + T12[4 * c + 3]) + dcorr * drr[c];
+        const dc::TsdfSample sm = dc::tsdf_sample_point_minus(x, g, trunc, min_count, total, own);
+        cls = dc::tsdf_loss_class(sm, max_residual);
+        if (sm.flag == 0) value = sm.phi;
+        if (cls == dc::kTsdfLossUsed) {
+          double gx[3];
+          out[0] += dc::tsdf_loss_term(sm.phi, sm.grad, squared != 0, gx);
+          out[1] += 1.0;
+          // dL/dd' = dir . (R^T g)
+          double gd = 0.0;
+          for (int c = 0; c < 3; ++c) gd += dr[c] * (T12[c] * gx[0] + T12[4 + c] * gx[1] + T12[8 + c] * gx[2]);
+          if (model_kind > DC_MODEL_SCALED_POLYNOMIAL && lm) {
+            for (int k = 0; k < nt && k < 3; ++k) out[5 + k] += gd * dc::model_dw_other(mp, k, d, ia);
+          } else if (model_kind != DC_MODEL_NONE && lm) {
+            const double base = model_kind == DC_MODEL_SCALED_POLYNOMIAL ? -d * gd : -gd;
+            for (int k = 0; k < nt; ++k) {
+              const double pk = dc::pow_term(ia, mp.e[k]);
+              out[5 + k] += base * pk;
+              if (want_exponent) out[5 + nt + k] += ia > 0.0 ? base * mp.w[k] * pk * std::log(ia) : 0.0;
+            }
+          }
+          const double xl[4] = {vp[0] + dcorr * dr[0], vp[1] + dcorr * dr[1], vp[2] + dcorr * dr[2], 1.0};
+          for (int q = 0; q < 12; ++q) gT[q] += gx[q >> 2] * xl[q & 3];
+        } else {
+          out[cls == dc::kTsdfLossGated ? 2 : (cls == dc::kTsdfLossUnobserved ? 3 : 4)] += 1.0;
+        }
+      }
+      if (value_out) value_out[j] = value;
+      if (flag_out) flag_out[j] = (uint8_t)cls;
+      if (x_out) for (int c = 0; c < 3; ++c) x_out[3 * j + c] = x[c];
+    }
+  }
+  const double M = out[1];
+  out[0] = M > 0.0 ? out[0] / M : nan;
+  for (int q = 5; q < o_grad + 12 * n_scans; ++q) out[q] = M > 0.0 ? out[q] / M : 0.0;
   return DC_OK;
 }
 

@@ -168,8 +168,9 @@ def eval_loss_clouds(clouds, poses, pose_deltas, masks, ns, model, loss_fun, cfg
         feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
         return loss, loss_cloud, poses_upd, feat
 
-    if cfg.loss in ('mesh_loss', 'cloud_loss'):
-        # supervised: masks[i] = (the sequence's ground-truth mesh / survey, point mask or None) -- see mesh_masks, survey_masks
+    if cfg.loss in ('mesh_loss', 'cloud_loss', 'tsdf_loss'):
+        # masks[i] = (the sequence's ground-truth mesh / survey / TSDF target, point mask or None) -- see mesh_masks, survey_masks,
+        # tsdf_masks
         loss, loss_cloud = loss_fun(clouds, poses_upd, model, masks=masks)
         feat = [LazyFeatureCloud(c, model, p, nn, cfg) for c, p, nn in zip(clouds, poses_upd, ns)] if ns else None
         return loss, loss_cloud, poses_upd, feat
@@ -254,6 +255,25 @@ def survey_masks(datasets, names, all_clouds, cfg=None):
     return out
 
 
+def tsdf_masks(datasets, names, all_clouds, cfg=None):
+    """tsdf_loss's per-sequence ``masks``: (a loss.TsdfTarget of its own, built from cfg.loss_kwargs over config.TSDF_LOSS_DEFAULTS, the
+    scans' masks concatenated -- the points the model corrects, which are the rays the target fuses -- or None when no scan has one)."""
+    from .config import TSDF_LOSS_DEFAULTS
+    from .loss import TsdfTarget
+    kw = dict(TSDF_LOSS_DEFAULTS)
+    kw.update({k: v for k, v in (getattr(cfg, 'loss_kwargs', None) or {}).items() if k in TSDF_LOSS_DEFAULTS})
+    out = []
+    for ds, name, clouds in zip(datasets, names, all_clouds):
+        target = TsdfTarget(kw['tsdf_voxel_size'], trunc=kw['tsdf_trunc'], leave_one_out=kw['tsdf_leave_one_out'],
+                            refresh_every=kw['tsdf_refresh_every'])
+        point_mask = None
+        if any(c.mask is not None for c in clouds):
+            point_mask = torch.cat([c.mask if c.mask is not None else torch.ones((len(c),), dtype=torch.bool, device=c.dirs.device)
+                                    for c in clouds])
+        out.append((target, point_mask))
+    return out
+
+
 def _load_test_sequences(cfg: Config, test_datasets):
     """Local clouds and poses of every test sequence (eval.py:147-164): ball neighbourhoods get local feature clouds, plane
     neighbourhoods plain DepthClouds (as train._load_sequences)."""
@@ -316,6 +336,8 @@ def eval_loss(cfg: Config, test_datasets=None, test_ns=None, model=None, loss_fu
         test_masks = mesh_masks(test_datasets, test_names, test_clouds)
     elif cfg.loss == 'cloud_loss':
         test_masks = survey_masks(test_datasets, test_names, test_clouds, cfg)
+    elif cfg.loss == 'tsdf_loss':
+        test_masks = tsdf_masks(test_datasets, test_names, test_clouds, cfg)
     test_pose_deltas = _test_pose_deltas(cfg, test_datasets)
     if test_ns is None:
         test_ns = [establish_neighborhoods(clouds=clouds, poses=poses, cfg=cfg) for clouds, poses in zip(test_clouds, test_poses)]
@@ -774,7 +796,7 @@ def _landscape_kernel(clouds, poses_upd, masks, ns, model, w, cfg: Config):
 def _loop_count(views, cfg: Config):
     """Entries behind the loop's mean: the fused views' counts, else the loss clouds' entries (loss.reduce keeps the finite /
     non-NaN ones under only_finite / skip_nans); nan for the ICP loss, which is no mean over points."""
-    if cfg.loss in ('icp_loss', 'mesh_loss', 'cloud_loss'):   # (mesh_loss, cloud_loss: the mean of the sequences' means)
+    if cfg.loss in ('icp_loss', 'mesh_loss', 'cloud_loss', 'tsdf_loss'):   # (mesh_loss, cloud_loss, tsdf_loss: the mean of the sequences' means)
         return float('nan')
     kw = cfg.loss_kwargs
     total = 0.0

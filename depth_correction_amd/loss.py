@@ -11,6 +11,9 @@ Two execution paths produce the same numbers:
 and backward (weights, exponents, poses) out of one dc_mesh_loss call per sequence.
 ``cloud_loss`` is the same against a surveyed point cloud (survey.SurveyCloud): point-to-plane or point-to-point distances to the
 nearest survey points, gated and trimmed, out of one dc_cloud_loss call per sequence.
+``tsdf_loss`` is the self-supervised counterpart of the two: the target is the sparse TSDF volume the sequence's own corrected scans
+fuse into (``TsdfTarget``, re-fused as training goes), each scan scored against the volume of the other scans, out of one dc_tsdf_loss
+call per sequence.
 ``icp_loss`` with precomputed correspondences runs as one kernel per scan pair (dc_p2plane_sequence for
 point-to-plane, dc_p2point_sequence for point-to-point distances) including its backward to the model weights and
 poses; ``point_to_point_dist`` as a metric on GPU clouds (scripts/model_poses_learning:142-146) uses the same kernel.
@@ -29,7 +32,7 @@ from .segmentation import Planes
 from .utils import trace
 
 __all__ = ['batch_loss', 'cloud_loss', 'create_loss', 'icp_loss', 'loss_by_name', 'mesh_loss', 'min_eigval_loss', 'point_to_plane_dist',
-           'point_to_point_dist', 'reduce', 'Reduction', 'trace_loss', 'icp_correspondences']
+           'point_to_point_dist', 'reduce', 'Reduction', 'trace_loss', 'icp_correspondences', 'tsdf_loss', 'TsdfTarget']
 
 
 class Reduction(Enum):
@@ -583,8 +586,179 @@ def cloud_loss(clouds, poses=None, model=None, masks=None, **kwargs):
                       _unfused_cloud_sequence, _cloud_options, clouds, poses, model, masks, kwargs)
 
 
+# ---- self-supervised loss against the volume the sequence's own scans fuse into ---------------------------------------------------
+class TsdfTarget(object):
+    """The per-sequence target of tsdf_loss: the sparse TSDF volume (reconstruction.SparseTsdfVolume, voxels of ``voxel_size`` metres,
+    truncation ``trunc``, None: three voxels) that the corrected, posed scans of the sequence fuse into, re-fused as the model and the
+    poses move.  ``leave_one_out``: every scan is scored against the volume of the OTHER scans, so that it does not pull the map
+    towards itself; the volume's sums are integers, so that volume is bit for bit the total minus the volume of the scan alone, and
+    S + 1 volumes are fused instead of S volumes of S - 1 scans.  The target counts the evaluations tsdf_loss makes with it and
+    re-fuses before evaluation 0 and then before every ``refresh_every``-th (0: never again).  ``min_count``, ``max_blocks``,
+    ``min_depth``, ``max_range`` as for SparseTsdfVolume and its integrate.
+
+    A re-fusion reads the host (the pools grow as the scans need them), so an evaluation cannot be captured into a graph: asked to
+    evaluate during a stream capture, the target raises unless ``refresh_every`` is 0, and train()'s loop then runs eagerly."""
+
+    def __init__(self, voxel_size, trunc=None, leave_one_out=True, refresh_every=1, min_count=1, max_blocks=None, min_depth=0.,
+                 max_range=None):
+        self.voxel_size = float(voxel_size)
+        self.trunc = 3.0 * self.voxel_size if trunc is None else float(trunc)
+        if not (self.voxel_size > 0.0 and self.trunc > 0.0 and self.trunc < float('inf') and self.voxel_size < float('inf')):
+            raise ValueError('TsdfTarget needs a voxel size and a truncation > 0, got %r and %r' % (voxel_size, trunc))
+        self.leave_one_out, self.refresh_every, self.min_count = bool(leave_one_out), int(refresh_every), int(min_count)
+        if self.refresh_every < 0 or self.min_count < 1:
+            raise ValueError('TsdfTarget needs refresh_every >= 0 and min_count >= 1, got %r and %r' % (refresh_every, min_count))
+        self.max_blocks, self.min_depth, self.max_range = max_blocks, float(min_depth), max_range
+        self.evaluations = self.refreshes = 0
+        self.total = self.tables = self.own = None
+        self._scans, self._loo = None, None
+
+    def _volume(self, device):
+        from .reconstruction import SparseTsdfVolume
+        return SparseTsdfVolume(self.voxel_size, trunc=self.trunc, max_blocks=self.max_blocks, device=device)
+
+    def _fuse(self, scans, device):
+        volume = self._volume(device)
+        for cloud, pose in scans:
+            volume.integrate(cloud, pose=pose, min_depth=self.min_depth, max_range=self.max_range)
+        return volume
+
+    def refresh(self, seq_clouds, seq_poses=None, model=None):
+        """Re-fuses the target from the scans ``seq_clouds`` (sensor frame) corrected by ``model(cloud)`` as reconstruct does and moved
+        by ``seq_poses`` ([4,4] each, None: identity): the total volume and, with leave_one_out, one volume per scan, concatenated
+        into one table with one pool.  Nothing of it enters an autograd graph."""
+        device = seq_clouds[0].dirs.device
+        with torch.no_grad():
+            clouds = [model(c) for c in seq_clouds] if model is not None else list(seq_clouds)
+            eye = torch.eye(4, dtype=torch.float64)
+            poses = [eye if seq_poses is None else seq_poses[i].detach().to(torch.float64).cpu() for i in range(len(clouds))]
+            self._scans, self._loo = list(zip(clouds, poses)), None
+            self.total = self._fuse(self._scans, device)
+            self.tables = self.total.tables()
+            self.own = None
+            if self.leave_one_out:
+                keys, slots, sums, counts, ptr_host = [], [], [], [], [0]
+                for scan in self._scans:
+                    v = self._fuse([scan], device)
+                    nb = v.n_blocks
+                    keys.append(v._keys[:nb])
+                    slots.append(v._slots[:nb] + ptr_host[-1])        # a volume hands out the slots 0 .. nb - 1: its pool is [:nb]
+                    sums.append(v._sum[:nb])
+                    counts.append(v._count[:nb])
+                    ptr_host.append(ptr_host[-1] + nb)
+                if ptr_host[-1] == 0:                                 # no scan wrote a block: a pool of one empty block
+                    sums.append(torch.zeros((1, 512), dtype=torch.int64, device=device))
+                    counts.append(torch.zeros((1, 512), dtype=torch.int32, device=device))
+                self.own = ops.TsdfOwnTables(torch.cat(keys).contiguous(), torch.cat(slots).to(torch.int32).contiguous(),
+                                             torch.tensor(ptr_host, dtype=torch.int64, device=device), torch.cat(sums).contiguous(),
+                                             torch.cat(counts).contiguous())
+        self.refreshes += 1
+        return self
+
+    def before_evaluation(self, seq_clouds, seq_poses=None, model=None):
+        """Counts one evaluation of tsdf_loss with this target and re-fuses first when it is due.  A stream capture runs nothing and is
+        not counted (nor are the replays of the graph it makes, which the host does not see: with refresh_every = 0, the one setting
+        that can be captured, the count decides nothing any more)."""
+        due = self.total is None or (self.refresh_every > 0 and self.evaluations % self.refresh_every == 0)
+        if torch.cuda.is_current_stream_capturing():
+            if due or self.refresh_every > 0:
+                raise RuntimeError('a TsdfTarget with refresh_every = %d re-fuses between evaluations and cannot be captured into a graph'
+                                   % self.refresh_every)
+            return
+        if due:
+            self.refresh(seq_clouds, seq_poses, model)
+        self.evaluations += 1
+
+    def leave_one_out_volumes(self):
+        """The S volumes of S - 1 scans each, fused explicitly from the scans of the last refresh: what the subtraction stands for,
+        and what the tensor form of the loss samples (built on first use after a refresh)."""
+        if self._scans is None:
+            raise RuntimeError('the target has not been fused yet: call refresh first')
+        if self._loo is None:
+            device = self.total.device
+            self._loo = [self._fuse([sc for j, sc in enumerate(self._scans) if j != s], device) for s in range(len(self._scans))]
+        return self._loo
+
+
+class _TsdfLossPlan(_ScanLossPlan):
+    """The target, whose tables are read anew at every call: a refresh replaces them."""
+    header, _workspace = 5, staticmethod(ops.tsdf_loss_workspace)
+
+    def __init__(self, seq_clouds, target, point_mask, with_model):
+        super().__init__(seq_clouds, point_mask, with_model)
+        self.target = target
+
+    def _call(self, poses12, kind, w, e, **opts):
+        t = self.target
+        return ops.tsdf_loss(t.tables, self.ps, self.scan_ptr, poses12, kind, w, e, mask=self.mask, own=t.own, min_count=t.min_count,
+                             **opts)
+
+
+_tsdf_plans = PlanRegistry()
+
+
+def _unfused_tsdf_sequence(seq_clouds, seq_poses, model, target, point_mask, squared, max_residual, return_used=False):
+    """The same loss from tensor operations: x in fp64 through the model and the poses, the sample (detached) from
+    SparseTsdfVolume.sample -- with leave-one-out, of S explicitly fused volumes of the other scans, which checks the subtraction
+    independently -- l from phi(x0) + grad . (x - x0), torch autograd.  For models without a kernel kind, and what the fused form is
+    tested against."""
+    dev = seq_clouds[0].dirs.device
+    with torch.no_grad():
+        keep = torch.cat([torch.isfinite(c.vps.expand(len(c), 3)).all(dim=1) & torch.isfinite(c.dirs).all(dim=1)
+                          & torch.isfinite(c.depth).reshape(-1) for c in seq_clouds])
+        scan_of = torch.cat([torch.full((len(c),), s, dtype=torch.int64, device=dev) for s, c in enumerate(seq_clouds)])[keep]
+    x = _posed_points64(seq_clouds, seq_poses, model, keep)
+    x0 = x.detach().contiguous()
+    in_mask = torch.ones((x.shape[0],), dtype=torch.bool, device=dev) if point_mask is None \
+        else torch.as_tensor(point_mask, device=dev).to(torch.bool)[keep]
+    if target.leave_one_out:
+        phi0 = torch.full((x.shape[0],), float('nan'), dtype=torch.float64, device=dev)
+        grad = torch.zeros((x.shape[0], 3), dtype=torch.float64, device=dev)
+        flag = torch.full((x.shape[0],), 255, dtype=torch.uint8, device=dev)
+        for s, volume in enumerate(target.leave_one_out_volumes()):
+            rows = torch.nonzero(scan_of == s).reshape(-1)
+            if rows.numel():
+                smp = volume.sample(x0[rows], min_count=target.min_count)
+                phi0[rows], grad[rows], flag[rows] = smp['value'], smp['grad'], smp['flag']
+    else:
+        smp = target.total.sample(x0, min_count=target.min_count)
+        phi0, grad, flag = smp['value'], smp['grad'], smp['flag']
+    gate = target.trunc if max_residual is None else float(max_residual)
+    used = in_mask & (flag == 0) & (phi0.abs() < gate)
+    phi = phi0[used] + (grad[used] * (x[used] - x0[used])).sum(dim=-1)
+    loss = (phi * phi).mean() if squared else phi.abs().mean()     # (abs: zero gradient at phi = 0, as in the kernel)
+    if return_used:
+        full = torch.zeros((keep.shape[0],), dtype=torch.bool, device=dev)
+        full[keep] = used
+        return loss, full
+    return loss
+
+
+def _tsdf_options(kwargs):
+    max_residual = kwargs.get('tsdf_max_residual')
+    return dict(squared=bool(kwargs.get('tsdf_squared', True)), max_residual=None if max_residual is None else float(max_residual))
+
+
+def tsdf_loss(clouds, poses=None, model=None, masks=None, **kwargs):
+    """Self-supervised loss against the volume the scans themselves fuse into, over lists of sequences of scans: the mean squared
+    (``tsdf_squared``, default True: the sum of phi^2 is what the scan-to-TSDF tracker minimises) or absolute trilinear distance phi
+    of the corrected, posed points of a sequence to the surface of its TsdfTarget; ``tsdf_max_residual`` (None: the truncation):
+    points with |phi| >= it are left out -- averaged over the sequences like icp_loss.  ``masks[i]`` = (TsdfTarget, bool point mask
+    [N_i] or None) of sequence ``i``; the target re-fuses itself inside this call when it is due (TsdfTarget.refresh_every), from
+    the clouds, the poses and the model of the call.  Differentiable to the model's weights and exponents and to the poses, the
+    volume held constant; GPU clouds with a kernel model (or none) and poses take one dc_tsdf_loss call per sequence
+    (``fused=False`` forces the tensor form)."""
+    if clouds and clouds[0] and clouds[0][0].dirs.is_cuda and masks is not None and len(masks) == len(clouds):
+        for i, seq in enumerate(clouds):
+            tgt = masks[i][0] if isinstance(masks[i], (tuple, list)) else masks[i]
+            if isinstance(tgt, TsdfTarget):
+                tgt.before_evaluation(seq, None if poses is None else poses[i], model)
+    return _scan_loss('tsdf_loss', ('TsdfTarget', 'TSDF target', ('before_evaluation', 'tables')), _tsdf_plans, _TsdfLossPlan,
+                      _unfused_tsdf_sequence, _tsdf_options, clouds, poses, model, masks, kwargs)
+
+
 def loss_by_name(name):
-    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss', 'mesh_loss', 'cloud_loss')
+    assert name in ('min_eigval_loss', 'trace_loss', 'icp_loss', 'mesh_loss', 'cloud_loss', 'tsdf_loss')
     return globals()[name]
 
 

@@ -23,6 +23,7 @@ __all__ = [
     'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
     'planereg_hypotheses', 'planereg_select', 'tsdf_k_steps', 'tsdf_integrate', 'tsdf_extract',
     'tsdf_sparse_allocate', 'tsdf_sparse_integrate', 'tsdf_sparse_extract', 'tsdf_sparse_sample', 'tsdf_icp_accumulate',
+    'TsdfTables', 'TsdfOwnTables', 'tsdf_loss', 'tsdf_loss_workspace',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -2685,3 +2686,92 @@ def tsdf_icp_accumulate(sample, threshold, max_residual, state, status, partials
     check(lib().dc_tsdf_icp_accumulate(ptr(x), ptr(sample['value']), ptr(sample['grad']), ptr(sample['dist']), ptr(sample['flag']), m,
                                        ptr(threshold), max_residual, ptr(state), ptr(status), ptr(partials), nb, ptr(kept), stream_ptr()),
           'dc_tsdf_icp_accumulate')
+
+
+# ------------------------------------------------------------------------------------------------
+# self-supervised training against the fused volume (csrc/dc_tsdf_loss.hip, loss.TsdfTarget)
+# ------------------------------------------------------------------------------------------------
+TSDF_LOSS_USED, TSDF_LOSS_INVALID, TSDF_LOSS_UNOBSERVED, TSDF_LOSS_GATED, TSDF_LOSS_MASKED = 0, 1, 2, 3, 255
+
+
+class TsdfTables(object):
+    """A sparse volume as tsdf_loss reads it: the table keys i64 [capacity] / slots i32 [capacity] / n_blocks i64 [1], the pool sum i64 /
+    count i32 [capacity, 512], and the lattice (origin [3], voxel, trunc).  reconstruction.SparseTsdfVolume.tables() makes one."""
+
+    def __init__(self, keys, slots, n_blocks, sum_, count, origin, voxel, trunc):
+        self.keys, self.slots, self.n_blocks, self.sum, self.count = keys, slots, n_blocks, sum_, count
+        self.origin, self.voxel, self.trunc = tuple(float(v) for v in origin), float(voxel), float(trunc)
+        self.device = keys.device
+
+
+class TsdfOwnTables(object):
+    """The volumes of the single scans of a sequence as ONE structure: keys i64 [sum nb_s], ascending within each scan's segment, slots
+    i32 already offset into the shared pool sum i64 / count i32 [cap_own, 512], ptr i64 [S+1] (scan s owns keys[ptr[s]:ptr[s+1]])."""
+
+    def __init__(self, keys, slots, ptr_, sum_, count):
+        self.keys, self.slots, self.ptr, self.sum, self.count = keys, slots, ptr_, sum_, count
+
+
+def tsdf_loss_workspace(n, n_scans, n_terms, device):
+    """Workspace of tsdf_loss for the given sizes (uint8 tensor)."""
+    return _ws(lib().dc_tsdf_loss_workspace_bytes(int(n), int(n_scans), int(n_terms)), device)
+
+
+@on_device
+def tsdf_loss(volume_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=None, mask=None, own=None, squared=True, max_residual=None,
+              min_count=1, want_exponent=False, want_points=False, out=None, ws=None):
+    """Mean squared (``squared``) or absolute trilinear distance of the corrected, posed points of a sequence to the surface held by
+    the sparse volume ``volume_dev`` (TsdfTables), with its gradient, in one host call of two launches (dc_tsdf_loss; the rule:
+    csrc/dc_tsdf_loss_math.h).  ``ps``, ``scan_ptr``, ``poses12``, ``mask`` as for mesh_loss.  ``own`` (TsdfOwnTables): scan s is scored
+    against the volume minus its own contribution (leave-one-out); None: no exclusion.  ``max_residual`` (None: the truncation): points
+    with |phi| >= it are gated; a voxel counts as observed from ``min_count`` samples on.  Returns out f64 [5 + 2P + 12 S] = {mean
+    loss, used, gated, unobserved, invalid, dL/dw, dL/dexponent (zero unless ``want_exponent``), dL/d[R|t]}; with ``want_points``
+    also (value f64 [N]: phi, NaN unless observed; flag u8 [N]: TSDF_LOSS_*; x f64 [N,3]: the points, NaN outside the mask)."""
+    if not isinstance(volume_dev, TsdfTables):
+        raise TypeError('tsdf_loss takes the volume as ops.TsdfTables, got %s' % type(volume_dev).__name__)
+    dev, capacity = _tsdf_sparse_table(volume_dev.keys, volume_dev.slots, volume_dev.n_blocks, 'tsdf_loss')
+    if ps.device != dev:
+        raise RuntimeError('points are on %s, the volume on %s' % (ps.device, dev))
+    kind, nt, w, e, ns = _scan_loss_args(ps, scan_ptr, poses12, model_kind, w, e, mask, dev)
+    need(volume_dev.sum, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='sum', device=dev)
+    need(volume_dev.count, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='count', device=dev)
+    origin, voxel, trunc, min_count = volume_dev.origin, volume_dev.voxel, volume_dev.trunc, int(min_count)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin) or not (voxel > 0.0 and math.isfinite(voxel)) or \
+            not (trunc > 0.0 and math.isfinite(trunc)):
+        raise ValueError('tsdf_loss needs a finite origin of 3 values, a voxel size and a truncation > 0, got %r, %r and %r'
+                         % (origin, voxel, trunc))
+    if min_count < 1:
+        raise ValueError('tsdf_loss needs min_count >= 1, got %d' % min_count)
+    mr = trunc if max_residual is None else float(max_residual)
+    if math.isnan(mr):
+        raise ValueError('max_residual must not be NaN')
+    own_args = (None, None, None, 0, 0, None, None)
+    if own is not None:
+        if not isinstance(own, TsdfOwnTables):
+            raise TypeError('tsdf_loss takes own as ops.TsdfOwnTables, got %s' % type(own).__name__)
+        need(own.keys, (None,), dtype=torch.int64, name='own keys', device=dev)
+        nk = own.keys.shape[0]
+        need(own.slots, (nk,), dtype=torch.int32, name='own slots', device=dev)
+        need(own.ptr, (ns + 1,), dtype=torch.int64, name='own ptr', device=dev)
+        need(own.sum, (None, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='own sum', device=dev)
+        cap_own = own.sum.shape[0]
+        need(own.count, (cap_own, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='own count', device=dev)
+        if cap_own < 1:
+            raise ValueError('tsdf_loss needs an own pool of at least one block')
+        # (keys of an empty tensor have no address: a table without keys is still a table, so it gets the pool's)
+        own_args = (ptr(own.keys) if nk else ptr(own.sum), ptr(own.slots) if nk else ptr(own.sum), ptr(own.ptr), nk, cap_own,
+                    ptr(own.sum), ptr(own.count))
+    n_out = 5 + 2 * nt + 12 * ns
+    out = _out_arg(out, n_out, dev)
+    ws = _ws_arg(ws, lib().dc_tsdf_loss_workspace_bytes(ps.n, ns, nt), dev)
+    value = flag = x = None
+    if want_points:
+        value = torch.empty((ps.n,), dtype=torch.float64, device=dev)
+        flag = torch.empty((ps.n,), dtype=torch.uint8, device=dev)
+        x = torch.empty((ps.n, 3), dtype=torch.float64, device=dev)
+    check(lib().dc_tsdf_loss(ptr(volume_dev.keys), ptr(volume_dev.slots), ptr(volume_dev.n_blocks), capacity, ptr(volume_dev.sum),
+                             ptr(volume_dev.count), *own_args, *origin, voxel, trunc, min_count, ptr(ps.vps), ptr(ps.dirs), ptr(ps.depth),
+                             ptr(ps.inc), ptr(ps.lmask), ptr(mask), dtype_code(ps.dirs), ps.n, ptr(scan_ptr), ptr(poses12), ns, kind, nt,
+                             ptr(w), ptr(e), int(bool(want_exponent)), int(bool(squared)), mr, ptr(value), ptr(flag), ptr(x), ptr(out),
+                             ptr(ws), ws.shape[0], stream_ptr()), 'dc_tsdf_loss')
+    return (out, value, flag, x) if want_points else out

@@ -265,6 +265,10 @@ class SparseTsdfVolume(object):
             count[have] = self._count.reshape(-1)[at[have]]
         return sum_, count
 
+    def tables(self):
+        """The table, the pool and the lattice as ops.tsdf_loss reads them (ops.TsdfTables; the tensors are shared, not copied)."""
+        return ops.TsdfTables(self._keys, self._slots, self._n_blocks, self._sum, self._count, self.origin, self.voxel_size, self.trunc)
+
     def sample(self, points, pose=None, min_count=1, stop=None, out=None):
         """The fused signed distance at ``points`` [M,3] (moved by ``pose`` 4 x 4 when given): dict(x f64 [M,3] the moved points, value
         [M] metres (trilinear over the eight voxels around a point), grad [M,3] its gradient, dist [M] = |value|, flag u8 [M]: 0, 1 out of

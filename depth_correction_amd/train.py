@@ -124,7 +124,7 @@ def _loss_weight(cfg, clouds, loss_clouds):
     add up: the number of pointwise terms behind a min-eigenvalue / trace mean (batch_loss concatenates the pointwise
     losses of all sequences and reduces once, loss.py:205-213), the number of sequences behind an ICP mean
     (loss.py:403)."""
-    if cfg.loss in ('icp_loss', 'mesh_loss', 'cloud_loss'):   # mesh_loss, cloud_loss: the mean of the per-sequence means, like icp_loss
+    if cfg.loss in ('icp_loss', 'mesh_loss', 'cloud_loss', 'tsdf_loss'):   # mesh_loss, cloud_loss, tsdf_loss: the mean of the per-sequence means, like icp_loss
         return float(len(clouds))
     kw = cfg.loss_kwargs
     total = 0.0
@@ -147,7 +147,7 @@ def _zero_first_pose(pose_deltas):
 def _plan_registries():
     from . import eval as _eval, loss as _loss
     return [r for r in (_eval._plans, getattr(_loss, '_icp_plans', None), getattr(_loss, '_mesh_plans', None),
-                        getattr(_loss, '_cloud_plans', None)) if r is not None]
+                        getattr(_loss, '_cloud_plans', None), getattr(_loss, '_tsdf_plans', None)) if r is not None]
 
 
 def release_plans(keep=None):
@@ -185,6 +185,8 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
         raise NotImplementedError('mesh_loss is not supported by the sharded (multi-rank) training loops')
     if cfg.loss == 'cloud_loss' and sharded:
         raise NotImplementedError('cloud_loss is not supported by the sharded (multi-rank) training loops')
+    if cfg.loss == 'tsdf_loss' and sharded:
+        raise NotImplementedError('tsdf_loss is not supported by the sharded (multi-rank) training loops')
     if sharded and torch.device(cfg.device).type == 'cuda' and torch.device(cfg.device).index is not None:
         # object collectives (the checkpoint gather) and RCCL's own staging use torch's current device: it must be this
         # rank's GPU, whatever the launcher did.  An index-less 'cuda' means "the current device" (the launcher has already
@@ -258,6 +260,10 @@ def _train(cfg: Config, callbacks=None, train_datasets=None, val_datasets=None):
         from .eval import survey_masks
         train_masks = survey_masks(train_datasets, [str(ds) for ds in train_datasets], train_clouds, cfg)
         val_masks = survey_masks(val_datasets, [str(ds) for ds in val_datasets], val_clouds, cfg)
+    elif cfg.loss == 'tsdf_loss':                     # self-supervised: one re-fused target per sequence and the scans' own masks
+        from .eval import tsdf_masks
+        train_masks = tsdf_masks(train_datasets, [str(ds) for ds in train_datasets], train_clouds, cfg)
+        val_masks = tsdf_masks(val_datasets, [str(ds) for ds in val_datasets], val_clouds, cfg)
     elif plane:                                       # no global mask with plane neighbourhoods (eval.py:104-106)
         train_masks, val_masks = len(train_global) * [None], len(val_global) * [None]
     else:
@@ -680,7 +686,7 @@ def _native_pose_loop_plan(cfg, model, optimizer, val_optimizer, train_clouds, t
     None."""
     from .eval import _plan_for, fused_supported
     from .optim import Adam
-    if cfg.loss in ('mesh_loss', 'cloud_loss'):                   # run on _batched_loop / the plain loop
+    if cfg.loss in ('mesh_loss', 'cloud_loss', 'tsdf_loss'):      # run on _batched_loop / the plain loop
         return None
     kw = cfg.loss_kwargs
     w = getattr(model, 'w', None)
@@ -878,7 +884,7 @@ def _native_loop_plan(cfg, model, optimizer, train_clouds, train_poses, train_ma
     fused min-eigenvalue / trace loss without inlier gating -- else None."""
     from .eval import _plan_for, fused_supported
     from .optim import Adam
-    if cfg.loss in ('mesh_loss', 'cloud_loss'):                   # run on _batched_loop / the plain loop
+    if cfg.loss in ('mesh_loss', 'cloud_loss', 'tsdf_loss'):      # run on _batched_loop / the plain loop
         return None
     kw = cfg.loss_kwargs
     w = getattr(model, 'w', None)

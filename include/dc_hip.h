@@ -1077,6 +1077,35 @@ int dc_cloud_loss(void* grid_ws, size_t grid_ws_bytes, int64_t n_query_max, cons
                   int n_terms, const double* w, const double* e, int want_exponent, int plane, int squared, double max_dist,
                   double inlier_ratio, int32_t* idx_out, double* dist_out, double* resid_out, double* out, void* ws, size_t ws_bytes,
                   dcStream_t stream);
+/* ---- self-supervised training against the fused volume (depth_correction_amd/csrc/dc_tsdf_loss.hip; the rules:
+ * dc_tsdf_loss_math.h; DESIGN "Self-supervised training against the fused volume") ----
+ * The mean of l_j over the used points of a sequence, l_j = phi(x_j)^2 (squared) or |phi(x_j)|, phi the trilinear signed distance of
+ * a sparse TSDF volume at x_j, and its gradient, in one call of two launches (no atomics: the same inputs give the same bits).  The
+ * points and the model follow dc_mesh_loss: point j of scan s is x_j = R_s (vp_j + d'_j dir_j) + t_s exactly as dc_points_fwd forms it
+ * in fp64 (scan_ptr DEVICE int64 [n_scans+1], ascending from 0 to n, NULL with n_scans == 1).  The volume is the table and pool of
+ * dc_tsdf_sparse_sample (keys / slots [capacity], *n_blocks DEVICE and clamped to the capacity, sum int64 / count int32 [capacity,
+ * 512]) on the lattice (ox, oy, oz, voxel) with the truncation trunc.  Exclusion (own_keys != NULL): the volumes of the single
+ * scans, concatenated -- own_keys uint64 [n_own_keys] ascending within each scan's segment, own_slots int32 [n_own_keys] indexing
+ * the shared pool own_sum / own_count [own_capacity, 512], own_ptr DEVICE int64 [n_scans+1] (scan s owns own_ptr[s] ..
+ * own_ptr[s+1], clamped to n_own_keys); a point of scan s then sees sum = total - own_s and count = total - own_s on each of its eight
+ * voxels, a voxel being observed iff its block is in the total table and count >= min_count.  With own_keys == NULL the sample is
+ * bit-equal to dc_tsdf_sparse_sample.  A point in mask (uint8 [n], optional) is INVALID (x_j not finite or outside the lattice's
+ * range), UNOBSERVED (one of its eight voxels unobserved), GATED (|phi| >= max_residual, which must not be NaN: at max_residual =
+ * trunc a fully clamped sample is never used) or USED.  The volume is a constant of the gradient; dl/dx = 0 at phi = 0 in the |phi|
+ * form.
+ * out double [5 + 2 n_terms + 12 n_scans] = {L = sum l / M, M = used, gated, unobserved, invalid, dL/dw, dL/dexponent (zero unless
+ * want_exponent), dL/d[R|t] per scan row-major 3 x 4}; M == 0: L = NaN, zero gradients.  value_out double [n] (phi; NaN unless the
+ * point is in the mask and observed), flag_out uint8 [n] (0 used, 1 invalid, 2 unobserved, 3 gated, 255 not in the mask), x_out
+ * double [n,3] (NaN rows outside the mask), each optional.  ws: dc_tsdf_loss_workspace_bytes(n, n_scans, n_terms) bytes
+ * (DC_ERR_WORKSPACE).  n == 0 and scans without points are legal.  No allocation, copy or synchronisation. */
+size_t dc_tsdf_loss_workspace_bytes(int64_t n, int n_scans, int n_terms);
+int dc_tsdf_loss(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                 const int32_t* count, const uint64_t* own_keys, const int32_t* own_slots, const int64_t* own_ptr, int64_t n_own_keys,
+                 int64_t own_capacity, const int64_t* own_sum, const int32_t* own_count, double ox, double oy, double oz, double voxel,
+                 double trunc, int min_count, const void* vps, const void* dirs, const void* depth, const void* inc, const uint8_t* lmask,
+                 const uint8_t* mask, int dtype, int64_t n, const int64_t* scan_ptr, const double* poses, int n_scans, int model_kind,
+                 int n_terms, const double* w, const double* e, int want_exponent, int squared, double max_residual, double* value_out,
+                 uint8_t* flag_out, double* x_out, double* out, void* ws, size_t ws_bytes, dcStream_t stream);
 /* Blocks of dc_icp_accumulate for m reading points (partials double [blocks * DC_ICP_PARTIALS]). */
 int dc_icp_blocks(int64_t m);
 /* state double [DC_ICP_STATE_COUNT] <- the prior (DEVICE double [16]) as estimate and bound origin, history cleared; status int32 [4]
