@@ -25,6 +25,20 @@ struct PointBasis {
   double w_scale;                      // weights are staged as w_k * w_scale: 1 / grid step for q32, 1 for fp64 points
 };
 
+// ---- the per-block row copy of the one-pass step kernel of float32 clouds (dcSequenceDesc.step_rows, dc_step_rows_build) ------------
+// For every entry e of a slot table's blk_ids the basis row blk_ids[e], W = 6 + P words as they stand, stored where the block stages
+// it from: block b's nd = blk_ptr[b + 1] - blk_ptr[b] entries fill the words [W blk_ptr[b], W blk_ptr[b + 1]) of the copy -- the `base`
+// of the block's header addresses it, nothing else is needed.  Inside that stretch the rows lie PIECE-MAJOR: piece g is the words
+// [4 g, 4 g + step_rows_piece_words(W, g)) of a row, all nd entries of piece 0 first, then all of piece 1, ...:
+//     word c of entry t  at  W blk_ptr[b] + 4 (c / 4) nd + step_rows_piece_words(W, c / 4) t + c % 4.
+// Lane t of a wavefront therefore reads a piece right beside lane t + 1's: one contiguous stream per piece instead of a gather by id.
+// The 8-word row (two weights) is two 16-byte pieces, 16-byte aligned.  A row of 7 or 9 words keeps its words and no padding: its
+// LAST piece is short (3 words for one weight, 1 word for three), stored at that stride, and its pieces are only 4-byte aligned
+// (W blk_ptr[b] words is no multiple of four) -- as the 28- and 36-byte basis rows themselves are.
+__host__ __device__ constexpr int step_rows_piece_words(int row_words, int piece) {
+  return row_words - 4 * piece < 4 ? row_words - 4 * piece : 4;
+}
+
 // s_w[k] = w_k * w_scale for the lanes of the block (call before a barrier); coherent: the weights were written by other
 // blocks of this very launch (chained steps), so the load must not be served by this XCD's L2
 __device__ __forceinline__ void stage_weights(const PointBasis& pb, double* s_w, bool coherent = false) {
@@ -181,6 +195,23 @@ __global__ __launch_bounds__(kBlock) void points_basis_kernel(PointInputs in, in
       }
       Basis<PT>::write_term(rows, i, mp.n_terms, k, dk);
     }
+  }
+}
+
+// The per-block row copy (layout: step_rows_piece_words): one workgroup per 256-point block walks the W nd words of its stretch in
+// the order they are stored -- contiguous stores -- and gathers each from the basis row its entry names.  Every listed entry is
+// written, those of blocks the step kernel skips included; blk_ptr and blk_ids bound everything that is read or written.
+__global__ __launch_bounds__(kBlock) void step_rows_kernel(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ blk_ids,
+                                                           const int32_t* __restrict__ basis, int W, int32_t* __restrict__ out) {
+  const int32_t base = blk_ptr[blockIdx.x], nd = blk_ptr[blockIdx.x + 1] - base;
+  const int32_t* ids = blk_ids + base;
+  int32_t* stretch = out + (int64_t)base * W;
+  const int full = (W / 4) * 4 * nd;                                    // words of the whole pieces; the short last piece follows
+  for (int j = threadIdx.x; j < W * nd; j += kBlock) {
+    const int g = j < full ? j / (4 * nd) : W / 4;
+    const int gw = step_rows_piece_words(W, g);
+    const int r = j - 4 * g * nd, t = r / gw, c = r - t * gw;
+    stretch[j] = basis[(int64_t)ids[t] * W + 4 * g + c];
   }
 }
 

@@ -28,6 +28,21 @@ template <int P> struct StepRow<q32, P> {
   static __device__ __forceinline__ void stage(const PointBasis& pb, const double* wq, int64_t row, int4* tile, int cap, int t) {
     place(fetch(pb, row), wq, tile, cap, t);
   }
+  // Entry t of a block's list of `nd` rows, from one of two sources (the same for the whole launch): `crow`, the block's stretch of the
+  // per-block row copy (dcSequenceDesc.step_rows, layout: step_rows_piece_words) -- one trip, lane t beside lane t + 1 -- or, when it
+  // is null, the basis row ids[t]: the id first, then a gather.  The same words either way.
+  static __device__ __forceinline__ Raw fetch_copy(const int32_t* crow, int nd, int t) {
+    constexpr int W = 6 + P;
+    Raw o;
+#pragma unroll
+    for (int g = 0; g < kPieces; ++g) {
+      const int gw = step_rows_piece_words(W, g);
+      const int32_t* r = crow + (uint32_t)(4 * g * nd + gw * t);
+#pragma unroll
+      for (int c = 0; c < gw; ++c) o.q[4 * g + c] = r[c];
+    }
+    return o;
+  }
   static __device__ __forceinline__ void place(const Raw& raw, const double* wq, int4* tile, int cap, int t) {
     const int32_t* q = raw.q;
     float sc = 0.0f;                                      // exactly Basis<q32>::point's arithmetic
@@ -611,7 +626,9 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_kernel(
 //    deflation path only for needles);
 //  * the second sweep is float32 (the difference to the centre is an exact int32, u and c are float32 words, the per-centre
 //    factors are rounded once);
-//  * the wavefront sums go through DPP row operations.
+//  * the wavefront sums go through DPP row operations;
+//  * with `step_rows` (dcSequenceDesc.step_rows: the rows of every block's list stored once, in staging order) a block fetches its
+//    rows straight after its header, as contiguous streams, instead of its ids first and then the rows they name -- the same words.
 // A fp64-difference row format ({x - ref} as doubles: no int -> fp conversions in the sweeps, 80 instructions fewer) was measured
 // and dropped: 48-B rows make the kernel LDS-bound (SQ_LDS_IDX_ACTIVE 87 % of its duration, 56 % of it bank conflicts of the
 // random row reads: 61 us against 52).
@@ -719,8 +736,8 @@ __device__ unsigned long long* g_block_trace = nullptr;
 // BLOCKS: what the launch bounds ask for; dc_set_option(9, 1) runs the instantiation with six where the default is seven (A-B)
 template <int NS, int P, int CAP, int BLOCKS = step_q32_blocks<P, CAP>()>
 __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
-    PointBasis pb, BlockTab tab, const StepHdr* __restrict__ hdr, const int32_t* __restrict__ centre_idx, int64_t n,
-    LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd, StepChain ch) {
+    PointBasis pb, BlockTab tab, const StepHdr* __restrict__ hdr, const int32_t* __restrict__ step_rows, const int32_t* __restrict__ centre_idx,
+    int64_t n, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd, StepChain ch) {
   constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8;
   constexpr int cap = CAP;
   __shared__ int4 tile[StepRow<q32, P>::kPieces * CAP];
@@ -766,13 +783,24 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
       pk[j] = (uint32_t)lrow[(uint32_t)(2 * j * kBlock) + tid] |
               (2 * j + 1 < NS ? (uint32_t)lrow[(uint32_t)((2 * j + 1 < NS ? 2 * j + 1 : 0) * kBlock) + tid] << 16 : 0u);
     const int32_t* ids = tab.blk_ids + base;
+    // step_rows (launch-uniform): the rows of the block's list stored once, in the order they are staged (StepRow::fetch_listed); the
+    // table of ids is then not read at all
+    const int32_t* crow = step_rows ? step_rows + (int64_t)base * (6 + P) : nullptr;
     double wq[P];
     if (chained) {
       // fetch the rows this lane stages before waiting for the weights of this launch (consistency_step_basis_kernel)
       typename StepRow<q32, P>::Raw r0, r1;
       const int t0 = (int)tid, t1 = (int)tid + kBlock;
-      if (t0 < nd) r0 = StepRow<q32, P>::fetch(pb, ids[t0]);
-      if (t1 < nd) r1 = StepRow<q32, P>::fetch(pb, ids[t1]);
+      // (the two sources as two branches here, not as one address with selected operands: a wait for a load counts every load issued
+      // before it, and where the paths share code the wait for the ids stays in it -- the copy's rows would then wait for the
+      // positions requested above, one trip like the one they are there to save)
+      if (crow) {
+        if (t0 < nd) r0 = StepRow<q32, P>::fetch_copy(crow, nd, t0);
+        if (t1 < nd) r1 = StepRow<q32, P>::fetch_copy(crow, nd, t1);
+      } else {
+        if (t0 < nd) r0 = StepRow<q32, P>::fetch(pb, ids[t0]);
+        if (t1 < nd) r1 = StepRow<q32, P>::fetch(pb, ids[t1]);
+      }
       chain_weights<P>(ch, pb.w_scale, s_w, s_ok);
       __syncthreads();
       if (!s_ok[0]) bad = true;
@@ -780,13 +808,15 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
       for (int k = 0; k < P; ++k) wq[k] = s_w[k];
       if (t0 < nd) StepRow<q32, P>::place(r0, wq, tile, cap, t0);
       if (t1 < nd) StepRow<q32, P>::place(r1, wq, tile, cap, t1);
-      for (int t = (int)tid + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
+      if (crow) for (int t = (int)tid + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::place(StepRow<q32, P>::fetch_copy(crow, nd, t), wq, tile, cap, t);
+      else for (int t = (int)tid + 2 * kBlock; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
     } else {
       stage_weights(pb, s_w);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < P; ++k) wq[k] = s_w[k];
-      for (int t = (int)tid; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
+      if (crow) for (int t = (int)tid; t < nd; t += kBlock) StepRow<q32, P>::place(StepRow<q32, P>::fetch_copy(crow, nd, t), wq, tile, cap, t);
+      else for (int t = (int)tid; t < nd; t += kBlock) StepRow<q32, P>::stage(pb, wq, ids[t], tile, cap, t);
     }
     Pt<q32>::Raw ci;
     if (own < 0) ci = Basis<q32>::template point<P>(pb, wq, live ? (centre_idx ? (int64_t)(centre_idx + i0)[tid] : i0 + tid) : 0);

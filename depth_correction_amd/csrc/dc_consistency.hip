@@ -1183,6 +1183,8 @@ static std::atomic<bool> g_no_reverse{false};
 // dc_set_option(9, 1): consistency_step_q32_kernel built for six blocks per CU where the default is built for seven (the 512-row tile,
 // one or two weights): the same body under __launch_bounds__(kBlock, 6) (A-B, tests); the other instantiations are not affected
 static std::atomic<bool> g_step_six{false};
+// dc_set_option(10, 1): consistency_step_q32_kernel ignores dcSequenceDesc.step_rows and stages through blk_ids (A-B, tests)
+static std::atomic<bool> g_no_step_rows{false};
 
 // consistency_step_ragged_q32_kernel with a tile of CAP rows: more than 64 KB of LDS per block needs the attribute (once per
 // instantiation, process and device).  Capacities up to the table's own limit (4095 rows), so every ball-neighbourhood table that can be
@@ -1331,6 +1333,16 @@ int dc_points_basis(const void* vps, const void* dirs, const void* depth, const 
     hipLaunchKernelGGL((points_basis_kernel<q32>), dim3((unsigned)n_blocks(n)), dim3(kBlock), 0, stream, in, n, qp, rows_out);
   else
     hipLaunchKernelGGL((points_basis_kernel<double>), dim3((unsigned)n_blocks(n)), dim3(kBlock), 0, stream, in, n, qp, rows_out);
+  DC_CHECK_LAUNCH();
+  return DC_OK;
+}
+
+int dc_step_rows_build(const dcBlockTable* table, int64_t n_rows, const void* basis, int row_words, void* rows_out, hipStream_t stream) {
+  if (!table || n_rows < 0 || table->layout != DC_TABLE_SLOTS || !table->blk_ptr || row_words < 7 || row_words > 6 + 3) return DC_ERR_ARG;
+  if (n_rows == 0) return DC_OK;
+  if (!table->blk_ids || !basis || !rows_out || ((uintptr_t)rows_out & 15)) return DC_ERR_ARG;
+  hipLaunchKernelGGL(step_rows_kernel, dim3((unsigned)n_blocks(n_rows)), dim3(kBlock), 0, stream, table->blk_ptr, table->blk_ids,
+                     static_cast<const int32_t*>(basis), row_words, static_cast<int32_t*>(rows_out));
   DC_CHECK_LAUNCH();
   return DC_OK;
 }
@@ -1607,6 +1619,7 @@ int dc_set_option(int option, int value) {
   if (option == 7) { g_pose_three_pass.store(value != 0); return DC_OK; }
   if (option == 8) { g_no_reverse.store(value != 0); return DC_OK; }
   if (option == 9) { g_step_six.store(value != 0); return DC_OK; }
+  if (option == 10) { g_no_step_rows.store(value != 0); return DC_OK; }
   return DC_ERR_ARG;
 }
 
@@ -1739,11 +1752,14 @@ static int launch_step_ragged(const SeqRoute& r, const StepLaunch& a) {
 static int launch_step_q32(const SeqRoute& r, const StepLaunch& a) {
   ProfScope prof(1);
   const StepHdr* hdr = static_cast<const StepHdr*>(a.d->step_hdr);
+  // the per-block row copy belongs to the same table as the headers (the route is here because of them): staged from when the caller
+  // passes one, unless dc_set_option(10, 1) asks for the trip through blk_ids
+  const int32_t* step_rows = g_no_step_rows.load() ? nullptr : static_cast<const int32_t*>(a.d->step_rows);
   const dim3 block(kBlock);
   static_assert(kStepQ32Cap == 512, "the profiler names the instantiation by its literal arguments");
   static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
                 "which instantiations dc_set_option(9, 1) has a six-block build of");
-#define STEPQ_TAIL a.pb, a.tab, hdr, a.d->centre_idx, r.n_rows, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
+#define STEPQ_TAIL a.pb, a.tab, hdr, step_rows, a.d->centre_idx, r.n_rows, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
 #define STEPQ(P, NS, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), a.grid, block, 0, a.stream, STEPQ_TAIL)
 #define STEPQ_SIX(P, NS, X) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), a.grid, block, 0, a.stream, STEPQ_TAIL)
 #define STEPQ_P(NS, CAP) DC_SWITCH_P(r.P, STEPQ(3, NS, CAP), STEPQ, NS, CAP)

@@ -47,7 +47,7 @@ class SequencePlan:
                  normalization=True, sqrt=False, spatial_sort=True, point_format='auto', degree_sort=False,
                  active_only=False, block_tables=True, bwd_layout='runs', stages=None, basis=True, lazy_backward=True,
                  scan_group=True, mask_first=False, nan_policy=None, pose_kernel=True, degree_group=False, heavy_first=False,
-                 wave_pack=None):
+                 wave_pack=None, step_rows=True):
         """
         :param clouds: per-scan dicts / objects with vps [n,3], dirs [n,3], depth [n,1], inc_angles [n,1], mask [n]
                        (local feature clouds, sensor frame), GPU tensors of one dtype.
@@ -59,6 +59,10 @@ class SequencePlan:
         :param lazy_backward: build the transposed neighbour lists / backward block table on first need instead of up front.
         :param basis: use the basis form x = X0 + (sum_k w_k c_k) u (dc_points_basis) whenever an evaluation asks for neither pose
                       nor exponent gradients: the basis rows are rebuilt only when the poses or the exponents change.
+        :param step_rows: keep, beside the basis rows, a copy of them per block of the forward table in the order the one-pass step
+                          kernel of float32 clouds stages them (dcSequenceDesc.step_rows: 4 (6 + P) bytes per listed row, 1.75 rows
+                          per point at C2).  Built when the same poses and exponents are evaluated a second time, dropped with the
+                          basis rows; results are the same bit for bit with and without it.
         :param pose_kernel: evaluations with pose gradients in one launch (consistency_step_pose_kernel) where the plan allows it.
         :param nan_policy: None, 'skip_nans' or 'only_finite' (loss.py:125-137): pointwise losses that are NaN / not finite are left
                            out of the sum, the count and the gradients; the count of an evaluation is then its own (out[1]).
@@ -333,7 +337,10 @@ class SequencePlan:
         self.use_basis = bool(basis)
         self.use_pose_kernel = bool(pose_kernel)
         self._pose_table = self._local_basis = None      # built on the first pose-gradient evaluation
-        self._basis = None             # (key, rows, poses12, exponent): the last two pin the storage the key names
+        # [key, rows, poses12, exponent, per-block row copy or None, evaluations under this key]: poses12 and exponent pin the storage
+        # the key names; the copy lives and dies with the rows it copies (_set_basis)
+        self._basis = None
+        self.use_step_rows = bool(step_rows)
         self._poses_key = self._poses12 = self._poses_ref = None
 
     # ------------------------------------------------------------------------------------------------
@@ -440,16 +447,18 @@ class SequencePlan:
                                 ptr(t['row_scan']))
         return desc, t
 
-    def _set_basis(self, d, w, exponent, poses12, want_exponent, want_pose):
+    def _set_basis(self, d, w, exponent, poses12, want_exponent, want_pose, stepping=True):
         """Point the descriptor at the basis rows valid for (poses12, exponent), building them when either changed; or clear the
-        fields when this evaluation cannot use the basis form (pose / exponent gradients, other formats, no tables)."""
+        fields when this evaluation cannot use the basis form (pose / exponent gradients, other formats, no tables).
+        The per-block copy of the rows (dcSequenceDesc.step_rows) shares the rows' key and lifetime and is built lazily: by the
+        second evaluation (``stepping``) under one key, so a caller who moves the poses or the exponents every time never pays for it."""
         f64 = self.qfmt is None and self.x.dtype == torch.float64 and self.ps.dirs.dtype == torch.float64
         ok = (self.use_basis and (self.qfmt is not None or f64) and w is not None
               and not want_exponent and not want_pose
               and self.fwd_table is not None and self._block_tables and self._bwd_layout == 'runs'
               and d.model_kind != 0)
         if not ok:
-            d.basis = None
+            d.basis = d.step_rows = None
             return
         nt = w.numel()
         b = self._basis
@@ -463,8 +472,19 @@ class SequencePlan:
                                         nv.DC_F64 if f64 else nv.DC_F32, None if f64 else self.qfmt._c, ptr(rows),
                                         ptr(self.status), stream_ptr()), 'dc_points_basis')
             # the tensors are kept alive with the entry, so their addresses cannot be recycled for other poses / exponents
-            self._basis = b = (key, rows, poses12, exponent)
+            self._basis = b = [key, rows, poses12, exponent, None, 0]
         d.basis = b[1].data_ptr()
+        if stepping:
+            b[5] += 1
+        # what consistency_step_q32_kernel stages, per block of the table the headers were built from (the kernel reads it with them only)
+        ft = getattr(self, 'fwd_table_loss', None) or self.fwd_table
+        if (b[4] is None and b[5] >= 2 and self.use_step_rows and self.qfmt is not None and nt <= 3 and self.n > 0
+                and getattr(self, 'step_hdr', None) is not None and ft.blk_ids is not None):
+            if getattr(self, '_step_rows_total', None) is None:
+                self._step_rows_total = int(ft.blk_ptr[-1].item())          # listed rows of all blocks (once per plan: synchronises)
+            b[4] = torch.empty((max(self._step_rows_total, 1) * (6 + nt),), dtype=torch.int32, device=self.device)
+            check(lib().dc_step_rows_build(ft.ref(), self.nbr.shape[0], ptr(b[1]), 6 + nt, ptr(b[4]), stream_ptr()), 'dc_step_rows_build')
+        d.step_rows = None if (b[4] is None or not self.use_step_rows) else b[4].data_ptr()
 
     @on_device
     def eval_native(self, w, exponent, poses12, out, want_grad=True, want_exponent=False, want_pose=False):
@@ -681,7 +701,7 @@ class SequencePlan:
         need(exponent, (nt,), dtype=torch.float64, name='exponent', device=self.device)
         need(poses12, (self.n_scans, 12), dtype=torch.float64, name='poses12', device=self.device)
         need(out, (nw, 2), dtype=torch.float64, name='out', device=self.device)
-        self._set_basis(d, weights[0], exponent, poses12, False, False)
+        self._set_basis(d, weights[0], exponent, poses12, False, False, stepping=False)      # (reads the rows by index: no copy for it)
         rows = self._basis[1]
         ws = torch.empty((lib().dc_sequence_landscape_workspace_count(self.n),), dtype=torch.float64, device=self.device)
         flat = [float(v) for b in bounds for v in b]

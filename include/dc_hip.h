@@ -245,6 +245,15 @@ int dc_block_table_slots(const int32_t* row_ptr, int64_t n_rows, int k, int32_t*
  * blk_skip: uint8 [blocks] or NULL (dc_block_group).  Valid for exactly these arrays: build it again when one of them changes. */
 int dc_step_header_build(const dcBlockTable* table, int64_t n_rows, const uint8_t* mask, const uint8_t* blk_skip, void* hdr_out,
                          dcStream_t stream);
+/* The per-block row copy of the one-pass step kernel (dcSequenceDesc.step_rows) of a DC_TABLE_SLOTS table over n_rows rows: for every
+ * entry e of table->blk_ids the basis row blk_ids[e] (dc_points_basis rows of a float32 cloud: row_words = 6 + P int32 / float32 words,
+ * P = 1..3), so that a block stages its list as contiguous streams instead of gathering rows by id.  rows_out: int32
+ * [blk_ptr[n_blocks] * row_words], 16-byte aligned; block b's entries fill the words [row_words blk_ptr[b], row_words blk_ptr[b + 1])
+ * and lie piece-major inside that stretch -- a piece is four consecutive words of a row, the last piece of a 7- or 9-word row the 3
+ * or 1 that remain -- all entries of piece 0 first, then all of piece 1, ...: word c of entry t of a block with nd entries is at
+ * row_words blk_ptr[b] + 4 (c / 4) nd + min(4, row_words - 4 (c / 4)) t + c % 4.  Every entry is written (those of skipped blocks too).
+ * Valid for exactly this table and these basis rows: build it again when either is rebuilt. */
+int dc_step_rows_build(const dcBlockTable* table, int64_t n_rows, const void* basis, int row_words, void* rows_out, dcStream_t stream);
 size_t dc_block_table_workspace_bytes(int64_t n_refs);
 /* A-B switch (measurements, tests; process-wide, not thread-safe like dc_set_option): 0 = [rows, K] tables through the radix-sort
  * build as well; returns the previous setting.  Default 1: K = 4 / 8 / 10 / 16 tables are built block by block in LDS. */
@@ -596,6 +605,14 @@ typedef struct dcSequenceDesc {
                                       and no mask with centre_idx), and goes stale whenever that table, the mask or blk_skip is
                                       rebuilt.  NULL (a caller with a descriptor of its own): dc_sequence_eval and dc_sequence_step* take
                                       consistency_step_basis_kernel there, which reads the tables themselves and returns the same sums */
+  const void* step_rows;           /* int32 [blk_ptr[blocks] * (6 + n_terms)], 16-byte aligned (dc_step_rows_build), or NULL.  The rows that
+                                      consistency_step_q32_kernel stages, stored once per block in the order it stages them: with it a
+                                      block fetches its rows right after its header, as contiguous streams, and never reads blk_ids.  Like
+                                      step_hdr it must be built from the table the one-pass evaluation stages from (fwd_table_loss where
+                                      the descriptor has one, else fwd_table); like `basis`, whose rows it copies, it is valid FOR THE
+                                      POSES AND EXPONENTS OF THE CALL and for this n_terms: build it again whenever the basis rows or
+                                      that table are rebuilt.  Read only together with step_hdr.  NULL: the kernel stages through
+                                      blk_ids -- the same words either way, so the same sums bit for bit */
 } dcSequenceDesc;
 
 /* Doubles of dcSequenceDesc.partials for a sequence of n points evaluated with up to n_terms weights and n_scans poses:
@@ -717,6 +734,8 @@ int dc_cloud_from_points(const void* points, int stride, int in_dtype, const voi
  *           each XCD's share backwards, so that its first blocks find their rows in that XCD's L2 (same sums to rounding).
  * option 9: value 1 runs the one-pass step kernel of float32 clouds (512-row tile, one or two weights) in its build for six resident
  *           blocks per CU instead of seven: the same kernel body and the same sums bit for bit, other launch bounds.
+ * option 10: value 1 makes the one-pass step kernel of float32 clouds ignore dcSequenceDesc.step_rows and stage its rows through
+ *           blk_ids, as it does when the field is NULL: the same staged words, the same sums bit for bit.
  * option 5: number of polls a chained launch's blocks make while they wait for the weights its leading blocks publish
  *           (default 2^22, negative restores it).  A wait that runs out yields NaN sums for that evaluation and raises bit 1 of
  *           dcSequenceDesc.status (bit 0: DC_Q32 overflow), so the two causes of a NaN loss can be told apart; tests force 0. */
