@@ -259,6 +259,10 @@ _SIGNATURES = {
     'dc_tsdf_loss': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32, _vp, _vp,
                             _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp,
                             _sz, _vp]),
+    # ray casting the fused volume (csrc/dc_tsdf_cast.hip)
+    'dc_tsdf_sparse_cast_rays': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _i32,
+                                        _vp, _vp, _vp, _i32, _i64, _vp, _vp, _i32, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
 }
 
 

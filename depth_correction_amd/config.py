@@ -340,6 +340,18 @@ class Config(object):
         self.bias_eval_surfel_scale = 1.0
         self.bias_eval_surfel_window = 0.1
         self.bias_eval_surfel_max_normal_angle = 0.7853981633974483      # pi / 4
+        # bias_eval_against = 'tsdf' (never chosen by 'auto'): no ground truth at all -- every test sequence's filtered scans are fused
+        # at the poses the dataset yields into a loss.TsdfTarget (voxel size in metres; trunc None: three voxels; min_count) and every
+        # ray is cast against that volume (leave_one_out: against the volume of the OTHER scans), marched in steps of
+        # bias_eval_tsdf_step (None: half a voxel) up to bias_eval_tsdf_max_range (None: the sequence's farthest depth plus the
+        # truncation).  The residual is the ray's bias minus the mean bias of the other views of the surface, not the bias itself
+        # (DESIGN "Ray casting the fused volume")
+        self.bias_eval_tsdf_voxel_size = 0.1
+        self.bias_eval_tsdf_trunc = None
+        self.bias_eval_tsdf_min_count = 1
+        self.bias_eval_tsdf_leave_one_out = True
+        self.bias_eval_tsdf_step = None
+        self.bias_eval_tsdf_max_range = None
         self.show_results = False
         # this build: use the fused per-sequence kernels whenever the configuration allows it
         self.depth_bias_model_class = Model.ScaledPolynomial   # dataset.noisy_dataset: a known bias through model.inverse

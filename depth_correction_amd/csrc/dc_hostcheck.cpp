@@ -27,6 +27,7 @@
 #include "dc_tsdf_sparse_math.h"
 #include "dc_tsdf_track_math.h"
 #include "dc_tsdf_loss_math.h"
+#include "dc_tsdf_cast_math.h"
 #include "dc_cons_route.h"
 
 // The finish kernels' prologue on the host: false when the registration has ended, else the NV totals of partials [n_blocks, NV]
@@ -1212,6 +1213,54 @@ int dc_host_tsdf_loss(const uint64_t* keys, const int32_t* slots, const int64_t*
   const double M = out[1];
   out[0] = M > 0.0 ? out[0] / M : nan;
   for (int q = 5; q < o_grad + 12 * n_scans; ++q) out[q] = M > 0.0 ? out[q] / M : 0.0;
+  return DC_OK;
+}
+
+// ---- ray casting the fused volume (dc_tsdf_cast_math.h; dc_tsdf_cast.hip) ----
+// dc_tsdf_sparse_cast_rays on host arrays, ray after ray: the arguments and the outputs are those of the device call.
+int dc_host_tsdf_sparse_cast_rays(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                                  const int32_t* count, const uint64_t* own_keys, const int32_t* own_slots, const int64_t* own_ptr,
+                                  int64_t n_own_keys, int64_t own_capacity, const int64_t* own_sum, const int32_t* own_count, const double* og,
+                                  double voxel, double trunc, int min_count, const void* vps, const void* dirs, const uint8_t* mask, int dtype,
+                                  int64_t n, const int64_t* scan_offset, const double* poses, int n_scans, double t_min, double t_max,
+                                  double step, int refine, int skip, int32_t* face_out, double* t_out, double* inc_out, double* normal_out,
+                                  double* phi_out, uint8_t* status_out, int32_t* samples_out) {
+  const dc::TsdfGrid g{{og[0], og[1], og[2]}, voxel, {0, 0, 0}};
+  if (dtype != DC_F32 && dtype != DC_F64) return DC_ERR_DTYPE;
+  if (!dc::tsdf_lattice_ok(g) || !(trunc > 0.0) || !std::isfinite(trunc) || min_count < 1 || n < 0 || capacity < 1 ||
+      capacity >= ((int64_t)1 << 22) || refine < 0)
+    return DC_ERR_ARG;
+  const int J = dc::tsdf_cast_steps(t_min, t_max, step, trunc);
+  if (J < 0) return DC_ERR_ARG;
+  if (own_keys && (!own_slots || !own_ptr || !own_sum || !own_count || n_own_keys < 0 || own_capacity < 1)) return DC_ERR_ARG;
+  if (n == 0) return DC_OK;
+  if (!keys || !slots || !n_blocks || !sum || !count || !vps || !dirs || !scan_offset || !poses || n_scans < 1) return DC_ERR_ARG;
+  const int64_t nb = *n_blocks < 0 ? 0 : (*n_blocks > capacity ? capacity : *n_blocks);
+  const dc::TsdfTable total{keys, slots, nb, capacity, sum, count};
+  const dc::TsdfCastRule rule{t_min, step, trunc, J, refine, min_count, skip != 0};
+  for (int64_t i = 0; i < n; ++i) {
+    const int s = dc::scan_of(scan_offset, n_scans, i);
+    dc::TsdfTable own{nullptr, nullptr, 0, own_capacity, own_sum, own_count};
+    if (own_keys) {
+      int64_t oa = own_ptr[s], ob = own_ptr[s + 1];
+      oa = oa < 0 ? 0 : (oa > n_own_keys ? n_own_keys : oa);
+      ob = ob < oa ? oa : (ob > n_own_keys ? n_own_keys : ob);
+      own.keys = own_keys + oa; own.slots = own_slots + oa; own.nb = ob - oa;
+    }
+    double vp[3], dir[3];
+    host_load3(vps, dtype, i, vp);
+    host_load3(dirs, dtype, i, dir);
+    dc::TsdfCastLane lane;
+    dc::TsdfCastResult r{-1, INFINITY, NAN, {NAN, NAN, NAN}, NAN, dc::kTsdfCastSkipped, 0};
+    if (dc::tsdf_cast_setup(vp, dir, poses + 16 * (int64_t)s, mask ? mask[i] != 0 : true, &lane)) r = dc::tsdf_cast_ray(lane, g, rule, total, own);
+    face_out[i] = r.face;
+    t_out[i] = r.t;
+    inc_out[i] = r.inc;
+    for (int a = 0; a < 3; ++a) normal_out[3 * i + a] = r.normal[a];
+    phi_out[i] = r.phi;
+    status_out[i] = (uint8_t)r.status;
+    samples_out[i] = r.samples;
+  }
   return DC_OK;
 }
 

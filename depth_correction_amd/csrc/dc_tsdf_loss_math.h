@@ -36,9 +36,10 @@ DC_HD int64_t tsdf_table_voxel(const TsdfTable& t, const int* i, TsdfBlockCache*
   return slot >= 0 && slot < t.capacity ? slot * kTsdfBlockVoxels + tsdf_voxel_local(i) : -1;
 }
 
-// The sample at the world point x of the volume `total` minus the volume `own` (own.keys == NULL: nothing is taken out).
+// The sample at the world point x of the volume `total` minus the volume `own` (own.keys == NULL: nothing is taken out).  The caches
+// are the lane's, one per table: a caller that samples along a line (dc_tsdf_cast_math.h) keeps them from sample to sample.
 DC_HD TsdfSample tsdf_sample_point_minus(const double* x, const TsdfGrid& g, double tau, int min_count, const TsdfTable& total,
-                                         const TsdfTable& own) {
+                                         const TsdfTable& own, TsdfBlockCache* cache_total, TsdfBlockCache* cache_own) {
   TsdfSample s{NAN, {0.0, 0.0, 0.0}, INFINITY, kTsdfSampleRange};
   double q[3];
   bool in = true;
@@ -58,7 +59,6 @@ DC_HD TsdfSample tsdf_sample_point_minus(const double* x, const TsdfGrid& g, dou
   }
   double v[8];
   bool all = true;
-  TsdfBlockCache cache_total{kTsdfNoKey, -1}, cache_own{kTsdfNoKey, -1};
 #pragma unroll
   for (int bx = 0; bx < 2; ++bx)
 #pragma unroll
@@ -66,14 +66,14 @@ DC_HD TsdfSample tsdf_sample_point_minus(const double* x, const TsdfGrid& g, dou
 #pragma unroll
       for (int bz = 0; bz < 2; ++bz) {
         const int i[3] = {i0[0] + bx, i0[1] + by, i0[2] + bz};
-        const int64_t at = tsdf_table_voxel(total, i, &cache_total);
+        const int64_t at = tsdf_table_voxel(total, i, cache_total);
         double val = 0.0;
         bool obs = at >= 0;
         if (obs) {
           int64_t sum = total.sum[at];
           int32_t count = total.count[at];
           if (own.keys) {
-            const int64_t mine = tsdf_table_voxel(own, i, &cache_own);
+            const int64_t mine = tsdf_table_voxel(own, i, cache_own);
             if (mine >= 0) {
               sum -= own.sum[mine];
               count -= own.count[mine];
@@ -97,6 +97,13 @@ DC_HD TsdfSample tsdf_sample_point_minus(const double* x, const TsdfGrid& g, dou
   s.dist = fabs(s.phi);
   s.flag = 0;
   return s;
+}
+
+// the same for a lane that takes one sample
+DC_HD TsdfSample tsdf_sample_point_minus(const double* x, const TsdfGrid& g, double tau, int min_count, const TsdfTable& total,
+                                         const TsdfTable& own) {
+  TsdfBlockCache cache_total{kTsdfNoKey, -1}, cache_own{kTsdfNoKey, -1};
+  return tsdf_sample_point_minus(x, g, tau, min_count, total, own, &cache_total, &cache_own);
 }
 
 // l and dl/dx [3] of a used point from its sample

@@ -633,6 +633,10 @@ def write_bias_curve_csv(path, name, res):
 def _bias_truth(ds, name, cfg):
     """What eval_bias casts the rays of ``ds`` against (cfg.bias_eval_against): its mesh, or its surveyed cloud."""
     against = cfg.bias_eval_against
+    if against == 'tsdf':                        # no ground truth: the sequence's own fused volume, made by depth_bias from the scans
+        from .loss import TsdfTarget
+        return TsdfTarget(cfg.bias_eval_tsdf_voxel_size, trunc=cfg.bias_eval_tsdf_trunc, leave_one_out=cfg.bias_eval_tsdf_leave_one_out,
+                          refresh_every=0, min_count=cfg.bias_eval_tsdf_min_count)
     if against == 'mesh' or (against == 'auto' and callable(getattr(ds, 'get_mesh', None))):
         return _dataset_mesh(ds, name, 'eval_bias')
     survey = _dataset_survey(ds, name, cfg, who='eval_bias', required=against == 'survey')
@@ -642,7 +646,9 @@ def _bias_truth(ds, name, cfg):
 def eval_bias(cfg: Config, test_datasets=None, model=None):
     """Depth bias of every test sequence against its dataset's ground truth (cfg.bias_eval_against: the mesh, or the surveyed cloud
     through its surfels -- metrics.depth_bias, DESIGN "Depth bias against a surveyed cloud" -- for a dataset such as the FEE corridor
-    that has a survey and no mesh).  Against the mesh (what scripts/bias_estimation and depth_bias.py measure with a
+    that has a survey and no mesh; or, with 'tsdf', which 'auto' never chooses, no ground truth at all: the sequence's own scans
+    fused into a loss.TsdfTarget by the cfg.bias_eval_tsdf_* keys, every scan cast against the volume of the others -- the residual
+    is then the ray's bias minus the mean bias of the other views, DESIGN "Ray casting the fused volume").  Against the mesh (what scripts/bias_estimation and depth_bias.py measure with a
     board; DESIGN "Depth bias against the mesh"): each scan goes through preproc.filtered_cloud and local_feature_cloud -- the
     estimated incidence angles and the planarity mask train() sees -- and its rays are cast in the mesh frame with the poses the
     dataset yields.  Only ground-truth poses are meaningful here: with any other pose the difference to the mesh measures the pose
@@ -654,8 +660,8 @@ def eval_bias(cfg: Config, test_datasets=None, model=None):
     from .io import append
     from .metrics import depth_bias, fit_bias
     from .preproc import filtered_cloud
-    if cfg.bias_eval_against not in ('auto', 'mesh', 'survey'):
-        raise ValueError("bias_eval_against must be 'auto', 'mesh' or 'survey', got %r" % (cfg.bias_eval_against,))
+    if cfg.bias_eval_against not in ('auto', 'mesh', 'survey', 'tsdf'):
+        raise ValueError("bias_eval_against must be 'auto', 'mesh', 'survey' or 'tsdf', got %r" % (cfg.bias_eval_against,))
     test_names, test_datasets, model = _test_setup(cfg, test_datasets, model)
     meshes = [_bias_truth(ds, name, cfg) for name, ds in zip(test_names, test_datasets)]
     if torch.device(cfg.device).type != 'cuda':
@@ -669,7 +675,8 @@ def eval_bias(cfg: Config, test_datasets=None, model=None):
         res = depth_bias(clouds, np.stack(poses), mesh, model=model, bins=cfg.bias_eval_bins, max_residual=cfg.bias_eval_max_residual,
                          cull=cfg.bias_eval_cull, surfel_radius=cfg.bias_eval_surfel_radius, surfel_k=cfg.bias_eval_surfel_k,
                          surfel_scale=cfg.bias_eval_surfel_scale, surfel_window=cfg.bias_eval_surfel_window,
-                         surfel_max_normal_angle=cfg.bias_eval_surfel_max_normal_angle)
+                         surfel_max_normal_angle=cfg.bias_eval_surfel_max_normal_angle, tsdf_step=cfg.bias_eval_tsdf_step,
+                         tsdf_max_range=cfg.bias_eval_tsdf_max_range)
         fit = res['fit'] = fit_bias(res, res['fit_class'], res['fit_exponent'])
         res['name'] = name
         b, a = res['before']['overall'], (res['after'] or {}).get('overall')

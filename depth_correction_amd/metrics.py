@@ -229,8 +229,48 @@ def _fit_basis(model, fit_class, fit_exponent):
     return fit_class, [float(e) for e in fit_exponent]
 
 
+def _is_tsdf_truth(truth):
+    from .loss import TsdfTarget
+    from .reconstruction import SparseTsdfVolume
+    return isinstance(truth, (SparseTsdfVolume, TsdfTarget))
+
+
+def _tsdf_truth_cast(truth, clouds, vps, dirs, offsets, T, step, max_range):
+    """cast(model) -> the outputs of ops.tsdf_sparse_cast_rays for the rays of depth_bias against ``truth``: a SparseTsdfVolume as it
+    is, or a loss.TsdfTarget -- as fused (fused here from ``clouds`` at the poses ``T`` when it has not been), every scan against the
+    volume of the others when it leaves one out; cast(model) with a model casts against a copy of the target re-fused from model(cloud)."""
+    from .loss import TsdfTarget
+    dev = dirs.device
+    off = torch.as_tensor(offsets, dtype=torch.int64, device=dev)
+
+    def fused(model):
+        if not isinstance(truth, TsdfTarget):
+            return truth.tables(), None, 1
+        target = truth
+        if model is not None:
+            target = TsdfTarget(truth.voxel_size, trunc=truth.trunc, leave_one_out=truth.leave_one_out, refresh_every=0,
+                                min_count=truth.min_count, max_blocks=truth.max_blocks, min_depth=truth.min_depth, max_range=truth.max_range)
+        if model is not None or target.total is None:
+            target.refresh(clouds, T.cpu(), model)
+        return target.tables, target.own, target.min_count
+
+    t_max = max_range
+    if t_max is None:                            # a ray is marched as far as the sequence measured, and through the band behind that
+        depth = torch.cat([c.depth.detach().reshape(-1) for c in clouds]).to(torch.float64)
+        depth = depth[torch.isfinite(depth)]
+        trunc = truth.trunc
+        t_max = (float(depth.max()) if depth.numel() else 0.0) + trunc
+
+    def cast(model):
+        tables, own, min_count = fused(model)
+        return ops.tsdf_sparse_cast_rays(tables, vps, dirs, off, T, t_min=0.0, t_max=max(float(t_max), tables.voxel), step=step,
+                                         min_count=min_count, own=own)
+    return cast
+
+
 def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cull=True, fit_class=None, fit_exponent=None,
-               surfel_radius=None, surfel_k=10, surfel_scale=1.0, surfel_window=0.1, surfel_max_normal_angle=math.pi / 4):
+               surfel_radius=None, surfel_k=10, surfel_scale=1.0, surfel_window=0.1, surfel_max_normal_angle=math.pi / 4, tsdf_step=None,
+               tsdf_max_range=None):
     """Depth error of every ray of the DepthClouds ``clouds`` (one sequence, on a GPU, sensor frame) against ``truth``
     (mesh.TriangleMesh or survey.SurveyCloud, the frame of ``poses`` [S,4,4]: world from sensor; only ground-truth poses give a
     meaningful answer), as a
@@ -248,7 +288,17 @@ def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cul
     behind the first one whose normals lie within ``surfel_max_normal_angle`` of its normal -- the first disk alone is biased
     towards the sensor by the survey's noise, growing with the incidence angle (DESIGN "Depth bias against a surveyed cloud") --,
     ``face`` holds the survey index of the first disk, and the result gains ``t_first`` (its depth) and ``count`` (disks blended per
-    ray).  Disks are two-sided: ``cull`` is ignored."""
+    ray).  Disks are two-sided: ``cull`` is ignored.
+
+    Without any ground truth, ``truth`` may be a fused volume (DESIGN "Ray casting the fused volume"): a
+    reconstruction.SparseTsdfVolume, cast as it is (ops.tsdf_sparse_cast_rays in steps of ``tsdf_step``, None: half a voxel, up to
+    ``tsdf_max_range``, None: the farthest finite depth plus the truncation), or a loss.TsdfTarget, fused here from ``clouds`` at
+    ``poses`` when it has not been; with its leave_one_out every scan is cast against the volume of the OTHER scans.  ``inc`` is then
+    the angle to the field's gradient at the hit, and the result gains ``status`` (ops.TSDF_CAST_* per ray).  Against a TsdfTarget
+    the truth is made of the measurements, so ``after`` is taken against a copy of the target re-fused from model(cloud) and the rays
+    are cast a second time: the result gains ``face_after`` / ``t_after`` / ``inc_after`` / ``status_after``.  The residual against the
+    own sequence's volume is a ray's bias MINUS the mean bias of the other views of that surface: fit_bias' weights come out
+    attenuated (by how much: DESIGN)."""
     clouds = list(clouds)
     if not clouds:
         raise ValueError('depth_bias needs at least one cloud')
@@ -264,7 +314,15 @@ def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cul
     if T.shape[0] != len(clouds):
         raise ValueError('%d clouds but %d poses' % (len(clouds), T.shape[0]))
     extra = {}
-    if hasattr(truth, 'surfels'):
+    recast = None                                # against a fused TsdfTarget: the cast of ``after``, against the re-fused target
+    if _is_tsdf_truth(truth):
+        cast = _tsdf_truth_cast(truth, clouds, vps, dirs, offsets, T, tsdf_step, tsdf_max_range)
+        hit = cast(None)
+        face, t, inc = hit['face'], hit['t'], hit['inc']
+        extra = dict(status=hit['status'])
+        if model is not None and hasattr(truth, 'refresh'):
+            recast = cast
+    elif hasattr(truth, 'surfels'):
         angle = float(surfel_max_normal_angle)
         if not 0.0 < angle <= math.pi / 2:
             raise ValueError('surfel_max_normal_angle must lie in (0, pi/2], got %r' % (surfel_max_normal_angle,))
@@ -283,7 +341,7 @@ def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cul
     n_terms = len(fit_exponent)
     ws = ops.bias_workspace(bins, n_terms, dev)
 
-    def stats(cs):
+    def stats(cs, face=face, t=t, inc=inc):
         depth = _cat_field(cs, 'depth', 0)
         est = None if inc_est is None else inc_est.to(depth.dtype)
         out = ops.bias_accumulate(depth, est, mask, face, t, inc, fit_class, fit_exponent, n_bins=bins, max_residual=max_residual, ws=ws)
@@ -296,7 +354,13 @@ def depth_bias(clouds, poses, truth, model=None, bins=18, max_residual=None, cul
     res.update(extra)
     if model is not None:
         with torch.no_grad():
-            res['after'] = stats([model(c) for c in clouds])
+            if recast is None:
+                res['after'] = stats([model(c) for c in clouds])
+            else:
+                # the truth is made of the measurements: the corrected depths are held against the volume the corrected scans fuse into
+                hit = recast(model)
+                res['after'] = stats([model(c) for c in clouds], hit['face'], hit['t'], hit['inc'])
+                res.update(face_after=hit['face'], t_after=hit['t'], inc_after=hit['inc'], status_after=hit['status'])
     return res
 
 

@@ -23,7 +23,7 @@ __all__ = [
     'survey_align_workspace', 'pair_histograms', 'feature_nn', 'feature_nn_tile', 'greg_fit', 'greg_score', 'planereg_triples', 'planereg_count', 'planereg_fill',
     'planereg_hypotheses', 'planereg_select', 'tsdf_k_steps', 'tsdf_integrate', 'tsdf_extract',
     'tsdf_sparse_allocate', 'tsdf_sparse_integrate', 'tsdf_sparse_extract', 'tsdf_sparse_sample', 'tsdf_icp_accumulate',
-    'TsdfTables', 'TsdfOwnTables', 'tsdf_loss', 'tsdf_loss_workspace',
+    'TsdfTables', 'TsdfOwnTables', 'tsdf_loss', 'tsdf_loss_workspace', 'tsdf_sparse_cast_rays',
     'compact_rows_device', 'range_project', 'range_organize', 'range_from_grid', 'range_index_image', 'image_features_fwd', 'image_shadow_mask',
 ]
 
@@ -2745,22 +2745,7 @@ def tsdf_loss(volume_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=None
     mr = trunc if max_residual is None else float(max_residual)
     if math.isnan(mr):
         raise ValueError('max_residual must not be NaN')
-    own_args = (None, None, None, 0, 0, None, None)
-    if own is not None:
-        if not isinstance(own, TsdfOwnTables):
-            raise TypeError('tsdf_loss takes own as ops.TsdfOwnTables, got %s' % type(own).__name__)
-        need(own.keys, (None,), dtype=torch.int64, name='own keys', device=dev)
-        nk = own.keys.shape[0]
-        need(own.slots, (nk,), dtype=torch.int32, name='own slots', device=dev)
-        need(own.ptr, (ns + 1,), dtype=torch.int64, name='own ptr', device=dev)
-        need(own.sum, (None, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='own sum', device=dev)
-        cap_own = own.sum.shape[0]
-        need(own.count, (cap_own, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='own count', device=dev)
-        if cap_own < 1:
-            raise ValueError('tsdf_loss needs an own pool of at least one block')
-        # (keys of an empty tensor have no address: a table without keys is still a table, so it gets the pool's)
-        own_args = (ptr(own.keys) if nk else ptr(own.sum), ptr(own.slots) if nk else ptr(own.sum), ptr(own.ptr), nk, cap_own,
-                    ptr(own.sum), ptr(own.count))
+    own_args = _tsdf_own_args(own, ns, dev, 'tsdf_loss')
     n_out = 5 + 2 * nt + 12 * ns
     out = _out_arg(out, n_out, dev)
     ws = _ws_arg(ws, lib().dc_tsdf_loss_workspace_bytes(ps.n, ns, nt), dev)
@@ -2775,3 +2760,86 @@ def tsdf_loss(volume_dev, ps, scan_ptr, poses12, model_kind=None, w=None, e=None
                              ptr(w), ptr(e), int(bool(want_exponent)), int(bool(squared)), mr, ptr(value), ptr(flag), ptr(x), ptr(out),
                              ptr(ws), ws.shape[0], stream_ptr()), 'dc_tsdf_loss')
     return (out, value, flag, x) if want_points else out
+
+
+# ------------------------------------------------------------------------------------------------
+# ray casting the fused volume (csrc/dc_tsdf_cast.hip, reconstruction.SparseTsdfVolume.raycast)
+# ------------------------------------------------------------------------------------------------
+TSDF_CAST_HIT, TSDF_CAST_SKIPPED, TSDF_CAST_MISS, TSDF_CAST_BEHIND, TSDF_CAST_LOST = 0, 1, 2, 3, 4
+TSDF_CAST_MAX_STEPS = 2 ** 24
+_TSDF_CAST_OUT = (('face', (), torch.int32), ('t', (), torch.float64), ('inc', (), torch.float64), ('normal', (3,), torch.float64),
+                  ('phi', (), torch.float64), ('status', (), torch.uint8), ('samples', (), torch.int32))
+
+
+def _tsdf_own_args(own, ns, dev, who):
+    """The seven exclusion arguments of dc_tsdf_loss / dc_tsdf_sparse_cast_rays from ``own`` (TsdfOwnTables of ``ns`` scans, or None)."""
+    if own is None:
+        return (None, None, None, 0, 0, None, None)
+    if not isinstance(own, TsdfOwnTables):
+        raise TypeError('%s takes own as ops.TsdfOwnTables, got %s' % (who, type(own).__name__))
+    need(own.keys, (None,), dtype=torch.int64, name='own keys', device=dev)
+    nk = own.keys.shape[0]
+    need(own.slots, (nk,), dtype=torch.int32, name='own slots', device=dev)
+    need(own.ptr, (ns + 1,), dtype=torch.int64, name='own ptr', device=dev)
+    need(own.sum, (None, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='own sum', device=dev)
+    cap_own = own.sum.shape[0]
+    need(own.count, (cap_own, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='own count', device=dev)
+    if cap_own < 1:
+        raise ValueError('%s needs an own pool of at least one block' % who)
+    # (keys of an empty tensor have no address: a table without keys is still a table, so it gets the pool's)
+    return (ptr(own.keys) if nk else ptr(own.sum), ptr(own.slots) if nk else ptr(own.sum), ptr(own.ptr), nk, cap_own, ptr(own.sum),
+            ptr(own.count))
+
+
+@on_device
+def tsdf_sparse_cast_rays(tables, vps, dirs, scan_offset, poses, t_min=0.0, t_max=100.0, step=None, refine=2, min_count=1, mask=None,
+                          own=None, skip=True, out=None):
+    """The rays of raycast_rays (vps, dirs f32 | f64 [N,3] in the sensor frame, scan-major; scan_offset, poses f64 [S,4,4] as there)
+    marched through the sparse volume ``tables`` (TsdfTables) to the zero crossing of its trilinear interpolant (dc_tsdf_sparse_cast_rays;
+    the rule: csrc/dc_tsdf_cast_math.h): samples at t_min + j step (``step`` None: voxel / 2; 0 < step <= trunc) up to ``t_max``, in units
+    of |dirs[i]|; the crossing is refined by ``refine`` rounds of regula falsi.  ``own`` (TsdfOwnTables): scan s is cast against the
+    volume minus its own contribution; ``mask`` bool / uint8 [N]: rays to skip.  Returns dict(face i32 [N] (the block's table position;
+    -1 unless hit), t f64 [N] (+inf unless hit), inc f64 [N] (NaN unless hit), normal f64 [N,3] (the field's unit gradient, NaN unless
+    hit), phi f64 [N] (the residual at t; NaN unless hit), status u8 [N] (TSDF_CAST_*), samples i32 [N]); face, t and inc follow
+    raycast_rays' miss conventions.  ``skip`` False marches every sample (same outputs but ``samples``; for timing and tests).  ``out``:
+    such a dict to write into.  One launch, nothing is read back."""
+    if not isinstance(tables, TsdfTables):
+        raise TypeError('tsdf_sparse_cast_rays takes the volume as ops.TsdfTables, got %s' % type(tables).__name__)
+    dev, capacity = _tsdf_sparse_table(tables.keys, tables.slots, tables.n_blocks, 'tsdf_sparse_cast_rays')
+    need(tables.sum, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int64, name='sum', device=dev)
+    need(tables.count, (capacity, TSDF_BLOCK_VOXELS), dtype=torch.int32, name='count', device=dev)
+    origin, voxel, trunc, min_count, refine = tables.origin, tables.voxel, tables.trunc, int(min_count), int(refine)
+    if len(origin) != 3 or not all(math.isfinite(v) for v in origin) or not (voxel > 0.0 and math.isfinite(voxel)) or \
+            not (trunc > 0.0 and math.isfinite(trunc)):
+        raise ValueError('tsdf_sparse_cast_rays needs a finite origin of 3 values, a voxel size and a truncation > 0, got %r, %r and %r'
+                         % (origin, voxel, trunc))
+    if min_count < 1 or refine < 0:
+        raise ValueError('tsdf_sparse_cast_rays needs min_count >= 1 and refine >= 0, got %d and %d' % (min_count, refine))
+    t_min, t_max, step = float(t_min), float(t_max), 0.5 * voxel if step is None else float(step)
+    if not (0.0 <= t_min < t_max and math.isfinite(t_max)):
+        raise ValueError('tsdf_sparse_cast_rays needs 0 <= t_min < t_max, both finite, got %r and %r' % (t_min, t_max))
+    if not 0.0 < step <= trunc:
+        raise ValueError('tsdf_sparse_cast_rays needs 0 < step <= the truncation %g, got %r' % (trunc, step))
+    if math.floor((t_max - t_min) / step) > TSDF_CAST_MAX_STEPS:
+        raise ValueError('tsdf_sparse_cast_rays marches 2^24 steps at the most, got (%g - %g) / %g' % (t_max, t_min, step))
+    n, code, ns, off = _measured_rays_arg(dev, vps, dirs, scan_offset, poses)
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
+        need(mask, (n,), name='mask', device=dev)
+    own_args = _tsdf_own_args(own, ns, dev, 'tsdf_sparse_cast_rays')
+    if out is None:
+        out = {name: torch.empty((n,) + shape, dtype=dt, device=dev) for name, shape, dt in _TSDF_CAST_OUT}
+    else:
+        for name, shape, dt in _TSDF_CAST_OUT:
+            need(out[name], (n,) + shape, dtype=dt, name=name, device=dev)
+    if n == 0:
+        return out
+    off = off.to(dev)
+    check(lib().dc_tsdf_sparse_cast_rays(ptr(tables.keys), ptr(tables.slots), ptr(tables.n_blocks), capacity, ptr(tables.sum),
+                                         ptr(tables.count), *own_args, *origin, voxel, trunc, min_count, ptr(vps), ptr(dirs), ptr(mask),
+                                         code, n, ptr(off), ptr(poses), ns, t_min, t_max, step, refine, 1 if skip else 0, ptr(out['face']),
+                                         ptr(out['t']), ptr(out['inc']), ptr(out['normal']), ptr(out['phi']), ptr(out['status']),
+                                         ptr(out['samples']), stream_ptr()), 'dc_tsdf_sparse_cast_rays')
+    return out

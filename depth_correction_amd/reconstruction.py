@@ -283,6 +283,42 @@ class SparseTsdfVolume(object):
             return ops.tsdf_sparse_sample(self._keys, self._slots, self._n_blocks, self._sum, self._count, self.origin, self.voxel_size,
                                           self.trunc, points, pose=pose, min_count=min_count, stop=stop, out=out)
 
+    def raycast(self, vps, dirs, poses=None, scan_offset=None, **kw):
+        """Casts the rays (vps, dirs [N,3]; f32 or f64) against the fused surface without extracting it: dict(face, t, inc, normal, phi,
+        status, samples) of ops.tsdf_sparse_cast_rays, whose keywords (t_min, t_max, step, refine, min_count, mask, own, skip, out) pass
+        through.  Without ``poses`` the rays are in the volume's frame; with ``poses`` [S,4,4] and ``scan_offset`` (S + 1 offsets) ray i
+        of scan s is moved by pose s first.  ``t`` is in units of |dirs[i]|; ``normal`` is the field's gradient at the hit, not a face's."""
+        dirs = torch.as_tensor(dirs, device=self.device)
+        if dirs.dtype not in (torch.float32, torch.float64):
+            dirs = dirs.to(torch.float64)
+        dirs = dirs.reshape(-1, 3).contiguous()
+        n = dirs.shape[0]
+        vps = torch.as_tensor(vps, device=self.device).to(dirs.dtype).reshape(-1, 3)
+        if vps.shape[0] == 1 and n != 1:
+            vps = vps.expand(n, 3)
+        vps = vps.contiguous()
+        if poses is None:
+            if scan_offset is not None:
+                raise ValueError('raycast takes scan_offset with poses only')
+            poses, scan_offset = torch.eye(4, dtype=torch.float64, device=self.device).reshape(1, 4, 4), [0, n]
+        else:
+            if not (isinstance(poses, torch.Tensor) and poses.is_cuda):
+                poses = torch.as_tensor(np.asarray(poses, dtype=np.float64), device=self.device)
+            poses = poses.to(torch.float64).reshape(-1, 4, 4).contiguous()
+            if scan_offset is None:
+                if poses.shape[0] != 1:
+                    raise ValueError('raycast needs scan_offset with %d poses' % poses.shape[0])
+                scan_offset = [0, n]
+        with torch.no_grad():
+            return ops.tsdf_sparse_cast_rays(self.tables(), vps, dirs, scan_offset, poses, **kw)
+
+    def raycast_cloud(self, cloud, pose=None, mask=None, **kw):
+        """raycast for the rays of one DepthCloud (its view points and directions, its mask unless ``mask`` is given) under ``pose``
+        [4,4]: what each ray would have measured on the fused surface (t in units of |dirs[i]|: metres for unit directions, to hold
+        against cloud.depth) and at what incidence angle."""
+        vps, dirs, _, pose, mask = _scan_args(cloud, pose, mask, self.device, 'raycast_cloud')
+        return self.raycast(vps, dirs, poses=None if pose is None else pose.reshape(1, 4, 4), mask=mask, **kw)
+
     def extract(self, min_count=1):
         """(vertices f64 [Nv,3], faces i32 [Nf,3]) on the device; both empty when the volume holds no surface."""
         return ops.tsdf_sparse_extract(self._keys, self._slots, self.n_blocks, self._sum, self._count, self.origin, self.voxel_size,

@@ -1491,6 +1491,39 @@ int dc_tsdf_icp_accumulate(const double* x, const double* value, const double* g
                            const double* threshold, double max_residual, const double* state, const int32_t* status, double* partials,
                            int n_blocks, uint8_t* kept_out, dcStream_t stream);
 
+/* ---- ray casting the fused volume (depth_correction_amd/csrc/dc_tsdf_cast.hip; the rule: dc_tsdf_cast_math.h; DESIGN "Ray casting
+ * the fused volume") ----
+ * Ray i of n (vps / dirs [n,3] of `dtype`, sensor frame, scan-major; mask uint8 [n] or NULL) belongs to the scan s found by clamped
+ * bisection of scan_offset (DEVICE int64 [n_scans+1]) and is cast from o = R_s vp + t_s along u = R_s dir (poses DEVICE double
+ * [n_scans,16], the row sums ((R0 v0 + R1 v1) + R2 v2) + t) through the sparse volume of dc_tsdf_loss: table and pool (keys / slots
+ * [capacity], *n_blocks DEVICE and clamped to the capacity, sum int64 / count int32 [capacity,512]) on the lattice (ox, oy, oz, voxel)
+ * with the truncation trunc, and, with own_keys != NULL, scan s against the total minus its own volume (dc_tsdf_loss' exclusion, to
+ * the bit).  Samples at t_j = t_min + j step, j = 0 .. J = floor((t_max - t_min) / step), t in units of |dir|; required: 0 <= t_min <
+ * t_max, both finite, 0 < step <= trunc, J <= 2^24, refine >= 0 (DC_ERR_ARG).  A sample with an unobserved corner or outside the
+ * lattice's range is invalid.  The march stops at the first valid sample with phi <= 0: a crossing iff the sample before it was valid
+ * with phi > 0, else DC_TSDF_CAST_BEHIND; no stop: DC_TSDF_CAST_MISS.  A crossing is refined by `refine` rounds of bracketed regula
+ * falsi from t* = t0 + (t1 - t0) (phi0 / (phi0 - phi1)) and read at t*; an invalid sample on the way, or a zero gradient at t*:
+ * DC_TSDF_CAST_LOST.  DC_TSDF_CAST_SKIPPED: mask 0, o or u not finite, or u = 0.
+ * Outputs per ray: face_out int32 (the table position of the block of the base voxel of the sample at t*; -1 unless HIT), t_out (+inf
+ * unless HIT), inc_out (the incidence angle of u on the field's normal; NaN unless HIT), normal_out double [n,3] (grad / |grad|, to the
+ * free side; NaN unless HIT), phi_out (the residual at t*; NaN unless HIT), status_out uint8 (DC_TSDF_CAST_*), samples_out int32 (the
+ * samples the lane took; with skip != 0 only those that read voxels).  face / t / inc follow the miss conventions of
+ * dc_raycast_rays.  skip != 0: a sample whose base voxel's block the table lacks is invalid by the look-up alone, and the lane
+ * jumps to that block's exit; every output but samples_out is bit-equal to skip == 0.  One launch, one lane per ray; no atomics,
+ * workspace, allocation or synchronisation. */
+#define DC_TSDF_CAST_HIT 0
+#define DC_TSDF_CAST_SKIPPED 1
+#define DC_TSDF_CAST_MISS 2
+#define DC_TSDF_CAST_BEHIND 3
+#define DC_TSDF_CAST_LOST 4
+int dc_tsdf_sparse_cast_rays(const uint64_t* keys, const int32_t* slots, const int64_t* n_blocks, int64_t capacity, const int64_t* sum,
+                             const int32_t* count, const uint64_t* own_keys, const int32_t* own_slots, const int64_t* own_ptr,
+                             int64_t n_own_keys, int64_t own_capacity, const int64_t* own_sum, const int32_t* own_count, double ox, double oy,
+                             double oz, double voxel, double trunc, int min_count, const void* vps, const void* dirs, const uint8_t* mask,
+                             int dtype, int64_t n, const int64_t* scan_offset, const double* poses, int n_scans, double t_min, double t_max,
+                             double step, int refine, int skip, int32_t* face_out, double* t_out, double* inc_out, double* normal_out,
+                             double* phi_out, uint8_t* status_out, int32_t* samples_out, dcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
