@@ -82,6 +82,7 @@ _SIGNATURES = {
     'dc_block_table_build': (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'dc_step_header_build': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
     'dc_step_rows_build': (_i32, [_vp, _i64, _vp, _i32, _vp, _vp]),
+    'dc_step_loc_build': (_i32, [_vp, _i64, _vp, _vp]),
     'dc_block_group': (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'dc_pose_table_build': (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'dc_points_local_basis': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
@@ -310,7 +311,7 @@ class SequenceDesc(ctypes.Structure):
                 ('partials_count', ctypes.c_int64), ('scan_seg', _vp), ('blk_skip', _vp), ('fwd_rows_active', ctypes.c_int32),
                 ('reserved2', ctypes.c_int32), ('pose_table', _vp), ('local_basis', _vp), ('fwd_table_loss', _vp),
                 ('fwd_rows_active_loss', ctypes.c_int32), ('reserved3', ctypes.c_int32), ('step_hdr', _vp),
-                ('step_rows', _vp)]
+                ('step_rows', _vp), ('step_loc', _vp)]
 
 
 def lib_path():

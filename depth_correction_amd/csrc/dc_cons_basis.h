@@ -215,6 +215,32 @@ __global__ __launch_bounds__(kBlock) void step_rows_kernel(const int32_t* __rest
   }
 }
 
+// ---- the packed tile positions of the one-pass step kernel of float32 clouds (dcSequenceDesc.step_loc, dc_step_loc_build) ----------
+// A lane of consistency_step_q32_kernel holds its NS 16-bit positions two to a register (pk[]: slot 2 j in the low half of word j).
+// They depend on the table alone, so they are stored in that form: block b's 256 NW words (NW = NS / 2) fill the byte range its NS
+// rows of `loc` occupy -- from byte 512 slot_ptr[b], word 128 slot_ptr[b], onward: the header's s0 addresses them -- PIECE-MAJOR like
+// the row copy: a piece is four consecutive words of a lane (the last piece of NW = 5 the one that remains), all 256 lanes of piece 0
+// first, then all of piece 1:   word j of lane t  at  128 slot_ptr[b] + 1024 (j / 4) + step_loc_piece_words(NW, j / 4) t + j % 4.
+// A lane fetches a piece with one load of 16 (8, 4) bytes right beside its neighbour's, 16-byte aligned where it is 16 bytes long.
+__host__ __device__ constexpr int step_loc_piece_words(int nw, int piece) { return nw - 4 * piece < 4 ? nw - 4 * piece : 4; }
+
+// One workgroup per 256-point block walks the 256 NW words of its range in the order they are stored.  slot_ptr bounds everything:
+// the words written are [128 s0, 128 s0 + 256 NW), inside the block's own rows of `loc`, which are what is read.
+__global__ __launch_bounds__(kBlock) void step_loc_kernel(const int32_t* __restrict__ slot_ptr, const uint16_t* __restrict__ loc,
+                                                          uint32_t* __restrict__ out) {
+  const int32_t s0 = slot_ptr[blockIdx.x];
+  const int nw = (slot_ptr[blockIdx.x + 1] - s0) / 2;
+  const uint16_t* lrow = loc + (int64_t)s0 * kBlock;
+  uint32_t* range = out + (int64_t)s0 * (kBlock / 2);
+  const int full = (nw / 4) * 4 * kBlock;                               // words of the whole pieces; the short last piece follows
+  for (int j = threadIdx.x; j < nw * kBlock; j += kBlock) {
+    const int g = j < full ? j / (4 * kBlock) : nw / 4;
+    const int gw = step_loc_piece_words(nw, g);
+    const int r = j - 4 * g * kBlock, t = r / gw, w = 4 * g + (r - t * gw);
+    range[j] = (uint32_t)lrow[2 * w * kBlock + t] | ((uint32_t)lrow[(2 * w + 1) * kBlock + t] << 16);
+  }
+}
+
 template <typename PT, bool FULL_EIG, int NS, int P>
 __global__ __launch_bounds__(kBlock) void consistency_fwd_basis_kernel(
     PointBasis pb, BlockTab tab, const int32_t* __restrict__ own_base, int cap, const int32_t* __restrict__ centre_idx, int64_t n,

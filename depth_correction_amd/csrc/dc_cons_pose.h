@@ -247,8 +247,8 @@ __global__ __launch_bounds__(kBlock, 4) void consistency_step_pose_kernel(
       for (int q = 1; q < NS; ++q) mo |= pre[q];
       const bool any_miss = __any((int)(mo & 1u)) != 0;
       int n_have;
-      if (any_miss) n_have = gather_fixed<q32, NS, true>(tile, CAP, ci, pre, acc);
-      else n_have = gather_fixed<q32, NS, false>(tile, CAP, ci, pre, acc);
+      if (any_miss) n_have = gather_fixed<q32, NS, true, true>(tile, CAP, ci, pre, acc);      // (16-byte reads: keep_row_word)
+      else n_have = gather_fixed<q32, NS, false, true>(tile, CAP, ci, pre, acc);
       acc.W = (double)n_have;
       double se2;
       step_point2<q32, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2, &se2);

@@ -559,8 +559,9 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_kernel(
       for (int q = 1; q < NS; ++q) mx = max(mx, pre[q]);
       const bool any_miss = __any((int)(mx == kNoLoc)) != 0;
       int n_have;
-      if (any_miss) n_have = gather_fixed<PT, NS, true>(tile, cap, ci, pre, acc);
-      else n_have = gather_fixed<PT, NS, false>(tile, cap, ci, pre, acc);
+      constexpr bool kWide = std::is_same<PT, q32>::value;            // (16-byte reads of the 16-byte rows: keep_row_word)
+      if (any_miss) n_have = gather_fixed<PT, NS, true, kWide>(tile, cap, ci, pre, acc);
+      else n_have = gather_fixed<PT, NS, false, kWide>(tile, cap, ci, pre, acc);
       acc.W = (double)n_have;
       double cm[3], v0[3], c1, c2;
       if constexpr ((VAR & kVarSlimTail) != 0) step_point2<PT, NS>(acc, n_have, !any_miss, in_mask, lp, qp, acc2, cm, v0, &c1, &c2);
@@ -675,6 +676,25 @@ template <int P, int CAP> constexpr int step_q32_blocks() {
 }
 // The lane's NS 16-bit tile positions two to a register (slot 2 j in the low half of word j): they live through both sweeps and the tail
 template <int Q> __device__ __forceinline__ uint32_t pre_at(const uint32_t* pk) { return (Q & 1) ? pk[Q >> 1] >> 16 : pk[Q >> 1] & 0xFFFFu; }
+// pk[] of lane `tid` from the block's stretch of the packed positions (layout: step_loc_piece_words): one load per piece of four words
+template <int NW>
+__device__ __forceinline__ void fetch_step_loc(const uint32_t* blk, uint32_t tid, uint32_t* pk) {
+  static_assert(NW % 4 == 0 || NW % 4 == 1 || NW % 4 == 2, "the slot counts the step kernel is built for: 4, 8, 10, 16");
+#pragma unroll
+  for (int g = 0; 4 * g < NW; ++g) {
+    const int gw = step_loc_piece_words(NW, g);
+    const uint32_t* r = blk + (uint32_t)(4 * g * kBlock) + (uint32_t)gw * tid;
+    if (gw == 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(r);
+      pk[4 * g] = v.x; pk[4 * g + 1] = v.y; pk[4 * g + 2] = v.z; pk[4 * g + 3] = v.w;
+    } else if (gw == 2) {
+      const uint2 v = *reinterpret_cast<const uint2*>(r);
+      pk[4 * g] = v.x; pk[4 * g + 1] = v.y;
+    } else {
+      pk[4 * g] = r[0];
+    }
+  }
+}
 // gather_fixed<q32, NS, MISS> over packed positions: the same reads, differences and additions in the same order
 template <int NS, bool MISS, int Q0 = 0>
 __device__ __forceinline__ int gather_fixed_pk(const int4* tile, const Pt<q32>::Raw& ci, const uint32_t* pk, CovAcc& acc) {
@@ -688,6 +708,7 @@ __device__ __forceinline__ int gather_fixed_pk(const int4* tile, const Pt<q32>::
     if constexpr (NQ > 3) off[3] = pre_at<Q0 + (NQ > 3 ? 3 : 0)>(pk);
     Pt<q32>::Raw cj[NQ];
     bool have[NQ];
+    int w4[NQ];
     int n_have = 0;
 #pragma unroll
     for (int u_ = 0; u_ < NQ; ++u_) {
@@ -695,9 +716,11 @@ __device__ __forceinline__ int gather_fixed_pk(const int4* tile, const Pt<q32>::
       int4 piece[1];
       read_row<1>(tile, 0, have[u_] ? off[u_] : 0u, piece);
       cj[u_] = Pt<q32>::from_row(piece);
+      w4[u_] = piece[0].w;
     }
 #pragma unroll
     for (int u_ = 0; u_ < NQ; ++u_) {
+      keep_row_word(w4[u_]);                              // the row read whole: ds_read_b128, not b96
       double d[3];
       Pt<q32>::delta(have[u_] ? cj[u_] : ci, ci, d);
       cov_add_d(acc, d[0], d[1], d[2]);
@@ -736,8 +759,8 @@ __device__ unsigned long long* g_block_trace = nullptr;
 // BLOCKS: what the launch bounds ask for; dc_set_option(9, 1) runs the instantiation with six where the default is seven (A-B)
 template <int NS, int P, int CAP, int BLOCKS = step_q32_blocks<P, CAP>()>
 __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
-    PointBasis pb, BlockTab tab, const StepHdr* __restrict__ hdr, const int32_t* __restrict__ step_rows, const int32_t* __restrict__ centre_idx,
-    int64_t n, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd, StepChain ch) {
+    PointBasis pb, BlockTab tab, const StepHdr* __restrict__ hdr, const int32_t* __restrict__ step_rows, const uint32_t* __restrict__ step_loc,
+    const int32_t* __restrict__ centre_idx, int64_t n, LossParams lp, QParams qp, double* __restrict__ p_fwd, double* __restrict__ p_bwd, StepChain ch) {
   constexpr int NV = 2 + P, NP2 = NV <= 4 ? 4 : 8;
   constexpr int cap = CAP;
   __shared__ int4 tile[StepRow<q32, P>::kPieces * CAP];
@@ -778,10 +801,19 @@ __global__ __launch_bounds__(kBlock, BLOCKS) void consistency_step_q32_kernel(
     const uint16_t* lrow = tab.loc + (int64_t)s0 * kBlock;
     constexpr int NW = (NS + 1) / 2;
     uint32_t pk[NW];
+    // step_loc (launch-uniform): the words as they are, from the block's own stretch (dcSequenceDesc.step_loc) -- one or two loads and
+    // nothing to join -- and only in a wavefront that sweeps (a scalar test); else the table's 16-bit positions, joined in pairs.  Two
+    // branches for the reason given at the row fetch below.
+    if (step_loc) {
 #pragma unroll
-    for (int j = 0; j < NW; ++j)
-      pk[j] = (uint32_t)lrow[(uint32_t)(2 * j * kBlock) + tid] |
-              (2 * j + 1 < NS ? (uint32_t)lrow[(uint32_t)((2 * j + 1 < NS ? 2 * j + 1 : 0) * kBlock) + tid] << 16 : 0u);
+      for (int j = 0; j < NW; ++j) pk[j] = 0u;
+      if (in_word != 0) fetch_step_loc<NW>(step_loc + (int64_t)s0 * (kBlock / 2), tid, pk);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+        pk[j] = (uint32_t)lrow[(uint32_t)(2 * j * kBlock) + tid] |
+                (2 * j + 1 < NS ? (uint32_t)lrow[(uint32_t)((2 * j + 1 < NS ? 2 * j + 1 : 0) * kBlock) + tid] << 16 : 0u);
+    }
     const int32_t* ids = tab.blk_ids + base;
     // step_rows (launch-uniform): the rows of the block's list stored once, in the order they are staged (StepRow::fetch_listed); the
     // table of ids is then not read at all
@@ -962,9 +994,10 @@ __global__ __launch_bounds__(kBlock) void consistency_step_basis_slots_kernel(
 #pragma unroll
     for (int q = 0; q < kPreSlots; ++q) miss |= (q < nslots) && pre[q] == kNoLoc;
     int n_have = 0;
-    if (__any((int)miss)) n_have = gather_slots<PT, true>(tile, cap, ci, pre, nslots, acc);
-    else n_have = gather_slots<PT, false>(tile, cap, ci, pre, nslots, acc);
-    if (nslots > kPreSlots) n_have += gather_tail<PT>(tile, cap, ci, lrow, nslots, packed != 0, acc);
+    constexpr bool kWide = std::is_same<PT, q32>::value;              // (16-byte reads of the 16-byte rows: keep_row_word)
+    if (__any((int)miss)) n_have = gather_slots<PT, true, kWide>(tile, cap, ci, pre, nslots, acc);
+    else n_have = gather_slots<PT, false, kWide>(tile, cap, ci, pre, nslots, acc);
+    if (nslots > kPreSlots) n_have += gather_tail<PT, kWide>(tile, cap, ci, lrow, nslots, packed != 0, acc);
     acc.W = (double)n_have;
     double cm[3], v0[3], c1, c2;
     // a wavefront all of whose lanes have every slot takes W and D as the fixed-K kernels' full wavefronts do (step_point2): on a
@@ -1099,8 +1132,10 @@ __global__ __launch_bounds__(kBlock, (CAP <= 1024 ? 5 : 4)) void consistency_ste
 #pragma unroll
       for (int u_ = 0; u_ < kTrip; ++u_) r[u_] = *reinterpret_cast<const int4*>(tb + (l[u_] == kNoLoc ? own_off : l[u_]));
 #pragma unroll
-      for (int u_ = 0; u_ < kTrip; ++u_)
+      for (int u_ = 0; u_ < kTrip; ++u_) {
+        keep_row_word(r[u_].w);                           // the row read whole: ds_read_b128, not b96
         cov_add_d(acc, (double)(r[u_].x - ci.v[0]), (double)(r[u_].y - ci.v[1]), (double)(r[u_].z - ci.v[2]));
+      }
     };
     {
       uint32_t la[kTrip], lb[kTrip];

@@ -560,16 +560,23 @@ __device__ __forceinline__ void read_row(const int4* tile, int cap, uint32_t off
   for (int a = 0; a < ROW16; ++a) q[a] = *reinterpret_cast<const int4*>(p + (size_t)a * cap * 16);
 }
 
+// A staged q32 row is one 16-byte piece {x0, x1, x2, u0}.  A sweep that uses the point alone lets the compiler narrow its read to
+// ds_read_b96, which the LDS serves in eight groups of 8 lanes on 32 banks where ds_read_b128 takes four groups of 16 on 64
+// (MI355X: twice the array cycles before any conflict).  Naming the fourth word as the input of an empty statement keeps the read
+// whole at no instruction.  The statement stands where the row is consumed, so the wait for the read stays where it was.
+__device__ __forceinline__ void keep_row_word(int w) { asm volatile("" ::"v"(w)); }
+
 constexpr int kPreSlots = 16;
 
 // one slot from LDS; returns 1 if it held a neighbour.  MISS = false: the caller knows the slot is filled.
-template <typename PT, bool MISS>
+template <typename PT, bool MISS, bool WIDE = false>
 __device__ __forceinline__ int slot_add(const int4* tile, int cap, const typename Pt<PT>::Raw& ci, uint32_t l, CovAcc& acc) {
   constexpr int XR = Pt<PT>::kRow16;
   const bool have = !MISS || l != kNoLoc;
   int4 piece[XR];
   read_row<XR>(tile, cap, have ? l : 0u, piece);
   const typename Pt<PT>::Raw cj = Pt<PT>::from_row(piece);
+  if constexpr (WIDE) keep_row_word(piece[0].w);
   double d[3];
   Pt<PT>::delta(have ? cj : ci, ci, d);
   cov_add_d(acc, d[0], d[1], d[2]);
@@ -577,7 +584,8 @@ __device__ __forceinline__ int slot_add(const int4* tile, int cap, const typenam
 }
 
 // the first min(nslots, 16) slots from registers: whole trips of four with the LDS reads batched, then the remainder
-template <typename PT, bool MISS>
+// (WIDE: as gather_fixed)
+template <typename PT, bool MISS, bool WIDE = false>
 __device__ __forceinline__ int gather_slots(const int4* tile, int cap, const typename Pt<PT>::Raw& ci, const uint32_t* pre,
                                             int nslots, CovAcc& acc) {
   constexpr int XR = Pt<PT>::kRow16;
@@ -587,15 +595,18 @@ __device__ __forceinline__ int gather_slots(const int4* tile, int cap, const typ
     if (4 * t + 4 <= nslots) {
       typename Pt<PT>::Raw cj[4];
       bool have[4];
+      int w4[4];
 #pragma unroll
       for (int u_ = 0; u_ < 4; ++u_) {
         have[u_] = !MISS || pre[4 * t + u_] != kNoLoc;
         int4 piece[XR];
         read_row<XR>(tile, cap, have[u_] ? pre[4 * t + u_] : 0u, piece);
         cj[u_] = Pt<PT>::from_row(piece);
+        w4[u_] = piece[0].w;
       }
 #pragma unroll
       for (int u_ = 0; u_ < 4; ++u_) {
+        if constexpr (WIDE) keep_row_word(w4[u_]);
         double d[3];
         Pt<PT>::delta(have[u_] ? cj[u_] : ci, ci, d);
         cov_add_d(acc, d[0], d[1], d[2]);
@@ -604,7 +615,7 @@ __device__ __forceinline__ int gather_slots(const int4* tile, int cap, const typ
     } else {
 #pragma unroll
       for (int u_ = 0; u_ < 4; ++u_)
-        if (4 * t + u_ < nslots) n_have += slot_add<PT, MISS>(tile, cap, ci, pre[4 * t + u_], acc);
+        if (4 * t + u_ < nslots) n_have += slot_add<PT, MISS, WIDE>(tile, cap, ci, pre[4 * t + u_], acc);
     }
   }
   return n_have;
@@ -616,7 +627,7 @@ __device__ __forceinline__ int gather_slots(const int4* tile, int cap, const typ
 // 200-slot row.  `packed` (dcBlockTable.packed): rows fill their slots from 0 upwards, so a wavefront stops at the first trip
 // that is empty for all its lanes -- its own longest row, not the block's.
 constexpr int kTrip = 8;
-template <typename PT>
+template <typename PT, bool WIDE = false>
 __device__ __forceinline__ int gather_tail(const int4* tile, int cap, const typename Pt<PT>::Raw& ci, const uint16_t* lrow,
                                            int nslots, bool packed, CovAcc& acc) {
   constexpr int XR = Pt<PT>::kRow16;
@@ -632,14 +643,17 @@ __device__ __forceinline__ int gather_tail(const int4* tile, int cap, const type
 #pragma unroll
     for (int u_ = 0; u_ < kTrip; ++u_) nxt[u_] = (q0 + kTrip + u_ < nslots) ? (uint32_t)lrow[(q0 + kTrip + u_) * kBlock] : kNoLoc;
     typename Pt<PT>::Raw cj[kTrip];
+    int w4[kTrip];
 #pragma unroll
     for (int u_ = 0; u_ < kTrip; ++u_) {
       int4 piece[XR];
       read_row<XR>(tile, cap, l[u_] != kNoLoc ? l[u_] : 0u, piece);
       cj[u_] = Pt<PT>::from_row(piece);
+      w4[u_] = piece[0].w;
     }
 #pragma unroll
     for (int u_ = 0; u_ < kTrip; ++u_) {
+      if constexpr (WIDE) keep_row_word(w4[u_]);
       const bool have = l[u_] != kNoLoc;
       double d[3];
       Pt<PT>::delta(have ? cj[u_] : ci, ci, d);
@@ -702,15 +716,18 @@ __global__ __launch_bounds__(kBlock) void consistency_fwd_staged_kernel(
 // Fixed slot count: a forward table built from a neighbour table [rows, K] has exactly K slots in every block, so the
 // slot loop, the position loads and the validity handling are resolved at compile time (the run-time variant above
 // spends ~60 VALU instructions per point on them).  Same arithmetic in the same order => bit-identical results.
-template <typename PT, int NS, bool MISS>
+// WIDE (the one-pass step kernels' q32 rows): the 16-byte row is read whole (keep_row_word)
+template <typename PT, int NS, bool MISS, bool WIDE = false>
 __device__ __forceinline__ int gather_fixed(const int4* tile, int cap, const typename Pt<PT>::Raw& ci, const uint32_t* pre,
                                             CovAcc& acc) {
   constexpr int XR = Pt<PT>::kRow16;
+  static_assert(!WIDE || XR == 1, "a row of one 16-byte piece");
   int n_have = 0;
 #pragma unroll
   for (int q0 = 0; q0 < NS; q0 += 4) {
     typename Pt<PT>::Raw cj[4];
     bool have[4];
+    int w4[4];
 #pragma unroll
     for (int u_ = 0; u_ < 4; ++u_) {
       if (q0 + u_ < NS) {
@@ -718,11 +735,13 @@ __device__ __forceinline__ int gather_fixed(const int4* tile, int cap, const typ
         int4 piece[XR];
         read_row<XR>(tile, cap, have[u_] ? pre[q0 + u_] : 0u, piece);
         cj[u_] = Pt<PT>::from_row(piece);
+        w4[u_] = piece[0].w;
       }
     }
 #pragma unroll
     for (int u_ = 0; u_ < 4; ++u_) {
       if (q0 + u_ < NS) {
+        if constexpr (WIDE) keep_row_word(w4[u_]);
         double d[3];
         Pt<PT>::delta(have[u_] ? cj[u_] : ci, ci, d);
         cov_add_d(acc, d[0], d[1], d[2]);
@@ -1185,6 +1204,8 @@ static std::atomic<bool> g_no_reverse{false};
 static std::atomic<bool> g_step_six{false};
 // dc_set_option(10, 1): consistency_step_q32_kernel ignores dcSequenceDesc.step_rows and stages through blk_ids (A-B, tests)
 static std::atomic<bool> g_no_step_rows{false};
+// dc_set_option(11, 1): consistency_step_q32_kernel ignores dcSequenceDesc.step_loc and reads its tile positions from the table's loc (A-B, tests)
+static std::atomic<bool> g_no_step_loc{false};
 
 // consistency_step_ragged_q32_kernel with a tile of CAP rows: more than 64 KB of LDS per block needs the attribute (once per
 // instantiation, process and device).  Capacities up to the table's own limit (4095 rows), so every ball-neighbourhood table that can be
@@ -1343,6 +1364,16 @@ int dc_step_rows_build(const dcBlockTable* table, int64_t n_rows, const void* ba
   if (!table->blk_ids || !basis || !rows_out || ((uintptr_t)rows_out & 15)) return DC_ERR_ARG;
   hipLaunchKernelGGL(step_rows_kernel, dim3((unsigned)n_blocks(n_rows)), dim3(kBlock), 0, stream, table->blk_ptr, table->blk_ids,
                      static_cast<const int32_t*>(basis), row_words, static_cast<int32_t*>(rows_out));
+  DC_CHECK_LAUNCH();
+  return DC_OK;
+}
+
+int dc_step_loc_build(const dcBlockTable* table, int64_t n_rows, void* loc_out, hipStream_t stream) {
+  if (!table || n_rows < 0 || table->layout != DC_TABLE_SLOTS || !table->slot_ptr) return DC_ERR_ARG;
+  if (n_rows == 0) return DC_OK;
+  if (!table->loc || !loc_out || ((uintptr_t)loc_out & 15)) return DC_ERR_ARG;
+  hipLaunchKernelGGL(step_loc_kernel, dim3((unsigned)n_blocks(n_rows)), dim3(kBlock), 0, stream, table->slot_ptr, table->loc,
+                     static_cast<uint32_t*>(loc_out));
   DC_CHECK_LAUNCH();
   return DC_OK;
 }
@@ -1620,6 +1651,7 @@ int dc_set_option(int option, int value) {
   if (option == 8) { g_no_reverse.store(value != 0); return DC_OK; }
   if (option == 9) { g_step_six.store(value != 0); return DC_OK; }
   if (option == 10) { g_no_step_rows.store(value != 0); return DC_OK; }
+  if (option == 11) { g_no_step_loc.store(value != 0); return DC_OK; }
   return DC_ERR_ARG;
 }
 
@@ -1755,11 +1787,13 @@ static int launch_step_q32(const SeqRoute& r, const StepLaunch& a) {
   // the per-block row copy belongs to the same table as the headers (the route is here because of them): staged from when the caller
   // passes one, unless dc_set_option(10, 1) asks for the trip through blk_ids
   const int32_t* step_rows = g_no_step_rows.load() ? nullptr : static_cast<const int32_t*>(a.d->step_rows);
+  // so do the packed tile positions (dc_set_option(11, 1): the table's loc)
+  const uint32_t* step_loc = g_no_step_loc.load() ? nullptr : static_cast<const uint32_t*>(a.d->step_loc);
   const dim3 block(kBlock);
   static_assert(kStepQ32Cap == 512, "the profiler names the instantiation by its literal arguments");
   static_assert(step_q32_blocks<1, 512>() == 7 && step_q32_blocks<2, 512>() == 7 && step_q32_blocks<3, 512>() == 6 && step_q32_blocks<2, 768>() == 6,
                 "which instantiations dc_set_option(9, 1) has a six-block build of");
-#define STEPQ_TAIL a.pb, a.tab, hdr, step_rows, a.d->centre_idx, r.n_rows, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
+#define STEPQ_TAIL a.pb, a.tab, hdr, step_rows, step_loc, a.d->centre_idx, r.n_rows, a.lp, a.qp, a.p_fwd, a.p_bwd, a.ch
 #define STEPQ(P, NS, CAP) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, CAP>), a.grid, block, 0, a.stream, STEPQ_TAIL)
 #define STEPQ_SIX(P, NS, X) DC_TIMED_LAUNCH((consistency_step_q32_kernel<NS, P, 512, 6>), a.grid, block, 0, a.stream, STEPQ_TAIL)
 #define STEPQ_P(NS, CAP) DC_SWITCH_P(r.P, STEPQ(3, NS, CAP), STEPQ, NS, CAP)

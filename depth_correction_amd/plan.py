@@ -47,7 +47,7 @@ class SequencePlan:
                  normalization=True, sqrt=False, spatial_sort=True, point_format='auto', degree_sort=False,
                  active_only=False, block_tables=True, bwd_layout='runs', stages=None, basis=True, lazy_backward=True,
                  scan_group=True, mask_first=False, nan_policy=None, pose_kernel=True, degree_group=False, heavy_first=False,
-                 wave_pack=None, step_rows=True):
+                 wave_pack=None, step_rows=True, step_loc=True):
         """
         :param clouds: per-scan dicts / objects with vps [n,3], dirs [n,3], depth [n,1], inc_angles [n,1], mask [n]
                        (local feature clouds, sensor frame), GPU tensors of one dtype.
@@ -63,6 +63,10 @@ class SequencePlan:
                           kernel of float32 clouds stages them (dcSequenceDesc.step_rows: 4 (6 + P) bytes per listed row, 1.75 rows
                           per point at C2).  Built when the same poses and exponents are evaluated a second time, dropped with the
                           basis rows; results are the same bit for bit with and without it.
+        :param step_loc: keep, beside the table the one-pass step kernel stages from, its tile positions packed two to a word in the
+                         order a lane of that kernel holds them (dcSequenceDesc.step_loc: as many bytes as the table's ``loc``).  Built
+                         with the first row copy, kept while the table lives (it depends on neither weights, poses nor exponents);
+                         results are the same bit for bit with and without it.
         :param pose_kernel: evaluations with pose gradients in one launch (consistency_step_pose_kernel) where the plan allows it.
         :param nan_policy: None, 'skip_nans' or 'only_finite' (loss.py:125-137): pointwise losses that are NaN / not finite are left
                            out of the sum, the count and the gradients; the count of an evaluation is then its own (out[1]).
@@ -341,6 +345,9 @@ class SequencePlan:
         # the key names; the copy lives and dies with the rows it copies (_set_basis)
         self._basis = None
         self.use_step_rows = bool(step_rows)
+        # [table, packed tile positions of that table]: dropped when the plan stages from another table object (_set_basis)
+        self._step_loc = None
+        self.use_step_loc = bool(step_loc)
         self._poses_key = self._poses12 = self._poses_ref = None
 
     # ------------------------------------------------------------------------------------------------
@@ -458,7 +465,7 @@ class SequencePlan:
               and self.fwd_table is not None and self._block_tables and self._bwd_layout == 'runs'
               and d.model_kind != 0)
         if not ok:
-            d.basis = d.step_rows = None
+            d.basis = d.step_rows = d.step_loc = None
             return
         nt = w.numel()
         b = self._basis
@@ -485,6 +492,17 @@ class SequencePlan:
             b[4] = torch.empty((max(self._step_rows_total, 1) * (6 + nt),), dtype=torch.int32, device=self.device)
             check(lib().dc_step_rows_build(ft.ref(), self.nbr.shape[0], ptr(b[1]), 6 + nt, ptr(b[4]), stream_ptr()), 'dc_step_rows_build')
         d.step_rows = None if (b[4] is None or not self.use_step_rows) else b[4].data_ptr()
+        # the same kernel's tile positions, packed (dcSequenceDesc.step_loc): a function of the table alone, so they are built once, with
+        # the first row copy (a caller who never evaluates a key twice pays for neither), and outlive the basis rows
+        sl = self._step_loc
+        if sl is not None and sl[0] is not ft:
+            self._step_loc = sl = None
+        if (sl is None and b[4] is not None and self.use_step_loc and self.k in (4, 8, 10, 16) and self.nbr.shape[1] == self.k
+                and ft.loc is not None and ft.slot_ptr is not None):
+            words = torch.empty(((ft.loc.numel() + 1) // 2,), dtype=torch.int32, device=self.device)
+            check(lib().dc_step_loc_build(ft.ref(), self.nbr.shape[0], ptr(words), stream_ptr()), 'dc_step_loc_build')
+            self._step_loc = sl = [ft, words]
+        d.step_loc = None if (sl is None or not self.use_step_loc) else sl[1].data_ptr()
 
     @on_device
     def eval_native(self, w, exponent, poses12, out, want_grad=True, want_exponent=False, want_pose=False):

@@ -254,6 +254,15 @@ int dc_step_header_build(const dcBlockTable* table, int64_t n_rows, const uint8_
  * row_words blk_ptr[b] + 4 (c / 4) nd + min(4, row_words - 4 (c / 4)) t + c % 4.  Every entry is written (those of skipped blocks too).
  * Valid for exactly this table and these basis rows: build it again when either is rebuilt. */
 int dc_step_rows_build(const dcBlockTable* table, int64_t n_rows, const void* basis, int row_words, void* rows_out, dcStream_t stream);
+/* The packed tile positions of the one-pass step kernel (dcSequenceDesc.step_loc) of a DC_TABLE_SLOTS table over n_rows rows: the 16-bit
+ * positions table->loc of every block, two to a 32-bit word as a lane of that kernel holds them -- word j of lane t of block b is
+ * loc[(slot_ptr[b] + 2 j) 256 + t] | loc[(slot_ptr[b] + 2 j + 1) 256 + t] << 16 (0xFFFF, the empty slot, as it stands) -- for
+ * j < NW = (slot_ptr[b + 1] - slot_ptr[b]) / 2.  loc_out: uint32 [slot_ptr[blocks] * 128], 16-byte aligned; block b's 256 NW words start
+ * at word 128 slot_ptr[b] -- the byte range its rows of `loc` occupy, so nothing but slot_ptr[b] addresses them -- and lie
+ * piece-major inside it: a piece is four consecutive words of a lane, the last piece of NW = 5 the one that remains, all 256 lanes of
+ * piece 0 first, then all of piece 1: word j of lane t is at 128 slot_ptr[b] + 1024 (j / 4) + min(4, NW - 4 (j / 4)) t + j % 4.  (The
+ * step kernel runs even slot counts only; of an odd count the last slot is not stored.)  Valid for exactly this table. */
+int dc_step_loc_build(const dcBlockTable* table, int64_t n_rows, void* loc_out, dcStream_t stream);
 size_t dc_block_table_workspace_bytes(int64_t n_refs);
 /* A-B switch (measurements, tests; process-wide, not thread-safe like dc_set_option): 0 = [rows, K] tables through the radix-sort
  * build as well; returns the previous setting.  Default 1: K = 4 / 8 / 10 / 16 tables are built block by block in LDS. */
@@ -613,6 +622,12 @@ typedef struct dcSequenceDesc {
                                       POSES AND EXPONENTS OF THE CALL and for this n_terms: build it again whenever the basis rows or
                                       that table are rebuilt.  Read only together with step_hdr.  NULL: the kernel stages through
                                       blk_ids -- the same words either way, so the same sums bit for bit */
+  const void* step_loc;            /* uint32 [slot_ptr[blocks] * 128], 16-byte aligned (dc_step_loc_build), or NULL.  The tile positions of
+                                      every block of that same table, two to a word as a lane of consistency_step_q32_kernel holds them: a
+                                      working wavefront fetches its lanes' words as they are instead of 16-bit values it joins in pairs,
+                                      and a wavefront without a centre inside the mask fetches none.  It depends on the table alone (not on
+                                      weights, poses or exponents): build it again when that table is rebuilt.  Read only together with
+                                      step_hdr.  NULL: the kernel reads the table's `loc` -- the same words, the same sums bit for bit */
 } dcSequenceDesc;
 
 /* Doubles of dcSequenceDesc.partials for a sequence of n points evaluated with up to n_terms weights and n_scans poses:
@@ -736,6 +751,8 @@ int dc_cloud_from_points(const void* points, int stride, int in_dtype, const voi
  *           blocks per CU instead of seven: the same kernel body and the same sums bit for bit, other launch bounds.
  * option 10: value 1 makes the one-pass step kernel of float32 clouds ignore dcSequenceDesc.step_rows and stage its rows through
  *           blk_ids, as it does when the field is NULL: the same staged words, the same sums bit for bit.
+ * option 11: value 1 makes that kernel ignore dcSequenceDesc.step_loc and read its tile positions from the table's `loc`, as it does
+ *           when the field is NULL: the same positions, the same sums bit for bit.
  * option 5: number of polls a chained launch's blocks make while they wait for the weights its leading blocks publish
  *           (default 2^22, negative restores it).  A wait that runs out yields NaN sums for that evaluation and raises bit 1 of
  *           dcSequenceDesc.status (bit 0: DC_Q32 overflow), so the two causes of a NaN loss can be told apart; tests force 0. */
